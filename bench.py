@@ -2,15 +2,28 @@
 """bench.py -- headline benchmark: STFT frames/s (1024-pt, 50 % overlap, Hamming)
 at batch = 65,536 frames per GPU (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (jdsp_stft_i16_dev: int16 framing + window
 + forward transform, full 1024-bin complex64 spectrum) over one batch of
 synthetic PCM that is already resident in HBM.  Successive steps read DIFFERENT
 PCM buffers (--pcm-buffers, default 6 x 64 MiB = 384 MiB > the 256 MiB Infinity
 Cache), so the input of every timed launch comes from HBM, not from a cache that
-the previous launch warmed; the same-buffer figure is reported beside it
-(`roofline.warm_input`).
+the previous launch warmed.
+
+A plain run times only the reported leg: set-up, warmup, the K timed steps, the
+outputs (--dump-outputs) and the JSON line.  --full adds the figures that take
+runs of their own: the same-buffer leg (`roofline.warm_input`), the leg without
+the read pass (`roofline.cold_input_without_read_pass`), the FP64 leg
+(`roofline.fp64`) and the CPU oracle's rate (`cpu_baseline`).
+
+--dump-outputs DIR writes what the last timed step computed, as DIR/<name>.npy
+(float32 / float64): for the STFT, DIR/spectrum.npy = the spectra of a fixed,
+seeded sample of frames (rows of the [B, 1024] complex64 output as [n, 1024, 2]
+real / imaginary float32, at most 32 MiB); for --workload mfcc10k, DIR/mfcc.npy
+= rank 0's [n, 13] float64 feature vectors, sampled the same way.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for
+output.
 
 N > 1: one rank per GPU over RCCL.  Either an external launcher started the ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`: RANK
@@ -40,6 +53,7 @@ BYTES_PER_FRAME_F64 = 512 * 2 + 1024 * 16     # the same analysis in the referen
 HBM_PEAK_GBS = 8000.0                         # MI355X_MICROARCH.md: 8.0 TB/s spec
 TRAFFIC_FILE = os.path.join("profiles", "stft_pmc_traffic.json")
 EXIT_STUCK_COLLECTIVE = 3
+DUMP_BYTES = 32 << 20                         # per dumped array; two workloads' worth stays under 64 MiB
 
 
 def parse_args(argv=None):
@@ -69,7 +83,16 @@ def parse_args(argv=None):
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU work at all: ranks rendezvous, barrier, reduce the timings and gather a dummy buffer, "
                          "so the N > 1 launch path can be tested on a CPU-only host (the line says so; value is null)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures that take runs of their own: the warm-input and no-read-pass legs, "
+                         "the FP64 leg and the CPU baseline (a plain run times the reported leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (rank 0; a fixed, seeded sample of "
+                         "rows, at most %d MiB per array) as DIR/<name>.npy" % (DUMP_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------ N > 1: start the ranks ourselves
@@ -167,6 +190,22 @@ def cpu_baseline(seconds=10.0):
             "all_cores": {"value": allc, "unit": "frames/s", "threads": cores, "nproc": visible,
                           "cgroup_cpu_quota": quota,
                           "note": "same oracle, one thread per usable host core (nproc cut to the cgroup CPU quota if any)"}}
+
+
+def dump_rows(out_dir, name, rows):
+    """DIR/<name>.npy: the device tensor `rows` (float32 or float64, rows along dim 0) on the host.  When it is larger
+    than DUMP_BYTES, a fixed sample of rows: sorted, drawn by default_rng(0), so the same for the same shape."""
+    import numpy as np
+    import torch
+    n = rows.shape[0]
+    keep = max(1, DUMP_BYTES // (rows[0].numel() * rows.element_size()))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+    arr = rows.cpu().numpy()
+    assert arr.dtype in (np.float32, np.float64), arr.dtype
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def read_traffic():
@@ -329,16 +368,17 @@ def run_rank(args):
         elapsed = time.perf_counter() - t0
         return elapsed, e0.elapsed_time(e1) / max(args.steps, 1)   # wall clock; average launch duration (incl. gaps)
 
-    # Three legs, each its own captured graph of the K steps:
+    # Three legs, each its own captured graph of the K steps (the last two with --full only):
     #   reported : library defaults ("stft.read_pass" auto: a read-only launch streams each slab's PCM into the
     #              Infinity Cache, then the transform runs), input ROTATED over P buffers -- PCM comes from HBM
     #   warm     : every step re-reads ONE buffer, read pass off -- round 1's figure (input served by the cache)
     #   cold, no read pass : what the transform alone does with its input in HBM
+    legs = args.full and P > 1
     eng.set_option("stft.read_pass", -1)
     graph = capture(pcms)
     eng.set_option("stft.read_pass", 0)
-    graph_warm = capture(pcms[:1]) if P > 1 else None
-    graph_cold0 = capture(pcms) if P > 1 else None
+    graph_warm = capture(pcms[:1]) if legs else None
+    graph_cold0 = capture(pcms) if legs else None
     eng.set_option("stft.read_pass", -1)
     # Clock spin-up, independent of W: a GPU that has idled needs tens of milliseconds of continuous load to reach
     # its sustained clocks; a caller that passes a small W would otherwise time the ramp.  Untimed, like the warmup,
@@ -352,17 +392,19 @@ def run_rank(args):
                 i += 1
             torch.cuda.synchronize()
     warm = cold0 = None
-    if P > 1:                                         # secondary figures first
+    if legs:                                          # secondary figures first
         eng.set_option("stft.read_pass", 0)           # (the eager warmup launches follow the leg's setting too)
         warm = timed(pcms[:1], graph_warm)
         cold0 = timed(pcms, graph_cold0)
         eng.set_option("stft.read_pass", -1)
     elapsed, kern_ms = timed(pcms, graph)             # the reported figure: library defaults, input rotated over P buffers
+    if args.dump_outputs and rank == 0:               # `spec` holds the last timed step's spectra
+        dump_rows(args.dump_outputs, "spectrum", torch.view_as_real(spec))
 
     # The reference computes in FP64 (SS:205-206 fftw_complex): the same K steps through jdsp_stft_i16_f64_dev
     # (complex128 out, 17,408 algorithmic bytes per frame), AFTER the reported leg so that `value` is untouched.
     f64 = None
-    if not args.no_fp64_leg:
+    if args.full and not args.no_fp64_leg:
         spec = None                                   # 512 MiB back before the 1 GiB of complex128
         spec64 = torch.empty((B, N_FFT), dtype=torch.complex128, device=dev)
         def step64(i, bufs):
@@ -487,7 +529,7 @@ def run_rank(args):
                               "frames_per_s_including_gather": float(B) * world / (elapsed / args.steps + gather_ms * 1e-3)}
         elif stuck:
             line["gather"] = {"stuck": True}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
 
@@ -578,6 +620,8 @@ def run_rank_mfcc(args):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         t = tt
     elapsed, kern_ms = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0 and nf:        # rank 0's feature vectors of the last timed step
+        dump_rows(args.dump_outputs, "mfcc", feats)
     if rank == 0:
         alg = MFCC_BYTES_PER_FRAME * nf
         ach = alg / (kern_ms * 1e-3) / 1e9
@@ -595,7 +639,7 @@ def run_rank_mfcc(args):
                              "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg,
                              "note": "424 B per frame against ~28 kflop: this chain is VALU/LDS-issue-bound, the HBM fraction "
                                      "is reported for completeness (DESIGN.md 3.6); rank 0's launch"}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib
             orc = oracle_lib.load_oracle()

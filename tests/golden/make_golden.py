@@ -12,6 +12,8 @@ produced for them -- never reference source text.
                     IFFTProcess on seeded frames, and main()'s WAV round trip.
   fftalg_1024.npz   same translation unit with -DBLOCK_LEN=1024 (the only edit:
                     the #define at :16), Bitrev table + FFTProcess fwd/inv.
+  fftalg_fresh_seed.npz  FFTProcess fwd/inv of both builds on the default_rng(99) frames
+                    test_live_reference_agrees_on_fresh_seed draws.
   stft_1024.npz     the headline path pinned to the reference's OWN transform: seeded int16 frames
   stft_512.npz      (hop n/2) x the applications' Hamming window (SpectralSubtraction_final.cpp:226,
                     PI 3.141592) -> FFTProcess of the compiled FFTAlgorithm_ver2.cpp (BLOCK_LEN = n),
@@ -110,6 +112,23 @@ def fftalg(block_len, n_frames, with_slow):
         out["main_out"] = run_ref_main(oracle_lib.ref_path(block_len), pcm)
     np.savez_compressed(os.path.join(HERE, "fftalg_%d.npz" % block_len), **out)
     print("fftalg_%d.npz" % block_len, {k: v.shape for k, v in out.items()})
+
+
+def fftalg_fresh_seed():
+    """test_live_reference_agrees_on_fresh_seed's own inputs (default_rng(99): three complex frames per size) and
+    FFTProcess's answers for them both ways, so that the test runs where oracle/_ref cannot be built."""
+    out = {}
+    for n in (512, 1024):
+        ref = oracle_lib.load_ref(n)
+        assert ref is not None and ref.block_len == n
+        rng = np.random.default_rng(99)
+        z = np.stack([rng.normal(size=n) * 1e3 + 1j * rng.normal(size=n) for _ in range(3)])
+        with quiet_stdout():
+            out["fwd_%d" % n] = np.stack([ref.fft_process(x, True) for x in z])
+            out["inv_%d" % n] = np.stack([ref.fft_process(x, False) for x in z])
+        out["z_%d" % n] = z
+    np.savez_compressed(os.path.join(HERE, "fftalg_fresh_seed.npz"), **out)
+    print("fftalg_fresh_seed.npz", {k: v.shape for k, v in out.items()})
 
 
 def stft(n, n_frames):
@@ -225,6 +244,7 @@ def vad():
 if __name__ == "__main__":
     fftalg(512, 4, True)
     fftalg(1024, 2, False)
+    fftalg_fresh_seed()
     stft(1024, 6)
     stft(512, 6)
     rir_taps()

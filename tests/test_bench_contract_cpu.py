@@ -54,6 +54,20 @@ def test_gpus_n_builds_a_torch_distributed_run_child_command():
     assert "import torch" not in src[:src.index("def synth_pcm")]
 
 
+def test_full_and_dump_outputs_options():
+    """A plain run is lean: --full (off by default) adds the secondary legs; --dump-outputs DIR names where the last
+    step's outputs go; --steps below 1 is refused rather than divided by."""
+    import pytest
+    bench = _load_bench()
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+    assert 2 * bench.DUMP_BYTES <= 64 << 20
+
+
 def test_self_launch_two_ranks_gloo_end_to_end():
     """The N > 1 path for real, on the CPU: `python bench.py --gpus 2 --launcher-selftest` spawns two ranks
     (gloo), which rendezvous, barrier, MAX-reduce their timings, all_gather a 256-frame dummy spectrum buffer
