@@ -40,7 +40,8 @@ extern "C" {
 
 /* 2: jdsp_vad_blocks_ex added; jdsp_denoise_apply and jdsp_denoise_shard_* accept 512-point streams;
  *    jdsp_denoise_vad_trace's energies / counts follow the option's value at the time of the traced call;
- *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only.  (1: rounds 1-2.) */
+ *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added
+ *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
 enum {
@@ -150,6 +151,54 @@ int jdsp_stft_i16(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples,
 int jdsp_stft_i16_f64_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames, int n_fft, int hop, double *spec_dev);
 int jdsp_stft_i16_f64(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, int n_fft, int hop, double *spec_host,
                       long *n_frames_out);
+
+/* ---- STFT synthesis: inverse transform + overlap-add to PCM ---------------------- */
+/* The step SpectralSubtraction_final.cpp:244-257 (= WienerFilter_final.cpp:215-228) performs -- unnormalised inverse
+ * DFT, real part, 1/N, overlap-add with a shift of one hop, truncating (short) cast -- as a public, streaming, batched
+ * entry for spectra the caller made (e.g. jdsp_stft_i16_dev's output with a mask applied in place).  A jdsp_istft
+ * handle holds ONE output stream; frames are counted from the last reset; n = n_fft, R = n / hop.
+ *   1. Spectrum of frame f: X_f = row f, row_pitch complex64 apart.
+ *      JDSP_SPEC_FULL  n bins per row.  The frame is the REAL PART of the full complex inverse (as SS:244-251 takes
+ *                      [i][0]), i.e. the inverse of H_f[k] = (X_f[k] + conj X_f[(n-k) mod n]) / 2: a non-Hermitian row
+ *                      is handled exactly, not assumed away.
+ *      JDSP_SPEC_HALF  bins 0..n/2 per row (jdsp_stft_half_i16_dev's layout), row_pitch >= n/2+1, taken as Hermitian:
+ *                      H[n-k] = conj X[k]; the imaginary parts of bins 0 and n/2 are ignored.
+ *   2. Frame signal: y_f[i] = w_s[i] * (1/n) * sum_k H_f[k] e^{+2 pi j i k / n}, i < n.  w_s = 1 for JDSP_WIN_NONE,
+ *      else the Hamming / Hann of "stft.window": 0.54-0.46cos(2*3.141592*i/(n-1)) / 0.5-0.5cos(same).
+ *   3. Overlap-add: s[t] = sum_f y_f[t - hop f], accumulated in FP32 in ascending frame order starting from 0 -- so the
+ *      output does not depend on how the stream is cut into calls, or on the launch geometry, bit for bit.
+ *   4. Emission: after frame f the samples t in [hop f, hop f + hop) are final and written as g[t mod hop] * s[t], with
+ *      g = 1 when analysis_window == JDSP_WIN_NONE, else g[i] = 1 / sum_{r<R} w_a[i + r hop] w_s[i + r hop] (WOLA
+ *      normalisation: jdsp_stft_i16_dev followed by this entry gives the input back).  create returns JDSP_EINVAL when
+ *      an entry of that sum is below 1e-6 of its largest (e.g. Hann analysis at R = 1).
+ *   5. Output: int16 = the oracle's cast_i16 of that float (truncate toward zero, keep the low 16 bits: values past
+ *      +-32,768 wrap; beyond +-2^31 is out of scope), and optionally the float32 values themselves.  A call of F frames
+ *      writes F*hop contiguous samples.  Both output pointers may be NULL: the stream then advances without writing
+ *      (sharding primes a halo this way, see jeicyboodsp_amd/sharding.py).
+ *   6. flush writes the n - hop samples still in the tail (same g, same cast), then resets the handle.
+ * n = 1024, hop = 512, FULL, NONE, NONE is SS:244-257 exactly.
+ * Supported: n_fft 1024 or 512 with hop = n, n/2 or n/4.  Alignment: spec 8 bytes (a jdsp_c32), out_i16 4 bytes,
+ * out_f32 8 bytes; anything else, or a row_pitch below the layout's bin count, is JDSP_EINVAL.  The _dev entries only
+ * enqueue on the handle's stream (no allocation, no host synchronisation; graph-capturable); the state is n_fft floats
+ * twice (ping-pong) plus the window and gain tables, allocated at create.  jdsp_istft_process / _flush: host
+ * pointers, synchronous (device buffers grown on demand in the handle). */
+typedef struct jdsp_istft jdsp_istft;
+enum { JDSP_SPEC_FULL = 0, JDSP_SPEC_HALF = 1 };
+enum { JDSP_WIN_NONE = -1, JDSP_WIN_HAMMING = 0, JDSP_WIN_HANN = 1 };   /* numbering of "stft.window" */
+typedef struct { int n_fft, hop, layout, synthesis_window, analysis_window; } jdsp_istft_cfg;
+int  jdsp_istft_create(jdsp_ctx *ctx, const jdsp_istft_cfg *cfg, jdsp_istft **out);
+int  jdsp_istft_destroy(jdsp_istft *h);
+int  jdsp_istft_reset(jdsp_istft *h);
+/* "frames_per_wave": consecutive frames one wavefront walks (0 = auto: about one round of resident waves, at least
+ * 4 (R - 1)); any value >= max(R - 1, 1) gives the same output bit for bit -- a tuning and testing knob. */
+int  jdsp_istft_set_option(jdsp_istft *h, const char *name, long value);
+long jdsp_istft_samples_out(const jdsp_istft *h, long n_frames);
+int  jdsp_istft_process_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitch, long n_frames,
+                            int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_istft_flush_dev(jdsp_istft *h, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_istft_process(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, long n_frames,
+                        int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
+int  jdsp_istft_flush(jdsp_istft *h, int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
 
 /* ---- spectral subtraction / Wiener filter ------------------------------------- */
 /* One jdsp_denoise object holds everything the reference keeps in static locals

@@ -19,6 +19,16 @@ class MfccCfg(C.Structure):
                 ("n_cep", C.c_int), ("lifter", C.c_int), ("half_rate", C.c_double), ("preemph", C.c_double)]
 
 
+class IstftCfg(C.Structure):
+    """jdsp_istft_cfg (include/jdsp.h)"""
+    _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("layout", C.c_int), ("synthesis_window", C.c_int),
+                ("analysis_window", C.c_int)]
+
+
+SPEC_FULL, SPEC_HALF = 0, 1
+WIN_NONE, WIN_HAMMING, WIN_HANN = -1, 0, 1
+
+
 class JdspError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("jdsp error %d: %s" % (code, text))
@@ -140,6 +150,15 @@ def _load():
         "jdsp_stft_i16": (i, [vp, vp, l, i, i, vp, C.POINTER(l)]),
         "jdsp_stft_i16_f64_dev": (i, [vp, vp, l, i, i, vp]),
         "jdsp_stft_i16_f64": (i, [vp, vp, l, i, i, vp, C.POINTER(l)]),
+        "jdsp_istft_create": (i, [vp, vp, C.POINTER(vp)]),
+        "jdsp_istft_destroy": (i, [vp]),
+        "jdsp_istft_reset": (i, [vp]),
+        "jdsp_istft_set_option": (i, [vp, C.c_char_p, l]),
+        "jdsp_istft_samples_out": (l, [vp, l]),
+        "jdsp_istft_process_dev": (i, [vp, vp, l, l, vp, vp]),
+        "jdsp_istft_flush_dev": (i, [vp, vp, vp]),
+        "jdsp_istft_process": (i, [vp, vp, l, l, vp, vp]),
+        "jdsp_istft_flush": (i, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

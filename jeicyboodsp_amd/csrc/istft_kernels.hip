@@ -1,0 +1,307 @@
+// istft_kernels.hip -- STFT synthesis (gfx950): batched inverse transform of caller-given spectra, synthesis window,
+// overlap-add and the (short) cast, as one streaming pass (include/jdsp.h, jdsp_istft_*).
+//
+// One wave per run of consecutive frames (persistent: the launch picks the run so that the batch is about one round of
+// resident waves, in XCD-aware order, as denoise_run_kernel).  Per frame:
+//   n = 1024  the real frame comes from ONE 512-point complex inverse through the pre-split of frame_io.h: the rows are
+//             made Hermitian first, H[k] = (X[k] + conj X[-k]) / 2 (FULL: X[-k] read back from a natural-order image
+//             of the row in the wave's LDS, the mirror_fetch_lds pattern; HALF: H[n-k] = conj X[k], the row's lower half
+//             through the same image), so a non-Hermitian row gives exactly the real part of its full inverse.
+//   n = 512   one 512-point complex inverse of H per frame, real part kept.  Never two frames in one transform: a
+//             frame's result must not depend on its neighbour, or on where a call or shard cut falls.
+// Lane l holds frame samples 2 l + 128 d, +1 (n = 1024, one float2 per register) or l + 64 d (n = 512, one float per
+// register), d < 8, so a hop of n / R is HR = 8 / R registers in both cases and the overlap-add is a register shift:
+// after frame f, registers 0..HR-1 are final (emitted) and the rest move down.  Every output sample is the FP32 sum of
+// its frames in ascending order, starting from 0 -- the same operations whatever the call cuts or the launch geometry,
+// so results are bit-identical across both.  A wave whose run starts at frame j0 > 0 recomputes the R - 1 frames
+// before it (the halo); only the wave with j0 = 0 reads the tail carried in the handle, and the wave that owns the
+// call's last frame writes the new tail (ping-pong buffers: another wave may still be reading the old one).
+#include "jdsp_internal.h"
+#include "frame_io.h"
+
+namespace jdsp {
+
+#ifndef JDSP_ISTFT_RESIDENT
+// Waves per SIMD the launch plans for (and __launch_bounds__ asks the compiler for).  Registers and LDS would allow three
+// at n = 1024 FULL, but with two the same batch is about 16 % faster (125 against 148 us per 65,536 frames, alternated on
+// one box); one per SIMD is faster still on 1024/256 and slower on the half spectrum and on 512-point frames
+// (profiles/r04_istft_launch_ab.txt)
+#define JDSP_ISTFT_RESIDENT 2
+#endif
+#ifndef JDSP_ISTFT_MIN_RUN_PER_HALO
+#define JDSP_ISTFT_MIN_RUN_PER_HALO 4   // shortest run, in halo frames (launch_istft)
+#endif
+
+template <int N> struct IstftSample;
+template <> struct IstftSample<1024> { typedef float2 T; };
+template <> struct IstftSample<512> { typedef float T; };
+
+__device__ __forceinline__ float2 ola_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float ola_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float2 ola_mul(float2 a, float2 b) { return make_float2(a.x * b.x, a.y * b.y); }
+__device__ __forceinline__ float ola_mul(float a, float b) { return a * b; }
+// streaming (nontemporal) accesses: the spectra are read once, the outputs written once
+#ifndef JDSP_ISTFT_NT_LOAD
+#define JDSP_ISTFT_NT_LOAD 1         // 0: plain loads of the spectra (tools/build_variant.sh A/B)
+#endif
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float2 nt_load(const float2 *p)
+{
+#if JDSP_ISTFT_NT_LOAD
+    const f32x2 v = __builtin_nontemporal_load(reinterpret_cast<const f32x2 *>(p));
+    return make_float2(v.x, v.y);
+#else
+    return *p;
+#endif
+}
+__device__ __forceinline__ void nt_store(float2 v, float2 *p)
+{
+    f32x2 w = {v.x, v.y};
+    __builtin_nontemporal_store(w, reinterpret_cast<f32x2 *>(p));
+}
+__device__ __forceinline__ void nt_store(float v, float *p) { __builtin_nontemporal_store(v, p); }
+template <class T> __device__ __forceinline__ T ola_zero();
+template <> __device__ __forceinline__ float2 ola_zero<float2>() { return make_float2(0.f, 0.f); }
+template <> __device__ __forceinline__ float ola_zero<float>() { return 0.f; }
+
+// Spectrum values one lane loads per frame: X[lane + 64 q] for q < kLoads (FULL: the whole row; HALF: bins below n/2,
+// the Nyquist bin X[n/2] comes separately)
+template <int N, int HALF> struct IstftLoad { static constexpr int kLoads = HALF ? N / 128 : N / 64; };
+
+template <int N, int HALF>
+__device__ __forceinline__ void istft_load(const float2 *__restrict__ row, int lane, float2 (&x)[IstftLoad<N, HALF>::kLoads],
+                                           float2 &nyq)
+{
+#pragma unroll
+    for (int q = 0; q < IstftLoad<N, HALF>::kLoads; q++) x[q] = nt_load(row + lane + 64 * q);
+    if (HALF) nyq = nt_load(row + N / 2);
+}
+
+// The row into this wave's image (natural order): slot k = X[k], plus slot n = X[0] (FULL) or slot n/2 = X[n/2]
+// (HALF, whose loads stop below n/2).  The image's previous reads must be done (fence before).
+template <int N, int HALF>
+__device__ __forceinline__ void istft_stage(const float2 (&x)[IstftLoad<N, HALF>::kLoads], float2 nyq, float2 *img,
+                                            int lane)
+{
+#pragma unroll
+    for (int q = 0; q < IstftLoad<N, HALF>::kLoads; q++) xchg_st(img, lane + 64 * q, x[q]);
+    if (lane == 0) img[HALF ? N / 2 : N] = HALF ? nyq : x[0];
+}
+
+// H[k], k = lane + 64 D, from the image:
+//   FULL  H[k] = (X[k] + conj X[(n - k) mod n]) / 2 -- a power-of-two scale (exact) of a sum that commutes, so a row
+//         that is already Hermitian comes out bit for bit as it went in
+//   HALF  H[k] = X[k] for k < n/2, conj X[n - k] above; Im of DC and Nyquist ignored
+template <int N, int HALF, int D>
+__device__ __forceinline__ float2 istft_bin(const float2 *img, int lane)
+{
+    constexpr int kHalfRegs = N / 128;                       // registers below n/2
+    if constexpr (HALF) {
+        const float2 x = D < kHalfRegs ? xchg_ld(img, lane + 64 * D) : xchg_ld(img, N - lane - 64 * D);
+        const bool real = lane == 0 && (D == 0 || D == kHalfRegs);
+        return make_float2(x.x, real ? 0.f : (D < kHalfRegs ? x.y : -x.y));
+    } else {
+        const float2 x = xchg_ld(img, lane + 64 * D), m = xchg_ld(img, N - lane - 64 * D);
+        return make_float2(0.5f * (x.x + m.x), 0.5f * (x.y - m.y));
+    }
+}
+
+// One frame from the staged image: y[d] = w_s / n * (real inverse of H) at the lane's samples of register d.
+// `scratch`: the transform's kWaveLdsComplex elements (not the image).
+template <int N, int HALF>
+__device__ __forceinline__ void istft_frame(const float2 *img, float2 *scratch, int lane, const WaveTwiddles &tw,
+                                            const SplitTwiddles &sw, const typename IstftSample<N>::T (&ws)[8],
+                                            typename IstftSample<N>::T (&y)[8])
+{
+    float2 v[8];
+    if constexpr (N == 1024) {
+        // Z'[m] from H[m], H[m + 512] (frame_io.h), m = lane + 64 d
+#define JDSP_ISTFT_Z(D) v[D] = presplit_inv_reg(istft_bin<N, HALF, D>(img, lane), istft_bin<N, HALF, D + 8>(img, lane), sw.w[D])
+        JDSP_ISTFT_Z(0); JDSP_ISTFT_Z(1); JDSP_ISTFT_Z(2); JDSP_ISTFT_Z(3);
+        JDSP_ISTFT_Z(4); JDSP_ISTFT_Z(5); JDSP_ISTFT_Z(6); JDSP_ISTFT_Z(7);
+#undef JDSP_ISTFT_Z
+    } else {
+#define JDSP_ISTFT_H(D) v[D] = istft_bin<N, HALF, D>(img, lane)
+        JDSP_ISTFT_H(0); JDSP_ISTFT_H(1); JDSP_ISTFT_H(2); JDSP_ISTFT_H(3);
+        JDSP_ISTFT_H(4); JDSP_ISTFT_H(5); JDSP_ISTFT_H(6); JDSP_ISTFT_H(7);
+#undef JDSP_ISTFT_H
+    }
+    wave_fft512<true>(v, scratch, lane, tw);
+    wave_lds_fence();                                            // the transform's last exchange reads are done
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        if constexpr (N == 1024) y[d] = ola_mul(v[d], ws[d]);
+        else y[d] = v[d].x * ws[d];
+    }
+}
+
+struct IstftArgs {
+    const float2 *spec;
+    long pitch, n_frames;
+    const float *ws;          // [n]   w_s[i] / n, natural order
+    const float *g;           // [hop] WOLA gain (1 without an analysis window)
+    const float *tail_in;     // [n - hop] partial sums of the samples after the last emitted one
+    float *tail_out;
+    short *out;               // may be NULL
+    float *out_f32;           // may be NULL
+    int run;
+};
+
+template <int N, int HALF, int R>
+__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(IstftArgs a, const float2 *__restrict__ table)
+{
+    typedef typename IstftSample<N>::T T;
+    constexpr int HR = 8 / R;                                   // registers per hop
+    constexpr int HOP = N / R;
+    constexpr int kL = IstftLoad<N, HALF>::kLoads;
+    // the row's natural-order image, then the transform's scratch: 12.9 KB per wave at n = 1024 FULL (three waves
+    // per SIMD, what its registers allow), 8.8 KB otherwise
+    constexpr int kImg = HALF ? N / 2 + 1 : N + 1;
+    __shared__ __attribute__((aligned(16))) float2 lds[kImg + 1 + kWaveLdsComplex];
+    float2 *const img = lds;
+    float2 *const scratch = lds + ((kImg + 1) & ~1);
+    const int lane = threadIdx.x;
+    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
+    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * a.run;
+    if (j0 >= a.n_frames) return;
+    const long j1 = j0 + a.run < a.n_frames ? j0 + a.run : a.n_frames;
+
+    WaveTwiddles tw;
+    load_wave_twiddles(tw, table, lane);
+    SplitTwiddles sw;
+    if (N == 1024) load_split_twiddles(sw, table, lane);
+    T ws[8], g[HR];
+    const T *ws_t = reinterpret_cast<const T *>(a.ws);
+    const T *g_t = reinterpret_cast<const T *>(a.g);
+#pragma unroll
+    for (int d = 0; d < 8; d++) ws[d] = ws_t[lane + 64 * d];
+#pragma unroll
+    for (int d = 0; d < HR; d++) g[d] = g_t[lane + 64 * d];
+
+    T acc[8], y[8];
+    float2 nx[kL], nnyq = make_float2(0.f, 0.f);
+#pragma unroll
+    for (int d = 0; d < 8; d++) acc[d] = ola_zero<T>();
+    if (j0 == 0) {
+        const T *tl = reinterpret_cast<const T *>(a.tail_in);
+#pragma unroll
+        for (int d = 0; d < 8 - HR; d++) acc[d] = tl[lane + 64 * d];
+    } else {
+        // halo: frames j0 - R + 1 .. j0 - 1 (all >= 0: the launch keeps run >= R - 1)
+#pragma unroll
+        for (int k = R - 1; k >= 1; k--) {
+            istft_load<N, HALF>(a.spec + (j0 - k) * a.pitch, lane, nx, nnyq);
+            istft_stage<N, HALF>(nx, nnyq, img, lane);
+            wave_lds_fence();
+            istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
+#pragma unroll
+            for (int d = 0; d < 8; d++) acc[d] = ola_add(acc[d], y[d]);
+#pragma unroll
+            for (int d = 0; d < 8; d++) acc[d] = d + HR < 8 ? acc[d + HR] : ola_zero<T>();
+        }
+    }
+
+    istft_load<N, HALF>(a.spec + j0 * a.pitch, lane, nx, nnyq);
+    istft_stage<N, HALF>(nx, nnyq, img, lane);
+    wave_lds_fence();
+    for (long j = j0; j < j1; j++) {
+        if (j + 1 < j1) istft_load<N, HALF>(a.spec + (j + 1) * a.pitch, lane, nx, nnyq);   // staged one frame from now
+        istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
+#pragma unroll
+        for (int d = 0; d < 8; d++) acc[d] = ola_add(acc[d], y[d]);
+        T o[HR];
+#pragma unroll
+        for (int d = 0; d < HR; d++) o[d] = ola_mul(g[d], acc[d]);
+        // stage the prefetched row before this frame's stores: vmcnt counts loads and stores in issue order, and a wait
+        // for the row at the top of the next iteration would also wait for these stores (denoise_run_kernel)
+        if (j + 1 < j1) istft_stage<N, HALF>(nx, nnyq, img, lane);    // the image's reads are behind istft_frame's fence
+        __builtin_amdgcn_sched_barrier(0);
+        if (a.out) {
+            if constexpr (N == 1024) {
+                unsigned int *dst = reinterpret_cast<unsigned int *>(a.out + j * HOP) + lane;
+#pragma unroll
+                for (int d = 0; d < HR; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
+            } else {
+                unsigned short *dst = reinterpret_cast<unsigned short *>(a.out + j * HOP) + lane;
+#pragma unroll
+                for (int d = 0; d < HR; d++) __builtin_nontemporal_store((unsigned short)cast_i16_bits(o[d]), dst + 64 * d);
+            }
+        }
+        if (a.out_f32) {
+            T *dst = reinterpret_cast<T *>(a.out_f32 + j * HOP) + lane;
+#pragma unroll
+            for (int d = 0; d < HR; d++) nt_store(o[d], dst + 64 * d);
+        }
+#pragma unroll
+        for (int d = 0; d < 8; d++) acc[d] = d + HR < 8 ? acc[d + HR] : ola_zero<T>();
+        if (j == a.n_frames - 1) {
+            T *tl = reinterpret_cast<T *>(a.tail_out);
+#pragma unroll
+            for (int d = 0; d < 8 - HR; d++) tl[lane + 64 * d] = acc[d];
+        }
+        wave_lds_fence();                                        // the staged row before the next frame reads it
+    }
+}
+
+// flush: the n - hop samples still in the tail, g[t mod hop] * s[t], then the same cast
+__global__ __launch_bounds__(256) void istft_flush_kernel(const float *__restrict__ tail, const float *__restrict__ g,
+                                                          int n_tail, int hop, short *__restrict__ out,
+                                                          float *__restrict__ out_f32)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tail) return;
+    const float o = g[i % hop] * tail[i];
+    if (out) out[i] = (short)cast_i16_bits(o);
+    if (out_f32) out_f32[i] = o;
+}
+
+template <int N, int HALF, int R>
+static void launch_run(hipStream_t s, long grid, const IstftArgs &a, const float2 *table)
+{
+    hipLaunchKernelGGL((istft_run_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, a, table);
+}
+
+template <int N, int HALF>
+static void launch_r(hipStream_t s, int r, long grid, const IstftArgs &a, const float2 *table)
+{
+    if (r == 1) launch_run<N, HALF, 1>(s, grid, a, table);
+    else if (r == 2) launch_run<N, HALF, 2>(s, grid, a, table);
+    else launch_run<N, HALF, 4>(s, grid, a, table);
+}
+
+int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch, long n_frames,
+                 const float *ws, const float *g, const float *tail_in, float *tail_out, short *out, float *out_f32,
+                 const float2 *table, int run_opt)
+{
+    if (n_frames <= 0) return 0;
+    const int r = n_fft / hop;
+    // one round of resident waves, but never a run shorter than JDSP_ISTFT_MIN_RUN_PER_HALO (R - 1) frames: the R - 1
+    // halo frames a wave recomputes are then at most 1 / JDSP_ISTFT_MIN_RUN_PER_HALO of its run (extra reads and
+    // transforms) whatever R is; a longer minimum leaves fewer waves for small batches
+    const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_ISTFT_RESIDENT;
+    long run = (n_frames + slots - 1) / slots;
+    const long min_run = r > 1 ? (long)JDSP_ISTFT_MIN_RUN_PER_HALO * (r - 1) : 1;
+    if (run < min_run) run = min_run;
+    if (run_opt > 0) run = run_opt < r - 1 ? r - 1 : run_opt;        // jdsp_istft_set_option("frames_per_wave")
+    const long waves = (n_frames + run - 1) / run;
+    const long grid = (waves + 7) / 8 * 8;
+    IstftArgs a = {spec, pitch, n_frames, ws, g, tail_in, tail_out, out, out_f32, (int)run};
+    if (n_fft == 1024) {
+        if (half) launch_r<1024, 1>(s, r, grid, a, table);
+        else launch_r<1024, 0>(s, r, grid, a, table);
+    } else {
+        if (half) launch_r<512, 1>(s, r, grid, a, table);
+        else launch_r<512, 0>(s, r, grid, a, table);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32)
+{
+    if (n_tail <= 0 || (!out && !out_f32)) return 0;
+    hipLaunchKernelGGL(istft_flush_kernel, dim3((unsigned)((n_tail + 255) / 256)), dim3(256), 0, s, tail, g, n_tail, hop,
+                       out, out_f32);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace jdsp

@@ -247,6 +247,12 @@ int launch_mvdrn512(hipStream_t s, const short *pcm, long chan_stride, int n_mic
 // pitch_kernels.hip
 int launch_pitch(hipStream_t s, const short *pcm, long n_blocks, const short *prev_block, const float2 *table, int *arg,
                  float *rmax, float *autocorr);
+// istft_kernels.hip
+// ws: [n_fft] synthesis window / n_fft; g: [hop] WOLA gain; tails: [n_fft - hop] floats; run_opt 0 = auto
+int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch, long n_frames,
+                 const float *ws, const float *g, const float *tail_in, float *tail_out, short *out, float *out_f32,
+                 const float2 *table, int run_opt);
+int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32);
 // mfcc_kernels.hip
 // ---- GMM / HMM (gmm_kernels.hip) ----
 // packed per-GMM record (doubles): alpa[4], mean[4][4], var[4][4], coef[4][4], eig[4][12][4], and for the

@@ -77,6 +77,11 @@ class Engine:
     def denoiser(self, mode, n_fft=1024, hop=512):
         return Denoiser(self, mode, n_fft, hop)
 
+    def istft(self, **cfg):
+        """STFT synthesis stream (jdsp_istft): n_fft, hop, layout ("full" / "half" or 0 / 1), synthesis_window,
+        analysis_window ("none" / "hamming" / "hann" or -1 / 0 / 1)."""
+        return Istft(self, **cfg)
+
     def synchronize(self):
         self._ck(L.jdsp_synchronize(self._h))
 
@@ -832,3 +837,86 @@ class MvdrMulti:
                                           out.ctypes.data_as(C.c_void_p),
                                           pre.ctypes.data_as(C.c_void_p) if want_precast else None, None))
         return (out[:n_out * B], pre[:n_out * B]) if want_precast else out[:n_out * B]
+
+
+class Istft(_Child):
+    """One STFT synthesis output stream (jdsp_istft, include/jdsp.h): spectra -> inverse transform -> synthesis window
+    -> overlap-add -> int16 (and optionally the float32 values before the cast).  torch CUDA spectra go through the
+    device entry on torch's current stream, numpy spectra through the host entry."""
+    _destroy = staticmethod(lambda h: L.jdsp_istft_destroy(h))
+    LAYOUTS = {"full": _lib.SPEC_FULL, "half": _lib.SPEC_HALF}
+    WINDOWS = {None: _lib.WIN_NONE, "none": _lib.WIN_NONE, "hamming": _lib.WIN_HAMMING, "hann": _lib.WIN_HANN}
+
+    def __init__(self, engine, n_fft=1024, hop=512, layout="full", synthesis_window="none", analysis_window="none"):
+        self.eng = engine
+        pick = lambda v, names: names[v] if isinstance(v, str) or v is None else int(v)  # noqa: E731
+        cfg = _lib.IstftCfg(int(n_fft), int(hop), pick(layout, self.LAYOUTS), pick(synthesis_window, self.WINDOWS),
+                            pick(analysis_window, self.WINDOWS))
+        h = C.c_void_p()
+        engine._ck(L.jdsp_istft_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        self.n_fft, self.hop, self.layout = cfg.n_fft, cfg.hop, cfg.layout
+        self.bins = self.n_fft // 2 + 1 if self.layout == _lib.SPEC_HALF else self.n_fft
+        self._torch = None              # the kind of the last process() input: flush() answers in the same kind
+        engine._children.append(self)
+
+    def reset(self):
+        self.eng._ck(L.jdsp_istft_reset(self._h))
+
+    def set_option(self, name, value):
+        self.eng._ck(L.jdsp_istft_set_option(self._h, name.encode(), int(value)))
+
+    def samples_out(self, n_frames):
+        return L.jdsp_istft_samples_out(self._h, int(n_frames))
+
+    def process(self, spec, want_f32=False, out=None, out_f32=None, n_frames=None, write=True):
+        """spec: complex64 [n_frames, row_pitch >= bins] (torch CUDA or numpy, rows contiguous).  Returns the int16
+        samples of these frames (n_frames * hop), or (int16, float32) with want_f32.  write=False advances the stream
+        without writing (both outputs NULL) and returns None."""
+        if n_frames is None:
+            n_frames = spec.shape[0]
+        pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
+        n_out = self.samples_out(n_frames)
+        if _is_torch(spec):
+            import torch
+            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
+            self._torch = spec.device
+            if write:
+                if out is None:
+                    out = torch.empty(max(n_out, 1), dtype=torch.int16, device=spec.device)
+                if want_f32 and out_f32 is None:
+                    out_f32 = torch.empty(max(n_out, 1), dtype=torch.float32, device=spec.device)
+            else:
+                out = out_f32 = None
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_istft_process_dev(self._h, C.c_void_p(spec.data_ptr()), pitch, n_frames, _vp(out),
+                                                  _vp(out_f32) if want_f32 else None))
+        else:
+            spec = np.ascontiguousarray(spec, np.complex64)
+            self._torch = None
+            if write:
+                out = np.zeros(max(n_out, 1), np.int16) if out is None else out
+                if want_f32 and out_f32 is None:
+                    out_f32 = np.zeros(max(n_out, 1), np.float32)
+            else:
+                out = out_f32 = None
+            self.eng._ck(L.jdsp_istft_process(self._h, _vp(spec), pitch, n_frames, _vp(out),
+                                              _vp(out_f32) if want_f32 else None))
+        if not write:
+            return None
+        return (out[:n_out], out_f32[:n_out]) if want_f32 else out[:n_out]
+
+    def flush(self, want_f32=False):
+        """The n_fft - hop samples still in the tail; the handle is reset afterwards."""
+        n = self.n_fft - self.hop
+        if self._torch is not None:
+            import torch
+            out = torch.zeros(max(n, 1), dtype=torch.int16, device=self._torch)
+            f = torch.zeros(max(n, 1), dtype=torch.float32, device=self._torch) if want_f32 else None
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_istft_flush_dev(self._h, _vp(out), _vp(f)))
+        else:
+            out = np.zeros(max(n, 1), np.int16)
+            f = np.zeros(max(n, 1), np.float32) if want_f32 else None
+            self.eng._ck(L.jdsp_istft_flush(self._h, _vp(out), _vp(f)))
+        return (out[:n], f[:n]) if want_f32 else out[:n]

@@ -103,6 +103,29 @@ def denoise_sharded(denoiser, pcm_ext, ext0, b0, b1, n_total, rank, world, gathe
     return denoiser.shard_finish(lasts, world, rank)
 
 
+def istft_frame_shard(n_frames, world, rank, R):
+    """STFT synthesis (jdsp_istft) of ONE stream of n_frames spectra over `world` ranks: rank owns frames
+    [first, end) and emits their samples [hop*first, hop*end); its output samples also take contributions from the
+    R - 1 frames in front (R = n_fft / hop), so it replays frames [halo, first) without output first.
+    Returns (halo, first, end).  Concatenating the ranks' outputs (plus the last rank's flush) is the single stream."""
+    first, count = split_even(n_frames, rank, world)
+    return max(first - (R - 1), 0), first, first + count
+
+
+def istft_sharded(istft, spec, n_frames, world, rank, want_f32=False):
+    """One rank's part of an STFT synthesis stream: reset, prime the halo frames with NULL outputs (the stream advances
+    without writing), then the rank's own frames.  spec: the rank-sliceable [n_frames, pitch] spectra (only rows
+    [halo, end) are read).  Returns what istft.process returns for the own frames (None when the rank owns none);
+    bit-identical to the same samples of a single-call run."""
+    halo, first, end = istft_frame_shard(n_frames, world, rank, istft.n_fft // istft.hop)
+    istft.reset()
+    if end == first:
+        return None
+    if first > halo:
+        istft.process(spec[halo:first], write=False)
+    return istft.process(spec[first:end], want_f32=want_f32)
+
+
 def fastconv_shard_blocks(n_blocks, hist_blocks, rank, world):
     """Input blocks a rank must be given to produce its share of an overlap-save stream.
     The stream of n_blocks input blocks emits n_blocks - hist_blocks output blocks (the first

@@ -123,6 +123,23 @@ def main():
         report("stft_1024_hop512_fp64", ms, B, "frames", 1024 + 16384, 5 * 512 * 9 + 512 * 14,
                "the headline analysis in the reference's own precision: FP64 window and transform, complex128 full spectrum "
                "(17,408 algorithmic bytes per frame); flops are FP64")
+    if on("istft"):
+        # STFT synthesis (jdsp_istft): 65,536 frames per call, spectra rotated over 6 copies (from HBM)
+        for name, n, hop, layout, pitch, nbytes in (("istft_1024_hop512_full", 1024, 512, "full", 1024, 8192 + 1024),
+                                                    ("istft_1024_hop512_half_pitch513", 1024, 512, "half", 513, 4104 + 1024),
+                                                    ("istft_1024_hop256_full", 1024, 256, "full", 1024, 8192 + 1024),
+                                                    ("istft_512_hop256_full", 512, 256, "full", 512, 4096 + 512)):
+            gen = torch.Generator(device="cuda").manual_seed(n + hop)
+            spec = torch.randn((B, pitch), dtype=torch.complex64, device="cuda", generator=gen) * 3000.0 * np.sqrt(n)
+            sr = rot(spec)
+            ist = eng.istft(n_fft=n, hop=hop, layout=layout)
+            o16 = torch.empty(B * hop, dtype=torch.int16, device="cuda")
+            ms = timed(lambda: ist.process(sr(), out=o16), a.iters)
+            report(name, ms, B, "frames", nbytes, 5 * (n // 2) * 9 + (n // 2) * 14,
+                   "STFT synthesis: Hermitian pairing, one 512-point inverse per frame, overlap-add, int16 out "
+                   "(%d algorithmic bytes per frame; the halo frames a wave recomputes are not counted)" % nbytes)
+            ist.close()
+            del spec, sr
     if on("denoise"):
         x = pcm_of(rng, B * 512)
         x[:12 * 512] = pcm_of(rng, 12 * 512, 45.0)          # the estimate latches at block 10
