@@ -40,7 +40,8 @@ extern "C" {
 
 /* 2: jdsp_vad_blocks_ex added; jdsp_denoise_apply and jdsp_denoise_shard_* accept 512-point streams;
  *    jdsp_denoise_vad_trace's energies / counts follow the option's value at the time of the traced call;
- *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added
+ *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added;
+ *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -509,6 +510,79 @@ int jdsp_hmm_viterbi_dev(jdsp_hmm *h, const double *feats_dev, long n_frames, co
 /* host entry: utt_first_host[0] must be 0 and utt_first_host[n_utts] is the total number of vectors */
 int jdsp_hmm_viterbi(jdsp_hmm *h, const double *feats_host, const int64_t *utt_first_host, long n_utts,
                      double *scores_host, int *best_host, int *path_host, double *trellis_host);
+
+/* ---- GMM training on MFCC vectors (GMMAlgorithm_Train_Auto_ver2.cpp) -------------- */
+/* The reference's training program (Train:49-172) on vectors that are already in HBM: a class is trained from its
+ * files in order.  First file of a class: mean[j] = frame[4j] (Train:120-124), KmeansAlogorithm (Train:342-438),
+ * alpa[k] = 1/4 (Train:129-131).  Every file, the first included: EmAlgorithmBasedGmmParameter (Train:255-340),
+ * exactly three iterations.  The record (Train:160) is PCADiagonalizeCovarianceMatrix (Train:456-518) of the state.
+ * FP64 throughout; the reference's quirks are kept because they define the output:
+ *   - k-means: Selection[i][j] is never cleared, so a frame counts for every cluster it was ever nearest to; the
+ *     arg-min runs j = 0..3 with `>=` (a tie goes to the LAST index); the loop goes on while
+ *     pass == 1 || fabs(cost - cost_before) >= 1.0; on exit the covariance is taken around the means that produced
+ *     the last assignment, divided by the accumulated selection count.  An empty cluster keeps a zero mean and gets
+ *     a 0/0 = NaN covariance (which then makes the whole class NaN through the E-step, as in the reference).
+ *     Option "kmeans_max_passes" (default 10,000) bounds the loop: pass number max takes the exit branch whatever
+ *     the cost did, and the class's stats.kmeans_capped is set.
+ *   - EM: w[i][k] = probability_k(x_i) alpa[k] / sum_k (0/0 = NaN when all four are 0); alpa[k] += sum_i w[i][k]
+ *     onto the OLD alpa, nOfKey[k] = alpa[k], alpa[k] /= n; mean[k] += sum_i w[i][k] x_i onto the OLD mean,
+ *     then /= nOfKey[k]; covariance around the NEW mean, / nOfKey[k].  The print-only log-likelihood pass
+ *     (Train:326-332) is not computed.
+ *   - probability() (Train:189-253): the top 8 eigenpairs of the full 12x12 covariance, ranked as Train:218-235
+ *     (rank = number of strictly larger eigenvalues; a missing rank keeps the previous pick), and
+ *     prod_{i<8} (1/sqrt(2*3.141592)) (1/sqrt(l_i)) exp(-0.5 (y_i - m_i)^2 / l_i) with y = x^T E, m = mean^T E.  The
+ *     decomposition does not depend on x: it is computed once per (class, mixture, EM iteration) on the device
+ *     (cyclic Jacobi, at most 32 sweeps; a matrix with a non-finite entry gives NaN eigenpairs).
+ *   - eigenvectors are defined up to sign: every kept column is made canonical -- its largest-magnitude component
+ *     (first index on ties) is positive.  Column and projected mean flip together; no density changes.
+ * Every sum over frames is ordered by frame index alone (64-frame tiles in ascending order), so results are
+ * bit-identical across "threads_per_class" and however the files are cut into calls.  Differences from the
+ * reference's ascending loops are rounding-level.  Defined here where the reference is not: the E-step buffer is
+ * sized per file (Train:106 sizes it by the first file); an empty file and a first file of fewer than 13 frames are
+ * errors. */
+typedef struct {                        /* Train:26-32 with PCA_LEN 8: 8,096 bytes */
+    double alpa[4];
+    double mean[4][12];
+    double covariance[4][12][12];
+    double eigenVector[4][12][8];
+} jdsp_gmm_train_param;
+/* Per class: k-means passes of the class's first file, whether the pass cap ended it, the accumulated selection
+ * counts and the final cost; files = files trained since reset; status = OR of JDSP_GMM_TRAIN_* flags recorded by
+ * the _dev entry since reset (offsets outside [0, n_frames] clamped, files skipped).  A file whose class is out of
+ * range belongs to no class: it is skipped and flagged in class 0's status.  Offsets that decrease anywhere are
+ * flagged JDSP_GMM_TRAIN_UNORDERED in class 0's status: files whose (clamped) ranges then overlap share per-vector
+ * workspace, and the results of their classes are unspecified -- nothing outside feats is read either way. */
+typedef struct { int kmeans_passes, kmeans_capped, selected[4], files, status; double kmeans_cost; } jdsp_gmm_train_stats;
+enum { JDSP_GMM_TRAIN_CLAMPED = 1, JDSP_GMM_TRAIN_BAD_CLASS = 2, JDSP_GMM_TRAIN_EMPTY_FILE = 4,
+       JDSP_GMM_TRAIN_SHORT_FIRST = 8, JDSP_GMM_TRAIN_UNORDERED = 16 };
+typedef struct jdsp_gmm_trainer jdsp_gmm_trainer;
+int jdsp_gmm_train_create(jdsp_ctx *ctx, int n_classes, jdsp_gmm_trainer **out);   /* 1..1024 classes */
+int jdsp_gmm_train_destroy(jdsp_gmm_trainer *h);
+int jdsp_gmm_train_reset(jdsp_gmm_trainer *h);   /* every class back to "no file seen" (enqueued, no sync) */
+/* "kmeans_max_passes" (>= 1, default 10,000); "threads_per_class" 256 / 512 / 1024 (default 256): workgroup size,
+ * a tuning and testing knob -- the output does not depend on it. */
+int jdsp_gmm_train_set_option(jdsp_gmm_trainer *h, const char *name, long value);
+/* Sizes the per-frame workspace (selection bits and E-step weights: 33 bytes per vector) ahead of a graph capture.
+ * max_files is accepted for symmetry with the other reserve entries and not used: nothing is sized by files. */
+int jdsp_gmm_train_reserve(jdsp_gmm_trainer *h, long max_frames, long max_files);
+/* Files f = 0..n_files-1: vectors file_first[f] .. file_first[f+1]-1 of feats (n_frames x double[12], 16-byte
+ * aligned), belonging to class file_class[f]; the files of one class are trained in ascending f, after every file
+ * that class received in earlier calls.  The _dev entry clamps offsets to [0, n_frames], skips empty files, files of
+ * an out-of-range class and a class's first file when it has fewer than 13 vectors, and records each in stats; it
+ * never reads outside feats.  The host entry rejects all of these with JDSP_EINVAL (file_first[0] must be 0). */
+int jdsp_gmm_train_files_dev(jdsp_gmm_trainer *h, const double *feats_dev, long n_frames,
+                             const int64_t *file_first_dev, const int32_t *file_class_dev, long n_files);
+int jdsp_gmm_train_files(jdsp_gmm_trainer *h, const double *feats_host, const int64_t *file_first_host,
+                         const int32_t *file_class_host, long n_files);   /* host pointers, synchronous */
+/* PCADiagonalizeCovarianceMatrix (Train:456-518) of a COPY of each class's state: the state is unchanged and
+ * training may go on.  mean[k][0..7] = projected mean, [8..11] = 0; covariance rows 0..7 zero with l_i on the
+ * diagonal, rows 8..11 kept; eigenVector[k] = the 8 sorted, sign-canonical eigenvectors.  out: n_classes records.
+ * The host entry's out_host and stats_host (n_classes each) may each be NULL. */
+int jdsp_gmm_train_params_dev(jdsp_gmm_trainer *h, jdsp_gmm_train_param *out_dev);
+int jdsp_gmm_train_params(jdsp_gmm_trainer *h, jdsp_gmm_train_param *out_host, jdsp_gmm_train_stats *stats_host);
+/* Host only (no GPU needed): the PCA_LEN 4 record the test and Viterbi programs read (GMMTest:216-235) -- the first
+ * four eigenvector columns, everything else copied.  in and out: n records. */
+int jdsp_gmm_param_from_train(const jdsp_gmm_train_param *in, int n, jdsp_gmm_param *out);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,16 @@ def _load():
         "jdsp_istft_flush_dev": (i, [vp, vp, vp]),
         "jdsp_istft_process": (i, [vp, vp, l, l, vp, vp]),
         "jdsp_istft_flush": (i, [vp, vp, vp]),
+        "jdsp_gmm_train_create": (i, [vp, i, C.POINTER(vp)]),
+        "jdsp_gmm_train_destroy": (i, [vp]),
+        "jdsp_gmm_train_reset": (i, [vp]),
+        "jdsp_gmm_train_set_option": (i, [vp, C.c_char_p, l]),
+        "jdsp_gmm_train_reserve": (i, [vp, l, l]),
+        "jdsp_gmm_train_files_dev": (i, [vp, vp, l, vp, vp, l]),
+        "jdsp_gmm_train_files": (i, [vp, vp, vp, vp, l]),
+        "jdsp_gmm_train_params_dev": (i, [vp, vp]),
+        "jdsp_gmm_train_params": (i, [vp, vp, vp]),
+        "jdsp_gmm_param_from_train": (i, [vp, i, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

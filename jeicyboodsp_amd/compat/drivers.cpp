@@ -12,6 +12,7 @@
 //   jdsp_mvdr     left.wav right.wav out.raw BeamForming_MVDR_ver1.cpp main()        (:47-122)
 //   jdsp_pitch1   in.wav                     PitchEstimation_method1.cpp main()      (:33-67); prints like :109
 //   jdsp_gmmtest  test_list.txt params.bin   GMMAlgorithm_Test_Auto_ver2.cpp main()  (:46-149)
+//   jdsp_gmmtrain class_lists.txt params.bin GMMAlgorithm_Train_Auto_ver2.cpp main() (:49-172)
 //   jdsp_viterbi  test_list.txt params.bin   Viterbi_version1.cpp main()             (:51-155)
 //
 // File conventions kept from the reference: raw little-endian int16 PCM; a 44-byte WAV header
@@ -262,6 +263,30 @@ static int run_gmmtest(int argc, char **argv)
     return 0;
 }
 
+// Train:76-163: per group of NUM_OF_CLASS class lists, every class trained from its .mfc files in list order, then one
+// 8,096-byte record (PCA_LEN 8) per class.  The progress prints are not reproduced; the parameter file is the output.
+static int run_gmmtrain(int argc, char **argv)
+{
+    if (argc != 3) { fprintf(stderr, "usage: jdsp_gmmtrain class_lists.txt params.bin\n"); return 1; }
+    const int C = env_int("JDSP_NUM_OF_CLASS", 25);                                     // Train:24
+    const std::vector<std::string> lists = read_names(argv[1]);
+    FILE *fp = open_or_die(argv[2], "wb");
+    for (size_t from = 0; from + C <= lists.size(); from += C) {                        // the outer while of :76
+        MfcBatch b = read_mfc_lists(lists, from, C);
+        const long n_files = (long)b.list_of.size();
+        jdsp_gmm_trainer *h = nullptr;
+        CK(jdsp_gmm_train_create(g_ctx, C, &h));
+        std::vector<int32_t> cls(b.list_of.begin(), b.list_of.end());                    // list_of is the class index
+        CK(jdsp_gmm_train_files(h, b.feats.data(), b.first.data(), cls.data(), n_files));
+        std::vector<jdsp_gmm_train_param> params(C);
+        CK(jdsp_gmm_train_params(h, params.data(), nullptr));
+        if (fwrite(params.data(), sizeof(jdsp_gmm_train_param), C, fp) != (size_t)C) die("params write");   // :160
+        jdsp_gmm_train_destroy(h);
+    }
+    fclose(fp);
+    return 0;
+}
+
 static int run_viterbi(int argc, char **argv)
 {
     if (argc != 3) { fprintf(stderr, "usage: jdsp_viterbi test_list.txt params.bin\n"); return 1; }
@@ -317,7 +342,8 @@ int main(int argc, char **argv)
     else if (prog == "jdsp_pitch1") rc = run_pitch1(argc, argv);
     else if (prog == "jdsp_gmmtest") rc = run_gmmtest(argc, argv);
     else if (prog == "jdsp_viterbi") rc = run_viterbi(argc, argv);
-    else fprintf(stderr, "unknown program name %s (expected jdsp_fftalg|jdsp_specsub|jdsp_wiener|jdsp_conv3d|jdsp_mfcc|jdsp_mvdr|jdsp_pitch1|jdsp_gmmtest|jdsp_viterbi)\n", prog.c_str());
+    else if (prog == "jdsp_gmmtrain") rc = run_gmmtrain(argc, argv);
+    else fprintf(stderr, "unknown program name %s (expected jdsp_fftalg|jdsp_specsub|jdsp_wiener|jdsp_conv3d|jdsp_mfcc|jdsp_mvdr|jdsp_pitch1|jdsp_gmmtest|jdsp_viterbi|jdsp_gmmtrain)\n", prog.c_str());
     jdsp_destroy(g_ctx);
     return rc;
 }

@@ -268,6 +268,22 @@ int launch_hmm_viterbi(hipStream_t stream, const double *feats, long n_frames, c
 int launch_mfcc(hipStream_t s, const short *pcm, const long long *starts, long n_frames, const MfccDev &p,
                 const float2 *table, double *feats, int *redo);
 
+// ---- GMM training (gmm_train_kernels.hip) ----
+// Per-class training state in HBM (doubles, then ints): what Train: keeps in its GMMParameter between files, plus the
+// stats of jdsp_gmm_train_stats.
+constexpr int kTrAlpa = 0, kTrMean = 4, kTrCov = 52, kTrCost = 628, kTrDoubles = 629;
+constexpr int kTrSeen = 0, kTrPasses = 1, kTrCapped = 2, kTrSelected = 3, kTrFiles = 7, kTrStatus = 8, kTrInts = 9;
+struct GmmTrainState {
+    double d[kTrDoubles];
+    int i[kTrInts];
+    int pad;
+};
+constexpr int kGmmTrainMaxClasses = 1024;
+int launch_gmm_train(hipStream_t s, int threads, int n_classes, const double *feats, long n_frames,
+                     const long long *file_first, const int *file_class, long n_files, int kmeans_max_passes,
+                     GmmTrainState *state, unsigned char *sel, double *wbuf);
+int launch_gmm_train_params(hipStream_t s, int n_classes, const GmmTrainState *state, jdsp_gmm_train_param *out);
+
 }  // namespace jdsp
 
 struct jdsp_denoise {
@@ -322,6 +338,18 @@ struct jdsp_gmm {
     int n_classes = 0;
     int fused = 0;                        // "evaluation" option: 0 the reference's operation order, 1 fused
     double *records = nullptr;            // [n_classes][kGmmRecord]
+};
+
+struct jdsp_gmm_trainer {
+    jdsp_ctx *ctx = nullptr;
+    int n_classes = 0;
+    int threads = 256;                    // "threads_per_class"
+    int kmeans_max_passes = 10000;        // "kmeans_max_passes"
+    jdsp::GmmTrainState *state = nullptr; // [n_classes]
+    jdsp_gmm_train_param *out = nullptr;  // [n_classes]: the host entry's staging of jdsp_gmm_train_params
+    unsigned char *sel = nullptr;         // [frames]: k-means Selection bits
+    double *wbuf = nullptr;               // [frames][4]: E-step weights
+    long cap_frames = 0;
 };
 
 struct jdsp_hmm {

@@ -74,6 +74,10 @@ class Engine:
     def hmm(self, models):
         return Hmm(self, models)
 
+    def gmm_trainer(self, n_classes):
+        """GMM training (jdsp_gmm_trainer) of n_classes classes (1..1024), GMMAlgorithm_Train_Auto_ver2.cpp."""
+        return GmmTrainer(self, n_classes)
+
     def denoiser(self, mode, n_fft=1024, hop=512):
         return Denoiser(self, mode, n_fft, hop)
 
@@ -487,6 +491,24 @@ class Mfcc:
 GMM_PARAM = np.dtype([("alpa", "<f8", (4,)), ("mean", "<f8", (4, 12)), ("covariance", "<f8", (4, 12, 12)),
                       ("eigenVector", "<f8", (4, 12, 4))])
 HMM_PARAM = np.dtype([("gMMParam", GMM_PARAM, (6,)), ("transProb", "<f8", (6, 6))])
+# the training program's record (GMMAlgorithm_Train_Auto_ver2.cpp:26-32, PCA_LEN 8): 8,096 bytes
+GMM_TRAIN_PARAM = np.dtype([("alpa", "<f8", (4,)), ("mean", "<f8", (4, 12)), ("covariance", "<f8", (4, 12, 12)),
+                            ("eigenVector", "<f8", (4, 12, 8))])
+# jdsp_gmm_train_stats
+GMM_TRAIN_STATS = np.dtype([("kmeans_passes", "<i4"), ("kmeans_capped", "<i4"), ("selected", "<i4", (4,)),
+                            ("files", "<i4"), ("status", "<i4"), ("kmeans_cost", "<f8")])
+
+
+def to_score_params(records):
+    """GMM_TRAIN_PARAM records -> the GMM_PARAM records Engine.gmm() scores with (jdsp_gmm_param_from_train: the first
+    four eigenvector columns, as GMMAlgorithm_Test_Auto_ver2.cpp:216-235 reads them; everything else copied).
+    Host only."""
+    records = np.ascontiguousarray(records, GMM_TRAIN_PARAM).reshape(-1)
+    out = np.zeros(len(records), GMM_PARAM)
+    rc = L.jdsp_gmm_param_from_train(_vp(records), len(records), _vp(out))
+    if rc != 0:
+        raise JdspError(rc, "jdsp_gmm_param_from_train")
+    return out
 
 
 def _vp(a):
@@ -920,3 +942,69 @@ class Istft(_Child):
             f = np.zeros(max(n, 1), np.float32) if want_f32 else None
             self.eng._ck(L.jdsp_istft_flush(self._h, _vp(out), _vp(f)))
         return (out[:n], f[:n]) if want_f32 else out[:n]
+
+
+class GmmTrainer(_Child):
+    """GMM training (jdsp_gmm_trainer): GMMAlgorithm_Train_Auto_ver2.cpp's per-class file loop on the device.
+    The state carries across train() calls; params() reads a PCA-diagonalised copy of it."""
+    _destroy = staticmethod(lambda h: L.jdsp_gmm_train_destroy(h))
+
+    def __init__(self, engine, n_classes):
+        self.eng = engine
+        self.n_classes = int(n_classes)
+        h = C.c_void_p()
+        engine._ck(L.jdsp_gmm_train_create(engine._h, self.n_classes, C.byref(h)))
+        self._h = h
+        engine._children.append(self)
+
+    def set_option(self, name, value):
+        self.eng._ck(L.jdsp_gmm_train_set_option(self._h, name.encode(), int(value)))
+
+    def reset(self):
+        self.eng._ck(L.jdsp_gmm_train_reset(self._h))
+
+    def reserve(self, max_frames, max_files=0):
+        self.eng._ck(L.jdsp_gmm_train_reserve(self._h, int(max_frames), int(max_files)))
+
+    def train(self, feats, file_first, file_class):
+        """feats [n_vectors, 12] float64; file f = vectors file_first[f] .. file_first[f+1]-1 (int64, n_files + 1),
+        of class file_class[f] (int32).  torch CUDA tensors go through the _dev entry on torch's current stream;
+        numpy arrays through the validating host entry."""
+        n_files = len(file_class)
+        if _is_torch(feats):
+            import torch
+            assert feats.is_cuda and feats.dtype == torch.float64 and feats.is_contiguous()
+            assert feats.dim() == 2 and feats.shape[1] == 12
+            assert file_first.is_cuda and file_first.dtype == torch.int64 and file_first.is_contiguous()
+            assert file_class.is_cuda and file_class.dtype == torch.int32 and file_class.is_contiguous()
+            assert file_first.numel() == n_files + 1
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_gmm_train_files_dev(self._h, _vp(feats), feats.shape[0], _vp(file_first),
+                                                    _vp(file_class), n_files))
+            return
+        feats = np.ascontiguousarray(feats, np.float64).reshape(-1, 12)
+        file_first = np.ascontiguousarray(file_first, np.int64)
+        file_class = np.ascontiguousarray(file_class, np.int32)
+        assert file_first.ndim == 1 and file_first.size == n_files + 1
+        assert n_files == 0 or len(feats) >= file_first[-1]
+        self.eng._ck(L.jdsp_gmm_train_files(self._h, _vp(feats), _vp(file_first), _vp(file_class), n_files))
+
+    def params(self, out=None):
+        """-> GMM_TRAIN_PARAM [n_classes] (host).  With `out` a torch CUDA uint8 tensor of n_classes * 8,096 bytes, the
+        records are written there by the _dev entry instead (nothing is synchronised)."""
+        if out is not None:
+            assert _is_torch(out) and out.is_cuda and out.is_contiguous()
+            assert out.numel() * out.element_size() >= self.n_classes * GMM_TRAIN_PARAM.itemsize
+            assert out.data_ptr() % 8 == 0
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_gmm_train_params_dev(self._h, _vp(out)))
+            return out
+        rec = np.zeros(self.n_classes, GMM_TRAIN_PARAM)
+        self.eng._ck(L.jdsp_gmm_train_params(self._h, _vp(rec), None))
+        return rec
+
+    def stats(self):
+        """-> GMM_TRAIN_STATS [n_classes]"""
+        st = np.zeros(self.n_classes, GMM_TRAIN_STATS)
+        self.eng._ck(L.jdsp_gmm_train_params(self._h, None, _vp(st)))
+        return st

@@ -232,6 +232,32 @@ def main():
                "FP64; emission kernel (vector-parallel) + one thread per utterance for the recursion",
                cpu=cpu_rate(lambda: orc.hmm_viterbi(feats_h[:20000], models[0]), 20000))
         h.close()
+    if on("gmmtrain"):
+        # GMM training (jdsp_gmm_trainer, GMMAlgorithm_Train_Auto_ver2.cpp): the gmm leg's ragged utterance lengths
+        # (98..598 vectors, 10,000 files) as 25 classes x 400 files, trained in one call; vectors from 4 anisotropic
+        # clusters per class (tests/gmm_train_cases.py) so that the kept eigen-subspaces are decided by the data
+        import gmm_train_cases as gtc
+        import gmm_train_ref as gtr
+        feats_h, ff_h, fc_h = gtc.bench_files()
+        nvec = int(ff_h[-1])
+        feats = torch.from_numpy(feats_h).cuda()
+        ff, fc = torch.from_numpy(ff_h).cuda(), torch.from_numpy(fc_h).cuda()
+        tr = eng.gmm_trainer(25)
+        tr.reserve(nvec, len(fc_h))
+
+        def train_all():
+            tr.reset()
+            tr.train(feats, ff, fc)
+        ms = timed(train_all, 1, rounds=3, spin_ms=0.0)
+        # per vector: 3 EM iterations x (4 mixtures x (96 MAC + 8 exp + 8 x 4 flops) E-step + 52 MAC + 312 x 3 flops)
+        n_cpu = int(ff_h[50])
+        report("gmm_train_25_classes_400_files", ms, nvec, "vectors", 96 + 32, 3 * (4 * 300 + 104 + 936),
+               "FP64; one workgroup per class over its 400 files (k-means, then 3 x (Jacobi -> E -> M) per file): "
+               "%d vectors; ms is one full training from reset; bounded by the serial chain of 1,200 EM iterations "
+               "per class, not by HBM; cpu_baseline: the numpy restatement (tests/gmm_train_ref.py) on the first "
+               "50 files" % nvec,
+               cpu=cpu_rate(lambda: gtr.train(feats_h[:n_cpu], ff_h[:51], fc_h[:50], 25), n_cpu))
+        tr.close()
     if on("fastconv"):
         nb = 4096
         taps = rng.normal(size=7169) * 0.01
