@@ -41,7 +41,8 @@ extern "C" {
 /* 2: jdsp_vad_blocks_ex added; jdsp_denoise_apply and jdsp_denoise_shard_* accept 512-point streams;
  *    jdsp_denoise_vad_trace's energies / counts follow the option's value at the time of the traced call;
  *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added;
- *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added
+ *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added; the time-domain pitch entries
+ *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -338,6 +339,44 @@ int jdsp_pitch_autocorr_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_blocks
                             int32_t *arg_dev, float *rmax_dev, float *autocorr_dev);
 int jdsp_pitch_autocorr(jdsp_ctx *ctx, const int16_t *pcm_host, long n_blocks, const int16_t *prev_block_host,
                         int32_t *arg_host, float *rmax_host, float *autocorr_host);
+
+/* ---- time-domain pitch: AMDF and autocorrelation (exact) -------------------------------- */
+/* PitchEstimation_method2.cpp (JDSP_PITCH_AMDF) and PitchEstimation_method3.cpp (JDSP_PITCH_ACF): CalcPitch
+ * (:69-101 of both) for n_blocks blocks of 512 samples.  Frame b = [block b-1, block b] with no window; block -1 is
+ * prev_block (NULL: zeros, the reference's initial keep buffer, :71).
+ *   curve[b][k] = dAutoCorrelation[k] (:79-84), k < 512: the sum over i < 1024-k of |x[i]-x[i+k]| (AMDF) or of
+ *                 x[i]*x[i+k] (ACF), divided by (double)(1024-k).  The sums are integers below 2^53 that the
+ *                 reference's double holds exactly, so they are computed exactly here and the one IEEE division
+ *                 gives the reference's bits.
+ *   value[b], arg[b] = dMin / dMax and iArg of the scan :87-95 (from lag 511 down to 101, `<=` for the AMDF, `>=`
+ *                 for the ACF: among equal values the smallest lag wins); pitch = 16000/arg.  A silent frame gives
+ *                 arg 101 and value 0.
+ * Any of arg, value and curve may be NULL; without curve the lags below 101 are not computed.  pcm, prev_block and
+ * curve must be 16-byte aligned.  n_blocks == 0 is a successful no-op; a method other than these two is JDSP_EINVAL.
+ * Results are bit-exact and do not depend on how a stream is cut into calls (hand the last block over as prev_block). */
+enum { JDSP_PITCH_AMDF = 2, JDSP_PITCH_ACF = 3 };          /* the reference's method numbers */
+int jdsp_pitch_lag_dev(jdsp_ctx *ctx, int method, const int16_t *pcm_dev, long n_blocks, const int16_t *prev_block_dev,
+                       int32_t *arg_dev, double *value_dev, double *curve_dev);
+int jdsp_pitch_lag(jdsp_ctx *ctx, int method, const int16_t *pcm_host, long n_blocks, const int16_t *prev_block_host,
+                   int32_t *arg_host, double *value_host, double *curve_host);
+
+/* ---- LPC ---------------------------------------------------------------------------------- */
+/* LPCEstimation.cpp: LPCEstimation (:87-137) for n_blocks blocks of block_len samples (256, the reference's
+ * BLOCK_LEN, or 512), order p = 1 .. 16 (the reference's LPC_LEN is 12).  With N = 2 block_len, frame b =
+ * [block b-1, block b] (block -1 = prev_block, NULL: zeros), all in FP64:
+ *   y[i] = x[i] * (0.54 - 0.46 cos(2*3.141592*i/(N-1)))                                  (:104-106)
+ *   autocorr[b][i] = (sum over j < N-i of y[j] y[j+i]) / (N-i), i <= p: p+1 doubles per block, may be NULL (:108-113)
+ *   lpc[b] = T^-1 v with T[i][j] = r[|i-j|], v[i] = -r[i+1]: p doubles per block                    (:115-130)
+ * The solve is Gaussian elimination with partial pivoting and a back substitution (the reference's Eigen inverse() is
+ * a partial-pivot LU as well); its bits are not the reference's, its forward error is of the same size.  The order of
+ * every sum is fixed per frame: a frame's output does not depend on the batch it arrives in.  A frame whose
+ * elimination meets a zero or non-finite pivot -- the all-zero frame is one; the reference's result there is an
+ * unspecified inf/NaN -- returns p quiet NaNs.  Every block gets a vector: the reference's "first call returns
+ * FALSE" (:133-136) is the caller's business.  pcm and prev_block must be 16-byte aligned. */
+int jdsp_lpc_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_blocks, int block_len, int order,
+                 const int16_t *prev_block_dev, double *autocorr_dev, double *lpc_dev);
+int jdsp_lpc(jdsp_ctx *ctx, const int16_t *pcm_host, long n_blocks, int block_len, int order,
+             const int16_t *prev_block_host, double *autocorr_host, double *lpc_host);
 
 /* ---- two-microphone MVDR beamformer ----------------------------------------------- */
 /* BeamForming_MVDR_ver1.cpp.  One jdsp_mvdr object = the statics of one stereo stream

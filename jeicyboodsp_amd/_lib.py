@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JDSP_LIB") or os.path.join(_HERE, "libjdsp.so")
 
 OK, EINVAL, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4
+PITCH_AMDF, PITCH_ACF = 2, 3
 
 
 class MfccCfg(C.Structure):
@@ -119,6 +120,10 @@ def _load():
         "jdsp_denoise_apply": (i, [vp, vp, l, vp, vp, vp, C.POINTER(l)]),
         "jdsp_pitch_autocorr_dev": (i, [vp, vp, l, vp, vp, vp, vp]),
         "jdsp_pitch_autocorr": (i, [vp, vp, l, vp, vp, vp, vp]),
+        "jdsp_pitch_lag_dev": (i, [vp, i, vp, l, vp, vp, vp, vp]),
+        "jdsp_pitch_lag": (i, [vp, i, vp, l, vp, vp, vp, vp]),
+        "jdsp_lpc_dev": (i, [vp, vp, l, i, i, vp, vp, vp]),
+        "jdsp_lpc": (i, [vp, vp, l, i, i, vp, vp, vp]),
         "jdsp_mvdr_create": (i, [vp, C.c_double, C.POINTER(vp)]),
         "jdsp_mvdr_destroy": (i, [vp]),
         "jdsp_mvdr_reset": (i, [vp]),

@@ -89,6 +89,11 @@ int main(int argc, char **argv)
             int a = JeicybooLastPitchArg();
             fwrite(&a, 4, 1, out);
         }
+    } else if (!strcmp(what, "lpc")) {
+        // LPCEstimation.cpp's main() loop (:67-79): blocks of 256, a vector written when the call returns true
+        double feat[12];
+        for (size_t b = 0; b + 256 <= pcm.size(); b += 256)
+            if (LPCEstimation(&pcm[b], feat)) fwrite(feat, 8, 12, out);
     } else if (!strcmp(what, "awgn")) {
         for (size_t b = 0; b + 512 <= pcm.size(); b += 512) {
             AnalysisAdditiveWhiteGaussianNoise(&pcm[b], 512);

@@ -1,6 +1,6 @@
 // drivers.cpp -- the reference programs' command lines over the BATCHED C ABI: each program
 // reads its whole input like the reference's fread() loop would, makes ONE engine call per
-// stream and writes the reference's output format.  Built as nine executables (Makefile):
+// stream and writes the reference's output format.  Built as one executable per program (Makefile):
 //
 //   jdsp_fftalg   in.wav  out.raw            FFTAlgorithm_ver2.cpp main()            (:30-92)
 //   jdsp_specsub  in.raw  out.raw            SpectralSubtraction_final.cpp main()    (:62-119)
@@ -11,6 +11,9 @@
 //   jdsp_mfcc     list.txt                   MFCCFeatureExtraction_auto_version1.cpp main() (:44-114)
 //   jdsp_mvdr     left.wav right.wav out.raw BeamForming_MVDR_ver1.cpp main()        (:47-122)
 //   jdsp_pitch1   in.wav                     PitchEstimation_method1.cpp main()      (:33-67); prints like :109
+//   jdsp_pitch2   in.wav                     PitchEstimation_method2.cpp main()      (:33-67); prints like :96
+//   jdsp_pitch3   in.wav                     PitchEstimation_method3.cpp main()      (:33-67); prints like :96
+//   jdsp_lpc      in.wav  out.lpc            LPCEstimation.cpp main()                (:39-85); raw double[12] per block
 //   jdsp_gmmtest  test_list.txt params.bin   GMMAlgorithm_Test_Auto_ver2.cpp main()  (:46-149)
 //   jdsp_gmmtrain class_lists.txt params.bin GMMAlgorithm_Train_Auto_ver2.cpp main() (:49-172)
 //   jdsp_viterbi  test_list.txt params.bin   Viterbi_version1.cpp main()             (:51-155)
@@ -189,6 +192,42 @@ static int run_pitch1(int argc, char **argv)
     return 0;
 }
 
+// PitchEstimation_method2.cpp (AMDF) and _method3.cpp (time-domain autocorrelation): both print dMin / dMax under
+// the name "dMin" (:96).  The per-block " dMin %f" line of :88 (the curve at lag 511) is not reproduced.
+static int run_pitch_lag(int method, int argc, char **argv)
+{
+    if (argc != 2) { fprintf(stderr, "usage: %s in.wav\n", argv[0]); return 1; }
+    FILE *in = open_or_die(argv[1], "rb");
+    std::vector<short> pcm = read_blocks(in, 512, 44);                                  // :53,:57
+    const long nb = (long)pcm.size() / 512;
+    std::vector<int32_t> arg((size_t)(nb > 0 ? nb : 1));
+    std::vector<double> val((size_t)(nb > 0 ? nb : 1));
+    CK(jdsp_pitch_lag(g_ctx, method, pcm.data(), nb, nullptr, arg.data(), val.data(), nullptr));
+    for (long b = 0; b < nb; b++)
+        printf("Estimation arg %d , dMin %f pitch %f \n", arg[b], val[b], 16000.0 / (double)arg[b]);   // :96
+    fclose(in);
+    printf("Processing End\n");
+    return 0;
+}
+
+// LPCEstimation.cpp main(): blocks of 256 (:35), the 44-byte header skipped (:64), a vector written for every block
+// but the stream's first (:74-78, :133-136).  The reference's progress print of three coefficients is kept (:75).
+static int run_lpc(int argc, char **argv)
+{
+    if (argc != 3) { fprintf(stderr, "usage: jdsp_lpc in.wav out.lpc\n"); return 1; }
+    FILE *in = open_or_die(argv[1], "rb"), *out = open_or_die(argv[2], "wb");
+    std::vector<short> pcm = read_blocks(in, 256, 44);
+    const long nb = (long)pcm.size() / 256;
+    std::vector<double> feat((size_t)(nb > 0 ? nb : 1) * 12);
+    CK(jdsp_lpc(g_ctx, pcm.data(), nb, 256, 12, nullptr, nullptr, feat.data()));
+    for (long b = 1; b < nb; b++)
+        printf("dLPCFeature[0] %f, dLPCFeature[1] %f, dLPCFeature[2] %f \n", feat[12 * b], feat[12 * b + 1], feat[12 * b + 2]);
+    if (nb > 1) fwrite(feat.data() + 12, sizeof(double), (size_t)(nb - 1) * 12, out);
+    fclose(in); fclose(out);
+    printf("Processing End\n");
+    return 0;
+}
+
 // ---- GMMAlgorithm_Test_Auto_ver2.cpp / Viterbi_version1.cpp ------------------------------------------
 // Both mains read: argv[1] = a text file naming NUM_OF_CLASS class list files, each naming .mfc files of raw
 // double[12] vectors (what jdsp_mfcc writes); argv[2] = NUM_OF_CLASS parameter records.  The reference's
@@ -340,10 +379,13 @@ int main(int argc, char **argv)
     else if (prog == "jdsp_mfcc") rc = run_mfcc(argc, argv);
     else if (prog == "jdsp_mvdr") rc = run_mvdr(argc, argv);
     else if (prog == "jdsp_pitch1") rc = run_pitch1(argc, argv);
+    else if (prog == "jdsp_pitch2") rc = run_pitch_lag(JDSP_PITCH_AMDF, argc, argv);
+    else if (prog == "jdsp_pitch3") rc = run_pitch_lag(JDSP_PITCH_ACF, argc, argv);
+    else if (prog == "jdsp_lpc") rc = run_lpc(argc, argv);
     else if (prog == "jdsp_gmmtest") rc = run_gmmtest(argc, argv);
     else if (prog == "jdsp_viterbi") rc = run_viterbi(argc, argv);
     else if (prog == "jdsp_gmmtrain") rc = run_gmmtrain(argc, argv);
-    else fprintf(stderr, "unknown program name %s (expected jdsp_fftalg|jdsp_specsub|jdsp_wiener|jdsp_conv3d|jdsp_mfcc|jdsp_mvdr|jdsp_pitch1|jdsp_gmmtest|jdsp_viterbi|jdsp_gmmtrain)\n", prog.c_str());
+    else fprintf(stderr, "unknown program name %s (expected jdsp_fftalg|jdsp_specsub|jdsp_wiener|jdsp_conv3d|jdsp_mfcc|jdsp_mvdr|jdsp_pitch1|jdsp_pitch2|jdsp_pitch3|jdsp_lpc|jdsp_gmmtest|jdsp_viterbi|jdsp_gmmtrain)\n", prog.c_str());
     jdsp_destroy(g_ctx);
     return rc;
 }

@@ -44,6 +44,7 @@ double rgdFilterBank[512] = {0};
 int rgdFiBins[512] = {0};
 double rgdMelFreqs[39] = {0};
 
+static void JeicybooResetLpc(void);
 void JeicybooSetBlockLen(int block_len) { g_block_len = block_len; }
 void JeicybooSetDevice(int d) { g_device = d; }
 
@@ -72,6 +73,7 @@ void JeicybooResetStreams(void)
     memset(g_est_keep, 0, sizeof(g_est_keep));
     memset(g_mfcc_keep, 0, sizeof(g_mfcc_keep));
     memset(g_pitch_keep, 0, sizeof(g_pitch_keep));
+    JeicybooResetLpc();
 }
 
 // ---- FFTAlgorithm_ver2.cpp ----------------------------------------------------------------
@@ -247,6 +249,21 @@ void AnalysisAdditiveWhiteGaussianNoise(short *noise, int n)
     memcpy(g_awgn_keep, noise, sizeof(g_awgn_keep));                                            // :129
 }
 const double *JeicybooLastAutoCorrelation(void) { return g_awgn_autocorr; }
+
+// ---- LPCEstimation.cpp:87-137 -------------------------------------------------------------------
+static short g_lpc_keep[256];                      // rgssKeepBuffer (:93)
+static int g_lpc_calls = 0;                        // iNumOfIteration (:92)
+static void JeicybooResetLpc(void)
+{
+    memset(g_lpc_keep, 0, sizeof(g_lpc_keep));
+    g_lpc_calls = 0;
+}
+bool LPCEstimation(short *in, double *feature)
+{
+    CK(jdsp_lpc(JeicybooContext(), in, 1, 256, 12, g_lpc_keep, nullptr, feature));
+    memcpy(g_lpc_keep, in, sizeof(g_lpc_keep));                                                 // :132
+    return ++g_lpc_calls > 1;                                                                   // :98,:133-136
+}
 
 // ---- GMMAlgorithm_Test_Auto_ver2.cpp / Viterbi_version1.cpp -----------------------------------
 static std::vector<double> gather_rows(double **rows, int n)

@@ -69,6 +69,14 @@ double JeicybooLastPitchMax(void);
 void AnalysisAdditiveWhiteGaussianNoise(short *psNoiseBuffer, int iFrameCount);                // :98
 const double *JeicybooLastAutoCorrelation(void);                                                // dAutoCorrelation[512]
 
+// ---- LPCEstimation.cpp:37 ------------------------------------------------------------------
+// One block of 256 samples (BLOCK_LEN :35) in, LPC_LEN = 12 coefficients out; the keep buffer and the call counter
+// are statics as in the reference (:92-93), and the first call of a stream returns false (:133-136).
+// PitchEstimation_method2.cpp and _method3.cpp define CalcPitch with method 1's name and signature: a program links
+// one of the three, so they get no wrapper of their own here -- jdsp_pitch_lag (include/jdsp.h) and the programs
+// jdsp_pitch2 / jdsp_pitch3 (drivers.cpp) are their entry points.
+bool LPCEstimation(short *rgsInputBuffer, double *dLPCFeature);                                 // :87
+
 // ---- GMMAlgorithm_Test_Auto_ver2.cpp:29-34,:44 / Viterbi_version1.cpp:30-40,:49 -------------
 // The parameter records are the C ABI's (same layout as the reference's structs).  One call scores one
 // utterance against one record; the class loop of main() (GMMTest:113-127) calls Recognition once per

@@ -120,6 +120,8 @@ int jdsp_destroy(jdsp_ctx *ctx)
     for (auto &row : ctx->vad_w_ex)
         for (auto &p : row)
             if (p) (void)hipFree(p);
+    for (auto &p : ctx->lpc_win)
+        if (p) (void)hipFree(p);
     if (ctx->win512) (void)hipFree(ctx->win512);
     if (ctx->win512_hann) (void)hipFree(ctx->win512_hann);
     if (ctx->stft1024_table_hann) (void)hipFree(ctx->stft1024_table_hann);

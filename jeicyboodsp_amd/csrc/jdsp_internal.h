@@ -38,6 +38,7 @@ struct jdsp_ctx {
     float2 *conv_tw4096 = nullptr, *conv_tw8192 = nullptr;
     double *vad_w_hi = nullptr;        // second half of the FP64 Hamming window
     double *vad_w_ex[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // jdsp_vad_blocks_ex: [variant][block 512 | 256]
+    double *lpc_win[2] = {nullptr, nullptr};   // jdsp_lpc: FP64 Hamming(2 block_len), block 256 | 512
     // pinned-host pipeline of jdsp_stft_i16: copy-in / compute / copy-out on three streams
     hipStream_t pipe_in = nullptr, pipe_out = nullptr;
     hipEvent_t pipe_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -247,6 +248,13 @@ int launch_mvdrn512(hipStream_t s, const short *pcm, long chan_stride, int n_mic
 // pitch_kernels.hip
 int launch_pitch(hipStream_t s, const short *pcm, long n_blocks, const short *prev_block, const float2 *table, int *arg,
                  float *rmax, float *autocorr);
+// timedomain_kernels.hip
+// method 2 (AMDF) | 3 (autocorrelation); arg, value and curve may each be NULL
+int launch_pitch_lag(hipStream_t s, int method, const short *pcm, long n_blocks, const short *prev_block, int *arg,
+                     double *value, double *curve);
+// win: [2 block_len] FP64 window; autocorr ([order + 1] per block) may be NULL
+int launch_lpc(hipStream_t s, const short *pcm, long n_blocks, int block_len, int order, const short *prev_block,
+               const double *win, double *autocorr, double *lpc);
 // istft_kernels.hip
 // ws: [n_fft] synthesis window / n_fft; g: [hop] WOLA gain; tails: [n_fft - hop] floats; run_opt 0 = auto
 int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch, long n_frames,

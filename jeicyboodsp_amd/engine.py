@@ -183,6 +183,66 @@ class Engine:
                                        ac.ctypes.data_as(C.c_void_p) if want_autocorr else None))
         return (arg, rmax, ac) if want_autocorr else (arg, rmax)
 
+    # ---- PitchEstimation_method2.cpp / PitchEstimation_method3.cpp ---------------------
+    def pitch_lag(self, pcm, method, prev_block=None, want_curve=False):
+        """CalcPitch of PitchEstimation_method2.cpp (method 2, AMDF: arg min) or _method3.cpp (method 3, time-domain
+        autocorrelation: arg max), :69-101, for every 512-sample block of pcm, bit-exact:
+        returns (arg int32[nb], value float64[nb][, curve float64[nb,512]])."""
+        method = int(method)
+        if _is_torch(pcm):
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous() and pcm.numel() % 512 == 0
+            nb = pcm.numel() // 512
+            arg = torch.empty(nb, dtype=torch.int32, device=pcm.device)
+            val = torch.empty(nb, dtype=torch.float64, device=pcm.device)
+            cv = torch.empty((nb, 512), dtype=torch.float64, device=pcm.device) if want_curve else None
+            self._use_torch_stream()
+            self._ck(L.jdsp_pitch_lag_dev(self._h, method, C.c_void_p(pcm.data_ptr()), nb,
+                                          C.c_void_p(prev_block.data_ptr()) if prev_block is not None else None,
+                                          C.c_void_p(arg.data_ptr()), C.c_void_p(val.data_ptr()),
+                                          C.c_void_p(cv.data_ptr()) if want_curve else None))
+            return (arg, val, cv) if want_curve else (arg, val)
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        assert pcm.size % 512 == 0
+        nb = pcm.size // 512
+        arg = np.zeros(nb, np.int32)
+        val = np.zeros(nb, np.float64)
+        cv = np.zeros((nb, 512), np.float64) if want_curve else None
+        pb = np.ascontiguousarray(prev_block, np.int16) if prev_block is not None else None
+        assert pb is None or pb.size == 512
+        self._ck(L.jdsp_pitch_lag(self._h, method, _vp(pcm), nb, _vp(pb) if pb is not None else None, _vp(arg), _vp(val),
+                                  _vp(cv) if want_curve else None))
+        return (arg, val, cv) if want_curve else (arg, val)
+
+    # ---- LPCEstimation.cpp -------------------------------------------------------------
+    def lpc(self, pcm, block_len=256, order=12, prev_block=None, want_autocorr=False):
+        """LPCEstimation (LPCEstimation.cpp:87-137) for every block_len-sample block of pcm (256 | 512), order 1..16:
+        returns lpc float64[nb, order] (every block gets a vector, the stream's first included), with
+        want_autocorr (lpc, autocorr float64[nb, order + 1]).  An all-zero frame gives NaNs."""
+        block_len, order = int(block_len), int(order)
+        if _is_torch(pcm):
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert block_len > 0 and pcm.numel() % block_len == 0
+            nb = pcm.numel() // block_len
+            out = torch.empty((nb, max(order, 0)), dtype=torch.float64, device=pcm.device)
+            ac = torch.empty((nb, max(order, 0) + 1), dtype=torch.float64, device=pcm.device) if want_autocorr else None
+            self._use_torch_stream()
+            self._ck(L.jdsp_lpc_dev(self._h, C.c_void_p(pcm.data_ptr()), nb, block_len, order,
+                                    C.c_void_p(prev_block.data_ptr()) if prev_block is not None else None,
+                                    C.c_void_p(ac.data_ptr()) if want_autocorr else None, C.c_void_p(out.data_ptr())))
+            return (out, ac) if want_autocorr else out
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        assert block_len > 0 and pcm.size % block_len == 0
+        nb = pcm.size // block_len
+        out = np.zeros((nb, max(order, 0)), np.float64)
+        ac = np.zeros((nb, max(order, 0) + 1), np.float64) if want_autocorr else None
+        pb = np.ascontiguousarray(prev_block, np.int16) if prev_block is not None else None
+        assert pb is None or pb.size == block_len
+        self._ck(L.jdsp_lpc(self._h, _vp(pcm), nb, block_len, order, _vp(pb) if pb is not None else None,
+                            _vp(ac) if want_autocorr else None, _vp(out)))
+        return (out, ac) if want_autocorr else out
+
     def stft_half(self, pcm, n_frames=None, out=None, pitch=513):
         """Bins 0..512 only: complex64 [n_frames, pitch >= 513], columns past 512 untouched."""
         import torch

@@ -22,6 +22,9 @@ import oracle_lib  # noqa: E402  (CPU checker: timed here as the per-chain CPU b
 
 HBM_PEAK = 8000.0       # GB/s
 FP32_PEAK = 157.3       # TFLOP/s vector
+TD_CLOCK_GHZ = 2.4      # peak engine clock: the issue bound of the time-domain legs counts one lane-instruction per lane and clock
+TD_TERMS_ALL = sum(1024 - k for k in range(512))            # 393,472 lag terms of a frame, all 512 lags
+TD_TERMS_SEARCH = sum(1024 - k for k in range(101, 512))    # 295,098: the lags the arg search reads
 
 
 def timed(fn, iters, rounds=5, spin_ms=60.0):
@@ -300,6 +303,35 @@ def main():
         report("pitch_autocorr", ms, B, "blocks", 1024 + 8, 2 * 5 * 512 * 9 + 2 * 512 * 14,
                "PitchEstimation_method1 CalcPitch: FFT -> |X|^2 -> IFFT -> arg max, 65,536 blocks",
                cpu=cpu_rate(lambda: orc.pitch_stream(x[:1024 * 512]), 1024))
+    # time-domain analysis (PitchEstimation_method2 / _method3, LPCEstimation): issue-bound, 1 KiB in per block
+    td = [n for n in ("pitch_amdf", "pitch_acf", "lpc") if on(n)]
+    if td:
+        import timedomain_ref
+        x = pcm_of(rng, B * 512)
+        tr_ = rot(torch.from_numpy(x).cuda())
+        slots = eng.n_cu * 64 * TD_CLOCK_GHZ * 1e9                 # lane-instructions per second of the whole chip
+        for name, method, per_instr, instr in (("pitch_amdf", 2, 2, "v_sad_u16, two terms each"),
+                                               ("pitch_acf", 3, 1, "FP64 FMA, one term each")):
+            if name not in td:
+                continue
+            ms = timed(lambda: eng.pitch_lag(tr_(), method), max(a.iters // 4, 3))
+            bound_ms = B * TD_TERMS_SEARCH / per_instr / slots * 1e3
+            report(name, ms, B, "blocks", 1024 + 12, 2 * TD_TERMS_SEARCH,
+                   "PitchEstimation_method%d CalcPitch, bit-exact, lags 101..511 (%d terms per block), 65,536 blocks; "
+                   "issue bound (%s, %d CUs x 64 lanes x %.1f GHz) %.1f us = %.3f of the time"
+                   % (method, TD_TERMS_SEARCH, instr, eng.n_cu, TD_CLOCK_GHZ, bound_ms * 1e3, bound_ms / ms),
+                   cpu=cpu_rate(lambda: timedomain_ref.pitch_stream(x[:64 * 512], method), 64))
+            ms = timed(lambda: eng.pitch_lag(tr_(), method, want_curve=True), max(a.iters // 4, 3))
+            bound_ms = B * TD_TERMS_ALL / per_instr / slots * 1e3
+            report(name + "_curve", ms, B, "blocks", 1024 + 12 + 4096, 2 * TD_TERMS_ALL,
+                   "the same with the 512-lag curve written (%d terms and 4 KiB out per block); issue bound %.1f us = "
+                   "%.3f of the time" % (TD_TERMS_ALL, bound_ms * 1e3, bound_ms / ms))
+        if "lpc" in td:
+            ms = timed(lambda: eng.lpc(tr_(), 256, 12), max(a.iters // 4, 3))
+            report("lpc", ms, 2 * B, "blocks", 512 + 96, 2 * 13 * 512 + 2 * 12 ** 3 // 3 * 2,
+                   "LPCEstimation: FP64 Hamming, 13 autocorrelation lags, 12x12 partial-pivot solve; 131,072 blocks of 256 "
+                   "(the 65,536 x 512 samples of the pitch legs)",
+                   cpu=cpu_rate(lambda: timedomain_ref.lpc_stream(x[:256 * 256], 256, 12), 256))
     if on("mvdr"):
         l = pcm_of(rng, B * 512)
         r = pcm_of(rng, B * 512)
