@@ -3,6 +3,8 @@
 
 using jdsp::fail;
 
+static jdsp::DenoiseGeom geom(const jdsp_denoise *h) { return {h->n_fft, h->win512h}; }
+
 static void free_workspace(jdsp_denoise *h)
 {
     void *p[] = {h->flags, h->ev_n, h->ver_base, h->snap_mask, h->events, h->dbg_energy, h->dbg_zcr, h->rows,
@@ -66,7 +68,7 @@ int jdsp_denoise_create_cfg(jdsp_ctx *ctx, int mode, int n_fft, int hop, jdsp_de
     if (e == hipSuccess) e = hipMalloc((void **)&h->sh_zero_run, sizeof(int));
     if (e == hipSuccess) e = hipMemset(h->sh_zero_run, 0, sizeof(int));
     if (e == hipSuccess && jdsp::ensure_vad_window(ctx)) e = hipErrorUnknown;
-    h->w_hi = ctx->vad_w_hi;
+    h->w_hi = n_fft == 512 ? h->w_hi256 : ctx->vad_w_hi;
     if (e != hipSuccess) {
         jdsp_denoise_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_denoise_create: alloc", e);
@@ -194,29 +196,14 @@ int jdsp_denoise_process_dev(jdsp_denoise *h, const int16_t *pcm_dev, long n_blo
     const jdsp::DenoiseState *st_in = h->st[h->cur];
     jdsp::DenoiseState *st_out = h->st[h->cur ^ 1];
     hipStream_t s = ctx->stream;
-    if (h->n_fft == 512) {
-        if (jdsp::launch_vad256(s, pcm_dev, n_blocks, h->w_hi256, h->flags, h->opt_vad_trace ? h->dbg_energy : nullptr,
-                                h->opt_vad_trace ? h->dbg_zcr : nullptr) ||
-            jdsp::launch_denoise_plan(s, h->flags, n_blocks, st_in, st_out, h->ver_base, h->snap_mask, h->events, h->ev_n,
-                                      h->plan) ||
-            jdsp::launch_noise_estimate512(s, pcm_dev, n_blocks, st_in, st_out, h->events, h->ev_n, h->plan,
-                                           h->ver_base, h->snap_mask, ctx->stft1024_table, h->win512h, h->acc, h->rows) ||
-            jdsp::launch_denoise512(s, h->mode, ctx->n_cu, pcm_dev, n_blocks, h->calls, st_in, st_out, h->ver_base, h->snap_mask,
-                                    h->rows, ctx->stft1024_table, h->win512h, out_dev, precast_dev))
-            return fail(ctx, JDSP_EHIP, "denoise512 launch", hipGetLastError());
-        h->cur ^= 1;
-        h->calls += n_blocks;
-        h->last_blocks = n_blocks;
-        h->last_trace_valid = h->opt_vad_trace;
-        return JDSP_OK;
-    }
-    if (jdsp::launch_vad(s, pcm_dev, n_blocks, h->w_hi, 1, h->flags, h->opt_vad_trace ? h->dbg_energy : nullptr,
+    const jdsp::DenoiseGeom g = geom(h);
+    if (jdsp::launch_vad(s, h->block, pcm_dev, n_blocks, h->w_hi, 1, h->flags, h->opt_vad_trace ? h->dbg_energy : nullptr,
                          h->opt_vad_trace ? h->dbg_zcr : nullptr) ||
         jdsp::launch_denoise_plan(s, h->flags, n_blocks, st_in, st_out, h->ver_base, h->snap_mask, h->events, h->ev_n,
                                   h->plan) ||
-        jdsp::launch_noise_estimate(s, pcm_dev, n_blocks, st_in, st_out, h->events, h->ev_n, h->plan,
-                                    h->ver_base, h->snap_mask, ctx->stft1024_table, h->acc, h->rows) ||
-        jdsp::launch_denoise(s, h->mode, h->opt_k, ctx->n_cu, pcm_dev, n_blocks, h->calls, st_in, st_out, h->ver_base,
+        jdsp::launch_noise_estimate(s, g, pcm_dev, n_blocks, st_in, st_out, h->events, h->ev_n, h->plan, h->ver_base,
+                                    h->snap_mask, ctx->stft1024_table, h->acc, h->rows) ||
+        jdsp::launch_denoise(s, g, h->mode, h->opt_k, ctx->n_cu, pcm_dev, n_blocks, h->calls, st_in, st_out, h->ver_base,
                              h->snap_mask, h->rows, ctx->stft1024_table, out_dev, precast_dev))
         return fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError());
     h->cur ^= 1;
@@ -240,27 +227,14 @@ int jdsp_denoise_process(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks
     const size_t blk = (size_t)h->block;
     const size_t in_b = (size_t)n_blocks * blk * sizeof(int16_t);
     const size_t out_b = (size_t)(n_out > 0 ? n_out : 1) * blk * sizeof(int16_t);
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    float *d_pre = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_b);
-    if (e == hipSuccess && precast_host) e = hipMalloc((void **)&d_pre, out_b * 2);
-    int rc = JDSP_OK;
-    if (e != hipSuccess) rc = fail(ctx, JDSP_ENOMEM, "jdsp_denoise_process: hipMalloc", e);
-    if (!rc && (e = hipMemcpyAsync(d_in, pcm_host, in_b, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_process: H2D", e);
-    if (!rc) rc = jdsp_denoise_process_dev(h, d_in, n_blocks, d_out, d_pre, nullptr);
-    if (!rc && n_out > 0 &&
-        (e = hipMemcpyAsync(out_host, d_out, (size_t)n_out * blk * 2, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_process: D2H", e);
-    if (!rc && n_out > 0 && precast_host &&
-        (e = hipMemcpyAsync(precast_host, d_pre, (size_t)n_out * blk * 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_process: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_process: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pre) (void)hipFree(d_pre);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_denoise_process");
+    const int16_t *d_in = hc.upload(pcm_host, in_b);
+    int16_t *d_out = hc.alloc<int16_t>(out_b);
+    float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
+    if (hc.ok()) hc.result(jdsp_denoise_process_dev(h, d_in, n_blocks, d_out, d_pre, nullptr));
+    hc.download(out_host, d_out, (size_t)n_out * blk * 2);
+    hc.download(precast_host, d_pre, (size_t)n_out * blk * 4);
+    return hc.finish();
 }
 
 int jdsp_denoise_apply(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks, const double *noise_host,
@@ -280,36 +254,22 @@ int jdsp_denoise_apply(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks, 
     for (int i = 0; i < h->n_fft; i++) row[i] = (float)noise_host[i];          // pdEstimatedNoiseSpec[FFT_PROCESSING_SIZE]
     const size_t blk_b = (size_t)h->block * sizeof(int16_t);
     const size_t in_b = (size_t)n_blocks * blk_b, out_b = (size_t)(n_out > 0 ? n_out : 1) * blk_b;
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    float *d_pre = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_b);
-    if (e == hipSuccess && precast_host) e = hipMalloc((void **)&d_pre, out_b * 2);
     hipStream_t s = ctx->stream;
     jdsp::DenoiseState *st_in = h->st[h->cur], *st_out = h->st[h->cur ^ 1];
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, pcm_host, in_b, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->rows, row, sizeof(float) * (size_t)h->n_fft, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(h->ver_base, 0, ((size_t)n_blocks / 64 + 1) * sizeof(int), s);   // every block uses row 0
-    if (e == hipSuccess) e = hipMemsetAsync(h->snap_mask, 0, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(st_out, st_in, sizeof(jdsp::DenoiseState), hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_apply: staging", e);
-    if (!rc && (h->n_fft == 512
-                    ? jdsp::launch_denoise512(s, h->mode, ctx->n_cu, d_in, n_blocks, h->calls, st_in, st_out, h->ver_base,
-                                              h->snap_mask, h->rows, ctx->stft1024_table, h->win512h, d_out, d_pre)
-                    : jdsp::launch_denoise(s, h->mode, h->opt_k, ctx->n_cu, d_in, n_blocks, h->calls, st_in, st_out, h->ver_base,
-                                           h->snap_mask, h->rows, ctx->stft1024_table, d_out, d_pre))) {
-        const hipError_t le = hipGetLastError();
-        rc = fail(ctx, JDSP_EHIP, "denoise launch", le);
-    }
-    if (!rc && n_out > 0 && (e = hipMemcpyAsync(out_host, d_out, (size_t)n_out * blk_b, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_apply: D2H", e);
-    if (!rc && n_out > 0 && precast_host &&
-        (e = hipMemcpyAsync(precast_host, d_pre, (size_t)n_out * blk_b * 2, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_apply: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_denoise_apply: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pre) (void)hipFree(d_pre);
+    jdsp::HostCall hc(ctx, "jdsp_denoise_apply");
+    const int16_t *d_in = hc.upload(pcm_host, in_b);
+    int16_t *d_out = hc.alloc<int16_t>(out_b);
+    float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
+    hc.upload_to(h->rows, row, sizeof(float) * (size_t)h->n_fft);
+    hc.zero(h->ver_base, ((size_t)n_blocks / 64 + 1) * sizeof(int));                   // every block uses row 0
+    hc.zero(h->snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
+    hc.copy_dev(st_out, st_in, sizeof(jdsp::DenoiseState));
+    if (hc.ok() && jdsp::launch_denoise(s, geom(h), h->mode, h->opt_k, ctx->n_cu, d_in, n_blocks, h->calls, st_in, st_out,
+                                        h->ver_base, h->snap_mask, h->rows, ctx->stft1024_table, d_out, d_pre))
+        hc.result(fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError()));
+    hc.download(out_host, d_out, (size_t)n_out * blk_b);
+    hc.download(precast_host, d_pre, (size_t)n_out * blk_b * 2);
+    rc = hc.finish();
     if (!rc) {
         h->cur ^= 1;
         h->calls += n_blocks;
@@ -331,32 +291,18 @@ int jdsp_vad_blocks_ex(jdsp_ctx *ctx, int variant, int block_len, const int16_t 
     int rc = jdsp::ensure_vad_window_ex(ctx, variant, block_len, &w);
     if (rc) return rc;
     const size_t n = (size_t)n_blocks, in_bytes = n * (size_t)block_len * sizeof(int16_t);
-    int16_t *d_in = nullptr;
-    unsigned char *d_v = nullptr;
-    long long *d_e = nullptr;
-    int *d_z = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_v, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_e, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_z, n * 4);
-    hipStream_t s = ctx->stream;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, pcm_host, in_bytes, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_vad_blocks: staging", e);
+    jdsp::HostCall hc(ctx, "jdsp_vad_blocks");
+    const int16_t *d_in = hc.upload(pcm_host, in_bytes);
+    unsigned char *d_v = hc.alloc<unsigned char>(n);
+    long long *d_e = hc.alloc<long long>(n * 8);
+    int *d_z = hc.alloc<int>(n * 4);
     const int use_zcr = variant == JDSP_VAD_DENOISE;                    // BF:233 tests the energy alone
-    if (!rc && (block_len == 512 ? jdsp::launch_vad(s, d_in, n_blocks, w, use_zcr, d_v, d_e, d_z)
-                                 : jdsp::launch_vad256(s, d_in, n_blocks, w, d_v, d_e, d_z, use_zcr))) {
-        const hipError_t le = hipGetLastError();
-        rc = fail(ctx, JDSP_EHIP, "vad launch", le);
-    }
-    if (!rc && voice_host && (e = hipMemcpyAsync(voice_host, d_v, n, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_vad_blocks: D2H", e);
-    if (!rc && energy_sum_host && (e = hipMemcpyAsync(energy_sum_host, d_e, n * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_vad_blocks: D2H", e);
-    if (!rc && zcr_host && (e = hipMemcpyAsync(zcr_host, d_z, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_vad_blocks: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_vad_blocks: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_v) (void)hipFree(d_v);
-    if (d_e) (void)hipFree(d_e);
-    if (d_z) (void)hipFree(d_z);
-    return rc;
+    if (hc.ok() && jdsp::launch_vad(ctx->stream, block_len, d_in, n_blocks, w, use_zcr, d_v, d_e, d_z))
+        hc.result(fail(ctx, JDSP_EHIP, "vad launch", hipGetLastError()));
+    hc.download(voice_host, d_v, n);
+    hc.download(energy_sum_host, d_e, n * 8);
+    hc.download(zcr_host, d_z, n * 4);
+    return hc.finish();
 }
 
 int jdsp_vad_blocks(jdsp_ctx *ctx, const int16_t *pcm_host, long n_blocks, uint8_t *voice_host,
@@ -381,13 +327,9 @@ int jdsp_denoise_shard_vad_dev(jdsp_denoise *h, const int16_t *pcm_ext_dev, long
     rc = jdsp_denoise_reset(h);                       // a sharded run is one fresh global stream
     if (rc) return rc;
     h->sh_ext0 = ext0; h->sh_b0 = b0; h->sh_b1 = b1; h->sh_total = n_total; h->sh_pcm = pcm_ext_dev;
-    if (h->n_fft == 512 ? jdsp::launch_vad256(ctx->stream, pcm_ext_dev + (b0 - ext0) * 256, b1 - b0, h->w_hi256, flags_own_dev,
-                                              nullptr, nullptr)
-                        : jdsp::launch_vad(ctx->stream, pcm_ext_dev + (b0 - ext0) * 512, b1 - b0, h->w_hi, 1, flags_own_dev,
-                                           nullptr, nullptr)) {
-        const hipError_t le = hipGetLastError();
-        return fail(ctx, JDSP_EHIP, "vad launch", le);
-    }
+    if (jdsp::launch_vad(ctx->stream, h->block, pcm_ext_dev + (b0 - ext0) * h->block, b1 - b0, h->w_hi, 1, flags_own_dev,
+                         nullptr, nullptr))
+        return fail(ctx, JDSP_EHIP, "vad launch", hipGetLastError());
     return JDSP_OK;
 }
 
@@ -401,16 +343,10 @@ int jdsp_denoise_shard_summary_dev(jdsp_denoise *h, const uint8_t *flags_all_dev
     hipStream_t s = ctx->stream;
     if (jdsp::launch_run_plan(s, flags_all_dev, h->sh_total, h->sh_zero_run, nullptr, 10, h->ver_base, h->snap_mask,
                               h->events, h->ev_n, h->plan) ||
-        (h->n_fft == 512
-             ? jdsp::launch_shard_summary512(s, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0, h->sh_b1, h->events,
-                                             h->ev_n, h->plan, h->ver_base, h->snap_mask, ctx->stft1024_table, h->win512h,
-                                             h->sh_range, h->acc, h->rows, summary_dev)
-             : jdsp::launch_shard_summary(s, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0, h->sh_b1, h->events,
-                                          h->ev_n, h->plan, h->ver_base, h->snap_mask, ctx->stft1024_table, h->sh_range,
-                                          h->acc, h->rows, summary_dev))) {
-        const hipError_t le = hipGetLastError();
-        return fail(ctx, JDSP_EHIP, "shard summary launch", le);
-    }
+        jdsp::launch_shard_summary(s, geom(h), h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0, h->sh_b1, h->events,
+                                   h->ev_n, h->plan, h->ver_base, h->snap_mask, ctx->stft1024_table, h->sh_range, h->acc,
+                                   h->rows, summary_dev))
+        return fail(ctx, JDSP_EHIP, "shard summary launch", hipGetLastError());
     return JDSP_OK;
 }
 
@@ -421,13 +357,9 @@ int jdsp_denoise_shard_rows_dev(jdsp_denoise *h, const float *summaries_all_dev,
     if (!summaries_all_dev || !last_dev || world < 1 || rank < 0 || rank >= world)
         return fail(ctx, JDSP_EINVAL, "jdsp_denoise_shard_rows: bad argument");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    if (h->n_fft == 512 ? jdsp::launch_shard_rows512(ctx->stream, summaries_all_dev, rank, h->sh_b0, h->sh_b1, h->plan,
-                                                     h->sh_range, h->acc, h->sh_a_in, h->rows, last_dev)
-                        : jdsp::launch_shard_rows(ctx->stream, summaries_all_dev, rank, h->sh_b0, h->sh_b1, h->plan,
-                                                  h->sh_range, h->acc, h->sh_a_in, h->rows, last_dev)) {
-        const hipError_t le = hipGetLastError();
-        return fail(ctx, JDSP_EHIP, "shard rows launch", le);
-    }
+    if (jdsp::launch_shard_rows(ctx->stream, geom(h), summaries_all_dev, rank, h->sh_b0, h->sh_b1, h->plan, h->sh_range,
+                                h->acc, h->sh_a_in, h->rows, last_dev))
+        return fail(ctx, JDSP_EHIP, "shard rows launch", hipGetLastError());
     return JDSP_OK;
 }
 
@@ -450,10 +382,8 @@ int jdsp_denoise_shard_finish_dev(jdsp_denoise *h, const float *last_all_dev, in
     if ((uintptr_t)out_dev & 15u) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_shard_finish: out must be 16-byte aligned");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (h->n_fft == 512 ? jdsp::launch_shard_row0_512(s, last_all_dev, rank, h->rows) : jdsp::launch_shard_row0(s, last_all_dev, rank, h->rows)) {
-        const hipError_t le = hipGetLastError();
-        return fail(ctx, JDSP_EHIP, "row0 launch", le);
-    }
+    if (jdsp::launch_shard_row0(s, geom(h), last_all_dev, rank, h->rows))
+        return fail(ctx, JDSP_EHIP, "row0 launch", hipGetLastError());
     if (n_out > 0) {
         jdsp::DenoiseShard sh;
         sh.ver_block_off = h->sh_ext0;
@@ -462,16 +392,10 @@ int jdsp_denoise_shard_finish_dev(jdsp_denoise *h, const float *last_all_dev, in
         sh.emit_from = lo - h->sh_ext0;
         sh.emit_to = h->sh_b1 - h->sh_ext0;
         // fresh state: the two halo blocks in front of the shard rebuild the overlap tail
-        if (h->n_fft == 512
-                ? jdsp::launch_denoise512(s, h->mode, ctx->n_cu, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->st[h->cur],
-                                          h->st[h->cur ^ 1], h->ver_base, h->snap_mask, h->rows, ctx->stft1024_table,
-                                          h->win512h, out_dev, precast_dev, &sh)
-                : jdsp::launch_denoise(s, h->mode, h->opt_k, ctx->n_cu, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0,
-                                       h->st[h->cur], h->st[h->cur ^ 1], h->ver_base, h->snap_mask, h->rows,
-                                       ctx->stft1024_table, out_dev, precast_dev, &sh)) {
-            const hipError_t le = hipGetLastError();
-            return fail(ctx, JDSP_EHIP, "denoise launch", le);
-        }
+        if (jdsp::launch_denoise(s, geom(h), h->mode, h->opt_k, ctx->n_cu, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0,
+                                 h->st[h->cur], h->st[h->cur ^ 1], h->ver_base, h->snap_mask, h->rows, ctx->stft1024_table,
+                                 out_dev, precast_dev, &sh))
+            return fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError());
     }
     return JDSP_OK;
 }

@@ -1129,65 +1129,21 @@ __global__ __launch_bounds__(256) void select_row0_kernel(const float *__restric
     rows[bin] = v;
 }
 
-// A rank's events through the chunked average (noise_accum_kernel / noise_combine_kernel) in two passes: the first
-// leaves the rank's composed map in `summary` (and every latched row as its partial map), the second -- once the
-// maps of the ranks before it are known -- completes the rows from the average this rank starts from.
-static int shard_accum_grid(long own) { return own < kNoiseChunks ? (int)(own > 0 ? own : 1) : kNoiseChunks; }
-
-int launch_shard_summary(hipStream_t s, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
-                         const int *events, const int *ev_n, const DenoisePlan *plan, const int *ver_base,
-                         const unsigned long long *snap_mask, const float2 *table, int *range, const NoiseAccum &acc,
-                         float *rows, float *summary)
-{
-    hipLaunchKernelGGL(event_range_kernel, dim3(1), dim3(64), 0, s, events, plan, ver_base, snap_mask, b0, b1, range);
-    const int grid = shard_accum_grid(b1 - b0);
-    hipLaunchKernelGGL(noise_accum_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm_ext, n_ext, (const DenoiseState *)nullptr,
-                       events, ev_n, plan, ver_base, snap_mask, table, acc, rows, 10, (const int *)range, ext0);
-    hipLaunchKernelGGL(noise_combine_kernel, dim3(1024 / kCombineBins), dim3(1024), 0, s, plan, (const DenoiseState *)nullptr,
-                       (DenoiseState *)nullptr, acc, rows, grid, (const int *)range, (const float *)nullptr, summary,
-                       (float *)nullptr, 0);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_shard_rows(hipStream_t s, const float *summaries_all, int rank, long b0, long b1, const DenoisePlan *plan,
-                      const int *range, const NoiseAccum &acc, float *a_in, float *rows, float *last)
-{
-    hipLaunchKernelGGL(fold_summaries_kernel, dim3(4), dim3(256), 0, s, summaries_all, rank, a_in);
-    hipLaunchKernelGGL(noise_combine_kernel, dim3(1024 / kCombineBins), dim3(1024), 0, s, plan, (const DenoiseState *)nullptr,
-                       (DenoiseState *)nullptr, acc, rows, shard_accum_grid(b1 - b0), range, (const float *)a_in,
-                       (float *)nullptr, last, 1);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_shard_row0(hipStream_t s, const float *last_all, int rank, float *rows)
-{
-    hipLaunchKernelGGL(select_row0_kernel, dim3(4), dim3(256), 0, s, last_all, rank, rows);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 // ---------------------------------------------------------------------------------------
-int launch_vad(hipStream_t s, const short *pcm, long n_blocks, const double *w_hi, int use_zcr, unsigned char *flags,
-               long long *dbg_energy, int *dbg_zcr)
+// block_len 512, or 256 (frames of 512); w_hi = the second half of the FP64 Hamming(2 block_len)
+int launch_vad(hipStream_t s, int block_len, const short *pcm, long n_blocks, const double *w_hi, int use_zcr,
+               unsigned char *flags, long long *dbg_energy, int *dbg_zcr)
 {
     if (n_blocks <= 0) return 0;
     const dim3 grid((unsigned)((n_blocks + kVadBlocksPerWave - 1) / kVadBlocksPerWave));
-    if (!dbg_energy && !dbg_zcr)
-        hipLaunchKernelGGL(vad_flags_kernel<8>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags);
-    else
-        hipLaunchKernelGGL(vad_kernel<8>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags, dbg_energy, dbg_zcr);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// 256-sample blocks (frames of 512): w_hi = the second half of Hamming(512), 256 doubles
-int launch_vad256(hipStream_t s, const short *pcm, long n_blocks, const double *w_hi, unsigned char *flags,
-                  long long *dbg_energy, int *dbg_zcr, int use_zcr)
-{
-    if (n_blocks <= 0) return 0;
-    const dim3 grid((unsigned)((n_blocks + kVadBlocksPerWave - 1) / kVadBlocksPerWave));
-    if (!dbg_energy && !dbg_zcr)
-        hipLaunchKernelGGL(vad_flags_kernel<4>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags);
-    else
-        hipLaunchKernelGGL(vad_kernel<4>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags, dbg_energy, dbg_zcr);
+    const bool trace = dbg_energy || dbg_zcr;
+    if (block_len == 512) {
+        if (!trace) hipLaunchKernelGGL(vad_flags_kernel<8>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags);
+        else hipLaunchKernelGGL(vad_kernel<8>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags, dbg_energy, dbg_zcr);
+    } else {
+        if (!trace) hipLaunchKernelGGL(vad_flags_kernel<4>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags);
+        else hipLaunchKernelGGL(vad_kernel<4>, grid, dim3(64), 0, s, pcm, n_blocks, w_hi, use_zcr, flags, dbg_energy, dbg_zcr);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1210,20 +1166,6 @@ int launch_run_plan(hipStream_t s, const unsigned char *flags, long n_blocks, co
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_noise_estimate(hipStream_t s, const short *pcm, long n_blocks, const DenoiseState *st_in,
-                          DenoiseState *st_out, const int *events, const int *ev_n, const DenoisePlan *plan,
-                          const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
-                          const NoiseAccum &acc, float *noise_rows)
-{
-    const int grid = n_blocks < kNoiseChunks ? (int)(n_blocks > 0 ? n_blocks : 1) : kNoiseChunks;
-    if (n_blocks > 0)
-        hipLaunchKernelGGL(noise_accum_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, st_in, events, ev_n, plan,
-                           ver_base, snap_mask, table, acc, noise_rows, 10, (const int *)nullptr, 0L);
-    hipLaunchKernelGGL(noise_combine_kernel, dim3(1024 / kCombineBins), dim3(1024), 0, s, plan, st_in, st_out, acc, noise_rows, grid,
-                       (const int *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, 1);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
 template <int MODE, int K>
 static void launch_dn(hipStream_t s, const short *pcm, long n_blocks, long calls_before, const DenoiseState *st_in,
                       DenoiseState *st_out, const int *ver_base, const unsigned long long *snap_mask,
@@ -1234,20 +1176,11 @@ static void launch_dn(hipStream_t s, const short *pcm, long n_blocks, long calls
                        st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh);
 }
 
-int launch_denoise(hipStream_t s, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks, long calls_before,
-                   const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
-                   const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
-                   float *precast, const DenoiseShard *shard)
+static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
+                             long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
+                             const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
+                             float *precast, const DenoiseShard &sh)
 {
-    if (n_blocks <= 0) return 0;
-    DenoiseShard sh;
-    if (shard) sh = *shard;
-    else {
-        sh.ver_block_off = 0;
-        sh.ver_row_off = nullptr;
-        sh.emit_from = calls_before >= 2 ? 0 : 2 - calls_before;
-        sh.emit_to = n_blocks;
-    }
     if (k_opt == 0) {
         // one round of resident waves: JDSP_DENOISE_RESIDENT per SIMD, 4 SIMDs per CU; never fewer than 4 blocks
         // per wave (a quarter of halo overhead at most)
@@ -1761,68 +1694,11 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
     }
 }
 
-int launch_noise_estimate512(hipStream_t s, const short *pcm, long n_blocks, const DenoiseState *st_in,
-                             DenoiseState *st_out, const int *events, const int *ev_n, const DenoisePlan *plan,
-                             const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
-                             const float *win512, const NoiseAccum &acc, float *noise_rows)
+static int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm, long n_blocks, long calls_before,
+                             const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
+                             const unsigned long long *snap_mask, const float *noise_rows, const float2 *table,
+                             const float *win512, short *out, float *precast, const DenoiseShard &sh)
 {
-    const int grid = n_blocks < kNoiseChunks ? (int)(n_blocks > 0 ? n_blocks : 1) : kNoiseChunks;
-    if (n_blocks > 0)
-        hipLaunchKernelGGL(noise_accum512_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, st_in, events, ev_n,
-                           plan, ver_base, snap_mask, table, win512, acc, noise_rows, 10, (const int *)nullptr, 0L);
-    // bins 0..511 only (rows keep the 1024-float pitch of the 1024-point path)
-    hipLaunchKernelGGL(noise_combine_kernel, dim3(512 / kCombineBins), dim3(1024), 0, s, plan, st_in, st_out, acc, noise_rows, grid,
-                       (const int *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, 1);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// sharded runs on 512-point frames: launch_shard_summary / launch_shard_rows with the 512-point accumulate kernel and
-// the combine kernel over bins 0..511 (rows and summaries keep the 1024-float pitch; bins 512.. are never read)
-int launch_shard_summary512(hipStream_t s, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
-                            const int *events, const int *ev_n, const DenoisePlan *plan, const int *ver_base,
-                            const unsigned long long *snap_mask, const float2 *table, const float *win512, int *range,
-                            const NoiseAccum &acc, float *rows, float *summary)
-{
-    hipLaunchKernelGGL(event_range_kernel, dim3(1), dim3(64), 0, s, events, plan, ver_base, snap_mask, b0, b1, range);
-    const int grid = shard_accum_grid(b1 - b0);
-    hipLaunchKernelGGL(noise_accum512_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm_ext, n_ext, (const DenoiseState *)nullptr,
-                       events, ev_n, plan, ver_base, snap_mask, table, win512, acc, rows, 10, (const int *)range, ext0);
-    hipLaunchKernelGGL(noise_combine_kernel, dim3(512 / kCombineBins), dim3(1024), 0, s, plan, (const DenoiseState *)nullptr,
-                       (DenoiseState *)nullptr, acc, rows, grid, (const int *)range, (const float *)nullptr, summary,
-                       (float *)nullptr, 0);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_shard_rows512(hipStream_t s, const float *summaries_all, int rank, long b0, long b1, const DenoisePlan *plan,
-                         const int *range, const NoiseAccum &acc, float *a_in, float *rows, float *last)
-{
-    hipLaunchKernelGGL(fold_summaries_kernel, dim3(2), dim3(256), 0, s, summaries_all, rank, a_in);
-    hipLaunchKernelGGL(noise_combine_kernel, dim3(512 / kCombineBins), dim3(1024), 0, s, plan, (const DenoiseState *)nullptr,
-                       (DenoiseState *)nullptr, acc, rows, shard_accum_grid(b1 - b0), range, (const float *)a_in,
-                       (float *)nullptr, last, 1);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_shard_row0_512(hipStream_t s, const float *last_all, int rank, float *rows)
-{
-    hipLaunchKernelGGL(select_row0_kernel, dim3(2), dim3(256), 0, s, last_all, rank, rows);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm, long n_blocks, long calls_before,
-                      const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
-                      const unsigned long long *snap_mask, const float *noise_rows, const float2 *table,
-                      const float *win512, short *out, float *precast, const DenoiseShard *shard)
-{
-    if (n_blocks <= 0) return 0;
-    DenoiseShard sh;
-    if (shard) sh = *shard;
-    else {
-        sh.ver_block_off = 0;
-        sh.ver_row_off = nullptr;
-        sh.emit_from = calls_before >= 2 ? 0 : 2 - calls_before;
-        sh.emit_to = n_blocks;
-    }
 #ifndef JDSP_DENOISE512_RUN
 #define JDSP_DENOISE512_RUN 1
 #endif
@@ -1850,6 +1726,95 @@ int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm, long 
     else
         hipLaunchKernelGGL(denoise512_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
                            st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- launchers of both frame sizes --------------------------------------------------------------
+// 512-point frames: the 512-point accumulate kernel, and the combine / fold / select kernels over bins 0..511 only (rows
+// and summaries keep the 1024-float pitch of the 1024-point path; bins 512.. are never read)
+int launch_denoise(hipStream_t s, DenoiseGeom g, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
+                   long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
+                   const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
+                   float *precast, const DenoiseShard *shard)
+{
+    if (n_blocks <= 0) return 0;
+    DenoiseShard sh;
+    if (shard) sh = *shard;
+    else {
+        sh.ver_block_off = 0;
+        sh.ver_row_off = nullptr;
+        sh.emit_from = calls_before >= 2 ? 0 : 2 - calls_before;
+        sh.emit_to = n_blocks;
+    }
+    if (g.n_fft == 512)
+        return launch_denoise512(s, mode, n_cu, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows,
+                                 table, g.win512, out, precast, sh);
+    return launch_denoise1024(s, mode, k_opt, n_cu, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask,
+                              noise_rows, table, out, precast, sh);
+}
+
+// range / ext0: a shard's event range and the global index of its first block (NULL / 0 when not sharded)
+static void launch_noise_accum(hipStream_t s, DenoiseGeom g, int grid, const short *pcm, long n_blocks,
+                               const DenoiseState *st_in, const int *events, const int *ev_n, const DenoisePlan *plan,
+                               const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
+                               const NoiseAccum &acc, float *rows, const int *range, long ext0)
+{
+    if (g.n_fft == 512)
+        hipLaunchKernelGGL(noise_accum512_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, st_in, events, ev_n,
+                           plan, ver_base, snap_mask, table, g.win512, acc, rows, 10, range, ext0);
+    else
+        hipLaunchKernelGGL(noise_accum_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, st_in, events, ev_n, plan,
+                           ver_base, snap_mask, table, acc, rows, 10, range, ext0);
+}
+
+int launch_noise_estimate(hipStream_t s, DenoiseGeom g, const short *pcm, long n_blocks, const DenoiseState *st_in,
+                          DenoiseState *st_out, const int *events, const int *ev_n, const DenoisePlan *plan,
+                          const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
+                          const NoiseAccum &acc, float *noise_rows)
+{
+    const int grid = n_blocks < kNoiseChunks ? (int)(n_blocks > 0 ? n_blocks : 1) : kNoiseChunks;
+    if (n_blocks > 0)
+        launch_noise_accum(s, g, grid, pcm, n_blocks, st_in, events, ev_n, plan, ver_base, snap_mask, table, acc, noise_rows,
+                           nullptr, 0L);
+    hipLaunchKernelGGL(noise_combine_kernel, dim3(g.n_fft / kCombineBins), dim3(1024), 0, s, plan, st_in, st_out, acc,
+                       noise_rows, grid, (const int *)nullptr, (const float *)nullptr, (float *)nullptr, (float *)nullptr, 1);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// A rank's events through the chunked average (noise_accum_kernel / noise_combine_kernel) in two passes: the first
+// leaves the rank's composed map in `summary` (and every latched row as its partial map), the second -- once the
+// maps of the ranks before it are known -- completes the rows from the average this rank starts from.
+static int shard_accum_grid(long own) { return own < kNoiseChunks ? (int)(own > 0 ? own : 1) : kNoiseChunks; }
+
+int launch_shard_summary(hipStream_t s, DenoiseGeom g, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
+                         const int *events, const int *ev_n, const DenoisePlan *plan, const int *ver_base,
+                         const unsigned long long *snap_mask, const float2 *table, int *range, const NoiseAccum &acc,
+                         float *rows, float *summary)
+{
+    hipLaunchKernelGGL(event_range_kernel, dim3(1), dim3(64), 0, s, events, plan, ver_base, snap_mask, b0, b1, range);
+    const int grid = shard_accum_grid(b1 - b0);
+    launch_noise_accum(s, g, grid, pcm_ext, n_ext, nullptr, events, ev_n, plan, ver_base, snap_mask, table, acc, rows, range,
+                       ext0);
+    hipLaunchKernelGGL(noise_combine_kernel, dim3(g.n_fft / kCombineBins), dim3(1024), 0, s, plan,
+                       (const DenoiseState *)nullptr, (DenoiseState *)nullptr, acc, rows, grid, (const int *)range,
+                       (const float *)nullptr, summary, (float *)nullptr, 0);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_shard_rows(hipStream_t s, DenoiseGeom g, const float *summaries_all, int rank, long b0, long b1,
+                      const DenoisePlan *plan, const int *range, const NoiseAccum &acc, float *a_in, float *rows,
+                      float *last)
+{
+    hipLaunchKernelGGL(fold_summaries_kernel, dim3(g.n_fft / 256), dim3(256), 0, s, summaries_all, rank, a_in);
+    hipLaunchKernelGGL(noise_combine_kernel, dim3(g.n_fft / kCombineBins), dim3(1024), 0, s, plan,
+                       (const DenoiseState *)nullptr, (DenoiseState *)nullptr, acc, rows, shard_accum_grid(b1 - b0), range,
+                       (const float *)a_in, (float *)nullptr, last, 1);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_shard_row0(hipStream_t s, DenoiseGeom g, const float *last_all, int rank, float *rows)
+{
+    hipLaunchKernelGGL(select_row0_kernel, dim3(g.n_fft / 256), dim3(256), 0, s, last_all, rank, rows);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -33,13 +33,9 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
     std::vector<double> hpad(2 * n, 0.0);
     for (int f = 0; f < n_filters; f++)
         for (int i = 0; i < n_taps; i++) hpad[2 * ((size_t)f * n_fft + i)] = taps[(size_t)f * n_taps + i];
-    double *d_h = nullptr, *d_H = nullptr;
-    hipError_t e = hipMalloc((void **)&d_h, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_H, n * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->H, n * sizeof(float2));
+    hipError_t e = hipMalloc((void **)&h->H, n * sizeof(float2));
     const int hl = n_taps - 1 > 0 ? n_taps - 1 : 1;
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&h->hist[i], (size_t)hl * sizeof(short));
-    if (e == hipSuccess) e = hipMemcpy(d_h, hpad.data(), n * 16, hipMemcpyHostToDevice);
     if (e == hipSuccess && n_fft == 8192 && !ctx->conv_tw4096) {
         std::vector<float2> a(4096), b(4096);
         jdsp::fill_conv_twiddles(a.data(), b.data());
@@ -49,13 +45,16 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
         if (e == hipSuccess) e = hipMemcpy(ctx->conv_tw8192, b.data(), 4096 * sizeof(float2), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: alloc", e);
-    if (!rc) rc = jdsp_fft_process_f64_dev(ctx, d_h, d_H, n_fft, n_filters, 1);
-    if (!rc && jdsp::launch_spectrum_to_f32(ctx->stream, (const double2 *)d_H, h->H, (long)n,
-                                            n_fft == 1024 ? 1.0f / 2048.0f : 1.0f))   // 1024: the kernel's 1/2 and 1/1024
-        rc = fail(ctx, JDSP_EHIP, "spectrum_to_f32 launch", hipGetLastError());
-    if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: sync", e);
-    if (d_h) (void)hipFree(d_h);
-    if (d_H) (void)hipFree(d_H);
+    if (!rc) {
+        jdsp::HostCall hc(ctx, "jdsp_fastconv_create");
+        const double *d_h = hc.upload(hpad.data(), n * 16);
+        double *d_H = hc.alloc<double>(n * 16);
+        if (hc.ok()) hc.result(jdsp_fft_process_f64_dev(ctx, d_h, d_H, n_fft, n_filters, 1));
+        if (hc.ok() && jdsp::launch_spectrum_to_f32(ctx->stream, (const double2 *)d_H, h->H, (long)n,
+                                                    n_fft == 1024 ? 1.0f / 2048.0f : 1.0f))   // 1024: the kernel's 1/2 and 1/1024
+            hc.result(fail(ctx, JDSP_EHIP, "spectrum_to_f32 launch", hipGetLastError()));
+        rc = hc.finish();
+    }
     // Uniformly partitioned form of the same convolution (fastconv_kernels.hip): spectra of the 512-tap
     // partitions, each zero-padded to 1024, bins 0..512.  JDSP_FASTCONV_PARTITIONED=0 keeps the 8192-point kernel.
     const char *env = getenv("JDSP_FASTCONV_PARTITIONED");
@@ -66,19 +65,18 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
         for (int f = 0; f < n_filters; f++)
             for (int i = 0; i < n_taps; i++)
                 part[2 * (((size_t)f * P + i / 512) * 1024 + i % 512)] = taps[(size_t)f * n_taps + i];
-        double *d_p = nullptr, *d_P = nullptr;
-        e = hipMalloc((void **)&d_p, rows * 1024 * 16);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_P, rows * 1024 * 16);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->Hp, rows * jdsp::kUpolsRowPitch * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(d_p, part.data(), rows * 1024 * 16, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: partitions", e);
+        if ((e = hipMalloc((void **)&h->Hp, rows * jdsp::kUpolsRowPitch * sizeof(float2))) != hipSuccess)
+            rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: partitions", e);
         if (!rc) rc = jdsp::ensure_stft1024_table_rect(ctx);
-        if (!rc) rc = jdsp_fft_process_f64_dev(ctx, d_p, d_P, 1024, (long)rows, 1);
-        if (!rc && jdsp::launch_spectrum_rows_to_f32(ctx->stream, (const double2 *)d_P, h->Hp, (long)rows))
-            rc = fail(ctx, JDSP_EHIP, "spectrum_rows_to_f32 launch", hipGetLastError());
-        if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: sync", e);
-        if (d_p) (void)hipFree(d_p);
-        if (d_P) (void)hipFree(d_P);
+        if (!rc) {
+            jdsp::HostCall hc(ctx, "jdsp_fastconv_create: partitions");
+            const double *d_p = hc.upload(part.data(), rows * 1024 * 16);
+            double *d_P = hc.alloc<double>(rows * 1024 * 16);
+            if (hc.ok()) hc.result(jdsp_fft_process_f64_dev(ctx, d_p, d_P, 1024, (long)rows, 1));
+            if (hc.ok() && jdsp::launch_spectrum_rows_to_f32(ctx->stream, (const double2 *)d_P, h->Hp, (long)rows))
+                hc.result(fail(ctx, JDSP_EHIP, "spectrum_rows_to_f32 launch", hipGetLastError()));
+            rc = hc.finish();
+        }
         if (!rc) h->n_part = P;
     }
     if (!rc) rc = jdsp_fastconv_reset(h);
@@ -201,27 +199,15 @@ int jdsp_fastconv_process(jdsp_fastconv *h, const int16_t *pcm_host, long n_bloc
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t in_b = (size_t)n_blocks * h->block * 2;
     const size_t out_n = (size_t)(n_out > 0 ? n_out : 1) * h->block * h->n_filters;
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    float *d_pre = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_n * 2);
-    if (e == hipSuccess && precast_host) e = hipMalloc((void **)&d_pre, out_n * 4);
-    int rc = JDSP_OK;
-    if (e != hipSuccess) rc = fail(ctx, JDSP_ENOMEM, "jdsp_fastconv_process: hipMalloc", e);
-    if (!rc && (e = hipMemcpyAsync(d_in, pcm_host, in_b, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_process: H2D", e);
-    if (!rc) rc = jdsp_fastconv_process_dev(h, d_in, n_blocks, d_out, d_pre, nullptr);
+    jdsp::HostCall hc(ctx, "jdsp_fastconv_process");
+    const int16_t *d_in = hc.upload(pcm_host, in_b);
+    int16_t *d_out = hc.alloc<int16_t>(out_n * 2);
+    float *d_pre = precast_host ? hc.alloc<float>(out_n * 4) : nullptr;
+    if (hc.ok()) hc.result(jdsp_fastconv_process_dev(h, d_in, n_blocks, d_out, d_pre, nullptr));
     const size_t got = (size_t)n_out * h->block * h->n_filters;
-    if (!rc && got && (e = hipMemcpyAsync(out_host, d_out, got * 2, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_process: D2H", e);
-    if (!rc && got && precast_host &&
-        (e = hipMemcpyAsync(precast_host, d_pre, got * 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_process: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_process: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pre) (void)hipFree(d_pre);
-    return rc;
+    hc.download(out_host, d_out, got * 2);
+    hc.download(precast_host, d_pre, got * 4);
+    return hc.finish();
 }
 
 #if JDSP_STAMP

@@ -124,29 +124,17 @@ int jdsp_gmm_score(jdsp_gmm *h, const double *feats_host, const int64_t *utt_fir
     if (n_frames < 0 || utt_first_host[0] != 0 || (n_frames > 0 && !feats_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_gmm_score: bad utterance table");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    double *d_feats = nullptr, *d_scores = nullptr;
-    int64_t *d_first = nullptr;
-    int *d_best = nullptr;
     const size_t sz_scores = (size_t)n_utts * h->n_classes * sizeof(double);
-    hipError_t e = hipMalloc(&d_feats, (size_t)(n_frames > 0 ? n_frames : 1) * 12 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_first, (size_t)(n_utts + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&d_scores, sz_scores);
-    if (e == hipSuccess) e = hipMalloc(&d_best, (size_t)n_utts * sizeof(int));
-    if (e == hipSuccess && n_frames > 0)
-        e = hipMemcpyAsync(d_feats, feats_host, (size_t)n_frames * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_first, utt_first_host, (size_t)(n_utts + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    int rc = JDSP_OK;
-    if (e == hipSuccess) rc = jdsp_gmm_score_dev(h, d_feats, n_frames, d_first, n_utts, d_scores, d_best);
-    if (e == hipSuccess && rc == JDSP_OK) e = hipMemcpyAsync(scores_host, d_scores, sz_scores, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && rc == JDSP_OK && best_host)
-        e = hipMemcpyAsync(best_host, d_best, (size_t)n_utts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    else (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_feats); (void)hipFree(d_first); (void)hipFree(d_scores); (void)hipFree(d_best);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_gmm_score", e);
-    return JDSP_OK;
+    jdsp::HostCall hc(ctx, "jdsp_gmm_score");
+    double *d_feats = hc.alloc<double>((size_t)(n_frames > 0 ? n_frames : 1) * 12 * sizeof(double));
+    hc.upload_to(d_feats, feats_host, (size_t)n_frames * 12 * sizeof(double));
+    const int64_t *d_first = hc.upload(utt_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    double *d_scores = hc.alloc<double>(sz_scores);
+    int *d_best = hc.alloc<int>((size_t)n_utts * sizeof(int));
+    if (hc.ok()) hc.result(jdsp_gmm_score_dev(h, d_feats, n_frames, d_first, n_utts, d_scores, d_best));
+    hc.download(scores_host, d_scores, sz_scores);
+    hc.download(best_host, d_best, (size_t)n_utts * sizeof(int));
+    return hc.finish();
 }
 
 int jdsp_hmm_create(jdsp_ctx *ctx, const jdsp_hmm_param *models, int n_models, jdsp_hmm **out)
@@ -245,41 +233,23 @@ int jdsp_hmm_viterbi(jdsp_hmm *h, const double *feats_host, const int64_t *utt_f
     if (n_frames < 0 || utt_first_host[0] != 0 || (n_frames > 0 && !feats_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_hmm_viterbi: bad utterance table");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    double *d_feats = nullptr, *d_scores = nullptr;
-    int64_t *d_first = nullptr;
-    int *d_best = nullptr, *d_path = nullptr;
-    double *d_trellis = nullptr;
     const size_t sz_trellis = (size_t)h->n_models * 6 * (size_t)(n_frames > 0 ? n_frames : 1) * sizeof(double);
     const size_t sz_scores = (size_t)n_utts * h->n_models * sizeof(double);
     const size_t sz_path = (size_t)h->n_models * (size_t)(n_frames > 0 ? n_frames : 1) * sizeof(int);
-    hipError_t e = hipMalloc(&d_feats, (size_t)(n_frames > 0 ? n_frames : 1) * 12 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_first, (size_t)(n_utts + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&d_scores, sz_scores);
-    if (e == hipSuccess) e = hipMalloc(&d_best, (size_t)n_utts * sizeof(int));
-    if (e == hipSuccess && path_host) e = hipMalloc(&d_path, sz_path);
-    if (e == hipSuccess && trellis_host) e = hipMalloc(&d_trellis, sz_trellis);
-    if (e == hipSuccess && n_frames > 0)
-        e = hipMemcpyAsync(d_feats, feats_host, (size_t)n_frames * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_first, utt_first_host, (size_t)(n_utts + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    int rc = JDSP_OK;
-    if (e == hipSuccess) rc = jdsp_hmm_viterbi_dev(h, d_feats, n_frames, d_first, n_utts, d_scores, d_best, d_path, d_trellis);
-    if (e == hipSuccess && rc == JDSP_OK && scores_host)
-        e = hipMemcpyAsync(scores_host, d_scores, sz_scores, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && rc == JDSP_OK && best_host)
-        e = hipMemcpyAsync(best_host, d_best, (size_t)n_utts * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && rc == JDSP_OK && path_host && n_frames > 0)
-        e = hipMemcpyAsync(path_host, d_path, (size_t)h->n_models * n_frames * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && rc == JDSP_OK && trellis_host && n_frames > 0)
-        e = hipMemcpyAsync(trellis_host, d_trellis, (size_t)h->n_models * 6 * n_frames * sizeof(double), hipMemcpyDeviceToHost,
-                           ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    else (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_feats); (void)hipFree(d_first); (void)hipFree(d_scores); (void)hipFree(d_best); (void)hipFree(d_path);
-    (void)hipFree(d_trellis);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_hmm_viterbi", e);
-    return JDSP_OK;
+    jdsp::HostCall hc(ctx, "jdsp_hmm_viterbi");
+    double *d_feats = hc.alloc<double>((size_t)(n_frames > 0 ? n_frames : 1) * 12 * sizeof(double));
+    hc.upload_to(d_feats, feats_host, (size_t)n_frames * 12 * sizeof(double));
+    const int64_t *d_first = hc.upload(utt_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    double *d_scores = hc.alloc<double>(sz_scores);
+    int *d_best = hc.alloc<int>((size_t)n_utts * sizeof(int));
+    int *d_path = path_host ? hc.alloc<int>(sz_path) : nullptr;
+    double *d_trellis = trellis_host ? hc.alloc<double>(sz_trellis) : nullptr;
+    if (hc.ok()) hc.result(jdsp_hmm_viterbi_dev(h, d_feats, n_frames, d_first, n_utts, d_scores, d_best, d_path, d_trellis));
+    hc.download(scores_host, d_scores, sz_scores);
+    hc.download(best_host, d_best, (size_t)n_utts * sizeof(int));
+    hc.download(path_host, d_path, (size_t)h->n_models * n_frames * sizeof(int));
+    hc.download(trellis_host, d_trellis, (size_t)h->n_models * 6 * n_frames * sizeof(double));
+    return hc.finish();
 }
 
 }  // extern "C"

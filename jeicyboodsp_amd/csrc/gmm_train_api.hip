@@ -146,26 +146,12 @@ int jdsp_gmm_train_files(jdsp_gmm_trainer *h, const double *feats_host, const in
             return fail(ctx, JDSP_EINVAL, "jdsp_gmm_train_files: a class's first file needs >= 13 vectors");
         seen[c] = 1;
     }
-    double *d_feats = nullptr;
-    int64_t *d_first = nullptr;
-    int32_t *d_class = nullptr;
-    hipError_t e = hipMalloc(&d_feats, (size_t)n_frames * 12 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_first, (size_t)(n_files + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&d_class, (size_t)n_files * sizeof(int32_t));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_feats, feats_host, (size_t)n_frames * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_first, file_first_host, (size_t)(n_files + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_class, file_class_host, (size_t)n_files * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream);
-    int rc = JDSP_OK;
-    if (e == hipSuccess) rc = jdsp_gmm_train_files_dev(h, d_feats, n_frames, d_first, d_class, n_files);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    else (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_feats); (void)hipFree(d_first); (void)hipFree(d_class);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_gmm_train_files", e);
-    return JDSP_OK;
+    jdsp::HostCall hc(ctx, "jdsp_gmm_train_files");
+    const double *d_feats = hc.upload(feats_host, (size_t)n_frames * 12 * sizeof(double));
+    const int64_t *d_first = hc.upload(file_first_host, (size_t)(n_files + 1) * sizeof(int64_t));
+    const int32_t *d_class = hc.upload(file_class_host, (size_t)n_files * sizeof(int32_t));
+    if (hc.ok()) hc.result(jdsp_gmm_train_files_dev(h, d_feats, n_frames, d_first, d_class, n_files));
+    return hc.finish();
 }
 
 int jdsp_gmm_train_params_dev(jdsp_gmm_trainer *h, jdsp_gmm_train_param *out_dev)

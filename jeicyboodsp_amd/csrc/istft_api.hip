@@ -187,16 +187,14 @@ int jdsp_istft_process(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch,
     if (!rc && out_i16_host) rc = grow(h, 1, n_out * sizeof(int16_t));
     if (!rc && out_f32_host) rc = grow(h, 2, n_out * sizeof(float));
     if (rc) return rc;
-    JDSP_HIP(ctx, hipMemcpyAsync(h->hbuf[0], spec_host, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = jdsp_istft_process_dev(h, (const jdsp_c32 *)h->hbuf[0], row_pitch, n_frames,
-                                out_i16_host ? (int16_t *)h->hbuf[1] : nullptr, out_f32_host ? (float *)h->hbuf[2] : nullptr);
-    if (rc) return rc;
-    if (out_i16_host)
-        JDSP_HIP(ctx, hipMemcpyAsync(out_i16_host, h->hbuf[1], n_out * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (out_f32_host)
-        JDSP_HIP(ctx, hipMemcpyAsync(out_f32_host, h->hbuf[2], n_out * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JDSP_OK;
+    int16_t *d_i16 = out_i16_host ? (int16_t *)h->hbuf[1] : nullptr;
+    float *d_f32 = out_f32_host ? (float *)h->hbuf[2] : nullptr;
+    jdsp::HostCall hc(ctx, "jdsp_istft_process");                       // the buffers are the handle's (grow)
+    hc.upload_to(h->hbuf[0], spec_host, in_bytes);
+    if (hc.ok()) hc.result(jdsp_istft_process_dev(h, (const jdsp_c32 *)h->hbuf[0], row_pitch, n_frames, d_i16, d_f32));
+    hc.download(out_i16_host, d_i16, n_out * sizeof(int16_t));
+    hc.download(out_f32_host, d_f32, n_out * sizeof(float));
+    return hc.finish();
 }
 
 int jdsp_istft_flush(jdsp_istft *h, int16_t *out_i16_host, float *out_f32_host)
@@ -209,15 +207,13 @@ int jdsp_istft_flush(jdsp_istft *h, int16_t *out_i16_host, float *out_f32_host)
     if (n_tail && out_i16_host) rc = grow(h, 1, n_tail * sizeof(int16_t));
     if (!rc && n_tail && out_f32_host) rc = grow(h, 2, n_tail * sizeof(float));
     if (rc) return rc;
-    rc = jdsp_istft_flush_dev(h, n_tail && out_i16_host ? (int16_t *)h->hbuf[1] : nullptr,
-                              n_tail && out_f32_host ? (float *)h->hbuf[2] : nullptr);
-    if (rc) return rc;
-    if (n_tail && out_i16_host)
-        JDSP_HIP(ctx, hipMemcpyAsync(out_i16_host, h->hbuf[1], n_tail * sizeof(int16_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (n_tail && out_f32_host)
-        JDSP_HIP(ctx, hipMemcpyAsync(out_f32_host, h->hbuf[2], n_tail * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return JDSP_OK;
+    int16_t *d_i16 = n_tail && out_i16_host ? (int16_t *)h->hbuf[1] : nullptr;
+    float *d_f32 = n_tail && out_f32_host ? (float *)h->hbuf[2] : nullptr;
+    jdsp::HostCall hc(ctx, "jdsp_istft_flush");
+    hc.result(jdsp_istft_flush_dev(h, d_i16, d_f32));
+    hc.download(out_i16_host, d_i16, n_tail * sizeof(int16_t));
+    hc.download(out_f32_host, d_f32, n_tail * sizeof(float));
+    return hc.finish();
 }
 
 }  // extern "C"

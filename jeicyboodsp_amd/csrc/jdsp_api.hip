@@ -293,16 +293,12 @@ int jdsp_bitrev_table(jdsp_ctx *ctx, int n_fft, int block_len, int16_t *table_ho
         return fail(ctx, JDSP_EINVAL, "jdsp_bitrev_table: bad argument");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const int bits = (int)log2((double)block_len);       // FFTAlgorithm_ver2.cpp:188
-    short *d = nullptr;
-    JDSP_HIP(ctx, hipMalloc((void **)&d, sizeof(short) * (size_t)n_fft));
-    int rc = JDSP_OK;
-    hipError_t e;
-    if (jdsp::launch_bitrev_table(ctx->stream, d, n_fft, bits)) rc = fail(ctx, JDSP_EHIP, "bitrev launch", hipGetLastError());
-    if (!rc && (e = hipMemcpyAsync(table_host, d, sizeof(short) * (size_t)n_fft, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_bitrev_table: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_bitrev_table: sync", e);
-    (void)hipFree(d);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_bitrev_table");
+    short *d = hc.alloc<short>(sizeof(short) * (size_t)n_fft);
+    if (hc.ok() && jdsp::launch_bitrev_table(ctx->stream, d, n_fft, bits))
+        hc.result(fail(ctx, JDSP_EHIP, "bitrev launch", hipGetLastError()));
+    hc.download(table_host, d, sizeof(short) * (size_t)n_fft);
+    return hc.finish();
 }
 
 int jdsp_fft_process_f64_dev(jdsp_ctx *ctx, const double *in_dev, double *out_dev, int n_fft, long batch, int forward)
@@ -331,23 +327,12 @@ int jdsp_fft_process_f64(jdsp_ctx *ctx, const double *in_host, double *out_host,
     if (!in_host || !out_host) return fail(ctx, JDSP_EINVAL, "jdsp_fft_process_f64: NULL buffer");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bytes = sizeof(double) * 2 * (size_t)n_fft * (size_t)batch;
-    double *d_in = nullptr, *d_out = nullptr;
-    JDSP_HIP(ctx, hipMalloc((void **)&d_in, bytes));
-    hipError_t e = hipMalloc((void **)&d_out, bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(d_in);
-        return fail(ctx, JDSP_ENOMEM, "jdsp_fft_process_f64: hipMalloc", e);
-    }
-    int rc = JDSP_OK;
-    if ((e = hipMemcpyAsync(d_in, in_host, bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_fft_process_f64: H2D", e);
-    if (!rc) rc = jdsp_fft_process_f64_dev(ctx, d_in, d_out, n_fft, batch, forward);
-    if (!rc && (e = hipMemcpyAsync(out_host, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_fft_process_f64: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_fft_process_f64: sync", e);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_fft_process_f64");
+    const double *d_in = hc.upload(in_host, bytes);
+    double *d_out = hc.alloc<double>(bytes);
+    if (hc.ok()) hc.result(jdsp_fft_process_f64_dev(ctx, d_in, d_out, n_fft, batch, forward));
+    hc.download(out_host, d_out, bytes);
+    return hc.finish();
 }
 
 int jdsp_dft_direct_f64_dev(jdsp_ctx *ctx, int kind, const void *in_dev, double *inout_dev, int n, long batch)
@@ -375,25 +360,12 @@ int jdsp_dft_direct_f64(jdsp_ctx *ctx, int kind, const void *in_host, double *in
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t out_b = sizeof(double) * 2 * (size_t)n * (size_t)batch;
     const size_t in_b = kind == JDSP_DFT_I16 ? sizeof(int16_t) * (size_t)n * (size_t)batch : out_b;
-    void *d_in = nullptr;
-    double *d_out = nullptr;
-    JDSP_HIP(ctx, hipMalloc(&d_in, in_b));
-    hipError_t e = hipMalloc((void **)&d_out, out_b);
-    if (e != hipSuccess) {
-        (void)hipFree(d_in);
-        return fail(ctx, JDSP_ENOMEM, "jdsp_dft_direct_f64: hipMalloc", e);
-    }
-    int rc = JDSP_OK;
-    if ((e = hipMemcpyAsync(d_in, in_host, in_b, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_out, inout_host, out_b, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_dft_direct_f64: H2D", e);
-    if (!rc) rc = jdsp_dft_direct_f64_dev(ctx, kind, d_in, d_out, n, batch);
-    if (!rc && (e = hipMemcpyAsync(inout_host, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_dft_direct_f64: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_dft_direct_f64: sync", e);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_dft_direct_f64");
+    const char *d_in = hc.upload((const char *)in_host, in_b);
+    double *d_out = hc.upload(inout_host, out_b);
+    if (hc.ok()) hc.result(jdsp_dft_direct_f64_dev(ctx, kind, d_in, d_out, n, batch));
+    hc.download(inout_host, d_out, out_b);
+    return hc.finish();
 }
 
 /* ---- PitchEstimation_method1 -------------------------------------------------- */
@@ -424,31 +396,17 @@ int jdsp_pitch_autocorr(jdsp_ctx *ctx, const int16_t *pcm_host, long n_blocks, c
     if (n_blocks == 0) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)n_blocks;
-    int16_t *d_in = nullptr, *d_prev = nullptr;
-    int32_t *d_arg = nullptr;
-    float *d_max = nullptr, *d_ac = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, n * 1024);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_arg, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_max, n * 4);
-    if (e == hipSuccess && prev_block_host) e = hipMalloc((void **)&d_prev, 1024);
-    if (e == hipSuccess && autocorr_host) e = hipMalloc((void **)&d_ac, n * 2048);
-    hipStream_t s = ctx->stream;
-    int rc = JDSP_OK;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, pcm_host, n * 1024, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && prev_block_host) e = hipMemcpyAsync(d_prev, prev_block_host, 1024, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_autocorr: staging", e);
-    if (!rc) rc = jdsp_pitch_autocorr_dev(ctx, d_in, n_blocks, d_prev, d_arg, d_max, d_ac);
-    if (!rc && (e = hipMemcpyAsync(arg_host, d_arg, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_autocorr: D2H", e);
-    if (!rc && (e = hipMemcpyAsync(rmax_host, d_max, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_autocorr: D2H", e);
-    if (!rc && autocorr_host && (e = hipMemcpyAsync(autocorr_host, d_ac, n * 2048, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_autocorr: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_autocorr: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_prev) (void)hipFree(d_prev);
-    if (d_arg) (void)hipFree(d_arg);
-    if (d_max) (void)hipFree(d_max);
-    if (d_ac) (void)hipFree(d_ac);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_pitch_autocorr");
+    const int16_t *d_in = hc.upload(pcm_host, n * 1024);
+    const int16_t *d_prev = prev_block_host ? hc.upload(prev_block_host, 1024) : nullptr;
+    int32_t *d_arg = hc.alloc<int32_t>(n * 4);
+    float *d_max = hc.alloc<float>(n * 4);
+    float *d_ac = autocorr_host ? hc.alloc<float>(n * 2048) : nullptr;
+    if (hc.ok()) hc.result(jdsp_pitch_autocorr_dev(ctx, d_in, n_blocks, d_prev, d_arg, d_max, d_ac));
+    hc.download(arg_host, d_arg, n * 4);
+    hc.download(rmax_host, d_max, n * 4);
+    hc.download(autocorr_host, d_ac, n * 2048);
+    return hc.finish();
 }
 
 /* ---- STFT ------------------------------------------------------------------ */
@@ -627,24 +585,12 @@ int jdsp_stft_i16_f64(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, in
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t in_bytes = sizeof(int16_t) * (size_t)((n_frames - 1) * hop + n_fft);
     const size_t out_bytes = 2 * sizeof(double) * (size_t)n_frames * (size_t)n_fft;
-    int16_t *d_in = nullptr;
-    double *d_out = nullptr;
-    JDSP_HIP(ctx, hipMalloc((void **)&d_in, in_bytes));
-    hipError_t e = hipMalloc((void **)&d_out, out_bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(d_in);
-        return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_stft_i16_f64: hipMalloc", e);
-    }
-    int rc = JDSP_OK;
-    if ((e = hipMemcpyAsync(d_in, pcm_host, in_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_stft_i16_f64: H2D", e);
-    if (!rc) rc = jdsp_stft_i16_f64_dev(ctx, d_in, n_frames, n_fft, hop, d_out);
-    if (!rc && (e = hipMemcpyAsync(spec_host, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_stft_i16_f64: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_stft_i16_f64: sync", e);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_stft_i16_f64");
+    const int16_t *d_in = hc.upload(pcm_host, in_bytes);
+    double *d_out = hc.alloc<double>(out_bytes);
+    if (hc.ok()) hc.result(jdsp_stft_i16_f64_dev(ctx, d_in, n_frames, n_fft, hop, d_out));
+    hc.download(spec_host, d_out, out_bytes);
+    return hc.finish();
 }
 
 int jdsp_stft_i16(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, int n_fft, int hop, jdsp_c32 *spec_host,
@@ -661,24 +607,12 @@ int jdsp_stft_i16(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, int n_
         return stft_pipelined(ctx, pcm_host, n_frames, n_fft, hop, spec_host);
     const size_t in_bytes = sizeof(int16_t) * (size_t)((n_frames - 1) * hop + n_fft);
     const size_t out_bytes = sizeof(jdsp_c32) * (size_t)n_frames * (size_t)n_fft;
-    int16_t *d_in = nullptr;
-    jdsp_c32 *d_out = nullptr;
-    JDSP_HIP(ctx, hipMalloc((void **)&d_in, in_bytes));
-    hipError_t e = hipMalloc((void **)&d_out, out_bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(d_in);
-        return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_stft_i16: hipMalloc", e);
-    }
-    int rc = JDSP_OK;
-    if ((e = hipMemcpyAsync(d_in, pcm_host, in_bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_stft_i16: H2D", e);
-    if (!rc) rc = jdsp_stft_i16_dev(ctx, d_in, n_frames, n_fft, hop, d_out);
-    if (!rc && (e = hipMemcpyAsync(spec_host, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_stft_i16: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_stft_i16: sync", e);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_stft_i16");
+    const int16_t *d_in = hc.upload(pcm_host, in_bytes);
+    jdsp_c32 *d_out = hc.alloc<jdsp_c32>(out_bytes);
+    if (hc.ok()) hc.result(jdsp_stft_i16_dev(ctx, d_in, n_frames, n_fft, hop, d_out));
+    hc.download(spec_host, d_out, out_bytes);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -76,6 +76,13 @@ struct DenoiseShard {
     long emit_from, emit_to;   // local block range written to `out`
 };
 
+// The frame size a denoise launcher works at: 1024 (blocks of 512), or 512 (blocks of 256) with the handle's halved
+// Hamming(512); win512 is not read at 1024.
+struct DenoiseGeom {
+    int n_fft;
+    const float *win512;
+};
+
 // BeamForming_MVDR_ver1.cpp's state between calls (device memory)
 constexpr int kMvdrTableVersions = 8192;     // 2-microphone MVDR: calls with fewer events than this get their weights from a table (16 KB per version)
 constexpr int kMvnChunks = 128;            // chunks the n-microphone covariance update cuts a call's events into
@@ -120,6 +127,80 @@ int fail(jdsp_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
         if (e_ != hipSuccess) return ::jdsp::fail((ctx), JDSP_EHIP, #call, e_); \
     } while (0)
 
+// The device side of one host-pointer entry: owns the call's device buffers (freed by the destructor) and enqueues its
+// copies on the context's stream.  The first failure sticks -- a failed allocation as JDSP_ENOMEM, a failed copy or
+// sync as JDSP_EHIP, the *_dev twin's or launcher's code through result() -- and every later step is a no-op.
+class HostCall {
+public:
+    HostCall(jdsp_ctx *ctx, const char *entry) : ctx_(ctx), entry_(entry) {}
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    ~HostCall()
+    {
+        for (int i = 0; i < n_; i++) (void)hipFree(buf_[i]);
+    }
+
+    bool ok() const { return rc_ == JDSP_OK; }
+    template <class T> T *alloc(size_t bytes)
+    {
+        if (!ok()) return nullptr;
+        void *p = nullptr;
+        const hipError_t e = n_ < kMaxBufs ? hipMalloc(&p, bytes ? bytes : 1) : hipErrorOutOfMemory;
+        step(JDSP_ENOMEM, "hipMalloc", e);
+        if (p) buf_[n_++] = p;
+        return (T *)p;
+    }
+    template <class T> T *upload(const T *host, size_t bytes)
+    {
+        T *d = alloc<T>(bytes);
+        upload_to(d, host, bytes);
+        return d;
+    }
+    // into memory the handle (or this call) already owns
+    void upload_to(void *dev, const void *host, size_t bytes)
+    {
+        if (ok() && bytes) step(JDSP_EHIP, "H2D", hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx_->stream));
+    }
+    void zero(void *dev, size_t bytes)
+    {
+        if (ok()) step(JDSP_EHIP, "memset", hipMemsetAsync(dev, 0, bytes, ctx_->stream));
+    }
+    void copy_dev(void *dst, const void *src, size_t bytes)
+    {
+        if (ok()) step(JDSP_EHIP, "D2D", hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx_->stream));
+    }
+    // host may be NULL (an output the caller did not ask for): skipped
+    void download(void *host, const void *dev, size_t bytes)
+    {
+        if (ok() && host && bytes)
+            step(JDSP_EHIP, "D2H", hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx_->stream));
+    }
+    // what the *_dev twin or launcher returned (it has set the context's message itself)
+    void result(int rc)
+    {
+        if (ok()) rc_ = rc;
+    }
+    // Synchronises even after a failure: the buffers are freed behind it.
+    int finish()
+    {
+        const hipError_t e = hipStreamSynchronize(ctx_->stream);
+        if (ok()) step(JDSP_EHIP, "sync", e);
+        return rc_;
+    }
+
+private:
+    void step(int code, const char *what, hipError_t e)
+    {
+        if (e != hipSuccess) rc_ = fail(ctx_, code, (std::string(entry_) + ": " + what).c_str(), e);
+    }
+    static constexpr int kMaxBufs = 8;
+    jdsp_ctx *ctx_;
+    const char *entry_;
+    void *buf_[kMaxBufs];
+    int n_ = 0;
+    int rc_ = JDSP_OK;
+};
+
 // stft_kernels.hip
 int stft1024_table_count();
 void fill_stft1024_table(float2 *host_table, int window_kind);
@@ -146,46 +227,32 @@ int launch_dft_direct_f64(hipStream_t stream, int kind, const void *in, double2 
 
 
 // denoise_kernels.hip
-int launch_vad(hipStream_t s, const short *pcm, long n_blocks, const double *w_hi, int use_zcr, unsigned char *flags,
-               long long *dbg_energy, int *dbg_zcr);
-int launch_vad256(hipStream_t s, const short *pcm, long n_blocks, const double *w_hi, unsigned char *flags,
-                  long long *dbg_energy, int *dbg_zcr, int use_zcr = 1);
-int launch_noise_estimate512(hipStream_t s, const short *pcm, long n_blocks, const DenoiseState *st_in,
-                             DenoiseState *st_out, const int *events, const int *ev_n, const DenoisePlan *plan,
-                             const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
-                             const float *win512, const NoiseAccum &acc, float *noise_rows);
-int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm, long n_blocks, long calls_before,
-                      const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
-                      const unsigned long long *snap_mask, const float *noise_rows, const float2 *table,
-                      const float *win512, short *out, float *precast, const DenoiseShard *shard = nullptr);
-int launch_shard_summary512(hipStream_t s, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
-                            const int *events, const int *ev_n, const DenoisePlan *plan, const int *ver_base,
-                            const unsigned long long *snap_mask, const float2 *table, const float *win512, int *range,
-                            const NoiseAccum &acc, float *rows, float *summary);
-int launch_shard_rows512(hipStream_t s, const float *summaries_all, int rank, long b0, long b1, const DenoisePlan *plan,
-                         const int *range, const NoiseAccum &acc, float *a_in, float *rows, float *last);
-int launch_shard_row0_512(hipStream_t s, const float *last_all, int rank, float *rows);
+// block_len 512 | 256
+int launch_vad(hipStream_t s, int block_len, const short *pcm, long n_blocks, const double *w_hi, int use_zcr,
+               unsigned char *flags, long long *dbg_energy, int *dbg_zcr);
 int launch_run_plan(hipStream_t s, const unsigned char *flags, long n_blocks, const int *run_len_in, int *run_len_out,
                     int latch_run, int *ver_base, unsigned long long *snap_mask, int *events, int *ev_n,
                     DenoisePlan *plan);
 int launch_denoise_plan(hipStream_t s, const unsigned char *flags, long n_blocks, const DenoiseState *st_in,
                         DenoiseState *st_out, int *ver_base, unsigned long long *snap_mask, int *events, int *ev_n,
                         DenoisePlan *plan);
-int launch_noise_estimate(hipStream_t s, const short *pcm, long n_blocks, const DenoiseState *st_in,
+int launch_noise_estimate(hipStream_t s, DenoiseGeom g, const short *pcm, long n_blocks, const DenoiseState *st_in,
                           DenoiseState *st_out, const int *events, const int *ev_n, const DenoisePlan *plan,
                           const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
                           const NoiseAccum &acc, float *noise_rows);
-int launch_denoise(hipStream_t s, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks, long calls_before,
-                   const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
+// k_opt: the handle's blocks_per_wave option (1024-point frames only)
+int launch_denoise(hipStream_t s, DenoiseGeom g, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
+                   long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                    const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
                    float *precast, const DenoiseShard *shard = nullptr);
-int launch_shard_summary(hipStream_t s, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
+int launch_shard_summary(hipStream_t s, DenoiseGeom g, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
                          const int *events, const int *ev_n, const DenoisePlan *plan, const int *ver_base,
                          const unsigned long long *snap_mask, const float2 *table, int *range, const NoiseAccum &acc,
                          float *rows, float *summary);
-int launch_shard_rows(hipStream_t s, const float *summaries_all, int rank, long b0, long b1, const DenoisePlan *plan,
-                      const int *range, const NoiseAccum &acc, float *a_in, float *rows, float *last);
-int launch_shard_row0(hipStream_t s, const float *last_all, int rank, float *rows);
+int launch_shard_rows(hipStream_t s, DenoiseGeom g, const float *summaries_all, int rank, long b0, long b1,
+                      const DenoisePlan *plan, const int *range, const NoiseAccum &acc, float *a_in, float *rows,
+                      float *last);
+int launch_shard_row0(hipStream_t s, DenoiseGeom g, const float *last_all, int rank, float *rows);
 int ensure_stft1024_table(jdsp_ctx *ctx);
 int ensure_vad_window(jdsp_ctx *ctx);
 // FP64 Hamming(2 block_len) over the positions a block occupies in the VAD's frame: keep + i, keep = block_len (SS:127-128)
@@ -300,7 +367,7 @@ struct jdsp_denoise {
     long calls = 0;                       // blocks consumed so far (the reference's call counters)
     jdsp::DenoiseState *st[2] = {nullptr, nullptr};
     int cur = 0;                          // st[cur] is the state the next call reads
-    double *w_hi = nullptr;               // second half of the FP64 Hamming window (VAD)
+    double *w_hi = nullptr;               // the VAD's window: second half of the FP64 Hamming(2 block), the context's or w_hi256
     long cap_blocks = 0;                  // workspace capacity (plan arrays)
     unsigned char *flags = nullptr;
     int *ev_n = nullptr, *ver_base = nullptr, *events = nullptr;

@@ -212,28 +212,14 @@ int jdsp_mfcc_frames(jdsp_mfcc *h, const int16_t *pcm_host, long n_samples, cons
         if (st < 0 || st + h->cfg.win_len > n_samples) return fail(ctx, JDSP_EINVAL, "jdsp_mfcc_frames: frame outside pcm");
     }
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    int16_t *d_in = nullptr;
-    int64_t *d_st = nullptr;
-    double *d_out = nullptr;
     const size_t out_b = (size_t)n_frames * h->cfg.n_cep * sizeof(double);
-    hipError_t e = hipMalloc((void **)&d_in, (size_t)n_samples * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_b);
-    if (e == hipSuccess && frame_start_host) e = hipMalloc((void **)&d_st, (size_t)n_frames * 8);
-    int rc = JDSP_OK;
-    if (e != hipSuccess) rc = fail(ctx, JDSP_ENOMEM, "jdsp_mfcc_frames: hipMalloc", e);
-    if (!rc && (e = hipMemcpyAsync(d_in, pcm_host, (size_t)n_samples * 2, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mfcc_frames: H2D", e);
-    if (!rc && frame_start_host &&
-        (e = hipMemcpyAsync(d_st, frame_start_host, (size_t)n_frames * 8, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mfcc_frames: H2D", e);
-    if (!rc) rc = jdsp_mfcc_frames_dev(h, d_in, d_st, n_frames, d_out);
-    if (!rc && (e = hipMemcpyAsync(feats_host, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mfcc_frames: D2H", e);
-    if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_mfcc_frames: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_st) (void)hipFree(d_st);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_mfcc_frames");
+    const int16_t *d_in = hc.upload(pcm_host, (size_t)n_samples * 2);
+    const int64_t *d_st = frame_start_host ? hc.upload(frame_start_host, (size_t)n_frames * 8) : nullptr;
+    double *d_out = hc.alloc<double>(out_b);
+    if (hc.ok()) hc.result(jdsp_mfcc_frames_dev(h, d_in, d_st, n_frames, d_out));
+    hc.download(feats_host, d_out, out_b);
+    return hc.finish();
 }
 
 }  // extern "C"

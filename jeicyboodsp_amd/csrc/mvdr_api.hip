@@ -136,7 +136,7 @@ int jdsp_mvdr_process_dev(jdsp_mvdr *h, const int16_t *left_dev, const int16_t *
     const jdsp::MvdrState *st_in = h->st[h->cur];
     jdsp::MvdrState *st_out = h->st[h->cur ^ 1];
     hipStream_t s = ctx->stream;
-    if (jdsp::launch_vad(s, left_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
+    if (jdsp::launch_vad(s, 512, left_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
         jdsp::launch_run_plan(s, h->flags, n_blocks, &st_in->run_len, &st_out->run_len, 0, h->ver_base, h->snap_mask,
                               h->events, h->ev_n, h->plan) ||
         jdsp::launch_mvdr(s, left_dev, right_dev, n_blocks, h->calls, st_in, st_out, h->events, h->plan, h->ver_base,
@@ -159,29 +159,15 @@ int jdsp_mvdr_process(jdsp_mvdr *h, const int16_t *left_host, const int16_t *rig
     if (!left_host || !right_host || (n_out > 0 && !out_host)) return fail(ctx, JDSP_EINVAL, "jdsp_mvdr_process: NULL buffer");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t in_b = (size_t)n_blocks * 1024, out_b = (size_t)(n_out > 0 ? n_out : 1) * 1024;
-    int16_t *d_l = nullptr, *d_r = nullptr, *d_out = nullptr;
-    float *d_pre = nullptr;
-    hipError_t e = hipMalloc((void **)&d_l, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_r, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_b);
-    if (e == hipSuccess && precast_host) e = hipMalloc((void **)&d_pre, out_b * 2);
-    hipStream_t s = ctx->stream;
-    int rc = JDSP_OK;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_l, left_host, in_b, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_r, right_host, in_b, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_process: staging", e);
-    if (!rc) rc = jdsp_mvdr_process_dev(h, d_l, d_r, n_blocks, d_out, d_pre, nullptr);
-    if (!rc && n_out > 0 && (e = hipMemcpyAsync(out_host, d_out, (size_t)n_out * 1024, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_process: D2H", e);
-    if (!rc && n_out > 0 && precast_host &&
-        (e = hipMemcpyAsync(precast_host, d_pre, (size_t)n_out * 2048, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_process: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_process: sync", e);
-    if (d_l) (void)hipFree(d_l);
-    if (d_r) (void)hipFree(d_r);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pre) (void)hipFree(d_pre);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_mvdr_process");
+    const int16_t *d_l = hc.upload(left_host, in_b);
+    const int16_t *d_r = hc.upload(right_host, in_b);
+    int16_t *d_out = hc.alloc<int16_t>(out_b);
+    float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
+    if (hc.ok()) hc.result(jdsp_mvdr_process_dev(h, d_l, d_r, n_blocks, d_out, d_pre, nullptr));
+    hc.download(out_host, d_out, (size_t)n_out * 1024);
+    hc.download(precast_host, d_pre, (size_t)n_out * 2048);
+    return hc.finish();
 }
 
 /* ---- multi-GPU: one rank's share of one stereo stream ------------------------------------------ */
@@ -201,7 +187,7 @@ int jdsp_mvdr_shard_vad_dev(jdsp_mvdr *h, const int16_t *left_ext_dev, const int
     if (rc) return rc;
     h->sh_ext0 = ext0; h->sh_b0 = b0; h->sh_b1 = b1; h->sh_total = n_total;
     h->sh_left = left_ext_dev; h->sh_right = right_ext_dev;
-    if (jdsp::launch_vad(ctx->stream, left_ext_dev + (b0 - ext0) * 512, b1 - b0, h->w_vad, 0, flags_own_dev, nullptr, nullptr))
+    if (jdsp::launch_vad(ctx->stream, 512, left_ext_dev + (b0 - ext0) * 512, b1 - b0, h->w_vad, 0, flags_own_dev, nullptr, nullptr))
         return fail(ctx, JDSP_EHIP, "vad launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -264,27 +250,19 @@ int jdsp_mvdr_estimate_corr(jdsp_mvdr *h, const int16_t *left_frames_host, const
     for (long i = 0; i < n_frames; i++) ev[(size_t)i] = (int)(2 * i + 1);
     const jdsp::DenoisePlan plan = {(int)n_frames, 0, 0, 0};
     const size_t in_b = (size_t)n_frames * 2048;
-    int16_t *d_l = nullptr, *d_r = nullptr;
-    double *d_tot = nullptr;
     hipStream_t s = ctx->stream;
-    hipError_t e = hipMalloc((void **)&d_l, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_r, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tot, 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_l, left_frames_host, in_b, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_r, right_frames_host, in_b, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->events, ev.data(), sizeof(int) * (size_t)n_frames, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->plan, &plan, sizeof(plan), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_estimate_corr: staging", e);
+    jdsp::HostCall hc(ctx, "jdsp_mvdr_estimate_corr");
+    const int16_t *d_l = hc.upload(left_frames_host, in_b);
+    const int16_t *d_r = hc.upload(right_frames_host, in_b);
+    double *d_tot = hc.alloc<double>(4 * sizeof(double));
+    hc.upload_to(h->events, ev.data(), sizeof(int) * (size_t)n_frames);
+    hc.upload_to(h->plan, &plan, sizeof(plan));
     double tot[4] = {0, 0, 0, 0};
-    if (!rc && jdsp::launch_mvdr_corr_total(s, d_l, d_r, 2 * n_frames, h->st[h->cur], h->events, h->plan, ctx->stft1024_table,
-                                            h->delta, d_tot, h->tile_sums))
-        rc = fail(ctx, JDSP_EHIP, "mvdr corr launch", hipGetLastError());
-    if (!rc && (e = hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_estimate_corr: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_estimate_corr: sync", e);
-    if (d_l) (void)hipFree(d_l);
-    if (d_r) (void)hipFree(d_r);
-    if (d_tot) (void)hipFree(d_tot);
+    if (hc.ok() && jdsp::launch_mvdr_corr_total(s, d_l, d_r, 2 * n_frames, h->st[h->cur], h->events, h->plan,
+                                                ctx->stft1024_table, h->delta, d_tot, h->tile_sums))
+        hc.result(fail(ctx, JDSP_EHIP, "mvdr corr launch", hipGetLastError()));
+    hc.download(tot, d_tot, sizeof(tot));
+    rc = hc.finish();
     if (!rc)
         for (int c = 0; c < 4; c++) corr4_inout_host[c] += tot[c];               // rgdSpatialCorr[..] += (:263-268)
     return rc;
@@ -304,35 +282,24 @@ int jdsp_mvdr_apply(jdsp_mvdr *h, const int16_t *left_host, const int16_t *right
     int rc = mvdr_reserve(h, n_blocks);
     if (rc) return rc;
     const size_t in_b = (size_t)n_blocks * 1024, out_b = (size_t)(n_out > 0 ? n_out : 1) * 1024;
-    int16_t *d_l = nullptr, *d_r = nullptr, *d_out = nullptr;
-    float *d_pre = nullptr;
     hipStream_t s = ctx->stream;
     jdsp::MvdrState *st_in = h->st[h->cur], *st_out = h->st[h->cur ^ 1];
-    hipError_t e = hipMalloc((void **)&d_l, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_r, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_b);
-    if (e == hipSuccess && precast_host) e = hipMalloc((void **)&d_pre, out_b * 2);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_l, left_host, in_b, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_r, right_host, in_b, hipMemcpyHostToDevice, s);
+    jdsp::HostCall hc(ctx, "jdsp_mvdr_apply");
+    const int16_t *d_l = hc.upload(left_host, in_b);
+    const int16_t *d_r = hc.upload(right_host, in_b);
+    int16_t *d_out = hc.alloc<int16_t>(out_b);
+    float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
     // every block uses matrix version 0 = the caller's rgdSpatialCorr; the handle's own matrix and run length carry over
-    if (e == hipSuccess) e = hipMemcpyAsync(h->rver, corr4_host, 4 * sizeof(double), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(h->ver_base, 0, ((size_t)n_blocks / 64 + 1) * sizeof(int), s);
-    if (e == hipSuccess) e = hipMemsetAsync(h->snap_mask, 0, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(st_out, st_in, sizeof(jdsp::MvdrState), hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_apply: staging", e);
-    if (!rc && jdsp::launch_mvdr_apply(s, d_l, d_r, n_blocks, h->calls, st_in, st_out, h->ver_base, h->snap_mask, h->rver,
-                                       h->steer, ctx->stft1024_table, d_out, d_pre))
-        rc = fail(ctx, JDSP_EHIP, "mvdr launch", hipGetLastError());
-    if (!rc && n_out > 0 && (e = hipMemcpyAsync(out_host, d_out, (size_t)n_out * 1024, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_apply: D2H", e);
-    if (!rc && n_out > 0 && precast_host &&
-        (e = hipMemcpyAsync(precast_host, d_pre, (size_t)n_out * 2048, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_apply: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdr_apply: sync", e);
-    if (d_l) (void)hipFree(d_l);
-    if (d_r) (void)hipFree(d_r);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pre) (void)hipFree(d_pre);
+    hc.upload_to(h->rver, corr4_host, 4 * sizeof(double));
+    hc.zero(h->ver_base, ((size_t)n_blocks / 64 + 1) * sizeof(int));
+    hc.zero(h->snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
+    hc.copy_dev(st_out, st_in, sizeof(jdsp::MvdrState));
+    if (hc.ok() && jdsp::launch_mvdr_apply(s, d_l, d_r, n_blocks, h->calls, st_in, st_out, h->ver_base, h->snap_mask, h->rver,
+                                           h->steer, ctx->stft1024_table, d_out, d_pre))
+        hc.result(fail(ctx, JDSP_EHIP, "mvdr launch", hipGetLastError()));
+    hc.download(out_host, d_out, (size_t)n_out * 1024);
+    hc.download(precast_host, d_pre, (size_t)n_out * 2048);
+    rc = hc.finish();
     if (!rc) {
         h->cur ^= 1;
         h->calls += n_blocks;

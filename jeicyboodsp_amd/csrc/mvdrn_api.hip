@@ -162,7 +162,7 @@ int jdsp_mvdrn_process_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stri
     const int in = h->cur, ou = h->cur ^ 1;
     hipStream_t s = ctx->stream;
     if (h->n_fft == 512) {
-        if (jdsp::launch_vad256(s, pcm_dev, n_blocks, h->w_vad, h->flags, nullptr, nullptr, 0) ||
+        if (jdsp::launch_vad(s, 256, pcm_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
             jdsp::launch_run_plan(s, h->flags, n_blocks, h->run_len[in], h->run_len[ou], 0, h->ver_base, h->snap_mask,
                                   h->events, h->ev_n, h->plan) ||
             jdsp::launch_mvdrn512(s, pcm_dev, chan_stride, h->n_mics, n_blocks, h->calls, h->prev[in], h->prev[ou], h->events,
@@ -173,7 +173,7 @@ int jdsp_mvdrn_process_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stri
         h->calls += n_blocks;
         return JDSP_OK;
     }
-    if (jdsp::launch_vad(s, pcm_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
+    if (jdsp::launch_vad(s, 512, pcm_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
         jdsp::launch_run_plan(s, h->flags, n_blocks, h->run_len[in], h->run_len[ou], 0, h->ver_base, h->snap_mask, h->events,
                               h->ev_n, h->plan) ||
         jdsp::launch_mvdrn(s, pcm_dev, chan_stride, h->n_mics, n_blocks, h->calls, h->prev[in], h->prev[ou], h->events,
@@ -198,28 +198,16 @@ int jdsp_mvdrn_process(jdsp_mvdrn *h, const int16_t *pcm_host, long chan_stride,
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const long stride_dev = n_blocks * h->block;               // repack the planes tightly (a multiple of 8)
     const size_t in_b = (size_t)stride_dev * h->n_mics * 2, out_b = (size_t)(n_out > 0 ? n_out : 1) * h->block * 2;
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    float *d_pre = nullptr;
-    hipError_t e = hipMalloc((void **)&d_in, in_b);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_b);
-    if (e == hipSuccess && precast_host) e = hipMalloc((void **)&d_pre, out_b * 2);
-    hipStream_t s = ctx->stream;
-    int rc = JDSP_OK;
-    for (int m = 0; m < h->n_mics && e == hipSuccess; m++)
-        e = hipMemcpyAsync(d_in + (size_t)m * stride_dev, pcm_host + (size_t)m * chan_stride, (size_t)stride_dev * 2,
-                           hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdrn_process: staging", e);
-    if (!rc) rc = jdsp_mvdrn_process_dev(h, d_in, stride_dev, n_blocks, d_out, d_pre, nullptr);
-    if (!rc && n_out > 0 && (e = hipMemcpyAsync(out_host, d_out, (size_t)n_out * h->block * 2, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdrn_process: D2H", e);
-    if (!rc && n_out > 0 && precast_host &&
-        (e = hipMemcpyAsync(precast_host, d_pre, (size_t)n_out * h->block * 4, hipMemcpyDeviceToHost, s)) != hipSuccess)
-        rc = fail(ctx, JDSP_EHIP, "jdsp_mvdrn_process: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_mvdrn_process: sync", e);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_pre) (void)hipFree(d_pre);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_mvdrn_process");
+    int16_t *d_in = hc.alloc<int16_t>(in_b);
+    int16_t *d_out = hc.alloc<int16_t>(out_b);
+    float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
+    for (int m = 0; m < h->n_mics; m++)
+        hc.upload_to(d_in + (size_t)m * stride_dev, pcm_host + (size_t)m * chan_stride, (size_t)stride_dev * 2);
+    if (hc.ok()) hc.result(jdsp_mvdrn_process_dev(h, d_in, stride_dev, n_blocks, d_out, d_pre, nullptr));
+    hc.download(out_host, d_out, (size_t)n_out * h->block * 2);
+    hc.download(precast_host, d_pre, (size_t)n_out * h->block * 4);
+    return hc.finish();
 }
 
 }  // extern "C"

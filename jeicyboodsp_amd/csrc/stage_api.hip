@@ -82,33 +82,6 @@ __global__ __launch_bounds__(256) void gmm_probability_kernel(const double *__re
 
 namespace {
 
-// host -> device -> host round trip shared by the four entries
-struct Staged {
-    jdsp_ctx *ctx;
-    void *d[3] = {nullptr, nullptr, nullptr};
-    explicit Staged(jdsp_ctx *c) : ctx(c) {}
-    ~Staged()
-    {
-        for (void *p : d)
-            if (p) (void)hipFree(p);
-    }
-    int up(int slot, const void *host, size_t bytes)
-    {
-        hipError_t e = hipMalloc(&d[slot], bytes ? bytes : 1);
-        if (e != hipSuccess) return fail(ctx, JDSP_ENOMEM, "stage: hipMalloc", e);
-        if (host && (e = hipMemcpyAsync(d[slot], host, bytes, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
-            return fail(ctx, JDSP_EHIP, "stage: H2D", e);
-        return JDSP_OK;
-    }
-    int down(int slot, void *host, size_t bytes)
-    {
-        hipError_t e = hipMemcpyAsync(host, d[slot], bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "stage: D2H", e);
-        return JDSP_OK;
-    }
-};
-
 // FP64 tables of the sub-step entries, built on first use: rgdFiBins / rgdFilterBank as MelFilterBankInit left
 // them (:131-150), cos(PI i (k-0.5)/C) of :180 and the lifter weights of :189 from the host's libm.
 int ensure_stage_tables(jdsp_mfcc *h)
@@ -154,13 +127,16 @@ int jdsp_mfcc_melfilterbank(jdsp_mfcc *h, const double *abs_host, long n_rows, d
     int rc = ensure_stage_tables(h);
     if (rc) return rc;
     const int NB = h->cfg.n_fft / 2, C = h->cfg.n_chan;
-    Staged s(ctx);
-    if ((rc = s.up(0, abs_host, sizeof(double) * (size_t)n_rows * NB)) || (rc = s.up(1, nullptr, sizeof(double) * (size_t)n_rows * C)))
-        return rc;
-    hipLaunchKernelGGL(jdsp::mel_filterbank_f64_kernel, dim3((unsigned)n_rows), dim3(64), 0, ctx->stream, (const double *)s.d[0],
-                       n_rows, NB, C, h->stage_fi, h->stage_fb, (double *)s.d[1]);
-    if (const hipError_t le = hipGetLastError(); le != hipSuccess) return fail(ctx, JDSP_EHIP, "mel filterbank launch", le);
-    return s.down(1, mel_host, sizeof(double) * (size_t)n_rows * C);
+    jdsp::HostCall hc(ctx, "jdsp_mfcc_melfilterbank");
+    const double *d_abs = hc.upload(abs_host, sizeof(double) * (size_t)n_rows * NB);
+    double *d_mel = hc.alloc<double>(sizeof(double) * (size_t)n_rows * C);
+    if (hc.ok()) {
+        hipLaunchKernelGGL(jdsp::mel_filterbank_f64_kernel, dim3((unsigned)n_rows), dim3(64), 0, ctx->stream, d_abs, n_rows, NB, C,
+                           h->stage_fi, h->stage_fb, d_mel);
+        if (const hipError_t le = hipGetLastError(); le != hipSuccess) hc.result(fail(ctx, JDSP_EHIP, "mel filterbank launch", le));
+    }
+    hc.download(mel_host, d_mel, sizeof(double) * (size_t)n_rows * C);
+    return hc.finish();
 }
 
 int jdsp_mfcc_dct(jdsp_mfcc *h, const double *mel_host, long n_rows, double *cep_inout_host)
@@ -174,14 +150,16 @@ int jdsp_mfcc_dct(jdsp_mfcc *h, const double *mel_host, long n_rows, double *cep
     int rc = ensure_stage_tables(h);
     if (rc) return rc;
     const int C = h->cfg.n_chan, NC = h->cfg.n_cep;
-    Staged s(ctx);
-    if ((rc = s.up(0, mel_host, sizeof(double) * (size_t)n_rows * C)) ||
-        (rc = s.up(1, cep_inout_host, sizeof(double) * (size_t)n_rows * NC)))
-        return rc;
-    hipLaunchKernelGGL(jdsp::dct_f64_kernel, dim3((unsigned)n_rows), dim3(32), 0, ctx->stream, (const double *)s.d[0], n_rows, C,
-                       NC, sqrt(2.0 / C), h->stage_cos, (double *)s.d[1]);
-    if (const hipError_t le = hipGetLastError(); le != hipSuccess) return fail(ctx, JDSP_EHIP, "dct launch", le);
-    return s.down(1, cep_inout_host, sizeof(double) * (size_t)n_rows * NC);
+    jdsp::HostCall hc(ctx, "jdsp_mfcc_dct");
+    const double *d_mel = hc.upload(mel_host, sizeof(double) * (size_t)n_rows * C);
+    double *d_cep = hc.upload(cep_inout_host, sizeof(double) * (size_t)n_rows * NC);
+    if (hc.ok()) {
+        hipLaunchKernelGGL(jdsp::dct_f64_kernel, dim3((unsigned)n_rows), dim3(32), 0, ctx->stream, d_mel, n_rows, C, NC,
+                           sqrt(2.0 / C), h->stage_cos, d_cep);
+        if (const hipError_t le = hipGetLastError(); le != hipSuccess) hc.result(fail(ctx, JDSP_EHIP, "dct launch", le));
+    }
+    hc.download(cep_inout_host, d_cep, sizeof(double) * (size_t)n_rows * NC);
+    return hc.finish();
 }
 
 int jdsp_mfcc_liftering(jdsp_mfcc *h, double *cep_inout_host, long n_rows)
@@ -195,12 +173,15 @@ int jdsp_mfcc_liftering(jdsp_mfcc *h, double *cep_inout_host, long n_rows)
     int rc = ensure_stage_tables(h);
     if (rc) return rc;
     const int NC = h->cfg.n_cep;
-    Staged s(ctx);
-    if ((rc = s.up(0, cep_inout_host, sizeof(double) * (size_t)n_rows * NC))) return rc;
-    hipLaunchKernelGGL(jdsp::lifter_f64_kernel, dim3((unsigned)n_rows), dim3(32), 0, ctx->stream, (double *)s.d[0], n_rows, NC,
-                       h->stage_lift);
-    if (const hipError_t le = hipGetLastError(); le != hipSuccess) return fail(ctx, JDSP_EHIP, "lifter launch", le);
-    return s.down(0, cep_inout_host, sizeof(double) * (size_t)n_rows * NC);
+    jdsp::HostCall hc(ctx, "jdsp_mfcc_liftering");
+    double *d_cep = hc.upload(cep_inout_host, sizeof(double) * (size_t)n_rows * NC);
+    if (hc.ok()) {
+        hipLaunchKernelGGL(jdsp::lifter_f64_kernel, dim3((unsigned)n_rows), dim3(32), 0, ctx->stream, d_cep, n_rows, NC,
+                           h->stage_lift);
+        if (const hipError_t le = hipGetLastError(); le != hipSuccess) hc.result(fail(ctx, JDSP_EHIP, "lifter launch", le));
+    }
+    hc.download(cep_inout_host, d_cep, sizeof(double) * (size_t)n_rows * NC);
+    return hc.finish();
 }
 
 int jdsp_gmm_probability(jdsp_ctx *ctx, const double *feats_host, long n, const double *mean12, const double *cov144,
@@ -220,15 +201,17 @@ int jdsp_gmm_probability(jdsp_ctx *ctx, const double *feats_host, long n, const 
         par[8 + i] = (1.0 / sqrt(2.0 * 3.141592)) * (1.0 / sqrt(cov144[12 * i + i]));
     }
     memcpy(par + 12, eig48, sizeof(double) * 48);
-    Staged s(ctx);
-    int rc;
-    if ((rc = s.up(0, feats_host, sizeof(double) * 12 * (size_t)n)) || (rc = s.up(1, par, sizeof(par))) ||
-        (rc = s.up(2, nullptr, sizeof(double) * (size_t)n)))
-        return rc;
-    hipLaunchKernelGGL(jdsp::gmm_probability_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const double *)s.d[0], n, (const double *)s.d[1], (double *)s.d[2]);
-    if (const hipError_t le = hipGetLastError(); le != hipSuccess) return fail(ctx, JDSP_EHIP, "gmm probability launch", le);
-    return s.down(2, prob_host, sizeof(double) * (size_t)n);
+    jdsp::HostCall hc(ctx, "jdsp_gmm_probability");
+    const double *d_feats = hc.upload(feats_host, sizeof(double) * 12 * (size_t)n);
+    const double *d_par = hc.upload((const double *)par, sizeof(par));
+    double *d_prob = hc.alloc<double>(sizeof(double) * (size_t)n);
+    if (hc.ok()) {
+        hipLaunchKernelGGL(jdsp::gmm_probability_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_feats, n,
+                           d_par, d_prob);
+        if (const hipError_t le = hipGetLastError(); le != hipSuccess) hc.result(fail(ctx, JDSP_EHIP, "gmm probability launch", le));
+    }
+    hc.download(prob_host, d_prob, sizeof(double) * (size_t)n);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -19,23 +19,6 @@ int ensure_lpc_window(jdsp_ctx *ctx, int block_len, const double **w_out)
     return 0;
 }
 
-// host entry staging: device buffers of one call, freed together
-struct Staging {
-    std::vector<void *> bufs;
-    hipError_t err = hipSuccess;
-    void *get(size_t bytes)
-    {
-        void *p = nullptr;
-        if (err == hipSuccess) err = hipMalloc(&p, bytes ? bytes : 1);
-        if (p) bufs.push_back(p);
-        return p;
-    }
-    ~Staging()
-    {
-        for (void *p : bufs) (void)hipFree(p);
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -67,22 +50,17 @@ int jdsp_pitch_lag(jdsp_ctx *ctx, int method, const int16_t *pcm_host, long n_bl
     if (n_blocks == 0) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)n_blocks;
-    Staging st;
-    int16_t *d_in = (int16_t *)st.get(n * 1024), *d_prev = prev_block_host ? (int16_t *)st.get(1024) : nullptr;
-    int32_t *d_arg = arg_host ? (int32_t *)st.get(n * 4) : nullptr;
-    double *d_val = value_host ? (double *)st.get(n * 8) : nullptr, *d_cv = curve_host ? (double *)st.get(n * 4096) : nullptr;
-    hipStream_t s = ctx->stream;
-    hipError_t e = st.err;
-    int rc = JDSP_OK;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, pcm_host, n * 1024, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && d_prev) e = hipMemcpyAsync(d_prev, prev_block_host, 1024, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_lag: staging", e);
-    if (!rc) rc = jdsp_pitch_lag_dev(ctx, method, d_in, n_blocks, d_prev, d_arg, d_val, d_cv);
-    if (!rc && d_arg && (e = hipMemcpyAsync(arg_host, d_arg, n * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_lag: D2H", e);
-    if (!rc && d_val && (e = hipMemcpyAsync(value_host, d_val, n * 8, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_lag: D2H", e);
-    if (!rc && d_cv && (e = hipMemcpyAsync(curve_host, d_cv, n * 4096, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_lag: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_pitch_lag: sync", e);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_pitch_lag");
+    const int16_t *d_in = hc.upload(pcm_host, n * 1024);
+    const int16_t *d_prev = prev_block_host ? hc.upload(prev_block_host, 1024) : nullptr;
+    int32_t *d_arg = arg_host ? hc.alloc<int32_t>(n * 4) : nullptr;
+    double *d_val = value_host ? hc.alloc<double>(n * 8) : nullptr;
+    double *d_cv = curve_host ? hc.alloc<double>(n * 4096) : nullptr;
+    if (hc.ok()) hc.result(jdsp_pitch_lag_dev(ctx, method, d_in, n_blocks, d_prev, d_arg, d_val, d_cv));
+    hc.download(arg_host, d_arg, n * 4);
+    hc.download(value_host, d_val, n * 8);
+    hc.download(curve_host, d_cv, n * 4096);
+    return hc.finish();
 }
 
 /* ---- LPCEstimation ------------------------------------------------------------------------ */
@@ -118,19 +96,15 @@ int jdsp_lpc(jdsp_ctx *ctx, const int16_t *pcm_host, long n_blocks, int block_le
     if (rc || n_blocks == 0) return rc;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)n_blocks, blk_b = (size_t)block_len * 2, ac_b = n * (size_t)(order + 1) * 8, lpc_b = n * (size_t)order * 8;
-    Staging st;
-    int16_t *d_in = (int16_t *)st.get(n * blk_b), *d_prev = prev_block_host ? (int16_t *)st.get(blk_b) : nullptr;
-    double *d_ac = autocorr_host ? (double *)st.get(ac_b) : nullptr, *d_lpc = (double *)st.get(lpc_b);
-    hipStream_t s = ctx->stream;
-    hipError_t e = st.err;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, pcm_host, n * blk_b, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && d_prev) e = hipMemcpyAsync(d_prev, prev_block_host, blk_b, hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_lpc: staging", e);
-    if (!rc) rc = jdsp_lpc_dev(ctx, d_in, n_blocks, block_len, order, d_prev, d_ac, d_lpc);
-    if (!rc && d_ac && (e = hipMemcpyAsync(autocorr_host, d_ac, ac_b, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_lpc: D2H", e);
-    if (!rc && (e = hipMemcpyAsync(lpc_host, d_lpc, lpc_b, hipMemcpyDeviceToHost, s)) != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_lpc: D2H", e);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess && !rc) rc = fail(ctx, JDSP_EHIP, "jdsp_lpc: sync", e);
-    return rc;
+    jdsp::HostCall hc(ctx, "jdsp_lpc");
+    const int16_t *d_in = hc.upload(pcm_host, n * blk_b);
+    const int16_t *d_prev = prev_block_host ? hc.upload(prev_block_host, blk_b) : nullptr;
+    double *d_ac = autocorr_host ? hc.alloc<double>(ac_b) : nullptr;
+    double *d_lpc = hc.alloc<double>(lpc_b);
+    if (hc.ok()) hc.result(jdsp_lpc_dev(ctx, d_in, n_blocks, block_len, order, d_prev, d_ac, d_lpc));
+    hc.download(autocorr_host, d_ac, ac_b);
+    hc.download(lpc_host, d_lpc, lpc_b);
+    return hc.finish();
 }
 
 }  // extern "C"

@@ -18,7 +18,29 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-class Engine:
+class _Handle:
+    """Owns one C handle in `_h`: closed when collected."""
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Child(_Handle):
+    """A stream object of an Engine; `_destroy` is its jdsp_*_destroy."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            type(self)._destroy(self._h)
+            self._h = None
+            if self in self.eng._children:
+                self.eng._children.remove(self)
+
+
+class Engine(_Handle):
     def __init__(self, device=0):
         h = C.c_void_p()
         rc = L.jdsp_create(int(device), C.byref(h))
@@ -38,12 +60,6 @@ class Engine:
                 c.close()
             L.jdsp_destroy(self._h)
             self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _ck(self, rc):
         if rc != 0:
@@ -316,9 +332,10 @@ class Engine:
         return res
 
 
-class Denoiser:
+class Denoiser(_Child):
     """One SS/Wiener audio stream (jdsp_denoise): mirrors main()'s loop of
     SpectralSubtraction_final.cpp:92-113 / WienerFilter_final.cpp:91-112 for batches of blocks."""
+    _destroy = staticmethod(lambda h: L.jdsp_denoise_destroy(h))
     SPECSUB, WIENER = 0, 1
 
     def __init__(self, engine, mode, n_fft=1024, hop=512):
@@ -328,19 +345,6 @@ class Denoiser:
         self._h = h
         self.n_fft, self.block = int(n_fft), L.jdsp_denoise_block_len(h)
         engine._children.append(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.jdsp_denoise_destroy(self._h)
-            self._h = None
-            if self in self.eng._children:
-                self.eng._children.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self.eng._ck(L.jdsp_denoise_reset(self._h))
@@ -449,9 +453,10 @@ class Denoiser:
         return v, e, z
 
 
-class Mfcc:
+class Mfcc(_Child):
     """MFCC front end (jdsp_mfcc): MFCCFeatureExtraction_auto_version1.cpp for batches of frames.
     Keyword arguments override the reference-native configuration (jdsp_mfcc_native_cfg)."""
+    _destroy = staticmethod(lambda h: L.jdsp_mfcc_destroy(h))
 
     def __init__(self, engine, **kw):
         self.eng = engine
@@ -464,19 +469,6 @@ class Mfcc:
         engine._ck(L.jdsp_mfcc_create(engine._h, C.byref(cfg), C.byref(h)))
         self._h = h
         engine._children.append(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.jdsp_mfcc_destroy(self._h)
-            self._h = None
-            if self in self.eng._children:
-                self.eng._children.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def tables(self):
         """MelFilterBankInit's rgdMelFreqs, rgdFiBins, rgdFilterBank."""
@@ -579,23 +571,6 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class _Child:
-    _destroy = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            type(self)._destroy(self._h)
-            self._h = None
-            if self in self.eng._children:
-                self.eng._children.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 class Gmm(_Child):
     """GMM scoring (jdsp_gmm): Recognition() of GMMAlgorithm_Test_Auto_ver2.cpp for batches of utterances.
     `classes`: numpy array of GMM_PARAM records, one per class."""
@@ -680,10 +655,11 @@ class Hmm(_Child):
         return (scores, best, path, trellis) if want_trellis else (scores, best, path)
 
 
-class FastConv:
+class FastConv(_Child):
     """Overlap-save convolver (jdsp_fastconv): AnalySisFreqDomain of
     Fast_Convolution_Based_3DAudio_Impl.cpp:102-177 for batches of blocks.
     taps: [n_taps] or [n_filters, n_taps] float64."""
+    _destroy = staticmethod(lambda h: L.jdsp_fastconv_destroy(h))
 
     def __init__(self, engine, taps, n_fft):
         self.eng = engine
@@ -696,19 +672,6 @@ class FastConv:
         self.block = L.jdsp_fastconv_block_len(h)
         self.hist_blocks = L.jdsp_fastconv_hist_blocks(h)
         engine._children.append(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.jdsp_fastconv_destroy(self._h)
-            self._h = None
-            if self in self.eng._children:
-                self.eng._children.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self.eng._ck(L.jdsp_fastconv_reset(self._h))
@@ -748,9 +711,10 @@ class FastConv:
         return (out, pre) if want_precast else out
 
 
-class Mvdr:
+class Mvdr(_Child):
     """Two-microphone MVDR beamformer (jdsp_mvdr): main()'s loop of BeamForming_MVDR_ver1.cpp:169-231
     for batches of 512-sample blocks per channel."""
+    _destroy = staticmethod(lambda h: L.jdsp_mvdr_destroy(h))
 
     def __init__(self, engine, d_time=0.0):
         self.eng = engine
@@ -758,19 +722,6 @@ class Mvdr:
         engine._ck(L.jdsp_mvdr_create(engine._h, float(d_time), C.byref(h)))
         self._h = h
         engine._children.append(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.jdsp_mvdr_destroy(self._h)
-            self._h = None
-            if self in self.eng._children:
-                self.eng._children.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self.eng._ck(L.jdsp_mvdr_reset(self._h))
@@ -858,9 +809,10 @@ class Mvdr:
         return (out[:n_out * 512], pre[:n_out * 512]) if want_precast else out[:n_out * 512]
 
 
-class MvdrMulti:
+class MvdrMulti(_Child):
     """MVDR generalised to n_mics <= 8 with a per-bin covariance (jdsp_mvdrn, BASELINE config 5).
     pcm: int16 [n_mics, n_blocks * block] (planar); block = n_fft / 2 (512, or 256 for 512-point frames)."""
+    _destroy = staticmethod(lambda h: L.jdsp_mvdrn_destroy(h))
 
     def __init__(self, engine, n_mics, delays=None, loading=0.0, n_fft=1024):
         self.eng = engine
@@ -873,19 +825,6 @@ class MvdrMulti:
         self._h = h
         self.block = L.jdsp_mvdrn_block_len(h)
         engine._children.append(self)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.jdsp_mvdrn_destroy(self._h)
-            self._h = None
-            if self in self.eng._children:
-                self.eng._children.remove(self)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self.eng._ck(L.jdsp_mvdrn_reset(self._h))
