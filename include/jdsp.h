@@ -42,7 +42,8 @@ extern "C" {
  *    jdsp_denoise_vad_trace's energies / counts follow the option's value at the time of the traced call;
  *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added;
  *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added; the time-domain pitch entries
- *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added
+ *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added; the multi-stream IIR equaliser
+ *    jdsp_geq_* and NLMS filter jdsp_nlms_* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -622,6 +623,77 @@ int jdsp_gmm_train_params(jdsp_gmm_trainer *h, jdsp_gmm_train_param *out_host, j
 /* Host only (no GPU needed): the PCA_LEN 4 record the test and Viterbi programs read (GMMTest:216-235) -- the first
  * four eigenvector columns, everything else copied.  in and out: n records. */
 int jdsp_gmm_param_from_train(const jdsp_gmm_train_param *in, int n, jdsp_gmm_param *out);
+
+/* ---- stream filters: layout common to jdsp_geq_* and jdsp_nlms_* ---------------------------- */
+/* A handle filters n_streams independent streams, each with its own state; a call hands every stream its next
+ * n_samples samples.  Stream s occupies elements s*pitch .. s*pitch + n_samples - 1 of every buffer of the call
+ * (a buffer need not extend past the last stream's last sample); pitch >= n_samples and pitch is a multiple of 8,
+ * device pointers are 16-byte aligned.  n_samples need not be a multiple of anything; n_samples == 0 is a successful
+ * no-op.  A stream may be cut into calls anywhere: the results do not depend on the cut, on the number of streams or
+ * on a stream's neighbours.  Everything is FP64 with every product and sum rounded on its own (no fused multiply-add),
+ * as the reference's build rounds them. */
+
+/* ---- 7-band graphic equaliser (7Band_GEQ.cpp) ------------------------------------------------ */
+/* Host only, no GPU: CalcCoefficient (7Band_GEQ.cpp:136-257).  coeff[k] = {{b0, b1, b2}, {0, a1, a2}} of band k at
+ * 44, 125, 250, 500, 2000, 6000, 11313 Hz (:47), 48 kHz, Q 4.318, PI 3.141592; gain_db NULL = the reference's +12,
+ * +12, 0, 0, +3, 0, -12 dB (:51-57).  The reference chooses the boost or cut formulas at compile time; here the branch
+ * follows the run-time sign of the gain (boost when > 0), and the formulas are the reference's as written: V inverted
+ * when below 1 (:139-142), K of the band BELOW in every peaking a2 (:231, :247), the bass-cut branch's K where V is
+ * meant (:173-174).  Only the reference's own gains are pinned to the compiled reference (bit for bit, with the C
+ * library's tan, pow and sqrt); other gains follow the same text.  A non-finite gain is JDSP_EINVAL. */
+int jdsp_geq_design(const double gain_db[7], double coeff[7][2][3]);
+/* ApplyIirGEQ (7Band_GEQ.cpp:259-332) as a cascade of n_sections biquads (1 .. 16; the reference's is 7) over
+ * n_streams (>= 1) streams.  coeff: [n_sections][2][3] as above ([k][1][0] is not read); NULL = jdsp_geq_design(NULL)
+ * and needs n_sections == 7.  Per section, in the reference's order (:280-283):
+ *   d = 0; d += b2 in[t-2]; d -= a2 out[t-2]; d += b1 in[t-1]; d -= a1 out[t-1]; d += b0 in[t];  out[t] = (short)d
+ * Every section's output is cast to int16 before the next section reads it, as the reference's short buffers do; the
+ * cast is the project's: truncate toward zero to int32, keep the low 16 bits (a loud stream wraps with the
+ * reference's gains, exactly as the compiled reference does).  JDSP_EINVAL: n_sections or n_streams out of range, a
+ * non-finite coefficient, or a section with |b0|+|b1|+|b2|+|a1|+|a2| >= 2^15 (the bound keeps every pre-cast value
+ * inside int32, where the cast is defined). */
+typedef struct jdsp_geq jdsp_geq;
+int jdsp_geq_create(jdsp_ctx *ctx, const double *coeff, int n_sections, long n_streams, jdsp_geq **out);
+int jdsp_geq_destroy(jdsp_geq *h);
+int jdsp_geq_reset(jdsp_geq *h);                 /* every stream back to the zero keep (:261-262); enqueued, no sync */
+/* out: int16 per sample; precast (may be NULL): the last section's d before its cast.  The _dev entry allocates
+ * nothing and does not synchronise.  JDSP_EINVAL for a bad pitch or alignment. */
+int jdsp_geq_process_dev(jdsp_geq *h, const int16_t *pcm_dev, long n_samples, long pitch, int16_t *out_dev,
+                         double *precast_dev);
+int jdsp_geq_process(jdsp_geq *h, const int16_t *pcm_host, long n_samples, long pitch, int16_t *out_host,
+                     double *precast_host);
+/* The state between calls, host int16 [n_streams][n_sections + 1][2], {older, newer}: row 0 the input's last two
+ * samples, row k + 1 the last two outputs of section k (which are the input keep of section k + 1, :288-300).
+ * Synchronous. */
+int jdsp_geq_get_state(jdsp_geq *h, int16_t *state_host);
+int jdsp_geq_set_state(jdsp_geq *h, const int16_t *state_host);
+
+/* ---- normalised LMS adaptive filter (NormalLMS.cpp) ------------------------------------------ */
+/* LMSFilter (NormalLMS.cpp:96-136), one sample at a time, for filter_len L = 64, 128 or 256 (the reference: 256), step
+ * mu and regulariser compensation (the reference: 0.0001 both, :32-33).  With x = the kept L-1 samples followed by the
+ * call's input and c the L coefficients (zero at first), sample i is
+ *   sum = sum over j < L of c[L-1-j] x[i+j];  est[i] = (short)sum;  e = reference[i] - est[i] in int;  err[i] = (short)e
+ *   c[m] += ((2.0 x[i+m]) mu) (double)e / (sum over j of x[i+j]^2 + compensation)          for every m < L  (:125)
+ * The reference adds the L products in ascending j; here the order is fixed by L alone: with T = L/64, leaf l < 64 adds
+ * the products j = T l .. T l + T - 1 in ascending j, and a balanced pairwise tree over the 64 leaves follows (adjacent
+ * leaves first).  The sum reaches everything else only through its cast, the norm is an exact integer and the update
+ * is per coefficient with a correctly rounded division, so the two orders can differ only at a sample whose sum lies
+ * within rounding of an integer; on the committed reference streams they do not differ at all.  The cast of est is
+ * the project's (truncate toward zero to int32, keep the low 16 bits); a filter driven past int32 is unspecified, as
+ * in the reference.  precast (may be NULL) = sum.  Every sample gets its outputs: the reference's "first call returns
+ * FALSE" (:132-135) is the caller's business.  JDSP_EINVAL: filter_len, n_streams < 1, non-finite mu or compensation,
+ * a bad pitch or alignment. */
+typedef struct jdsp_nlms jdsp_nlms;
+int jdsp_nlms_create(jdsp_ctx *ctx, int filter_len, double mu, double compensation, long n_streams, jdsp_nlms **out);
+int jdsp_nlms_destroy(jdsp_nlms *h);
+int jdsp_nlms_reset(jdsp_nlms *h);               /* zero coefficients and keep (:98-99); enqueued, no sync */
+int jdsp_nlms_process_dev(jdsp_nlms *h, const int16_t *input_dev, const int16_t *reference_dev, long n_samples,
+                          long pitch, int16_t *est_dev, int16_t *err_dev, double *precast_dev);
+int jdsp_nlms_process(jdsp_nlms *h, const int16_t *input_host, const int16_t *reference_host, long n_samples,
+                      long pitch, int16_t *est_host, int16_t *err_host, double *precast_host);
+/* coefficients: host double [n_streams][L] (rgsdCoefficient, :99); keep: host int16 [n_streams][L-1], oldest first
+ * (rgssKeepInput, :98).  get: either may be NULL.  Synchronous. */
+int jdsp_nlms_get_state(jdsp_nlms *h, double *coef_host, int16_t *keep_host);
+int jdsp_nlms_set_state(jdsp_nlms *h, const double *coef_host, const int16_t *keep_host);
 
 #ifdef __cplusplus
 }

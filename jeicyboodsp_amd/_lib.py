@@ -174,6 +174,21 @@ def _load():
         "jdsp_gmm_train_params_dev": (i, [vp, vp]),
         "jdsp_gmm_train_params": (i, [vp, vp, vp]),
         "jdsp_gmm_param_from_train": (i, [vp, i, vp]),
+        "jdsp_geq_design": (i, [vp, vp]),
+        "jdsp_geq_create": (i, [vp, vp, i, l, C.POINTER(vp)]),
+        "jdsp_geq_destroy": (i, [vp]),
+        "jdsp_geq_reset": (i, [vp]),
+        "jdsp_geq_process_dev": (i, [vp, vp, l, l, vp, vp]),
+        "jdsp_geq_process": (i, [vp, vp, l, l, vp, vp]),
+        "jdsp_geq_get_state": (i, [vp, vp]),
+        "jdsp_geq_set_state": (i, [vp, vp]),
+        "jdsp_nlms_create": (i, [vp, i, C.c_double, C.c_double, l, C.POINTER(vp)]),
+        "jdsp_nlms_destroy": (i, [vp]),
+        "jdsp_nlms_reset": (i, [vp]),
+        "jdsp_nlms_process_dev": (i, [vp, vp, vp, l, l, vp, vp, vp]),
+        "jdsp_nlms_process": (i, [vp, vp, vp, l, l, vp, vp, vp]),
+        "jdsp_nlms_get_state": (i, [vp, vp, vp]),
+        "jdsp_nlms_set_state": (i, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

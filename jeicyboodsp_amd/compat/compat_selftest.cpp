@@ -1,6 +1,6 @@
 // compat_selftest.cpp -- drives the reference-signature functions exactly the way the
 // reference main()s do (one block per call) and dumps what they return, for tests/ to compare
-// with the CPU checker.  usage: compat_selftest <ss|wf|noise|vad|conv|mfcc|mfccsteps|pitch|awgn|fft|dft|gmm|prob|hmm> in.raw out.bin [taps.f64 | params.bin]
+// with the CPU checker.  usage: compat_selftest <ss|wf|noise|vad|conv|mfcc|mfccsteps|pitch|lpc|geq|nlms|awgn|fft|dft|gmm|prob|hmm> in.raw out.bin [taps.f64 | params.bin | ref.raw]
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -94,6 +94,25 @@ int main(int argc, char **argv)
         double feat[12];
         for (size_t b = 0; b + 256 <= pcm.size(); b += 256)
             if (LPCEstimation(&pcm[b], feat)) fwrite(feat, 8, 12, out);
+    } else if (!strcmp(what, "geq")) {
+        // 7Band_GEQ.cpp's main() loop (:118-127): CalcCoefficient once, then blocks of 512
+        short ob[512];
+        CalcCoefficient();
+        for (size_t b = 0; b + 512 <= pcm.size(); b += 512) {
+            ApplyIirGEQ(&pcm[b], ob, 512);
+            fwrite(ob, 2, 512, out);
+        }
+    } else if (!strcmp(what, "nlms")) {
+        // NormalLMS.cpp's main() loop (:69-86): blocks of 1024 of in.raw and of argv[4], the estimate and then the error
+        // written when the call returns true
+        if (argc < 5) return 1;
+        std::vector<short> ref = slurp(argv[4]);
+        short est[1024], err[1024];
+        for (size_t b = 0; b + 1024 <= pcm.size() && b + 1024 <= ref.size(); b += 1024)
+            if (LMSFilter(&pcm[b], &ref[b], est, err)) {
+                fwrite(est, 2, 1024, out);
+                fwrite(err, 2, 1024, out);
+            }
     } else if (!strcmp(what, "awgn")) {
         for (size_t b = 0; b + 512 <= pcm.size(); b += 512) {
             AnalysisAdditiveWhiteGaussianNoise(&pcm[b], 512);

@@ -14,6 +14,8 @@
 //   jdsp_pitch2   in.wav                     PitchEstimation_method2.cpp main()      (:33-67); prints like :96
 //   jdsp_pitch3   in.wav                     PitchEstimation_method3.cpp main()      (:33-67); prints like :96
 //   jdsp_lpc      in.wav  out.lpc            LPCEstimation.cpp main()                (:39-85); raw double[12] per block
+//   jdsp_geq      in.wav  out.raw            7Band_GEQ.cpp main()                    (:91-133)
+//   jdsp_nlms     in.wav ref.raw est.raw err.raw   NormalLMS.cpp main()              (:37-94); ref.raw has no header
 //   jdsp_gmmtest  test_list.txt params.bin   GMMAlgorithm_Test_Auto_ver2.cpp main()  (:46-149)
 //   jdsp_gmmtrain class_lists.txt params.bin GMMAlgorithm_Train_Auto_ver2.cpp main() (:49-172)
 //   jdsp_viterbi  test_list.txt params.bin   Viterbi_version1.cpp main()             (:51-155)
@@ -228,6 +230,47 @@ static int run_lpc(int argc, char **argv)
     return 0;
 }
 
+// 7Band_GEQ.cpp main(): the 44-byte header skipped (:116), blocks of 512 (:43), a short last fread() filtered as a whole
+// block with the stale tail (:121-126).  The keep buffers make the block loop one stream: one call.
+static int run_geq(int argc, char **argv)
+{
+    if (argc != 3) { fprintf(stderr, "usage: jdsp_geq in.wav out.raw\n"); return 1; }
+    FILE *in = open_or_die(argv[1], "rb"), *out = open_or_die(argv[2], "wb");
+    std::vector<short> pcm = read_blocks(in, 512, 44);
+    std::vector<short> res(pcm.size() + 8);
+    jdsp_geq *h = nullptr;
+    CK(jdsp_geq_create(g_ctx, nullptr, 7, 1, &h));                        // CalcCoefficient (:118)
+    CK(jdsp_geq_process(h, pcm.data(), (long)pcm.size(), (long)pcm.size(), res.data(), nullptr));
+    fwrite(res.data(), sizeof(short), pcm.size(), out);
+    jdsp_geq_destroy(h);
+    fclose(in); fclose(out);
+    printf("Processing End\n");
+    return 0;
+}
+
+// NormalLMS.cpp main(): the header skipped on the input only (:65-66), blocks of 1024 (:29) of both files until either
+// ends (:71-79), the first block's outputs not written (:81-85, :132-135).
+static int run_nlms(int argc, char **argv)
+{
+    if (argc != 5) { fprintf(stderr, "usage: jdsp_nlms in.wav ref.raw est.raw err.raw\n"); return 1; }
+    FILE *in = open_or_die(argv[1], "rb"), *rf = open_or_die(argv[2], "rb");
+    FILE *fe = open_or_die(argv[3], "wb"), *fr = open_or_die(argv[4], "wb");
+    std::vector<short> x = read_blocks(in, 1024, 44), ref = read_blocks(rf, 1024, 0);
+    const size_t n = std::min(x.size(), ref.size());
+    std::vector<short> est(n + 8), err(n + 8);
+    jdsp_nlms *h = nullptr;
+    CK(jdsp_nlms_create(g_ctx, 256, 0.0001, 0.0001, 1, &h));              // FILTER_LEN, MU, COMPENSATION (:30-33)
+    CK(jdsp_nlms_process(h, x.data(), ref.data(), (long)n, (long)n, est.data(), err.data(), nullptr));
+    if (n > 1024) {
+        fwrite(est.data() + 1024, sizeof(short), n - 1024, fe);
+        fwrite(err.data() + 1024, sizeof(short), n - 1024, fr);
+    }
+    jdsp_nlms_destroy(h);
+    fclose(in); fclose(rf); fclose(fe); fclose(fr);
+    printf("Processing End\n");
+    return 0;
+}
+
 // ---- GMMAlgorithm_Test_Auto_ver2.cpp / Viterbi_version1.cpp ------------------------------------------
 // Both mains read: argv[1] = a text file naming NUM_OF_CLASS class list files, each naming .mfc files of raw
 // double[12] vectors (what jdsp_mfcc writes); argv[2] = NUM_OF_CLASS parameter records.  The reference's
@@ -382,10 +425,12 @@ int main(int argc, char **argv)
     else if (prog == "jdsp_pitch2") rc = run_pitch_lag(JDSP_PITCH_AMDF, argc, argv);
     else if (prog == "jdsp_pitch3") rc = run_pitch_lag(JDSP_PITCH_ACF, argc, argv);
     else if (prog == "jdsp_lpc") rc = run_lpc(argc, argv);
+    else if (prog == "jdsp_geq") rc = run_geq(argc, argv);
+    else if (prog == "jdsp_nlms") rc = run_nlms(argc, argv);
     else if (prog == "jdsp_gmmtest") rc = run_gmmtest(argc, argv);
     else if (prog == "jdsp_viterbi") rc = run_viterbi(argc, argv);
     else if (prog == "jdsp_gmmtrain") rc = run_gmmtrain(argc, argv);
-    else fprintf(stderr, "unknown program name %s (expected jdsp_fftalg|jdsp_specsub|jdsp_wiener|jdsp_conv3d|jdsp_mfcc|jdsp_mvdr|jdsp_pitch1|jdsp_pitch2|jdsp_pitch3|jdsp_lpc|jdsp_gmmtest|jdsp_viterbi|jdsp_gmmtrain)\n", prog.c_str());
+    else fprintf(stderr, "unknown program name %s (expected jdsp_fftalg|jdsp_specsub|jdsp_wiener|jdsp_conv3d|jdsp_mfcc|jdsp_mvdr|jdsp_pitch1|jdsp_pitch2|jdsp_pitch3|jdsp_lpc|jdsp_geq|jdsp_nlms|jdsp_gmmtest|jdsp_viterbi|jdsp_gmmtrain)\n", prog.c_str());
     jdsp_destroy(g_ctx);
     return rc;
 }

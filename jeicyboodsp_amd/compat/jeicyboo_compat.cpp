@@ -45,6 +45,7 @@ int rgdFiBins[512] = {0};
 double rgdMelFreqs[39] = {0};
 
 static void JeicybooResetLpc(void);
+static void JeicybooResetStreamFilters(void);
 void JeicybooSetBlockLen(int block_len) { g_block_len = block_len; }
 void JeicybooSetDevice(int d) { g_device = d; }
 
@@ -74,6 +75,7 @@ void JeicybooResetStreams(void)
     memset(g_mfcc_keep, 0, sizeof(g_mfcc_keep));
     memset(g_pitch_keep, 0, sizeof(g_pitch_keep));
     JeicybooResetLpc();
+    JeicybooResetStreamFilters();
 }
 
 // ---- FFTAlgorithm_ver2.cpp ----------------------------------------------------------------
@@ -263,6 +265,51 @@ bool LPCEstimation(short *in, double *feature)
     CK(jdsp_lpc(JeicybooContext(), in, 1, 256, 12, g_lpc_keep, nullptr, feature));
     memcpy(g_lpc_keep, in, sizeof(g_lpc_keep));                                                 // :132
     return ++g_lpc_calls > 1;                                                                   // :98,:133-136
+}
+
+// ---- 7Band_GEQ.cpp:136-332 ----------------------------------------------------------------------
+double rgdBandCoeff[7][2][3] = {{{0}}};            // :87
+static jdsp_geq *g_geq = nullptr;
+static bool g_geq_stale = false;                   // rgdBandCoeff was rewritten after the handle was made
+void CalcCoefficient()
+{
+    CK(jdsp_geq_design(nullptr, rgdBandCoeff));
+    g_geq_stale = true;
+}
+void JeicybooGeqCoefficientsChanged(void) { g_geq_stale = true; }
+void ApplyIirGEQ(short *in, short *out, int n)
+{
+    if (!g_geq || g_geq_stale) {                   // new coefficients, the same keep buffers
+        int16_t keep[8][2] = {{0}};
+        if (g_geq) {
+            CK(jdsp_geq_get_state(g_geq, &keep[0][0]));
+            jdsp_geq_destroy(g_geq);
+            g_geq = nullptr;
+        }
+        CK(jdsp_geq_create(JeicybooContext(), &rgdBandCoeff[0][0][0], 7, 1, &g_geq));
+        CK(jdsp_geq_set_state(g_geq, &keep[0][0]));
+        g_geq_stale = false;
+    }
+    CK(jdsp_geq_process(g_geq, in, n, (n + 7) / 8 * 8, out, nullptr));
+}
+
+// ---- NormalLMS.cpp:96-136 -----------------------------------------------------------------------
+static jdsp_nlms *g_nlms = nullptr;
+static int g_nlms_calls = 0;                       // iNumOfIteration (:102)
+bool LMSFilter(short *in, short *ref, short *est, short *err)
+{
+    if (!g_nlms) CK(jdsp_nlms_create(JeicybooContext(), 256, 0.0001, 0.0001, 1, &g_nlms));
+    CK(jdsp_nlms_process(g_nlms, in, ref, 1024, 1024, est, err, nullptr));
+    return ++g_nlms_calls > 1;                                                                  // :105,:132-135
+}
+
+static void JeicybooResetStreamFilters(void)
+{
+    if (g_geq) jdsp_geq_destroy(g_geq);
+    g_geq = nullptr;
+    if (g_nlms) jdsp_nlms_destroy(g_nlms);
+    g_nlms = nullptr;
+    g_nlms_calls = 0;
 }
 
 // ---- GMMAlgorithm_Test_Auto_ver2.cpp / Viterbi_version1.cpp -----------------------------------

@@ -77,6 +77,22 @@ const double *JeicybooLastAutoCorrelation(void);                                
 // jdsp_pitch2 / jdsp_pitch3 (drivers.cpp) are their entry points.
 bool LPCEstimation(short *rgsInputBuffer, double *dLPCFeature);                                 // :87
 
+// ---- 7Band_GEQ.cpp:87-90 -------------------------------------------------------------------
+// rgdBandCoeff is the reference's global (:87): CalcCoefficient fills it with the reference's gains (jdsp_geq_design)
+// and ApplyIirGEQ filters with whatever it holds at the time -- a caller may write its own coefficients into it and
+// call JeicybooGeqCoefficientsChanged().  One stream; the keep buffers are statics as in the reference (:261-262).
+// iFrameCount may be any positive count (the reference's main passes 512).
+extern double rgdBandCoeff[7][2][3];
+void CalcCoefficient();                                                                         // :136
+void ApplyIirGEQ(short *psInputBuffer, short *psOutputBuffer, int iFrameCount);                 // :259
+void JeicybooGeqCoefficientsChanged(void);
+
+// ---- NormalLMS.cpp:35 ----------------------------------------------------------------------
+// One block of 1024 samples (BLOCK_LEN :29) of the input and of the reference signal in, the estimate and the error
+// out; FILTER_LEN 256, MU and COMPENSATION 0.0001 (:30-33).  Coefficients, keep buffer and call counter are statics as
+// in the reference (:98-102); the first call of a stream returns false (:132-135) -- its outputs are computed all the same.
+bool LMSFilter(short *rgsInputBuffer, short *rgsRefBuffer, short *rgdLMSFilteringBuffer, short *rgsError);   // :96
+
 // ---- GMMAlgorithm_Test_Auto_ver2.cpp:29-34,:44 / Viterbi_version1.cpp:30-40,:49 -------------
 // The parameter records are the C ABI's (same layout as the reference's structs).  One call scores one
 // utterance against one record; the class loop of main() (GMMTest:113-127) calls Recognition once per

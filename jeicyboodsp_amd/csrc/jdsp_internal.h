@@ -322,6 +322,14 @@ int launch_pitch_lag(hipStream_t s, int method, const short *pcm, long n_blocks,
 // win: [2 block_len] FP64 window; autocorr ([order + 1] per block) may be NULL
 int launch_lpc(hipStream_t s, const short *pcm, long n_blocks, int block_len, int order, const short *prev_block,
                const double *win, double *autocorr, double *lpc);
+// streamfilter_kernels.hip
+// coeff: [n_sections][2][3] doubles; state: [n_streams][n_sections + 1][2] int16; precast may be NULL
+int launch_geq(hipStream_t s, const short *pcm, long n_streams, long n_samples, long pitch, const double *coeff,
+               int n_sections, short *state, short *out, double *precast);
+// coef: [n_streams][filter_len] doubles; keep: [n_streams][filter_len - 1] int16; precast may be NULL
+int launch_nlms(hipStream_t s, const short *input, const short *refsig, long n_streams, long n_samples, long pitch,
+                int filter_len, double mu, double compensation, double *coef, short *keep, short *est, short *err,
+                double *precast);
 // istft_kernels.hip
 // ws: [n_fft] synthesis window / n_fft; g: [hop] WOLA gain; tails: [n_fft - hop] floats; run_opt 0 = auto
 int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch, long n_frames,
@@ -425,6 +433,23 @@ struct jdsp_gmm_trainer {
     unsigned char *sel = nullptr;         // [frames]: k-means Selection bits
     double *wbuf = nullptr;               // [frames][4]: E-step weights
     long cap_frames = 0;
+};
+
+struct jdsp_geq {
+    jdsp_ctx *ctx = nullptr;
+    int n_sections = 0;
+    long n_streams = 0;
+    double *coeff = nullptr;              // [n_sections][2][3]
+    short *state = nullptr;               // [n_streams][n_sections + 1][2]
+};
+
+struct jdsp_nlms {
+    jdsp_ctx *ctx = nullptr;
+    int filter_len = 0;
+    long n_streams = 0;
+    double mu = 0, compensation = 0;
+    double *coef = nullptr;               // [n_streams][filter_len]
+    short *keep = nullptr;                // [n_streams][filter_len - 1]
 };
 
 struct jdsp_hmm {

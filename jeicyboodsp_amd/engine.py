@@ -102,6 +102,15 @@ class Engine(_Handle):
         analysis_window ("none" / "hamming" / "hann" or -1 / 0 / 1)."""
         return Istft(self, **cfg)
 
+    def geq(self, n_streams, coeff=None):
+        """Multi-stream IIR equaliser (jdsp_geq), 7Band_GEQ.cpp: coeff [n_sections, 2, 3] float64 (1..16 sections), or
+        None for the reference's seven bands (geq_design())."""
+        return Geq(self, n_streams, coeff)
+
+    def nlms(self, n_streams, filter_len=256, mu=1e-4, compensation=1e-4):
+        """Multi-stream normalised LMS filter (jdsp_nlms), NormalLMS.cpp: filter_len 64 | 128 | 256."""
+        return Nlms(self, n_streams, filter_len, mu, compensation)
+
     def synchronize(self):
         self._ck(L.jdsp_synchronize(self._h))
 
@@ -1007,3 +1016,163 @@ class GmmTrainer(_Child):
         st = np.zeros(self.n_classes, GMM_TRAIN_STATS)
         self.eng._ck(L.jdsp_gmm_train_params(self._h, None, _vp(st)))
         return st
+
+
+def geq_design(gain_db=None):
+    """CalcCoefficient of 7Band_GEQ.cpp:136-257 on the host (no GPU): float64 [7, 2, 3] = {{b0, b1, b2}, {0, a1, a2}}
+    per band; gain_db None = the reference's gains."""
+    g = None if gain_db is None else np.ascontiguousarray(gain_db, np.float64)
+    assert g is None or g.shape == (7,)
+    out = np.zeros((7, 2, 3), np.float64)
+    rc = L.jdsp_geq_design(_vp(g) if g is not None else None, _vp(out))
+    if rc != 0:
+        raise JdspError(rc, "jdsp_geq_design: seven finite gains")
+    return out
+
+
+def _pitch_of(n):
+    return max(8, (int(n) + 7) // 8 * 8)
+
+
+def _streams_host(x, n_streams):
+    """int16 [n_streams, n] -> (contiguous [n_streams, pitch] copy, n, pitch), pitch a multiple of 8"""
+    x = np.asarray(x, np.int16)
+    x = x.reshape(n_streams, -1)
+    n = x.shape[1]
+    buf = np.zeros((n_streams, _pitch_of(n)), np.int16)
+    buf[:, :n] = x
+    return buf, n, buf.shape[1]
+
+
+def _streams_dev(x, n_streams, pitch=None):
+    """torch int16 CUDA [n_streams, n] -> (view [n_streams, n] whose row stride is a multiple of 8 and whose base is
+    16-byte aligned, n, pitch); copied into a padded tensor only when the caller's layout is not that already"""
+    import torch
+    assert x.is_cuda and x.dtype == torch.int16
+    x = x.reshape(n_streams, -1) if x.dim() != 2 else x
+    assert x.shape[0] == n_streams
+    n = x.shape[1]
+    st = x.stride(0) if n_streams > 1 else (pitch or _pitch_of(n))
+    ok = (n == 0 or x.stride(1) == 1) and st % 8 == 0 and st >= n and x.data_ptr() % 16 == 0
+    if ok and (pitch is None or st == pitch):
+        return x, n, st
+    pitch = pitch or _pitch_of(n)
+    buf = torch.zeros((n_streams, pitch), dtype=torch.int16, device=x.device)
+    buf[:, :n] = x
+    return buf[:, :n], n, pitch
+
+
+class Geq(_Child):
+    """Cascade of biquads over n_streams independent int16 streams (jdsp_geq): ApplyIirGEQ of 7Band_GEQ.cpp:259-332,
+    every section's output cast to int16.  The state is carried between calls; a stream may be cut anywhere."""
+    _destroy = staticmethod(lambda h: L.jdsp_geq_destroy(h))
+
+    def __init__(self, engine, n_streams, coeff=None):
+        self.eng = engine
+        self.n_streams = int(n_streams)
+        if coeff is None:
+            self.n_sections, c = 7, None
+        else:
+            c = np.ascontiguousarray(coeff, np.float64)
+            assert c.ndim == 3 and c.shape[1:] == (2, 3)
+            self.n_sections = c.shape[0]
+        h = C.c_void_p()
+        engine._ck(L.jdsp_geq_create(engine._h, _vp(c) if c is not None else None, self.n_sections, self.n_streams,
+                                     C.byref(h)))
+        self._h = h
+        engine._children.append(self)
+
+    def reset(self):
+        self.eng._ck(L.jdsp_geq_reset(self._h))
+
+    def state(self):
+        """int16 [n_streams, n_sections + 1, 2]: row 0 the last two inputs, row k + 1 the last two outputs of section k"""
+        st = np.zeros((self.n_streams, self.n_sections + 1, 2), np.int16)
+        self.eng._ck(L.jdsp_geq_get_state(self._h, _vp(st)))
+        return st
+
+    def set_state(self, state):
+        st = np.ascontiguousarray(state, np.int16)
+        assert st.shape == (self.n_streams, self.n_sections + 1, 2)
+        self.eng._ck(L.jdsp_geq_set_state(self._h, _vp(st)))
+
+    def process(self, pcm, want_precast=False, out=None):
+        """pcm: int16 [n_streams, n] (any n).  Returns out int16 [n_streams, n] (and precast float64 [n_streams, n]).
+        out (device tensors only): an int16 [n_streams, pitch] tensor to write into, pitch = pcm's row stride."""
+        if _is_torch(pcm):
+            import torch
+            x, n, pitch = _streams_dev(pcm, self.n_streams)
+            if out is None:
+                out = torch.zeros((self.n_streams, pitch), dtype=torch.int16, device=x.device)
+            assert out.dtype == torch.int16 and out.shape == (self.n_streams, pitch) and out.is_contiguous()
+            pre = torch.zeros((self.n_streams, pitch), dtype=torch.float64, device=x.device) if want_precast else None
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_geq_process_dev(self._h, C.c_void_p(x.data_ptr()), n, pitch, C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(pre.data_ptr()) if want_precast else None))
+            return (out[:, :n], pre[:, :n]) if want_precast else out[:, :n]
+        x, n, pitch = _streams_host(pcm, self.n_streams)
+        out = np.zeros((self.n_streams, pitch), np.int16)
+        pre = np.zeros((self.n_streams, pitch), np.float64) if want_precast else None
+        self.eng._ck(L.jdsp_geq_process(self._h, _vp(x), n, pitch, _vp(out), _vp(pre) if want_precast else None))
+        return (out[:, :n], pre[:, :n]) if want_precast else out[:, :n]
+
+
+class Nlms(_Child):
+    """Normalised LMS filter over n_streams independent (input, reference) stream pairs (jdsp_nlms): LMSFilter of
+    NormalLMS.cpp:96-136 per sample.  Coefficients and the last filter_len - 1 inputs are carried between calls."""
+    _destroy = staticmethod(lambda h: L.jdsp_nlms_destroy(h))
+
+    def __init__(self, engine, n_streams, filter_len=256, mu=1e-4, compensation=1e-4):
+        self.eng = engine
+        self.n_streams, self.filter_len = int(n_streams), int(filter_len)
+        h = C.c_void_p()
+        engine._ck(L.jdsp_nlms_create(engine._h, self.filter_len, float(mu), float(compensation), self.n_streams,
+                                      C.byref(h)))
+        self._h = h
+        engine._children.append(self)
+
+    def reset(self):
+        self.eng._ck(L.jdsp_nlms_reset(self._h))
+
+    def state(self):
+        """(coefficients float64 [n_streams, L], keep int16 [n_streams, L - 1], oldest first)"""
+        cf = np.zeros((self.n_streams, self.filter_len), np.float64)
+        kp = np.zeros((self.n_streams, self.filter_len - 1), np.int16)
+        self.eng._ck(L.jdsp_nlms_get_state(self._h, _vp(cf), _vp(kp)))
+        return cf, kp
+
+    def set_state(self, coefficients, keep):
+        cf = np.ascontiguousarray(coefficients, np.float64)
+        kp = np.ascontiguousarray(keep, np.int16)
+        assert cf.shape == (self.n_streams, self.filter_len) and kp.shape == (self.n_streams, self.filter_len - 1)
+        self.eng._ck(L.jdsp_nlms_set_state(self._h, _vp(cf), _vp(kp)))
+
+    def process(self, x, ref, want_precast=False, out=None):
+        """x, ref: int16 [n_streams, n] (any n).  Returns (est, err) int16 [n_streams, n] (and precast float64).
+        out (device tensors only): (est, err), int16 [n_streams, pitch] tensors to write into, pitch = x's row stride."""
+        if _is_torch(x):
+            import torch
+            assert _is_torch(ref)
+            xv, n, pitch = _streams_dev(x, self.n_streams)
+            rv, rn, _ = _streams_dev(ref, self.n_streams, pitch)
+            assert rn == n
+            if out is None:
+                out = tuple(torch.zeros((self.n_streams, pitch), dtype=torch.int16, device=xv.device) for _ in range(2))
+            est, err = out
+            for t in out:
+                assert t.dtype == torch.int16 and t.shape == (self.n_streams, pitch) and t.is_contiguous()
+            pre = torch.zeros((self.n_streams, pitch), dtype=torch.float64, device=xv.device) if want_precast else None
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_nlms_process_dev(self._h, C.c_void_p(xv.data_ptr()), C.c_void_p(rv.data_ptr()), n, pitch,
+                                                 C.c_void_p(est.data_ptr()), C.c_void_p(err.data_ptr()),
+                                                 C.c_void_p(pre.data_ptr()) if want_precast else None))
+            return (est[:, :n], err[:, :n], pre[:, :n]) if want_precast else (est[:, :n], err[:, :n])
+        xv, n, pitch = _streams_host(x, self.n_streams)
+        rv, rn, _ = _streams_host(ref, self.n_streams)
+        assert rn == n
+        est = np.zeros((self.n_streams, pitch), np.int16)
+        err = np.zeros((self.n_streams, pitch), np.int16)
+        pre = np.zeros((self.n_streams, pitch), np.float64) if want_precast else None
+        self.eng._ck(L.jdsp_nlms_process(self._h, _vp(xv), _vp(rv), n, pitch, _vp(est), _vp(err),
+                                         _vp(pre) if want_precast else None))
+        return (est[:, :n], err[:, :n], pre[:, :n]) if want_precast else (est[:, :n], err[:, :n])

@@ -20,6 +20,12 @@ def split_even(n, rank, world):
     return first, base + (1 if rank < rem else 0)
 
 
+def stream_shard(n_streams, rank, world):
+    """Streams [first, first+count) of a multi-stream filter (Engine.geq, Engine.nlms): streams never exchange
+    anything, so a rank owns whole streams, state included, and there is no halo."""
+    return split_even(n_streams, rank, world)
+
+
 def stft_shard(n_frames, rank, world, n_fft=1024, hop=512):
     """Frames [first, first+count) and the PCM slice they need: frame f covers
     samples [hop*f, hop*f + n_fft), so neighbouring shards overlap by n_fft - hop samples."""

@@ -332,6 +332,41 @@ def main():
                    "LPCEstimation: FP64 Hamming, 13 autocorrelation lags, 12x12 partial-pivot solve; 131,072 blocks of 256 "
                    "(the 65,536 x 512 samples of the pitch legs)",
                    cpu=cpu_rate(lambda: timedomain_ref.lpc_stream(x[:256 * 256], 256, 12), 256))
+    # the sample-serial filters (7Band_GEQ, NormalLMS), batched over streams: one dependent FP64 chain per stream
+    sf = [n for n in ("geq", "nlms") if on(n)]
+    if sf:
+        import streamfilter_ref
+    if "geq" in sf:
+        x = pcm_of(rng, B * 512, 1500.0).reshape(B, 512)
+        xr = rot(torch.from_numpy(x).cuda())
+        g = eng.geq(B)
+        o16 = torch.empty((B, 512), dtype=torch.int16, device="cuda")
+        ms = timed(lambda: g.process(xr(), out=o16), max(a.iters // 4, 3))
+        co = streamfilter_ref.geq_design()
+        report("geq", ms, B, "blocks", 2048, 7 * 512 * 10,
+               "ApplyIirGEQ: 7 biquads, every section cast to int16, bit-exact; 65,536 streams x one reference block of 512 "
+               "(8 lanes per stream, 8 streams per wave, 518 pipeline steps per call); flops are FP64; a single long stream "
+               "runs at the latency of the per-step chain whatever the width of the GPU; cpu_baseline: the Python "
+               "restatement (tests/streamfilter_ref.py)",
+               cpu=cpu_rate(lambda: streamfilter_ref.geq(x[0], co), 1))
+        g.close()
+    if "nlms" in sf:
+        ns, nblk = 4096, 16
+        pairs = [streamfilter_ref.echo_pair(500 + i, nblk * 1024) for i in range(8)]
+        xi = np.stack([pairs[i % 8][0] for i in range(ns)])
+        xf = np.stack([pairs[i % 8][1] for i in range(ns)])
+        xir, xfr = rot(torch.from_numpy(xi).cuda()), rot(torch.from_numpy(xf).cuda())
+        f = eng.nlms(ns)
+        o2 = (torch.empty((ns, nblk * 1024), dtype=torch.int16, device="cuda"),
+              torch.empty((ns, nblk * 1024), dtype=torch.int16, device="cuda"))
+        ms = timed(lambda: f.process(xir(), xfr(), out=o2), 2, rounds=3, spin_ms=0.0)
+        report("nlms", ms, ns * nblk, "blocks", 3 * 2048, 1024 * (2 * 256 + 4 * 256),
+               "LMSFilter: 256 taps, one wave per stream, bit-exact in the documented summation order; 4,096 streams x 16 "
+               "blocks of 1,024 (16,384 serial steps per stream and call); flops are FP64, a division counted as one; a "
+               "single long stream runs at the latency of the per-step chain; cpu_baseline: the numpy restatement "
+               "(tests/streamfilter_ref.py)",
+               cpu=cpu_rate(lambda: streamfilter_ref.nlms(pairs[0][0][:1024], pairs[0][1][:1024]), 1))
+        f.close()
     if on("mvdr"):
         l = pcm_of(rng, B * 512)
         r = pcm_of(rng, B * 512)
