@@ -43,7 +43,7 @@ extern "C" {
  *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added;
  *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added; the time-domain pitch entries
  *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added; the multi-stream IIR equaliser
- *    jdsp_geq_* and NLMS filter jdsp_nlms_* added
+ *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -202,6 +202,53 @@ int  jdsp_istft_flush_dev(jdsp_istft *h, int16_t *out_i16_dev, float *out_f32_de
 int  jdsp_istft_process(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, long n_frames,
                         int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
 int  jdsp_istft_flush(jdsp_istft *h, int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
+
+/* ---- fused STFT masking: PCM -> analysis -> per-bin mask -> synthesis -> PCM ------- */
+/* jdsp_stft_* followed by a multiplication of the spectrum and jdsp_istft_*, as ONE pass in which the spectrum never
+ * reaches memory: a time-frequency mask from an enhancer or separator, a fixed spectral equaliser, a noise gate.
+ * A jdsp_stftmask handle holds ONE output stream, like jdsp_istft; n = n_fft, R = n / hop.  The semantics are the
+ * composition of entries above:
+ *   1. Frame f of a call = pcm[hop f .. hop f + n) * w_a.  w_a, w_s: the numbering of JDSP_WIN_* (JDSP_WIN_NONE =
+ *      rectangular; Hamming / Hann by the formulas of "stft.window").  pcm must hold hop (n_frames - 1) + n samples,
+ *      as jdsp_stft_i16_dev requires: the caller presents the overlap again at a call cut -- the handle keeps no PCM,
+ *      only the overlap-add tail.
+ *   2. X_f = the unnormalised forward DFT of the frame, bins 0..n/2.
+ *   3. Y_f[k] = M_f[k] X_f[k], k = 0..n/2.  M_f = row f of `mask`, mask_pitch ELEMENTS apart: float for
+ *      JDSP_MASK_REAL, jdsp_c32 for JDSP_MASK_COMPLEX.  mask_pitch >= n/2 + 1, or 0: one row for every frame of the
+ *      call (a fixed equaliser; the kernel keeps it in registers).
+ *   4. Synthesis of Y is jdsp_istft's with JDSP_SPEC_HALF: Hermitian by construction (the imaginary parts of bins 0
+ *      and n/2 -- so those of M[0], M[n/2] -- are ignored), 1/n, times w_s, overlap-add in FP32 in ascending frame
+ *      order starting from 0, emission g[t mod hop] * s[t] with g = 1 when normalise == 0, else
+ *      g[i] = 1 / sum_{r<R} w_a[i + r hop] w_s[i + r hop] (create returns JDSP_EINVAL when an entry of that sum is
+ *      below 1e-6 of its largest: jdsp_istft_create's rule), the oracle's cast_i16.  Either output pointer may be
+ *      NULL; with both NULL the stream advances without writing (a shard primes its halo this way,
+ *      jeicyboodsp_amd/sharding.py).  A call of F frames writes F * hop contiguous samples.
+ *   5. flush writes the n - hop samples still in the tail (same g, same cast), then resets the handle.
+ * The output does not depend on how the stream is cut into calls or on the launch geometry, bit for bit.
+ * n_fft 1024, hop 512, JDSP_WIN_HAMMING, JDSP_WIN_NONE, normalise 0 with a mask of ones is SS:218-257 at a zero noise
+ * estimate.
+ * Supported: n_fft = 1024 with hop 1024, 512 or 256; both mask kinds.  (n_fft = 512 is JDSP_EINVAL: DESIGN.md 7.)
+ * Alignment: pcm and out_i16 4 bytes, out_f32 8 bytes, a REAL mask 4 bytes, a COMPLEX mask 8 bytes; anything else, a
+ * mask_pitch in 1..n/2 or n_frames < 0 is JDSP_EINVAL with a jdsp_last_error text.  The _dev entries only enqueue on
+ * the handle's stream (no allocation, no host synchronisation; graph-capturable); the state -- two tails (ping-pong),
+ * the windows and the gain -- is allocated at create.  jdsp_stftmask_process / _flush: host pointers, synchronous
+ * (device buffers grown on demand in the handle). */
+typedef struct jdsp_stftmask jdsp_stftmask;
+enum { JDSP_MASK_REAL = 0, JDSP_MASK_COMPLEX = 1 };
+typedef struct { int n_fft, hop, analysis_window, synthesis_window, normalise, mask_kind; } jdsp_stftmask_cfg;
+int  jdsp_stftmask_create(jdsp_ctx *ctx, const jdsp_stftmask_cfg *cfg, jdsp_stftmask **out);
+int  jdsp_stftmask_destroy(jdsp_stftmask *h);
+int  jdsp_stftmask_reset(jdsp_stftmask *h);
+/* "frames_per_wave": consecutive frames one wavefront walks (0 = auto: about one round of resident waves, at least
+ * 4 (R - 1)); values below max(R - 1, 1) are raised to it.  Every value gives the same output bit for bit. */
+int  jdsp_stftmask_set_option(jdsp_stftmask *h, const char *name, long value);
+long jdsp_stftmask_samples_out(const jdsp_stftmask *h, long n_frames);
+int  jdsp_stftmask_process_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void *mask_dev, long mask_pitch,
+                               long n_frames, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_stftmask_flush_dev(jdsp_stftmask *h, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_stftmask_process(jdsp_stftmask *h, const int16_t *pcm_host, const void *mask_host, long mask_pitch,
+                           long n_frames, int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
+int  jdsp_stftmask_flush(jdsp_stftmask *h, int16_t *out_i16_host, float *out_f32_host);  /* host path, synchronous */
 
 /* ---- spectral subtraction / Wiener filter ------------------------------------- */
 /* One jdsp_denoise object holds everything the reference keeps in static locals

@@ -26,7 +26,14 @@ class IstftCfg(C.Structure):
                 ("analysis_window", C.c_int)]
 
 
+class StftMaskCfg(C.Structure):
+    """jdsp_stftmask_cfg (include/jdsp.h)"""
+    _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("analysis_window", C.c_int), ("synthesis_window", C.c_int),
+                ("normalise", C.c_int), ("mask_kind", C.c_int)]
+
+
 SPEC_FULL, SPEC_HALF = 0, 1
+MASK_REAL, MASK_COMPLEX = 0, 1
 WIN_NONE, WIN_HAMMING, WIN_HANN = -1, 0, 1
 
 
@@ -164,6 +171,15 @@ def _load():
         "jdsp_istft_flush_dev": (i, [vp, vp, vp]),
         "jdsp_istft_process": (i, [vp, vp, l, l, vp, vp]),
         "jdsp_istft_flush": (i, [vp, vp, vp]),
+        "jdsp_stftmask_create": (i, [vp, vp, C.POINTER(vp)]),
+        "jdsp_stftmask_destroy": (i, [vp]),
+        "jdsp_stftmask_reset": (i, [vp]),
+        "jdsp_stftmask_set_option": (i, [vp, C.c_char_p, l]),
+        "jdsp_stftmask_samples_out": (l, [vp, l]),
+        "jdsp_stftmask_process_dev": (i, [vp, vp, vp, l, l, vp, vp]),
+        "jdsp_stftmask_flush_dev": (i, [vp, vp, vp]),
+        "jdsp_stftmask_process": (i, [vp, vp, vp, l, l, vp, vp]),
+        "jdsp_stftmask_flush": (i, [vp, vp, vp]),
         "jdsp_gmm_train_create": (i, [vp, i, C.POINTER(vp)]),
         "jdsp_gmm_train_destroy": (i, [vp]),
         "jdsp_gmm_train_reset": (i, [vp]),

@@ -336,6 +336,12 @@ int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const fl
                  const float *ws, const float *g, const float *tail_in, float *tail_out, short *out, float *out_f32,
                  const float2 *table, int run_opt);
 int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32);
+// stftmask_kernels.hip (n_fft 1024)
+// mask: rows of float or float2 (complex_mask), pitch elements apart (0: one row); wa: [1024] analysis window / 2;
+// ws: [1024] synthesis window; g: [hop] emission gain; tails: [1024 - hop] floats; run_opt 0 = auto
+int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask, long pitch,
+                    long n_frames, const float *wa, const float *ws, const float *g, const float *tail_in,
+                    float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt);
 // mfcc_kernels.hip
 // ---- GMM / HMM (gmm_kernels.hip) ----
 // packed per-GMM record (doubles): alpa[4], mean[4][4], var[4][4], coef[4][4], eig[4][12][4], and for the

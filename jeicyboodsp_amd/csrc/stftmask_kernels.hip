@@ -1,0 +1,282 @@
+// stftmask_kernels.hip -- fused STFT masking (gfx950): PCM -> analysis window -> forward transform -> per-bin mask ->
+// inverse transform -> synthesis window -> overlap-add -> (short), one streaming pass (include/jdsp.h, jdsp_stftmask_*).
+// The spectrum never leaves the wave: what the unfused route (jdsp_stft_* -> multiply -> jdsp_istft_*) writes to HBM,
+// multiplies there and reads back stays in registers and the wave's LDS scratch.
+//
+// The kernel joins two that exist.  The frame is denoise_frame_pairs' (denoise_kernels.hip): one 512-point complex
+// transform of the packed real frame, the split with every mirror pair of bins owned by one lane (frame_io.h,
+// PairTwiddles), the per-bin stage, the inverse pre-split and one inverse transform -- with a mask value streamed from
+// HBM where the denoiser evaluates a gain from a noise estimate.  Everything after the frame is istft_run_kernel's
+// (istft_kernels.hip): lane l holds the frame's samples 2 l + 128 d, +1 in register d, so a hop of 1024 / R samples is
+// HR = 8 / R registers and the overlap-add is a register shift; every output sample is the FP32 sum of its frames in
+// ascending order starting from 0, whatever the call cuts or the launch geometry; a wave whose run starts at frame
+// j0 > 0 recomputes the R - 1 frames in front of it (their PCM and mask rows are read again), only the wave with j0 = 0
+// reads the tail carried in the handle, and the wave that owns the call's last frame writes the other ping-pong tail.
+//
+// Mask.  Lane l owns the bins m and m + 512 of m = l + 64 d, d < 5.  Bin m <= 319 takes M[m]; bin m + 512 lies above
+// n/2, where the caller gives no value: Y[1024 - k] = conj(Y[k]) (the output is real), so it takes M[512 - m],
+// conjugated for a complex mask.  Lane 0's d = 0 item holds bins 0 and 512, whose imaginary mask parts are ignored.
+// The items of d = 3 and 4 cover the bins 193..319 from both sides (frame_io.h); both sides use the same M[k].  A lane
+// reads M[l + 64 d] and M[512 - l - 64 d]: ten coalesced loads per frame, bins 193..319 twice (the second from L2).
+// The 1/1024 of the inverse transform is folded into the mask value (a power of two: exact).
+//
+// PCM.  Frame j + 1 starts one hop after frame j, and a hop is HR registers of the frame's layout, so the raw sample
+// pairs shift down like the overlap-add does: a wave reads every sample of its run once (HR dwords per lane and frame)
+// plus the R - 1 halo frames.
+#include "jdsp_internal.h"
+#include "frame_io.h"
+
+namespace jdsp {
+
+#ifndef JDSP_STFTMASK_RESIDENT
+// Waves per SIMD the launch plans for and __launch_bounds__ asks for.  A wave holds two mask rows (the frame's and
+// the prefetched one: 20 registers REAL, 40 COMPLEX), both windows, the gain, the overlap-add sums, the raw PCM and
+// the transform's twiddles: 162-164 registers with a real mask, 196 with a complex one, nothing in scratch
+// (profiles/r08_stftmask_isa.txt).  That is past the 128 of four waves per SIMD and, for the complex mask, past the
+// 168 of three; two (256 registers) hold every instantiation, and two is what istft_run_kernel measured fastest for
+// the same overlap-add and store pattern (profiles/r04_istft_launch_ab.txt).
+#define JDSP_STFTMASK_RESIDENT 2
+#endif
+#ifndef JDSP_ISTFT_MIN_RUN_PER_HALO
+#define JDSP_ISTFT_MIN_RUN_PER_HALO 4   // shortest run, in halo frames: the value launch_istft uses (istft_kernels.hip)
+#endif
+
+namespace {
+
+typedef float sm_f32x2 __attribute__((ext_vector_type(2)));
+
+// one mask row as a lane holds it: lo[d] for bin l + 64 d, hi[d] for bin l + 64 d + 512 (the value of bin 512 - l - 64 d)
+template <int CPX> struct MaskRow;
+template <> struct MaskRow<0> { float lo[5], hi[5]; };
+template <> struct MaskRow<1> { float2 lo[5], hi[5]; };
+
+// nontemporal: a mask row is read once
+__device__ __forceinline__ void mask_load(MaskRow<0> &m, const void *row, int lane)
+{
+    const float *r = static_cast<const float *>(row);
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        m.lo[d] = __builtin_nontemporal_load(r + lane + 64 * d);
+        m.hi[d] = __builtin_nontemporal_load(r + 512 - lane - 64 * d);
+    }
+}
+__device__ __forceinline__ void mask_load(MaskRow<1> &m, const void *row, int lane)
+{
+    const sm_f32x2 *r = static_cast<const sm_f32x2 *>(row);
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        const sm_f32x2 a = __builtin_nontemporal_load(r + lane + 64 * d);
+        const sm_f32x2 b = __builtin_nontemporal_load(r + 512 - lane - 64 * d);
+        m.lo[d] = make_float2(a.x, a.y);
+        m.hi[d] = make_float2(b.x, b.y);
+    }
+}
+
+// raw row -> the factors the frame multiplies by: M / 1024, the upper bins' conjugated, no imaginary part at DC and n/2
+__device__ __forceinline__ void mask_prepare(MaskRow<0> &m, const MaskRow<0> &raw, int)
+{
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        m.lo[d] = raw.lo[d] * (1.0f / 1024.0f);
+        m.hi[d] = raw.hi[d] * (1.0f / 1024.0f);
+    }
+}
+__device__ __forceinline__ void mask_prepare(MaskRow<1> &m, const MaskRow<1> &raw, int lane)
+{
+    const float c = 1.0f / 1024.0f;
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        const bool real = d == 0 && lane == 0;
+        m.lo[d] = make_float2(raw.lo[d].x * c, real ? 0.0f : raw.lo[d].y * c);
+        m.hi[d] = make_float2(raw.hi[d].x * c, real ? 0.0f : -(raw.hi[d].y * c));
+    }
+}
+
+__device__ __forceinline__ float2 mask_mul(float2 x, float m) { return make_float2(x.x * m, x.y * m); }
+__device__ __forceinline__ float2 mask_mul(float2 x, float2 m)
+{
+    // spelled with fmaf: the same operations in every instantiation
+    return make_float2(__builtin_fmaf(-x.y, m.y, x.x * m.x), __builtin_fmaf(x.y, m.x, x.x * m.y));
+}
+
+// One frame: y[d] = w_s * IDFT(M * DFT(w_a * frame)) at the samples (2 lane + 128 d, +1).  wa = w_a / 2 (the forward
+// split's 1/2, frame_io.h), m as mask_prepare left it (so the 1/1024 is in), ws = w_s.
+template <int CPX>
+__device__ __forceinline__ void stftmask_frame(const unsigned int (&raw)[8], const float2 (&wa)[8], const WaveTwiddles &tw,
+                                               const PairTwiddles &pw, float2 *lds, int lane, const MaskRow<CPX> &m,
+                                               const float2 (&ws)[8], float2 (&y)[8])
+{
+    float2 v[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const float2 s = unpack_i16x2(raw[r]);
+        v[r] = make_float2(s.x * wa[r].x, s.y * wa[r].y);
+    }
+    wave_fft512<false>(v, lds, lane, tw);
+    float2 zr[5], ret[4];
+    wave_lds_fence();                                            // the transform's last exchange reads are done
+    pair_fetch_lds(v, lds, lane, zr);
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        const float2 e = cadd_conj(v[d], zr[d]);
+        const float2 o = csub_conj_mj(v[d], zr[d]);
+        const float2 p = cmul(pw.w[d], o);
+        const float2 lo = mask_mul(cadd(e, p), m.lo[d]);         // Y[m] / 1024
+        const float2 hi = mask_mul(csub(e, p), m.hi[d]);         // Y[m + 512] / 1024
+        if (d < 4) presplit_inv_pair(lo, hi, pw.w[d], y[d], ret[d]);
+        else y[d] = presplit_inv_reg(lo, hi, pw.w[d]);
+    }
+    pair_return_lds(ret, lds, lane, y);
+    wave_fft512<true>(y, lds, lane, tw);
+    wave_lds_fence();                                            // the scratch is free for the next frame
+#pragma unroll
+    for (int d = 0; d < 8; d++) y[d] = make_float2(y[d].x * ws[d].x, y[d].y * ws[d].y);
+}
+
+}  // namespace
+
+struct StftMaskArgs {
+    const short *pcm;         // hop (n_frames - 1) + 1024 samples
+    const void *mask;         // rows of float (REAL) or float2 (COMPLEX), bins 0..512
+    long pitch, n_frames;     // pitch in elements; 0: one row for every frame
+    const float *wa;          // [1024] w_a[i] / 2
+    const float *ws;          // [1024] w_s[i]
+    const float *g;           // [hop]  emission gain
+    const float *tail_in;     // [1024 - hop] partial sums of the samples after the last emitted one
+    float *tail_out;
+    short *out;               // may be NULL
+    float *out_f32;           // may be NULL
+    int run;
+};
+
+template <int R, int CPX>
+__global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kernel(StftMaskArgs a,
+                                                                                  const float2 *__restrict__ table)
+{
+    constexpr int HR = 8 / R;                                   // registers per hop
+    constexpr int HOP = 1024 / R;
+    constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
+    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * a.run;
+    if (j0 >= a.n_frames) return;
+    const long j1 = j0 + a.run < a.n_frames ? j0 + a.run : a.n_frames;
+    // the halo: frames j0 - R + 1 .. j0 - 1 are transformed and added, not emitted (all >= 0: the launch keeps
+    // run >= R - 1)
+    const long js = j0 == 0 ? 0 : j0 - (R - 1);
+
+    WaveTwiddles tw;
+    load_wave_twiddles(tw, table, lane);
+    PairTwiddles pw;
+    load_pair_twiddles(pw, table, lane);
+    float2 wa[8], ws[8], g[HR];
+    {
+        const float2 *wa_t = reinterpret_cast<const float2 *>(a.wa);
+        const float2 *ws_t = reinterpret_cast<const float2 *>(a.ws);
+        const float2 *g_t = reinterpret_cast<const float2 *>(a.g);
+#pragma unroll
+        for (int d = 0; d < 8; d++) { wa[d] = wa_t[lane + 64 * d]; ws[d] = ws_t[lane + 64 * d]; }
+#pragma unroll
+        for (int d = 0; d < HR; d++) g[d] = g_t[lane + 64 * d];
+    }
+
+    float2 acc[8], y[8];
+#pragma unroll
+    for (int d = 0; d < 8; d++) acc[d] = make_float2(0.f, 0.f);
+    if (j0 == 0) {
+        const float2 *tl = reinterpret_cast<const float2 *>(a.tail_in);
+#pragma unroll
+        for (int d = 0; d < 8 - HR; d++) acc[d] = tl[lane + 64 * d];
+    }
+
+    const char *mask = static_cast<const char *>(a.mask);
+    const size_t row_bytes = (size_t)a.pitch * kElem;
+    unsigned int raw[8], nraw[HR];
+    MaskRow<CPX> m, nm;
+    {
+        const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + js * HOP) + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+        mask_load(nm, mask + (size_t)js * row_bytes, lane);
+        mask_prepare(m, nm, lane);
+    }
+    for (long j = js; j < j1; j++) {
+        // frame j + 1's new hop of PCM and its mask row, needed one iteration from now: unguarded loads at a clamped
+        // frame (past the wave's run they are never used), raw until they are staged below
+        const long jn = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
+        {
+            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + jn * HOP) + 64 * (8 - HR) + lane;
+#pragma unroll
+            for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
+        }
+        if (a.pitch) mask_load(nm, mask + (size_t)jn * row_bytes, lane);     // pitch 0: the row stays in registers
+        stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, ws, y);
+#pragma unroll
+        for (int d = 0; d < 8; d++) acc[d] = make_float2(acc[d].x + y[d].x, acc[d].y + y[d].y);
+        float2 o[HR];
+#pragma unroll
+        for (int d = 0; d < HR; d++) o[d] = make_float2(g[d].x * acc[d].x, g[d].y * acc[d].y);
+        // stage the prefetched values before this frame's stores: vmcnt counts loads and stores in issue order, and a
+        // wait for them at the top of the next iteration would also wait for these stores (istft_run_kernel)
+#pragma unroll
+        for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
+#pragma unroll
+        for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
+        if (a.pitch) mask_prepare(m, nm, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j >= j0) {
+            if (a.out) {
+                unsigned int *dst = reinterpret_cast<unsigned int *>(a.out + j * HOP) + lane;
+#pragma unroll
+                for (int d = 0; d < HR; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
+            }
+            if (a.out_f32) {
+                sm_f32x2 *dst = reinterpret_cast<sm_f32x2 *>(a.out_f32 + j * HOP) + lane;
+#pragma unroll
+                for (int d = 0; d < HR; d++) {
+                    const sm_f32x2 w = {o[d].x, o[d].y};
+                    __builtin_nontemporal_store(w, dst + 64 * d);
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < 8; d++) acc[d] = d + HR < 8 ? acc[d + HR] : make_float2(0.f, 0.f);
+        if (j == a.n_frames - 1) {
+            float2 *tl = reinterpret_cast<float2 *>(a.tail_out);
+#pragma unroll
+            for (int d = 0; d < 8 - HR; d++) tl[lane + 64 * d] = acc[d];
+        }
+    }
+}
+
+template <int R>
+static void launch_kind(hipStream_t s, int cpx, long grid, const StftMaskArgs &a, const float2 *table)
+{
+    if (cpx) hipLaunchKernelGGL((stftmask_run_kernel<R, 1>), dim3((unsigned)grid), dim3(64), 0, s, a, table);
+    else hipLaunchKernelGGL((stftmask_run_kernel<R, 0>), dim3((unsigned)grid), dim3(64), 0, s, a, table);
+}
+
+int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask, long pitch,
+                    long n_frames, const float *wa, const float *ws, const float *g, const float *tail_in,
+                    float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt)
+{
+    if (n_frames <= 0) return 0;
+    const int r = 1024 / hop;
+    // as launch_istft: one round of resident waves, and never a run shorter than JDSP_ISTFT_MIN_RUN_PER_HALO (R - 1)
+    // frames, so that the halo a wave recomputes (here: transforms both ways) is a bounded share of its run
+    const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_STFTMASK_RESIDENT;
+    long run = (n_frames + slots - 1) / slots;
+    const long min_run = r > 1 ? (long)JDSP_ISTFT_MIN_RUN_PER_HALO * (r - 1) : 1;
+    if (run < min_run) run = min_run;
+    if (run_opt > 0) run = run_opt < r - 1 ? r - 1 : run_opt;        // jdsp_stftmask_set_option("frames_per_wave")
+    const long waves = (n_frames + run - 1) / run;
+    const long grid = (waves + 7) / 8 * 8;
+    StftMaskArgs a = {pcm, mask, pitch, n_frames, wa, ws, g, tail_in, tail_out, out, out_f32, (int)run};
+    if (r == 1) launch_kind<1>(s, complex_mask, grid, a, table);
+    else if (r == 2) launch_kind<2>(s, complex_mask, grid, a, table);
+    else launch_kind<4>(s, complex_mask, grid, a, table);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace jdsp

@@ -102,6 +102,11 @@ class Engine(_Handle):
         analysis_window ("none" / "hamming" / "hann" or -1 / 0 / 1)."""
         return Istft(self, **cfg)
 
+    def stft_mask(self, **cfg):
+        """Fused STFT masking stream (jdsp_stftmask): n_fft, hop, analysis_window, synthesis_window ("none" /
+        "hamming" / "hann" or -1 / 0 / 1), normalise (0 / 1), mask_kind ("real" / "complex" or 0 / 1)."""
+        return StftMask(self, **cfg)
+
     def geq(self, n_streams, coeff=None):
         """Multi-stream IIR equaliser (jdsp_geq), 7Band_GEQ.cpp: coeff [n_sections, 2, 3] float64 (1..16 sections), or
         None for the reference's seven bands (geq_design())."""
@@ -949,6 +954,97 @@ class Istft(_Child):
             out = np.zeros(max(n, 1), np.int16)
             f = np.zeros(max(n, 1), np.float32) if want_f32 else None
             self.eng._ck(L.jdsp_istft_flush(self._h, _vp(out), _vp(f)))
+        return (out[:n], f[:n]) if want_f32 else out[:n]
+
+
+class StftMask(_Child):
+    """One fused STFT masking stream (jdsp_stftmask, include/jdsp.h): int16 PCM -> analysis window -> forward
+    transform -> per-bin mask -> inverse transform -> synthesis window -> overlap-add -> int16 (and optionally the
+    float32 values before the cast), without the spectrum reaching memory.  torch CUDA inputs go through the device
+    entry on torch's current stream, numpy inputs through the host entry."""
+    _destroy = staticmethod(lambda h: L.jdsp_stftmask_destroy(h))
+    WINDOWS = Istft.WINDOWS
+    KINDS = {"real": _lib.MASK_REAL, "complex": _lib.MASK_COMPLEX}
+
+    def __init__(self, engine, n_fft=1024, hop=512, analysis_window="hamming", synthesis_window="none", normalise=0,
+                 mask_kind="real"):
+        self.eng = engine
+        pick = lambda v, names: names[v] if isinstance(v, str) or v is None else int(v)  # noqa: E731
+        cfg = _lib.StftMaskCfg(int(n_fft), int(hop), pick(analysis_window, self.WINDOWS),
+                               pick(synthesis_window, self.WINDOWS), int(normalise), pick(mask_kind, self.KINDS))
+        h = C.c_void_p()
+        engine._ck(L.jdsp_stftmask_create(engine._h, C.byref(cfg), C.byref(h)))
+        self._h = h
+        self.n_fft, self.hop, self.mask_kind = cfg.n_fft, cfg.hop, cfg.mask_kind
+        self.bins = self.n_fft // 2 + 1
+        self._torch = None              # the kind of the last process() input: flush() answers in the same kind
+        engine._children.append(self)
+
+    def reset(self):
+        self.eng._ck(L.jdsp_stftmask_reset(self._h))
+
+    def set_option(self, name, value):
+        self.eng._ck(L.jdsp_stftmask_set_option(self._h, name.encode(), int(value)))
+
+    def samples_out(self, n_frames):
+        return L.jdsp_stftmask_samples_out(self._h, int(n_frames))
+
+    def process(self, pcm, mask, n_frames=None, want_f32=False, write=True, out=None, out_f32=None):
+        """pcm: int16, hop (n_frames - 1) + n_fft samples (n_frames defaults to all the whole frames pcm holds).
+        mask: float32 (real) or complex64 (complex); [n_frames, pitch >= bins] with contiguous rows, or 1-D [bins]: one
+        row for every frame (pitch 0).  Both torch CUDA or both numpy.  Returns the int16 samples of these frames
+        (n_frames * hop), or (int16, float32) with want_f32 (into out / out_f32 when given).  write=False advances the
+        stream without writing (both outputs NULL) and returns None."""
+        if n_frames is None:
+            n_frames = max((pcm.shape[0] - self.n_fft) // self.hop + 1, 0)
+        n_frames = int(n_frames)
+        assert pcm.ndim == 1 and pcm.shape[0] >= (self.hop * (n_frames - 1) + self.n_fft if n_frames else 0)
+        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_frames)
+        pitch = mask.shape[1] if mask.ndim == 2 else 0
+        n_out = self.samples_out(n_frames)
+        if not write:
+            out = out_f32 = None
+        if _is_torch(pcm):
+            import torch
+            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
+            self._torch = pcm.device
+            if write:
+                if out is None:
+                    out = torch.empty(max(n_out, 1), dtype=torch.int16, device=pcm.device)
+                if want_f32 and out_f32 is None:
+                    out_f32 = torch.empty(max(n_out, 1), dtype=torch.float32, device=pcm.device)
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_stftmask_process_dev(self._h, _vp(pcm), _vp(mask), pitch, n_frames, _vp(out),
+                                                     _vp(out_f32) if want_f32 else None))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
+            self._torch = None
+            if write:
+                out = np.zeros(max(n_out, 1), np.int16) if out is None else out
+                if want_f32 and out_f32 is None:
+                    out_f32 = np.zeros(max(n_out, 1), np.float32)
+            self.eng._ck(L.jdsp_stftmask_process(self._h, _vp(pcm), _vp(mask), pitch, n_frames, _vp(out),
+                                                 _vp(out_f32) if want_f32 else None))
+        if not write:
+            return None
+        return (out[:n_out], out_f32[:n_out]) if want_f32 else out[:n_out]
+
+    def flush(self, want_f32=False):
+        """The n_fft - hop samples still in the tail; the handle is reset afterwards."""
+        n = self.n_fft - self.hop
+        if self._torch is not None:
+            import torch
+            out = torch.zeros(max(n, 1), dtype=torch.int16, device=self._torch)
+            f = torch.zeros(max(n, 1), dtype=torch.float32, device=self._torch) if want_f32 else None
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_stftmask_flush_dev(self._h, _vp(out), _vp(f)))
+        else:
+            out = np.zeros(max(n, 1), np.int16)
+            f = np.zeros(max(n, 1), np.float32) if want_f32 else None
+            self.eng._ck(L.jdsp_stftmask_flush(self._h, _vp(out), _vp(f)))
         return (out[:n], f[:n]) if want_f32 else out[:n]
 
 

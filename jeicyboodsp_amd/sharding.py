@@ -132,6 +132,26 @@ def istft_sharded(istft, spec, n_frames, world, rank, want_f32=False):
     return istft.process(spec[first:end], want_f32=want_f32)
 
 
+def stftmask_sharded(stftmask, pcm, mask, n_frames, world, rank, want_f32=False):
+    """One rank's part of a fused STFT masking stream (jdsp_stftmask): the frame split, the halo and the priming are
+    istft_frame_shard's -- reset, run the R - 1 halo frames with NULL outputs, then the rank's own frames.  pcm: the
+    stream's samples (only those of frames [halo, end) are read); mask: [n_frames, pitch] rows, or 1-D (one row for
+    every frame).  Returns what stftmask.process returns for the own frames (None when the rank owns none);
+    bit-identical to the same samples of a single-call run."""
+    n, hop = stftmask.n_fft, stftmask.hop
+    halo, first, end = istft_frame_shard(n_frames, world, rank, n // hop)
+    stftmask.reset()
+    if end == first:
+        return None
+
+    def part(a, b):
+        return pcm[hop * a: hop * (b - 1) + n], (mask if mask.ndim == 1 else mask[a:b]), b - a
+
+    if first > halo:
+        stftmask.process(*part(halo, first), write=False)
+    return stftmask.process(*part(first, end), want_f32=want_f32)
+
+
 def fastconv_shard_blocks(n_blocks, hist_blocks, rank, world):
     """Input blocks a rank must be given to produce its share of an overlap-save stream.
     The stream of n_blocks input blocks emits n_blocks - hist_blocks output blocks (the first

@@ -143,6 +143,55 @@ def main():
                    "(%d algorithmic bytes per frame; the halo frames a wave recomputes are not counted)" % nbytes)
             ist.close()
             del spec, sr
+    if on("stftmask"):
+        # Fused STFT masking (jdsp_stftmask) against the unfused route timed the same way: analysis to HBM -> in-place
+        # torch multiply -> synthesis.  65,536 frames per call; PCM and mask rows rotate over 6 copies (from HBM).
+        flops = 2 * (5 * 512 * 9 + 512 * 14)
+        for name, hop, kind in (("stftmask_1024_hop512_real", 512, "real"), ("stftmask_1024_hop512_complex", 512, "complex"),
+                                ("stftmask_1024_hop256_real", 256, "real")):
+            cpx = kind == "complex"
+            nbytes = 2 * hop + 513 * (8 if cpx else 4) + 2 * hop
+            gen = torch.Generator(device="cuda").manual_seed(hop + cpx)
+            x = torch.from_numpy(pcm_of(rng, hop * (B - 1) + 1024)).cuda()
+            mask = torch.rand((B, 513), dtype=torch.float32, device="cuda", generator=gen) * 1.5
+            if cpx:
+                mask = torch.polar(mask, torch.rand((B, 513), dtype=torch.float32, device="cuda", generator=gen) * 6.2831853)
+            xr, mr = rot(x), rot(mask)
+            o16 = torch.empty(B * hop, dtype=torch.int16, device="cuda")
+            sm = eng.stft_mask(n_fft=1024, hop=hop, analysis_window="hamming", synthesis_window="none", normalise=0,
+                               mask_kind=kind)
+            ms = timed(lambda: sm.process(xr(), mr(), B, out=o16), a.iters)
+            report(name, ms, B, "frames", nbytes, flops,
+                   "fused analysis -> %s mask -> synthesis, int16 in and out, no spectrum in memory (%d algorithmic bytes "
+                   "per frame: %d PCM + %d mask + %d out; the halo frames a wave recomputes are not counted)"
+                   % (kind, nbytes, 2 * hop, nbytes - 4 * hop, 2 * hop))
+            sm.close()
+            # the unfused route on the same inputs: the spectrum goes to HBM, is multiplied there and read back
+            half = hop == 512
+            if half:
+                spec = torch.empty((B, 513), dtype=torch.complex64, device="cuda")
+                full_mask = None
+                analyse = lambda: eng.stft_half(xr(), B, out=spec, pitch=513)  # noqa: E731
+            else:
+                spec = torch.empty((B, 1024), dtype=torch.complex64, device="cuda")
+                full_mask = rot(torch.cat([mask, mask[:, 1:512].flip(1)], dim=1).contiguous())
+                analyse = lambda: eng.stft(xr(), B, 1024, hop, out=spec)  # noqa: E731
+            ist = eng.istft(n_fft=1024, hop=hop, layout="half" if half else "full")
+
+            def unfused():
+                analyse()
+                spec.mul_(mr() if half else full_mask())
+                ist.process(spec, out=o16)
+
+            ms_u = timed(unfused, a.iters)
+            ubytes = 2 * hop + 3 * spec.shape[1] * 8 + spec.shape[1] * (8 if cpx else 4) + 2 * hop
+            report(name.replace("stftmask_", "unfused_stft_mul_istft_"), ms_u, B, "frames", ubytes, flops,
+                   "the same work as three launches through a %d-byte-per-frame spectrum workspace (%s): %.3f ms against "
+                   "%.3f ms fused on the same box in the same process, ratio %.2f"
+                   % (spec.shape[1] * 8, "stft_half pitch 513 -> torch mul_ -> istft half" if half
+                      else "stft full -> torch mul_ -> istft full", ms_u, ms, ms_u / ms))
+            ist.close()
+            del x, mask, xr, mr, spec, full_mask, o16
     if on("denoise"):
         x = pcm_of(rng, B * 512)
         x[:12 * 512] = pcm_of(rng, 12 * 512, 45.0)          # the estimate latches at block 10
