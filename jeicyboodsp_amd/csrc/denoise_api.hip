@@ -3,24 +3,13 @@
 
 using jdsp::fail;
 
-static jdsp::DenoiseGeom geom(const jdsp_denoise *h) { return {h->n_fft, h->win512h}; }
+static jdsp::DenoiseGeom geom(const jdsp_denoise *h) { return {h->n_fft, h->win512h.get()}; }
 
-static void free_workspace(jdsp_denoise *h)
+// the launchers' view of the workspace's chunked noise average
+static jdsp::NoiseAccum accum(const jdsp_denoise *h)
 {
-    void *p[] = {h->flags, h->ev_n, h->ver_base, h->snap_mask, h->events, h->dbg_energy, h->dbg_zcr, h->rows,
-                 h->acc.lat_alpha, h->acc.lat_chunk, h->acc.chunk_alpha, h->acc.chunk_beta, h->acc.a_start};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
-    h->flags = nullptr;
-    h->ev_n = h->ver_base = h->events = nullptr;
-    h->snap_mask = nullptr;
-    h->dbg_energy = nullptr;
-    h->dbg_zcr = nullptr;
-    h->rows = nullptr;
-    h->acc.lat_alpha = h->acc.chunk_alpha = h->acc.chunk_beta = h->acc.a_start = nullptr;
-    h->acc.lat_chunk = nullptr;
-    h->cap_rows = 0;
-    h->cap_blocks = 0;
+    const jdsp_denoise::Workspace &w = h->ws;
+    return {w.chunk_alpha.get(), w.chunk_beta.get(), w.a_start.get(), w.lat_alpha.get(), w.lat_chunk.get()};
 }
 
 extern "C" {
@@ -56,19 +45,17 @@ int jdsp_denoise_create_cfg(jdsp_ctx *ctx, int mode, int n_fft, int hop, jdsp_de
             w_h[i] = (float)(0.5 * w);
             if (i >= 256) w_hi[i - 256] = w;
         }
-        e = hipMalloc((void **)&h->w_hi256, sizeof(w_hi));
-        if (e == hipSuccess) e = hipMalloc((void **)&h->win512h, sizeof(w_h));
-        if (e == hipSuccess) e = hipMemcpy(h->w_hi256, w_hi, sizeof(w_hi), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(h->win512h, w_h, sizeof(w_h), hipMemcpyHostToDevice);
+        e = h->w_hi256.upload(w_hi, 256);
+        if (e == hipSuccess) e = h->win512h.upload(w_h, 512);
     }
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&h->st[i], sizeof(jdsp::DenoiseState));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->plan, sizeof(jdsp::DenoisePlan));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->sh_range, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->sh_a_in, 1024 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->sh_zero_run, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(h->sh_zero_run, 0, sizeof(int));
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = h->st[i].alloc(1);
+    if (e == hipSuccess) e = h->plan.alloc(1);
+    if (e == hipSuccess) e = h->sh_range.alloc(4);
+    if (e == hipSuccess) e = h->sh_a_in.alloc(1024);
+    if (e == hipSuccess) e = h->sh_zero_run.alloc(1);
+    if (e == hipSuccess) e = hipMemset(h->sh_zero_run.get(), 0, sizeof(int));
     if (e == hipSuccess && jdsp::ensure_vad_window(ctx)) e = hipErrorUnknown;
-    h->w_hi = n_fft == 512 ? h->w_hi256 : ctx->vad_w_hi;
+    h->w_hi = n_fft == 512 ? h->w_hi256.get() : ctx->vad_w_hi.get();
     if (e != hipSuccess) {
         jdsp_denoise_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_denoise_create: alloc", e);
@@ -87,15 +74,6 @@ int jdsp_denoise_destroy(jdsp_denoise *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    free_workspace(h);
-    for (int i = 0; i < 2; i++)
-        if (h->st[i]) (void)hipFree(h->st[i]);
-    if (h->plan) (void)hipFree(h->plan);
-    if (h->sh_range) (void)hipFree(h->sh_range);
-    if (h->sh_a_in) (void)hipFree(h->sh_a_in);
-    if (h->sh_zero_run) (void)hipFree(h->sh_zero_run);
-    if (h->w_hi256) (void)hipFree(h->w_hi256);
-    if (h->win512h) (void)hipFree(h->win512h);
     delete h;
     return JDSP_OK;
 }
@@ -104,7 +82,7 @@ int jdsp_denoise_reset(jdsp_denoise *h)
 {
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
-    for (int i = 0; i < 2; i++) JDSP_HIP(ctx, hipMemsetAsync(h->st[i], 0, sizeof(jdsp::DenoiseState), ctx->stream));
+    for (int i = 0; i < 2; i++) JDSP_HIP(ctx, hipMemsetAsync(h->st[i].get(), 0, sizeof(jdsp::DenoiseState), ctx->stream));
     h->calls = 0;
     h->cur = 0;
     h->last_blocks = 0;
@@ -147,34 +125,29 @@ int jdsp_denoise_reserve(jdsp_denoise *h, long max_blocks)
 static int reserve2(jdsp_denoise *h, long max_blocks)
 {
     jdsp_ctx *ctx = h->ctx;
-    if (max_blocks <= h->cap_blocks) return JDSP_OK;
+    if (max_blocks <= h->ws.run.cap_blocks) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    free_workspace(h);
+    jdsp_denoise::Workspace &w = h->ws;
+    w = {};                                           // freed before anything is allocated
     const size_t n = (size_t)max_blocks;
-    hipError_t e = hipMalloc((void **)&h->flags, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ev_n, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ver_base, (n / 64 + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->snap_mask, (n / 64 + 1) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->events, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->dbg_energy, n * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->dbg_zcr, n * sizeof(int));
+    hipError_t e = w.run.reserve(n);
+    if (e == hipSuccess) e = w.dbg_energy.alloc(n);
+    if (e == hipSuccess) e = w.dbg_zcr.alloc(n);
     // worst case: every block feeds the noise average; an estimate can latch at most every 10th block.  (No magnitude
     // rows: noise_accum_kernel folds them into per-chunk maps in registers.)
     const size_t n_rows = n / 10 + 2;
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rows, n_rows * 1024 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->acc.lat_alpha, n_rows * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->acc.lat_chunk, n_rows * sizeof(int));
+    if (e == hipSuccess) e = w.rows.alloc(n_rows * 1024);
+    if (e == hipSuccess) e = w.lat_alpha.alloc(n_rows);
+    if (e == hipSuccess) e = w.lat_chunk.alloc(n_rows);
     const size_t n_chunks = n < (size_t)jdsp::kNoiseChunks ? (n > 0 ? n : 1) : (size_t)jdsp::kNoiseChunks;   // launch_noise_estimate's grid
-    if (e == hipSuccess) e = hipMalloc((void **)&h->acc.chunk_alpha, n_chunks * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->acc.chunk_beta, n_chunks * 1024 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->acc.a_start, n_chunks * 1024 * sizeof(float));
+    if (e == hipSuccess) e = w.chunk_alpha.alloc(n_chunks);
+    if (e == hipSuccess) e = w.chunk_beta.alloc(n_chunks * 1024);
+    if (e == hipSuccess) e = w.a_start.alloc(n_chunks * 1024);
     if (e != hipSuccess) {
-        free_workspace(h);
+        w = {};
         return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_denoise_reserve", e);
     }
-    h->cap_blocks = max_blocks;
-    h->cap_rows = (long)n_rows;
     return JDSP_OK;
 }
 
@@ -193,18 +166,21 @@ int jdsp_denoise_process_dev(jdsp_denoise *h, const int16_t *pcm_dev, long n_blo
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = jdsp_denoise_reserve(h, n_blocks);      // no-op once sized (call jdsp_denoise_reserve before graph capture)
     if (rc) return rc;
-    const jdsp::DenoiseState *st_in = h->st[h->cur];
-    jdsp::DenoiseState *st_out = h->st[h->cur ^ 1];
+    const jdsp::DenoiseState *st_in = h->st[h->cur].get();
+    jdsp::DenoiseState *st_out = h->st[h->cur ^ 1].get();
     hipStream_t s = ctx->stream;
     const jdsp::DenoiseGeom g = geom(h);
-    if (jdsp::launch_vad(s, h->block, pcm_dev, n_blocks, h->w_hi, 1, h->flags, h->opt_vad_trace ? h->dbg_energy : nullptr,
-                         h->opt_vad_trace ? h->dbg_zcr : nullptr) ||
-        jdsp::launch_denoise_plan(s, h->flags, n_blocks, st_in, st_out, h->ver_base, h->snap_mask, h->events, h->ev_n,
-                                  h->plan) ||
-        jdsp::launch_noise_estimate(s, g, pcm_dev, n_blocks, st_in, st_out, h->events, h->ev_n, h->plan, h->ver_base,
-                                    h->snap_mask, ctx->stft1024_table, h->acc, h->rows) ||
-        jdsp::launch_denoise(s, g, h->mode, h->opt_k, ctx->n_cu, pcm_dev, n_blocks, h->calls, st_in, st_out, h->ver_base,
-                             h->snap_mask, h->rows, ctx->stft1024_table, out_dev, precast_dev))
+    const jdsp_denoise::Workspace &w = h->ws;
+    const jdsp::RunPlanWs &r = w.run;
+    const float2 *table = ctx->stft1024_table.get();
+    if (jdsp::launch_vad(s, h->block, pcm_dev, n_blocks, h->w_hi, 1, r.flags.get(),
+                         h->opt_vad_trace ? w.dbg_energy.get() : nullptr, h->opt_vad_trace ? w.dbg_zcr.get() : nullptr) ||
+        jdsp::launch_denoise_plan(s, r.flags.get(), n_blocks, st_in, st_out, r.ver_base.get(), r.snap_mask.get(),
+                                  r.events.get(), r.ev_n.get(), h->plan.get()) ||
+        jdsp::launch_noise_estimate(s, g, pcm_dev, n_blocks, st_in, st_out, r.events.get(), r.ev_n.get(), h->plan.get(),
+                                    r.ver_base.get(), r.snap_mask.get(), table, accum(h), w.rows.get()) ||
+        jdsp::launch_denoise(s, g, h->mode, h->opt_k, ctx->n_cu, pcm_dev, n_blocks, h->calls, st_in, st_out,
+                             r.ver_base.get(), r.snap_mask.get(), w.rows.get(), table, out_dev, precast_dev))
         return fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError());
     h->cur ^= 1;
     h->calls += n_blocks;
@@ -255,17 +231,20 @@ int jdsp_denoise_apply(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks, 
     const size_t blk_b = (size_t)h->block * sizeof(int16_t);
     const size_t in_b = (size_t)n_blocks * blk_b, out_b = (size_t)(n_out > 0 ? n_out : 1) * blk_b;
     hipStream_t s = ctx->stream;
-    jdsp::DenoiseState *st_in = h->st[h->cur], *st_out = h->st[h->cur ^ 1];
+    jdsp::DenoiseState *st_in = h->st[h->cur].get(), *st_out = h->st[h->cur ^ 1].get();
+    float *rows = h->ws.rows.get();
+    int *ver_base = h->ws.run.ver_base.get();
+    unsigned long long *snap_mask = h->ws.run.snap_mask.get();
     jdsp::HostCall hc(ctx, "jdsp_denoise_apply");
     const int16_t *d_in = hc.upload(pcm_host, in_b);
     int16_t *d_out = hc.alloc<int16_t>(out_b);
     float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
-    hc.upload_to(h->rows, row, sizeof(float) * (size_t)h->n_fft);
-    hc.zero(h->ver_base, ((size_t)n_blocks / 64 + 1) * sizeof(int));                   // every block uses row 0
-    hc.zero(h->snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
+    hc.upload_to(rows, row, sizeof(float) * (size_t)h->n_fft);
+    hc.zero(ver_base, ((size_t)n_blocks / 64 + 1) * sizeof(int));                      // every block uses row 0
+    hc.zero(snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
     hc.copy_dev(st_out, st_in, sizeof(jdsp::DenoiseState));
     if (hc.ok() && jdsp::launch_denoise(s, geom(h), h->mode, h->opt_k, ctx->n_cu, d_in, n_blocks, h->calls, st_in, st_out,
-                                        h->ver_base, h->snap_mask, h->rows, ctx->stft1024_table, d_out, d_pre))
+                                        ver_base, snap_mask, rows, ctx->stft1024_table.get(), d_out, d_pre))
         hc.result(fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError()));
     hc.download(out_host, d_out, (size_t)n_out * blk_b);
     hc.download(precast_host, d_pre, (size_t)n_out * blk_b * 2);
@@ -341,11 +320,12 @@ int jdsp_denoise_shard_summary_dev(jdsp_denoise *h, const uint8_t *flags_all_dev
     if (!flags_all_dev || !summary_dev) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_shard_summary: NULL buffer");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (jdsp::launch_run_plan(s, flags_all_dev, h->sh_total, h->sh_zero_run, nullptr, 10, h->ver_base, h->snap_mask,
-                              h->events, h->ev_n, h->plan) ||
-        jdsp::launch_shard_summary(s, geom(h), h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0, h->sh_b1, h->events,
-                                   h->ev_n, h->plan, h->ver_base, h->snap_mask, ctx->stft1024_table, h->sh_range, h->acc,
-                                   h->rows, summary_dev))
+    const jdsp::RunPlanWs &r = h->ws.run;
+    if (jdsp::launch_run_plan(s, flags_all_dev, h->sh_total, h->sh_zero_run.get(), nullptr, 10, r.ver_base.get(),
+                              r.snap_mask.get(), r.events.get(), r.ev_n.get(), h->plan.get()) ||
+        jdsp::launch_shard_summary(s, geom(h), h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0, h->sh_b1,
+                                   r.events.get(), r.ev_n.get(), h->plan.get(), r.ver_base.get(), r.snap_mask.get(),
+                                   ctx->stft1024_table.get(), h->sh_range.get(), accum(h), h->ws.rows.get(), summary_dev))
         return fail(ctx, JDSP_EHIP, "shard summary launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -357,8 +337,8 @@ int jdsp_denoise_shard_rows_dev(jdsp_denoise *h, const float *summaries_all_dev,
     if (!summaries_all_dev || !last_dev || world < 1 || rank < 0 || rank >= world)
         return fail(ctx, JDSP_EINVAL, "jdsp_denoise_shard_rows: bad argument");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    if (jdsp::launch_shard_rows(ctx->stream, geom(h), summaries_all_dev, rank, h->sh_b0, h->sh_b1, h->plan, h->sh_range,
-                                h->acc, h->sh_a_in, h->rows, last_dev))
+    if (jdsp::launch_shard_rows(ctx->stream, geom(h), summaries_all_dev, rank, h->sh_b0, h->sh_b1, h->plan.get(),
+                                h->sh_range.get(), accum(h), h->sh_a_in.get(), h->ws.rows.get(), last_dev))
         return fail(ctx, JDSP_EHIP, "shard rows launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -382,19 +362,20 @@ int jdsp_denoise_shard_finish_dev(jdsp_denoise *h, const float *last_all_dev, in
     if ((uintptr_t)out_dev & 15u) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_shard_finish: out must be 16-byte aligned");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (jdsp::launch_shard_row0(s, geom(h), last_all_dev, rank, h->rows))
+    if (jdsp::launch_shard_row0(s, geom(h), last_all_dev, rank, h->ws.rows.get()))
         return fail(ctx, JDSP_EHIP, "row0 launch", hipGetLastError());
     if (n_out > 0) {
         jdsp::DenoiseShard sh;
         sh.ver_block_off = h->sh_ext0;
-        sh.ver_row_off = h->sh_range + 2;
+        sh.ver_row_off = h->sh_range.get() + 2;
         const long lo = h->sh_b0 > 2 ? h->sh_b0 : 2;
         sh.emit_from = lo - h->sh_ext0;
         sh.emit_to = h->sh_b1 - h->sh_ext0;
         // fresh state: the two halo blocks in front of the shard rebuild the overlap tail
         if (jdsp::launch_denoise(s, geom(h), h->mode, h->opt_k, ctx->n_cu, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0,
-                                 h->st[h->cur], h->st[h->cur ^ 1], h->ver_base, h->snap_mask, h->rows, ctx->stft1024_table,
-                                 out_dev, precast_dev, &sh))
+                                 h->st[h->cur].get(), h->st[h->cur ^ 1].get(), h->ws.run.ver_base.get(),
+                                 h->ws.run.snap_mask.get(), h->ws.rows.get(), ctx->stft1024_table.get(), out_dev,
+                                 precast_dev, &sh))
             return fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError());
     }
     return JDSP_OK;
@@ -405,7 +386,7 @@ int jdsp_denoise_noise(jdsp_denoise *h, double *noise_host)
     if (!h || !noise_host) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
     float tmp[1024];
-    JDSP_HIP(ctx, hipMemcpyAsync(tmp, h->st[h->cur]->noise, sizeof(tmp), hipMemcpyDeviceToHost, ctx->stream));
+    JDSP_HIP(ctx, hipMemcpyAsync(tmp, h->st[h->cur].get()->noise, sizeof(tmp), hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < h->n_fft; i++) noise_host[i] = tmp[i];
     return JDSP_OK;
@@ -419,10 +400,10 @@ int jdsp_denoise_vad_trace(jdsp_denoise *h, long n, uint8_t *voice_host, int64_t
     if ((energy_sum_host || zcr_host) && !h->last_trace_valid)
         return fail(ctx, JDSP_EINVAL, "jdsp_denoise_vad_trace: energies / ZCR are kept only with set_option(\"vad_trace\", 1) before the call");
     if (n == 0) return JDSP_OK;
-    if (voice_host) JDSP_HIP(ctx, hipMemcpyAsync(voice_host, h->flags, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (voice_host) JDSP_HIP(ctx, hipMemcpyAsync(voice_host, h->ws.run.flags.get(), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     if (energy_sum_host)
-        JDSP_HIP(ctx, hipMemcpyAsync(energy_sum_host, h->dbg_energy, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (zcr_host) JDSP_HIP(ctx, hipMemcpyAsync(zcr_host, h->dbg_zcr, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        JDSP_HIP(ctx, hipMemcpyAsync(energy_sum_host, h->ws.dbg_energy.get(), (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (zcr_host) JDSP_HIP(ctx, hipMemcpyAsync(zcr_host, h->ws.dbg_zcr.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JDSP_OK;
 }

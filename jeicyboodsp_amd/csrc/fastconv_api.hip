@@ -33,16 +33,15 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
     std::vector<double> hpad(2 * n, 0.0);
     for (int f = 0; f < n_filters; f++)
         for (int i = 0; i < n_taps; i++) hpad[2 * ((size_t)f * n_fft + i)] = taps[(size_t)f * n_taps + i];
-    hipError_t e = hipMalloc((void **)&h->H, n * sizeof(float2));
+    hipError_t e = h->H.alloc(n);
     const int hl = n_taps - 1 > 0 ? n_taps - 1 : 1;
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&h->hist[i], (size_t)hl * sizeof(short));
-    if (e == hipSuccess && n_fft == 8192 && !ctx->conv_tw4096) {
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = h->hist[i].alloc((size_t)hl);
+    if (e == hipSuccess && n_fft == 8192 && !ctx->conv_tw8192.get()) {
         std::vector<float2> a(4096), b(4096);
         jdsp::fill_conv_twiddles(a.data(), b.data());
-        e = hipMalloc((void **)&ctx->conv_tw4096, 4096 * sizeof(float2));
-        if (e == hipSuccess) e = hipMalloc((void **)&ctx->conv_tw8192, 4096 * sizeof(float2));
-        if (e == hipSuccess) e = hipMemcpy(ctx->conv_tw4096, a.data(), 4096 * sizeof(float2), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(ctx->conv_tw8192, b.data(), 4096 * sizeof(float2), hipMemcpyHostToDevice);
+        e = ctx->conv_tw4096.upload(a.data(), 4096);
+        if (e == hipSuccess) e = ctx->conv_tw8192.upload(b.data(), 4096);
+        if (e != hipSuccess) ctx->conv_tw4096.reset();       // both or neither
     }
     if (e != hipSuccess) rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: alloc", e);
     if (!rc) {
@@ -50,7 +49,7 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
         const double *d_h = hc.upload(hpad.data(), n * 16);
         double *d_H = hc.alloc<double>(n * 16);
         if (hc.ok()) hc.result(jdsp_fft_process_f64_dev(ctx, d_h, d_H, n_fft, n_filters, 1));
-        if (hc.ok() && jdsp::launch_spectrum_to_f32(ctx->stream, (const double2 *)d_H, h->H, (long)n,
+        if (hc.ok() && jdsp::launch_spectrum_to_f32(ctx->stream, (const double2 *)d_H, h->H.get(), (long)n,
                                                     n_fft == 1024 ? 1.0f / 2048.0f : 1.0f))   // 1024: the kernel's 1/2 and 1/1024
             hc.result(fail(ctx, JDSP_EHIP, "spectrum_to_f32 launch", hipGetLastError()));
         rc = hc.finish();
@@ -65,7 +64,7 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
         for (int f = 0; f < n_filters; f++)
             for (int i = 0; i < n_taps; i++)
                 part[2 * (((size_t)f * P + i / 512) * 1024 + i % 512)] = taps[(size_t)f * n_taps + i];
-        if ((e = hipMalloc((void **)&h->Hp, rows * jdsp::kUpolsRowPitch * sizeof(float2))) != hipSuccess)
+        if ((e = h->Hp.alloc(rows * jdsp::kUpolsRowPitch)) != hipSuccess)
             rc = fail(ctx, JDSP_EHIP, "jdsp_fastconv_create: partitions", e);
         if (!rc) rc = jdsp::ensure_stft1024_table_rect(ctx);
         if (!rc) {
@@ -73,7 +72,7 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
             const double *d_p = hc.upload(part.data(), rows * 1024 * 16);
             double *d_P = hc.alloc<double>(rows * 1024 * 16);
             if (hc.ok()) hc.result(jdsp_fft_process_f64_dev(ctx, d_p, d_P, 1024, (long)rows, 1));
-            if (hc.ok() && jdsp::launch_spectrum_rows_to_f32(ctx->stream, (const double2 *)d_P, h->Hp, (long)rows))
+            if (hc.ok() && jdsp::launch_spectrum_rows_to_f32(ctx->stream, (const double2 *)d_P, h->Hp.get(), (long)rows))
                 hc.result(fail(ctx, JDSP_EHIP, "spectrum_rows_to_f32 launch", hipGetLastError()));
             rc = hc.finish();
         }
@@ -93,12 +92,6 @@ int jdsp_fastconv_destroy(jdsp_fastconv *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->H) (void)hipFree(h->H);
-    if (h->Hp) (void)hipFree(h->Hp);
-    if (h->staged) (void)hipFree(h->staged);
-    if (h->X) (void)hipFree(h->X);
-    for (int i = 0; i < 2; i++)
-        if (h->hist[i]) (void)hipFree(h->hist[i]);
     delete h;
     return JDSP_OK;
 }
@@ -107,7 +100,7 @@ int jdsp_fastconv_reset(jdsp_fastconv *h)
 {
     if (!h) return JDSP_EINVAL;
     const int hl = h->n_taps - 1 > 0 ? h->n_taps - 1 : 1;
-    for (int i = 0; i < 2; i++) JDSP_HIP(h->ctx, hipMemsetAsync(h->hist[i], 0, (size_t)hl * sizeof(short), h->ctx->stream));
+    for (int i = 0; i < 2; i++) JDSP_HIP(h->ctx, hipMemsetAsync(h->hist[i].get(), 0, (size_t)hl * sizeof(short), h->ctx->stream));
     h->calls = 0;
     h->cur = 0;
     return JDSP_OK;
@@ -131,12 +124,12 @@ int jdsp_fastconv_reserve(jdsp_fastconv *h, long n_blocks)
     if (samples <= h->ws_samples) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h->staged) (void)hipFree(h->staged);
-    if (h->X) (void)hipFree(h->X);
-    h->staged = nullptr; h->X = nullptr; h->ws_samples = 0;
+    h->ws_samples = 0;
+    h->staged.reset();
+    h->X.reset();
     const long total = 512L * h->n_part + samples;
-    JDSP_HIP(ctx, hipMalloc((void **)&h->staged, (size_t)total * sizeof(short)));
-    JDSP_HIP(ctx, hipMalloc((void **)&h->X, (size_t)(total / 512) * jdsp::kUpolsRowPitch * sizeof(float2)));
+    JDSP_HIP(ctx, h->staged.alloc((size_t)total));
+    JDSP_HIP(ctx, h->X.alloc((size_t)(total / 512) * jdsp::kUpolsRowPitch));
     h->ws_samples = samples;
     return JDSP_OK;
 }
@@ -164,7 +157,7 @@ int jdsp_fastconv_process_dev(jdsp_fastconv *h, const int16_t *pcm_dev, long n_b
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     jdsp::ConvStream s;
     s.pcm = pcm_dev;
-    s.hist = h->hist[h->cur];
+    s.hist = h->hist[h->cur].get();
     s.n_samples = n_blocks * h->block;
     s.global0 = h->calls * h->block;
     s.valid_from = (long)h->n_hist * h->block;
@@ -173,13 +166,13 @@ int jdsp_fastconv_process_dev(jdsp_fastconv *h, const int16_t *pcm_dev, long n_b
     if (h->n_part) {
         int rc = jdsp_fastconv_reserve(h, n_blocks);
         if (rc) return rc;
-        if (jdsp::launch_fastconv_upols(ctx->stream, s, n_out, first, h->block, h->n_part, h->n_filters, h->Hp,
-                                        ctx->stft1024_table_rect, h->staged, h->X, out_dev, precast_dev, n_out * h->block,
-                                        h->hist[h->cur ^ 1]))
+        if (jdsp::launch_fastconv_upols(ctx->stream, s, n_out, first, h->block, h->n_part, h->n_filters, h->Hp.get(),
+                                        ctx->stft1024_table_rect.get(), h->staged.get(), h->X.get(), out_dev, precast_dev,
+                                        n_out * h->block, h->hist[h->cur ^ 1].get()))
             return fail(ctx, JDSP_EHIP, "fastconv (partitioned) launch", hipGetLastError());
-    } else if (jdsp::launch_fastconv(ctx->stream, h->n_fft, s, n_out, first, h->block, h->n_taps, h->n_filters, h->H,
-                              ctx->stft1024_table, ctx->conv_tw4096, ctx->conv_tw8192, out_dev, precast_dev,
-                              n_out * h->block, h->hist[h->cur ^ 1]))
+    } else if (jdsp::launch_fastconv(ctx->stream, h->n_fft, s, n_out, first, h->block, h->n_taps, h->n_filters, h->H.get(),
+                              ctx->stft1024_table.get(), ctx->conv_tw4096.get(), ctx->conv_tw8192.get(), out_dev,
+                              precast_dev, n_out * h->block, h->hist[h->cur ^ 1].get()))
         return fail(ctx, JDSP_EHIP, "fastconv launch", hipGetLastError());
     h->cur ^= 1;
     h->calls += n_blocks;

@@ -65,8 +65,7 @@ int jdsp_gmm_create(jdsp_ctx *ctx, const jdsp_gmm_param *classes, int n_classes,
     h->n_classes = n_classes;
     std::vector<double> rec((size_t)n_classes * jdsp::kGmmRecord);
     for (int c = 0; c < n_classes; c++) pack_gmm(classes[c], &rec[(size_t)c * jdsp::kGmmRecord]);
-    hipError_t e = hipMalloc(&h->records, rec.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(h->records, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice);
+    const hipError_t e = h->records.upload(rec.data(), rec.size());
     if (e != hipSuccess) {
         jdsp_gmm_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_gmm_create: upload", e);
@@ -80,7 +79,6 @@ int jdsp_gmm_destroy(jdsp_gmm *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->records) (void)hipFree(h->records);
     delete h;
     return JDSP_OK;
 }
@@ -106,7 +104,7 @@ int jdsp_gmm_score_dev(jdsp_gmm *h, const double *feats_dev, long n_frames, cons
     if (n_utts > 0 && !scores_dev) return fail(ctx, JDSP_EINVAL, "jdsp_gmm_score_dev: scores required");
     if (n_utts == 0) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    if (jdsp::launch_gmm_score(ctx->stream, feats_dev, n_frames, (const long long *)utt_first_dev, n_utts, h->records, h->n_classes,
+    if (jdsp::launch_gmm_score(ctx->stream, feats_dev, n_frames, (const long long *)utt_first_dev, n_utts, h->records.get(), h->n_classes,
                                h->fused, scores_dev, best_dev))
         return fail(ctx, JDSP_EHIP, "gmm score launch", hipGetLastError());
     return JDSP_OK;
@@ -153,10 +151,8 @@ int jdsp_hmm_create(jdsp_ctx *ctx, const jdsp_hmm_param *models, int n_models, j
         for (int u = 0; u < 6; u++)
             for (int v = 0; v < 6; v++) lt[(size_t)m * 36 + 6 * u + v] = log(models[m].transProb[u][v]);   // Viterbi:196
     }
-    hipError_t e = hipMalloc(&h->records, rec.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&h->log_trans, lt.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(h->records, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->log_trans, lt.data(), lt.size() * sizeof(double), hipMemcpyHostToDevice);
+    hipError_t e = h->records.upload(rec.data(), rec.size());
+    if (e == hipSuccess) e = h->log_trans.upload(lt.data(), lt.size());
     if (e != hipSuccess) {
         jdsp_hmm_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_hmm_create: upload", e);
@@ -170,9 +166,6 @@ int jdsp_hmm_destroy(jdsp_hmm *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->records) (void)hipFree(h->records);
-    if (h->log_trans) (void)hipFree(h->log_trans);
-    if (h->emission) (void)hipFree(h->emission);
     delete h;
     return JDSP_OK;
 }
@@ -192,14 +185,11 @@ int jdsp_hmm_reserve(jdsp_hmm *h, long n_frames)
 {
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
-    if (n_frames <= h->emission_frames) return JDSP_OK;
+    const size_t per_frame = (size_t)h->n_models * 6;
+    if (n_frames <= (long)(h->emission.count() / per_frame)) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h->emission) (void)hipFree(h->emission);
-    h->emission = nullptr;
-    h->emission_frames = 0;
-    JDSP_HIP(ctx, hipMalloc(&h->emission, (size_t)n_frames * h->n_models * 6 * sizeof(double)));
-    h->emission_frames = n_frames;
+    JDSP_HIP(ctx, h->emission.grow((size_t)n_frames * per_frame));
     return JDSP_OK;
 }
 
@@ -215,8 +205,8 @@ int jdsp_hmm_viterbi_dev(jdsp_hmm *h, const double *feats_dev, long n_frames, co
     if (rc) return rc;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     const double log_init = log(1.0 / 6.0);                                      // Viterbi:186
-    if (jdsp::launch_hmm_viterbi(ctx->stream, feats_dev, n_frames, (const long long *)utt_first_dev, n_utts, h->records,
-                                 h->log_trans, h->n_models, h->fused, log_init, h->emission, scores_dev, best_dev, path_dev,
+    if (jdsp::launch_hmm_viterbi(ctx->stream, feats_dev, n_frames, (const long long *)utt_first_dev, n_utts, h->records.get(),
+                                 h->log_trans.get(), h->n_models, h->fused, log_init, h->emission.get(), scores_dev, best_dev, path_dev,
                                  trellis_dev))
         return fail(ctx, JDSP_EHIP, "hmm launch", hipGetLastError());
     return JDSP_OK;

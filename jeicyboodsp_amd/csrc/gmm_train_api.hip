@@ -9,17 +9,14 @@ namespace {
 int grow(jdsp_gmm_trainer *h, long frames)
 {
     jdsp_ctx *ctx = h->ctx;
-    if (frames <= h->cap_frames) return JDSP_OK;
+    const size_t n = (size_t)frames;
+    if (n * 4 <= h->wbuf.count()) return JDSP_OK;       // wbuf is made last: it stands for both
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (h->sel) (void)hipFree(h->sel);
-    if (h->wbuf) (void)hipFree(h->wbuf);
-    h->sel = nullptr;
-    h->wbuf = nullptr;
-    h->cap_frames = 0;
-    JDSP_HIP(ctx, hipMalloc(&h->sel, (size_t)frames));
-    JDSP_HIP(ctx, hipMalloc(&h->wbuf, (size_t)frames * 4 * sizeof(double)));
-    h->cap_frames = frames;
+    h->sel.reset();
+    h->wbuf.reset();
+    JDSP_HIP(ctx, h->sel.alloc(n));
+    JDSP_HIP(ctx, h->wbuf.alloc(n * 4));
     return JDSP_OK;
 }
 
@@ -38,9 +35,9 @@ int jdsp_gmm_train_create(jdsp_ctx *ctx, int n_classes, jdsp_gmm_trainer **out)
     if (!h) return fail(ctx, JDSP_ENOMEM, "jdsp_gmm_train_create");
     h->ctx = ctx;
     h->n_classes = n_classes;
-    hipError_t e = hipMalloc(&h->state, (size_t)n_classes * sizeof(jdsp::GmmTrainState));
-    if (e == hipSuccess) e = hipMalloc(&h->out, (size_t)n_classes * sizeof(jdsp_gmm_train_param));
-    if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, (size_t)n_classes * sizeof(jdsp::GmmTrainState), ctx->stream);
+    hipError_t e = h->state.alloc((size_t)n_classes);
+    if (e == hipSuccess) e = h->out.alloc((size_t)n_classes);
+    if (e == hipSuccess) e = hipMemsetAsync(h->state.get(), 0, (size_t)n_classes * sizeof(jdsp::GmmTrainState), ctx->stream);
     if (e != hipSuccess) {
         jdsp_gmm_train_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_gmm_train_create: allocation", e);
@@ -54,10 +51,6 @@ int jdsp_gmm_train_destroy(jdsp_gmm_trainer *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->state) (void)hipFree(h->state);
-    if (h->out) (void)hipFree(h->out);
-    if (h->sel) (void)hipFree(h->sel);
-    if (h->wbuf) (void)hipFree(h->wbuf);
     delete h;
     return JDSP_OK;
 }
@@ -67,7 +60,7 @@ int jdsp_gmm_train_reset(jdsp_gmm_trainer *h)
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    JDSP_HIP(ctx, hipMemsetAsync(h->state, 0, (size_t)h->n_classes * sizeof(jdsp::GmmTrainState), ctx->stream));
+    JDSP_HIP(ctx, hipMemsetAsync(h->state.get(), 0, (size_t)h->n_classes * sizeof(jdsp::GmmTrainState), ctx->stream));
     return JDSP_OK;
 }
 
@@ -110,7 +103,7 @@ int jdsp_gmm_train_files_dev(jdsp_gmm_trainer *h, const double *feats_dev, long 
     if (rc) return rc;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     if (jdsp::launch_gmm_train(ctx->stream, h->threads, h->n_classes, feats_dev, n_frames, (const long long *)file_first_dev,
-                               (const int *)file_class_dev, n_files, h->kmeans_max_passes, h->state, h->sel, h->wbuf))
+                               (const int *)file_class_dev, n_files, h->kmeans_max_passes, h->state.get(), h->sel.get(), h->wbuf.get()))
         return fail(ctx, JDSP_EHIP, "gmm train launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -136,7 +129,7 @@ int jdsp_gmm_train_files(jdsp_gmm_trainer *h, const double *feats_host, const in
     // first file ever?
     std::vector<jdsp::GmmTrainState> st(h->n_classes);
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    JDSP_HIP(ctx, hipMemcpyAsync(st.data(), h->state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost, ctx->stream));
+    JDSP_HIP(ctx, hipMemcpyAsync(st.data(), h->state.get(), st.size() * sizeof(st[0]), hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<char> seen(h->n_classes);
     for (int c = 0; c < h->n_classes; c++) seen[c] = st[c].i[jdsp::kTrSeen] != 0;
@@ -160,7 +153,7 @@ int jdsp_gmm_train_params_dev(jdsp_gmm_trainer *h, jdsp_gmm_train_param *out_dev
     jdsp_ctx *ctx = h->ctx;
     if (!out_dev || ((uintptr_t)out_dev & 7u)) return fail(ctx, JDSP_EINVAL, "jdsp_gmm_train_params_dev: bad buffer");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    if (jdsp::launch_gmm_train_params(ctx->stream, h->n_classes, h->state, out_dev))
+    if (jdsp::launch_gmm_train_params(ctx->stream, h->n_classes, h->state.get(), out_dev))
         return fail(ctx, JDSP_EHIP, "gmm train params launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -171,14 +164,14 @@ int jdsp_gmm_train_params(jdsp_gmm_trainer *h, jdsp_gmm_train_param *out_host, j
     jdsp_ctx *ctx = h->ctx;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     if (out_host) {
-        int rc = jdsp_gmm_train_params_dev(h, h->out);
+        int rc = jdsp_gmm_train_params_dev(h, h->out.get());
         if (rc) return rc;
-        JDSP_HIP(ctx, hipMemcpyAsync(out_host, h->out, (size_t)h->n_classes * sizeof(jdsp_gmm_train_param),
+        JDSP_HIP(ctx, hipMemcpyAsync(out_host, h->out.get(), (size_t)h->n_classes * sizeof(jdsp_gmm_train_param),
                                      hipMemcpyDeviceToHost, ctx->stream));
     }
     std::vector<jdsp::GmmTrainState> st(stats_host ? h->n_classes : 0);
     if (stats_host)
-        JDSP_HIP(ctx, hipMemcpyAsync(st.data(), h->state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost, ctx->stream));
+        JDSP_HIP(ctx, hipMemcpyAsync(st.data(), h->state.get(), st.size() * sizeof(st[0]), hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t c = 0; c < st.size(); c++) {
         jdsp_gmm_train_stats &o = stats_host[c];

@@ -6,13 +6,14 @@ using jdsp::fail;
 struct jdsp_istft {
     jdsp_ctx *ctx = nullptr;
     jdsp_istft_cfg cfg;
-    float *blob = nullptr;                // device: ws[n_fft] (w_s / n_fft), g[hop], tail[2][n_fft]
-    float *ws = nullptr, *g = nullptr, *tail[2] = {nullptr, nullptr};
+    jdsp::DevBuf<float> blob;             // ws[n_fft] (w_s / n_fft), g[hop], tail[2][n_fft]
+    float *ws = nullptr, *g = nullptr, *tail[2] = {nullptr, nullptr};   // views into blob
     int cur = 0;                          // tail[cur] holds the partial sums the next call starts from
     int run_opt = 0;                      // "frames_per_wave": 0 = auto
-    // host entry points' device buffers, grown on demand
-    void *hbuf[3] = {nullptr, nullptr, nullptr};   // spectra, int16, float32
-    size_t hcap[3] = {0, 0, 0};
+    // host entry points' device buffers, grown on demand (those entries end with a synchronise: none is in use then)
+    jdsp::DevBuf<jdsp_c32> h_spec;
+    jdsp::DevBuf<int16_t> h_i16;
+    jdsp::DevBuf<float> h_f32;
 };
 
 static int bins_of(const jdsp_istft_cfg &c) { return c.layout == JDSP_SPEC_HALF ? c.n_fft / 2 + 1 : c.n_fft; }
@@ -23,17 +24,6 @@ static double window_at(int kind, int i, int n)
     if (kind == JDSP_WIN_NONE) return 1.0;
     const double a = kind == JDSP_WIN_HANN ? 0.5 : 0.54, b = kind == JDSP_WIN_HANN ? 0.5 : 0.46;
     return a - b * cos(2 * 3.141592 * i / (n - 1));
-}
-
-static int grow(jdsp_istft *h, int i, size_t bytes)
-{
-    if (h->hcap[i] >= bytes) return JDSP_OK;
-    if (h->hbuf[i]) (void)hipFree(h->hbuf[i]);
-    h->hbuf[i] = nullptr;
-    h->hcap[i] = 0;
-    JDSP_HIP(h->ctx, hipMalloc(&h->hbuf[i], bytes));
-    h->hcap[i] = bytes;
-    return JDSP_OK;
 }
 
 static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -79,13 +69,13 @@ int jdsp_istft_create(jdsp_ctx *ctx, const jdsp_istft_cfg *cfg, jdsp_istft **out
     h->ctx = ctx;
     h->cfg = c;
     const size_t floats = (size_t)n + hop + 2 * (size_t)n;
-    hipError_t e = hipMalloc((void **)&h->blob, floats * sizeof(float));
+    hipError_t e = h->blob.alloc(floats);
     if (e == hipSuccess) {
-        h->ws = h->blob;
-        h->g = h->blob + n;
-        h->tail[0] = h->blob + n + hop;
+        h->ws = h->blob.get();
+        h->g = h->ws + n;
+        h->tail[0] = h->g + hop;
         h->tail[1] = h->tail[0] + n;
-        e = hipMemcpy(h->blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+        e = hipMemcpy(h->ws, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         jdsp_istft_destroy(h);
@@ -105,9 +95,6 @@ int jdsp_istft_destroy(jdsp_istft *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->blob) (void)hipFree(h->blob);
-    for (void *p : h->hbuf)
-        if (p) (void)hipFree(p);
     delete h;
     return JDSP_OK;
 }
@@ -153,7 +140,7 @@ int jdsp_istft_process_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pit
     const int cur = h->cur;
     if (jdsp::launch_istft(ctx->stream, ctx->n_cu, h->cfg.n_fft, h->cfg.hop, h->cfg.layout == JDSP_SPEC_HALF,
                            reinterpret_cast<const float2 *>(spec_dev), row_pitch, n_frames, h->ws, h->g, h->tail[cur],
-                           h->tail[cur ^ 1], out_i16_dev, out_f32_dev, ctx->stft1024_table, h->run_opt))
+                           h->tail[cur ^ 1], out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->run_opt))
         return fail(ctx, JDSP_EHIP, "jdsp_istft_process: launch", hipGetLastError());
     h->cur = cur ^ 1;
     return JDSP_OK;
@@ -181,17 +168,17 @@ int jdsp_istft_process(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch,
     if (n_frames == 0) return JDSP_OK;
     if (!spec_host) return fail(ctx, JDSP_EINVAL, "jdsp_istft_process: spec is NULL");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t in_bytes = ((size_t)(n_frames - 1) * row_pitch + bins_of(h->cfg)) * sizeof(jdsp_c32);
+    const size_t n_in = (size_t)(n_frames - 1) * row_pitch + bins_of(h->cfg);
     const size_t n_out = (size_t)n_frames * h->cfg.hop;
-    int rc = grow(h, 0, in_bytes);
-    if (!rc && out_i16_host) rc = grow(h, 1, n_out * sizeof(int16_t));
-    if (!rc && out_f32_host) rc = grow(h, 2, n_out * sizeof(float));
-    if (rc) return rc;
-    int16_t *d_i16 = out_i16_host ? (int16_t *)h->hbuf[1] : nullptr;
-    float *d_f32 = out_f32_host ? (float *)h->hbuf[2] : nullptr;
-    jdsp::HostCall hc(ctx, "jdsp_istft_process");                       // the buffers are the handle's (grow)
-    hc.upload_to(h->hbuf[0], spec_host, in_bytes);
-    if (hc.ok()) hc.result(jdsp_istft_process_dev(h, (const jdsp_c32 *)h->hbuf[0], row_pitch, n_frames, d_i16, d_f32));
+    hipError_t e = h->h_spec.grow(n_in);
+    if (e == hipSuccess && out_i16_host) e = h->h_i16.grow(n_out);
+    if (e == hipSuccess && out_f32_host) e = h->h_f32.grow(n_out);
+    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_istft_process: buffers", e);
+    int16_t *d_i16 = out_i16_host ? h->h_i16.get() : nullptr;
+    float *d_f32 = out_f32_host ? h->h_f32.get() : nullptr;
+    jdsp::HostCall hc(ctx, "jdsp_istft_process");                       // the buffers are the handle's
+    hc.upload_to(h->h_spec.get(), spec_host, n_in * sizeof(jdsp_c32));
+    if (hc.ok()) hc.result(jdsp_istft_process_dev(h, h->h_spec.get(), row_pitch, n_frames, d_i16, d_f32));
     hc.download(out_i16_host, d_i16, n_out * sizeof(int16_t));
     hc.download(out_f32_host, d_f32, n_out * sizeof(float));
     return hc.finish();
@@ -203,12 +190,12 @@ int jdsp_istft_flush(jdsp_istft *h, int16_t *out_i16_host, float *out_f32_host)
     jdsp_ctx *ctx = h->ctx;
     const size_t n_tail = (size_t)(h->cfg.n_fft - h->cfg.hop);
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = JDSP_OK;
-    if (n_tail && out_i16_host) rc = grow(h, 1, n_tail * sizeof(int16_t));
-    if (!rc && n_tail && out_f32_host) rc = grow(h, 2, n_tail * sizeof(float));
-    if (rc) return rc;
-    int16_t *d_i16 = n_tail && out_i16_host ? (int16_t *)h->hbuf[1] : nullptr;
-    float *d_f32 = n_tail && out_f32_host ? (float *)h->hbuf[2] : nullptr;
+    hipError_t e = hipSuccess;
+    if (n_tail && out_i16_host) e = h->h_i16.grow(n_tail);
+    if (e == hipSuccess && n_tail && out_f32_host) e = h->h_f32.grow(n_tail);
+    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_istft_flush: buffers", e);
+    int16_t *d_i16 = n_tail && out_i16_host ? h->h_i16.get() : nullptr;
+    float *d_f32 = n_tail && out_f32_host ? h->h_f32.get() : nullptr;
     jdsp::HostCall hc(ctx, "jdsp_istft_flush");
     hc.result(jdsp_istft_flush_dev(h, d_i16, d_f32));
     hc.download(out_i16_host, d_i16, n_tail * sizeof(int16_t));

@@ -17,50 +17,33 @@ int fail(jdsp_ctx *ctx, int code, const char *what, hipError_t e)
     return code;
 }
 
-int ensure_stft1024_table(jdsp_ctx *ctx)
+// window_kind: 0 Hamming, 1 Hann, 2 rectangular
+static int ensure_stft1024_table_of(jdsp_ctx *ctx, DevBuf<float2> &table, int window_kind)
 {
-    if (ctx->stft1024_table) return 0;
-    const int n = stft1024_table_count();
-    std::vector<float2> host((size_t)n);
-    fill_stft1024_table(host.data(), 0);
-    JDSP_HIP(ctx, hipMalloc((void **)&ctx->stft1024_table, sizeof(float2) * (size_t)n));
-    JDSP_HIP(ctx, hipMemcpy(ctx->stft1024_table, host.data(), sizeof(float2) * (size_t)n, hipMemcpyHostToDevice));
-    return 0;
+    return ensure_table(ctx, table, (size_t)stft1024_table_count(),
+                        [window_kind](float2 *t) { fill_stft1024_table(t, window_kind); });
 }
 
-int ensure_stft1024_table_rect(jdsp_ctx *ctx)
-{
-    if (ctx->stft1024_table_rect) return 0;
-    const int n = stft1024_table_count();
-    std::vector<float2> host((size_t)n);
-    fill_stft1024_table(host.data(), 2);
-    JDSP_HIP(ctx, hipMalloc((void **)&ctx->stft1024_table_rect, sizeof(float2) * (size_t)n));
-    JDSP_HIP(ctx, hipMemcpy(ctx->stft1024_table_rect, host.data(), sizeof(float2) * (size_t)n, hipMemcpyHostToDevice));
-    return 0;
-}
+int ensure_stft1024_table(jdsp_ctx *ctx) { return ensure_stft1024_table_of(ctx, ctx->stft1024_table, 0); }
+
+int ensure_stft1024_table_rect(jdsp_ctx *ctx) { return ensure_stft1024_table_of(ctx, ctx->stft1024_table_rect, 2); }
 
 int ensure_vad_window(jdsp_ctx *ctx)
 {
-    if (ctx->vad_w_hi) return 0;
-    double w[512];
-    for (int i = 0; i < 512; i++) w[i] = (0.54 - 0.46 * cos(2 * 3.141592 * (512 + i) / (1024 - 1)));   // SS:131
-    JDSP_HIP(ctx, hipMalloc((void **)&ctx->vad_w_hi, sizeof(w)));
-    JDSP_HIP(ctx, hipMemcpy(ctx->vad_w_hi, w, sizeof(w), hipMemcpyHostToDevice));
-    return 0;
+    return ensure_table(ctx, ctx->vad_w_hi, 512, [](double *w) {
+        for (int i = 0; i < 512; i++) w[i] = (0.54 - 0.46 * cos(2 * 3.141592 * (512 + i) / (1024 - 1)));   // SS:131
+    });
 }
 
 int ensure_vad_window_ex(jdsp_ctx *ctx, int variant, int block_len, const double **w_out)
 {
-    const int bi = block_len == 512 ? 0 : 1;
-    if (!ctx->vad_w_ex[variant][bi]) {
-        const int n = 2 * block_len, keep = variant == 0 ? block_len : block_len - 1;
-        double w[512];
+    DevBuf<double> &buf = ctx->vad_w_ex[variant][block_len == 512 ? 0 : 1];
+    const int n = 2 * block_len, keep = variant == 0 ? block_len : block_len - 1;
+    const int rc = ensure_table(ctx, buf, (size_t)block_len, [=](double *w) {
         for (int i = 0; i < block_len; i++) w[i] = (0.54 - 0.46 * cos(2 * 3.141592 * (keep + i) / (n - 1)));   // SS:131 / BF:217
-        JDSP_HIP(ctx, hipMalloc((void **)&ctx->vad_w_ex[variant][bi], sizeof(double) * block_len));
-        JDSP_HIP(ctx, hipMemcpy(ctx->vad_w_ex[variant][bi], w, sizeof(double) * block_len, hipMemcpyHostToDevice));
-    }
-    *w_out = ctx->vad_w_ex[variant][bi];
-    return 0;
+    });
+    *w_out = buf.get();
+    return rc;
 }
 
 }  // namespace jdsp
@@ -112,31 +95,15 @@ int jdsp_destroy(jdsp_ctx *ctx)
     if (!ctx) return JDSP_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stft1024_table) (void)hipFree(ctx->stft1024_table);
-    if (ctx->stft_f64_table) (void)hipFree(ctx->stft_f64_table);
-    for (auto &p : ctx->c2c_tw)
-        if (p) (void)hipFree(p);
-    if (ctx->vad_w_hi) (void)hipFree(ctx->vad_w_hi);
-    for (auto &row : ctx->vad_w_ex)
-        for (auto &p : row)
-            if (p) (void)hipFree(p);
-    for (auto &p : ctx->lpc_win)
-        if (p) (void)hipFree(p);
-    if (ctx->win512) (void)hipFree(ctx->win512);
-    if (ctx->win512_hann) (void)hipFree(ctx->win512_hann);
-    if (ctx->stft1024_table_hann) (void)hipFree(ctx->stft1024_table_hann);
-    if (ctx->stft1024_table_rect) (void)hipFree(ctx->stft1024_table_rect);
-    for (auto &p : ctx->pipe_buf)
-        if (p) (void)hipFree(p);
-    for (auto &ev : ctx->pipe_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (ctx->pipe_in) (void)hipStreamDestroy(ctx->pipe_in);
-    if (ctx->pipe_out) (void)hipStreamDestroy(ctx->pipe_out);
-    if (ctx->conv_tw4096) (void)hipFree(ctx->conv_tw4096);
-    if (ctx->conv_tw8192) (void)hipFree(ctx->conv_tw8192);
-    if (ctx->switch_ev) (void)hipEventDestroy(ctx->switch_ev);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+    // the events and streams outlive the buffers, which go with the context
+    const hipEvent_t events[] = {ctx->pipe_ev[0], ctx->pipe_ev[1], ctx->pipe_ev[2], ctx->pipe_ev[3],
+                                 ctx->pipe_ev[4], ctx->pipe_ev[5], ctx->switch_ev};
+    const hipStream_t streams[] = {ctx->pipe_in, ctx->pipe_out, ctx->own_stream};
     delete ctx;
+    for (hipEvent_t ev : events)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipStream_t st : streams)
+        if (st) (void)hipStreamDestroy(st);
     return JDSP_OK;
 }
 
@@ -314,7 +281,7 @@ int jdsp_fft_process_f64_dev(jdsp_ctx *ctx, const double *in_dev, double *out_de
         if (rc_tw) return rc_tw;
     }
     if (jdsp::launch_fft_process_f64(ctx->stream, (const double2 *)in_dev, (double2 *)out_dev, n_fft, lg, batch, forward,
-                                     ctx->c2c_tw[lg]))
+                                     ctx->c2c_tw[lg].get()))
         return fail(ctx, JDSP_EHIP, "fft_process_f64 launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -381,7 +348,7 @@ int jdsp_pitch_autocorr_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_blocks
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = jdsp::ensure_stft1024_table(ctx);
     if (rc) return rc;
-    if (jdsp::launch_pitch(ctx->stream, pcm_dev, n_blocks, prev_block_dev, ctx->stft1024_table, arg_dev, rmax_dev,
+    if (jdsp::launch_pitch(ctx->stream, pcm_dev, n_blocks, prev_block_dev, ctx->stft1024_table.get(), arg_dev, rmax_dev,
                            autocorr_dev))
         return fail(ctx, JDSP_EHIP, "pitch launch", hipGetLastError());
     return JDSP_OK;
@@ -424,23 +391,12 @@ int jdsp_stft_i16_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames, int 
     int rc = jdsp::ensure_stft1024_table(ctx);
     if (rc) return rc;
     const int wk = ctx->opt_stft_window;
-    if (wk == 1 && !ctx->stft1024_table_hann) {          // same tables, Hann in the window slots
-        const int n = jdsp::stft1024_table_count();
-        std::vector<float2> host((size_t)n);
-        jdsp::fill_stft1024_table(host.data(), 1);
-        JDSP_HIP(ctx, hipMalloc((void **)&ctx->stft1024_table_hann, sizeof(float2) * (size_t)n));
-        JDSP_HIP(ctx, hipMemcpy(ctx->stft1024_table_hann, host.data(), sizeof(float2) * (size_t)n, hipMemcpyHostToDevice));
-    }
-    const float2 *tab = wk == 1 ? ctx->stft1024_table_hann : ctx->stft1024_table;
+    if (wk == 1 && (rc = jdsp::ensure_stft1024_table_of(ctx, ctx->stft1024_table_hann, 1))) return rc;   // same tables, Hann in the window slots
+    const float2 *tab = wk == 1 ? ctx->stft1024_table_hann.get() : ctx->stft1024_table.get();
     if (n_fft == 512) {
-        float2 *&w512 = wk == 1 ? ctx->win512_hann : ctx->win512;
-        if (!w512) {
-            float2 w[256];
-            jdsp::fill_win512(w, wk);
-            JDSP_HIP(ctx, hipMalloc((void **)&w512, sizeof(w)));
-            JDSP_HIP(ctx, hipMemcpy(w512, w, sizeof(w), hipMemcpyHostToDevice));
-        }
-        if (jdsp::launch_stft512(ctx->stream, ctx->n_cu, pcm_dev, n_frames, hop, (float2 *)spec_dev, tab, w512))
+        jdsp::DevBuf<float2> &w512 = wk == 1 ? ctx->win512_hann : ctx->win512;
+        if ((rc = jdsp::ensure_table(ctx, w512, 256, [wk](float2 *w) { jdsp::fill_win512(w, wk); }))) return rc;
+        if (jdsp::launch_stft512(ctx->stream, ctx->n_cu, pcm_dev, n_frames, hop, (float2 *)spec_dev, tab, w512.get()))
             return fail(ctx, JDSP_EHIP, "stft512 launch", hipGetLastError());
         return JDSP_OK;
     }
@@ -461,7 +417,7 @@ int jdsp_stft_half_i16_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames,
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = jdsp::ensure_stft1024_table(ctx);
     if (rc) return rc;
-    if (jdsp::launch_stft1024_half(ctx->stream, pcm_dev, n_frames, (float2 *)spec_dev, row_pitch, ctx->stft1024_table))
+    if (jdsp::launch_stft1024_half(ctx->stream, pcm_dev, n_frames, (float2 *)spec_dev, row_pitch, ctx->stft1024_table.get()))
         return fail(ctx, JDSP_EHIP, "stft half launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -492,13 +448,7 @@ static int stft_pipelined(jdsp_ctx *ctx, const int16_t *pcm_host, long n_frames,
     const size_t in_cap = sizeof(int16_t) * (size_t)(kPipeFrames * hop + n_fft), out_cap = sizeof(jdsp_c32) * (size_t)kPipeFrames * n_fft;
     for (int b = 0; b < 4; b++) {
         const size_t want = b < 2 ? in_cap : out_cap;
-        if (ctx->pipe_cap[b] < want) {
-            if (ctx->pipe_buf[b]) (void)hipFree(ctx->pipe_buf[b]);
-            ctx->pipe_buf[b] = nullptr;
-            ctx->pipe_cap[b] = 0;
-            if ((e = hipMalloc(&ctx->pipe_buf[b], want)) != hipSuccess) return fail(ctx, JDSP_ENOMEM, "stft pipeline: buffers", e);
-            ctx->pipe_cap[b] = want;
-        }
+        if ((e = ctx->pipe_buf[b].grow(want)) != hipSuccess) return fail(ctx, JDSP_ENOMEM, "stft pipeline: buffers", e);
     }
     hipEvent_t *ev_in = ctx->pipe_ev, *ev_comp = ctx->pipe_ev + 2, *ev_out = ctx->pipe_ev + 4;
     hipStream_t comp = ctx->stream;
@@ -507,8 +457,8 @@ static int stft_pipelined(jdsp_ctx *ctx, const int16_t *pcm_host, long n_frames,
     for (long f0 = 0; f0 < n_frames && !rc; f0 += kPipeFrames, c++) {
         const int b = (int)(c & 1);
         const long nf = n_frames - f0 < kPipeFrames ? n_frames - f0 : kPipeFrames;
-        int16_t *d_in = (int16_t *)ctx->pipe_buf[b];
-        jdsp_c32 *d_out = (jdsp_c32 *)ctx->pipe_buf[2 + b];
+        int16_t *d_in = (int16_t *)ctx->pipe_buf[b].get();
+        jdsp_c32 *d_out = (jdsp_c32 *)ctx->pipe_buf[2 + b].get();
         if (c >= 2) e = hipStreamWaitEvent(ctx->pipe_in, ev_comp[b], 0);          // the transform that read d_in is done
         if (e == hipSuccess) e = hipMemcpyAsync(d_in, pcm_host + f0 * hop, sizeof(int16_t) * (size_t)((nf - 1) * hop + n_fft), hipMemcpyHostToDevice, ctx->pipe_in);
         if (e == hipSuccess) e = hipEventRecord(ev_in[b], ctx->pipe_in);
@@ -530,12 +480,8 @@ static int stft_pipelined(jdsp_ctx *ctx, const int16_t *pcm_host, long n_frames,
 
 static int ensure_c2c_tw(jdsp_ctx *ctx, int n_fft, int lg)
 {
-    if (ctx->c2c_tw[lg]) return JDSP_OK;
-    std::vector<double2> host((size_t)n_fft / 2 + 1);
-    jdsp::fill_c2c_twiddles(host.data(), n_fft);
-    JDSP_HIP(ctx, hipMalloc((void **)&ctx->c2c_tw[lg], sizeof(double2) * host.size()));
-    JDSP_HIP(ctx, hipMemcpy(ctx->c2c_tw[lg], host.data(), sizeof(double2) * host.size(), hipMemcpyHostToDevice));
-    return JDSP_OK;
+    return jdsp::ensure_table(ctx, ctx->c2c_tw[lg], (size_t)n_fft / 2 + 1,
+                              [n_fft](double2 *t) { jdsp::fill_c2c_twiddles(t, n_fft); });
 }
 
 int jdsp_stft_i16_f64_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames, int n_fft, int hop, double *spec_dev)
@@ -550,12 +496,7 @@ int jdsp_stft_i16_f64_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames, 
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_c2c_tw(ctx, 512, 9);
     if (rc) return rc;
-    if (!ctx->stft_f64_table) {
-        std::vector<double> host(1024 + 2 * 512);
-        jdsp::fill_stft1024_f64_table(host.data());
-        JDSP_HIP(ctx, hipMalloc((void **)&ctx->stft_f64_table, sizeof(double) * host.size()));
-        JDSP_HIP(ctx, hipMemcpy(ctx->stft_f64_table, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice));
-    }
+    if ((rc = jdsp::ensure_table(ctx, ctx->stft_f64_table, 1024 + 2 * 512, jdsp::fill_stft1024_f64_table))) return rc;
     // hop-512 batches out of HBM: the read pass of the FP32 path (stft_kernels.hip), slab by slab -- the transform then
     // finds its PCM in the Infinity Cache and the memory system sees a read stream, then a write stream
     const int rp = ctx->opt_stft_read_pass;
@@ -564,7 +505,7 @@ int jdsp_stft_i16_f64_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames, 
     for (long f0 = 0; f0 < n_frames; f0 += slab) {
         const long nf = n_frames - f0 < slab ? n_frames - f0 : slab;
         if ((touch && jdsp::launch_pcm_read_pass(ctx->stream, ctx->n_cu, ctx->opt_stft_touch_wg, pcm_dev + f0 * hop, hop * (nf + 1))) ||
-            jdsp::launch_stft1024_f64(ctx->stream, ctx->n_cu, pcm_dev + f0 * hop, nf, hop, ctx->stft_f64_table, ctx->c2c_tw[9],
+            jdsp::launch_stft1024_f64(ctx->stream, ctx->n_cu, pcm_dev + f0 * hop, nf, hop, ctx->stft_f64_table.get(), ctx->c2c_tw[9].get(),
                                       (double2 *)spec_dev + f0 * 1024, ctx->opt_stft_f64_kernel, ctx->opt_stft_f64_fpw)) {
             const hipError_t le = hipGetLastError();
             return fail(ctx, JDSP_EHIP, "stft f64 launch", le);

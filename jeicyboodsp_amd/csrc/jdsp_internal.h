@@ -12,6 +12,59 @@
 
 #include "../../include/jdsp.h"
 
+namespace jdsp {
+
+// Owner of one device allocation of count() elements: move-only, freed by the destructor.  Every step hands back HIP's
+// own error -- the JDSP_* code and the message stay the caller's -- and after a failed one the buffer is empty
+// (get() == nullptr, count() == 0).  It sets no device and synchronises nothing: both are the caller's job.
+template <class T> class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = o.p_, n_ = o.n_;
+            o.p_ = nullptr, o.n_ = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+
+    T *get() const { return p_; }
+    size_t count() const { return n_; }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr, n_ = 0;
+    }
+    // frees what it holds first: the peak footprint is one allocation, not two
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        void *p = nullptr;      // hipMalloc leaves it alone when it fails
+        const hipError_t e = hipMalloc(&p, count * sizeof(T));
+        if (e == hipSuccess) p_ = (T *)p, n_ = count;
+        return e;
+    }
+    // all or nothing: a buffer whose copy failed is not kept
+    hipError_t upload(const T *host, size_t count)
+    {
+        hipError_t e = alloc(count);
+        if (e == hipSuccess && (e = hipMemcpy(p_, host, count * sizeof(T), hipMemcpyHostToDevice)) != hipSuccess) reset();
+        return e;
+    }
+    // contents are not carried over
+    hipError_t grow(size_t count) { return count <= n_ ? hipSuccess : alloc(count); }
+
+private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+
+}  // namespace jdsp
+
 struct jdsp_ctx {
     int device = 0;
     int n_cu = 0;
@@ -28,22 +81,21 @@ struct jdsp_ctx {
     int opt_stft_touch_wg = 0;         // tuning: workgroups per CU of that pass (0 = default)
     int opt_stft_f64_kernel = 0;       // 0: stft1024_f64_v2_kernel, 1: round 2's stft1024_f64_kernel (A/B)
     int opt_stft_f64_fpw = 0;          // frames one wave of the FP64 analysis walks (0 = one round of resident waves)
-    float2 *stft1024_table_hann = nullptr, *win512_hann = nullptr;
-    float2 *stft1024_table_rect = nullptr;   // rectangular window: the partitioned convolver's forward frames
-    // device tables, created on first use
-    float2 *stft1024_table = nullptr;
-    float2 *win512 = nullptr;          // halved Hamming-512 pairs
-    double2 *c2c_tw[16] = {nullptr};   // by log2(n_fft)
-    double *stft_f64_table = nullptr;  // FP64 STFT: window + split twiddles (fft_c2c_kernels.hip)
-    float2 *conv_tw4096 = nullptr, *conv_tw8192 = nullptr;
-    double *vad_w_hi = nullptr;        // second half of the FP64 Hamming window
-    double *vad_w_ex[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // jdsp_vad_blocks_ex: [variant][block 512 | 256]
-    double *lpc_win[2] = {nullptr, nullptr};   // jdsp_lpc: FP64 Hamming(2 block_len), block 256 | 512
+    // device tables, created on first use (jdsp::ensure_table)
+    jdsp::DevBuf<float2> stft1024_table;
+    jdsp::DevBuf<float2> stft1024_table_hann, win512_hann;
+    jdsp::DevBuf<float2> stft1024_table_rect;   // rectangular window: the partitioned convolver's forward frames
+    jdsp::DevBuf<float2> win512;             // halved Hamming-512 pairs
+    jdsp::DevBuf<double2> c2c_tw[16];        // by log2(n_fft)
+    jdsp::DevBuf<double> stft_f64_table;     // FP64 STFT: window + split twiddles (fft_c2c_kernels.hip)
+    jdsp::DevBuf<float2> conv_tw4096, conv_tw8192;   // made together; conv_tw8192 goes up last, so it stands for both
+    jdsp::DevBuf<double> vad_w_hi;           // second half of the FP64 Hamming window
+    jdsp::DevBuf<double> vad_w_ex[2][2];     // jdsp_vad_blocks_ex: [variant][block 512 | 256]
+    jdsp::DevBuf<double> lpc_win[2];         // jdsp_lpc: FP64 Hamming(2 block_len), block 256 | 512
     // pinned-host pipeline of jdsp_stft_i16: copy-in / compute / copy-out on three streams
     hipStream_t pipe_in = nullptr, pipe_out = nullptr;
     hipEvent_t pipe_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void *pipe_buf[4] = {nullptr, nullptr, nullptr, nullptr};   // in[2], out[2]
-    size_t pipe_cap[4] = {0, 0, 0, 0};
+    jdsp::DevBuf<char> pipe_buf[4];    // in[2], out[2]
 };
 
 namespace jdsp {
@@ -135,20 +187,14 @@ public:
     HostCall(jdsp_ctx *ctx, const char *entry) : ctx_(ctx), entry_(entry) {}
     HostCall(const HostCall &) = delete;
     HostCall &operator=(const HostCall &) = delete;
-    ~HostCall()
-    {
-        for (int i = 0; i < n_; i++) (void)hipFree(buf_[i]);
-    }
 
     bool ok() const { return rc_ == JDSP_OK; }
     template <class T> T *alloc(size_t bytes)
     {
         if (!ok()) return nullptr;
-        void *p = nullptr;
-        const hipError_t e = n_ < kMaxBufs ? hipMalloc(&p, bytes ? bytes : 1) : hipErrorOutOfMemory;
+        const hipError_t e = n_ < kMaxBufs ? buf_[n_].alloc(bytes ? bytes : 1) : hipErrorOutOfMemory;
         step(JDSP_ENOMEM, "hipMalloc", e);
-        if (p) buf_[n_++] = p;
-        return (T *)p;
+        return e == hipSuccess ? (T *)buf_[n_++].get() : nullptr;
     }
     template <class T> T *upload(const T *host, size_t bytes)
     {
@@ -196,9 +242,43 @@ private:
     static constexpr int kMaxBufs = 8;
     jdsp_ctx *ctx_;
     const char *entry_;
-    void *buf_[kMaxBufs];
+    DevBuf<char> buf_[kMaxBufs];
     int n_ = 0;
     int rc_ = JDSP_OK;
+};
+
+// A device table made on first use: JDSP_OK at once when `buf` holds it; otherwise fill(host) writes its `count`
+// elements and they go up whole or not at all, so a table that exists is a table that was filled.
+template <class T, class Fill> int ensure_table(jdsp_ctx *ctx, DevBuf<T> &buf, size_t count, Fill fill)
+{
+    if (buf.get()) return JDSP_OK;
+    std::vector<T> host(count);
+    fill(host.data());
+    const hipError_t e = buf.upload(host.data(), count);
+    return e == hipSuccess ? JDSP_OK : fail(ctx, JDSP_EHIP, "device table", e);
+}
+
+// The per-call arrays of the run-length plan (launch_run_plan, launch_denoise_plan) for calls of up to cap_blocks
+// blocks.  reserve() is all or nothing; the early return when the workspace is large enough, the stream synchronise
+// before anything is freed and the error code stay with the handle's own reserve function.
+struct RunPlanWs {
+    DevBuf<unsigned char> flags;            // [n] the VAD's decision per block
+    DevBuf<int> events, ev_n;               // [n]
+    DevBuf<int> ver_base;                   // [n / 64 + 1]
+    DevBuf<unsigned long long> snap_mask;   // [n / 64 + 1]
+    long cap_blocks = 0;
+
+    hipError_t reserve(size_t n)
+    {
+        hipError_t e = flags.alloc(n);
+        if (e == hipSuccess) e = events.alloc(n);
+        if (e == hipSuccess) e = ev_n.alloc(n);
+        if (e == hipSuccess) e = ver_base.alloc(n / 64 + 1);
+        if (e == hipSuccess) e = snap_mask.alloc(n / 64 + 1);
+        if (e == hipSuccess) cap_blocks = (long)n;
+        else *this = RunPlanWs();
+        return e;
+    }
 };
 
 // stft_kernels.hip
@@ -379,46 +459,46 @@ struct jdsp_denoise {
     jdsp_ctx *ctx = nullptr;
     int mode = 0;
     long calls = 0;                       // blocks consumed so far (the reference's call counters)
-    jdsp::DenoiseState *st[2] = {nullptr, nullptr};
+    jdsp::DevBuf<jdsp::DenoiseState> st[2];
     int cur = 0;                          // st[cur] is the state the next call reads
-    double *w_hi = nullptr;               // the VAD's window: second half of the FP64 Hamming(2 block), the context's or w_hi256
-    long cap_blocks = 0;                  // workspace capacity (plan arrays)
-    unsigned char *flags = nullptr;
-    int *ev_n = nullptr, *ver_base = nullptr, *events = nullptr;
-    unsigned long long *snap_mask = nullptr;
-    long long *dbg_energy = nullptr;
-    int *dbg_zcr = nullptr;
-    jdsp::DenoisePlan *plan = nullptr;
-    float *rows = nullptr;                // [cap_rows][1024] latched estimates of the call (row 0: the one carried in)
-    long cap_rows = 0;                    // rows of `rows` / entries of acc.lat_*
-    jdsp::NoiseAccum acc = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const double *w_hi = nullptr;         // borrowed: the VAD's window, second half of the FP64 Hamming(2 block) -- the context's or w_hi256
+    jdsp::DevBuf<jdsp::DenoisePlan> plan;
+    // sized by jdsp_denoise_reserve for calls of up to run.cap_blocks blocks
+    struct Workspace {
+        jdsp::RunPlanWs run;
+        jdsp::DevBuf<long long> dbg_energy;
+        jdsp::DevBuf<int> dbg_zcr;
+        jdsp::DevBuf<float> rows;         // [n / 10 + 2][1024] latched estimates of the call (row 0: the one carried in)
+        // jdsp::NoiseAccum's arrays
+        jdsp::DevBuf<float> chunk_alpha, chunk_beta, a_start, lat_alpha;
+        jdsp::DevBuf<int> lat_chunk;
+    } ws;
     long last_blocks = 0;
     int opt_k = 0;
     int opt_vad_trace = 0;                // 1: keep every block's energy sum and ZCR for jdsp_denoise_vad_trace (slower VAD kernel)
     int last_trace_valid = 0;             // the option's value when the last call ran: what jdsp_denoise_vad_trace may hand out
     int n_fft = 1024, block = 512;        // FFT_PROCESSING_SIZE, BLOCK_LEN = KEEP_LEN (SS:53-55); 512 / 256 also built
-    double *w_hi256 = nullptr;            // 512-point frames: second half of the FP64 Hamming(512) (VAD)
-    float *win512h = nullptr;             // 512-point frames: 0.5 * Hamming(512), natural order
+    jdsp::DevBuf<double> w_hi256;         // 512-point frames: second half of the FP64 Hamming(512) (VAD)
+    jdsp::DevBuf<float> win512h;          // 512-point frames: 0.5 * Hamming(512), natural order
     // sharded (multi-GPU) run in progress: jdsp_denoise_shard_*
     long sh_ext0 = 0, sh_b0 = 0, sh_b1 = 0, sh_total = 0;
-    const int16_t *sh_pcm = nullptr;
-    int *sh_range = nullptr;              // device: {first event, one past last event, latches before the shard}
-    float *sh_a_in = nullptr;             // device: [1024]
-    int *sh_zero_run = nullptr;           // device: a zero (run length entering a fresh global stream)
+    const int16_t *sh_pcm = nullptr;      // borrowed: the caller's PCM of the run
+    jdsp::DevBuf<int> sh_range;           // {first event, one past last event, latches before the shard}
+    jdsp::DevBuf<float> sh_a_in;          // [1024]
+    jdsp::DevBuf<int> sh_zero_run;        // a zero (run length entering a fresh global stream)
 };
 
 struct jdsp_mfcc {
     jdsp_ctx *ctx = nullptr;
     jdsp_mfcc_cfg cfg;
-    jdsp::MfccDev dev;
-    void *blob = nullptr;                 // one device allocation holding every table
-    int *redo = nullptr;                  // 512-FFT configurations: {count, frame pairs to recompute apart} (mfcc512_run_kernel)
-    long redo_cap = 0;                    // pairs it holds
+    jdsp::MfccDev dev;                    // its pointers are views into blob
+    jdsp::DevBuf<char> blob;              // one device allocation holding every table
+    jdsp::DevBuf<int> redo;               // 512-FFT configurations: {count, frame pairs to recompute apart} (mfcc512_run_kernel)
     std::vector<double> mel_freqs, fbank;
     std::vector<int> fi_bins;
     // FP64 tables of the separately callable sub-steps (stage_api.hip), built on first use
-    void *stage_blob = nullptr;
-    const double *stage_fb = nullptr, *stage_cos = nullptr, *stage_lift = nullptr;
+    jdsp::DevBuf<char> stage_blob;
+    const double *stage_fb = nullptr, *stage_cos = nullptr, *stage_lift = nullptr;   // views into stage_blob
     const int *stage_fi = nullptr;
 };
 
@@ -426,7 +506,7 @@ struct jdsp_gmm {
     jdsp_ctx *ctx = nullptr;
     int n_classes = 0;
     int fused = 0;                        // "evaluation" option: 0 the reference's operation order, 1 fused
-    double *records = nullptr;            // [n_classes][kGmmRecord]
+    jdsp::DevBuf<double> records;         // [n_classes][kGmmRecord]
 };
 
 struct jdsp_gmm_trainer {
@@ -434,19 +514,18 @@ struct jdsp_gmm_trainer {
     int n_classes = 0;
     int threads = 256;                    // "threads_per_class"
     int kmeans_max_passes = 10000;        // "kmeans_max_passes"
-    jdsp::GmmTrainState *state = nullptr; // [n_classes]
-    jdsp_gmm_train_param *out = nullptr;  // [n_classes]: the host entry's staging of jdsp_gmm_train_params
-    unsigned char *sel = nullptr;         // [frames]: k-means Selection bits
-    double *wbuf = nullptr;               // [frames][4]: E-step weights
-    long cap_frames = 0;
+    jdsp::DevBuf<jdsp::GmmTrainState> state;   // [n_classes]
+    jdsp::DevBuf<jdsp_gmm_train_param> out;    // [n_classes]: the host entry's staging of jdsp_gmm_train_params
+    jdsp::DevBuf<unsigned char> sel;      // [frames]: k-means Selection bits
+    jdsp::DevBuf<double> wbuf;            // [frames][4]: E-step weights
 };
 
 struct jdsp_geq {
     jdsp_ctx *ctx = nullptr;
     int n_sections = 0;
     long n_streams = 0;
-    double *coeff = nullptr;              // [n_sections][2][3]
-    short *state = nullptr;               // [n_streams][n_sections + 1][2]
+    jdsp::DevBuf<double> coeff;           // [n_sections][2][3]
+    jdsp::DevBuf<short> state;            // [n_streams][n_sections + 1][2]
 };
 
 struct jdsp_nlms {
@@ -454,31 +533,30 @@ struct jdsp_nlms {
     int filter_len = 0;
     long n_streams = 0;
     double mu = 0, compensation = 0;
-    double *coef = nullptr;               // [n_streams][filter_len]
-    short *keep = nullptr;                // [n_streams][filter_len - 1]
+    jdsp::DevBuf<double> coef;            // [n_streams][filter_len]
+    jdsp::DevBuf<short> keep;             // [n_streams][filter_len - 1]
 };
 
 struct jdsp_hmm {
     jdsp_ctx *ctx = nullptr;
     int n_models = 0;
     int fused = 0;                        // "evaluation" option, as jdsp_gmm
-    double *records = nullptr;            // [n_models * 6][kGmmRecord]
-    double *log_trans = nullptr;          // [n_models][6][6], log() taken on the host
-    double *emission = nullptr;           // scratch [frames][n_models * 6], grown on demand
-    long emission_frames = 0;
+    jdsp::DevBuf<double> records;         // [n_models * 6][kGmmRecord]
+    jdsp::DevBuf<double> log_trans;       // [n_models][6][6], log() taken on the host
+    jdsp::DevBuf<double> emission;        // scratch [frames][n_models * 6], grown on demand
 };
 
 struct jdsp_fastconv {
     jdsp_ctx *ctx = nullptr;
     int n_fft = 0, n_taps = 0, n_filters = 0, block = 0, n_hist = 0;
-    float2 *H = nullptr;                  // [n_filters][n_fft]
+    jdsp::DevBuf<float2> H;               // [n_filters][n_fft]
     // uniformly partitioned path (n_fft 8192, block % 512 == 0): see fastconv_kernels.hip
     int n_part = 0;                       // 0: not used
-    float2 *Hp = nullptr;                 // [n_filters][n_part][520]: bins 0..512 of every 512-tap partition
-    short *staged = nullptr;              // [512 n_part + samples of a call]
-    float2 *X = nullptr;                  // [frames][520]
+    jdsp::DevBuf<float2> Hp;              // [n_filters][n_part][520]: bins 0..512 of every 512-tap partition
+    jdsp::DevBuf<short> staged;           // [512 n_part + samples of a call]
+    jdsp::DevBuf<float2> X;               // [frames][520]
     long ws_samples = 0;                  // samples per call the workspace is sized for
-    short *hist[2] = {nullptr, nullptr};  // last n_taps-1 samples of the stream, ping-pong
+    jdsp::DevBuf<short> hist[2];          // last n_taps-1 samples of the stream, ping-pong
     int cur = 0;
     long calls = 0;                       // blocks consumed so far (siNumOfCount)
 };
@@ -487,23 +565,23 @@ struct jdsp_mvdr {
     jdsp_ctx *ctx = nullptr;
     double d_time = 0;
     long calls = 0;
-    jdsp::MvdrState *st[2] = {nullptr, nullptr};
+    jdsp::DevBuf<jdsp::MvdrState> st[2];
     int cur = 0;
-    jdsp::DenoisePlan *plan = nullptr;
-    double2 *steer = nullptr;             // [1024] steering vector's second component per bin
-    double *w_vad = nullptr;              // Hamming[511 .. 1022] in FP64
-    long cap_blocks = 0;
-    unsigned char *flags = nullptr;
-    int *events = nullptr, *ev_n = nullptr, *ver_base = nullptr;
-    unsigned long long *snap_mask = nullptr;
-    double *delta = nullptr, *rver = nullptr;
-    double *tile_sums = nullptr;          // [cap_blocks / 1024 + 1][4] sums of the prefix pass's tiles of 1024 events
-    float4 *wtab = nullptr;               // [min(cap_blocks + 1, kMvdrTableVersions)][1024] per-version weights (mvdr_weights_kernel)
+    jdsp::DevBuf<jdsp::DenoisePlan> plan;
+    jdsp::DevBuf<double2> steer;          // [1024] steering vector's second component per bin
+    jdsp::DevBuf<double> w_vad;           // Hamming[511 .. 1022] in FP64
+    // sized by mvdr_reserve for calls of up to n = run.cap_blocks blocks
+    struct Workspace {
+        jdsp::RunPlanWs run;
+        jdsp::DevBuf<double> delta, rver;
+        jdsp::DevBuf<double> tile_sums;   // [n / 1024 + 1][4] sums of the prefix pass's tiles of 1024 events
+        jdsp::DevBuf<float4> wtab;        // [min(n + 1, kMvdrTableVersions)][1024] per-version weights (mvdr_weights_kernel)
+    } ws;
     // sharded (multi-GPU) run in progress
     long sh_ext0 = 0, sh_b0 = 0, sh_b1 = 0, sh_total = 0;
-    const int16_t *sh_left = nullptr, *sh_right = nullptr;
-    int *sh_range = nullptr;              // device: {first event, one past last, versions before the shard}
-    int *sh_zero_run = nullptr;
+    const int16_t *sh_left = nullptr, *sh_right = nullptr;   // borrowed: the caller's channels of the run
+    jdsp::DevBuf<int> sh_range;           // {first event, one past last, versions before the shard}
+    jdsp::DevBuf<int> sh_zero_run;
 };
 
 struct jdsp_mvdrn {
@@ -513,17 +591,17 @@ struct jdsp_mvdrn {
     double loading = 0;
     long calls = 0;
     int cur = 0;
-    double2 *cov[2] = {nullptr, nullptr};     // [513][64] per-bin covariance, ping-pong
-    short *prev[2] = {nullptr, nullptr};      // [8][512] previous block per microphone
-    int *run_len[2] = {nullptr, nullptr};
-    jdsp::DenoisePlan *plan = nullptr;
-    double2 *steer = nullptr;                 // [513][8]
-    double *w_vad = nullptr;
-    long cap_blocks = 0;
-    unsigned char *flags = nullptr;
-    int *events = nullptr, *ev_n = nullptr, *ver_base = nullptr;
-    unsigned long long *snap_mask = nullptr;
-    float2 *spec = nullptr, *weights = nullptr;
-    double2 *chunk_ws = nullptr;              // [2][chunk_cap][n_bins][64]: per-chunk covariance sums and entering matrices (sized with the workspace)
-    int chunk_cap = 0;
+    jdsp::DevBuf<double2> cov[2];         // [513][64] per-bin covariance, ping-pong
+    jdsp::DevBuf<short> prev[2];          // [8][512] previous block per microphone
+    jdsp::DevBuf<int> run_len[2];
+    jdsp::DevBuf<jdsp::DenoisePlan> plan;
+    jdsp::DevBuf<double2> steer;          // [513][8]
+    jdsp::DevBuf<double> w_vad;
+    // sized by mvdrn_reserve for calls of up to run.cap_blocks blocks
+    struct Workspace {
+        jdsp::RunPlanWs run;
+        jdsp::DevBuf<float2> spec, weights;
+        jdsp::DevBuf<double2> chunk_ws;   // [2][chunk_cap][n_bins][64]: per-chunk covariance sums and entering matrices
+        int chunk_cap = 0;
+    } ws;
 };

@@ -130,13 +130,12 @@ int jdsp_mfcc_create(jdsp_ctx *ctx, const jdsp_mfcc_cfg *cfg, jdsp_mfcc **out)
     memcpy(&host[o_seg], seg.data(), seg.size() * sizeof(int));
     memcpy(&host[o_segw], seg_wc.data(), seg_wc.size() * sizeof(float));
     memcpy(&host[o_chan], chan_src.data(), chan_src.size() * sizeof(int));
-    hipError_t e = hipMalloc(&h->blob, total);
-    if (e == hipSuccess) e = hipMemcpy(h->blob, host.data(), total, hipMemcpyHostToDevice);
+    const hipError_t e = h->blob.upload(host.data(), total);
     if (e != hipSuccess) {
         jdsp_mfcc_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_mfcc_create: tables", e);
     }
-    char *b = (char *)h->blob;
+    const char *b = h->blob.get();
     h->dev.win_len = c.win_len; h->dev.hop = c.hop; h->dev.n_chan = C; h->dev.n_cep = c.n_cep;
     h->dev.bin_stride = c.n_fft == 512 ? 2 : 1;
     h->dev.preemph = (float)c.preemph;
@@ -161,9 +160,6 @@ int jdsp_mfcc_destroy(jdsp_mfcc *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->blob) (void)hipFree(h->blob);
-    if (h->redo) (void)hipFree(h->redo);
-    if (h->stage_blob) (void)hipFree(h->stage_blob);
     delete h;
     return JDSP_OK;
 }
@@ -185,16 +181,13 @@ int jdsp_mfcc_frames_dev(jdsp_mfcc *h, const int16_t *pcm_dev, const int64_t *fr
     if (n_frames < 0 || (n_frames > 0 && (!pcm_dev || !feats_dev))) return fail(ctx, JDSP_EINVAL, "jdsp_mfcc_frames: bad buffer");
     if (n_frames == 0) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    if (h->dev.bin_stride == 2 && (n_frames + 1) / 2 > h->redo_cap) {        // no-op once sized (size it before a graph capture)
+    const size_t n_redo = (size_t)(n_frames + 1) / 2 + 1;                    // the count, then one entry per frame pair
+    if (h->dev.bin_stride == 2 && n_redo > h->redo.count()) {                // no-op once sized (size it before a graph capture)
         JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (h->redo) (void)hipFree(h->redo);
-        h->redo = nullptr;
-        h->redo_cap = 0;
-        JDSP_HIP(ctx, hipMalloc((void **)&h->redo, ((size_t)(n_frames + 1) / 2 + 1) * sizeof(int)));
-        h->redo_cap = (n_frames + 1) / 2;
+        JDSP_HIP(ctx, h->redo.grow(n_redo));
     }
-    if (jdsp::launch_mfcc(ctx->stream, pcm_dev, (const long long *)frame_start_dev, n_frames, h->dev, ctx->stft1024_table,
-                          feats_dev, h->redo))
+    if (jdsp::launch_mfcc(ctx->stream, pcm_dev, (const long long *)frame_start_dev, n_frames, h->dev, ctx->stft1024_table.get(),
+                          feats_dev, h->redo.get()))
         return fail(ctx, JDSP_EHIP, "mfcc launch", hipGetLastError());
     return JDSP_OK;
 }

@@ -3,19 +3,6 @@
 
 using jdsp::fail;
 
-static void mvdr_free_ws(jdsp_mvdr *h)
-{
-    void *p[] = {h->flags, h->events, h->ev_n, h->ver_base, h->snap_mask, h->delta, h->rver, h->tile_sums, h->wtab};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
-    h->flags = nullptr;
-    h->events = h->ev_n = h->ver_base = nullptr;
-    h->snap_mask = nullptr;
-    h->delta = h->rver = h->tile_sums = nullptr;
-    h->wtab = nullptr;
-    h->cap_blocks = 0;
-}
-
 extern "C" {
 
 int jdsp_mvdr_create(jdsp_ctx *ctx, double d_time, jdsp_mvdr **out)
@@ -37,15 +24,13 @@ int jdsp_mvdr_create(jdsp_ctx *ctx, double d_time, jdsp_mvdr **out)
     double w[512];
     for (int i = 0; i < 512; i++) w[i] = (0.54 - 0.46 * cos(2 * 3.141592 * (511 + i) / (1024 - 1)));   // :217, frame offset 511
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void **)&h->st[i], sizeof(jdsp::MvdrState));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->plan, sizeof(jdsp::DenoisePlan));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->steer, sizeof(double2) * 1024);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->w_vad, sizeof(w));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->sh_range, 4 * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->sh_zero_run, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(h->sh_zero_run, 0, sizeof(int));
-    if (e == hipSuccess) e = hipMemcpy(h->steer, steer.data(), sizeof(double2) * 1024, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->w_vad, w, sizeof(w), hipMemcpyHostToDevice);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = h->st[i].alloc(1);
+    if (e == hipSuccess) e = h->plan.alloc(1);
+    if (e == hipSuccess) e = h->sh_range.alloc(4);
+    if (e == hipSuccess) e = h->sh_zero_run.alloc(1);
+    if (e == hipSuccess) e = hipMemset(h->sh_zero_run.get(), 0, sizeof(int));
+    if (e == hipSuccess) e = h->steer.upload(steer.data(), 1024);
+    if (e == hipSuccess) e = h->w_vad.upload(w, 512);
     if (e != hipSuccess) {
         jdsp_mvdr_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_mvdr_create: alloc", e);
@@ -64,14 +49,6 @@ int jdsp_mvdr_destroy(jdsp_mvdr *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    mvdr_free_ws(h);
-    for (int i = 0; i < 2; i++)
-        if (h->st[i]) (void)hipFree(h->st[i]);
-    if (h->plan) (void)hipFree(h->plan);
-    if (h->steer) (void)hipFree(h->steer);
-    if (h->w_vad) (void)hipFree(h->w_vad);
-    if (h->sh_range) (void)hipFree(h->sh_range);
-    if (h->sh_zero_run) (void)hipFree(h->sh_zero_run);
     delete h;
     return JDSP_OK;
 }
@@ -79,7 +56,7 @@ int jdsp_mvdr_destroy(jdsp_mvdr *h)
 int jdsp_mvdr_reset(jdsp_mvdr *h)
 {
     if (!h) return JDSP_EINVAL;
-    for (int i = 0; i < 2; i++) JDSP_HIP(h->ctx, hipMemsetAsync(h->st[i], 0, sizeof(jdsp::MvdrState), h->ctx->stream));
+    for (int i = 0; i < 2; i++) JDSP_HIP(h->ctx, hipMemsetAsync(h->st[i].get(), 0, sizeof(jdsp::MvdrState), h->ctx->stream));
     h->calls = 0;
     h->cur = 0;
     return JDSP_OK;
@@ -95,26 +72,22 @@ long jdsp_mvdr_blocks_out(const jdsp_mvdr *h, long n_blocks)
 static int mvdr_reserve(jdsp_mvdr *h, long n_blocks)
 {
     jdsp_ctx *ctx = h->ctx;
-    if (n_blocks <= h->cap_blocks) return JDSP_OK;
+    if (n_blocks <= h->ws.run.cap_blocks) return JDSP_OK;
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    mvdr_free_ws(h);
+    jdsp_mvdr::Workspace &w = h->ws;
+    w = {};                                           // freed before anything is allocated
     const size_t n = (size_t)n_blocks;
-    hipError_t e = hipMalloc((void **)&h->flags, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->events, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ev_n, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ver_base, (n / 64 + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->snap_mask, (n / 64 + 1) * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->delta, n * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rver, (n + 1) * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->tile_sums, (n / 1024 + 1) * 4 * sizeof(double));
+    hipError_t e = w.run.reserve(n);
+    if (e == hipSuccess) e = w.delta.alloc(n * 4);
+    if (e == hipSuccess) e = w.rver.alloc((n + 1) * 4);
+    if (e == hipSuccess) e = w.tile_sums.alloc((n / 1024 + 1) * 4);
     // a call has at most as many events as blocks: the weight table needs no more rows than that
     const size_t wrows = n + 1 < (size_t)jdsp::kMvdrTableVersions ? n + 1 : (size_t)jdsp::kMvdrTableVersions;
-    if (e == hipSuccess) e = hipMalloc((void **)&h->wtab, sizeof(float4) * wrows * 1024);
+    if (e == hipSuccess) e = w.wtab.alloc(wrows * 1024);
     if (e != hipSuccess) {
-        mvdr_free_ws(h);
+        w = {};
         return fail(ctx, JDSP_ENOMEM, "jdsp_mvdr: workspace", e);
     }
-    h->cap_blocks = n_blocks;
     return JDSP_OK;
 }
 
@@ -133,14 +106,17 @@ int jdsp_mvdr_process_dev(jdsp_mvdr *h, const int16_t *left_dev, const int16_t *
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = mvdr_reserve(h, n_blocks);
     if (rc) return rc;
-    const jdsp::MvdrState *st_in = h->st[h->cur];
-    jdsp::MvdrState *st_out = h->st[h->cur ^ 1];
+    const jdsp::MvdrState *st_in = h->st[h->cur].get();
+    jdsp::MvdrState *st_out = h->st[h->cur ^ 1].get();
     hipStream_t s = ctx->stream;
-    if (jdsp::launch_vad(s, 512, left_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
-        jdsp::launch_run_plan(s, h->flags, n_blocks, &st_in->run_len, &st_out->run_len, 0, h->ver_base, h->snap_mask,
-                              h->events, h->ev_n, h->plan) ||
-        jdsp::launch_mvdr(s, left_dev, right_dev, n_blocks, h->calls, st_in, st_out, h->events, h->plan, h->ver_base,
-                          h->snap_mask, h->delta, h->rver, h->steer, ctx->stft1024_table, out_dev, precast_dev, h->wtab, h->tile_sums))
+    const jdsp_mvdr::Workspace &w = h->ws;
+    const jdsp::RunPlanWs &r = w.run;
+    if (jdsp::launch_vad(s, 512, left_dev, n_blocks, h->w_vad.get(), 0, r.flags.get(), nullptr, nullptr) ||
+        jdsp::launch_run_plan(s, r.flags.get(), n_blocks, &st_in->run_len, &st_out->run_len, 0, r.ver_base.get(),
+                              r.snap_mask.get(), r.events.get(), r.ev_n.get(), h->plan.get()) ||
+        jdsp::launch_mvdr(s, left_dev, right_dev, n_blocks, h->calls, st_in, st_out, r.events.get(), h->plan.get(),
+                          r.ver_base.get(), r.snap_mask.get(), w.delta.get(), w.rver.get(), h->steer.get(),
+                          ctx->stft1024_table.get(), out_dev, precast_dev, w.wtab.get(), w.tile_sums.get()))
         return fail(ctx, JDSP_EHIP, "mvdr launch", hipGetLastError());
     h->cur ^= 1;
     h->calls += n_blocks;
@@ -187,7 +163,7 @@ int jdsp_mvdr_shard_vad_dev(jdsp_mvdr *h, const int16_t *left_ext_dev, const int
     if (rc) return rc;
     h->sh_ext0 = ext0; h->sh_b0 = b0; h->sh_b1 = b1; h->sh_total = n_total;
     h->sh_left = left_ext_dev; h->sh_right = right_ext_dev;
-    if (jdsp::launch_vad(ctx->stream, 512, left_ext_dev + (b0 - ext0) * 512, b1 - b0, h->w_vad, 0, flags_own_dev, nullptr, nullptr))
+    if (jdsp::launch_vad(ctx->stream, 512, left_ext_dev + (b0 - ext0) * 512, b1 - b0, h->w_vad.get(), 0, flags_own_dev, nullptr, nullptr))
         return fail(ctx, JDSP_EHIP, "vad launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -199,11 +175,13 @@ int jdsp_mvdr_shard_summary_dev(jdsp_mvdr *h, const uint8_t *flags_all_dev, doub
     if (!flags_all_dev || !sum4_dev) return fail(ctx, JDSP_EINVAL, "jdsp_mvdr_shard_summary: NULL buffer");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (jdsp::launch_run_plan(s, flags_all_dev, h->sh_total, h->sh_zero_run, nullptr, 0, h->ver_base, h->snap_mask, h->events,
-                              h->ev_n, h->plan) ||
+    const jdsp::RunPlanWs &r = h->ws.run;
+    if (jdsp::launch_run_plan(s, flags_all_dev, h->sh_total, h->sh_zero_run.get(), nullptr, 0, r.ver_base.get(),
+                              r.snap_mask.get(), r.events.get(), r.ev_n.get(), h->plan.get()) ||
         jdsp::launch_mvdr_shard_summary(s, h->sh_left, h->sh_right, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0, h->sh_b1,
-                                        h->st[h->cur], h->events, h->plan, h->ver_base, h->snap_mask, ctx->stft1024_table,
-                                        h->sh_range, h->delta, sum4_dev, h->tile_sums))
+                                        h->st[h->cur].get(), r.events.get(), h->plan.get(), r.ver_base.get(),
+                                        r.snap_mask.get(), ctx->stft1024_table.get(), h->sh_range.get(), h->ws.delta.get(),
+                                        sum4_dev, h->ws.tile_sums.get()))
         return fail(ctx, JDSP_EHIP, "mvdr shard summary launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -226,9 +204,10 @@ int jdsp_mvdr_shard_finish_dev(jdsp_mvdr *h, const double *sums_all_dev, int wor
         return fail(ctx, JDSP_EINVAL, "jdsp_mvdr_shard_finish: bad argument");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     if (jdsp::launch_mvdr_shard_finish(ctx->stream, h->sh_left, h->sh_right, h->sh_b1 - h->sh_ext0, h->sh_ext0, h->sh_b0,
-                                       h->sh_b1, h->st[h->cur], h->st[h->cur ^ 1], h->plan, h->ver_base, h->snap_mask,
-                                       h->sh_range, h->delta, sums_all_dev, rank, h->rver, h->steer, ctx->stft1024_table,
-                                       out_dev, precast_dev, h->tile_sums))
+                                       h->sh_b1, h->st[h->cur].get(), h->st[h->cur ^ 1].get(), h->plan.get(),
+                                       h->ws.run.ver_base.get(), h->ws.run.snap_mask.get(), h->sh_range.get(),
+                                       h->ws.delta.get(), sums_all_dev, rank, h->ws.rver.get(), h->steer.get(),
+                                       ctx->stft1024_table.get(), out_dev, precast_dev, h->ws.tile_sums.get()))
         return fail(ctx, JDSP_EHIP, "mvdr shard finish launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -255,11 +234,12 @@ int jdsp_mvdr_estimate_corr(jdsp_mvdr *h, const int16_t *left_frames_host, const
     const int16_t *d_l = hc.upload(left_frames_host, in_b);
     const int16_t *d_r = hc.upload(right_frames_host, in_b);
     double *d_tot = hc.alloc<double>(4 * sizeof(double));
-    hc.upload_to(h->events, ev.data(), sizeof(int) * (size_t)n_frames);
-    hc.upload_to(h->plan, &plan, sizeof(plan));
+    hc.upload_to(h->ws.run.events.get(), ev.data(), sizeof(int) * (size_t)n_frames);
+    hc.upload_to(h->plan.get(), &plan, sizeof(plan));
     double tot[4] = {0, 0, 0, 0};
-    if (hc.ok() && jdsp::launch_mvdr_corr_total(s, d_l, d_r, 2 * n_frames, h->st[h->cur], h->events, h->plan,
-                                                ctx->stft1024_table, h->delta, d_tot, h->tile_sums))
+    if (hc.ok() && jdsp::launch_mvdr_corr_total(s, d_l, d_r, 2 * n_frames, h->st[h->cur].get(), h->ws.run.events.get(),
+                                                h->plan.get(), ctx->stft1024_table.get(), h->ws.delta.get(), d_tot,
+                                                h->ws.tile_sums.get()))
         hc.result(fail(ctx, JDSP_EHIP, "mvdr corr launch", hipGetLastError()));
     hc.download(tot, d_tot, sizeof(tot));
     rc = hc.finish();
@@ -283,19 +263,22 @@ int jdsp_mvdr_apply(jdsp_mvdr *h, const int16_t *left_host, const int16_t *right
     if (rc) return rc;
     const size_t in_b = (size_t)n_blocks * 1024, out_b = (size_t)(n_out > 0 ? n_out : 1) * 1024;
     hipStream_t s = ctx->stream;
-    jdsp::MvdrState *st_in = h->st[h->cur], *st_out = h->st[h->cur ^ 1];
+    jdsp::MvdrState *st_in = h->st[h->cur].get(), *st_out = h->st[h->cur ^ 1].get();
+    double *rver = h->ws.rver.get();
+    int *ver_base = h->ws.run.ver_base.get();
+    unsigned long long *snap_mask = h->ws.run.snap_mask.get();
     jdsp::HostCall hc(ctx, "jdsp_mvdr_apply");
     const int16_t *d_l = hc.upload(left_host, in_b);
     const int16_t *d_r = hc.upload(right_host, in_b);
     int16_t *d_out = hc.alloc<int16_t>(out_b);
     float *d_pre = precast_host ? hc.alloc<float>(out_b * 2) : nullptr;
     // every block uses matrix version 0 = the caller's rgdSpatialCorr; the handle's own matrix and run length carry over
-    hc.upload_to(h->rver, corr4_host, 4 * sizeof(double));
-    hc.zero(h->ver_base, ((size_t)n_blocks / 64 + 1) * sizeof(int));
-    hc.zero(h->snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
+    hc.upload_to(rver, corr4_host, 4 * sizeof(double));
+    hc.zero(ver_base, ((size_t)n_blocks / 64 + 1) * sizeof(int));
+    hc.zero(snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
     hc.copy_dev(st_out, st_in, sizeof(jdsp::MvdrState));
-    if (hc.ok() && jdsp::launch_mvdr_apply(s, d_l, d_r, n_blocks, h->calls, st_in, st_out, h->ver_base, h->snap_mask, h->rver,
-                                           h->steer, ctx->stft1024_table, d_out, d_pre))
+    if (hc.ok() && jdsp::launch_mvdr_apply(s, d_l, d_r, n_blocks, h->calls, st_in, st_out, ver_base, snap_mask, rver,
+                                           h->steer.get(), ctx->stft1024_table.get(), d_out, d_pre))
         hc.result(fail(ctx, JDSP_EHIP, "mvdr launch", hipGetLastError()));
     hc.download(out_host, d_out, (size_t)n_out * 1024);
     hc.download(precast_host, d_pre, (size_t)n_out * 2048);
@@ -311,7 +294,7 @@ int jdsp_mvdr_corr(jdsp_mvdr *h, double *corr4_host)
 {
     if (!h || !corr4_host) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
-    JDSP_HIP(ctx, hipMemcpyAsync(corr4_host, h->st[h->cur]->corr, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    JDSP_HIP(ctx, hipMemcpyAsync(corr4_host, h->st[h->cur].get()->corr, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JDSP_OK;
 }

@@ -3,20 +3,6 @@
 
 using jdsp::fail;
 
-static void mvdrn_free_ws(jdsp_mvdrn *h)
-{
-    void *p[] = {h->flags, h->events, h->ev_n, h->ver_base, h->snap_mask, h->spec, h->weights, h->chunk_ws};
-    for (void *q : p)
-        if (q) (void)hipFree(q);
-    h->flags = nullptr;
-    h->events = h->ev_n = h->ver_base = nullptr;
-    h->snap_mask = nullptr;
-    h->spec = h->weights = nullptr;
-    h->chunk_ws = nullptr;
-    h->chunk_cap = 0;
-    h->cap_blocks = 0;
-}
-
 extern "C" {
 
 int jdsp_mvdrn_create(jdsp_ctx *ctx, int n_mics, const double *delays_s, double loading, jdsp_mvdrn **out)
@@ -55,15 +41,13 @@ int jdsp_mvdrn_create_cfg(jdsp_ctx *ctx, int n_mics, const double *delays_s, dou
     for (int i = 0; i < h->block; i++) w[i] = (0.54 - 0.46 * cos(2 * 3.141592 * (keep + i) / (n_fft - 1)));   // :217
     hipError_t e = hipSuccess;
     for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipMalloc((void **)&h->cov[i], sizeof(double2) * 513 * 64);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->prev[i], sizeof(short) * 512 * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->run_len[i], sizeof(int));
+        e = h->cov[i].alloc(513 * 64);
+        if (e == hipSuccess) e = h->prev[i].alloc(512 * 8);
+        if (e == hipSuccess) e = h->run_len[i].alloc(1);
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&h->plan, sizeof(jdsp::DenoisePlan));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->steer, sizeof(double2) * steer.size());
-    if (e == hipSuccess) e = hipMalloc((void **)&h->w_vad, sizeof(w));
-    if (e == hipSuccess) e = hipMemcpy(h->steer, steer.data(), sizeof(double2) * steer.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(h->w_vad, w, sizeof(w), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = h->plan.alloc(1);
+    if (e == hipSuccess) e = h->steer.upload(steer.data(), steer.size());
+    if (e == hipSuccess) e = h->w_vad.upload(w, 512);
     if (e != hipSuccess) {
         jdsp_mvdrn_destroy(h);
         return fail(ctx, JDSP_EHIP, "jdsp_mvdrn_create: alloc", e);
@@ -82,15 +66,6 @@ int jdsp_mvdrn_destroy(jdsp_mvdrn *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    mvdrn_free_ws(h);
-    for (int i = 0; i < 2; i++) {
-        if (h->cov[i]) (void)hipFree(h->cov[i]);
-        if (h->prev[i]) (void)hipFree(h->prev[i]);
-        if (h->run_len[i]) (void)hipFree(h->run_len[i]);
-    }
-    if (h->plan) (void)hipFree(h->plan);
-    if (h->steer) (void)hipFree(h->steer);
-    if (h->w_vad) (void)hipFree(h->w_vad);
     delete h;
     return JDSP_OK;
 }
@@ -100,9 +75,9 @@ int jdsp_mvdrn_reset(jdsp_mvdrn *h)
     if (!h) return JDSP_EINVAL;
     hipStream_t s = h->ctx->stream;
     for (int i = 0; i < 2; i++) {
-        JDSP_HIP(h->ctx, hipMemsetAsync(h->cov[i], 0, sizeof(double2) * 513 * 64, s));
-        JDSP_HIP(h->ctx, hipMemsetAsync(h->prev[i], 0, sizeof(short) * 512 * 8, s));
-        JDSP_HIP(h->ctx, hipMemsetAsync(h->run_len[i], 0, sizeof(int), s));
+        JDSP_HIP(h->ctx, hipMemsetAsync(h->cov[i].get(), 0, sizeof(double2) * 513 * 64, s));
+        JDSP_HIP(h->ctx, hipMemsetAsync(h->prev[i].get(), 0, sizeof(short) * 512 * 8, s));
+        JDSP_HIP(h->ctx, hipMemsetAsync(h->run_len[i].get(), 0, sizeof(int), s));
     }
     h->calls = 0;
     h->cur = 0;
@@ -119,28 +94,24 @@ long jdsp_mvdrn_blocks_out(const jdsp_mvdrn *h, long n_blocks)
 static int mvdrn_reserve(jdsp_mvdrn *h, long n_blocks)
 {
     jdsp_ctx *ctx = h->ctx;
-    if (n_blocks <= h->cap_blocks) return JDSP_OK;
+    if (n_blocks <= h->ws.run.cap_blocks) return JDSP_OK;
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    mvdrn_free_ws(h);
+    jdsp_mvdrn::Workspace &w = h->ws;
+    w = {};                                           // freed before anything is allocated
     const size_t n = (size_t)n_blocks;
-    hipError_t e = hipMalloc((void **)&h->flags, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->events, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ev_n, n * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->ver_base, (n / 64 + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->snap_mask, (n / 64 + 1) * sizeof(unsigned long long));
+    hipError_t e = w.run.reserve(n);
     // worst case: every block is an estimation frame -- one spectrum set and one weight set per block
-    if (e == hipSuccess) e = hipMalloc((void **)&h->spec, n * h->n_mics * (size_t)h->n_bins * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->weights, (n + 1) * (size_t)h->n_bins * 8 * sizeof(float2));
+    if (e == hipSuccess) e = w.spec.alloc(n * h->n_mics * (size_t)h->n_bins);
+    if (e == hipSuccess) e = w.weights.alloc((n + 1) * (size_t)h->n_bins * 8);
     // the chunked covariance update's sums and entering matrices: a call of n blocks has at most min(n, kMvnChunks) chunks
     // (1 KB per bin and chunk: 134 MB at 128 chunks of 513 bins -- a per-block caller gets 1 MB)
     const int chunk_cap = (int)(n < (size_t)jdsp::kMvnChunks ? n : (size_t)jdsp::kMvnChunks);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->chunk_ws, sizeof(double2) * 2 * (size_t)chunk_cap * (size_t)h->n_bins * 64);
+    if (e == hipSuccess) e = w.chunk_ws.alloc(2 * (size_t)chunk_cap * (size_t)h->n_bins * 64);
     if (e != hipSuccess) {
-        mvdrn_free_ws(h);
+        w = {};
         return fail(ctx, JDSP_ENOMEM, "jdsp_mvdrn: workspace", e);
     }
-    h->cap_blocks = n_blocks;
-    h->chunk_cap = chunk_cap;
+    w.chunk_cap = chunk_cap;
     return JDSP_OK;
 }
 
@@ -161,25 +132,18 @@ int jdsp_mvdrn_process_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stri
     if (rc) return rc;
     const int in = h->cur, ou = h->cur ^ 1;
     hipStream_t s = ctx->stream;
-    if (h->n_fft == 512) {
-        if (jdsp::launch_vad(s, 256, pcm_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
-            jdsp::launch_run_plan(s, h->flags, n_blocks, h->run_len[in], h->run_len[ou], 0, h->ver_base, h->snap_mask,
-                                  h->events, h->ev_n, h->plan) ||
-            jdsp::launch_mvdrn512(s, pcm_dev, chan_stride, h->n_mics, n_blocks, h->calls, h->prev[in], h->prev[ou], h->events,
-                                  h->plan, h->ver_base, h->snap_mask, h->spec, h->cov[in], h->cov[ou], h->steer, h->loading,
-                                  h->weights, ctx->stft1024_table, out_dev, precast_dev, h->chunk_ws, h->chunk_cap))
-            return fail(ctx, JDSP_EHIP, "mvdrn512 launch", hipGetLastError());
-        h->cur ^= 1;
-        h->calls += n_blocks;
-        return JDSP_OK;
-    }
-    if (jdsp::launch_vad(s, 512, pcm_dev, n_blocks, h->w_vad, 0, h->flags, nullptr, nullptr) ||
-        jdsp::launch_run_plan(s, h->flags, n_blocks, h->run_len[in], h->run_len[ou], 0, h->ver_base, h->snap_mask, h->events,
-                              h->ev_n, h->plan) ||
-        jdsp::launch_mvdrn(s, pcm_dev, chan_stride, h->n_mics, n_blocks, h->calls, h->prev[in], h->prev[ou], h->events,
-                           h->plan, h->ver_base, h->snap_mask, h->spec, h->cov[in], h->cov[ou], h->steer, h->loading,
-                           h->weights, ctx->stft1024_table, out_dev, precast_dev, h->chunk_ws, h->chunk_cap))
-        return fail(ctx, JDSP_EHIP, "mvdrn launch", hipGetLastError());
+    const jdsp_mvdrn::Workspace &w = h->ws;
+    const jdsp::RunPlanWs &r = w.run;
+    const bool half = h->n_fft == 512;
+    if (jdsp::launch_vad(s, h->block, pcm_dev, n_blocks, h->w_vad.get(), 0, r.flags.get(), nullptr, nullptr) ||
+        jdsp::launch_run_plan(s, r.flags.get(), n_blocks, h->run_len[in].get(), h->run_len[ou].get(), 0, r.ver_base.get(),
+                              r.snap_mask.get(), r.events.get(), r.ev_n.get(), h->plan.get()) ||
+        (half ? jdsp::launch_mvdrn512 : jdsp::launch_mvdrn)(
+            s, pcm_dev, chan_stride, h->n_mics, n_blocks, h->calls, h->prev[in].get(), h->prev[ou].get(), r.events.get(),
+            h->plan.get(), r.ver_base.get(), r.snap_mask.get(), w.spec.get(), h->cov[in].get(), h->cov[ou].get(),
+            h->steer.get(), h->loading, w.weights.get(), ctx->stft1024_table.get(), out_dev, precast_dev, w.chunk_ws.get(),
+            w.chunk_cap))
+        return fail(ctx, JDSP_EHIP, half ? "mvdrn512 launch" : "mvdrn launch", hipGetLastError());
     h->cur ^= 1;
     h->calls += n_blocks;
     return JDSP_OK;

@@ -86,25 +86,21 @@ namespace {
 // them (:131-150), cos(PI i (k-0.5)/C) of :180 and the lifter weights of :189 from the host's libm.
 int ensure_stage_tables(jdsp_mfcc *h)
 {
-    if (h->stage_blob) return JDSP_OK;
-    jdsp_ctx *ctx = h->ctx;
     const int NB = h->cfg.n_fft / 2, C = h->cfg.n_chan, NC = h->cfg.n_cep;
     const double PI = 3.141592;                                                  // MFCC:26
-    std::vector<double> cosv((size_t)NC * C), lift(NC);
-    for (int i = 1; i <= NC; i++) {
-        for (int k = 1; k <= C; k++) cosv[(size_t)(i - 1) * C + (k - 1)] = cos(PI * i * (k - 0.5) / (double)C);
-        lift[i - 1] = (1 + 0.5 * h->cfg.lifter * sin(PI * i / h->cfg.lifter));
-    }
-    const size_t o_fb = 0, o_cos = o_fb + sizeof(double) * NB, o_lift = o_cos + sizeof(double) * cosv.size(),
+    const size_t o_fb = 0, o_cos = o_fb + sizeof(double) * NB, o_lift = o_cos + sizeof(double) * NC * C,
                  o_fi = o_lift + sizeof(double) * NC, total = o_fi + sizeof(int) * NB;
-    std::vector<char> host(total);
-    memcpy(&host[o_fb], h->fbank.data(), sizeof(double) * NB);
-    memcpy(&host[o_cos], cosv.data(), sizeof(double) * cosv.size());
-    memcpy(&host[o_lift], lift.data(), sizeof(double) * NC);
-    memcpy(&host[o_fi], h->fi_bins.data(), sizeof(int) * NB);
-    JDSP_HIP(ctx, hipMalloc(&h->stage_blob, total));
-    JDSP_HIP(ctx, hipMemcpy(h->stage_blob, host.data(), total, hipMemcpyHostToDevice));
-    char *b = (char *)h->stage_blob;
+    const int rc = jdsp::ensure_table(h->ctx, h->stage_blob, total, [&](char *host) {
+        double *cosv = (double *)(host + o_cos), *lift = (double *)(host + o_lift);
+        for (int i = 1; i <= NC; i++) {
+            for (int k = 1; k <= C; k++) cosv[(size_t)(i - 1) * C + (k - 1)] = cos(PI * i * (k - 0.5) / (double)C);
+            lift[i - 1] = (1 + 0.5 * h->cfg.lifter * sin(PI * i / h->cfg.lifter));
+        }
+        memcpy(host + o_fb, h->fbank.data(), sizeof(double) * NB);
+        memcpy(host + o_fi, h->fi_bins.data(), sizeof(int) * NB);
+    });
+    if (rc) return rc;
+    const char *b = h->stage_blob.get();
     h->stage_fb = (const double *)(b + o_fb);
     h->stage_cos = (const double *)(b + o_cos);
     h->stage_lift = (const double *)(b + o_lift);

@@ -6,13 +6,14 @@ using jdsp::fail;
 struct jdsp_stftmask {
     jdsp_ctx *ctx = nullptr;
     jdsp_stftmask_cfg cfg;
-    float *blob = nullptr;                // device: wa[n] (w_a / 2), ws[n] (w_s), g[hop], tail[2][n]
-    float *wa = nullptr, *ws = nullptr, *g = nullptr, *tail[2] = {nullptr, nullptr};
+    jdsp::DevBuf<float> blob;             // wa[n] (w_a / 2), ws[n] (w_s), g[hop], tail[2][n]
+    float *wa = nullptr, *ws = nullptr, *g = nullptr, *tail[2] = {nullptr, nullptr};   // views into blob
     int cur = 0;                          // tail[cur] holds the partial sums the next call starts from
     int run_opt = 0;                      // "frames_per_wave": 0 = auto
-    // host entry points' device buffers, grown on demand
-    void *hbuf[4] = {nullptr, nullptr, nullptr, nullptr};   // PCM, mask, int16, float32
-    size_t hcap[4] = {0, 0, 0, 0};
+    // host entry points' device buffers, grown on demand (those entries end with a synchronise: none is in use then)
+    jdsp::DevBuf<int16_t> h_pcm, h_i16;
+    jdsp::DevBuf<char> h_mask;            // bytes: rows of float or jdsp_c32
+    jdsp::DevBuf<float> h_f32;
 };
 
 static constexpr int kBins = 513;         // n/2 + 1 of the one supported n_fft
@@ -23,17 +24,6 @@ static double window_at(int kind, int i, int n)
     if (kind == JDSP_WIN_NONE) return 1.0;
     const double a = kind == JDSP_WIN_HANN ? 0.5 : 0.54, b = kind == JDSP_WIN_HANN ? 0.5 : 0.46;
     return a - b * cos(2 * 3.141592 * i / (n - 1));
-}
-
-static int grow(jdsp_stftmask *h, int i, size_t bytes)
-{
-    if (h->hcap[i] >= bytes) return JDSP_OK;
-    if (h->hbuf[i]) (void)hipFree(h->hbuf[i]);
-    h->hbuf[i] = nullptr;
-    h->hcap[i] = 0;
-    JDSP_HIP(h->ctx, hipMalloc(&h->hbuf[i], bytes));
-    h->hcap[i] = bytes;
-    return JDSP_OK;
 }
 
 static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -85,14 +75,14 @@ int jdsp_stftmask_create(jdsp_ctx *ctx, const jdsp_stftmask_cfg *cfg, jdsp_stftm
     h->ctx = ctx;
     h->cfg = c;
     const size_t floats = 2 * (size_t)n + hop + 2 * (size_t)n;
-    hipError_t e = hipMalloc((void **)&h->blob, floats * sizeof(float));
+    hipError_t e = h->blob.alloc(floats);
     if (e == hipSuccess) {
-        h->wa = h->blob;
-        h->ws = h->blob + n;
-        h->g = h->blob + 2 * n;
-        h->tail[0] = h->blob + 2 * n + hop;
+        h->wa = h->blob.get();
+        h->ws = h->wa + n;
+        h->g = h->ws + n;
+        h->tail[0] = h->g + hop;
         h->tail[1] = h->tail[0] + n;
-        e = hipMemcpy(h->blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+        e = hipMemcpy(h->wa, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         jdsp_stftmask_destroy(h);
@@ -112,9 +102,6 @@ int jdsp_stftmask_destroy(jdsp_stftmask *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->blob) (void)hipFree(h->blob);
-    for (void *p : h->hbuf)
-        if (p) (void)hipFree(p);
     delete h;
     return JDSP_OK;
 }
@@ -163,7 +150,7 @@ int jdsp_stftmask_process_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const vo
     const int cur = h->cur;
     if (jdsp::launch_stftmask(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev, mask_dev,
                               mask_pitch, n_frames, h->wa, h->ws, h->g, h->tail[cur], h->tail[cur ^ 1], out_i16_dev,
-                              out_f32_dev, ctx->stft1024_table, h->run_opt))
+                              out_f32_dev, ctx->stft1024_table.get(), h->run_opt))
         return fail(ctx, JDSP_EHIP, "jdsp_stftmask_process: launch", hipGetLastError());
     h->cur = cur ^ 1;
     return JDSP_OK;
@@ -192,21 +179,21 @@ int jdsp_stftmask_process(jdsp_stftmask *h, const int16_t *pcm_host, const void 
     if (n_frames == 0) return JDSP_OK;
     if (!pcm_host || !mask_host) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_process: pcm or mask is NULL");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t pcm_bytes = ((size_t)(n_frames - 1) * h->cfg.hop + h->cfg.n_fft) * sizeof(int16_t);
+    const size_t n_pcm = (size_t)(n_frames - 1) * h->cfg.hop + h->cfg.n_fft;
     const size_t mask_bytes = ((size_t)(n_frames - 1) * mask_pitch + kBins) * mask_elem(h);
     const size_t n_out = (size_t)n_frames * h->cfg.hop;
-    int rc = grow(h, 0, pcm_bytes);
-    if (!rc) rc = grow(h, 1, mask_bytes);
-    if (!rc && out_i16_host) rc = grow(h, 2, n_out * sizeof(int16_t));
-    if (!rc && out_f32_host) rc = grow(h, 3, n_out * sizeof(float));
-    if (rc) return rc;
-    int16_t *d_i16 = out_i16_host ? (int16_t *)h->hbuf[2] : nullptr;
-    float *d_f32 = out_f32_host ? (float *)h->hbuf[3] : nullptr;
-    jdsp::HostCall hc(ctx, "jdsp_stftmask_process");                    // the buffers are the handle's (grow)
-    hc.upload_to(h->hbuf[0], pcm_host, pcm_bytes);
-    hc.upload_to(h->hbuf[1], mask_host, mask_bytes);
+    hipError_t e = h->h_pcm.grow(n_pcm);
+    if (e == hipSuccess) e = h->h_mask.grow(mask_bytes);
+    if (e == hipSuccess && out_i16_host) e = h->h_i16.grow(n_out);
+    if (e == hipSuccess && out_f32_host) e = h->h_f32.grow(n_out);
+    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_stftmask_process: buffers", e);
+    int16_t *d_i16 = out_i16_host ? h->h_i16.get() : nullptr;
+    float *d_f32 = out_f32_host ? h->h_f32.get() : nullptr;
+    jdsp::HostCall hc(ctx, "jdsp_stftmask_process");                    // the buffers are the handle's
+    hc.upload_to(h->h_pcm.get(), pcm_host, n_pcm * sizeof(int16_t));
+    hc.upload_to(h->h_mask.get(), mask_host, mask_bytes);
     if (hc.ok())
-        hc.result(jdsp_stftmask_process_dev(h, (const int16_t *)h->hbuf[0], h->hbuf[1], mask_pitch, n_frames, d_i16, d_f32));
+        hc.result(jdsp_stftmask_process_dev(h, h->h_pcm.get(), h->h_mask.get(), mask_pitch, n_frames, d_i16, d_f32));
     hc.download(out_i16_host, d_i16, n_out * sizeof(int16_t));
     hc.download(out_f32_host, d_f32, n_out * sizeof(float));
     return hc.finish();
@@ -218,12 +205,12 @@ int jdsp_stftmask_flush(jdsp_stftmask *h, int16_t *out_i16_host, float *out_f32_
     jdsp_ctx *ctx = h->ctx;
     const size_t n_tail = (size_t)(h->cfg.n_fft - h->cfg.hop);
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = JDSP_OK;
-    if (n_tail && out_i16_host) rc = grow(h, 2, n_tail * sizeof(int16_t));
-    if (!rc && n_tail && out_f32_host) rc = grow(h, 3, n_tail * sizeof(float));
-    if (rc) return rc;
-    int16_t *d_i16 = n_tail && out_i16_host ? (int16_t *)h->hbuf[2] : nullptr;
-    float *d_f32 = n_tail && out_f32_host ? (float *)h->hbuf[3] : nullptr;
+    hipError_t e = hipSuccess;
+    if (n_tail && out_i16_host) e = h->h_i16.grow(n_tail);
+    if (e == hipSuccess && n_tail && out_f32_host) e = h->h_f32.grow(n_tail);
+    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_stftmask_flush: buffers", e);
+    int16_t *d_i16 = n_tail && out_i16_host ? h->h_i16.get() : nullptr;
+    float *d_f32 = n_tail && out_f32_host ? h->h_f32.get() : nullptr;
     jdsp::HostCall hc(ctx, "jdsp_stftmask_flush");
     hc.result(jdsp_stftmask_flush_dev(h, d_i16, d_f32));
     hc.download(out_i16_host, d_i16, n_tail * sizeof(int16_t));

@@ -125,11 +125,10 @@ int jdsp_geq_create(jdsp_ctx *ctx, const double *coeff, int n_sections, long n_s
     h->ctx = ctx;
     h->n_sections = n_sections;
     h->n_streams = n_streams;
-    const size_t cb = sizeof(double) * 6 * (size_t)n_sections, sb = sizeof(short) * 2 * (size_t)(n_sections + 1) * (size_t)n_streams;
-    hipError_t e = hipMalloc((void **)&h->coeff, cb);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->state, sb);
-    if (e == hipSuccess) e = hipMemcpy(h->coeff, coeff, cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemsetAsync(h->state, 0, sb, ctx->stream);
+    const size_t n_state = 2 * (size_t)(n_sections + 1) * (size_t)n_streams;
+    hipError_t e = h->coeff.upload(coeff, 6 * (size_t)n_sections);
+    if (e == hipSuccess) e = h->state.alloc(n_state);
+    if (e == hipSuccess) e = hipMemsetAsync(h->state.get(), 0, sizeof(short) * n_state, ctx->stream);
     if (e != hipSuccess) {
         jdsp_geq_destroy(h);
         return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_geq_create", e);
@@ -143,8 +142,6 @@ int jdsp_geq_destroy(jdsp_geq *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->coeff) (void)hipFree(h->coeff);
-    if (h->state) (void)hipFree(h->state);
     delete h;
     return JDSP_OK;
 }
@@ -152,7 +149,7 @@ int jdsp_geq_destroy(jdsp_geq *h)
 int jdsp_geq_reset(jdsp_geq *h)
 {
     if (!h) return JDSP_EINVAL;
-    JDSP_HIP(h->ctx, hipMemsetAsync(h->state, 0, sizeof(short) * 2 * (size_t)(h->n_sections + 1) * (size_t)h->n_streams, h->ctx->stream));
+    JDSP_HIP(h->ctx, hipMemsetAsync(h->state.get(), 0, sizeof(short) * h->state.count(), h->ctx->stream));
     return JDSP_OK;
 }
 
@@ -160,7 +157,7 @@ int jdsp_geq_get_state(jdsp_geq *h, int16_t *state_host)
 {
     if (!h || !state_host) return JDSP_EINVAL;
     jdsp::HostCall hc(h->ctx, "jdsp_geq_get_state");
-    hc.download(state_host, h->state, sizeof(short) * 2 * (size_t)(h->n_sections + 1) * (size_t)h->n_streams);
+    hc.download(state_host, h->state.get(), sizeof(short) * h->state.count());
     return hc.finish();
 }
 
@@ -168,7 +165,7 @@ int jdsp_geq_set_state(jdsp_geq *h, const int16_t *state_host)
 {
     if (!h || !state_host) return JDSP_EINVAL;
     jdsp::HostCall hc(h->ctx, "jdsp_geq_set_state");
-    hc.upload_to(h->state, state_host, sizeof(short) * 2 * (size_t)(h->n_sections + 1) * (size_t)h->n_streams);
+    hc.upload_to(h->state.get(), state_host, sizeof(short) * h->state.count());
     return hc.finish();
 }
 
@@ -182,7 +179,7 @@ int jdsp_geq_process_dev(jdsp_geq *h, const int16_t *pcm_dev, long n_samples, lo
     if (misaligned(pcm_dev) || misaligned(out_dev) || misaligned(precast_dev))
         return fail(ctx, JDSP_EINVAL, "jdsp_geq_process: pcm, out and precast must be 16-byte aligned");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    if (jdsp::launch_geq(ctx->stream, pcm_dev, h->n_streams, n_samples, pitch, h->coeff, h->n_sections, h->state, out_dev, precast_dev))
+    if (jdsp::launch_geq(ctx->stream, pcm_dev, h->n_streams, n_samples, pitch, h->coeff.get(), h->n_sections, h->state.get(), out_dev, precast_dev))
         return fail(ctx, JDSP_EHIP, "geq launch", hipGetLastError());
     return JDSP_OK;
 }
@@ -228,8 +225,8 @@ int jdsp_nlms_create(jdsp_ctx *ctx, int filter_len, double mu, double compensati
     h->n_streams = n_streams;
     h->mu = mu;
     h->compensation = compensation;
-    hipError_t e = hipMalloc((void **)&h->coef, sizeof(double) * (size_t)filter_len * (size_t)n_streams);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->keep, sizeof(short) * (size_t)(filter_len - 1) * (size_t)n_streams);
+    hipError_t e = h->coef.alloc((size_t)filter_len * (size_t)n_streams);
+    if (e == hipSuccess) e = h->keep.alloc((size_t)(filter_len - 1) * (size_t)n_streams);
     if (e != hipSuccess) {
         jdsp_nlms_destroy(h);
         return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_nlms_create", e);
@@ -248,8 +245,6 @@ int jdsp_nlms_destroy(jdsp_nlms *h)
     if (!h) return JDSP_OK;
     (void)hipSetDevice(h->ctx->device);
     (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->coef) (void)hipFree(h->coef);
-    if (h->keep) (void)hipFree(h->keep);
     delete h;
     return JDSP_OK;
 }
@@ -257,8 +252,8 @@ int jdsp_nlms_destroy(jdsp_nlms *h)
 int jdsp_nlms_reset(jdsp_nlms *h)
 {
     if (!h) return JDSP_EINVAL;
-    JDSP_HIP(h->ctx, hipMemsetAsync(h->coef, 0, sizeof(double) * (size_t)h->filter_len * (size_t)h->n_streams, h->ctx->stream));
-    JDSP_HIP(h->ctx, hipMemsetAsync(h->keep, 0, sizeof(short) * (size_t)(h->filter_len - 1) * (size_t)h->n_streams, h->ctx->stream));
+    JDSP_HIP(h->ctx, hipMemsetAsync(h->coef.get(), 0, sizeof(double) * h->coef.count(), h->ctx->stream));
+    JDSP_HIP(h->ctx, hipMemsetAsync(h->keep.get(), 0, sizeof(short) * h->keep.count(), h->ctx->stream));
     return JDSP_OK;
 }
 
@@ -266,8 +261,8 @@ int jdsp_nlms_get_state(jdsp_nlms *h, double *coef_host, int16_t *keep_host)
 {
     if (!h) return JDSP_EINVAL;
     jdsp::HostCall hc(h->ctx, "jdsp_nlms_get_state");
-    hc.download(coef_host, h->coef, sizeof(double) * (size_t)h->filter_len * (size_t)h->n_streams);
-    hc.download(keep_host, h->keep, sizeof(short) * (size_t)(h->filter_len - 1) * (size_t)h->n_streams);
+    hc.download(coef_host, h->coef.get(), sizeof(double) * h->coef.count());
+    hc.download(keep_host, h->keep.get(), sizeof(short) * h->keep.count());
     return hc.finish();
 }
 
@@ -275,8 +270,8 @@ int jdsp_nlms_set_state(jdsp_nlms *h, const double *coef_host, const int16_t *ke
 {
     if (!h || !coef_host || !keep_host) return JDSP_EINVAL;
     jdsp::HostCall hc(h->ctx, "jdsp_nlms_set_state");
-    hc.upload_to(h->coef, coef_host, sizeof(double) * (size_t)h->filter_len * (size_t)h->n_streams);
-    hc.upload_to(h->keep, keep_host, sizeof(short) * (size_t)(h->filter_len - 1) * (size_t)h->n_streams);
+    hc.upload_to(h->coef.get(), coef_host, sizeof(double) * h->coef.count());
+    hc.upload_to(h->keep.get(), keep_host, sizeof(short) * h->keep.count());
     return hc.finish();
 }
 
@@ -292,7 +287,7 @@ int jdsp_nlms_process_dev(jdsp_nlms *h, const int16_t *input_dev, const int16_t 
         return fail(ctx, JDSP_EINVAL, "jdsp_nlms_process: input, reference, est, err and precast must be 16-byte aligned");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     if (jdsp::launch_nlms(ctx->stream, input_dev, reference_dev, h->n_streams, n_samples, pitch, h->filter_len, h->mu,
-                          h->compensation, h->coef, h->keep, est_dev, err_dev, precast_dev))
+                          h->compensation, h->coef.get(), h->keep.get(), est_dev, err_dev, precast_dev))
         return fail(ctx, JDSP_EHIP, "nlms launch", hipGetLastError());
     return JDSP_OK;
 }

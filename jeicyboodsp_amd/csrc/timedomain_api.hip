@@ -9,14 +9,11 @@ namespace {
 int ensure_lpc_window(jdsp_ctx *ctx, int block_len, const double **w_out)
 {
     const int bi = block_len == 256 ? 0 : 1, n = 2 * block_len;
-    if (!ctx->lpc_win[bi]) {
-        std::vector<double> w((size_t)n);
+    const int rc = jdsp::ensure_table(ctx, ctx->lpc_win[bi], (size_t)n, [n](double *w) {
         for (int i = 0; i < n; i++) w[i] = (double)(0.54 - 0.46 * cos(2 * 3.141592 * i / (double)(n - 1)));
-        JDSP_HIP(ctx, hipMalloc((void **)&ctx->lpc_win[bi], sizeof(double) * n));
-        JDSP_HIP(ctx, hipMemcpy(ctx->lpc_win[bi], w.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    }
-    *w_out = ctx->lpc_win[bi];
-    return 0;
+    });
+    *w_out = ctx->lpc_win[bi].get();
+    return rc;
 }
 
 }  // namespace

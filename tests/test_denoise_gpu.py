@@ -38,6 +38,11 @@ def speechlike(seed, n_blocks, pattern=None):
     return np.clip(np.rint(x), -32768, 32767).astype(np.int16)
 
 
+# Calls that grow, reuse and regrow a handle's workspace: 2 blocks size it, 70 exceed it and cross the 64-block word of the
+# plan's version arrays, 3 reuse it, 130 exceed it again, 1 reuses it.
+GROW_CALLS = [2, 70, 3, 130, 1]
+
+
 def check_stream(out, pre, o_out, o_pre):
     assert out.shape == o_out.shape
     if out.size == 0:
@@ -95,23 +100,25 @@ def test_vad_energy_and_zcr_bit_exact(eng, oracle):
 @pytest.mark.parametrize("mode", [0, 1])
 def test_chunked_streaming_equals_one_shot_and_per_block_calls(eng, oracle, mode):
     """The reference calls its function once per block; any batching must give the same stream."""
-    n_blocks = 97
-    pcm = speechlike(5, n_blocks)
-    o_out, o_pre, *_ = oracle.denoise_trace(mode, pcm)
-    d = eng.denoiser(mode)
-    pieces, pres = [], []
-    pos = 0
-    for n in [1, 1, 1, 2, 7, 1, 30, 1, 1, 52]:
-        o, p = d.process(pcm[pos * 512:(pos + n) * 512], want_precast=True)
-        pieces.append(o)
-        pres.append(p)
-        pos += n
-    assert pos == n_blocks
-    check_stream(np.concatenate(pieces), np.concatenate(pres), o_out, o_pre)
-    d.reset()
-    out2, pre2 = d.process(pcm, want_precast=True)
-    check_stream(out2, pre2, o_out, o_pre)
-    d.close()
+    for calls in ([1, 1, 1, 2, 7, 1, 30, 1, 1, 52], GROW_CALLS):
+        n_blocks = sum(calls)
+        pcm = speechlike(5, n_blocks)
+        o_out, o_pre, *_ = oracle.denoise_trace(mode, pcm)
+        d = eng.denoiser(mode)
+        pieces, pres = [], []
+        pos = 0
+        for n in calls:
+            o, p = d.process(pcm[pos * 512:(pos + n) * 512], want_precast=True)
+            pieces.append(o)
+            pres.append(p)
+            pos += n
+        assert pos == n_blocks
+        check_stream(np.concatenate(pieces), np.concatenate(pres), o_out, o_pre)
+        d.reset()                               # after growth: all state gone, the stream replays in one call
+        out2, pre2 = d.process(pcm, want_precast=True)
+        check_stream(out2, pre2, o_out, o_pre)
+        d.close()
+        eng.denoiser(mode).close()              # a grown handle is gone; the next one starts from nothing
 
 
 @pytest.mark.parametrize("k", [1, 2, 4, 8])
@@ -220,24 +227,29 @@ def test_denoise_512_point_frames_chunked_calls_equal_one_call(eng, oracle, mode
     the last bits of its FP32 spectrum -- depends on where the call boundaries fall; what is required is the
     tolerance every stream is held to: +-1 LSB of the one-call stream and of the oracle."""
     import torch
-    n_blocks = 97
-    pcm = speechlike256(77, n_blocks, pattern=[13, 5, 2, 3, 11, 4, 1, 1, 16, 14])
-    o_out, o_pre = oracle.denoise_stream(mode, pcm, block=256)
-    whole = eng.denoiser(mode, 512, 256)
-    w_out = whole.process(pcm)
-    whole.close()
-    assert np.abs(w_out.astype(np.int32) - o_out.astype(np.int32)).max() <= 1
-    for chunks in ([1] * n_blocks, [2, 5, 1, 7, 14, 3, 65], [96, 1]):
-        d = eng.denoiser(mode, 512, 256)
-        got, b = [], 0
-        for c in chunks:
-            got.append(d.process(torch.from_numpy(pcm[b * 256:(b + c) * 256]).cuda()).cpu().numpy())
-            b += c
-        d.close()
-        got = np.concatenate(got)
-        assert got.shape == w_out.shape, chunks
-        assert np.abs(got.astype(np.int32) - w_out.astype(np.int32)).max() <= 1, chunks
-        assert np.abs(got.astype(np.int32) - o_out.astype(np.int32)).max() <= 1, chunks
+    for n_blocks, chunkings in ((97, ([1] * 97, [2, 5, 1, 7, 14, 3, 65], [96, 1])), (sum(GROW_CALLS), (GROW_CALLS,))):
+        pcm = speechlike256(77, n_blocks, pattern=[13, 5, 2, 3, 11, 4, 1, 1, 16, 14])
+        o_out, o_pre = oracle.denoise_stream(mode, pcm, block=256)
+        whole = eng.denoiser(mode, 512, 256)
+        w_out = whole.process(pcm)
+        whole.close()
+        assert np.abs(w_out.astype(np.int32) - o_out.astype(np.int32)).max() <= 1
+        for chunks in chunkings:
+            d = eng.denoiser(mode, 512, 256)
+            got, b = [], 0
+            for c in chunks:
+                got.append(d.process(torch.from_numpy(pcm[b * 256:(b + c) * 256]).cuda()).cpu().numpy())
+                b += c
+            got = np.concatenate(got)
+            assert got.shape == w_out.shape, chunks
+            assert np.abs(got.astype(np.int32) - w_out.astype(np.int32)).max() <= 1, chunks
+            assert np.abs(got.astype(np.int32) - o_out.astype(np.int32)).max() <= 1, chunks
+            d.reset()                           # after growth: all state gone, the stream replays in one call
+            again = d.process(pcm)
+            assert np.abs(again.astype(np.int32) - w_out.astype(np.int32)).max() <= 1, chunks
+            assert np.abs(again.astype(np.int32) - o_out.astype(np.int32)).max() <= 1, chunks
+            d.close()
+            eng.denoiser(mode, 512, 256).close()        # a grown handle is gone; the next one starts from nothing
 
 
 def test_denoise_512_point_full_batch(eng, oracle):

@@ -135,9 +135,12 @@ def test_mfcc_to_gmm_without_leaving_the_device(eng, oracle):
     m.close()
 
 
-def _check_hmm(eng, oracle, models, x, first):
+def _check_hmm(eng, oracle, models, x, first, h=None):
+    """h: a handle to run on (it stays open); None: one of its own"""
     import torch
-    h = eng.hmm(models)
+    own = h is None
+    if own:
+        h = eng.hmm(models)
     scores, best, path, trellis = h.viterbi(torch.from_numpy(x).cuda(), torch.from_numpy(first).cuda(),
                                             want_trellis=True)
     scores, best, path, trellis = (t.cpu().numpy() for t in (scores, best, path, trellis))
@@ -157,7 +160,8 @@ def _check_hmm(eng, oracle, models, x, first):
         assert best[u] == arg
     hs, hb, hp = h.viterbi(x, first)                                  # host entry = device entry
     assert np.array_equal(hs, scores, equal_nan=True) and np.array_equal(hb, best) and np.array_equal(hp, path)
-    h.close()
+    if own:
+        h.close()
     return scores, path
 
 
@@ -169,6 +173,12 @@ def test_hmm_recursion_finite_regime(eng, oracle):
     scores, path = _check_hmm(eng, oracle, models, x, first)
     assert np.isfinite(scores[0]).any() and path.any()
     assert np.all(scores[1] == 0.0)                                   # one vector: dTempProb keeps its initial 0
+    # one handle's emission buffer: sized by 3 vectors, exceeded by all 95, reused by 23
+    h = eng.hmm(models)
+    for u0, u1 in ((1, 3), (0, 5), (0, 3)):
+        _check_hmm(eng, oracle, models, x[first[u0]:first[u1]], first[u0:u1 + 1] - first[u0], h=h)
+    h.close()
+    eng.hmm(models).close()                                           # a grown handle is gone; the next one starts from nothing
 
 
 def test_hmm_fused_evaluation_option(eng, oracle):

@@ -400,3 +400,18 @@ def test_host_path_matches_device_path(eng):
     td = ist.flush()
     assert np.array_equal(oh, od.cpu().numpy()) and np.array_equal(fh, fd.cpu().numpy()) and np.array_equal(th, td.cpu().numpy())
     ist.close()
+    # the host entries' device buffers: one stream in calls of 5 frames (sizes them), 20 (exceeds them) and 3 (reuses
+    # them) on a fresh handle, against the device path's single call
+    ist = eng.istft(n_fft=1024, hop=512, layout="half", synthesis_window="hann")
+    spec = rows(rng, 28, 1024, pitch=520)
+    od, fd = ist.process(torch.from_numpy(spec).cuda(), want_f32=True)
+    td = ist.flush()
+    od, fd, td = od.cpu().numpy(), fd.cpu().numpy(), td.cpu().numpy()
+    parts = [ist.process(spec[a:b], want_f32=True) for a, b in ((0, 5), (5, 25), (25, 28))]
+    assert np.array_equal(np.concatenate([o for o, _ in parts]), od)
+    assert np.array_equal(np.concatenate([f for _, f in parts]), fd)
+    ist.reset()                              # after growth: the partial sums are gone, the stream replays in one call
+    oh, fh = ist.process(spec, want_f32=True)
+    assert np.array_equal(oh, od) and np.array_equal(fh, fd) and np.array_equal(ist.flush(), td)
+    ist.close()
+    eng.istft(n_fft=1024, hop=512, layout="half", synthesis_window="hann").close()     # after a grown handle is gone

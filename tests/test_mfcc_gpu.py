@@ -80,6 +80,14 @@ def test_baseline_config_400_160_512fft_40mel(eng, oracle):
     omel, ofi, ofb = oracle.mel_init(ocfg)
     assert np.array_equal(mel, omel) and np.array_equal(fi, ofi) and np.array_equal(fb, ofb)
     m.close()
+    # one handle's list of frame pairs to redo: sized by 3 frames (2 pairs), exceeded by 98, reused by 2
+    m = eng.mfcc(**kw)
+    for n in (720, 16000, 560):
+        nf = m.n_frames(n)
+        _check(m.frames(pcm[:n]), oracle.mfcc_frames(ocfg, pcm[:n], nf))
+    assert nf == 2
+    m.close()
+    eng.mfcc(**kw).close()                    # a grown handle is gone; the next one starts from nothing
 
 
 def test_utterance_batch_with_frame_starts(eng, oracle):

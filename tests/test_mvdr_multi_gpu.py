@@ -68,6 +68,25 @@ def test_distortionless_towards_the_steered_source_and_chunked_calls(eng, oracle
     got = pre[(b - 1) * 512:b * 512].astype(np.float64)
     assert np.corrcoef(got, src[b * 512:(b + 1) * 512])[0, 1] > 0.995        # w^H c = 1: the source passes
     m.close()
+    # A workspace that grows, is reused and grows again: 2 blocks size it, 70 exceed it and cross the 64-block word of
+    # the plan's version arrays, 3 reuse it, 130 exceed it again past the 128 chunks of the covariance update, 1 reuses
+    # it.  Quiet runs in the 70-, 3- and 130-block calls, so each has events of its own.
+    calls = [2, 70, 3, 130, 1]
+    pcm, _, delays = array_scene(6, 8, sum(calls), quiet=((0, 14), (40, 12), (72, 3), (90, 25), (150, 40)))
+    o_out, o_pre = oracle.mvdrn_stream(pcm, delays, 1e-3)
+    m = eng.mvdr_multi(8, delays, 1e-3)
+    t = torch.from_numpy(pcm).cuda()
+    outs, pres, pos = [], [], 0
+    for n in calls:
+        o, p = m.process(t[:, pos * 512:(pos + n) * 512].contiguous(), want_precast=True)
+        outs.append(o); pres.append(p); pos += n
+    torch.cuda.synchronize()
+    check(torch.cat(outs).cpu().numpy(), torch.cat(pres).cpu().numpy(), o_out, o_pre)
+    m.reset()                                # after growth: all state gone, the stream replays in one call
+    out, pre = m.process(pcm, want_precast=True)
+    check(out, pre, o_out, o_pre)
+    m.close()
+    eng.mvdr_multi(8, delays, 1e-3).close()  # a grown handle is gone; the next one starts from nothing
 
 
 def test_singular_until_enough_noise_frames_without_loading(eng, oracle):

@@ -355,6 +355,23 @@ def test_host_path_and_null_outputs(eng, hop, kind):
     t3 = sm.flush()
     assert np.array_equal(o3, oh[hop * k:]) and np.array_equal(t3, th)
     sm.close()
+    # the host entries' device buffers: one stream in calls of 5 frames (sizes them), 20 (exceeds them) and 3 (reuses
+    # them) on a fresh handle, against the device path's single call
+    F = 28
+    pcm, mask = pcm_of(rng, F, hop), mask_of(rng, kind, F, pitch=520)
+    sm = eng.stft_mask(**cfg_of(hop, kind, stream_combo(hop)))
+    od, fd = sm.process(torch.from_numpy(pcm).cuda(), torch.from_numpy(mask).cuda(), F, want_f32=True)
+    td = sm.flush()
+    od, fd, td = od.cpu().numpy(), fd.cpu().numpy(), td.cpu().numpy()
+    parts = [sm.process(pcm[hop * a:], mask[a:b], b - a, want_f32=True) for a, b in ((0, 5), (5, 25), (25, 28))]
+    assert np.array_equal(np.concatenate([o for o, _ in parts]), od)
+    assert np.array_equal(np.concatenate([f for _, f in parts]).view(np.int32), fd.view(np.int32))
+    sm.reset()                               # after growth: the partial sums are gone, the stream replays in one call
+    oh, fh = sm.process(pcm, mask, F, want_f32=True)
+    assert np.array_equal(oh, od) and np.array_equal(fh.view(np.int32), fd.view(np.int32))
+    assert np.array_equal(sm.flush(), td)
+    sm.close()
+    eng.stft_mask(**cfg_of(hop, kind, stream_combo(hop))).close()      # after a grown handle is gone
 
 
 # ---- 7. errors -----------------------------------------------------------------------------------------------------
