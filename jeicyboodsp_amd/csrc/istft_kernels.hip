@@ -1,23 +1,17 @@
 // istft_kernels.hip -- STFT synthesis (gfx950): batched inverse transform of caller-given spectra, synthesis window,
 // overlap-add and the (short) cast, as one streaming pass (include/jdsp.h, jdsp_istft_*).
 //
-// One wave per run of consecutive frames (persistent: the launch picks the run so that the batch is about one round of
-// resident waves, in XCD-aware order, as denoise_run_kernel).  Per frame:
+// One wave per run of consecutive frames; what happens to a frame once it is computed -- the overlap-add, the gain, the
+// stores, the tail, the halo and the run order -- is the stream of ola_stream.h.  Per frame:
 //   n = 1024  the real frame comes from ONE 512-point complex inverse through the pre-split of frame_io.h: the rows are
 //             made Hermitian first, H[k] = (X[k] + conj X[-k]) / 2 (FULL: X[-k] read back from a natural-order image
 //             of the row in the wave's LDS, the mirror_fetch_lds pattern; HALF: H[n-k] = conj X[k], the row's lower half
 //             through the same image), so a non-Hermitian row gives exactly the real part of its full inverse.
 //   n = 512   one 512-point complex inverse of H per frame, real part kept.  Never two frames in one transform: a
 //             frame's result must not depend on its neighbour, or on where a call or shard cut falls.
-// Lane l holds frame samples 2 l + 128 d, +1 (n = 1024, one float2 per register) or l + 64 d (n = 512, one float per
-// register), d < 8, so a hop of n / R is HR = 8 / R registers in both cases and the overlap-add is a register shift:
-// after frame f, registers 0..HR-1 are final (emitted) and the rest move down.  Every output sample is the FP32 sum of
-// its frames in ascending order, starting from 0 -- the same operations whatever the call cuts or the launch geometry,
-// so results are bit-identical across both.  A wave whose run starts at frame j0 > 0 recomputes the R - 1 frames
-// before it (the halo); only the wave with j0 = 0 reads the tail carried in the handle, and the wave that owns the
-// call's last frame writes the new tail (ping-pong buffers: another wave may still be reading the old one).
+// The halo frames run through an unrolled loop of their own in front of the run: they need no prefetch and no stores.
 #include "jdsp_internal.h"
-#include "frame_io.h"
+#include "ola_stream.h"
 
 namespace jdsp {
 
@@ -28,23 +22,15 @@ namespace jdsp {
 // (profiles/r04_istft_launch_ab.txt)
 #define JDSP_ISTFT_RESIDENT 2
 #endif
-#ifndef JDSP_ISTFT_MIN_RUN_PER_HALO
-#define JDSP_ISTFT_MIN_RUN_PER_HALO 4   // shortest run, in halo frames (launch_istft)
-#endif
 
 template <int N> struct IstftSample;
 template <> struct IstftSample<1024> { typedef float2 T; };
 template <> struct IstftSample<512> { typedef float T; };
 
-__device__ __forceinline__ float2 ola_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float ola_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float2 ola_mul(float2 a, float2 b) { return make_float2(a.x * b.x, a.y * b.y); }
-__device__ __forceinline__ float ola_mul(float a, float b) { return a * b; }
-// streaming (nontemporal) accesses: the spectra are read once, the outputs written once
+// streaming (nontemporal) loads: the spectra are read once
 #ifndef JDSP_ISTFT_NT_LOAD
 #define JDSP_ISTFT_NT_LOAD 1         // 0: plain loads of the spectra (tools/build_variant.sh A/B)
 #endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float2 nt_load(const float2 *p)
 {
 #if JDSP_ISTFT_NT_LOAD
@@ -54,15 +40,6 @@ __device__ __forceinline__ float2 nt_load(const float2 *p)
     return *p;
 #endif
 }
-__device__ __forceinline__ void nt_store(float2 v, float2 *p)
-{
-    f32x2 w = {v.x, v.y};
-    __builtin_nontemporal_store(w, reinterpret_cast<f32x2 *>(p));
-}
-__device__ __forceinline__ void nt_store(float v, float *p) { __builtin_nontemporal_store(v, p); }
-template <class T> __device__ __forceinline__ T ola_zero();
-template <> __device__ __forceinline__ float2 ola_zero<float2>() { return make_float2(0.f, 0.f); }
-template <> __device__ __forceinline__ float ola_zero<float>() { return 0.f; }
 
 // Spectrum values one lane loads per frame: X[lane + 64 q] for q < kLoads (FULL: the whole row; HALF: bins below n/2,
 // the Nyquist bin X[n/2] comes separately)
@@ -161,31 +138,24 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(Istf
     float2 *const img = lds;
     float2 *const scratch = lds + ((kImg + 1) & ~1);
     const int lane = threadIdx.x;
-    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
-    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * a.run;
-    if (j0 >= a.n_frames) return;
-    const long j1 = j0 + a.run < a.n_frames ? j0 + a.run : a.n_frames;
+    long j0, j1;
+    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
 
     WaveTwiddles tw;
     load_wave_twiddles(tw, table, lane);
     SplitTwiddles sw;
     if (N == 1024) load_split_twiddles(sw, table, lane);
-    T ws[8], g[HR];
+    T ws[8];
     const T *ws_t = reinterpret_cast<const T *>(a.ws);
-    const T *g_t = reinterpret_cast<const T *>(a.g);
 #pragma unroll
     for (int d = 0; d < 8; d++) ws[d] = ws_t[lane + 64 * d];
-#pragma unroll
-    for (int d = 0; d < HR; d++) g[d] = g_t[lane + 64 * d];
 
-    T acc[8], y[8];
+    OlaAcc<T, HR> ola;
+    ola.init(a.g, lane);
+    T y[8], o[HR];
     float2 nx[kL], nnyq = make_float2(0.f, 0.f);
-#pragma unroll
-    for (int d = 0; d < 8; d++) acc[d] = ola_zero<T>();
     if (j0 == 0) {
-        const T *tl = reinterpret_cast<const T *>(a.tail_in);
-#pragma unroll
-        for (int d = 0; d < 8 - HR; d++) acc[d] = tl[lane + 64 * d];
+        ola.load_tail(a.tail_in, lane);
     } else {
         // halo: frames j0 - R + 1 .. j0 - 1 (all >= 0: the launch keeps run >= R - 1)
 #pragma unroll
@@ -194,10 +164,8 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(Istf
             istft_stage<N, HALF>(nx, nnyq, img, lane);
             wave_lds_fence();
             istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
-#pragma unroll
-            for (int d = 0; d < 8; d++) acc[d] = ola_add(acc[d], y[d]);
-#pragma unroll
-            for (int d = 0; d < 8; d++) acc[d] = d + HR < 8 ? acc[d + HR] : ola_zero<T>();
+            ola.add(y, o);
+            ola.shift(false, nullptr, lane);
         }
     }
 
@@ -207,38 +175,13 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(Istf
     for (long j = j0; j < j1; j++) {
         if (j + 1 < j1) istft_load<N, HALF>(a.spec + (j + 1) * a.pitch, lane, nx, nnyq);   // staged one frame from now
         istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
-#pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] = ola_add(acc[d], y[d]);
-        T o[HR];
-#pragma unroll
-        for (int d = 0; d < HR; d++) o[d] = ola_mul(g[d], acc[d]);
+        ola.add(y, o);
         // stage the prefetched row before this frame's stores: vmcnt counts loads and stores in issue order, and a wait
         // for the row at the top of the next iteration would also wait for these stores (denoise_run_kernel)
         if (j + 1 < j1) istft_stage<N, HALF>(nx, nnyq, img, lane);    // the image's reads are behind istft_frame's fence
         __builtin_amdgcn_sched_barrier(0);
-        if (a.out) {
-            if constexpr (N == 1024) {
-                unsigned int *dst = reinterpret_cast<unsigned int *>(a.out + j * HOP) + lane;
-#pragma unroll
-                for (int d = 0; d < HR; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
-            } else {
-                unsigned short *dst = reinterpret_cast<unsigned short *>(a.out + j * HOP) + lane;
-#pragma unroll
-                for (int d = 0; d < HR; d++) __builtin_nontemporal_store((unsigned short)cast_i16_bits(o[d]), dst + 64 * d);
-            }
-        }
-        if (a.out_f32) {
-            T *dst = reinterpret_cast<T *>(a.out_f32 + j * HOP) + lane;
-#pragma unroll
-            for (int d = 0; d < HR; d++) nt_store(o[d], dst + 64 * d);
-        }
-#pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] = d + HR < 8 ? acc[d + HR] : ola_zero<T>();
-        if (j == a.n_frames - 1) {
-            T *tl = reinterpret_cast<T *>(a.tail_out);
-#pragma unroll
-            for (int d = 0; d < 8 - HR; d++) tl[lane + 64 * d] = acc[d];
-        }
+        ola.emit(o, a.out, a.out_f32, j * HOP, lane);
+        ola.shift(j == a.n_frames - 1, a.tail_out, lane);
         wave_lds_fence();                                        // the staged row before the next frame reads it
     }
 }
@@ -275,23 +218,14 @@ int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const fl
 {
     if (n_frames <= 0) return 0;
     const int r = n_fft / hop;
-    // one round of resident waves, but never a run shorter than JDSP_ISTFT_MIN_RUN_PER_HALO (R - 1) frames: the R - 1
-    // halo frames a wave recomputes are then at most 1 / JDSP_ISTFT_MIN_RUN_PER_HALO of its run (extra reads and
-    // transforms) whatever R is; a longer minimum leaves fewer waves for small batches
-    const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_ISTFT_RESIDENT;
-    long run = (n_frames + slots - 1) / slots;
-    const long min_run = r > 1 ? (long)JDSP_ISTFT_MIN_RUN_PER_HALO * (r - 1) : 1;
-    if (run < min_run) run = min_run;
-    if (run_opt > 0) run = run_opt < r - 1 ? r - 1 : run_opt;        // jdsp_istft_set_option("frames_per_wave")
-    const long waves = (n_frames + run - 1) / run;
-    const long grid = (waves + 7) / 8 * 8;
-    IstftArgs a = {spec, pitch, n_frames, ws, g, tail_in, tail_out, out, out_f32, (int)run};
+    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, n_frames, run_opt);
+    IstftArgs a = {spec, pitch, n_frames, ws, g, tail_in, tail_out, out, out_f32, (int)p.run};
     if (n_fft == 1024) {
-        if (half) launch_r<1024, 1>(s, r, grid, a, table);
-        else launch_r<1024, 0>(s, r, grid, a, table);
+        if (half) launch_r<1024, 1>(s, r, p.grid, a, table);
+        else launch_r<1024, 0>(s, r, p.grid, a, table);
     } else {
-        if (half) launch_r<512, 1>(s, r, grid, a, table);
-        else launch_r<512, 0>(s, r, grid, a, table);
+        if (half) launch_r<512, 1>(s, r, p.grid, a, table);
+        else launch_r<512, 0>(s, r, p.grid, a, table);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

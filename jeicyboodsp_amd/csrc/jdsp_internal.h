@@ -453,6 +453,110 @@ int launch_gmm_train(hipStream_t s, int threads, int n_classes, const double *fe
                      GmmTrainState *state, unsigned char *sel, double *wbuf);
 int launch_gmm_train_params(hipStream_t s, int n_classes, const GmmTrainState *state, jdsp_gmm_train_param *out);
 
+// What a jdsp_istft or jdsp_stftmask handle carries of its overlap-add output stream between calls (the kernels' side
+// and the stream's rules: ola_stream.h): the emission gain, the ping-pong tail, the "frames_per_wave" option and the
+// host entries' output staging.  `entry` is the calling entry's name, the prefix of its messages.
+struct OlaStream {
+    jdsp_ctx *ctx = nullptr;
+    int n = 0, hop = 0;
+    float *g = nullptr, *tail[2] = {nullptr, nullptr};   // views into the handle's blob: g[hop], tail[2][n]
+    int cur = 0;                          // tail[cur] holds the partial sums the next call starts from
+    int run_opt = 0;                      // "frames_per_wave": 0 = auto
+    // host entry points' device buffers, grown on demand (those entries end with a synchronise: none is in use then)
+    DevBuf<int16_t> h_i16;
+    DevBuf<float> h_f32;
+
+    // "stft.window"'s formulas (fill_stft1024_table / fill_win512): PI 3.141592 as the reference writes it
+    static double window_at(int kind, int i, int n)
+    {
+        if (kind == JDSP_WIN_NONE) return 1.0;
+        const double a = kind == JDSP_WIN_HANN ? 0.5 : 0.54, b = kind == JDSP_WIN_HANN ? 0.5 : 0.46;
+        return a - b * cos(2 * 3.141592 * i / (n - 1));
+    }
+    // WOLA: gain[i] = 1 / sum_r w_a[i + r hop] w_s[i + r hop], i < hop; 1 when not normalising.  false: the windows'
+    // overlap-add vanishes somewhere (no WOLA inverse), for the caller to report
+    static bool wola_gain(int wa_kind, int ws_kind, int n, int hop, bool normalise, float *gain)
+    {
+        std::vector<double> den((size_t)hop, 1.0);
+        if (normalise) {
+            double mx = 0;
+            for (int i = 0; i < hop; i++) {
+                double s = 0;
+                for (int r = 0; r < n / hop; r++)
+                    s += window_at(wa_kind, i + r * hop, n) * window_at(ws_kind, i + r * hop, n);
+                den[i] = s;
+                mx = s > mx ? s : mx;
+            }
+            for (int i = 0; i < hop; i++)
+                if (!(den[i] >= 1e-6 * mx)) return false;
+        }
+        for (int i = 0; i < hop; i++) gain[i] = (float)(1.0 / den[i]);
+        return true;
+    }
+    static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+    // the stream's share of the handle's blob, the gain first
+    static size_t floats(int n, int hop) { return (size_t)hop + 2 * (size_t)n; }
+    void attach(jdsp_ctx *c, int n_fft, int hop_len, float *base)
+    {
+        ctx = c, n = n_fft, hop = hop_len;
+        g = base, tail[0] = g + hop, tail[1] = tail[0] + n;
+    }
+    long least_run() const { return n / hop > 1 ? n / hop - 1 : 1; }     // max(R - 1, 1): the halo stays above frame 0
+    long samples_out(long n_frames) const { return n_frames < 0 ? 0 : n_frames * hop; }
+    int reset()
+    {
+        JDSP_HIP(ctx, hipMemsetAsync(tail[0], 0, 2 * (size_t)n * sizeof(float), ctx->stream));
+        cur = 0;
+        return JDSP_OK;
+    }
+    // before the handle is deleted: the stream's work on its memory is done
+    void drain() const
+    {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    // the n - hop samples still in the tail (g[t mod hop] * s[t], the same cast), then the reset
+    int flush_dev(const char *entry, int16_t *out_i16_dev, float *out_f32_dev)
+    {
+        const std::string e(entry);
+        if (!aligned(out_i16_dev, 4) || !aligned(out_f32_dev, 8))
+            return fail(ctx, JDSP_EINVAL, (e + ": out_i16 must be 4-byte, out_f32 8-byte aligned").c_str());
+        if (launch_istft_flush(ctx->stream, tail[cur], g, n - hop, hop, out_i16_dev, out_f32_dev))
+            return fail(ctx, JDSP_EHIP, (e + ": launch").c_str(), hipGetLastError());
+        return reset();
+    }
+    // The output half of a host entry: device staging for n_samples of each output the caller wants (d_* NULL where
+    // it wants none, or for no samples), and after the *_dev call the copies back.
+    hipError_t stage_out(size_t n_samples, const void *want_i16, const void *want_f32, int16_t *&d_i16, float *&d_f32)
+    {
+        hipError_t e = hipSuccess;
+        if (n_samples && want_i16) e = h_i16.grow(n_samples);
+        if (e == hipSuccess && n_samples && want_f32) e = h_f32.grow(n_samples);
+        d_i16 = n_samples && want_i16 ? h_i16.get() : nullptr;
+        d_f32 = n_samples && want_f32 ? h_f32.get() : nullptr;
+        return e;
+    }
+    void download_out(HostCall &hc, size_t n_samples, int16_t *out_i16_host, float *out_f32_host) const
+    {
+        hc.download(out_i16_host, h_i16.get(), n_samples * sizeof(int16_t));
+        hc.download(out_f32_host, h_f32.get(), n_samples * sizeof(float));
+    }
+    int flush(const char *entry, int16_t *out_i16_host, float *out_f32_host)
+    {
+        const size_t n_tail = (size_t)(n - hop);
+        JDSP_HIP(ctx, hipSetDevice(ctx->device));
+        int16_t *d_i16;
+        float *d_f32;
+        const hipError_t e = stage_out(n_tail, out_i16_host, out_f32_host, d_i16, d_f32);
+        if (e != hipSuccess) return fail(ctx, JDSP_EHIP, (std::string(entry) + ": buffers").c_str(), e);
+        HostCall hc(ctx, entry);
+        hc.result(flush_dev(entry, d_i16, d_f32));
+        download_out(hc, n_tail, out_i16_host, out_f32_host);
+        return hc.finish();
+    }
+};
+
 }  // namespace jdsp
 
 struct jdsp_denoise {

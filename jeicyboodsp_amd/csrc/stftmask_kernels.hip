@@ -6,12 +6,10 @@
 // The kernel joins two that exist.  The frame is denoise_frame_pairs' (denoise_kernels.hip): one 512-point complex
 // transform of the packed real frame, the split with every mirror pair of bins owned by one lane (frame_io.h,
 // PairTwiddles), the per-bin stage, the inverse pre-split and one inverse transform -- with a mask value streamed from
-// HBM where the denoiser evaluates a gain from a noise estimate.  Everything after the frame is istft_run_kernel's
-// (istft_kernels.hip): lane l holds the frame's samples 2 l + 128 d, +1 in register d, so a hop of 1024 / R samples is
-// HR = 8 / R registers and the overlap-add is a register shift; every output sample is the FP32 sum of its frames in
-// ascending order starting from 0, whatever the call cuts or the launch geometry; a wave whose run starts at frame
-// j0 > 0 recomputes the R - 1 frames in front of it (their PCM and mask rows are read again), only the wave with j0 = 0
-// reads the tail carried in the handle, and the wave that owns the call's last frame writes the other ping-pong tail.
+// HBM where the denoiser evaluates a gain from a noise estimate.  Everything after the frame is the stream of
+// ola_stream.h, which istft_run_kernel feeds too: lane l holds the frame's samples 2 l + 128 d, +1 in register d.  The
+// halo frames of a wave (their PCM and mask rows are read again) go through the one loop, without the stores: the raw
+// PCM registers shift from frame to frame, so the halo cannot stand apart as it does in istft_run_kernel.
 //
 // Mask.  Lane l owns the bins m and m + 512 of m = l + 64 d, d < 5.  Bin m <= 319 takes M[m]; bin m + 512 lies above
 // n/2, where the caller gives no value: Y[1024 - k] = conj(Y[k]) (the output is real), so it takes M[512 - m],
@@ -24,7 +22,7 @@
 // pairs shift down like the overlap-add does: a wave reads every sample of its run once (HR dwords per lane and frame)
 // plus the R - 1 halo frames.
 #include "jdsp_internal.h"
-#include "frame_io.h"
+#include "ola_stream.h"
 
 namespace jdsp {
 
@@ -37,13 +35,8 @@ namespace jdsp {
 // the same overlap-add and store pattern (profiles/r04_istft_launch_ab.txt).
 #define JDSP_STFTMASK_RESIDENT 2
 #endif
-#ifndef JDSP_ISTFT_MIN_RUN_PER_HALO
-#define JDSP_ISTFT_MIN_RUN_PER_HALO 4   // shortest run, in halo frames: the value launch_istft uses (istft_kernels.hip)
-#endif
 
 namespace {
-
-typedef float sm_f32x2 __attribute__((ext_vector_type(2)));
 
 // one mask row as a lane holds it: lo[d] for bin l + 64 d, hi[d] for bin l + 64 d + 512 (the value of bin 512 - l - 64 d)
 template <int CPX> struct MaskRow;
@@ -62,11 +55,11 @@ __device__ __forceinline__ void mask_load(MaskRow<0> &m, const void *row, int la
 }
 __device__ __forceinline__ void mask_load(MaskRow<1> &m, const void *row, int lane)
 {
-    const sm_f32x2 *r = static_cast<const sm_f32x2 *>(row);
+    const f32x2 *r = static_cast<const f32x2 *>(row);
 #pragma unroll
     for (int d = 0; d < 5; d++) {
-        const sm_f32x2 a = __builtin_nontemporal_load(r + lane + 64 * d);
-        const sm_f32x2 b = __builtin_nontemporal_load(r + 512 - lane - 64 * d);
+        const f32x2 a = __builtin_nontemporal_load(r + lane + 64 * d);
+        const f32x2 b = __builtin_nontemporal_load(r + 512 - lane - 64 * d);
         m.lo[d] = make_float2(a.x, a.y);
         m.hi[d] = make_float2(b.x, b.y);
     }
@@ -158,10 +151,8 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
     constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
-    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
-    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * a.run;
-    if (j0 >= a.n_frames) return;
-    const long j1 = j0 + a.run < a.n_frames ? j0 + a.run : a.n_frames;
+    long j0, j1;
+    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
     // the halo: frames j0 - R + 1 .. j0 - 1 are transformed and added, not emitted (all >= 0: the launch keeps
     // run >= R - 1)
     const long js = j0 == 0 ? 0 : j0 - (R - 1);
@@ -170,25 +161,17 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
     load_wave_twiddles(tw, table, lane);
     PairTwiddles pw;
     load_pair_twiddles(pw, table, lane);
-    float2 wa[8], ws[8], g[HR];
+    float2 wa[8], ws[8];
     {
         const float2 *wa_t = reinterpret_cast<const float2 *>(a.wa);
         const float2 *ws_t = reinterpret_cast<const float2 *>(a.ws);
-        const float2 *g_t = reinterpret_cast<const float2 *>(a.g);
 #pragma unroll
         for (int d = 0; d < 8; d++) { wa[d] = wa_t[lane + 64 * d]; ws[d] = ws_t[lane + 64 * d]; }
-#pragma unroll
-        for (int d = 0; d < HR; d++) g[d] = g_t[lane + 64 * d];
     }
-
-    float2 acc[8], y[8];
-#pragma unroll
-    for (int d = 0; d < 8; d++) acc[d] = make_float2(0.f, 0.f);
-    if (j0 == 0) {
-        const float2 *tl = reinterpret_cast<const float2 *>(a.tail_in);
-#pragma unroll
-        for (int d = 0; d < 8 - HR; d++) acc[d] = tl[lane + 64 * d];
-    }
+    OlaAcc<float2, HR> ola;
+    ola.init(a.g, lane);
+    if (j0 == 0) ola.load_tail(a.tail_in, lane);
+    float2 y[8], o[HR];
 
     const char *mask = static_cast<const char *>(a.mask);
     const size_t row_bytes = (size_t)a.pitch * kElem;
@@ -212,11 +195,7 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
         }
         if (a.pitch) mask_load(nm, mask + (size_t)jn * row_bytes, lane);     // pitch 0: the row stays in registers
         stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, ws, y);
-#pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] = make_float2(acc[d].x + y[d].x, acc[d].y + y[d].y);
-        float2 o[HR];
-#pragma unroll
-        for (int d = 0; d < HR; d++) o[d] = make_float2(g[d].x * acc[d].x, g[d].y * acc[d].y);
+        ola.add(y, o);
         // stage the prefetched values before this frame's stores: vmcnt counts loads and stores in issue order, and a
         // wait for them at the top of the next iteration would also wait for these stores (istft_run_kernel)
 #pragma unroll
@@ -225,28 +204,8 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
         for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
         if (a.pitch) mask_prepare(m, nm, lane);
         __builtin_amdgcn_sched_barrier(0);
-        if (j >= j0) {
-            if (a.out) {
-                unsigned int *dst = reinterpret_cast<unsigned int *>(a.out + j * HOP) + lane;
-#pragma unroll
-                for (int d = 0; d < HR; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
-            }
-            if (a.out_f32) {
-                sm_f32x2 *dst = reinterpret_cast<sm_f32x2 *>(a.out_f32 + j * HOP) + lane;
-#pragma unroll
-                for (int d = 0; d < HR; d++) {
-                    const sm_f32x2 w = {o[d].x, o[d].y};
-                    __builtin_nontemporal_store(w, dst + 64 * d);
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < 8; d++) acc[d] = d + HR < 8 ? acc[d + HR] : make_float2(0.f, 0.f);
-        if (j == a.n_frames - 1) {
-            float2 *tl = reinterpret_cast<float2 *>(a.tail_out);
-#pragma unroll
-            for (int d = 0; d < 8 - HR; d++) tl[lane + 64 * d] = acc[d];
-        }
+        if (j >= j0) ola.emit(o, a.out, a.out_f32, j * HOP, lane);
+        ola.shift(j == a.n_frames - 1, a.tail_out, lane);
     }
 }
 
@@ -263,19 +222,11 @@ int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const sh
 {
     if (n_frames <= 0) return 0;
     const int r = 1024 / hop;
-    // as launch_istft: one round of resident waves, and never a run shorter than JDSP_ISTFT_MIN_RUN_PER_HALO (R - 1)
-    // frames, so that the halo a wave recomputes (here: transforms both ways) is a bounded share of its run
-    const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_STFTMASK_RESIDENT;
-    long run = (n_frames + slots - 1) / slots;
-    const long min_run = r > 1 ? (long)JDSP_ISTFT_MIN_RUN_PER_HALO * (r - 1) : 1;
-    if (run < min_run) run = min_run;
-    if (run_opt > 0) run = run_opt < r - 1 ? r - 1 : run_opt;        // jdsp_stftmask_set_option("frames_per_wave")
-    const long waves = (n_frames + run - 1) / run;
-    const long grid = (waves + 7) / 8 * 8;
-    StftMaskArgs a = {pcm, mask, pitch, n_frames, wa, ws, g, tail_in, tail_out, out, out_f32, (int)run};
-    if (r == 1) launch_kind<1>(s, complex_mask, grid, a, table);
-    else if (r == 2) launch_kind<2>(s, complex_mask, grid, a, table);
-    else launch_kind<4>(s, complex_mask, grid, a, table);
+    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_STFTMASK_RESIDENT, r, n_frames, run_opt);
+    StftMaskArgs a = {pcm, mask, pitch, n_frames, wa, ws, g, tail_in, tail_out, out, out_f32, (int)p.run};
+    if (r == 1) launch_kind<1>(s, complex_mask, p.grid, a, table);
+    else if (r == 2) launch_kind<2>(s, complex_mask, p.grid, a, table);
+    else launch_kind<4>(s, complex_mask, p.grid, a, table);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -874,69 +874,59 @@ class MvdrMulti(_Child):
         return (out[:n_out * B], pre[:n_out * B]) if want_precast else out[:n_out * B]
 
 
-class Istft(_Child):
-    """One STFT synthesis output stream (jdsp_istft, include/jdsp.h): spectra -> inverse transform -> synthesis window
-    -> overlap-add -> int16 (and optionally the float32 values before the cast).  torch CUDA spectra go through the
-    device entry on torch's current stream, numpy spectra through the host entry."""
-    _destroy = staticmethod(lambda h: L.jdsp_istft_destroy(h))
-    LAYOUTS = {"full": _lib.SPEC_FULL, "half": _lib.SPEC_HALF}
+class _OlaStream(_Child):
+    """What Istft and StftMask share, the overlap-add output stream behind both handles: a subclass names its C entry
+    points by `_prefix` and hands its inputs to _process()."""
     WINDOWS = {None: _lib.WIN_NONE, "none": _lib.WIN_NONE, "hamming": _lib.WIN_HAMMING, "hann": _lib.WIN_HANN}
+    _prefix = None
 
-    def __init__(self, engine, n_fft=1024, hop=512, layout="full", synthesis_window="none", analysis_window="none"):
+    @classmethod
+    def _c(cls, name):
+        return getattr(L, cls._prefix + name)
+
+    @staticmethod
+    def _pick(v, names):
+        return names[v] if isinstance(v, str) or v is None else int(v)
+
+    def _create(self, engine, cfg):
         self.eng = engine
-        pick = lambda v, names: names[v] if isinstance(v, str) or v is None else int(v)  # noqa: E731
-        cfg = _lib.IstftCfg(int(n_fft), int(hop), pick(layout, self.LAYOUTS), pick(synthesis_window, self.WINDOWS),
-                            pick(analysis_window, self.WINDOWS))
         h = C.c_void_p()
-        engine._ck(L.jdsp_istft_create(engine._h, C.byref(cfg), C.byref(h)))
+        engine._ck(self._c("_create")(engine._h, C.byref(cfg), C.byref(h)))
         self._h = h
-        self.n_fft, self.hop, self.layout = cfg.n_fft, cfg.hop, cfg.layout
-        self.bins = self.n_fft // 2 + 1 if self.layout == _lib.SPEC_HALF else self.n_fft
+        self.n_fft, self.hop = cfg.n_fft, cfg.hop
         self._torch = None              # the kind of the last process() input: flush() answers in the same kind
         engine._children.append(self)
 
     def reset(self):
-        self.eng._ck(L.jdsp_istft_reset(self._h))
+        self.eng._ck(self._c("_reset")(self._h))
 
     def set_option(self, name, value):
-        self.eng._ck(L.jdsp_istft_set_option(self._h, name.encode(), int(value)))
+        self.eng._ck(self._c("_set_option")(self._h, name.encode(), int(value)))
 
     def samples_out(self, n_frames):
-        return L.jdsp_istft_samples_out(self._h, int(n_frames))
+        return self._c("_samples_out")(self._h, int(n_frames))
 
-    def process(self, spec, want_f32=False, out=None, out_f32=None, n_frames=None, write=True):
-        """spec: complex64 [n_frames, row_pitch >= bins] (torch CUDA or numpy, rows contiguous).  Returns the int16
-        samples of these frames (n_frames * hop), or (int16, float32) with want_f32.  write=False advances the stream
-        without writing (both outputs NULL) and returns None."""
-        if n_frames is None:
-            n_frames = spec.shape[0]
-        pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
+    def _process(self, dev, inputs, n_frames, want_f32, write, out, out_f32):
+        """inputs: the C entry's arguments between the handle and the outputs, on the torch device `dev` (the device
+        entry on torch's current stream) or, with dev None, in numpy arrays (the host entry)."""
         n_out = self.samples_out(n_frames)
-        if _is_torch(spec):
+        self._torch = dev
+        if not write:
+            out = out_f32 = None
+        elif dev is not None:
             import torch
-            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
-            self._torch = spec.device
-            if write:
-                if out is None:
-                    out = torch.empty(max(n_out, 1), dtype=torch.int16, device=spec.device)
-                if want_f32 and out_f32 is None:
-                    out_f32 = torch.empty(max(n_out, 1), dtype=torch.float32, device=spec.device)
-            else:
-                out = out_f32 = None
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_istft_process_dev(self._h, C.c_void_p(spec.data_ptr()), pitch, n_frames, _vp(out),
-                                                  _vp(out_f32) if want_f32 else None))
+            if out is None:
+                out = torch.empty(max(n_out, 1), dtype=torch.int16, device=dev)
+            if want_f32 and out_f32 is None:
+                out_f32 = torch.empty(max(n_out, 1), dtype=torch.float32, device=dev)
         else:
-            spec = np.ascontiguousarray(spec, np.complex64)
-            self._torch = None
-            if write:
-                out = np.zeros(max(n_out, 1), np.int16) if out is None else out
-                if want_f32 and out_f32 is None:
-                    out_f32 = np.zeros(max(n_out, 1), np.float32)
-            else:
-                out = out_f32 = None
-            self.eng._ck(L.jdsp_istft_process(self._h, _vp(spec), pitch, n_frames, _vp(out),
-                                              _vp(out_f32) if want_f32 else None))
+            out = np.zeros(max(n_out, 1), np.int16) if out is None else out
+            if want_f32 and out_f32 is None:
+                out_f32 = np.zeros(max(n_out, 1), np.float32)
+        if dev is not None:
+            self.eng._use_torch_stream()
+        entry = self._c("_process_dev" if dev is not None else "_process")
+        self.eng._ck(entry(self._h, *inputs, n_frames, _vp(out), _vp(out_f32) if want_f32 else None))
         if not write:
             return None
         return (out[:n_out], out_f32[:n_out]) if want_f32 else out[:n_out]
@@ -949,45 +939,62 @@ class Istft(_Child):
             out = torch.zeros(max(n, 1), dtype=torch.int16, device=self._torch)
             f = torch.zeros(max(n, 1), dtype=torch.float32, device=self._torch) if want_f32 else None
             self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_istft_flush_dev(self._h, _vp(out), _vp(f)))
+            self.eng._ck(self._c("_flush_dev")(self._h, _vp(out), _vp(f)))
         else:
             out = np.zeros(max(n, 1), np.int16)
             f = np.zeros(max(n, 1), np.float32) if want_f32 else None
-            self.eng._ck(L.jdsp_istft_flush(self._h, _vp(out), _vp(f)))
+            self.eng._ck(self._c("_flush")(self._h, _vp(out), _vp(f)))
         return (out[:n], f[:n]) if want_f32 else out[:n]
 
 
-class StftMask(_Child):
+class Istft(_OlaStream):
+    """One STFT synthesis output stream (jdsp_istft, include/jdsp.h): spectra -> inverse transform -> synthesis window
+    -> overlap-add -> int16 (and optionally the float32 values before the cast).  torch CUDA spectra go through the
+    device entry on torch's current stream, numpy spectra through the host entry."""
+    _destroy = staticmethod(lambda h: L.jdsp_istft_destroy(h))
+    _prefix = "jdsp_istft"
+    LAYOUTS = {"full": _lib.SPEC_FULL, "half": _lib.SPEC_HALF}
+
+    def __init__(self, engine, n_fft=1024, hop=512, layout="full", synthesis_window="none", analysis_window="none"):
+        pick = self._pick
+        self._create(engine, _lib.IstftCfg(int(n_fft), int(hop), pick(layout, self.LAYOUTS),
+                                           pick(synthesis_window, self.WINDOWS), pick(analysis_window, self.WINDOWS)))
+        self.layout = pick(layout, self.LAYOUTS)
+        self.bins = self.n_fft // 2 + 1 if self.layout == _lib.SPEC_HALF else self.n_fft
+
+    def process(self, spec, want_f32=False, out=None, out_f32=None, n_frames=None, write=True):
+        """spec: complex64 [n_frames, row_pitch >= bins] (torch CUDA or numpy, rows contiguous).  Returns the int16
+        samples of these frames (n_frames * hop), or (int16, float32) with want_f32.  write=False advances the stream
+        without writing (both outputs NULL) and returns None."""
+        if n_frames is None:
+            n_frames = spec.shape[0]
+        pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
+        if _is_torch(spec):
+            import torch
+            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
+            dev = spec.device
+        else:
+            spec = np.ascontiguousarray(spec, np.complex64)
+            dev = None
+        return self._process(dev, (_vp(spec), pitch), n_frames, want_f32, write, out, out_f32)
+
+
+class StftMask(_OlaStream):
     """One fused STFT masking stream (jdsp_stftmask, include/jdsp.h): int16 PCM -> analysis window -> forward
     transform -> per-bin mask -> inverse transform -> synthesis window -> overlap-add -> int16 (and optionally the
     float32 values before the cast), without the spectrum reaching memory.  torch CUDA inputs go through the device
     entry on torch's current stream, numpy inputs through the host entry."""
     _destroy = staticmethod(lambda h: L.jdsp_stftmask_destroy(h))
-    WINDOWS = Istft.WINDOWS
+    _prefix = "jdsp_stftmask"
     KINDS = {"real": _lib.MASK_REAL, "complex": _lib.MASK_COMPLEX}
 
     def __init__(self, engine, n_fft=1024, hop=512, analysis_window="hamming", synthesis_window="none", normalise=0,
                  mask_kind="real"):
-        self.eng = engine
-        pick = lambda v, names: names[v] if isinstance(v, str) or v is None else int(v)  # noqa: E731
-        cfg = _lib.StftMaskCfg(int(n_fft), int(hop), pick(analysis_window, self.WINDOWS),
-                               pick(synthesis_window, self.WINDOWS), int(normalise), pick(mask_kind, self.KINDS))
-        h = C.c_void_p()
-        engine._ck(L.jdsp_stftmask_create(engine._h, C.byref(cfg), C.byref(h)))
-        self._h = h
-        self.n_fft, self.hop, self.mask_kind = cfg.n_fft, cfg.hop, cfg.mask_kind
+        pick = self._pick
+        self.mask_kind = pick(mask_kind, self.KINDS)
+        self._create(engine, _lib.StftMaskCfg(int(n_fft), int(hop), pick(analysis_window, self.WINDOWS),
+                                              pick(synthesis_window, self.WINDOWS), int(normalise), self.mask_kind))
         self.bins = self.n_fft // 2 + 1
-        self._torch = None              # the kind of the last process() input: flush() answers in the same kind
-        engine._children.append(self)
-
-    def reset(self):
-        self.eng._ck(L.jdsp_stftmask_reset(self._h))
-
-    def set_option(self, name, value):
-        self.eng._ck(L.jdsp_stftmask_set_option(self._h, name.encode(), int(value)))
-
-    def samples_out(self, n_frames):
-        return L.jdsp_stftmask_samples_out(self._h, int(n_frames))
 
     def process(self, pcm, mask, n_frames=None, want_f32=False, write=True, out=None, out_f32=None):
         """pcm: int16, hop (n_frames - 1) + n_fft samples (n_frames defaults to all the whole frames pcm holds).
@@ -1001,51 +1008,17 @@ class StftMask(_Child):
         assert pcm.ndim == 1 and pcm.shape[0] >= (self.hop * (n_frames - 1) + self.n_fft if n_frames else 0)
         assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_frames)
         pitch = mask.shape[1] if mask.ndim == 2 else 0
-        n_out = self.samples_out(n_frames)
-        if not write:
-            out = out_f32 = None
         if _is_torch(pcm):
             import torch
             want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
             assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
             assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
-            self._torch = pcm.device
-            if write:
-                if out is None:
-                    out = torch.empty(max(n_out, 1), dtype=torch.int16, device=pcm.device)
-                if want_f32 and out_f32 is None:
-                    out_f32 = torch.empty(max(n_out, 1), dtype=torch.float32, device=pcm.device)
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_stftmask_process_dev(self._h, _vp(pcm), _vp(mask), pitch, n_frames, _vp(out),
-                                                     _vp(out_f32) if want_f32 else None))
+            dev = pcm.device
         else:
             pcm = np.ascontiguousarray(pcm, np.int16)
             mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
-            self._torch = None
-            if write:
-                out = np.zeros(max(n_out, 1), np.int16) if out is None else out
-                if want_f32 and out_f32 is None:
-                    out_f32 = np.zeros(max(n_out, 1), np.float32)
-            self.eng._ck(L.jdsp_stftmask_process(self._h, _vp(pcm), _vp(mask), pitch, n_frames, _vp(out),
-                                                 _vp(out_f32) if want_f32 else None))
-        if not write:
-            return None
-        return (out[:n_out], out_f32[:n_out]) if want_f32 else out[:n_out]
-
-    def flush(self, want_f32=False):
-        """The n_fft - hop samples still in the tail; the handle is reset afterwards."""
-        n = self.n_fft - self.hop
-        if self._torch is not None:
-            import torch
-            out = torch.zeros(max(n, 1), dtype=torch.int16, device=self._torch)
-            f = torch.zeros(max(n, 1), dtype=torch.float32, device=self._torch) if want_f32 else None
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_stftmask_flush_dev(self._h, _vp(out), _vp(f)))
-        else:
-            out = np.zeros(max(n, 1), np.int16)
-            f = np.zeros(max(n, 1), np.float32) if want_f32 else None
-            self.eng._ck(L.jdsp_stftmask_flush(self._h, _vp(out), _vp(f)))
-        return (out[:n], f[:n]) if want_f32 else out[:n]
+            dev = None
+        return self._process(dev, (_vp(pcm), _vp(mask), pitch), n_frames, want_f32, write, out, out_f32)
 
 
 class GmmTrainer(_Child):
