@@ -169,6 +169,13 @@ struct MfccDev {
     int chan_ok;
     const double *dct;           // [max(n_chan, 40)][32]: sqrt(2/C) cos(PI i (k-0.5)/C), zero past n_cep and past n_chan
     const double *lifter_w;      // [32]: 1 + L/2 sin(PI i / L)
+    // which frames to compute again (mfcc_leak_one), and what the FP64 pass needs
+    const float *chan_w2;        // [64]: sum over the channel's bins of its squared filterbank weights, zero past n_chan
+    float leak_k2;               // 2^-46 L_max^2 (2 / C) / 2.5e-6^2
+    double preemph_f64;
+    const double *win_f64;       // [1024] Hamming over win_len (not halved), zero beyond
+    const double2 *tw_f64;       // [n_fft of 1024] exp(-2 pi j m / n_fft)
+    const double *fb_f64;        // [512] rgdFilterBank (zero beyond n_bins)
 };
 
 int fail(jdsp_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
@@ -597,7 +604,7 @@ struct jdsp_mfcc {
     jdsp_mfcc_cfg cfg;
     jdsp::MfccDev dev;                    // its pointers are views into blob
     jdsp::DevBuf<char> blob;              // one device allocation holding every table
-    jdsp::DevBuf<int> redo;               // 512-FFT configurations: {count, frame pairs to recompute apart} (mfcc512_run_kernel)
+    jdsp::DevBuf<int> redo;               // 512-FFT configurations: {count, frames or frame pairs to compute again in FP64} (mfcc_redo_f64_kernel)
     std::vector<double> mel_freqs, fbank;
     std::vector<int> fi_bins;
     // FP64 tables of the separately callable sub-steps (stage_api.hip), built on first use

@@ -115,12 +115,41 @@ int jdsp_mfcc_create(jdsp_ctx *ctx, const jdsp_mfcc_cfg *cfg, jdsp_mfcc **out)
         if (i & 1) window[i >> 1].y = (float)w;
         else window[i >> 1].x = (float)w;
     }
+    // ---- frames that share a transform (n_fft = 512): the criterion's constants (mfcc_leak_redo in mfcc_kernels.hip
+    // derives them) and the FP64 pass's tables ----
+    std::vector<float> chan_w2(64, 0.f);
+    {
+        std::vector<double> w2(C, 0.0);
+        for (int i = 0; i < NB; i++) {                                           // the weights of :157-168, squared
+            const int k = h->fi_bins[i];
+            const double f = h->fbank[i];
+            if (k == 0) w2[0] += (1 - f) * (1 - f);
+            else {
+                w2[k - 1] += f * f;
+                if (k != C) w2[k] += (1 - f) * (1 - f);
+            }
+        }
+        for (int k = 0; k < C; k++) chan_w2[k] = (float)w2[k];
+    }
+    double lift_max = 0;
+    for (int i = 0; i < c.n_cep; i++) lift_max = fabs(lift[i]) > lift_max ? fabs(lift[i]) : lift_max;
+    const double leak_k2 = ldexp(1.0, -46) * lift_max * lift_max * (2.0 / C) / (2.5e-6 * 2.5e-6);
+    std::vector<double> win_f64(1024, 0.0), tw_f64(2 * 1024, 0.0), fb_f64(512, 0.0);
+    for (int i = 0; i < c.win_len; i++) win_f64[i] = 0.54 - 0.46 * cos(2 * PI * i / (c.win_len - 1));
+    for (int m = 0; m < c.n_fft; m++) {
+        const double a = -6.283185307179586476925286766559 * m / c.n_fft;
+        tw_f64[2 * m] = cos(a);
+        tw_f64[2 * m + 1] = sin(a);
+    }
+    for (int i = 0; i < NB; i++) fb_f64[i] = h->fbank[i];
     // ---- one blob ----
     const size_t o_win = 0, o_fb = o_win + sizeof(float2) * 512, o_k = o_fb + 512 * sizeof(float),
                  o_dct = o_k + 512 * sizeof(int), o_lift = o_dct + dct.size() * sizeof(double),
                  o_seg = o_lift + 32 * sizeof(double), o_segw = o_seg + seg.size() * sizeof(int),
                  o_chan = o_segw + seg_wc.size() * sizeof(float),
-                 total = o_chan + chan_src.size() * sizeof(int);
+                 o_w2 = o_chan + chan_src.size() * sizeof(int), o_tw64 = o_w2 + chan_w2.size() * sizeof(float),
+                 o_win64 = o_tw64 + tw_f64.size() * sizeof(double), o_fb64 = o_win64 + win_f64.size() * sizeof(double),
+                 total = o_fb64 + fb_f64.size() * sizeof(double);
     std::vector<char> host(total, 0);
     memcpy(&host[o_win], window.data(), sizeof(float2) * 512);
     memcpy(&host[o_fb], mel_fb.data(), 512 * sizeof(float));
@@ -130,6 +159,10 @@ int jdsp_mfcc_create(jdsp_ctx *ctx, const jdsp_mfcc_cfg *cfg, jdsp_mfcc **out)
     memcpy(&host[o_seg], seg.data(), seg.size() * sizeof(int));
     memcpy(&host[o_segw], seg_wc.data(), seg_wc.size() * sizeof(float));
     memcpy(&host[o_chan], chan_src.data(), chan_src.size() * sizeof(int));
+    memcpy(&host[o_w2], chan_w2.data(), chan_w2.size() * sizeof(float));
+    memcpy(&host[o_tw64], tw_f64.data(), tw_f64.size() * sizeof(double));
+    memcpy(&host[o_win64], win_f64.data(), win_f64.size() * sizeof(double));
+    memcpy(&host[o_fb64], fb_f64.data(), fb_f64.size() * sizeof(double));
     const hipError_t e = h->blob.upload(host.data(), total);
     if (e != hipSuccess) {
         jdsp_mfcc_destroy(h);
@@ -151,6 +184,12 @@ int jdsp_mfcc_create(jdsp_ctx *ctx, const jdsp_mfcc_cfg *cfg, jdsp_mfcc **out)
     h->dev.chan_ok = chan_ok ? 1 : 0;
     h->dev.dct = (const double *)(b + o_dct);
     h->dev.lifter_w = (const double *)(b + o_lift);
+    h->dev.chan_w2 = (const float *)(b + o_w2);
+    h->dev.leak_k2 = (float)leak_k2;
+    h->dev.preemph_f64 = c.preemph;
+    h->dev.win_f64 = (const double *)(b + o_win64);
+    h->dev.tw_f64 = (const double2 *)(b + o_tw64);
+    h->dev.fb_f64 = (const double *)(b + o_fb64);
     *out = h;
     return JDSP_OK;
 }
@@ -181,8 +220,8 @@ int jdsp_mfcc_frames_dev(jdsp_mfcc *h, const int16_t *pcm_dev, const int64_t *fr
     if (n_frames < 0 || (n_frames > 0 && (!pcm_dev || !feats_dev))) return fail(ctx, JDSP_EINVAL, "jdsp_mfcc_frames: bad buffer");
     if (n_frames == 0) return JDSP_OK;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n_redo = (size_t)(n_frames + 1) / 2 + 1;                    // the count, then one entry per frame pair
-    if (h->dev.bin_stride == 2 && n_redo > h->redo.count()) {                // no-op once sized (size it before a graph capture)
+    const size_t n_redo = (size_t)n_frames + 1;                              // the count, then at most one entry per frame (or pair)
+    if (n_redo > h->redo.count()) {                // no-op once sized (size it before a graph capture)
         JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         JDSP_HIP(ctx, h->redo.grow(n_redo));
     }

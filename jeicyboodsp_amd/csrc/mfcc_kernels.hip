@@ -12,26 +12,72 @@
 
 namespace jdsp {
 
-// redo (or NULL): {count, pair indices...} left by mfcc512_run_kernel -- the frames 2 q and 2 q + 1 of every listed pair
-// are computed again here, each in a transform of its own, by waves that stride over the list.
+// sum over the wave, the same value in every lane's copy of lane 63 (five DPP adds and a v_readlane; a __shfl_xor tree
+// is six ds_bpermute, 8.9 issue slots each)
+__device__ __forceinline__ float wave_sum_f32(float v)
+{
+#define JDSP_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, true))
+    JDSP_DPP_ADD(0xB1, 0xf);     // quad_perm [1,0,3,2]
+    JDSP_DPP_ADD(0x4E, 0xf);     // quad_perm [2,3,0,1]
+    JDSP_DPP_ADD(0x141, 0xf);    // row_half_mirror: sums of 8
+    JDSP_DPP_ADD(0x140, 0xf);    // row_mirror: sums of 16
+    JDSP_DPP_ADD(0x142, 0xa);    // row_bcast15 into rows 1 and 3
+    JDSP_DPP_ADD(0x143, 0xc);    // row_bcast31 into rows 2 and 3
+#undef JDSP_DPP_ADD
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// ---- which frames must be computed again, in FP64 (every MFCC kernel; derived for two frames that share a transform) -----
+// Two frames share one FP32 transform there; its rounding -- 2^-23 of the rms of ITS OUTPUT per bin, three radix-8
+// passes (measured: profiles/r10_mfcc_pair_leak.txt) -- lands in both frames' bins whoever's samples caused it.  With
+// E = sum |z|^2 over both frames (kernel units: the window table is halved), a bin of |A| or |B| is off by
+// r = 2^-23 sqrt(E) rms, independently per bin; a mel channel M_c = sum_i w_ci |X_i| by r sqrt(sum_i w_ci^2); its
+// logarithm by that over M_c; and cepstrum i, whose DCT row has d_ci^2 <= 2 / C, by no more than
+//     sigma = L_max sqrt(2 / C) r sqrt(sum_c W2_c / M_c^2),      W2_c = sum_i w_ci^2,  L_max = the largest lifter weight.
+// A frame keeps its packed result while 3.5 sigma + 1e-6 (the FP32 filterbank sums and logarithm) <= 1e-5 of its
+// vector's peak, the bar every MFCC vector is held to: sigma <= 2.5e-6 peak, or peak^2 > leak_k2 E sum_c W2_c / M_c^2
+// with leak_k2 = 2^-46 L_max^2 (2 / C) / 2.5e-6^2 (mfcc_api.hip).  The strict comparison fails on an infinite or NaN
+// right-hand side: a frame with an empty channel (ln 0 = -inf, :171, must stay exact) is always computed again.
+// mfcc_leak_term: on the channel lanes, before the logarithm.  mfcc_leak_redo: wave-uniform, after the lifter.
+__device__ __forceinline__ float mfcc_leak_term(float chan_sum, float w2)
+{
+    return w2 * __builtin_amdgcn_rcpf(chan_sum * chan_sum);
+}
+// One frame: t = its channel lanes' terms, cep = its cepstrum on the lanes cep_lane, e = what its transform's rounding
+// scales with.  Wave-uniform.
+__device__ __forceinline__ bool mfcc_leak_one(float t, double cep, bool cep_lane, float e, float k2)
+{
+    const float bound = k2 * e * wave_sum_f32(t);
+    const float c = (float)cep;
+    // the peak is the largest |cepstrum|: some lane's square passes exactly when the peak's does
+    return __ballot(cep_lane && c * c > bound) == 0;
+}
+__device__ __forceinline__ bool mfcc_leak_redo(float ta, float tb, double cep_a, double cep_b, bool cep_lane, float e_a, float e_b, float k2)
+{
+    return mfcc_leak_one(ta, cep_a, cep_lane, e_a, k2) | mfcc_leak_one(tb, cep_b, cep_lane, e_b, k2);
+}
+// The kernels that give every frame a transform of its own run it as a packed real transform: X[m] = Zh[m] (1 - j W^m)
+// + conj Zh[512 - m] (1 + j W^m), |1 - j W|^2 + |1 + j W|^2 = 4, so the same rounding reaches a bin of |X| with
+// r^2 = 2^-46 * 4 E, E = sum x^2 of the frame (halved window): the frame's own rounding is judged by the same bound.
+__device__ __forceinline__ float mfcc_packed_real_energy(const float2 (&v)[8])
+{
+    float e = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; r++) e = fmaf(v[r].x, v[r].x, fmaf(v[r].y, v[r].y, e));
+    return 4.f * wave_sum_f32(e);
+}
+
 __global__ __launch_bounds__(64) void mfcc_kernel(const short *__restrict__ pcm, const long long *__restrict__ starts,
                                                   long n_frames, MfccDev p, const float2 *__restrict__ table,
-                                                  double *__restrict__ feats, const int *__restrict__ redo)
+                                                  double *__restrict__ feats, int *__restrict__ redo)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     __shared__ float mag[512];
     __shared__ float logmel[64];
     const int lane = threadIdx.x;
     const long per_xcd = (gridDim.x + 7) >> 3;
-    long f = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    long it = blockIdx.x;
-  for (;;) {
-    if (redo) {
-        if (it >= 2L * redo[0]) return;
-        f = 2L * redo[1 + (it >> 1)] + (it & 1);
-        it += gridDim.x;
-        if (f >= n_frames) continue;
-    } else if (f >= n_frames) return;
+    const long f = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (f >= n_frames) return;
     const short *src = pcm + (starts ? starts[f] : (long long)p.hop * f);
 
     WaveTwiddles tw;
@@ -69,6 +115,7 @@ __global__ __launch_bounds__(64) void mfcc_kernel(const short *__restrict__ pcm,
             v[r] = make_float2(x0 * w.x, x1 * w.y);
         }
     }
+    const float e_frame = mfcc_packed_real_energy(v);
     wave_fft512<false>(v, lds, lane, tw);
     store_natural_image(lds, lane, v);
     wave_lds_fence();
@@ -127,7 +174,12 @@ __global__ __launch_bounds__(64) void mfcc_kernel(const short *__restrict__ pcm,
         }
     }
     wave_lds_fence();
-    if (lane < p.n_chan) logmel[lane] = logf(logmel[lane]);               // :171
+    float t_leak = 0.f;                                                   // W2_c / M_c^2 (mfcc_leak_one)
+    if (lane < p.n_chan) {
+        const float sum = logmel[lane];
+        t_leak = mfcc_leak_term(sum, p.chan_w2[lane]);
+        logmel[lane] = logf(sum);                                         // :171
+    }
     wave_lds_fence();
     // DCT-II (:178-182) and lifter (:189): cepstrum i on lanes i, i+16, i+32, i+48, each summing every
     // fourth channel (four short independent chains of table loads instead of one long one)
@@ -143,11 +195,11 @@ __global__ __launch_bounds__(64) void mfcc_kernel(const short *__restrict__ pcm,
         const double other = __shfl_xor(acc, 16);
         if (!wide) acc += other;
         acc += __shfl_xor(acc, 32);
-        if (lane < p.n_cep) feats[f * p.n_cep + lane] = acc * p.lifter_w[lane];
+        const double cep = acc * p.lifter_w[lane & 31];
+        if (lane < p.n_cep) feats[f * p.n_cep + lane] = cep;
+        // a frame whose own transform's rounding could show (mfcc_leak_one): again, in FP64 (mfcc_redo_f64_kernel)
+        if (mfcc_leak_one(t_leak, cep, lane < p.n_cep, e_frame, p.leak_k2) && lane == 0) redo[1 + atomicAdd(redo, 1)] = (int)f;
     }
-    if (!redo) return;
-    wave_lds_fence();
-  }
 }
 
 
@@ -311,9 +363,12 @@ __device__ __forceinline__ double sum_xor32_f64(double a)
 // and frame and a few reads on the channel lanes instead of two LDS atomics per lane and frame: the atomics were 10 us
 // of mfcc_x2_kernel's 95 (profiles/r02_mfcc512_run.txt), and their order -- hence the last bit of the sum -- was not
 // reproducible.  pieces: 2 x 2 x 64 floats of LDS.
+template <bool LEAK = false>
 __device__ __forceinline__ void mel_channel_sums(float (*pieces)[2][64], float (*logmel)[64], const MfccDev &p, int lane,
-                                                 float lo_a, float hi_a, float lo_b, float hi_b)
+                                                 float lo_a, float hi_a, float lo_b, float hi_b, float *ta = nullptr,
+                                                 float *tb = nullptr)
 {
+    if constexpr (LEAK) { *ta = 0.f; *tb = 0.f; }
     pieces[0][0][lane] = lo_a; pieces[0][1][lane] = hi_a;
     pieces[1][0][lane] = lo_b; pieces[1][1][lane] = hi_b;
     wave_lds_fence();
@@ -331,6 +386,11 @@ __device__ __forceinline__ void mel_channel_sums(float (*pieces)[2][64], float (
         // per value for the last half ulp, of which nothing survives the 1e-5 bar); ln 0 = -inf as in the reference
         logmel[0][lane] = __logf(sa);
         logmel[1][lane] = __logf(sb);
+        if constexpr (LEAK) {
+            const float w2 = p.chan_w2[lane];
+            *ta = mfcc_leak_term(sa, w2);
+            *tb = mfcc_leak_term(sb, w2);
+        }
     }
     wave_lds_fence();
 }
@@ -362,11 +422,15 @@ __device__ __forceinline__ void mfcc_load_dct(double (&dc)[10], const MfccDev &p
 #pragma unroll
     for (int t = 0; t < 10; t++) dc[t] = p.dct[(cpart + cstep * t) * 32 + ci];   // (a guarded load is a branch and a wait of its own)
 }
-template <int PL>
-__device__ __forceinline__ void mfcc_tail_pre(const float *mag_a, const float *mag_b, float (*logmel)[64], float (*pieces)[2][64],
+// LEAK (e_a, e_b: what each frame's transform rounding scales with; the same sum |z|^2 over both where two frames share
+// a transform): returns whether the pair must be computed again, in FP64 (mfcc_leak_redo); false otherwise.
+template <int PL, bool LEAK = false>
+__device__ __forceinline__ bool mfcc_tail_pre(const float *mag_a, const float *mag_b, float (*logmel)[64], float (*pieces)[2][64],
                                               const MfccDev &p, int lane, const MfccLaneTables<PL> &mt, const double (&dc)[10],
-                                              double lw, long fa, long fb, bool two, double *__restrict__ feats)
+                                              double lw, long fa, long fb, bool two, double *__restrict__ feats,
+                                              float e_a = 0.f, float e_b = 0.f)
 {
+    float ta = 0.f, tb = 0.f;                                        // LEAK: W2_c / M_c^2 on the channel lanes
     const bool wide = p.n_cep > 16;
     const int ci = wide ? (lane & 31) : (lane & 15), cpart = wide ? (lane >> 5) : (lane >> 4), cstep = wide ? 2 : 4;
     const int4 sg = mt.sg;
@@ -406,7 +470,7 @@ __device__ __forceinline__ void mfcc_tail_pre(const float *mag_a, const float *m
         if constexpr (PL > 8) batch(std::integral_constant<int, 8>{}, std::integral_constant<int, PL - 8>{});
         if (p.chan_ok) {
             if (sg.y <= 0) { lo_a = hi_a = lo_b = hi_b = 0.f; }
-            mel_channel_sums(pieces, logmel, p, lane, lo_a, hi_a, lo_b, hi_b);
+            mel_channel_sums<LEAK>(pieces, logmel, p, lane, lo_a, hi_a, lo_b, hi_b, &ta, &tb);
         } else {
             if (sg.y > 0) {
                 if (sg.z >= 1) { atomicAdd(&logmel[0][sg.z - 1], lo_a); atomicAdd(&logmel[1][sg.z - 1], lo_b); }
@@ -414,8 +478,14 @@ __device__ __forceinline__ void mfcc_tail_pre(const float *mag_a, const float *m
             }
             wave_lds_fence();
             if (lane < p.n_chan) {
-                logmel[0][lane] = __logf(logmel[0][lane]);               // :171, as in mel_channel_sums
-                logmel[1][lane] = __logf(logmel[1][lane]);
+                const float sa = logmel[0][lane], sb = logmel[1][lane];
+                logmel[0][lane] = __logf(sa);                            // :171, as in mel_channel_sums
+                logmel[1][lane] = __logf(sb);
+                if constexpr (LEAK) {
+                    const float w2 = p.chan_w2[lane];
+                    ta = mfcc_leak_term(sa, w2);
+                    tb = mfcc_leak_term(sb, w2);
+                }
             }
             wave_lds_fence();
         }
@@ -449,13 +519,15 @@ __device__ __forceinline__ void mfcc_tail_pre(const float *mag_a, const float *m
             feats[fa * p.n_cep + lane] = acc_a * lw;
             if (two) feats[fb * p.n_cep + lane] = acc_b * lw;
         }
+        if constexpr (LEAK) return mfcc_leak_redo(ta, tb, acc_a * lw, acc_b * lw, lane < p.n_cep, e_a, e_b, p.leak_k2);
     }
+    return false;
 }
 
 template <bool ALIGNED, int PL>
 __device__ __forceinline__ void mfcc_x2_body(const short *__restrict__ src_a, const short *__restrict__ src_b, long fa, long fb, bool two,
                                              const MfccDev &p, const float2 *__restrict__ table, double *__restrict__ feats,
-                                             float2 (*lds)[kWaveLdsComplex], int lane)
+                                             float2 (*lds)[kWaveLdsComplex], int lane, int *__restrict__ redo)
 {
     float (*logmel)[64] = reinterpret_cast<float (*)[64]>(reinterpret_cast<float *>(lds[0]) + 640);       // [2][64]
     float (*pieces)[2][64] = reinterpret_cast<float (*)[2][64]>(reinterpret_cast<float *>(lds[1]) + 640); // [2][2][64]
@@ -483,6 +555,7 @@ __device__ __forceinline__ void mfcc_x2_body(const short *__restrict__ src_a, co
     mfcc_load_lane_tables(mt, p, lane);
     const double lw = p.lifter_w[lane & 31];
 
+    const float e_a = mfcc_packed_real_energy(va), e_b = mfcc_packed_real_energy(vb);
     wave_fft512_x2<false>(va, vb, lds[0], lds[1], lane, tw);
 #if JDSP_MFCC_X2_PAIRS
     // |X[m]| and |X[512 - m]| (= |X[m + 512]|) for m = lane + 64 d, d < 5 -- bins 0..319 and 193..511 -- from the
@@ -558,13 +631,15 @@ __device__ __forceinline__ void mfcc_x2_body(const short *__restrict__ src_a, co
     // now -- the transforms' registers are free again -- so that they have arrived when the channel logarithms have
     double dc[10];
     mfcc_load_dct(dc, p, lane);
-    mfcc_tail_pre(mag_a, mag_b, logmel, pieces, p, lane, mt, dc, lw, fa, fb, two, feats);
+    // a pair with a frame whose own transform's rounding could show: both again, in FP64 (mfcc_redo_f64_kernel)
+    if (mfcc_tail_pre<PL, true>(mag_a, mag_b, logmel, pieces, p, lane, mt, dc, lw, fa, fb, two, feats, e_a, e_b) && lane == 0)
+        redo[1 + atomicAdd(redo, 1)] = (int)(fa >> 1);
 }
 
 template <int PL>
 __global__ __launch_bounds__(64) void mfcc_x2_kernel(const short *__restrict__ pcm, const long long *__restrict__ starts,
                                                      long n_frames, MfccDev p, const float2 *__restrict__ table,
-                                                     double *__restrict__ feats)
+                                                     double *__restrict__ feats, int *__restrict__ redo)
 {
     // 9,344 B per wave: the two transform scratches; |X| (544 floats each), the filterbank pieces and the channel
     // logarithms live in the scratches' second halves (seventeen waves per CU instead of fourteen)
@@ -579,9 +654,9 @@ __global__ __launch_bounds__(64) void mfcc_x2_kernel(const short *__restrict__ p
     const short *src_b = pcm + (starts ? starts[fb] : (long long)p.hop * fb);
     // full-length window and both frames 4-byte aligned: one dword per sample pair (wave-uniform)
     if (p.win_len == 1024 && ((((uintptr_t)src_a) | ((uintptr_t)src_b)) & 3u) == 0)
-        mfcc_x2_body<true, PL>(src_a, src_b, fa, fb, two, p, table, feats, lds, lane);
+        mfcc_x2_body<true, PL>(src_a, src_b, fa, fb, two, p, table, feats, lds, lane, redo);
     else
-        mfcc_x2_body<false, PL>(src_a, src_b, fa, fb, two, p, table, feats, lds, lane);
+        mfcc_x2_body<false, PL>(src_a, src_b, fa, fb, two, p, table, feats, lds, lane, redo);
 }
 
 // ---- persistent waves, spectrum in registers ------------------------------------------------------------------------
@@ -602,10 +677,12 @@ __device__ __forceinline__ void load_mel_piece(MelPiece &m, const MfccDev &p, in
 }
 
 // |X| of two frames, bin i at mag[i + (i >> 4)] (see mfcc_x2_kernel) -> feats[fa], feats[fb]
-__device__ __forceinline__ void mfcc_tail_x2(const float *mag_a, const float *mag_b, float (*logmel)[64], float (*pieces)[2][64],
+// Returns whether the pair must be computed again, apart (mfcc_leak_redo; e_pair = sum |z|^2 over both frames).
+__device__ __forceinline__ bool mfcc_tail_x2(const float *mag_a, const float *mag_b, float (*logmel)[64], float (*pieces)[2][64],
                                              const MfccDev &p, int lane, const MelPiece &mp, long fa, long fb, bool two,
-                                             double *__restrict__ feats)
+                                             double *__restrict__ feats, float e_pair)
 {
+    float ta = 0.f, tb = 0.f;
     {
         float lo_a = 0.f, hi_a = 0.f, lo_b = 0.f, hi_b = 0.f;
         float ma[16], mb[16];
@@ -624,7 +701,7 @@ __device__ __forceinline__ void mfcc_tail_x2(const float *mag_a, const float *ma
         }
         if (p.chan_ok) {
             if (mp.sg.y <= 0) { lo_a = hi_a = lo_b = hi_b = 0.f; }
-            mel_channel_sums(pieces, logmel, p, lane, lo_a, hi_a, lo_b, hi_b);
+            mel_channel_sums<true>(pieces, logmel, p, lane, lo_a, hi_a, lo_b, hi_b, &ta, &tb);
         } else {
             if (mp.sg.y > 0) {
                 if (mp.sg.z >= 1) { atomicAdd(&logmel[0][mp.sg.z - 1], lo_a); atomicAdd(&logmel[1][mp.sg.z - 1], lo_b); }
@@ -632,8 +709,11 @@ __device__ __forceinline__ void mfcc_tail_x2(const float *mag_a, const float *ma
             }
             wave_lds_fence();
             if (lane < p.n_chan) {                                   // :171, hardware log2 (see mel_channel_sums)
-                logmel[0][lane] = __logf(logmel[0][lane]);
-                logmel[1][lane] = __logf(logmel[1][lane]);
+                const float sa = logmel[0][lane], sb = logmel[1][lane], w2 = p.chan_w2[lane];
+                logmel[0][lane] = __logf(sa);
+                logmel[1][lane] = __logf(sb);
+                ta = mfcc_leak_term(sa, w2);
+                tb = mfcc_leak_term(sb, w2);
             }
             wave_lds_fence();
         }
@@ -653,27 +733,13 @@ __device__ __forceinline__ void mfcc_tail_x2(const float *mag_a, const float *ma
     }
     if (!wide) { acc_a = sum_xor16_f64(acc_a); acc_b = sum_xor16_f64(acc_b); }
     acc_a = sum_xor32_f64(acc_a); acc_b = sum_xor32_f64(acc_b);
+    const double lw = p.lifter_w[lane & 31];
     if (lane < p.n_cep) {
-        const double lw = p.lifter_w[lane];
         feats[fa * p.n_cep + lane] = acc_a * lw;
         if (two) feats[fb * p.n_cep + lane] = acc_b * lw;
     }
     wave_lds_fence();                                                // logmel and the magnitudes are rewritten next
-}
-
-// sum over the wave, the same value in every lane's copy of lane 63 (five DPP adds and a v_readlane; a __shfl_xor tree
-// is six ds_bpermute, 8.9 issue slots each)
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-#define JDSP_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, true))
-    JDSP_DPP_ADD(0xB1, 0xf);     // quad_perm [1,0,3,2]
-    JDSP_DPP_ADD(0x4E, 0xf);     // quad_perm [2,3,0,1]
-    JDSP_DPP_ADD(0x141, 0xf);    // row_half_mirror: sums of 8
-    JDSP_DPP_ADD(0x140, 0xf);    // row_mirror: sums of 16
-    JDSP_DPP_ADD(0x142, 0xa);    // row_bcast15 into rows 1 and 3
-    JDSP_DPP_ADD(0x143, 0xc);    // row_bcast31 into rows 2 and 3
-#undef JDSP_DPP_ADD
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+    return mfcc_leak_redo(ta, tb, acc_a * lw, acc_b * lw, lane < p.n_cep, e_pair, e_pair, p.leak_k2);
 }
 
 // previous lane's value (wave_shr:1); lane 0 gets `lane0`
@@ -684,26 +750,24 @@ __device__ __forceinline__ float prev_lane(float v, float lane0, int lane)
 }
 
 // Two frames' samples (lane + 64 r) -> pre-emphasis (:208-210), window, one transform, |A[k]|, |B[k]| for k = lane + 64 d,
-// d < 4.  Returns whether the two frames' energies are more than 36 dB apart (wave-uniform).
-__device__ __forceinline__ bool mfcc512_pair_mags(const float (&sa)[8], const float (&sb)[8], float preemph,
+// d < 4.  Returns sum |z|^2 over both frames (wave-uniform), what the transform's rounding scales with (mfcc_leak_redo).
+__device__ __forceinline__ float mfcc512_pair_mags(const float (&sa)[8], const float (&sb)[8], float preemph,
                                                   const float (&win)[8], const WaveTwiddles &tw, float2 *lds, int lane,
                                                   float (&ma)[4], float (&mb)[4])
 {
     // x[i] = s[i] - preemph * s[i-1] for 1 <= i < win_len, x[0] = 0 (:208 starts at i = 1); the window is zero beyond
     float2 v[8];
-    float ea = 0.f, eb = 0.f;
+    float e = 0.f;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const float pa = prev_lane(sa[r], r > 0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sa[r > 0 ? r - 1 : 0]), 63)) : 0.f, lane);
         const float pb = prev_lane(sb[r], r > 0 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sb[r > 0 ? r - 1 : 0]), 63)) : 0.f, lane);
         float xa = (sa[r] - preemph * pa) * win[r], xb = (sb[r] - preemph * pb) * win[r];
         if (r == 0 && lane == 0) { xa = 0.f; xb = 0.f; }
-        ea = fmaf(xa, xa, ea);
-        eb = fmaf(xb, xb, eb);
+        e = fmaf(xa, xa, fmaf(xb, xb, e));
         v[r] = make_float2(xa, xb);
     }
-    ea = wave_sum_f32(ea);
-    eb = wave_sum_f32(eb);
+    e = wave_sum_f32(e);
     wave_fft512<false>(v, lds, lane, tw);
     wave_lds_fence();
     // bins k = lane + 64 d, d < 4 (0..255): mirrors Z[512 - k] are registers 4..7 of other lanes and Z[512] = Z[0]
@@ -719,7 +783,7 @@ __device__ __forceinline__ bool mfcc512_pair_mags(const float (&sa)[8], const fl
         mb[d] = __builtin_amdgcn_sqrtf(B.x * B.x + B.y * B.y);
     }
     wave_lds_fence();
-    return !(ea <= 4096.f * eb && eb <= 4096.f * ea);            // also when exactly one frame is all zeros
+    return e;
 }
 
 #ifndef JDSP_MFCC512_WAVES
@@ -729,11 +793,16 @@ __device__ __forceinline__ bool mfcc512_pair_mags(const float (&sa)[8], const fl
 // A[k] = (Z[k] + conj Z[512-k]) / 2, B[k] = -j (Z[k] - conj Z[512-k]) / 2 (the 1/2 is in the window table) -- half the
 // transform work of the zero-padded 1024-point form mfcc_x2_kernel uses for this configuration.  Lane l holds sample
 // l + 64 r of both frames (2-byte loads: any frame start), the sample before it comes from lane l - 1.
-// The two spectra come apart exactly only in exact arithmetic: frame b's rounding (6e-8 of ITS magnitudes) lands in
-// frame a's bins.  Between neighbours of similar level that is the FP32 noise floor the 1e-5 bar already allows for;
-// when the two frames' energies differ by more than 36 dB (or one of them is all zeros, whose ln 0 = -inf, :171, must
-// stay exact) the pair's index goes onto a list and mfcc_kernel computes both frames again, one per transform (a branch
-// inside this kernel cost 15 % of its speed in registers: profiles/r02_mfcc512_run.txt).
+// The two spectra come apart exactly only in exact arithmetic: the shared transform's rounding, which scales with the
+// LOUDER frame, lands in the quieter frame's bins too, and ln() of a mel channel divides it by the channel's own sum.
+// A flat spectrum next to one of similar level never notices; a coloured frame does, next to a partner as little as
+// 10 dB louder -- and the loudest frames of some families next to nobody (a tone, high-pass noise: low channels 90 dB
+// under the peak).  Measured on white, vowel, low-pass, high-pass and tone frames 0-35 dB under a partner
+// (profiles/r10_mfcc_pair_leak.txt): up to 4.0e-4 of the vector's peak with only a whole-frame energy test (pairs
+// more than 36 dB apart), which is what this kernel had.  Now the tail judges every frame where the mel sums and the
+// cepstrum exist (mfcc_leak_redo, above, with its bound); a pair with a frame that fails goes onto a list, and
+// mfcc_redo_f64_kernel computes both its frames again, apart and in FP64 (a branch inside this kernel cost 15 % of
+// its speed in registers: profiles/r02_mfcc512_run.txt).  At most one entry per pair: the list holds a call's pairs.
 __global__ __launch_bounds__(64, JDSP_MFCC512_WAVES) void mfcc512_run_kernel(const short *__restrict__ pcm, const long long *__restrict__ starts,
                                                             long n_frames, MfccDev p, const float2 *__restrict__ table,
                                                             double *__restrict__ feats, int *__restrict__ redo)
@@ -774,8 +843,7 @@ __global__ __launch_bounds__(64, JDSP_MFCC512_WAVES) void mfcc512_run_kernel(con
         for (int r = 0; r < 8; r++) { sa[r] = na[r]; sb[r] = nb[r]; }
         if (q + gridDim.x < n_pairs) fetch(q + gridDim.x);
         float ma[4], mb[4];
-        if (mfcc512_pair_mags(sa, sb, p.preemph, win, tw, lds, lane, ma, mb) && lane == 0)
-            redo[1 + atomicAdd(redo, 1)] = (int)q;                   // rare: both frames again, apart (mfcc_kernel)
+        const float e_pair = mfcc512_pair_mags(sa, sb, p.preemph, win, tw, lds, lane, ma, mb);
         float *mag_a = reinterpret_cast<float *>(lds), *mag_b = mag_a + 320;
 #pragma unroll
         for (int d = 0; d < 4; d++) {
@@ -786,7 +854,9 @@ __global__ __launch_bounds__(64, JDSP_MFCC512_WAVES) void mfcc512_run_kernel(con
         logmel[0][lane] = 0.f;
         logmel[1][lane] = 0.f;
         wave_lds_fence();
-        mfcc_tail_x2(mag_a, mag_b, logmel, pieces, p, lane, mp, fa, fb, two, feats);
+        // (|: the tail's ballots are not skipped.)  The odd last frame of a call has no partner: taken as well
+        if ((mfcc_tail_x2(mag_a, mag_b, logmel, pieces, p, lane, mp, fa, fb, two, feats, e_pair) | !two) && lane == 0)
+            redo[1 + atomicAdd(redo, 1)] = (int)q;                   // both frames again, apart (mfcc_redo_f64_kernel)
     }
 }
 
@@ -849,8 +919,7 @@ __global__ __launch_bounds__(64) void mfcc512_pair_kernel(const short *__restric
 #endif
     const double lw = p.lifter_w[lane & 31];
     float ma[4], mb[4];
-    if (mfcc512_pair_mags(sa, sb, p.preemph, win, tw, lds, lane, ma, mb) && lane == 0)
-        redo[1 + atomicAdd(redo, 1)] = (int)q;
+    const float e_pair = mfcc512_pair_mags(sa, sb, p.preemph, win, tw, lds, lane, ma, mb);
 #if !JDSP_MFCC512_EARLY_TABLES
     mfcc_load_lane_tables(mt, p, lane);
     mfcc_load_dct(dc, p, lane);
@@ -865,7 +934,79 @@ __global__ __launch_bounds__(64) void mfcc512_pair_kernel(const short *__restric
     logmel[0][lane] = 0.f;                                           // (the atomics of the !chan_ok form add to them)
     logmel[1][lane] = 0.f;
     wave_lds_fence();
-    mfcc_tail_pre(mag_a, mag_b, logmel, pieces, p, lane, mt, dc, lw, fa, fb, two, feats);
+    // The odd last frame of a call has no partner (the second slot repeats it): it is taken as well, so a frame submitted
+    // alone and the same frame separated from a partner come out of the same arithmetic, bit for bit.
+    if ((mfcc_tail_pre<PL, true>(mag_a, mag_b, logmel, pieces, p, lane, mt, dc, lw, fa, fb, two, feats, e_pair, e_pair) | !two) && lane == 0)
+        redo[1 + atomicAdd(redo, 1)] = (int)q;                           // both frames again, apart (mfcc_redo_f64_kernel)
+}
+
+// The frames on the list {count, entries...} again, each on its own and in FP64 from the samples on, as the reference
+// computes them (:208-226): pre-emphasis, Hamming, a direct NFFT-point DFT over the win_len samples (bins lane + 64 d,
+// twiddles from a table of exact cosines and sines in LDS), |X|, the mel sums in the reference's order, ln, DCT,
+// lifter.  Nothing of FP32 is left in a frame that FP32 could not hold; win_len * NFFT / 64 FP64 multiply-adds per lane
+// and frame are the price, paid only by the frames the criterion names.  PER = 2: an entry q is the pair of frames
+// 2 q, 2 q + 1 (the kernels with two frames per wave); PER = 1: an entry is a frame (mfcc_kernel).  One wave per
+// block, waves stride over the list.
+template <int NFFT, int PER>
+__global__ __launch_bounds__(64) void mfcc_redo_f64_kernel(const short *__restrict__ pcm, const long long *__restrict__ starts,
+                                                           long n_frames, MfccDev p, double *__restrict__ feats,
+                                                           const int *__restrict__ redo)
+{
+    constexpr int NB = NFFT / 2, D = NB / 64;
+    __shared__ double2 tw[NFFT];
+    __shared__ double x[NFFT];
+    __shared__ double mag[NB];
+    __shared__ double logmel[64];
+    const int lane = threadIdx.x;
+    const long n_redo = (long)PER * redo[0];
+    if ((long)blockIdx.x >= n_redo) return;
+#pragma unroll
+    for (int r = 0; r < NFFT / 64; r++) tw[lane + 64 * r] = p.tw_f64[lane + 64 * r];
+    for (long it = blockIdx.x; it < n_redo; it += gridDim.x) {
+        const long f = (long)PER * redo[1 + it / PER] + it % PER;
+        if (f >= n_frames) continue;                                 // the odd tail's second slot
+        const short *src = pcm + (starts ? starts[f] : (long long)p.hop * f);
+        __syncthreads();                                             // (one wave: orders LDS reuse between frames)
+#pragma unroll
+        for (int r = 0; r < NFFT / 64; r++) {
+            const int i = lane + 64 * r;
+            double v = 0.0;
+            if (i >= 1 && i < p.win_len) v = ((double)src[i] - p.preemph_f64 * (double)src[i - 1]) * p.win_f64[i];   // :208-214
+            x[i] = v;
+        }
+        __syncthreads();
+        double re[D], im[D];
+#pragma unroll
+        for (int d = 0; d < D; d++) re[d] = im[d] = 0.0;
+        for (int n = 1; n < p.win_len; n++) {                        // x[0] = 0
+            const double xn = x[n];
+#pragma unroll
+            for (int d = 0; d < D; d++) {
+                const double2 w = tw[(n * (lane + 64 * d)) & (NFFT - 1)];
+                re[d] = fma(xn, w.x, re[d]);
+                im[d] = fma(xn, w.y, im[d]);
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < D; d++) mag[lane + 64 * d] = sqrt(re[d] * re[d] + im[d] * im[d]);          // :218-220
+        __syncthreads();
+        if (lane < p.n_chan) {                                       // :157-168, channel `lane`, bins in the reference's order
+            double m = 0.0;
+            for (int i = 0; i < p.n_bins; i++) {
+                const int k = p.mel_k[i];
+                const double fb = p.fb_f64[i];
+                if (k == lane) m += (1 - fb) * mag[i];
+                else if (k == lane + 1) m += fb * mag[i];
+            }
+            logmel[lane] = log(m);                                   // :171
+        }
+        __syncthreads();
+        if (lane < p.n_cep) {                                        // :178-182, :189
+            double acc = 0.0;
+            for (int k = 0; k < p.n_chan; k++) acc += p.dct[k * 32 + lane] * logmel[k];
+            feats[f * p.n_cep + lane] = acc * p.lifter_w[lane];
+        }
+    }
 }
 
 // (Tried for n_fft = 1024 too -- two frames per iteration through wave_fft512_x2, pair-owned |X|, tables in registers:
@@ -884,9 +1025,11 @@ int launch_mfcc(hipStream_t s, const short *pcm, const long long *starts, long n
 #ifndef JDSP_MFCC_RUN
 #define JDSP_MFCC_RUN 1            // 1: persistent register-resident kernels where they apply
 #endif
-    if (JDSP_MFCC_RUN && p.seg_ok && p.bin_stride == 2 && p.win_len <= 512 && redo) {
+    // every kernel leaves the frames FP32 could not hold on `redo` (mfcc_leak_one); the FP64 pass computes them again
+    if (hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
+    int per = 2;
+    if (JDSP_MFCC_RUN && p.seg_ok && p.bin_stride == 2 && p.win_len <= 512) {
         const long n_pairs = (n_frames + 1) / 2;
-        if (hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
         if (JDSP_MFCC512_ONE) {
             const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8));
             if (p.piece_len <= 8) hipLaunchKernelGGL(mfcc512_pair_kernel<8>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
@@ -897,16 +1040,23 @@ int launch_mfcc(hipStream_t s, const short *pcm, const long long *starts, long n
             const long grid = n_pairs < slots ? n_pairs : slots;
             hipLaunchKernelGGL(mfcc512_run_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
         }
-        hipLaunchKernelGGL(mfcc_kernel, dim3(1024), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, (const int *)redo);
     } else if (JDSP_MFCC_X2 && p.seg_ok) {
         const long grid = ((n_frames + 1) / 2 + 7) / 8 * 8;
-        if (p.piece_len <= 8) hipLaunchKernelGGL(mfcc_x2_kernel<8>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats);
-        else if (p.piece_len <= 12) hipLaunchKernelGGL(mfcc_x2_kernel<12>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats);
-        else hipLaunchKernelGGL(mfcc_x2_kernel<16>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats);
+        if (p.piece_len <= 8) hipLaunchKernelGGL(mfcc_x2_kernel<8>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
+        else if (p.piece_len <= 12) hipLaunchKernelGGL(mfcc_x2_kernel<12>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
+        else hipLaunchKernelGGL(mfcc_x2_kernel<16>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
     } else {                              // filterbanks that do not fit one piece per lane (many narrow channels)
         const long grid = (n_frames + 7) / 8 * 8;
-        hipLaunchKernelGGL(mfcc_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats,
-                           (const int *)nullptr);
+        hipLaunchKernelGGL(mfcc_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
+        per = 1;
+    }
+    const int *list = redo;
+    if (p.bin_stride == 2) {
+        if (per == 2) hipLaunchKernelGGL((mfcc_redo_f64_kernel<512, 2>), dim3(2048), dim3(64), 0, s, pcm, starts, n_frames, p, feats, list);
+        else hipLaunchKernelGGL((mfcc_redo_f64_kernel<512, 1>), dim3(2048), dim3(64), 0, s, pcm, starts, n_frames, p, feats, list);
+    } else {
+        if (per == 2) hipLaunchKernelGGL((mfcc_redo_f64_kernel<1024, 2>), dim3(2048), dim3(64), 0, s, pcm, starts, n_frames, p, feats, list);
+        else hipLaunchKernelGGL((mfcc_redo_f64_kernel<1024, 1>), dim3(2048), dim3(64), 0, s, pcm, starts, n_frames, p, feats, list);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -190,8 +190,8 @@ def test_baseline_config4_ten_thousand_ragged_utterances(eng, oracle):
 
 def test_paired_frames_of_very_different_level_and_silence(eng, oracle):
     """512-FFT configurations put two frames into one transform.  A loud frame's rounding must not show in a quiet
-    partner (more than 36 dB apart: separate passes), and an all-zero frame keeps the reference's ln 0 = -inf whatever
-    it is paired with."""
+    partner (separate passes: test_mfcc_coloured_gpu.py has the coloured cases), and an all-zero frame keeps the
+    reference's ln 0 = -inf whatever it is paired with."""
     kw = dict(win_len=400, hop=160, n_fft=512, n_chan=40, n_cep=13, half_rate=8000.0)
     ocfg = oracle.mfcc_cfg(n_bins=256, **kw)
     rng = np.random.default_rng(31)

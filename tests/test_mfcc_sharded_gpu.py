@@ -70,9 +70,9 @@ def test_utterance_sharded_mfcc_equals_the_single_gpu_batch(eng, oracle, batch, 
         want = whole[f0:f1]
         assert got.shape == want.shape
         err = ((got - want).abs() / want.abs().amax(dim=1, keepdim=True)).max().item()
-        # whatever the pairing: both results are FP32 chains held to 1e-5 of the FP64 oracle, so 2e-5 of each other.  (Over
-        # 3.5 M noise frames the largest difference seen is 9.7e-6: a frame whose low channels happen to be 40 dB below
-        # its own average takes the transform's rounding floor relative to those channels, ln() divides by them.)
+        # whatever the pairing: both results are held to 1e-5 of the FP64 oracle, so 2e-5 of each other.  Which frames a
+        # partner can push towards that bar, and what the kernel does about them: test_mfcc_coloured_gpu.py and
+        # profiles/r10_mfcc_pair_leak.txt.
         assert err < 2e-5, err
         if f0 % 2 == 0:
             # same pairs as the batch -> bit for bit; except the shard's LAST frame when its length is odd: alone in
