@@ -43,7 +43,8 @@ extern "C" {
  *    jdsp_set_option("stft.read_pass") accepts -1 / 0 / 1 only; the STFT synthesis entries jdsp_istft_* added;
  *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added; the time-domain pitch entries
  *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added; the multi-stream IIR equaliser
- *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added
+ *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added;
+ *    jdsp_denoise_frames_recomputed added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -291,6 +292,12 @@ int jdsp_denoise_process(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks
                          float *precast_host, long *n_out_blocks);
 /* Current rgdEstimatedNS (n_fft doubles, host).  Synchronises. */
 int jdsp_denoise_noise(jdsp_denoise *h, double *noise_host);
+/* How many frames of the last call (process, apply or shard_finish) the FP32 kernels handed to the FP64 pass: in
+ * spectral subtraction because transform rounding could show through the phase of bins far below the noise estimate
+ * (exactly periodic input), and at 512-point frames, in both modes, because a quiet frame shares its transform with a
+ * loud one.  1024-point Wiener: always 0.  Negative: an error code.
+ * Synchronises. */
+long jdsp_denoise_frames_recomputed(jdsp_denoise *h);
 /* VoiceActivityDetection results of the first n blocks of the last process call:
  * voice flag, sum of squared truncated samples (dEnergy*1024, SS:135) and dZCR (SS:140).
  * Any pointer may be NULL.  The flags are always there; energies and counts only when the "vad_trace" option was

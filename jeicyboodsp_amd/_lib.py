@@ -90,6 +90,7 @@ def _load():
         "jdsp_denoise_process_dev": (i, [vp, vp, l, vp, vp, C.POINTER(l)]),
         "jdsp_denoise_process": (i, [vp, vp, l, vp, vp, C.POINTER(l)]),
         "jdsp_denoise_noise": (i, [vp, vp]),
+        "jdsp_denoise_frames_recomputed": (l, [vp]),
         "jdsp_denoise_vad_trace": (i, [vp, l, vp, vp, vp]),
         "jdsp_gmm_create": (i, [vp, vp, i, C.POINTER(vp)]),
         "jdsp_gmm_destroy": (i, [vp]),

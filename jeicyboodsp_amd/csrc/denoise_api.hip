@@ -86,6 +86,7 @@ int jdsp_denoise_reset(jdsp_denoise *h)
     h->calls = 0;
     h->cur = 0;
     h->last_blocks = 0;
+    h->redo_valid = 0;
     return JDSP_OK;
 }
 
@@ -144,6 +145,8 @@ static int reserve2(jdsp_denoise *h, long max_blocks)
     if (e == hipSuccess) e = w.chunk_alpha.alloc(n_chunks);
     if (e == hipSuccess) e = w.chunk_beta.alloc(n_chunks * 1024);
     if (e == hipSuccess) e = w.a_start.alloc(n_chunks * 1024);
+    if (e == hipSuccess) e = w.redo.alloc(n + 1);
+    h->redo_valid = 0;
     if (e != hipSuccess) {
         w = {};
         return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_denoise_reserve", e);
@@ -180,8 +183,9 @@ int jdsp_denoise_process_dev(jdsp_denoise *h, const int16_t *pcm_dev, long n_blo
         jdsp::launch_noise_estimate(s, g, pcm_dev, n_blocks, st_in, st_out, r.events.get(), r.ev_n.get(), h->plan.get(),
                                     r.ver_base.get(), r.snap_mask.get(), table, accum(h), w.rows.get()) ||
         jdsp::launch_denoise(s, g, h->mode, h->opt_k, ctx->n_cu, pcm_dev, n_blocks, h->calls, st_in, st_out,
-                             r.ver_base.get(), r.snap_mask.get(), w.rows.get(), table, out_dev, precast_dev))
+                             r.ver_base.get(), r.snap_mask.get(), w.rows.get(), table, out_dev, precast_dev, w.redo.get()))
         return fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError());
+    h->redo_valid = 1;
     h->cur ^= 1;
     h->calls += n_blocks;
     h->last_blocks = n_blocks;
@@ -244,7 +248,8 @@ int jdsp_denoise_apply(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks, 
     hc.zero(snap_mask, ((size_t)n_blocks / 64 + 1) * sizeof(unsigned long long));
     hc.copy_dev(st_out, st_in, sizeof(jdsp::DenoiseState));
     if (hc.ok() && jdsp::launch_denoise(s, geom(h), h->mode, h->opt_k, ctx->n_cu, d_in, n_blocks, h->calls, st_in, st_out,
-                                        ver_base, snap_mask, rows, ctx->stft1024_table.get(), d_out, d_pre))
+                                        ver_base, snap_mask, rows, ctx->stft1024_table.get(), d_out, d_pre,
+                                        h->ws.redo.get()))
         hc.result(fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError()));
     hc.download(out_host, d_out, (size_t)n_out * blk_b);
     hc.download(precast_host, d_pre, (size_t)n_out * blk_b * 2);
@@ -253,6 +258,7 @@ int jdsp_denoise_apply(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks, 
         h->cur ^= 1;
         h->calls += n_blocks;
         h->last_blocks = 0;
+        h->redo_valid = 1;
     }
     return rc;
 }
@@ -375,8 +381,9 @@ int jdsp_denoise_shard_finish_dev(jdsp_denoise *h, const float *last_all_dev, in
         if (jdsp::launch_denoise(s, geom(h), h->mode, h->opt_k, ctx->n_cu, h->sh_pcm, h->sh_b1 - h->sh_ext0, h->sh_ext0,
                                  h->st[h->cur].get(), h->st[h->cur ^ 1].get(), h->ws.run.ver_base.get(),
                                  h->ws.run.snap_mask.get(), h->ws.rows.get(), ctx->stft1024_table.get(), out_dev,
-                                 precast_dev, &sh))
+                                 precast_dev, h->ws.redo.get(), &sh))
             return fail(ctx, JDSP_EHIP, "denoise launch", hipGetLastError());
+        h->redo_valid = 1;
     }
     return JDSP_OK;
 }
@@ -390,6 +397,18 @@ int jdsp_denoise_noise(jdsp_denoise *h, double *noise_host)
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < h->n_fft; i++) noise_host[i] = tmp[i];
     return JDSP_OK;
+}
+
+long jdsp_denoise_frames_recomputed(jdsp_denoise *h)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    if (!h->redo_valid || (h->mode != JDSP_SPECSUB && h->n_fft == 1024)) return 0;   // 1024-point Wiener lists nothing
+    int n = 0;
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    JDSP_HIP(ctx, hipMemcpyAsync(&n, h->ws.redo.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return n;
 }
 
 int jdsp_denoise_vad_trace(jdsp_denoise *h, long n, uint8_t *voice_host, int64_t *energy_sum_host, int32_t *zcr_host)

@@ -586,32 +586,93 @@ __global__ __launch_bounds__(1024) void noise_combine_kernel(const DenoisePlan *
 #ifndef JDSP_GAIN_SELECT
 #define JDSP_GAIN_SELECT 1
 #endif
+//
+// Which spectral-subtraction frames FP32 cannot hold.  In a bin far below its noise value the output is -N e^{j phase(X)}:
+// its size is N however small X is, and its direction is the phase of X -- which a FP32 transform leaves arbitrary once
+// |X| is at its own rounding, eps = 2^-23 sqrt(E) per bin (E = the energy of the windowed samples that share the
+// transform; tests/mfcc_fp32_ref.py pins that constant for these radix-8 passes).  Rounding eps in X[k] moves Y[k] by
+// eps along X (the gain is near 1 or below) and by eps N / |X| across it, so the frame's samples are off, relative to
+// their own root mean square (Parseval on both sides), by
+//     rho^2 = eps^2 sum_k (1 + (N_k / |X_k|)^2) / sum_k |Y_k|^2 .
+// q = N / |X| is the gain's own subtrahend; E is summed over the windowed samples before the forward transform and
+// sum |Y|^2 = n_fft sum y^2 over the samples after the inverse one, and each sum goes through the wave to a scalar
+// register as soon as it is complete, so nothing of this stays in vector registers across a transform.  A frame with
+// rho above kPhaseRho = half the project's bar of 1e-5 is computed again in FP64 (denoise_redo_f64_kernel);
+// tests/denoise_fp32_ref.py restates rho and the FP32 chain on the CPU, where no frame with rho under 9.9e-6 misses
+// half its bar: a margin of two (the constant was not tuned on the device).  Wiener's gain has no such amplifier (its
+// term is (1 + 2 r)^2, r = min(1, N^2 / |X|^2)); only the 512-point kernels evaluate it, for the partner's rounding.  Bins 0 and n_fft / 2 of a real frame are real: rounding cannot turn them, only flip their
+// sign, and only when they are at the rounding itself; they count when |X| < 16 eps.  A bin FP32 rounded to exactly
+// zero counts as q = infinity (or NaN); an all-zero transform (E = 0) is exact.  Two 512-point frames that share a
+// transform share its rounding: E is the pair's, and the 1 in the sum is what a quiet frame takes from a loud partner.
+struct PhaseStat { float e, err; };        // wave-uniform: sum |v|^2 of the transform's input (= E / 4: the window is halved), sum (1 + q^2)
+#ifndef JDSP_PHASE_RHO
+#define JDSP_PHASE_RHO 5.0e-6f
+#endif
+constexpr float kPhaseRho = JDSP_PHASE_RHO;
+// rho^2 > kPhaseRho^2  <=>  err * e * phase_k() > sum y^2, with e = E / 4
+template <int NFFT>
+__device__ __forceinline__ constexpr float phase_k() { return 4.0f * 1.4210854715202004e-14f / ((float)NFFT * kPhaseRho * kPhaseRho); }
+// a real bin counts when |X|^2 < (16 eps)^2 = kRealBinK e: a lane's threshold for the bins that may be real
+constexpr float kRealBinK = 256.0f * 4.0f * 1.4210854715202004e-14f;
+__device__ __forceinline__ float real_bin_thr(float e, bool real) { return real ? kRealBinK * e : __builtin_inff(); }
+
+__device__ __forceinline__ float wave_sum_f32(float v)
+{
+    // as wave_sum_u32: five DPP adds and a v_readlane; the result is wave-uniform
+#define JDSP_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, true))
+    JDSP_DPP_ADD(0xB1, 0xf); JDSP_DPP_ADD(0x4E, 0xf); JDSP_DPP_ADD(0x141, 0xf); JDSP_DPP_ADD(0x140, 0xf);
+    JDSP_DPP_ADD(0x142, 0xa); JDSP_DPP_ADD(0x143, 0xc);
+#undef JDSP_DPP_ADD
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// the frame's verdict; ysq = this lane's share of sum y^2 over the frame's samples
+template <int NFFT>
+__device__ __forceinline__ bool phase_unsafe(float e, float err, float ysq)
+{
+    return e > 0.0f && !(err * e * phase_k<NFFT>() <= wave_sum_f32(ysq));
+}
+__device__ __forceinline__ float sumsq(const float2 (&v)[8])
+{
+    float a = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 8; r++) a += v[r].x * v[r].x + v[r].y * v[r].y;
+    return a;
+}
+
+// one frame more on the list {count, frames...} of denoise_redo_f64_kernel
+__device__ __forceinline__ void phase_redo(int *__restrict__ redo, long j, int lane)
+{
+    if (lane == 0) redo[1 + atomicAdd(redo, 1)] = (int)j;
+}
+
+// w: how many bins of the spectrum this value stands for (a lane that owns a mirror pair evaluates one of the two)
 template <int MODE>
-__device__ __forceinline__ float2 apply_gain(float2 x, float n)
+__device__ __forceinline__ float2 apply_gain(float2 x, float n, float &err, float w, bool maybe_real = false,
+                                             float rthr = 0.0f)
 {
     // hardware reciprocal / reciprocal square root (1 ulp): the bar is 1e-5, not IEEE division
     const float p = x.x * x.x + x.y * x.y;
     if (MODE == 0) {
-#if JDSP_GAIN_SELECT
-        const float g = 1.0f - n * __frsqrt_rn(p);           // (|X| - N) / |X|; p == 0 gives inf / NaN, replaced below
+        const float q = n * __frsqrt_rn(p);                   // N / |X|; p == 0 gives inf / NaN: the frame goes to FP64
+        const float g = 1.0f - q;                               // (|X| - N) / |X|; p == 0: replaced below
         const bool zero = p == 0.0f;
+        if (maybe_real) w = p < rthr ? w : 0.0f;                // (maybe_real is a compile-time fact of every call)
+        err += w * (q * q + 1.0f);
         return make_float2(zero ? -n : x.x * g, zero ? 0.0f : x.y * g);
-#else
-        if (p == 0.0f) return make_float2(-n, 0.0f);
-        const float g = 1.0f - n * __frsqrt_rn(p);           // (|X| - N) / |X|
-        return make_float2(x.x * g, x.y * g);
-#endif
     } else {
         float r = (n * n) * __builtin_amdgcn_rcpf(p);                    // 0 * inf = NaN keeps the reference's 0/0
         if (r >= 1.0f) r = 1.0f;
         const float g = 1.0f - r;
+        const float t = 1.0f + 2.0f * r;                        // Wiener: rounding eps in X moves Y by at most (1 + 2 r) eps
+        err += w * (t * t);
         return make_float2(x.x * g, x.y * g);
     }
 }
 
 template <int MODE, int J>
 __device__ __forceinline__ void gain_presplit_j(const float2 *lds, float2 *zout, int lane, const float2 *wsp,
-                                                const float *__restrict__ noise)
+                                                const float *__restrict__ noise, float &err, float e)
 {
     const int m = 128 * J + 2 * lane;
     const float4 zz = *reinterpret_cast<const float4 *>(&lds[m]);
@@ -622,8 +683,9 @@ __device__ __forceinline__ void gain_presplit_j(const float2 *lds, float2 *zout,
     float2 lo0, hi0, lo1, hi1;
     split_fwd<J>(make_float2(zz.x, zz.y), zr0, wsp[0], lo0, hi0);
     split_fwd<J>(make_float2(zz.z, zz.w), zr1, wsp[1], lo1, hi1);
-    lo0 = apply_gain<MODE>(lo0, nlo.x); hi0 = apply_gain<MODE>(hi0, nhi.x);
-    lo1 = apply_gain<MODE>(lo1, nlo.y); hi1 = apply_gain<MODE>(hi1, nhi.y);
+    const float rthr = real_bin_thr(e, lane == 0);              // J == 0, lane 0: lo0 and hi0 are the bins 0 and 512
+    lo0 = apply_gain<MODE>(lo0, nlo.x, err, 1.0f, J == 0, rthr); hi0 = apply_gain<MODE>(hi0, nhi.x, err, 1.0f, J == 0, rthr);
+    lo1 = apply_gain<MODE>(lo1, nlo.y, err, 1.0f); hi1 = apply_gain<MODE>(hi1, nhi.y, err, 1.0f);
     zout[2 * J] = presplit_inv<J>(lo0, hi0, wsp[0]);
     zout[2 * J + 1] = presplit_inv<J>(lo1, hi1, wsp[1]);
 }
@@ -632,14 +694,25 @@ __device__ __forceinline__ void gain_presplit_j(const float2 *lds, float2 *zout,
 // transform layout: y[d] = (y[2 lane + 128 d], y[2 lane + 128 d + 1]).
 template <int MODE>
 __device__ __forceinline__ void denoise_frame(const unsigned int *raw, const FrameTables &t, float2 *lds, int lane,
-                                              const float *__restrict__ noise, float2 (&y)[8])
+                                              const float *__restrict__ noise, float2 (&y)[8], PhaseStat &ps)
 {
+    if (MODE == 0) {
+        float e = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const float2 sv = unpack_i16x2(raw[r]);
+            e += (sv.x * t.win[r].x) * (sv.x * t.win[r].x) + (sv.y * t.win[r].y) * (sv.y * t.win[r].y);
+        }
+        ps.e = wave_sum_f32(e);
+    }
     forward_to_lds(raw, t, lds, lane);
     float2 z[8];
-    gain_presplit_j<MODE, 0>(lds, z, lane, t.wsp, noise);
-    gain_presplit_j<MODE, 1>(lds, z, lane, t.wsp, noise);
-    gain_presplit_j<MODE, 2>(lds, z, lane, t.wsp, noise);
-    gain_presplit_j<MODE, 3>(lds, z, lane, t.wsp, noise);
+    float err = 0.0f;
+    gain_presplit_j<MODE, 0>(lds, z, lane, t.wsp, noise, err, ps.e);
+    gain_presplit_j<MODE, 1>(lds, z, lane, t.wsp, noise, err, ps.e);
+    gain_presplit_j<MODE, 2>(lds, z, lane, t.wsp, noise, err, ps.e);
+    gain_presplit_j<MODE, 3>(lds, z, lane, t.wsp, noise, err, ps.e);
+    if (MODE == 0) ps.err = wave_sum_f32(err);
     wave_lds_fence();
 #pragma unroll
     for (int j = 0; j < 4; j++)
@@ -663,7 +736,8 @@ __device__ __forceinline__ void denoise_frame(const unsigned int *raw, const Fra
 // no natural-order image, no Z' image, three fences fewer (frame_io.h).  noise[m] is read at m = lane + 64 d.
 template <int MODE>
 __device__ __forceinline__ void denoise_frame_reg(const unsigned int *raw, const FrameTables &t, const SplitTwiddles &sw,
-                                                  float2 *lds, int lane, const float *__restrict__ noise, float2 (&y)[8])
+                                                  float2 *lds, int lane, const float *__restrict__ noise, float2 (&y)[8],
+                                                  PhaseStat &ps)
 {
     float2 v[8];
 #pragma unroll
@@ -671,6 +745,8 @@ __device__ __forceinline__ void denoise_frame_reg(const unsigned int *raw, const
         const float2 s = unpack_i16x2(raw[r]);
         v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
     }
+    if (MODE == 0) ps.e = wave_sum_f32(sumsq(v));
+    float err = 0.0f;
     wave_fft512<false>(v, lds, lane, t.tw);
     float2 zr[8], lo[8], hi[8];
     mirror_fetch(v, lane, zr);
@@ -678,10 +754,12 @@ __device__ __forceinline__ void denoise_frame_reg(const unsigned int *raw, const
 #pragma unroll
     for (int d = 0; d < 8; d++) {
         const int m = lane + 64 * d;
-        lo[d] = apply_gain<MODE>(lo[d], noise[m]);
-        hi[d] = apply_gain<MODE>(hi[d], noise[m + 512]);
+        const float rthr = real_bin_thr(ps.e, lane == 0);       // d == 0, lane 0: the bins 0 and 512
+        lo[d] = apply_gain<MODE>(lo[d], noise[m], err, 1.0f, d == 0, rthr);
+        hi[d] = apply_gain<MODE>(hi[d], noise[m + 512], err, 1.0f, d == 0, rthr);
         y[d] = presplit_inv_reg(lo[d], hi[d], sw.w[d]);
     }
+    if (MODE == 0) ps.err = wave_sum_f32(err);
     wave_lds_fence();                                            // the forward transform's last exchange reads are done
     wave_fft512<true>(y, lds, lane, t.tw);
     // the reference's 1/N after FFTW's unnormalised inverse (SS:248); a power of two, exact
@@ -706,7 +784,7 @@ __device__ __forceinline__ void load_noise_regs(NoiseRegs &n, const float *__res
 #endif
 template <int MODE>
 __device__ __forceinline__ void denoise_frame_nreg(const unsigned int *raw, const FrameTables &t, const SplitTwiddles &sw,
-                                                   float2 *lds, int lane, const NoiseRegs &n, float2 (&y)[8])
+                                                   float2 *lds, int lane, const NoiseRegs &n, float2 (&y)[8], PhaseStat &ps)
 {
     float2 v[8];
 #pragma unroll
@@ -714,6 +792,8 @@ __device__ __forceinline__ void denoise_frame_nreg(const unsigned int *raw, cons
         const float2 s = unpack_i16x2(raw[r]);
         v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
     }
+    if (MODE == 0) ps.e = wave_sum_f32(sumsq(v));
+    float err = 0.0f;
     wave_fft512<false>(v, lds, lane, t.tw);
     float2 zr[8], lo[8], hi[8];
 #if JDSP_DENOISE_MIRROR_LDS
@@ -729,11 +809,13 @@ __device__ __forceinline__ void denoise_frame_nreg(const unsigned int *raw, cons
     {
 #pragma unroll
         for (int d = 0; d < 8; d++) {
-            lo[d] = apply_gain<MODE>(lo[d], n.lo[d]);
-            hi[d] = apply_gain<MODE>(hi[d], n.hi[d]);
+            const float rthr = real_bin_thr(ps.e, lane == 0);   // d == 0, lane 0: the bins 0 and 512
+            lo[d] = apply_gain<MODE>(lo[d], n.lo[d], err, 1.0f, d == 0, rthr);
+            hi[d] = apply_gain<MODE>(hi[d], n.hi[d], err, 1.0f, d == 0, rthr);
             y[d] = presplit_inv_reg(lo[d], hi[d], sw.w[d]);
         }
     }
+    if (MODE == 0) ps.err = wave_sum_f32(err);
     wave_lds_fence();                                            // the forward transform's last exchange reads are done
     wave_fft512<true>(y, lds, lane, t.tw);
     // the reference's 1/N after FFTW's unnormalised inverse (SS:248); a power of two, exact
@@ -765,34 +847,56 @@ __device__ __forceinline__ void load_noise_pair_regs(NoisePairRegs &n, const flo
 }
 
 // apply_gain<MODE>(x, n) / 2^LOG2N (1024 or 512) with n as load_noise_pair_regs left it
+// (err comes out scaled by 2^-2 LOG2N)
 template <int MODE, int LOG2N = 10>
-__device__ __forceinline__ float2 apply_gain_scaled(float2 x, float n)
+__device__ __forceinline__ float2 apply_gain_scaled(float2 x, float n, float &err, float w, bool maybe_real = false,
+                                                    float rthr = 0.0f)
 {
     const float c = 1.0f / (float)(1 << LOG2N);
     const float p = x.x * x.x + x.y * x.y;
     if (MODE == 0) {
-        const float g = c - n * __frsqrt_rn(p);              // (|X| - N) / (1024 |X|); p == 0 gives inf / NaN, replaced below
+        const float q = n * __frsqrt_rn(p);                   // N / (1024 |X|); p == 0 gives inf / NaN: the frame goes to FP64
+        const float g = c - q;                                  // (|X| - N) / (1024 |X|); p == 0: replaced below
         const bool zero = p == 0.0f;
+        if (maybe_real) w = p < rthr ? w : 0.0f;                // (maybe_real is a compile-time fact of every call)
+        err += w * (q * q + c * c);
         return make_float2(zero ? -n : x.x * g, zero ? 0.0f : x.y * g);
     } else {
         // v_rcp_f32 (1 ulp; __frcp_rn() expands to the IEEE division sequence, a dozen instructions per bin)
         float r = (n * n) * __builtin_amdgcn_rcpf(p);                    // 0 * inf = NaN keeps the reference's 0/0
         if (r >= 1.0f) r = 1.0f;
         const float g = c - c * r;
+        const float t = c + 2.0f * c * r;                       // Wiener: rounding eps in X moves Y by at most (1 + 2 r) eps
+        err += w * (t * t);
         return make_float2(x.x * g, x.y * g);
     }
 }
 
 template <int MODE>
-__device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, const FrameTables &t, const PairTwiddles &pw,
-                                                    float2 *lds, int lane, const NoisePairRegs &n, float2 (&y)[8])
+__device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, const FrameTables &t, const PairTwiddles &pw_regs,
+                                                    const float2 *__restrict__ table, float2 *lds, int lane,
+                                                    const NoisePairRegs &n, float2 (&y)[8], PhaseStat &ps)
 {
+    // Spectral subtraction's criterion sums (phase_unsafe) need registers the persistent wave does not have at four
+    // waves per SIMD (kept for the run, the tables and the sums spill: 28 to 188 bytes per lane in every arrangement
+    // tried).  There the window and the five pair twiddles are fetched per frame (6.5 KB per wave, the same lines
+    // every frame: L1 hits) instead of being kept for the whole run: 125 registers, no scratch.
+    PairTwiddles pw_frame;
+    int pl = lane;
+    if (MODE == 0) {
+        asm volatile("" : "+v"(pl));                            // per frame: not a loop invariant to hoist (and spill)
+        load_pair_twiddles(pw_frame, table, pl);
+    }
+    const PairTwiddles &pw = MODE == 0 ? pw_frame : pw_regs;
     float2 v[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const float2 s = unpack_i16x2(raw[r]);
-        v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
+        const float2 w = MODE == 0 ? table[kStftWin + pl + 64 * r] : t.win[r];
+        v[r] = make_float2(s.x * w.x, s.y * w.y);
     }
+    if (MODE == 0) ps.e = wave_sum_f32(sumsq(v));
+    float err = 0.0f;
     wave_fft512<false>(v, lds, lane, t.tw);
     float2 zr[5], ret[4];
     wave_lds_fence();                                            // the transform's last exchange reads are done
@@ -810,8 +914,11 @@ __device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, con
 #if JDSP_DENOISE_ABLATE & 1                                           /* timing-only: no gain */
         const float2 lo = cadd(e, p), hi = csub(e, p);
 #else
-        const float2 lo = apply_gain_scaled<MODE>(cadd(e, p), n.lo[d]);      // Y[m] / 1024
-        const float2 hi = apply_gain_scaled<MODE>(csub(e, p), n.hi[d]);      // Y[m + 512] / 1024
+        // bins m and m + 512 stand for their mirrors 1024 - m and 512 - m too where those have no owner: m = 1..192
+        const float w = d < 3 ? ((d == 0 && lane == 0) ? 1.0f : 2.0f) : ((d == 3 && lane == 0) ? 2.0f : 1.0f);
+        const float rthr = real_bin_thr(ps.e, lane == 0);       // d == 0, lane 0: the bins 0 and 512
+        const float2 lo = apply_gain_scaled<MODE>(cadd(e, p), n.lo[d], err, w, d == 0, rthr);      // Y[m] / 1024
+        const float2 hi = apply_gain_scaled<MODE>(csub(e, p), n.hi[d], err, w, d == 0, rthr);      // Y[m + 512] / 1024
 #endif
         if (d < 4) {
             presplit_inv_pair(lo, hi, pw.w[d], y[d], ret[d]);
@@ -819,6 +926,7 @@ __device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, con
             y[d] = presplit_inv_reg(lo, hi, pw.w[d]);
         }
     }
+    if (MODE == 0) ps.err = wave_sum_f32(err) * 1048576.0f;            // the gain's 2^-20 undone
 #if JDSP_DENOISE_ABLATE & 2
 #pragma unroll
     for (int d = 5; d < 8; d++) y[d] = ret[d - 5];
@@ -863,10 +971,11 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
     const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
     DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
     const float *__restrict__ noise_rows, const float2 *__restrict__ table, short *__restrict__ out,
-    float *__restrict__ precast, DenoiseShard sh)
+    float *__restrict__ precast, DenoiseShard sh, int *__restrict__ redo)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
+    PhaseStat ps;
     const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware chunk order (speed only)
     const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * K;
     if (j0 >= n_blocks) return;
@@ -879,9 +988,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
 #if JDSP_DENOISE_REGSPLIT
     SplitTwiddles sw;
     load_split_twiddles(sw, table, lane);
-#define JDSP_DN_FRAME(RAW, NOISE, Y) denoise_frame_reg<MODE>(RAW, t, sw, lds, lane, NOISE, Y)
+#define JDSP_DN_FRAME(RAW, NOISE, Y) denoise_frame_reg<MODE>(RAW, t, sw, lds, lane, NOISE, Y, ps)
 #else
-#define JDSP_DN_FRAME(RAW, NOISE, Y) denoise_frame<MODE>(RAW, t, lds, lane, NOISE, Y)
+#define JDSP_DN_FRAME(RAW, NOISE, Y) denoise_frame<MODE>(RAW, t, lds, lane, NOISE, Y, ps)
 #endif
 
     const long first_emit = sh.emit_from;                     // SS:260-263: calls 1 and 2 emit nothing
@@ -914,6 +1023,8 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
             for (int d = 0; d < 8; d++) y[d] = make_float2(0.f, 0.f);
         } else {
             JDSP_DN_FRAME(raw, noise_row(noise_rows, ver_base, snap_mask, j, sh), y);
+            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
+            if (MODE == 0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
         }
         float2 o[4];
 #pragma unroll
@@ -962,10 +1073,11 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
     const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
     DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
     const float *__restrict__ noise_rows, const float2 *__restrict__ table, short *__restrict__ out,
-    float *__restrict__ precast, DenoiseShard sh, int run)
+    float *__restrict__ precast, DenoiseShard sh, int run, int *__restrict__ redo)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
+    PhaseStat ps;
     const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
     const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * run;
     if (j0 >= n_blocks) return;
@@ -978,13 +1090,13 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
     load_pair_twiddles(sw, table, lane);
     NoisePairRegs nz;
 #define JDSP_RUN_LOAD_NOISE(ROW) load_noise_pair_regs<MODE>(nz, ROW, lane)
-#define JDSP_RUN_FRAME() denoise_frame_pairs<MODE>(raw, t, sw, lds, lane, nz, y)
+#define JDSP_RUN_FRAME() denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps)
 #else
     SplitTwiddles sw;
     load_split_twiddles(sw, table, lane);
     NoiseRegs nz;
 #define JDSP_RUN_LOAD_NOISE(ROW) load_noise_regs(nz, ROW, lane)
-#define JDSP_RUN_FRAME() denoise_frame_nreg<MODE>(raw, t, sw, lds, lane, nz, y)
+#define JDSP_RUN_FRAME() denoise_frame_nreg<MODE>(raw, t, sw, lds, lane, nz, y, ps)
 #endif
 
     unsigned int raw[8], nxt[4];
@@ -1046,6 +1158,8 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
                 JDSP_RUN_LOAD_NOISE(row);
             }
             JDSP_RUN_FRAME();
+            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
+            if (MODE == 0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
         }
         float2 o[4];
 #pragma unroll
@@ -1169,17 +1283,18 @@ int launch_run_plan(hipStream_t s, const unsigned char *flags, long n_blocks, co
 template <int MODE, int K>
 static void launch_dn(hipStream_t s, const short *pcm, long n_blocks, long calls_before, const DenoiseState *st_in,
                       DenoiseState *st_out, const int *ver_base, const unsigned long long *snap_mask,
-                      const float *noise_rows, const float2 *table, short *out, float *precast, const DenoiseShard &sh)
+                      const float *noise_rows, const float2 *table, short *out, float *precast, const DenoiseShard &sh,
+                      int *redo)
 {
     long grid = ((n_blocks + K - 1) / K + 7) / 8 * 8;
     hipLaunchKernelGGL((denoise_kernel<MODE, K>), dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before,
-                       st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh);
+                       st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, redo);
 }
 
 static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
                              long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                              const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
-                             float *precast, const DenoiseShard &sh)
+                             float *precast, const DenoiseShard &sh, int *redo)
 {
     if (k_opt == 0) {
         // one round of resident waves: JDSP_DENOISE_RESIDENT per SIMD, 4 SIMDs per CU; never fewer than 4 blocks
@@ -1195,13 +1310,13 @@ static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, cons
         const long grid = (waves + 7) / 8 * 8;
         if (mode == 0)
             hipLaunchKernelGGL(denoise_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run);
+                               st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
         else
             hipLaunchKernelGGL(denoise_run_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run);
+                               st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-#define JDSP_DN(M, KK) launch_dn<M, KK>(s, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh)
+#define JDSP_DN(M, KK) launch_dn<M, KK>(s, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, redo)
     if (mode == 0) {
         switch (k_opt) {
         case 1: JDSP_DN(0, 1); break;
@@ -1347,8 +1462,16 @@ __global__ __launch_bounds__(64) void noise_accum512_kernel(const short *__restr
 template <int MODE>
 __device__ __forceinline__ void dn512_pair(const float (&xa)[8], const float (&xb)[8], const float (&win)[8],
                                            const WaveTwiddles &tw, float2 *lds, int lane,
-                                           const float *__restrict__ na, const float *__restrict__ nb, float2 (&y)[8])
+                                           const float *__restrict__ na, const float *__restrict__ nb, float2 (&y)[8],
+                                           PhaseStat &pa, PhaseStat &pb)
 {
+    float ea = 0.0f, eb = 0.0f;
+    {
+        float e = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 8; r++) e += (xa[r] * win[r]) * (xa[r] * win[r]) + (xb[r] * win[r]) * (xb[r] * win[r]);
+        pa.e = pb.e = wave_sum_f32(e);                            // the pair's: the two frames share the transform's rounding
+    }
     dn512_forward(xa, xb, win, tw, lds, lane);
     float2 yka[4], ykb[4], yma[4], ymb[4];
 #pragma unroll
@@ -1357,15 +1480,20 @@ __device__ __forceinline__ void dn512_pair(const float (&xa)[8], const float (&x
         const float2 zk = lds[k], zm = lds[512 - k];
         const float2 A = cadd_conj(zk, zm), B = csub_conj_mj(zk, zm);
         // bin k of both frames, and bin 512-k (= the conjugates) with ITS noise values
-        yka[q] = apply_gain<MODE>(A, na[k]); ykb[q] = apply_gain<MODE>(B, nb[k]);
-        yma[q] = apply_gain<MODE>(A, na[m]); ymb[q] = apply_gain<MODE>(B, nb[m]);
+        const float wm = k == 0 ? 0.0f : 1.0f;                     // bin 0 is its own mirror: counted once
+        const float rthr = real_bin_thr(pa.e, k == 0);
+        yka[q] = apply_gain<MODE>(A, na[k], ea, 1.0f, q == 0, rthr); ykb[q] = apply_gain<MODE>(B, nb[k], eb, 1.0f, q == 0, rthr);
+        yma[q] = apply_gain<MODE>(A, na[m], ea, wm); ymb[q] = apply_gain<MODE>(B, nb[m], eb, wm);
     }
     float2 a256, b256;
     {
         const float2 z = lds[256];                                // self-mirrored bin: A = 2 Re z, B = 2 Im z, both real
-        a256 = apply_gain<MODE>(make_float2(2.f * z.x, 0.f), na[256]);
-        b256 = apply_gain<MODE>(make_float2(2.f * z.y, 0.f), nb[256]);
+        const float w256 = lane == 0 ? 1.0f : 0.0f;               // every lane evaluates it; one counts it
+        a256 = apply_gain<MODE>(make_float2(2.f * z.x, 0.f), na[256], ea, w256, true, real_bin_thr(pa.e, true));
+        b256 = apply_gain<MODE>(make_float2(2.f * z.y, 0.f), nb[256], eb, w256, true, real_bin_thr(pa.e, true));
     }
+    pa.err = wave_sum_f32(ea);
+    pb.err = wave_sum_f32(eb);
     // A frame with a non-finite bin (Wiener's 0/0 on an all-zero frame before any estimate, WF:204) has an all-NaN
     // inverse transform in the reference.  Here it must not poison the frame it shares the transform with: its
     // spectrum goes in as zero and its samples come out as NaN.
@@ -1415,7 +1543,7 @@ __global__ __launch_bounds__(64, 3) void denoise512_kernel(
     const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
     DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
     const float *__restrict__ noise_rows, const float2 *__restrict__ table, const float *__restrict__ win512,
-    short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh)
+    short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh, int *__restrict__ redo)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
@@ -1445,10 +1573,20 @@ __global__ __launch_bounds__(64, 3) void denoise512_kernel(
 #pragma unroll
         for (int r = 0; r < 8; r++) { xa[r] = xs[8 * p + r]; xb[r] = xs[8 * p + 4 + r]; }
         float2 y[8];
+        PhaseStat pa, pb;
         dn512_pair<MODE>(xa, xb, win, tw, lds, lane, noise_row(noise_rows, ver_base, snap_mask, ja >= 0 ? ja : 0, sh),
-                         noise_row(noise_rows, ver_base, snap_mask, jb < n_blocks ? jb : n_blocks - 1, sh), y);
+                         noise_row(noise_rows, ver_base, snap_mask, jb < n_blocks ? jb : n_blocks - 1, sh), y, pa, pb);
         // the very first call of a stream only stashes its block (SS:211-216): no transform, empty overlap
         const bool a_void = calls_before + ja <= 0, b_void = calls_before + jb <= 0;
+        {
+            // frames FP32 cannot hold (phase_unsafe; the halo frame is its own wave's): again, in FP64.  Wiener too at
+            // this frame size: its gain has no amplifier, but a quiet frame still takes a loud partner's rounding.
+            float sa = 0.0f, sb = 0.0f;
+#pragma unroll
+            for (int d = 0; d < 8; d++) { sa += y[d].x * y[d].x; sb += y[d].y * y[d].y; }
+            if (p > 0 && !a_void && ja + 1 >= sh.emit_from && phase_unsafe<512>(pa.e, pa.err, sa)) phase_redo(redo, ja, lane);
+            if (jb < n_blocks && !b_void && jb + 1 >= sh.emit_from && phase_unsafe<512>(pb.e, pb.err, sb)) phase_redo(redo, jb, lane);
+        }
         float oa[4], ob[4];
         if (p == 0) {
             // frame ja = j0 - 1 is the halo: its block belongs to the previous wave (or call); only its second half counts
@@ -1523,7 +1661,7 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
     const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
     DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
     const float *__restrict__ noise_rows, const float2 *__restrict__ table, const float *__restrict__ win512,
-    short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh, int run)
+    short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh, int run, int *__restrict__ redo)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
@@ -1596,15 +1734,24 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
             v[r] = make_float2(xk[0][r] * win[r], xk[1][r] * win[r]);
             v[r + 4] = make_float2(xk[1][r] * win[r + 4], xk[2][r] * win[r + 4]);
         }
+        float e_pair = 0.0f;                                      // wave-uniform: the two frames share the transform's rounding
+        e_pair = wave_sum_f32(sumsq(v));
         wave_fft512<false>(v, lds, lane, tw);
         float2 zr[5], ya[5], yb[5], ret[4];
         wave_lds_fence();
         pair_fetch_lds(v, lds, lane, zr);
+        float ea = 0.0f, eb = 0.0f;
 #pragma unroll
         for (int d = 0; d < 5; d++) {
-            ya[d] = apply_gain_scaled<MODE, 9>(cadd_conj(v[d], zr[d]), na[d]);        // frame a, bin lane + 64 d
-            yb[d] = apply_gain_scaled<MODE, 9>(csub_conj_mj(v[d], zr[d]), nb[d]);     // frame b
+            // bin k stands for its mirror 512 - k too where that has no owner: k = 1..192
+            const float w = d < 3 ? ((d == 0 && lane == 0) ? 1.0f : 2.0f) : ((d == 3 && lane == 0) ? 2.0f : 1.0f);
+            const float rthr = real_bin_thr(e_pair, lane == 0);   // d == 0 or 4, lane 0: the bins 0 and 256
+            ya[d] = apply_gain_scaled<MODE, 9>(cadd_conj(v[d], zr[d]), na[d], ea, w, d == 0 || d == 4, rthr);        // frame a, bin lane + 64 d
+            yb[d] = apply_gain_scaled<MODE, 9>(csub_conj_mj(v[d], zr[d]), nb[d], eb, w, d == 0 || d == 4, rthr);     // frame b
         }
+        float err_a = 0.0f, err_b = 0.0f;                         // wave-uniform; the gain's 2^-18 undone
+        err_a = wave_sum_f32(ea) * 262144.0f;
+        err_b = wave_sum_f32(eb) * 262144.0f;
         // A frame with a non-finite bin (Wiener's 0/0 on an all-zero frame before any estimate, WF:204) has an all-NaN
         // inverse transform in the reference.  Here it must not poison the frame it shares the transform with: its
         // spectrum goes in as zero and its samples come out as NaN.
@@ -1631,6 +1778,15 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
         }
         // the very first call of a stream only stashes its block (SS:211-216): no transform, empty overlap
         const bool a_void = calls_before + ja <= 0, b_void = calls_before + jb <= 0;
+        {
+            // frames FP32 cannot hold (phase_unsafe; the halo frame is its own wave's): again, in FP64.  Wiener too at
+            // this frame size: its gain has no amplifier, but a quiet frame still takes a loud partner's rounding.
+            float sa = 0.0f, sb = 0.0f;
+#pragma unroll
+            for (int d = 0; d < 8; d++) { sa += y[d].x * y[d].x; sb += y[d].y * y[d].y; }
+            if (!halo && !a_void && ja + 1 >= sh.emit_from && phase_unsafe<512>(e_pair, err_a, sa)) phase_redo(redo, ja, lane);
+            if (jb < n_blocks && !b_void && jb + 1 >= sh.emit_from && phase_unsafe<512>(e_pair, err_b, sb)) phase_redo(redo, jb, lane);
+        }
         float oa[4], ob[4], tail_b[4];
         if (halo) {
             if (j0 == 0) {
@@ -1697,7 +1853,7 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
 static int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm, long n_blocks, long calls_before,
                              const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                              const unsigned long long *snap_mask, const float *noise_rows, const float2 *table,
-                             const float *win512, short *out, float *precast, const DenoiseShard &sh)
+                             const float *win512, short *out, float *precast, const DenoiseShard &sh, int *redo)
 {
 #ifndef JDSP_DENOISE512_RUN
 #define JDSP_DENOISE512_RUN 1
@@ -1712,21 +1868,175 @@ static int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm
         const long grid = (waves + 7) / 8 * 8;
         if (mode == 0)
             hipLaunchKernelGGL(denoise512_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run);
+                               st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run, redo);
         else
             hipLaunchKernelGGL(denoise512_run_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run);
+                               st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run, redo);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     const long waves = (n_blocks + kDn512BlocksPerWave - 1) / kDn512BlocksPerWave;
     const long grid = (waves + 7) / 8 * 8;
     if (mode == 0)
         hipLaunchKernelGGL(denoise512_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh);
+                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, redo);
     else
         hipLaunchKernelGGL(denoise512_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh);
+                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, redo);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---------------------------------------------------------------------------------------
+// The frames on the list {count, frames...} again, in FP64 from the samples on, as the reference computes them
+// (SS:226-256 / WF:181-228): Hamming with the reference's PI, an n_fft-point complex transform of the real frame, the
+// gain on every bin with its own noise value (Y = (|X| - N) e^{j phase(X)} written as X (1 - N / |X|); Wiener
+// X (1 - min(1, N^2 / |X|^2)), 0 / 0 staying NaN), the inverse transform, its real part, 1 / n_fft.  The transform is a
+// radix-2 in LDS: bit-reversed load, log2(n_fft) passes of n_fft / 2 butterflies over the workgroup's 256 threads,
+// twiddles from a table of exact cosines and sines -- 20 passes per frame, not n_fft^2 multiply-adds.  A listed frame f
+// adds into the blocks f and f + 1, so the workgroup computes the frames f - 1, f and f + 1 and writes both blocks
+// again, and the overlap carried out of the call if f is its last frame.  Workgroups of neighbouring listed frames write
+// the block between them twice, with the same values.
+template <int NFFT>
+__device__ __forceinline__ double redo_sample(const short *__restrict__ pcm, long n_samples,
+                                              const DenoiseState *__restrict__ st_in, long s)
+{
+    constexpr int B = NFFT / 2;
+    if (s >= 0) return s < n_samples ? (double)pcm[s] : 0.0;
+    if (s >= -B) return (double)st_in->prev[B + s];             // (every launcher passes a state)
+    return 0.0;
+}
+
+// buf (bit-reversed order in, natural order out) <- its transform; every thread of the workgroup calls it
+template <int NFFT, bool INV>
+__device__ __forceinline__ void redo_fft_lds(double2 *buf, const double2 *tw, int tid)
+{
+#pragma unroll 1
+    for (int half = 1; half < NFFT; half <<= 1) {
+        const int step = NFFT / (2 * half);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < NFFT / 512; r++) {
+            const int b = tid + 256 * r, pos = b & (half - 1), i0 = ((b - pos) << 1) + pos, i1 = i0 + half;
+            double2 w = tw[pos * step];
+            if (INV) w.y = -w.y;
+            const double2 u = buf[i0], v = buf[i1];
+            const double2 t = make_double2(v.x * w.x - v.y * w.y, v.x * w.y + v.y * w.x);
+            buf[i0] = make_double2(u.x + t.x, u.y + t.y);
+            buf[i1] = make_double2(u.x - t.x, u.y - t.y);
+        }
+    }
+    __syncthreads();
+}
+
+template <int NFFT>
+__global__ __launch_bounds__(256) void denoise_redo_f64_kernel(
+    const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
+    DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
+    const float *__restrict__ noise_rows, short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh,
+    const int *__restrict__ redo, int mode)
+{
+    constexpr int B = NFFT / 2, R = NFFT / 256, LOG = NFFT == 1024 ? 10 : 9;
+    __shared__ double2 tw[B];
+    __shared__ double2 buf[NFFT];
+    __shared__ double yy[3][NFFT];
+    const int tid = threadIdx.x;
+    const long n_redo = redo[0];
+    if ((long)blockIdx.x >= n_redo) return;                     // (the whole workgroup)
+    double win[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int i = tid + 256 * r;
+        if (i < B) {
+            double sn, cs;
+            sincospi(2.0 * (double)i / (double)NFFT, &sn, &cs);
+            tw[i] = make_double2(cs, -sn);
+        }
+        win[r] = 0.54 - 0.46 * cos(2 * 3.141592 * i / (NFFT - 1));    // SS:226
+    }
+    const long n_samples = n_blocks * B;
+    for (long it = blockIdx.x; it < n_redo; it += gridDim.x) {
+        const long f = redo[1 + it];
+        for (int q = 0; q < 3; q++) {
+            const long j = f - 1 + q;
+            // (uniform) frames outside the call add nothing here: block 0 takes the overlap carried in instead;
+            // the very first call of a stream only stashes its block (SS:211-216)
+            const bool have = j >= 0 && j < n_blocks && calls_before + j > 0;
+            __syncthreads();
+            if (!have) {
+#pragma unroll
+                for (int r = 0; r < R; r++) yy[q][tid + 256 * r] = 0.0;
+                continue;
+            }
+            const float *row = noise_row(noise_rows, ver_base, snap_mask, j, sh);
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const int i = tid + 256 * r;
+                const double v = redo_sample<NFFT>(pcm, n_samples, st_in, (j - 1) * B + i) * win[r];
+                buf[__brev((unsigned)i) >> (32 - LOG)] = make_double2(v, 0.0);
+            }
+            redo_fft_lds<NFFT, false>(buf, tw, tid);
+            double2 Y[R];
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const int k = tid + 256 * r;
+                const double2 X = buf[k];
+                const double nk = (double)row[k];
+                if (mode == 1) {                                     // WF:196-213; 0 / 0 stays NaN as in the reference
+                    double rk = nk * nk / (X.x * X.x + X.y * X.y);
+                    if (rk >= 1.0) rk = 1.0;                         // (a NaN stays one: fmin would drop it)
+                    Y[r] = make_double2(X.x * (1.0 - rk), X.y * (1.0 - rk));
+                } else {
+                    const double mag = sqrt(X.x * X.x + X.y * X.y);
+                    if (mag == 0.0) {
+                        Y[r] = make_double2(-nk, 0.0);               // phase 0 (SS:233-242)
+                    } else {
+                        const double g = 1.0 - nk / mag;
+                        Y[r] = make_double2(X.x * g, X.y * g);
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < R; r++) buf[__brev((unsigned)(tid + 256 * r)) >> (32 - LOG)] = Y[r];
+            redo_fft_lds<NFFT, true>(buf, tw, tid);
+#pragma unroll
+            for (int r = 0; r < R; r++) yy[q][tid + 256 * r] = buf[tid + 256 * r].x * (1.0 / NFFT);     // SS:248
+        }
+        __syncthreads();
+        for (int q = 0; q < 2; q++) {
+            const long b = f + q;
+            if (b >= n_blocks) break;
+#pragma unroll
+            for (int r = 0; r < R / 2; r++) {
+                const int i = tid + 256 * r;
+                const double t = b == 0 ? (double)st_in->tail[i] : yy[q][B + i];        // rgsdOveraped carried over
+                const float o = (float)(t + yy[q + 1][i]);                              // SS:248 overlap-add
+                if (b >= sh.emit_from && b < sh.emit_to) {
+                    const long oi = b - sh.emit_from;
+                    out[oi * B + i] = (short)cast_i16_bits(o);
+                    if (precast) precast[oi * B + i] = o;
+                }
+            }
+        }
+        if (f == n_blocks - 1) {
+#pragma unroll
+            for (int r = 0; r < R / 2; r++) st_out->tail[tid + 256 * r] = (float)yy[1][B + tid + 256 * r];   // SS:255-256
+        }
+    }
+}
+
+constexpr int kRedoGrid = 1024;
+static void launch_denoise_redo(hipStream_t s, int n_fft, const short *pcm, long n_blocks, long calls_before,
+                                const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
+                                const unsigned long long *snap_mask, const float *noise_rows, short *out, float *precast,
+                                const DenoiseShard &sh, const int *redo, int mode)
+{
+    const dim3 grid((unsigned)(n_blocks < kRedoGrid ? n_blocks : kRedoGrid));
+    if (n_fft == 512)
+        hipLaunchKernelGGL(denoise_redo_f64_kernel<512>, grid, dim3(256), 0, s, pcm, n_blocks, calls_before, st_in, st_out,
+                           ver_base, snap_mask, noise_rows, out, precast, sh, redo, mode);
+    else
+        hipLaunchKernelGGL(denoise_redo_f64_kernel<1024>, grid, dim3(256), 0, s, pcm, n_blocks, calls_before, st_in, st_out,
+                           ver_base, snap_mask, noise_rows, out, precast, sh, redo, mode);
 }
 
 // ---- launchers of both frame sizes --------------------------------------------------------------
@@ -1735,9 +2045,14 @@ static int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm
 int launch_denoise(hipStream_t s, DenoiseGeom g, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
                    long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                    const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
-                   float *precast, const DenoiseShard *shard)
+                   float *precast, int *redo, const DenoiseShard *shard)
 {
+    // redo: [n_blocks + 1] ints, {count, frames...}: the spectral-subtraction frames FP32 could not hold (phase_unsafe),
+    // left there by whichever kernel runs and computed again by denoise_redo_f64_kernel; the count stays for
+    // jdsp_denoise_frames_recomputed.  1024-point Wiener lists nothing: no memset, no FP64 launch, the count is not read.
     if (n_blocks <= 0) return 0;
+    const bool lists = mode == 0 || g.n_fft == 512;
+    if (lists && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
     DenoiseShard sh;
     if (shard) sh = *shard;
     else {
@@ -1746,11 +2061,15 @@ int launch_denoise(hipStream_t s, DenoiseGeom g, int mode, int k_opt, int n_cu, 
         sh.emit_from = calls_before >= 2 ? 0 : 2 - calls_before;
         sh.emit_to = n_blocks;
     }
-    if (g.n_fft == 512)
-        return launch_denoise512(s, mode, n_cu, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows,
-                                 table, g.win512, out, precast, sh);
-    return launch_denoise1024(s, mode, k_opt, n_cu, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask,
-                              noise_rows, table, out, precast, sh);
+    const int rc = g.n_fft == 512
+        ? launch_denoise512(s, mode, n_cu, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows,
+                            table, g.win512, out, precast, sh, redo)
+        : launch_denoise1024(s, mode, k_opt, n_cu, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask,
+                             noise_rows, table, out, precast, sh, redo);
+    if (rc || !lists) return rc;
+    launch_denoise_redo(s, g.n_fft, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows, out, precast,
+                        sh, redo, mode);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // range / ext0: a shard's event range and the global index of its first block (NULL / 0 when not sharded)

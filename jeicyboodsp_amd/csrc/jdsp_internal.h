@@ -331,7 +331,7 @@ int launch_noise_estimate(hipStream_t s, DenoiseGeom g, const short *pcm, long n
 int launch_denoise(hipStream_t s, DenoiseGeom g, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
                    long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                    const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
-                   float *precast, const DenoiseShard *shard = nullptr);
+                   float *precast, int *redo, const DenoiseShard *shard = nullptr);
 int launch_shard_summary(hipStream_t s, DenoiseGeom g, const short *pcm_ext, long n_ext, long ext0, long b0, long b1,
                          const int *events, const int *ev_n, const DenoisePlan *plan, const int *ver_base,
                          const unsigned long long *snap_mask, const float2 *table, int *range, const NoiseAccum &acc,
@@ -583,8 +583,10 @@ struct jdsp_denoise {
         // jdsp::NoiseAccum's arrays
         jdsp::DevBuf<float> chunk_alpha, chunk_beta, a_start, lat_alpha;
         jdsp::DevBuf<int> lat_chunk;
+        jdsp::DevBuf<int> redo;           // [n + 1] {count, frames...}: spectral-subtraction frames computed again in FP64
     } ws;
     long last_blocks = 0;
+    int redo_valid = 0;                   // ws.redo[0] is the last call's count (jdsp_denoise_frames_recomputed)
     int opt_k = 0;
     int opt_vad_trace = 0;                // 1: keep every block's energy sum and ZCR for jdsp_denoise_vad_trace (slower VAD kernel)
     int last_trace_valid = 0;             // the option's value when the last call ran: what jdsp_denoise_vad_trace may hand out

@@ -452,6 +452,13 @@ class Denoiser(_Child):
         self.eng._ck(L.jdsp_denoise_noise(self._h, n.ctypes.data_as(C.c_void_p)))
         return n
 
+    def frames_recomputed(self):
+        """Spectral-subtraction frames of the last call that went through the FP64 pass (jdsp_denoise_frames_recomputed)."""
+        n = L.jdsp_denoise_frames_recomputed(self._h)
+        if n < 0:
+            self.eng._ck(int(n))
+        return int(n)
+
     def vad_trace(self, n, flags_only=False):
         """(voice, energy sums, ZCR) of the last call's first n blocks; energies / ZCR need set_option("vad_trace", 1)
         before that call (flags_only=True asks for the flags alone, which are always kept)."""
