@@ -105,19 +105,9 @@ __global__ __launch_bounds__(64) void vad_kernel(const short *__restrict__ pcm, 
 //     the scalar unit counts its bits (s_bcnt1), beside the vector pipe;
 //   * a lane's energy is clamped to 2^20 per four samples before the wave sum: the sum then fits 32 bits, and it
 //     exceeds 700 * n exactly when the true sum does (a clamped lane alone is already above the threshold);
-//   * the one 32-bit wave sum is five DPP adds (quad swaps, row mirrors, row broadcasts) and a v_readlane.
+//   * the one 32-bit wave sum is five DPP adds (quad swaps, row mirrors, row broadcasts) and a v_readlane
+//     (wave_sum_u32, frame_io.h).
 // Flags are bit-identical to the traced kernel's (tests/test_denoise_gpu.py checks both against the CPU restatement).
-__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v)
-{
-    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
-    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
-    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true);    // row_half_mirror: sums of 8
-    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true);    // row_mirror: sums of 16
-    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);    // row_bcast15 into rows 1 and 3
-    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);    // row_bcast31 into rows 2 and 3
-    return (unsigned int)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 template <int SPL>
 __global__ __launch_bounds__(64) void vad_flags_kernel(const short *__restrict__ pcm, long n_blocks,
                                                        const double *__restrict__ w_hi, int use_zcr,
@@ -350,20 +340,6 @@ __device__ __forceinline__ void load_block_pairs(const short *__restrict__ pcm, 
     for (int r = 0; r < 4; r++) q[r] = src ? src[lane + 64 * r] : 0u;
 }
 
-// window -> forward transform -> natural-order image of Zh in LDS
-__device__ __forceinline__ void forward_to_lds(const unsigned int *raw, const FrameTables &t, float2 *lds, int lane)
-{
-    float2 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const float2 s = unpack_i16x2(raw[r]);
-        v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
-    }
-    wave_fft512<false>(v, lds, lane, t.tw);
-    store_natural_image(lds, lane, v);
-    wave_lds_fence();
-}
-
 // ---------------------------------------------------------------------------------------
 // A12 (SS:165-193), the noise average: at every EstimateNoiseSpectrum event  A += |X|;  from run length 3 on  A /= 2;  at
 // run length 10 the average is latched as the estimate.  Over the events of a call that is a chain of affine maps
@@ -390,9 +366,6 @@ __device__ __forceinline__ ChunkGeom chunk_geom(int n_events, int grid)
     return g;
 }
 
-#ifndef JDSP_ACCUM_PAIRS
-#define JDSP_ACCUM_PAIRS 1
-#endif
 __global__ __launch_bounds__(64) void noise_accum_kernel(const short *__restrict__ pcm, long n_blocks,
                                                          const DenoiseState *__restrict__ st_in,
                                                          const int *__restrict__ events, const int *__restrict__ ev_n,
@@ -416,7 +389,6 @@ __global__ __launch_bounds__(64) void noise_accum_kernel(const short *__restrict
     const int e1 = e0 + cg.per_chunk < n_events ? e0 + cg.per_chunk : n_events;
     FrameTables t;
     load_frame_tables(t, table, lane);
-#if JDSP_ACCUM_PAIRS
     // Pair-owned bins (frame_io.h): |X| of the bins m, m + 512 of m = lane + 64 d, d < 5; the bins 1024 - m and 512 - m
     // are their mirrors (a real frame), so ten magnitudes per lane and event instead of sixteen.  A row is stored as the
     // ten own values plus the mirrors of m = 1..192 (the items of d = 3, 4 mirror each other: those bins are stored by
@@ -424,22 +396,15 @@ __global__ __launch_bounds__(64) void noise_accum_kernel(const short *__restrict
     PairTwiddles pw;
     load_pair_twiddles(pw, table, lane);
     constexpr int ND = 5;
-#else
-    SplitTwiddles sw;
-    load_split_twiddles(sw, table, lane);
-    constexpr int ND = 8;
-#endif
     float blo[ND], bhi[ND], alpha = 1.0f;                        // beta[lane + 64 d], beta[lane + 64 d + 512]
     auto store_row = [&](float *row) {
 #pragma unroll
         for (int d = 0; d < ND; d++) { row[lane + 64 * d] = blo[d]; row[lane + 64 * d + 512] = bhi[d]; }
-#if JDSP_ACCUM_PAIRS
 #pragma unroll
         for (int d = 0; d < 4; d++) {
             const int m = lane + 64 * d;
             if (m >= 1 && m <= 192) { row[1024 - m] = blo[d]; row[512 - m] = bhi[d]; }
         }
-#endif
     };
 #pragma unroll
     for (int d = 0; d < ND; d++) blo[d] = bhi[d] = 0.0f;
@@ -458,7 +423,6 @@ __global__ __launch_bounds__(64) void noise_accum_kernel(const short *__restrict
         }
         wave_fft512<false>(v, lds, lane, t.tw);
         wave_lds_fence();
-#if JDSP_ACCUM_PAIRS
         pair_fetch_lds(v, lds, lane, zr);
 #pragma unroll
         for (int d = 0; d < ND; d++) {
@@ -467,10 +431,6 @@ __global__ __launch_bounds__(64) void noise_accum_kernel(const short *__restrict
             lo[d] = cadd(ev, tw);
             hi[d] = csub(ev, tw);
         }
-#else
-        mirror_fetch_lds(v, lds, lane, zr);
-        split_fwd_reg(v, zr, sw, lo, hi);
-#endif
         const float h = n >= 3 ? 0.5f : 1.0f;                    // SS:182-187
 #pragma unroll
         for (int d = 0; d < ND; d++) {
@@ -583,9 +543,6 @@ __global__ __launch_bounds__(1024) void noise_combine_kernel(const DenoisePlan *
 // ---------------------------------------------------------------------------------------
 // A8 (SS:233-242): Y = (|X| - N) e^{j phase(X)}; no clamp at zero; X == 0 -> phase 0 -> (-N, 0).
 // A9 (WF:196-213): Y = |X| (1 - min(1, N^2/|X|^2)) e^{j phase(X)}; 0/0 stays NaN as in the reference.
-#ifndef JDSP_GAIN_SELECT
-#define JDSP_GAIN_SELECT 1
-#endif
 //
 // Which spectral-subtraction frames FP32 cannot hold.  In a bin far below its noise value the output is -N e^{j phase(X)}:
 // its size is N however small X is, and its direction is the phase of X -- which a FP32 transform leaves arbitrary once
@@ -615,16 +572,6 @@ __device__ __forceinline__ constexpr float phase_k() { return 4.0f * 1.421085471
 // a real bin counts when |X|^2 < (16 eps)^2 = kRealBinK e: a lane's threshold for the bins that may be real
 constexpr float kRealBinK = 256.0f * 4.0f * 1.4210854715202004e-14f;
 __device__ __forceinline__ float real_bin_thr(float e, bool real) { return real ? kRealBinK * e : __builtin_inff(); }
-
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-    // as wave_sum_u32: five DPP adds and a v_readlane; the result is wave-uniform
-#define JDSP_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, true))
-    JDSP_DPP_ADD(0xB1, 0xf); JDSP_DPP_ADD(0x4E, 0xf); JDSP_DPP_ADD(0x141, 0xf); JDSP_DPP_ADD(0x140, 0xf);
-    JDSP_DPP_ADD(0x142, 0xa); JDSP_DPP_ADD(0x143, 0xc);
-#undef JDSP_DPP_ADD
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
 
 // the frame's verdict; ysq = this lane's share of sum y^2 over the frame's samples
 template <int NFFT>
@@ -670,70 +617,9 @@ __device__ __forceinline__ float2 apply_gain(float2 x, float n, float &err, floa
     }
 }
 
-template <int MODE, int J>
-__device__ __forceinline__ void gain_presplit_j(const float2 *lds, float2 *zout, int lane, const float2 *wsp,
-                                                const float *__restrict__ noise, float &err, float e)
-{
-    const int m = 128 * J + 2 * lane;
-    const float4 zz = *reinterpret_cast<const float4 *>(&lds[m]);
-    float2 zr0, zr1;
-    load_mirror_pair(lds, m, zr0, zr1);
-    const float2 nlo = *reinterpret_cast<const float2 *>(noise + m);
-    const float2 nhi = *reinterpret_cast<const float2 *>(noise + m + 512);
-    float2 lo0, hi0, lo1, hi1;
-    split_fwd<J>(make_float2(zz.x, zz.y), zr0, wsp[0], lo0, hi0);
-    split_fwd<J>(make_float2(zz.z, zz.w), zr1, wsp[1], lo1, hi1);
-    const float rthr = real_bin_thr(e, lane == 0);              // J == 0, lane 0: lo0 and hi0 are the bins 0 and 512
-    lo0 = apply_gain<MODE>(lo0, nlo.x, err, 1.0f, J == 0, rthr); hi0 = apply_gain<MODE>(hi0, nhi.x, err, 1.0f, J == 0, rthr);
-    lo1 = apply_gain<MODE>(lo1, nlo.y, err, 1.0f); hi1 = apply_gain<MODE>(hi1, nhi.y, err, 1.0f);
-    zout[2 * J] = presplit_inv<J>(lo0, hi0, wsp[0]);
-    zout[2 * J + 1] = presplit_inv<J>(lo1, hi1, wsp[1]);
-}
-
-// One frame: samples -> y = IDFT(gain(DFT(window * frame))) / 1024, returned in the
-// transform layout: y[d] = (y[2 lane + 128 d], y[2 lane + 128 d + 1]).
-template <int MODE>
-__device__ __forceinline__ void denoise_frame(const unsigned int *raw, const FrameTables &t, float2 *lds, int lane,
-                                              const float *__restrict__ noise, float2 (&y)[8], PhaseStat &ps)
-{
-    if (MODE == 0) {
-        float e = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const float2 sv = unpack_i16x2(raw[r]);
-            e += (sv.x * t.win[r].x) * (sv.x * t.win[r].x) + (sv.y * t.win[r].y) * (sv.y * t.win[r].y);
-        }
-        ps.e = wave_sum_f32(e);
-    }
-    forward_to_lds(raw, t, lds, lane);
-    float2 z[8];
-    float err = 0.0f;
-    gain_presplit_j<MODE, 0>(lds, z, lane, t.wsp, noise, err, ps.e);
-    gain_presplit_j<MODE, 1>(lds, z, lane, t.wsp, noise, err, ps.e);
-    gain_presplit_j<MODE, 2>(lds, z, lane, t.wsp, noise, err, ps.e);
-    gain_presplit_j<MODE, 3>(lds, z, lane, t.wsp, noise, err, ps.e);
-    if (MODE == 0) ps.err = wave_sum_f32(err);
-    wave_lds_fence();
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        *reinterpret_cast<float4 *>(&lds[128 * j + 2 * lane]) = make_float4(z[2 * j].x, z[2 * j].y, z[2 * j + 1].x, z[2 * j + 1].y);
-    wave_lds_fence();
-#pragma unroll
-    for (int r = 0; r < 8; r++) y[r] = lds[lane + 64 * r];
-    wave_lds_fence();
-    wave_fft512<true>(y, lds, lane, t.tw);
-    // the reference's 1/N after FFTW's unnormalised inverse (SS:248); a power of two, exact
-#pragma unroll
-    for (int d = 0; d < 8; d++) y[d] = make_float2(y[d].x * (1.0f / 1024.0f), y[d].y * (1.0f / 1024.0f));
-    wave_lds_fence();
-}
-
-#ifndef JDSP_DENOISE_REGSPLIT
-#define JDSP_DENOISE_REGSPLIT 1       // 1: split / pre-split in registers (mirror operands by ds_bpermute); 0: LDS images
-#endif
-#if JDSP_DENOISE_REGSPLIT
-// The same frame with the bins kept in "lane + 64 d" registers from the forward transform to the inverse one:
-// no natural-order image, no Z' image, three fences fewer (frame_io.h).  noise[m] is read at m = lane + 64 d.
+// One frame: samples -> y = IDFT(gain(DFT(window * frame))) / 1024, returned in the transform layout: y[d] =
+// (y[2 lane + 128 d], y[2 lane + 128 d + 1]).  The bins stay in "lane + 64 d" registers from the forward transform to
+// the inverse one: no natural-order image, no Z' image (frame_io.h).  noise[m] is read at m = lane + 64 d.
 template <int MODE>
 __device__ __forceinline__ void denoise_frame_reg(const unsigned int *raw, const FrameTables &t, const SplitTwiddles &sw,
                                                   float2 *lds, int lane, const float *__restrict__ noise, float2 (&y)[8],
@@ -767,62 +653,6 @@ __device__ __forceinline__ void denoise_frame_reg(const unsigned int *raw, const
     for (int d = 0; d < 8; d++) y[d] = make_float2(y[d].x * (1.0f / 1024.0f), y[d].y * (1.0f / 1024.0f));
     wave_lds_fence();
 }
-#endif
-
-// The noise row of a frame held in registers: nlo[d] = N[lane + 64 d], nhi[d] = N[lane + 64 d + 512].  An estimate
-// changes at most every tenth block (SS:189) and usually far less often, so a wave walking a run of blocks reloads these
-// sixteen values only when the row pointer changes instead of fetching 4 KB per frame through L2.
-struct NoiseRegs { float lo[8], hi[8]; };
-__device__ __forceinline__ void load_noise_regs(NoiseRegs &n, const float *__restrict__ row, int lane)
-{
-#pragma unroll
-    for (int d = 0; d < 8; d++) { n.lo[d] = row[lane + 64 * d]; n.hi[d] = row[lane + 64 * d + 512]; }
-}
-
-#ifndef JDSP_DENOISE_MIRROR_LDS
-#define JDSP_DENOISE_MIRROR_LDS 1     // 1: mirror operands through a natural-order LDS image; 0: by ds_bpermute
-#endif
-template <int MODE>
-__device__ __forceinline__ void denoise_frame_nreg(const unsigned int *raw, const FrameTables &t, const SplitTwiddles &sw,
-                                                   float2 *lds, int lane, const NoiseRegs &n, float2 (&y)[8], PhaseStat &ps)
-{
-    float2 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const float2 s = unpack_i16x2(raw[r]);
-        v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
-    }
-    if (MODE == 0) ps.e = wave_sum_f32(sumsq(v));
-    float err = 0.0f;
-    wave_fft512<false>(v, lds, lane, t.tw);
-    float2 zr[8], lo[8], hi[8];
-#if JDSP_DENOISE_MIRROR_LDS
-    wave_lds_fence();                                            // the transform's last exchange reads are done
-    mirror_fetch_lds(v, lds, lane, zr);
-#else
-    mirror_fetch(v, lane, zr);
-#endif
-    split_fwd_reg(v, zr, sw, lo, hi);
-    // (Tried: skipping the two X == 0 selects per bin of spectral subtraction unless a wave-wide test finds a zero
-    // bin -- a second copy of the gain loop behind a uniform branch.  134.6 us against 120.1 us per 65,536 blocks:
-    // the doubled loop body costs far more than the 32 selects it saves.  profiles/r02_denoise_ab.txt.)
-    {
-#pragma unroll
-        for (int d = 0; d < 8; d++) {
-            const float rthr = real_bin_thr(ps.e, lane == 0);   // d == 0, lane 0: the bins 0 and 512
-            lo[d] = apply_gain<MODE>(lo[d], n.lo[d], err, 1.0f, d == 0, rthr);
-            hi[d] = apply_gain<MODE>(hi[d], n.hi[d], err, 1.0f, d == 0, rthr);
-            y[d] = presplit_inv_reg(lo[d], hi[d], sw.w[d]);
-        }
-    }
-    if (MODE == 0) ps.err = wave_sum_f32(err);
-    wave_lds_fence();                                            // the forward transform's last exchange reads are done
-    wave_fft512<true>(y, lds, lane, t.tw);
-    // the reference's 1/N after FFTW's unnormalised inverse (SS:248); a power of two, exact
-#pragma unroll
-    for (int d = 0; d < 8; d++) y[d] = make_float2(y[d].x * (1.0f / 1024.0f), y[d].y * (1.0f / 1024.0f));
-    wave_lds_fence();
-}
 
 // The frame with every mirror pair of bins owned by one lane (frame_io.h, PairTwiddles): five items per lane, the gain
 // evaluated on the 640 bins m, m + 512 (m = lane + 64 d, d < 5) and the rest of the inverse transform's input taken
@@ -830,12 +660,6 @@ __device__ __forceinline__ void denoise_frame_nreg(const unsigned int *raw, cons
 // estimate (|X[k]| and |X[1024 - k]| of a real frame, 1e-7 apart in FP32; the reference's own FFTW spectrum is
 // symmetric to 1e-16).  The reference's 1/1024 after the inverse transform (SS:248, a power of two: exact wherever it
 // is applied) is folded into the gain, so the noise values arrive pre-multiplied by it.
-#ifndef JDSP_DENOISE_PAIRS
-#define JDSP_DENOISE_PAIRS 1
-#endif
-#ifndef JDSP_DENOISE_ABLATE
-#define JDSP_DENOISE_ABLATE 0       // timing-only ablations of denoise_frame_pairs (tools/build_variant.sh): wrong results
-#endif
 struct NoisePairRegs { float lo[5], hi[5]; };
 template <int MODE>
 __device__ __forceinline__ void load_noise_pair_regs(NoisePairRegs &n, const float *__restrict__ row, int lane)
@@ -900,26 +724,17 @@ __device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, con
     wave_fft512<false>(v, lds, lane, t.tw);
     float2 zr[5], ret[4];
     wave_lds_fence();                                            // the transform's last exchange reads are done
-#if JDSP_DENOISE_ABLATE & 2                                           /* timing-only: no mirror fetch / return */
-#pragma unroll
-    for (int d = 0; d < 5; d++) zr[d] = v[7 - d];
-#else
     pair_fetch_lds(v, lds, lane, zr);
-#endif
 #pragma unroll
     for (int d = 0; d < 5; d++) {
         const float2 e = cadd_conj(v[d], zr[d]);
         const float2 o = csub_conj_mj(v[d], zr[d]);
         const float2 p = cmul(pw.w[d], o);
-#if JDSP_DENOISE_ABLATE & 1                                           /* timing-only: no gain */
-        const float2 lo = cadd(e, p), hi = csub(e, p);
-#else
         // bins m and m + 512 stand for their mirrors 1024 - m and 512 - m too where those have no owner: m = 1..192
         const float w = d < 3 ? ((d == 0 && lane == 0) ? 1.0f : 2.0f) : ((d == 3 && lane == 0) ? 2.0f : 1.0f);
         const float rthr = real_bin_thr(ps.e, lane == 0);       // d == 0, lane 0: the bins 0 and 512
         const float2 lo = apply_gain_scaled<MODE>(cadd(e, p), n.lo[d], err, w, d == 0, rthr);      // Y[m] / 1024
         const float2 hi = apply_gain_scaled<MODE>(csub(e, p), n.hi[d], err, w, d == 0, rthr);      // Y[m + 512] / 1024
-#endif
         if (d < 4) {
             presplit_inv_pair(lo, hi, pw.w[d], y[d], ret[d]);
         } else {
@@ -927,15 +742,8 @@ __device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, con
         }
     }
     if (MODE == 0) ps.err = wave_sum_f32(err) * 1048576.0f;            // the gain's 2^-20 undone
-#if JDSP_DENOISE_ABLATE & 2
-#pragma unroll
-    for (int d = 5; d < 8; d++) y[d] = ret[d - 5];
-#else
     pair_return_lds(ret, lds, lane, y);
-#endif
-#if !(JDSP_DENOISE_ABLATE & 4)                                        /* 4, timing-only: no inverse transform */
     wave_fft512<true>(y, lds, lane, t.tw);
-#endif
     wave_lds_fence();
 }
 
@@ -985,13 +793,8 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
     for (int h = 0; h < K + 2; h++) load_block_pairs(pcm, n_blocks, st_in, j0 - 2 + h, lane, half[h]);
     FrameTables t;
     load_frame_tables(t, table, lane);
-#if JDSP_DENOISE_REGSPLIT
     SplitTwiddles sw;
     load_split_twiddles(sw, table, lane);
-#define JDSP_DN_FRAME(RAW, NOISE, Y) denoise_frame_reg<MODE>(RAW, t, sw, lds, lane, NOISE, Y, ps)
-#else
-#define JDSP_DN_FRAME(RAW, NOISE, Y) denoise_frame<MODE>(RAW, t, lds, lane, NOISE, Y, ps)
-#endif
 
     const long first_emit = sh.emit_from;                     // SS:260-263: calls 1 and 2 emit nothing
     unsigned int raw[8];
@@ -1007,7 +810,7 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
 #pragma unroll
         for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
     } else {
-        JDSP_DN_FRAME(raw, noise_row(noise_rows, ver_base, snap_mask, j0 - 1, sh), y);   // halo frame
+        denoise_frame_reg<MODE>(raw, t, sw, lds, lane, noise_row(noise_rows, ver_base, snap_mask, j0 - 1, sh), y, ps);   // halo frame
 #pragma unroll
         for (int d = 0; d < 4; d++) tail[d] = y[d + 4];
     }
@@ -1022,7 +825,7 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
 #pragma unroll
             for (int d = 0; d < 8; d++) y[d] = make_float2(0.f, 0.f);
         } else {
-            JDSP_DN_FRAME(raw, noise_row(noise_rows, ver_base, snap_mask, j, sh), y);
+            denoise_frame_reg<MODE>(raw, t, sw, lds, lane, noise_row(noise_rows, ver_base, snap_mask, j, sh), y, ps);
             // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
             if (MODE == 0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
         }
@@ -1054,19 +857,13 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
 
 // The same work as denoise_kernel<MODE, K> with the run length chosen at launch instead of at compile time: one wave
 // walks `run` consecutive blocks (one recomputed halo frame in front), and the launch picks `run` so that the whole
-// batch is ONE round of resident waves (3 per SIMD at this register budget).  With K = 8 a 65,536-block batch is
+// batch is ONE round of resident waves (three per SIMD when this was measured).  With K = 8 a 65,536-block batch is
 // 8,192 waves = 2.67 rounds of the 3,072 resident ones, i.e. 3 rounds of 9 frames = 27 frame times per wave slot for
 // 24 of work; with run = 22 it is 2,979 waves, one round, 23 frame times -- and the halo overhead falls from 1/8 to
 // 1/22.  A wave needs the next block's samples only one iteration later, so they are loaded at the top of the
 // iteration that precedes their use (4 dwords per lane) instead of all K + 2 blocks up front (40 VGPRs at K = 8).
 #ifndef JDSP_DENOISE_RESIDENT
-#define JDSP_DENOISE_RESIDENT (JDSP_DENOISE_PAIRS ? 4 : 3)      // waves per SIMD the run kernel's register budget allows
-#endif
-#ifndef JDSP_DENOISE_TAKE_EARLY
-#define JDSP_DENOISE_TAKE_EARLY 1                                // 1: the prefetched block is taken before this block's stores, not after them
-#endif
-#ifndef JDSP_DENOISE_PRIO
-#define JDSP_DENOISE_PRIO 1                                      // 1: the run kernels' waves rotate through the priority levels
+#define JDSP_DENOISE_RESIDENT 4      // waves per SIMD the run kernel's register budget allows
 #endif
 template <int MODE>
 __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
@@ -1085,19 +882,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
 
     FrameTables t;
     load_frame_tables(t, table, lane);
-#if JDSP_DENOISE_PAIRS
     PairTwiddles sw;
     load_pair_twiddles(sw, table, lane);
     NoisePairRegs nz;
-#define JDSP_RUN_LOAD_NOISE(ROW) load_noise_pair_regs<MODE>(nz, ROW, lane)
-#define JDSP_RUN_FRAME() denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps)
-#else
-    SplitTwiddles sw;
-    load_split_twiddles(sw, table, lane);
-    NoiseRegs nz;
-#define JDSP_RUN_LOAD_NOISE(ROW) load_noise_regs(nz, ROW, lane)
-#define JDSP_RUN_FRAME() denoise_frame_nreg<MODE>(raw, t, sw, lds, lane, nz, y, ps)
-#endif
 
     unsigned int raw[8], nxt[4];
     float2 tail[4], y[8];
@@ -1120,8 +907,8 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
         for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
     } else {
         cur_row = noise_row_at(noise_rows, ver_base, snap_mask, j0 - 1, sh.ver_block_off, row_off);
-        JDSP_RUN_LOAD_NOISE(cur_row);
-        JDSP_RUN_FRAME();                                          // halo frame
+        load_noise_pair_regs<MODE>(nz, cur_row, lane);
+        denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);   // halo frame
 #pragma unroll
         for (int d = 0; d < 4; d++) tail[d] = y[d + 4];
     }
@@ -1136,14 +923,12 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
 #pragma unroll
     for (int r = 0; r < 4; r++) tk[r] = nxt[r];
     for (long j = j0; j < j1; j++) {
-#if JDSP_DENOISE_PRIO
         switch (prio_step++ & 3u) {
         case 0: __builtin_amdgcn_s_setprio(0); break;
         case 1: __builtin_amdgcn_s_setprio(1); break;
         case 2: __builtin_amdgcn_s_setprio(2); break;
         default: __builtin_amdgcn_s_setprio(3); break;
         }
-#endif
         unsigned int cur[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) { cur[r] = tk[r]; raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
@@ -1155,9 +940,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
             const float *row = noise_row_at(noise_rows, ver_base, snap_mask, j, sh.ver_block_off, row_off);
             if (row != cur_row) {                                // wave-uniform: a new estimate was latched
                 cur_row = row;
-                JDSP_RUN_LOAD_NOISE(row);
+                load_noise_pair_regs<MODE>(nz, row, lane);
             }
-            JDSP_RUN_FRAME();
+            denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);
             // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
             if (MODE == 0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
         }
@@ -1167,11 +952,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
             o[d] = make_float2(tail[d].x + y[d].x, tail[d].y + y[d].y);      // SS:248 overlap-add
             tail[d] = y[d + 4];                                               // SS:255-256
         }
-#if JDSP_DENOISE_TAKE_EARLY
 #pragma unroll
         for (int r = 0; r < 4; r++) { tk[r] = nxt[r]; asm volatile("" : "+v"(tk[r])); }
         __builtin_amdgcn_sched_barrier(0);
-#endif
         if (j >= first_emit && j < sh.emit_to) {
             const long oi = j - first_emit;
             unsigned int *dst = reinterpret_cast<unsigned int *>(out + oi * 512) + lane;
@@ -1189,15 +972,8 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
 #pragma unroll
             for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(&st_out->tail[2 * lane + 128 * d]) = tail[d];
         }
-#if !JDSP_DENOISE_TAKE_EARLY
-#pragma unroll
-        for (int r = 0; r < 4; r++) tk[r] = nxt[r];
-#endif
     }
 }
-
-#undef JDSP_RUN_LOAD_NOISE
-#undef JDSP_RUN_FRAME
 
 // ---------------------------------------------------------------------------------------
 // Multi-GPU sharding of the noise estimate.  Rank r owns blocks [b0, b1) of the
@@ -1303,9 +1079,6 @@ static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, cons
         long waves = (n_blocks + 3) / 4;
         if (waves > slots) waves = slots;
         long run = (n_blocks + waves - 1) / waves;
-#ifdef JDSP_DENOISE_RUN_BLOCKS
-        run = JDSP_DENOISE_RUN_BLOCKS;                             // tools/build_variant.sh: run-length sweeps only
-#endif
         waves = (n_blocks + run - 1) / run;
         const long grid = (waves + 7) / 8 * 8;
         if (mode == 0)
@@ -1350,10 +1123,8 @@ static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, cons
 // time signals (both spectra are Hermitian).  Overlap-add with hop 256 pairs "lane + 64 d" registers exactly as
 // the 1024-point kernel does with hop 512: y[d], d < 4, is the first half of a frame, y[d + 4] its second half.
 //
-// One wave owns 2 kDn512Pairs - 1 consecutive blocks: pairs (j0-1, j0), (j0+1, j0+2), ...; the first frame of the
-// first pair is the halo that rebuilds the overlap tail (its output block belongs to the previous wave).
-constexpr int kDn512Pairs = 4;
-constexpr int kDn512BlocksPerWave = 2 * kDn512Pairs - 1;
+// One wave owns an odd run of consecutive blocks: pairs (j0-1, j0), (j0+1, j0+2), ...; the first frame of the first pair
+// is the halo that rebuilds the overlap tail (its output block belongs to the previous wave).
 
 // Sample s of this call's stream; s in [-256, 0) is the previous call's last block (state), anything else
 // outside the call is silence.  s = base + lane + 64 t with base a multiple of 256: every branch is wave-uniform.
@@ -1459,192 +1230,14 @@ __global__ __launch_bounds__(64) void noise_accum512_kernel(const short *__restr
     if (lane == 0) acc.chunk_alpha[chunk] = alpha;
 }
 
-template <int MODE>
-__device__ __forceinline__ void dn512_pair(const float (&xa)[8], const float (&xb)[8], const float (&win)[8],
-                                           const WaveTwiddles &tw, float2 *lds, int lane,
-                                           const float *__restrict__ na, const float *__restrict__ nb, float2 (&y)[8],
-                                           PhaseStat &pa, PhaseStat &pb)
-{
-    float ea = 0.0f, eb = 0.0f;
-    {
-        float e = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 8; r++) e += (xa[r] * win[r]) * (xa[r] * win[r]) + (xb[r] * win[r]) * (xb[r] * win[r]);
-        pa.e = pb.e = wave_sum_f32(e);                            // the pair's: the two frames share the transform's rounding
-    }
-    dn512_forward(xa, xb, win, tw, lds, lane);
-    float2 yka[4], ykb[4], yma[4], ymb[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int k = lane + 64 * q, m = (512 - k) & 511;
-        const float2 zk = lds[k], zm = lds[512 - k];
-        const float2 A = cadd_conj(zk, zm), B = csub_conj_mj(zk, zm);
-        // bin k of both frames, and bin 512-k (= the conjugates) with ITS noise values
-        const float wm = k == 0 ? 0.0f : 1.0f;                     // bin 0 is its own mirror: counted once
-        const float rthr = real_bin_thr(pa.e, k == 0);
-        yka[q] = apply_gain<MODE>(A, na[k], ea, 1.0f, q == 0, rthr); ykb[q] = apply_gain<MODE>(B, nb[k], eb, 1.0f, q == 0, rthr);
-        yma[q] = apply_gain<MODE>(A, na[m], ea, wm); ymb[q] = apply_gain<MODE>(B, nb[m], eb, wm);
-    }
-    float2 a256, b256;
-    {
-        const float2 z = lds[256];                                // self-mirrored bin: A = 2 Re z, B = 2 Im z, both real
-        const float w256 = lane == 0 ? 1.0f : 0.0f;               // every lane evaluates it; one counts it
-        a256 = apply_gain<MODE>(make_float2(2.f * z.x, 0.f), na[256], ea, w256, true, real_bin_thr(pa.e, true));
-        b256 = apply_gain<MODE>(make_float2(2.f * z.y, 0.f), nb[256], eb, w256, true, real_bin_thr(pa.e, true));
-    }
-    pa.err = wave_sum_f32(ea);
-    pb.err = wave_sum_f32(eb);
-    // A frame with a non-finite bin (Wiener's 0/0 on an all-zero frame before any estimate, WF:204) has an all-NaN
-    // inverse transform in the reference.  Here it must not poison the frame it shares the transform with: its
-    // spectrum goes in as zero and its samples come out as NaN.
-    bool bad_a = false, bad_b = false;
-    if (MODE == 1) {
-        float ta = a256.x * 0.f, tb = b256.x * 0.f;               // NaN iff NaN or inf
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            ta += (yka[q].x + yka[q].y + yma[q].x + yma[q].y) * 0.f;
-            tb += (ykb[q].x + ykb[q].y + ymb[q].x + ymb[q].y) * 0.f;
-        }
-        bad_a = __ballot(ta != ta) != 0ull;
-        bad_b = __ballot(tb != tb) != 0ull;
-    }
-    float2 yk[4], ym[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float2 ak = bad_a ? make_float2(0.f, 0.f) : yka[q], am = bad_a ? make_float2(0.f, 0.f) : yma[q];
-        const float2 bk = bad_b ? make_float2(0.f, 0.f) : ykb[q], bm = bad_b ? make_float2(0.f, 0.f) : ymb[q];
-        yk[q] = cadd_pj(ak, bk);                                  // Ya[k] + j Yb[k]
-        const float2 t = cadd_mj(am, bm);                         // conj(Ya) + j conj(Yb) = conj(Ya - j Yb)
-        ym[q] = make_float2(t.x, -t.y);
-    }
-    const float2 y256 = cadd_pj(bad_a ? make_float2(0.f, 0.f) : a256, bad_b ? make_float2(0.f, 0.f) : b256);
-    wave_lds_fence();
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int k = lane + 64 * q;
-        lds[512 - k] = ym[q];                                     // k = 0 lands in the spare slot 512
-        lds[k] = yk[q];
-    }
-    if (lane == 0) lds[256] = y256;
-    wave_lds_fence();
-#pragma unroll
-    for (int r = 0; r < 8; r++) y[r] = lds[lane + 64 * r];
-    wave_lds_fence();
-    wave_fft512<true>(y, lds, lane, tw);
-    // the reference's 1/N after FFTW's unnormalised inverse (SS:248) with N = 512; a power of two, exact
-#pragma unroll
-    for (int d = 0; d < 8; d++)
-        y[d] = make_float2(bad_a ? __builtin_nanf("") : y[d].x * (1.0f / 512.0f), bad_b ? __builtin_nanf("") : y[d].y * (1.0f / 512.0f));
-    wave_lds_fence();
-}
-
-template <int MODE>
-__global__ __launch_bounds__(64, 3) void denoise512_kernel(
-    const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
-    DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
-    const float *__restrict__ noise_rows, const float2 *__restrict__ table, const float *__restrict__ win512,
-    short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh, int *__restrict__ redo)
-{
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    const int lane = threadIdx.x;
-    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware chunk order (speed only)
-    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * kDn512BlocksPerWave;
-    if (j0 >= n_blocks) return;
-    const long n_samples = n_blocks * 256;
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    float win[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) win[r] = win512[lane + 64 * r];
-
-    // samples base + lane + 64 t: frame (j0 - 1 + 2p) starts at t = 8 p, frame (j0 + 2p) at t = 8 p + 4
-    float xs[8 * kDn512Pairs + 4];
-    const long base = (j0 - 2) * 256;
-#pragma unroll
-    for (int t = 0; t < 8 * kDn512Pairs + 4; t++) xs[t] = dn512_sample(pcm, n_samples, st_in, base + lane + 64 * t);
-
-    float tail[4];
-    const long first_emit = sh.emit_from;
-#pragma unroll
-    for (int p = 0; p < kDn512Pairs; p++) {
-        const long ja = j0 - 1 + 2 * p, jb = ja + 1;
-        if (ja >= n_blocks) break;
-        float xa[8], xb[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) { xa[r] = xs[8 * p + r]; xb[r] = xs[8 * p + 4 + r]; }
-        float2 y[8];
-        PhaseStat pa, pb;
-        dn512_pair<MODE>(xa, xb, win, tw, lds, lane, noise_row(noise_rows, ver_base, snap_mask, ja >= 0 ? ja : 0, sh),
-                         noise_row(noise_rows, ver_base, snap_mask, jb < n_blocks ? jb : n_blocks - 1, sh), y, pa, pb);
-        // the very first call of a stream only stashes its block (SS:211-216): no transform, empty overlap
-        const bool a_void = calls_before + ja <= 0, b_void = calls_before + jb <= 0;
-        {
-            // frames FP32 cannot hold (phase_unsafe; the halo frame is its own wave's): again, in FP64.  Wiener too at
-            // this frame size: its gain has no amplifier, but a quiet frame still takes a loud partner's rounding.
-            float sa = 0.0f, sb = 0.0f;
-#pragma unroll
-            for (int d = 0; d < 8; d++) { sa += y[d].x * y[d].x; sb += y[d].y * y[d].y; }
-            if (p > 0 && !a_void && ja + 1 >= sh.emit_from && phase_unsafe<512>(pa.e, pa.err, sa)) phase_redo(redo, ja, lane);
-            if (jb < n_blocks && !b_void && jb + 1 >= sh.emit_from && phase_unsafe<512>(pb.e, pb.err, sb)) phase_redo(redo, jb, lane);
-        }
-        float oa[4], ob[4];
-        if (p == 0) {
-            // frame ja = j0 - 1 is the halo: its block belongs to the previous wave (or call); only its second half counts
-            if (j0 == 0) {
-#pragma unroll
-                for (int d = 0; d < 4; d++) tail[d] = st_in->tail[lane + 64 * d];       // rgsdOveraped carried over
-            } else {
-#pragma unroll
-                for (int d = 0; d < 4; d++) tail[d] = a_void ? 0.f : y[d + 4].x;
-            }
-        } else {
-#pragma unroll
-            for (int d = 0; d < 4; d++) {
-                oa[d] = tail[d] + (a_void ? 0.f : y[d].x);                              // SS:248 overlap-add
-                tail[d] = a_void ? 0.f : y[d + 4].x;                                    // SS:255-256
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < 4; d++) ob[d] = tail[d] + (b_void ? 0.f : y[d].y);
-        float tail_b[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++) tail_b[d] = b_void ? 0.f : y[d + 4].y;
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const long j = half ? jb : ja;
-            if (half == 0 && p == 0) continue;
-            if (j >= n_blocks) continue;
-            const float *o = half ? ob : oa;
-            if (j >= first_emit && j < sh.emit_to) {
-                const long oi = j - first_emit;
-#pragma unroll
-                for (int d = 0; d < 4; d++) out[oi * 256 + lane + 64 * d] = (short)cast_i16_bits(o[d]);
-                if (precast) {
-#pragma unroll
-                    for (int d = 0; d < 4; d++) precast[oi * 256 + lane + 64 * d] = o[d];
-                }
-            }
-            if (j == n_blocks - 1) {                                                    // SS:257 and the overlap carried out
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    st_out->prev[lane + 64 * d] = pcm[j * 256 + lane + 64 * d];
-                    st_out->tail[lane + 64 * d] = half ? tail_b[d] : tail[d];
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < 4; d++) tail[d] = tail_b[d];
-    }
-}
-
-// The same frames with the spectrum in registers and every mirror pair of bins owned by one lane (frame_io.h,
-// pair_fetch_lds / pair_return_lds): after the forward transform lane l works on k = l + 64 d, d < 5 -- A[k], B[k] from
-// Z[k] and Z[512 - k], ONE gain per frame and bin (N[512 - k] = N[k]: the estimate of a real frame's spectrum is
-// symmetric by construction, noise_accum512_kernel writes both from one value), Z'[k] = Ya + j Yb kept and
-// Z'[512 - k] = conj(Ya - j Yb) sent to its owner.  Ten gains per lane and frame pair instead of eighteen, no natural-
-// order image and no Y image; the wave is persistent over `run` consecutive blocks (run odd: pairs (j0 - 1, j0),
-// (j0 + 1, j0 + 2), ...), keeps both frames' noise values in registers until the estimate changes, and requests the
-// next pair's two new blocks before this pair's arithmetic.  The reference's 1/512 (SS:248) is folded into the gain.
+// The spectrum stays in registers and every mirror pair of bins is owned by one lane (frame_io.h, pair_fetch_lds /
+// pair_return_lds): after the forward transform lane l works on k = l + 64 d, d < 5 -- A[k], B[k] from Z[k] and
+// Z[512 - k], ONE gain per frame and bin (N[512 - k] = N[k]: the estimate of a real frame's spectrum is symmetric by
+// construction, noise_accum512_kernel writes both from one value), Z'[k] = Ya + j Yb kept and Z'[512 - k] =
+// conj(Ya - j Yb) sent to its owner.  Ten gains per lane and frame pair, no natural-order image and no Y image; the wave
+// is persistent over `run` consecutive blocks (run odd), keeps both frames' noise values in registers until the estimate
+// changes, and requests the next pair's two new blocks before this pair's arithmetic.  The reference's 1/512 (SS:248) is
+// folded into the gain.  (Against a fixed seven blocks per wave with LDS images: profiles/r02_denoise512_run.txt.)
 template <int MODE>
 __device__ __forceinline__ void load_noise512_regs(float (&n)[5], const float *__restrict__ row, int lane)
 {
@@ -1701,14 +1294,12 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
     bool halo = true;                                         // frame j0 - 1 only rebuilds the overlap tail
     unsigned prio_step = blockIdx.x >> 10;                    // as in denoise_run_kernel: one priority step per frame pair
     for (long ja = j0 - 1; ja < j1; ja += 2) {
-#if JDSP_DENOISE_PRIO
         switch (prio_step++ & 3u) {
         case 0: __builtin_amdgcn_s_setprio(0); break;
         case 1: __builtin_amdgcn_s_setprio(1); break;
         case 2: __builtin_amdgcn_s_setprio(2); break;
         default: __builtin_amdgcn_s_setprio(3); break;
         }
-#endif
         const long jb = ja + 1;
         if (ja + 2 < j1) {                                    // the next pair's two new blocks, needed one iteration from now
             if (ja + 2 >= 0 && ja + 4 <= n_blocks) {            // both inside this call's buffer (wave-uniform)
@@ -1808,7 +1399,6 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
             ob[d] = tail[d] + (b_void ? 0.f : y[d].y);
             tail_b[d] = b_void ? 0.f : y[d + 4].y;
         }
-#if JDSP_DENOISE_TAKE_EARLY
         if (ja + 2 < j1) {                                        // the next pair's samples are taken before this pair's stores
 #pragma unroll
             for (int b = 0; b < 2; b++)
@@ -1816,7 +1406,6 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
                 for (int t = 0; t < 4; t++) asm volatile("" : "+v"(nx[b][t]));
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
 #pragma unroll
         for (int half = 0; half < 2; half++) {
             const long j = half ? jb : ja;
@@ -1855,33 +1444,19 @@ static int launch_denoise512(hipStream_t s, int mode, int n_cu, const short *pcm
                              const unsigned long long *snap_mask, const float *noise_rows, const float2 *table,
                              const float *win512, short *out, float *precast, const DenoiseShard &sh, int *redo)
 {
-#ifndef JDSP_DENOISE512_RUN
-#define JDSP_DENOISE512_RUN 1
-#endif
-    if (JDSP_DENOISE512_RUN) {
-        // one round of resident waves (4 per SIMD); an odd number of blocks per wave, 7 at least
-        const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_DENOISE512_WAVES(mode);
-        long run = (n_blocks + slots - 1) / slots;
-        if (run < 7) run = 7;
-        run |= 1;
-        const long waves = (n_blocks + run - 1) / run;
-        const long grid = (waves + 7) / 8 * 8;
-        if (mode == 0)
-            hipLaunchKernelGGL(denoise512_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run, redo);
-        else
-            hipLaunchKernelGGL(denoise512_run_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run, redo);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    const long waves = (n_blocks + kDn512BlocksPerWave - 1) / kDn512BlocksPerWave;
+    // one round of resident waves (4 per SIMD); an odd number of blocks per wave, 7 at least
+    const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_DENOISE512_WAVES(mode);
+    long run = (n_blocks + slots - 1) / slots;
+    if (run < 7) run = 7;
+    run |= 1;
+    const long waves = (n_blocks + run - 1) / run;
     const long grid = (waves + 7) / 8 * 8;
     if (mode == 0)
-        hipLaunchKernelGGL(denoise512_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, redo);
+        hipLaunchKernelGGL(denoise512_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
+                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run, redo);
     else
-        hipLaunchKernelGGL(denoise512_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, redo);
+        hipLaunchKernelGGL(denoise512_run_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
+                           st_out, ver_base, snap_mask, noise_rows, table, win512, out, precast, sh, (int)run, redo);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

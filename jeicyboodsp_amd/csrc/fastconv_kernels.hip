@@ -154,15 +154,6 @@ __global__ __launch_bounds__(64) void fastconv1024_kernel(ConvStream s, long n_o
 // the odd pairing taking its second half from the next lane (DPP wave_shl:1; lane 63: lane 0's next register).  Waves
 // are persistent over blocks with the filters' 2 x 5 spectrum values per lane in registers.
 // H spectra are Hermitian (real taps), so Y[1024 - k] = conj(Y[k]) holds exactly as the pair scheme assumes.
-#ifndef JDSP_CONV1024_PAIRS
-#define JDSP_CONV1024_PAIRS 1
-#endif
-#ifndef JDSP_CONV_PLAIN_STORES
-#define JDSP_CONV_PLAIN_STORES 0
-#endif
-#ifndef JDSP_CONV_ABLATE
-#define JDSP_CONV_ABLATE 0          // timing-only ablations of fastconv1024_pairs_kernel (tools/build_variant.sh): wrong results
-#endif
 #ifndef JDSP_CONV1024_GRID
 #define JDSP_CONV1024_GRID (1024 * JDSP_CONV1024_MINWAVES)
 #endif
@@ -177,16 +168,7 @@ __device__ __forceinline__ void constexpr_row(int d, int odd, short *obase, unsi
     if (first + 128 <= N0 || first >= N1) return;
     const int na = 2 * lane + first;
     if (first >= N0 && first + 128 <= N1) {
-#if JDSP_CONV_ABLATE & 8                                          /* 8, timing-only: casts and packing stay, the row stores never execute */
-        const unsigned int pk = cast_i16x2_bits(va, vb);
-        if (pk == 0xdeadbeefu && __builtin_amdgcn_readfirstlane((int)pk) == 123) p32[64 * d] = pk;
-        return;
-#endif
-#if JDSP_CONV_PLAIN_STORES                                        /* timing-only A/B: cached stores (L2 merges the partial lines of the odd-pitch rows) */
-        p32[64 * d] = cast_i16x2_bits(va, vb);
-#else
         __builtin_nontemporal_store(cast_i16x2_bits(va, vb), p32 + 64 * d);
-#endif
         if (PC) { pc[na] = va; pc[na + 1] = vb; }
         return;
     }
@@ -203,17 +185,8 @@ __device__ __forceinline__ void constexpr_row(int d, int odd, short *obase, unsi
 // N0 = n_taps - 1, BLOCK: compile-time, so that which register rows are kept whole, partly or not at all is decided
 // when the kernel is built (instantiated for BASELINE config 2's 256 taps / 769-sample blocks; other shapes take
 // fastconv1024_kernel).
-#ifndef JDSP_CONV1024_H_IN_REGS
-#define JDSP_CONV1024_H_IN_REGS 1
-#endif
 #ifndef JDSP_CONV1024_MINWAVES
 #define JDSP_CONV1024_MINWAVES 3
-#endif
-#ifndef JDSP_CONV1024_X2
-#define JDSP_CONV1024_X2 1          // 1: a filter pair's two inverse transforms staggered in one wave; 0: one after the other (round 2)
-#endif
-#if JDSP_CONV1024_X2 && !JDSP_CONV1024_H_IN_REGS
-#error "JDSP_CONV1024_X2 takes the filter spectra from registers"
 #endif
 // PC: the pre-cast tap (tests only) is a build-time property of the kernel -- as a run-time test per register row it cut
 // the output stage into two dozen basic blocks that the scheduler could not interleave with anything
@@ -225,7 +198,7 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
                                                                 short *__restrict__ hist_out)
 {
     // NF == 2: the two ears' inverse transforms run staggered in one wave (wave_fft512.h), each in its own scratch
-    __shared__ __attribute__((aligned(16))) float2 lds[(NF == 2 && JDSP_CONV1024_X2) ? 2 * kWaveLdsComplex : kWaveLdsComplex];
+    __shared__ __attribute__((aligned(16))) float2 lds[NF == 2 ? 2 * kWaveLdsComplex : kWaveLdsComplex];
     const int lane = threadIdx.x;
     if ((long)blockIdx.x >= n_out_blocks) return;
 #if JDSP_STAMP
@@ -248,7 +221,6 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
     load_pair_twiddles(pw, table, lane);
     constexpr int block = BLOCK, n0 = N0, n1 = N0 + BLOCK;       // samples [n0, n1) of every segment are kept (:156-158)
     static_assert(n1 <= 1024, "segment of 1024 samples");
-#if JDSP_CONV1024_H_IN_REGS
     float2 Hlo[NF][5], Hhi[NF][5];                              // the filters' spectrum values of this lane's ten bins
 #pragma unroll
     for (int f = 0; f < NF; f++)
@@ -257,7 +229,6 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
             Hlo[f][d] = Hall[(size_t)f * 1024 + lane + 64 * d];
             Hhi[f][d] = Hall[(size_t)f * 1024 + lane + 64 * d + 512];
         }
-#endif
     // Plain loads, no per-sample tests (but see the first block below).  A segment starts at a
     // multiple of BLOCK samples, so its sample pairs are 2-byte-aligned dwords (the hardware takes them as they are);
     // the next block's eight are requested before this block's arithmetic starts -- without that the wave spent 61 % of
@@ -287,24 +258,17 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
     // empty for the last third of the launch.  Handing the blocks out at run time instead costs an atomic per block
     // (65,535 returning atomics on one line: 1,030 us).  So every wave walks the priority levels, one step per block:
     // priority outranks age, each wave does the same number of blocks at each level, and equal shares end together.
-#ifndef JDSP_CONV_PRIO
-#define JDSP_CONV_PRIO 1
-#endif
-    unsigned prio_step = JDSP_CONV_PRIO == 2 ? blockIdx.x % 3u : blockIdx.x >> 10;
+    unsigned prio_step = blockIdx.x >> 10;
     // vmcnt counts loads and stores together, in issue order, and across the loop's back edge the compiler waits for
     // vmcnt(0): taking the prefetched samples at the TOP of an iteration therefore waited for the previous block's two
     // dozen output stores to complete, every block.  They are taken (cur <- nxt) just BEFORE this block's stores instead:
     // the loads were issued a whole block's arithmetic earlier, and the stores then have until the next block's take.
-#ifndef JDSP_CONV_TAKE_EARLY
-#define JDSP_CONV_TAKE_EARLY 1
-#endif
-    constexpr bool take_early = JDSP_CONV_TAKE_EARLY && NF == 2 && JDSP_CONV1024_X2;   // (the one-filter form stores inside its filter loop)
+    constexpr bool take_early = NF == 2;   // (the one-filter form stores inside its filter loop)
     if (take_early) {
 #pragma unroll
         for (int r = 0; r < 8; r++) cur[r] = nxt[r];
     }
     for (long e = blockIdx.x; e < n_out_blocks; e += gridDim.x) {
-#if JDSP_CONV_PRIO
         {
             const unsigned lvl = prio_step % 3u;
             if (lvl == 0) __builtin_amdgcn_s_setprio(0);
@@ -312,7 +276,6 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
             else __builtin_amdgcn_s_setprio(2);
             prio_step++;
         }
-#endif
         if (!take_early) {
 #pragma unroll
             for (int r = 0; r < 8; r++) cur[r] = nxt[r];
@@ -338,7 +301,6 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
             hi[d] = csub(ev, p);
         }
         float2 yy[NF][8];
-#if JDSP_CONV1024_X2
         if (NF == 2) {
             float2 ret[2][4];
 #pragma unroll
@@ -359,7 +321,6 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
             wave_lds_fence();
             wave_fft512_x2_staggered<true>(yy[0], yy[NF - 1], lds, lds_b, lane, tw);
         }
-#endif
         if (take_early) {
 #pragma unroll
             for (int r = 0; r < 8; r++) { cur[r] = nxt[r]; asm volatile("" : "+v"(cur[r])); }
@@ -368,44 +329,22 @@ __global__ __launch_bounds__(64, JDSP_CONV1024_MINWAVES) void fastconv1024_pairs
 #pragma unroll
         for (int f = 0; f < NF; f++) {
             float2 (&y)[8] = yy[f];
-            if (!(NF == 2 && JDSP_CONV1024_X2)) {
+            if (NF != 2) {
                 float2 ret[4];
 #pragma unroll
                 for (int d = 0; d < 5; d++) {
-#if JDSP_CONV1024_H_IN_REGS
                     const float2 yl = cmul(lo[d], Hlo[f][d]), yh = cmul(hi[d], Hhi[f][d]);           // :150-151
-#else
-                    const float2 *H = Hall + (size_t)f * 1024 + lane;         // 16 KB for a filter pair: L1 / L2 hits
-                    const float2 yl = cmul(lo[d], H[64 * d]), yh = cmul(hi[d], H[64 * d + 512]);     // :150-151
-#endif
                     if (d < 4) presplit_inv_pair(yl, yh, pw.w[d], y[d], ret[d]);
                     else y[d] = presplit_inv_reg(yl, yh, pw.w[d]);
                 }
                 pair_return_lds(ret, lds, lane, y);
-#if !(JDSP_CONV_ABLATE & 1)                                            /* 1, timing-only: no inverse transforms */
                 wave_fft512<true>(y, lds, lane, tw);
-#endif
                 wave_lds_fence();
             }
             short *obase = out + (size_t)f * plane + e * block - n0;         // obase[n] = where sample n of the segment goes
             const int odd = (int)((reinterpret_cast<uintptr_t>(obase) >> 1) & 1);  // wave-uniform: which pairing is dword-aligned
             unsigned int *p32 = reinterpret_cast<unsigned int *>(obase + 2 * lane + odd);
             float *pc = PC ? precast + (size_t)f * plane + e * block - n0 : nullptr;
-#if JDSP_CONV_ABLATE & 4                                               /* 4, timing-only: no output stores (one lane keeps the values alive) */
-            if (y[0].x == 1.2345e30f && y[7].y == 5.4321e-30f && y[3].x == y[4].y && y[2].y == y[5].x && y[1].x == y[6].y) {
-                out[lane] = (short)cast_i16_bits(y[0].x + y[1].x + y[2].x + y[3].x + y[4].x + y[5].x + y[6].x + y[7].x +
-                                                 y[0].y + y[1].y + y[2].y + y[3].y + y[4].y + y[5].y + y[6].y + y[7].y);
-            }
-            continue;
-#endif
-#if JDSP_CONV_ABLATE & 2                                               /* 2, timing-only: aligned stores only */
-            if (true) {
-#pragma unroll
-                for (int d = 2; d < 8; d++)
-                    __builtin_nontemporal_store(cast_i16x2_bits(y[d].x, y[d].y),
-                                                reinterpret_cast<unsigned int *>(out + (size_t)f * plane + e * block + odd) + lane + 64 * (d - 2));
-            } else
-#endif
             if (!odd) {
 #pragma unroll
                 for (int d = 0; d < 8; d++) {
@@ -586,7 +525,7 @@ int launch_fastconv(hipStream_t st, int n_fft, const ConvStream &s, long n_out_b
                     const float2 *tw8192, short *out, float *precast, long plane, short *hist_out)
 {
     if (n_out_blocks > 0) {
-        if (n_fft == 1024 && JDSP_CONV1024_PAIRS && (n_filters == 1 || n_filters == 2) && n_taps == 256 && block == 769) {
+        if (n_fft == 1024 && (n_filters == 1 || n_filters == 2) && n_taps == 256 && block == 769) {
             // persistent waves (a wave's first block may reach into the history / the silent head: handled there)
             const unsigned grid = (unsigned)(n_out_blocks < JDSP_CONV1024_GRID ? n_out_blocks : JDSP_CONV1024_GRID);
             short *ho = s.hist_len > 0 ? hist_out : (short *)nullptr;
@@ -624,8 +563,8 @@ int launch_fastconv(hipStream_t st, int n_fft, const ConvStream &s, long n_out_b
 //   conv_stage_kernel   lays [history | this call's samples] out as one int16 run, with the reference's
 //                       silent head (conv_sample) already applied
 //   stft1024_hop512_half_kernel (stft_kernels.hip)   X rows, bins 0..512 at a pitch of 520
-//   fastconv_upols_kernel   one wave per output sub-block: P multiply-accumulates per bin from L2-resident
-//                       rows, Hermitian extension through LDS, pre-split, inverse wave FFT, cast
+//   fastconv_upols4_kernel  a wave per kUpolsK output sub-blocks: P multiply-accumulates per bin (rows from L2, partition
+//                       spectra from LDS), Hermitian extension through LDS, pre-split, inverse wave FFT, cast
 __global__ void conv_stage_kernel(ConvStream s, long lead, long n_total, short *__restrict__ staged,
                                   short *__restrict__ hist_out)
 {
@@ -655,12 +594,6 @@ __global__ void conv_stage_kernel(ConvStream s, long lead, long n_total, short *
     }
 }
 
-#ifndef JDSP_UPOLS_SIMPLE
-#define JDSP_UPOLS_SIMPLE 0       // 1: the one-wave-per-sub-block kernel (kept for comparison)
-#endif
-#ifndef JDSP_UPOLS_UNROLL
-#define JDSP_UPOLS_UNROLL 1       // partitions whose loads are in flight together
-#endif
 constexpr int kUpolsPitch = kUpolsRowPitch;   // 520 complex elements per spectrum row (513 used): 65 x 64 bytes
 
 template <int J>
@@ -675,6 +608,13 @@ __device__ __forceinline__ void upols_presplit_j(const float2 *img, float2 *zout
     zout[2 * J + 1] = presplit_inv<J>(make_float2(yy.z, yy.w), make_float2(zr1.x, -zr1.y), wsp[1]);
 }
 
+// One wave per output sub-block, every row and partition spectrum from L2.  NOT LAUNCHED: fastconv_upols4_kernel below
+// replaced it (profiles/r01_fastconv_partitioned.txt).  It is still here because the compiler pairs four of
+// fastconv_upols4_kernel's LDS reads differently once this kernel is gone from the module
+// (profiles/r12_dead_variants_isa.txt); it goes when that kernel's speed has been measured without it.
+#ifndef JDSP_UPOLS_UNROLL
+#define JDSP_UPOLS_UNROLL 1       // partitions whose loads are in flight together
+#endif
 __global__ __launch_bounds__(64) void fastconv_upols_kernel(const float2 *__restrict__ X, const float2 *__restrict__ Hp,
                                                             int n_part, int n_filters, long first_row, long n_sub,
                                                             const float2 *__restrict__ table, short *__restrict__ out,
@@ -739,20 +679,13 @@ __global__ __launch_bounds__(64) void fastconv_upols_kernel(const float2 *__rest
     }
 }
 
-// The same sums with the traffic cut down: one workgroup = 4 waves, one wave = kUpolsK consecutive output
-// sub-blocks.  A row X[r] feeds sub-block t through H_(t-r), so a wave walking the rows it needs from the
-// newest down uses every row for up to kUpolsK outputs (P + kUpolsK - 1 rows from L2 instead of
-// kUpolsK * P), with the next row in flight while the current one is used, and the partition spectra sit in
-// LDS, loaded once per workgroup.  (One wave per sub-block reading P rows and P partition spectra from L2
-// ran at 22 TB/s of L2 traffic: 44 us for the native shape; profiles/r01_fastconv_partitioned.txt.)
-#ifndef JDSP_UPOLS_SHAPE
-#define JDSP_UPOLS_SHAPE 1        // 0: 4 waves x 4 outputs, 4 rows in flight (2 waves/SIMD); 1: 16 waves x 2 outputs, 2 rows
-#endif                            //    in flight (4 waves/SIMD: the workgroup fills a CU, LDS = 60 KB of spectra + 73 KB scratch)
-#if JDSP_UPOLS_SHAPE
+// One workgroup = kUpolsWaves waves, one wave = kUpolsK consecutive output sub-blocks.  A row X[r] feeds sub-block t
+// through H_(t-r), so a wave walking the rows it needs from the newest down uses every row for up to kUpolsK outputs
+// (P + kUpolsK - 1 rows from L2 instead of kUpolsK * P), with the next row in flight while the current one is used, and
+// the partition spectra sit in LDS, loaded once per workgroup.  (One wave per sub-block reading P rows and P partition
+// spectra from L2 ran at 22 TB/s of L2 traffic: 44 us for the native shape; profiles/r01_fastconv_partitioned.txt.)
+// 16 waves x 2 outputs, 2 rows in flight (4 waves/SIMD: the workgroup fills a CU, LDS = 60 KB of spectra + 73 KB scratch).
 constexpr int kUpolsWaves = 16, kUpolsK = 2, kUpolsDepth = 2;
-#else
-constexpr int kUpolsWaves = 4, kUpolsK = 4, kUpolsDepth = 4;
-#endif
 
 __global__ __launch_bounds__(kUpolsWaves * 64) void fastconv_upols4_kernel(const float2 *__restrict__ X, const float2 *__restrict__ Hp,
                                                               int n_part, int n_filters, long first_row, long n_sub,
@@ -899,11 +832,6 @@ int launch_fastconv_upols(hipStream_t st, const ConvStream &s, long n_out_blocks
         // output sub-block t = call-local samples [first_block * block + 512 t, +512) = staged sub-block
         // n_part + first_block * block / 512 + t = the second half of frame (that index - 1)
         const long first_row = n_part + (long)first_block * (block / 512) - 1;
-#if JDSP_UPOLS_SIMPLE
-        const long grid = (n_sub + 7) / 8 * 8;
-        hipLaunchKernelGGL(fastconv_upols_kernel, dim3((unsigned)grid), dim3(64), 0, st, X, Hp, n_part, n_filters, first_row,
-                           n_sub, rect_table, out, precast, plane);
-#else
         const long per_wg = kUpolsWaves * kUpolsK;
         const long grid = ((n_sub + per_wg - 1) / per_wg + 7) / 8 * 8;
         const size_t lds = ((size_t)n_part * kUpolsPitch + kUpolsWaves * (size_t)kWaveLdsComplex) * sizeof(float2);
@@ -913,7 +841,6 @@ int launch_fastconv_upols(hipStream_t st, const ConvStream &s, long n_out_blocks
             return -1;
         hipLaunchKernelGGL(fastconv_upols4_kernel, dim3((unsigned)grid), dim3(kUpolsWaves * 64), lds, st, X, Hp, n_part, n_filters,
                            first_row, n_sub, n_frames - 1, rect_table, out, precast, plane);
-#endif
     }
     if (s.hist_len > 0 && n_out_blocks <= 0)                           // otherwise the staging kernel wrote it
         hipLaunchKernelGGL(conv_hist_update_kernel, dim3((s.hist_len + 255) / 256), dim3(256), 0, st, s, hist_out);

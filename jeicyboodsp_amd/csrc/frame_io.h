@@ -110,21 +110,6 @@ __device__ __forceinline__ void mirror_fetch(const float2 (&v)[8], int lane, flo
     }
 }
 
-// The same operands through a natural-order LDS image instead: 8 ds_write_b64 + 8 ds_read_b64 (lane l reads slot
-// 512 - l - 64 d: consecutive lanes, consecutive slots, conflict-free; slot 512 = slot 0, so lane 0 needs no special
-// case).  A ds_bpermute_b32 costs the LDS pipe three times a ds_read_b64's worth per byte (tools/valu_rate.hip: 8.9
-// issue slots against 16 x 1.6 for the selects it also needs), so this is the cheaper way to fetch the mirror --
-// what is saved against the round-1 image is its second read (Zh[m] stays in registers) and the whole Z' image.
-// `img` must not be in use: fence before this if the transform's last exchange may still be reading it.
-__device__ __forceinline__ void mirror_fetch_lds(const float2 (&v)[8], float2 *img, int lane, float2 (&zr)[8])
-{
-    store_natural_image(img, lane, v);
-    wave_lds_fence();
-#pragma unroll
-    for (int d = 0; d < 8; d++) zr[d] = xchg_ld(img, 512 - lane - 64 * d);
-    wave_lds_fence();
-}
-
 // X[m] = E + W^m O, X[m + 512] = E - W^m O for m = lane + 64 d (the 1/2 is folded into the window as everywhere)
 __device__ __forceinline__ void split_fwd_reg(const float2 (&v)[8], const float2 (&zr)[8], const SplitTwiddles &t,
                                               float2 (&lo)[8], float2 (&hi)[8])
@@ -158,7 +143,10 @@ __device__ __forceinline__ float2 presplit_inv_reg(float2 ylo, float2 yhi, float
 // keeps Z'[l + 64 d] for d <= 4 and receives registers 5..7; the pairs of d = 3, 4 overlap (m = 192 + l and 256 + (64 - l)
 // are mirrors) so that every lane runs the same five items and no lane needs a special case.  Five split / per-bin /
 // pre-split items per lane instead of eight, ten per-bin evaluations instead of sixteen, ten noise values and five
-// twiddles in registers instead of sixteen and eight; the LDS moves the same nine + eight vectors as mirror_fetch_lds.
+// twiddles in registers instead of sixteen and eight.  The mirror operands go through an LDS image (lane l reads slot
+// 512 - l - 64 d: consecutive lanes, consecutive slots, conflict-free; slot 512 = slot 0, so lane 0 needs no special
+// case), not through ds_bpermute as in mirror_fetch: a ds_bpermute_b32 costs the LDS pipe three times a ds_read_b64's
+// worth per byte (tools/valu_rate.hip: 8.9 issue slots against 16 x 1.6 for the selects it also needs).
 struct PairTwiddles { float2 w[5]; };
 
 __device__ __forceinline__ void load_pair_twiddles(PairTwiddles &t, const float2 *__restrict__ table, int lane)
@@ -269,6 +257,27 @@ __device__ __forceinline__ int version_of(const int *__restrict__ ver_base,
 {
     const unsigned long long m = snap_mask[j >> 6] & (~0ull >> (63 - (int)(j & 63)));
     return ver_base[j >> 6] + __popcll(m);
+}
+
+// Sums over the wave, the result wave-uniform: five DPP adds (quad swaps, row mirrors, row broadcasts) and a v_readlane
+// of lane 63.  (A __shfl_xor tree is six ds_bpermute, 8.9 issue slots each on this chip: tools/valu_rate.hip.)
+__device__ __forceinline__ unsigned int wave_sum_u32(unsigned int v)
+{
+    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
+    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
+    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, true);    // row_half_mirror: sums of 8
+    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, true);    // row_mirror: sums of 16
+    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, true);    // row_bcast15 into rows 1 and 3
+    v += (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, true);    // row_bcast31 into rows 2 and 3
+    return (unsigned int)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ float wave_sum_f32(float v)
+{
+#define JDSP_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, true))
+    JDSP_DPP_ADD(0xB1, 0xf); JDSP_DPP_ADD(0x4E, 0xf); JDSP_DPP_ADD(0x141, 0xf); JDSP_DPP_ADD(0x140, 0xf);
+    JDSP_DPP_ADD(0x142, 0xa); JDSP_DPP_ADD(0x143, 0xc);
+#undef JDSP_DPP_ADD
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
 

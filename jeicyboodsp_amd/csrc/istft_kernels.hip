@@ -5,7 +5,7 @@
 // stores, the tail, the halo and the run order -- is the stream of ola_stream.h.  Per frame:
 //   n = 1024  the real frame comes from ONE 512-point complex inverse through the pre-split of frame_io.h: the rows are
 //             made Hermitian first, H[k] = (X[k] + conj X[-k]) / 2 (FULL: X[-k] read back from a natural-order image
-//             of the row in the wave's LDS, the mirror_fetch_lds pattern; HALF: H[n-k] = conj X[k], the row's lower half
+//             of the row in the wave's LDS, slot 512 - k; HALF: H[n-k] = conj X[k], the row's lower half
 //             through the same image), so a non-Hermitian row gives exactly the real part of its full inverse.
 //   n = 512   one 512-point complex inverse of H per frame, real part kept.  Never two frames in one transform: a
 //             frame's result must not depend on its neighbour, or on where a call or shard cut falls.

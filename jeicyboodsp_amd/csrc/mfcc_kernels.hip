@@ -12,21 +12,6 @@
 
 namespace jdsp {
 
-// sum over the wave, the same value in every lane's copy of lane 63 (five DPP adds and a v_readlane; a __shfl_xor tree
-// is six ds_bpermute, 8.9 issue slots each)
-__device__ __forceinline__ float wave_sum_f32(float v)
-{
-#define JDSP_DPP_ADD(CTRL, ROWS) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROWS, 0xf, true))
-    JDSP_DPP_ADD(0xB1, 0xf);     // quad_perm [1,0,3,2]
-    JDSP_DPP_ADD(0x4E, 0xf);     // quad_perm [2,3,0,1]
-    JDSP_DPP_ADD(0x141, 0xf);    // row_half_mirror: sums of 8
-    JDSP_DPP_ADD(0x140, 0xf);    // row_mirror: sums of 16
-    JDSP_DPP_ADD(0x142, 0xa);    // row_bcast15 into rows 1 and 3
-    JDSP_DPP_ADD(0x143, 0xc);    // row_bcast31 into rows 2 and 3
-#undef JDSP_DPP_ADD
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-
 // ---- which frames must be computed again, in FP64 (every MFCC kernel; derived for two frames that share a transform) -----
 // Two frames share one FP32 transform there; its rounding -- 2^-23 of the rms of ITS OUTPUT per bin, three radix-8
 // passes (measured: profiles/r10_mfcc_pair_leak.txt) -- lands in both frames' bins whoever's samples caused it.  With
@@ -209,42 +194,11 @@ __global__ __launch_bounds__(64) void mfcc_kernel(const short *__restrict__ pcm,
 // carries two frames through every phase together: the table loads are shared, every fence covers two
 // frames, and two independent dependency chains interleave.  |X| goes through registers and reuses the
 // transform scratch, which keeps the LDS footprint at 9.8 KB per wave (four waves per SIMD).
-__device__ __forceinline__ void mfcc_load_frame(const short *__restrict__ src, const MfccDev &p, int lane, float2 (&v)[8])
-{
-    // x[i] = s[i] - preemph * s[i-1] for 1 <= i < win_len, x[0] = 0 (:208 starts at i = 1), zero beyond
-    if (p.win_len == 1024 && (((uintptr_t)src) & 3u) == 0) {
-        const unsigned int *s32 = reinterpret_cast<const unsigned int *>(src) + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const float2 cur = unpack_i16x2(s32[64 * r]);
-            const bool first = (lane == 0 && r == 0);
-            const float sm = first ? 0.f : (float)((int)s32[first ? 0 : 64 * r - 1] >> 16);
-            const float2 w = p.window[lane + 64 * r];
-            const float x0 = first ? 0.f : cur.x - p.preemph * sm;
-            const float x1 = cur.y - p.preemph * cur.x;
-            v[r] = make_float2(x0 * w.x, x1 * w.y);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int i0 = 2 * lane + 128 * r;
-            float sm = 0.f, s0 = 0.f, s1 = 0.f;
-            if (i0 >= 1 && i0 - 1 < p.win_len) sm = (float)src[i0 - 1];
-            if (i0 < p.win_len) s0 = (float)src[i0];
-            if (i0 + 1 < p.win_len) s1 = (float)src[i0 + 1];
-            const float2 w = p.window[lane + 64 * r];            // halved Hamming pair, zero beyond win_len
-            const float x0 = (i0 >= 1) ? s0 - p.preemph * sm : 0.f;
-            const float x1 = s1 - p.preemph * s0;
-            v[r] = make_float2(x0 * w.x, x1 * w.y);
-        }
-    }
-}
-
-// The same in two halves, so that a kernel can have every load of a wave -- both frames' samples, window, twiddles,
-// filterbank piece -- in flight before it waits for the first: mfcc_load_frame's `aligned?` branch sits between the
-// two frames' loads and the tables', which made three memory round trips in series of what can be one (ISA: frame a's
-// loads, s_waitcnt vmcnt(0), frame b's, vmcnt(0), tables), and its general path guards every halfword with a branch
-// and a wait of its own.  ALIGNED: the dword holding samples 2 lane + 128 r, +1 (the sample before them is the previous lane's).  Otherwise
+// A frame is loaded in two halves (mfcc_fetch, mfcc_finish), so that a kernel can have every load of a wave -- both
+// frames' samples, window, twiddles, filterbank piece -- in flight before it waits for the first: loaded in one piece, the
+// `aligned?` branch sat between the two frames' loads and the tables', which made three memory round trips in series of
+// what can be one (ISA: frame a's loads, s_waitcnt vmcnt(0), frame b's, vmcnt(0), tables), and the general path guarded
+// every halfword with a branch and a wait of its own.  ALIGNED: the dword holding samples 2 lane + 128 r, +1 (the sample before them is the previous lane's).  Otherwise
 // three halfwords at positions clamped into [0, win_len): the window is zero wherever the clamp changes a position.
 template <bool ALIGNED> struct MfccRaw;
 template <> struct MfccRaw<true> { unsigned int cur[8]; };
@@ -291,53 +245,6 @@ __device__ __forceinline__ void mfcc_finish(const MfccRaw<false> &raw, const flo
         const float x1 = s1 - preemph * s0;
         v[r] = make_float2(x0 * w[r].x, x1 * w[r].y);
     }
-}
-
-// |X[m]|, m = 128 j + 2 lane + e < 512, of the natural-order image `img` (:218-220)
-__device__ __forceinline__ void mfcc_magnitudes(const float2 *img, int lane, float2 wsp0, float2 wsp1, float2 (&amp)[4])
-{
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int m = 128 * j + 2 * lane;
-        const float4 zz = *reinterpret_cast<const float4 *>(&img[m]);
-        float2 zr0, zr1;
-        load_mirror_pair(img, m, zr0, zr1);
-        float2 lo0, hi0, lo1, hi1;
-        if (j == 0) { split_fwd<0>(make_float2(zz.x, zz.y), zr0, wsp0, lo0, hi0); split_fwd<0>(make_float2(zz.z, zz.w), zr1, wsp1, lo1, hi1); }
-        if (j == 1) { split_fwd<1>(make_float2(zz.x, zz.y), zr0, wsp0, lo0, hi0); split_fwd<1>(make_float2(zz.z, zz.w), zr1, wsp1, lo1, hi1); }
-        if (j == 2) { split_fwd<2>(make_float2(zz.x, zz.y), zr0, wsp0, lo0, hi0); split_fwd<2>(make_float2(zz.z, zz.w), zr1, wsp1, lo1, hi1); }
-        if (j == 3) { split_fwd<3>(make_float2(zz.x, zz.y), zr0, wsp0, lo0, hi0); split_fwd<3>(make_float2(zz.z, zz.w), zr1, wsp1, lo1, hi1); }
-        amp[j] = make_float2(__builtin_amdgcn_sqrtf(lo0.x * lo0.x + lo0.y * lo0.y),
-                             __builtin_amdgcn_sqrtf(lo1.x * lo1.x + lo1.y * lo1.y));
-    }
-}
-
-// mel filterbank (:157-168) of one frame: `mag` -> channel sums in `logmel` (LDS atomics, see mfcc_kernel)
-__device__ __forceinline__ void mfcc_mel(const float *mag, float *logmel, const MfccDev &p, int lane, const float (&ff)[8],
-                                         const int (&kk)[8])
-{
-    const int i0 = 8 * lane;
-    if (i0 >= p.n_bins) return;
-    const float4 m0 = *reinterpret_cast<const float4 *>(&mag[i0]), m1 = *reinterpret_cast<const float4 *>(&mag[i0 + 4]);
-    const float mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-    int cur = kk[0];
-    float lo = 0.f, hi = 0.f;
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        if (kk[t] != cur) {
-            if (cur >= 1) atomicAdd(&logmel[cur - 1], lo);
-            if (cur < p.n_chan) atomicAdd(&logmel[cur], hi);
-            cur = kk[t];
-            lo = hi = 0.f;
-        }
-        if (cur == 0) hi += (1.f - ff[t]) * mm[t];                 // :161
-        else {
-            lo += ff[t] * mm[t];                                   // :164
-            if (cur != p.n_chan) hi += (1.f - ff[t]) * mm[t];      // :165-166
-        }
-    }
-    if (cur >= 1) atomicAdd(&logmel[cur - 1], lo);
-    if (cur < p.n_chan) atomicAdd(&logmel[cur], hi);
 }
 
 // a + a[lane ^ 16] / a + a[lane ^ 32] for a double: the swap leaves {even-row value, odd-row value} (resp. {lower-half,
@@ -395,13 +302,9 @@ __device__ __forceinline__ void mel_channel_sums(float (*pieces)[2][64], float (
     wave_lds_fence();
 }
 
-#ifndef JDSP_MFCC_X2_PAIRS
-#define JDSP_MFCC_X2_PAIRS 1
-#endif
-#ifndef JDSP_MFCC_ABLATE
-#define JDSP_MFCC_ABLATE 0        // timing-only ablations of mfcc_x2_kernel's tail (tools/build_variant.sh): wrong results
-#endif
-// The tail both two-frame kernels share: |X| of two frames, bin i at mag[i + (i >> 4)] -> feats[fa], feats[fb].  sg/sw/cw:
+// The tail both two-frame kernels share: |X| of two frames, bin i at mag[i + (i >> 4)] -> feats[fa], feats[fb].  (PADDED:
+// the filterbank reads |X| one piece per lane, and the pieces of the wide upper channels start 16 bins apart -- unpadded,
+// those lanes' addresses are 16 words apart and fall on two banks: 18 % of the LDS pipe's busy time.)  sg/sw/cw:
 // this lane's filterbank piece (MfccDev::seg, seg_wc), dc: its ten DCT coefficients (rows cpart + cstep t of column ci,
 // unguarded loads from the zero-padded table), lw: its lifter weight -- all requested by the caller long before.
 template <int PL> struct MfccLaneTables { int4 sg; float sw[PL], cw[PL]; };
@@ -453,12 +356,8 @@ __device__ __forceinline__ bool mfcc_tail_pre(const float *mag_a, const float *m
             for (int t = 0; t < n; t++) {
                 const int bin = min(sg.x + h + t, last_bin);         // past the piece: any finite value, its weights are 0
                 const int q = bin + (bin >> 4);
-#if JDSP_MFCC_ABLATE & 1                                             /* timing-only: no filterbank reads */
-                ma[t] = (float)q; mb[t] = (float)(q + 1);
-#else
                 ma[t] = mag_a[q];
                 mb[t] = mag_b[q];
-#endif
             }
 #pragma unroll
             for (int t = 0; t < n; t++) {
@@ -540,9 +439,6 @@ __device__ __forceinline__ void mfcc_x2_body(const short *__restrict__ src_a, co
     for (int r = 0; r < 8; r++) win[r] = p.window[lane + 64 * r];
     WaveTwiddles tw;
     load_wave_twiddles(tw, table, lane);
-#if !JDSP_MFCC_X2_PAIRS
-    const float2 wsp0 = table[kStftSplit + 2 * lane], wsp1 = table[kStftSplit + 2 * lane + 1];
-#endif
     float2 va[8], vb[8];
     mfcc_finish(raw_a, win, p.preemph, lane, va);
     mfcc_finish(raw_b, win, p.preemph, lane, vb);
@@ -557,7 +453,6 @@ __device__ __forceinline__ void mfcc_x2_body(const short *__restrict__ src_a, co
 
     const float e_a = mfcc_packed_real_energy(va), e_b = mfcc_packed_real_energy(vb);
     wave_fft512_x2<false>(va, vb, lds[0], lds[1], lane, tw);
-#if JDSP_MFCC_X2_PAIRS
     // |X[m]| and |X[512 - m]| (= |X[m + 512]|) for m = lane + 64 d, d < 5 -- bins 0..319 and 193..511 -- from the
     // pair-owned split (frame_io.h): five mirror operands per frame through LDS instead of a natural-order image and
     // two reads of it (11 KB instead of 24 KB per pair of frames through the LDS pipe, which bounds this kernel)
@@ -598,34 +493,6 @@ __device__ __forceinline__ void mfcc_x2_body(const short *__restrict__ src_a, co
             }
         }
     }
-#else
-    store_natural_image(lds[0], lane, va);
-    store_natural_image(lds[1], lane, vb);
-    wave_lds_fence();
-    float2 amp_a[4], amp_b[4];
-    mfcc_magnitudes(lds[0], lane, wsp0, wsp1, amp_a);
-    mfcc_magnitudes(lds[1], lane, wsp0, wsp1, amp_b);
-    wave_lds_fence();                                                // every lane's split reads are done: overwrite
-    logmel[0][lane] = 0.f;
-    logmel[1][lane] = 0.f;
-    float *mag_a = reinterpret_cast<float *>(lds[0]), *mag_b = reinterpret_cast<float *>(lds[1]);
-    // |X| is stored PADDED, bin i at i + (i >> 4): the filterbank below reads it one piece per lane, and the pieces
-    // of the wide upper channels start 16 bins apart -- unpadded, those lanes' addresses are 16 words apart and fall
-    // on two banks (the counter pass showed the LDS pipe busy 72 % of the kernel, 18 % of it bank conflicts)
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int m = 128 * j + 2 * lane;
-        if (p.bin_stride == 1) {
-            const int q = m + (m >> 4);                              // m even: m and m + 1 share a group of 16
-            mag_a[q] = amp_a[j].x; mag_a[q + 1] = amp_a[j].y;
-            mag_b[q] = amp_b[j].x; mag_b[q + 1] = amp_b[j].y;
-        } else {                                                     // 512-point bins = even 1024-point bins
-            const int h = m >> 1, q = h + (h >> 4);
-            mag_a[q] = amp_a[j].x;
-            mag_b[q] = amp_b[j].x;
-        }
-    }
-#endif
     wave_lds_fence();
     // the DCT coefficients this lane will need (up to ten channels per quarter of the wave: 40 channels), requested
     // now -- the transforms' registers are free again -- so that they have arrived when the channel logarithms have
@@ -659,89 +526,7 @@ __global__ __launch_bounds__(64) void mfcc_x2_kernel(const short *__restrict__ p
         mfcc_x2_body<false, PL>(src_a, src_b, fa, fb, two, p, table, feats, lds, lane, redo);
 }
 
-// ---- persistent waves, spectrum in registers ------------------------------------------------------------------------
-// (Round 2, when mfcc_x2_kernel still spent 44 % of its wave cycles in s_waitcnt:) the kernels below keep the tables in
-// registers over a grid-stride loop of frame pairs, request the next pair's samples before this pair's arithmetic, take
-// |X| from registers (frame_io.h: mirror operands by pair_fetch_lds, no natural-order image) and share a filterbank /
-// ln / DCT / lifter tail.  The persistent form stays selectable (JDSP_MFCC512_ONE = 0); production is the pair kernel.
-struct MelPiece { int4 sg; float sw[16], cw[16]; };
-
-__device__ __forceinline__ void load_mel_piece(MelPiece &m, const MfccDev &p, int lane)
-{
-    m.sg = p.seg[lane];
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const float4 a = p.seg_wc[q * 64 + lane];
-        m.sw[2 * q] = a.x; m.cw[2 * q] = a.y; m.sw[2 * q + 1] = a.z; m.cw[2 * q + 1] = a.w;
-    }
-}
-
-// |X| of two frames, bin i at mag[i + (i >> 4)] (see mfcc_x2_kernel) -> feats[fa], feats[fb]
-// Returns whether the pair must be computed again, apart (mfcc_leak_redo; e_pair = sum |z|^2 over both frames).
-__device__ __forceinline__ bool mfcc_tail_x2(const float *mag_a, const float *mag_b, float (*logmel)[64], float (*pieces)[2][64],
-                                             const MfccDev &p, int lane, const MelPiece &mp, long fa, long fb, bool two,
-                                             double *__restrict__ feats, float e_pair)
-{
-    float ta = 0.f, tb = 0.f;
-    {
-        float lo_a = 0.f, hi_a = 0.f, lo_b = 0.f, hi_b = 0.f;
-        float ma[16], mb[16];
-        const int last = p.n_bins - 1;
-#pragma unroll
-        for (int t = 0; t < 16; t++) {                               // all thirty-two reads in flight together
-            const int bin = min(mp.sg.x + t, last);                  // past the piece: a finite value, its weights are 0
-            const int q = bin + (bin >> 4);
-            ma[t] = mag_a[q];
-            mb[t] = mag_b[q];
-        }
-#pragma unroll
-        for (int t = 0; t < 16; t++) {
-            lo_a = fmaf(mp.sw[t], ma[t], lo_a); hi_a = fmaf(mp.cw[t], ma[t], hi_a);   // :164 / :161,:165-166
-            lo_b = fmaf(mp.sw[t], mb[t], lo_b); hi_b = fmaf(mp.cw[t], mb[t], hi_b);
-        }
-        if (p.chan_ok) {
-            if (mp.sg.y <= 0) { lo_a = hi_a = lo_b = hi_b = 0.f; }
-            mel_channel_sums<true>(pieces, logmel, p, lane, lo_a, hi_a, lo_b, hi_b, &ta, &tb);
-        } else {
-            if (mp.sg.y > 0) {
-                if (mp.sg.z >= 1) { atomicAdd(&logmel[0][mp.sg.z - 1], lo_a); atomicAdd(&logmel[1][mp.sg.z - 1], lo_b); }
-                if (mp.sg.z < p.n_chan) { atomicAdd(&logmel[0][mp.sg.z], hi_a); atomicAdd(&logmel[1][mp.sg.z], hi_b); }
-            }
-            wave_lds_fence();
-            if (lane < p.n_chan) {                                   // :171, hardware log2 (see mel_channel_sums)
-                const float sa = logmel[0][lane], sb = logmel[1][lane], w2 = p.chan_w2[lane];
-                logmel[0][lane] = __logf(sa);
-                logmel[1][lane] = __logf(sb);
-                ta = mfcc_leak_term(sa, w2);
-                tb = mfcc_leak_term(sb, w2);
-            }
-            wave_lds_fence();
-        }
-    }
-    // (requesting the DCT coefficients ahead of the filterbank, as mfcc_x2_kernel does, costs this kernel 20 registers
-    // it does not have: 73 spills at three waves per SIMD, 168 us)
-    const bool wide = p.n_cep > 16;                                  // DCT-II (:178-182) and lifter (:189), see mfcc_kernel
-    const int i = wide ? (lane & 31) : (lane & 15), part = wide ? (lane >> 5) : (lane >> 4), step = wide ? 2 : 4;
-    double acc_a = 0.0, acc_b = 0.0;
-    if (i < p.n_cep) {
-#pragma unroll 4
-        for (int k = part; k < p.n_chan; k += step) {
-            const double c = p.dct[k * 32 + i];
-            acc_a += c * (double)logmel[0][k];
-            acc_b += c * (double)logmel[1][k];
-        }
-    }
-    if (!wide) { acc_a = sum_xor16_f64(acc_a); acc_b = sum_xor16_f64(acc_b); }
-    acc_a = sum_xor32_f64(acc_a); acc_b = sum_xor32_f64(acc_b);
-    const double lw = p.lifter_w[lane & 31];
-    if (lane < p.n_cep) {
-        feats[fa * p.n_cep + lane] = acc_a * lw;
-        if (two) feats[fb * p.n_cep + lane] = acc_b * lw;
-    }
-    wave_lds_fence();                                                // logmel and the magnitudes are rewritten next
-    return mfcc_leak_redo(ta, tb, acc_a * lw, acc_b * lw, lane < p.n_cep, e_pair, e_pair, p.leak_k2);
-}
-
+// ---- n_fft = 512: two frames per transform ---------------------------------------------------------------------------
 // previous lane's value (wave_shr:1); lane 0 gets `lane0`
 __device__ __forceinline__ float prev_lane(float v, float lane0, int lane)
 {
@@ -786,9 +571,6 @@ __device__ __forceinline__ float mfcc512_pair_mags(const float (&sa)[8], const f
     return e;
 }
 
-#ifndef JDSP_MFCC512_WAVES
-#define JDSP_MFCC512_WAVES 3
-#endif
 // n_fft = 512 (BASELINE config 4: 400-sample window, 512-FFT): TWO frames per 512-point transform, z[n] = a[n] + j b[n],
 // A[k] = (Z[k] + conj Z[512-k]) / 2, B[k] = -j (Z[k] - conj Z[512-k]) / 2 (the 1/2 is in the window table) -- half the
 // transform work of the zero-padded 1024-point form mfcc_x2_kernel uses for this configuration.  Lane l holds sample
@@ -799,79 +581,15 @@ __device__ __forceinline__ float mfcc512_pair_mags(const float (&sa)[8], const f
 // 10 dB louder -- and the loudest frames of some families next to nobody (a tone, high-pass noise: low channels 90 dB
 // under the peak).  Measured on white, vowel, low-pass, high-pass and tone frames 0-35 dB under a partner
 // (profiles/r10_mfcc_pair_leak.txt): up to 4.0e-4 of the vector's peak with only a whole-frame energy test (pairs
-// more than 36 dB apart), which is what this kernel had.  Now the tail judges every frame where the mel sums and the
+// more than 36 dB apart), which is what the kernel had.  Now the tail judges every frame where the mel sums and the
 // cepstrum exist (mfcc_leak_redo, above, with its bound); a pair with a frame that fails goes onto a list, and
-// mfcc_redo_f64_kernel computes both its frames again, apart and in FP64 (a branch inside this kernel cost 15 % of
+// mfcc_redo_f64_kernel computes both its frames again, apart and in FP64 (a branch inside the kernel cost 15 % of
 // its speed in registers: profiles/r02_mfcc512_run.txt).  At most one entry per pair: the list holds a call's pairs.
-__global__ __launch_bounds__(64, JDSP_MFCC512_WAVES) void mfcc512_run_kernel(const short *__restrict__ pcm, const long long *__restrict__ starts,
-                                                            long n_frames, MfccDev p, const float2 *__restrict__ table,
-                                                            double *__restrict__ feats, int *__restrict__ redo)
-{
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    __shared__ float logmel[2][64];
-    __shared__ float pieces[2][2][64];
-    const int lane = threadIdx.x;
-    const long n_pairs = (n_frames + 1) >> 1;
-    if ((long)blockIdx.x >= n_pairs) return;
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    float win[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) win[r] = reinterpret_cast<const float *>(p.window)[lane + 64 * r];   // zero from win_len on
-    MelPiece mp;
-    load_mel_piece(mp, p, lane);
-    const int rows = (p.win_len + 63) >> 6;                          // register rows that hold samples (wave-uniform)
-    float na[8], nb[8];                                              // the next pair's samples
-    auto fetch = [&](long q) {
-        const long fa = 2 * q, fb = fa + 1 < n_frames ? fa + 1 : fa;
-        const short *sa = pcm + (starts ? starts[fa] : (long long)p.hop * fa) + lane;
-        const short *sb = pcm + (starts ? starts[fb] : (long long)p.hop * fb) + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const bool in = r < rows - 1 || (r == rows - 1 && lane + 64 * r < p.win_len);
-            na[r] = in ? (float)sa[64 * r] : 0.f;
-            nb[r] = in ? (float)sb[64 * r] : 0.f;
-        }
-    };
-    fetch(blockIdx.x);
-    for (long q = blockIdx.x; q < n_pairs; q += gridDim.x) {
-        const long fa = 2 * q;
-        const bool two = fa + 1 < n_frames;
-        const long fb = two ? fa + 1 : fa;                           // odd tail: the second slot repeats the first
-        float sa[8], sb[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) { sa[r] = na[r]; sb[r] = nb[r]; }
-        if (q + gridDim.x < n_pairs) fetch(q + gridDim.x);
-        float ma[4], mb[4];
-        const float e_pair = mfcc512_pair_mags(sa, sb, p.preemph, win, tw, lds, lane, ma, mb);
-        float *mag_a = reinterpret_cast<float *>(lds), *mag_b = mag_a + 320;
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const int k = lane + 64 * d, qk = k + (k >> 4);
-            mag_a[qk] = ma[d];
-            mag_b[qk] = mb[d];
-        }
-        logmel[0][lane] = 0.f;
-        logmel[1][lane] = 0.f;
-        wave_lds_fence();
-        // (|: the tail's ballots are not skipped.)  The odd last frame of a call has no partner: taken as well
-        if ((mfcc_tail_x2(mag_a, mag_b, logmel, pieces, p, lane, mp, fa, fb, two, feats, e_pair) | !two) && lane == 0)
-            redo[1 + atomicAdd(redo, 1)] = (int)q;                   // both frames again, apart (mfcc_redo_f64_kernel)
-    }
-}
-
-// The same pair of frames, ONE pair per wave: nothing is kept between pairs, so the tables are loaded where they are
-// used and die there -- 72 registers instead of 168, seven waves per SIMD instead of three.  Round 2: 53 us per
-// 65,536 frames against the persistent kernel's 78 (profiles/r02_mfcc512_run.txt); round 3, with every load of the
-// wave unguarded and in flight together and the pieces cut to the filterbank: 43 us, the 10,000-utterance batch 2.05 ms
-// (profiles/r03_guarded_loads.txt).
-// JDSP_MFCC512_ONE = 0 selects the persistent kernel.
-#ifndef JDSP_MFCC512_ONE
-#define JDSP_MFCC512_ONE 1
-#endif
-#ifndef JDSP_MFCC512_EARLY_TABLES
-#define JDSP_MFCC512_EARLY_TABLES 0      // 1: 128 registers, four waves per SIMD, 50.5 us per 65,536 frames; 0: 82, five waves, 48.1 us
-#endif
+// ONE pair per wave: nothing is kept between pairs, so the tables are loaded where they are used and die there.  Round 2:
+// 53 us per 65,536 frames against 78 for persistent waves that kept the tables in registers over a grid-stride loop of
+// pairs (72 registers instead of 168, seven waves per SIMD instead of three: profiles/r02_mfcc512_run.txt); round 3, with
+// every load of the wave unguarded and in flight together and the pieces cut to the filterbank: 43 us, the
+// 10,000-utterance batch 2.05 ms (profiles/r03_guarded_loads.txt).
 template <int PL>
 __global__ __launch_bounds__(64) void mfcc512_pair_kernel(const short *__restrict__ pcm, const long long *__restrict__ starts,
                                                           long n_frames, MfccDev p, const float2 *__restrict__ table,
@@ -889,8 +607,9 @@ __global__ __launch_bounds__(64) void mfcc512_pair_kernel(const short *__restric
     const bool two = fa + 1 < n_frames;
     const long fb = two ? fa + 1 : fa;
     // Every load of the wave is requested before the first is waited for, in the order of use: samples, window,
-    // twiddles, then (JDSP_MFCC512_EARLY_TABLES) the filterbank piece and the DCT column, which the tail needs only
-    // after the transform.  The samples are read UNGUARDED at positions clamped into the window -- the window table is
+    // twiddles; the filterbank piece and the DCT column, which the tail needs only after the transform, are requested
+    // after it (ahead of it: 128 registers, four waves per SIMD, 50.5 us per 65,536 frames; so: 82, five waves, 48.1 us).
+    // The samples are read UNGUARDED at positions clamped into the window -- the window table is
     // zero from win_len on, so what a clamped position returns never counts.  (Guarded, each halfword was a branch
     // with an s_waitcnt vmcnt(0) of its own: sixteen memory round trips in series per wave, hidden only by running
     // seven waves per SIMD.)
@@ -913,17 +632,11 @@ __global__ __launch_bounds__(64) void mfcc512_pair_kernel(const short *__restric
     load_wave_twiddles(tw, table, lane);
     MfccLaneTables<PL> mt;
     double dc[10];
-#if JDSP_MFCC512_EARLY_TABLES
-    mfcc_load_lane_tables(mt, p, lane);
-    mfcc_load_dct(dc, p, lane);
-#endif
     const double lw = p.lifter_w[lane & 31];
     float ma[4], mb[4];
     const float e_pair = mfcc512_pair_mags(sa, sb, p.preemph, win, tw, lds, lane, ma, mb);
-#if !JDSP_MFCC512_EARLY_TABLES
     mfcc_load_lane_tables(mt, p, lane);
     mfcc_load_dct(dc, p, lane);
-#endif
     float *mag_a = reinterpret_cast<float *>(lds), *mag_b = mag_a + 320;
 #pragma unroll
     for (int d = 0; d < 4; d++) {
@@ -1019,28 +732,16 @@ int launch_mfcc(hipStream_t s, const short *pcm, const long long *starts, long n
                 const float2 *table, double *feats, int *redo)
 {
     if (n_frames <= 0) return 0;
-#ifndef JDSP_MFCC_X2
-#define JDSP_MFCC_X2 1             // 1: two frames per wavefront in lock-step (mfcc_x2_kernel); 0: one frame per wavefront
-#endif
-#ifndef JDSP_MFCC_RUN
-#define JDSP_MFCC_RUN 1            // 1: persistent register-resident kernels where they apply
-#endif
     // every kernel leaves the frames FP32 could not hold on `redo` (mfcc_leak_one); the FP64 pass computes them again
     if (hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
     int per = 2;
-    if (JDSP_MFCC_RUN && p.seg_ok && p.bin_stride == 2 && p.win_len <= 512) {
+    if (p.seg_ok && p.bin_stride == 2 && p.win_len <= 512) {
         const long n_pairs = (n_frames + 1) / 2;
-        if (JDSP_MFCC512_ONE) {
-            const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8));
-            if (p.piece_len <= 8) hipLaunchKernelGGL(mfcc512_pair_kernel<8>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
-            else if (p.piece_len <= 12) hipLaunchKernelGGL(mfcc512_pair_kernel<12>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
-            else hipLaunchKernelGGL(mfcc512_pair_kernel<16>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
-        } else {
-            const long slots = 1024L * JDSP_MFCC512_WAVES;          // resident waves of a 256-CU part
-            const long grid = n_pairs < slots ? n_pairs : slots;
-            hipLaunchKernelGGL(mfcc512_run_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
-        }
-    } else if (JDSP_MFCC_X2 && p.seg_ok) {
+        const dim3 grid((unsigned)((n_pairs + 7) / 8 * 8));
+        if (p.piece_len <= 8) hipLaunchKernelGGL(mfcc512_pair_kernel<8>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
+        else if (p.piece_len <= 12) hipLaunchKernelGGL(mfcc512_pair_kernel<12>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
+        else hipLaunchKernelGGL(mfcc512_pair_kernel<16>, grid, dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
+    } else if (p.seg_ok) {
         const long grid = ((n_frames + 1) / 2 + 7) / 8 * 8;
         if (p.piece_len <= 8) hipLaunchKernelGGL(mfcc_x2_kernel<8>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);
         else if (p.piece_len <= 12) hipLaunchKernelGGL(mfcc_x2_kernel<12>, dim3((unsigned)grid), dim3(64), 0, s, pcm, starts, n_frames, p, table, feats, redo);

@@ -316,12 +316,7 @@ __global__ __launch_bounds__(64) void mvdr_kernel(const short *__restrict__ left
     wave_fft512<true>(y, lds, lane, tw);
 
     const long first_emit = sh.emit_from;                           // :201-204: the first call's block is dropped
-#if JDSP_MVDR_ABLATE == 3                                   // timing only: one store per lane
-    if (y[0].x + y[3].y + y[5].x + y[7].y == 1.2345f) out[lane] = 1;
-    if (false) {
-#else
     if (j >= first_emit && j < sh.emit_to) {
-#endif
         short *o = out + (j - first_emit) * 512;
         float *pc = precast ? precast + (j - first_emit) * 512 : nullptr;
 #pragma unroll
@@ -351,15 +346,6 @@ __global__ __launch_bounds__(64) void mvdr_kernel(const short *__restrict__ left
 //    values an output pair needs (bins m, 1024 - m, m + 512, 512 - m, each with its own steering phase) are formed
 //    where they are used, the Hermitian parts and the pre-split follow in registers, and only the mirror operands and
 //    Z'[512 - m] cross lanes.
-#ifndef JDSP_MVDR_PAIRS
-#define JDSP_MVDR_PAIRS 1
-#endif
-#ifndef JDSP_MVDR_EARLY_LOADS
-#define JDSP_MVDR_EARLY_LOADS 1
-#endif
-#ifndef JDSP_MVDR_ABLATE
-#define JDSP_MVDR_ABLATE 0      // 1..4: timing-only builds that drop one part of mvdr_pairs_kernel (tools/build_variant.sh)
-#endif
 struct MvdrInv { double i00, i01, i10, i11; };
 
 __device__ __forceinline__ MvdrInv mvdr_inverse(const double *__restrict__ R)     // mxAutoCorr.inverse() (:170)
@@ -460,9 +446,6 @@ __device__ __forceinline__ void mvdr_frame_pairs_direct(const unsigned int (&P)[
     }
 }
 
-#ifndef JDSP_MVDR_DIRECT
-#define JDSP_MVDR_DIRECT 1      // 1: frames from dwords in registers, both forward transforms staggered in one wave, dword output stores
-#endif
 __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict__ left, const short *__restrict__ right,
                                                         long n_blocks, long calls_before,
                                                         const MvdrState *__restrict__ st_in, MvdrState *st_out,
@@ -473,13 +456,8 @@ __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict_
                                                         float *__restrict__ precast, DenoiseShard sh,
                                                         const DenoisePlan *__restrict__ plan, const float4 *__restrict__ wtab)
 {
-#if JDSP_MVDR_DIRECT
     __shared__ __attribute__((aligned(16))) float2 lds2[2][kWaveLdsComplex];
     float2 *lds = lds2[0];
-#else
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    __shared__ __attribute__((aligned(16))) unsigned int stage32[528];
-#endif
     const int lane = threadIdx.x;
     const long per_xcd = (gridDim.x + 7) >> 3;
     const long j = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
@@ -492,7 +470,6 @@ __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict_
     const long jp = have_prev ? j - 1 : -2;          // keep buffer of a stream's very first block: zeros (:130-131)
 
     float2 llo[5], lhi[5], rlo[5], rhi[5], v[8], zr[5];
-#if JDSP_MVDR_DIRECT
     {
         unsigned int lp[4], lc[4], rp[4], rc[4];
         mvdr_load_block32(left, n_blocks, st_in->prev_l, jp, lane, lp);
@@ -523,56 +500,11 @@ __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict_
             rhi[d] = csub(e2, t2);
         }
     }
-#else
-#if JDSP_MVDR_EARLY_LOADS
-    // the right channel's blocks are requested before the left channel's transform (whose LDS fences would hold the loads back)
-    const u32x4 r_prev = mvdr_load_block(right, n_blocks, st_in->prev_r, jp, lane);
-    const u32x4 r_cur = mvdr_load_block(right, n_blocks, st_in->prev_r, j, lane);
-#endif
-    mvdr_frame_pairs(stage32, lane, mvdr_load_block(left, n_blocks, st_in->prev_l, jp, lane),
-                     mvdr_load_block(left, n_blocks, st_in->prev_l, j, lane), v, 0.5f);
-    wave_fft512<false>(v, lds, lane, tw);
-    wave_lds_fence();
-    pair_fetch_lds(v, lds, lane, zr);
-#pragma unroll
-    for (int d = 0; d < 5; d++) {
-        const float2 e = cadd_conj(v[d], zr[d]), o = csub_conj_mj(v[d], zr[d]);
-        const float2 t = cmul(pw.w[d], o);
-        llo[d] = cadd(e, t);
-        lhi[d] = csub(e, t);
-    }
-#if JDSP_MVDR_ABLATE == 2                                   // timing only: no second forward transform
-#pragma unroll
-    for (int d = 0; d < 5; d++) { rlo[d] = lhi[d]; rhi[d] = llo[d]; }
-#else
-#if JDSP_MVDR_EARLY_LOADS
-    mvdr_frame_pairs(stage32, lane, r_prev, r_cur, v, 0.5f);
-#else
-    mvdr_frame_pairs(stage32, lane, mvdr_load_block(right, n_blocks, st_in->prev_r, jp, lane),
-                     mvdr_load_block(right, n_blocks, st_in->prev_r, j, lane), v, 0.5f);
-#endif
-    wave_fft512<false>(v, lds, lane, tw);
-    wave_lds_fence();
-    pair_fetch_lds(v, lds, lane, zr);
-#pragma unroll
-    for (int d = 0; d < 5; d++) {
-        const float2 e = cadd_conj(v[d], zr[d]), o = csub_conj_mj(v[d], zr[d]);
-        const float2 t = cmul(pw.w[d], o);
-        rlo[d] = cadd(e, t);
-        rhi[d] = csub(e, t);
-    }
-#endif
-#endif   // JDSP_MVDR_DIRECT
     // the matrix in effect at this block (looking it up ahead of the transforms instead measured the same)
-#if JDSP_MVDR_ABLATE == 4                                   // timing only: no version lookup
-    int ver = 0;
-    const bool tabled = true;
-#else
     int ver = version_of(ver_base, snap_mask, j + sh.ver_block_off);
     if (sh.ver_row_off) ver -= *sh.ver_row_off;
     if (ver < 0) ver = 0;
     const bool tabled = wtab && mvdr_tabled(plan->n_events, n_blocks);     // wave-uniform
-#endif
     const float4 *wrow = wtab + (size_t)ver * 1024;
     MvdrInv iv = {0.0, 0.0, 0.0, 0.0};
     if (!tabled) iv = mvdr_inverse(rver + (size_t)ver * 4);
@@ -582,11 +514,7 @@ __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict_
         const int m = lane + 64 * d;
         const int b1 = (1024 - m) & 1023, b3 = 512 - m;
         float4 w0, w1, w2, w3;
-#if JDSP_MVDR_ABLATE == 1                                   // timing only: no table loads
-        if (tabled) { w0 = w1 = w2 = w3 = make_float4(0.5f, 0.25f, 0.5f, -0.25f); }
-#else
         if (tabled) { w0 = wrow[m]; w1 = wrow[b1]; w2 = wrow[m + 512]; w3 = wrow[b3]; }
-#endif
         else {
             w0 = mvdr_bin_weights(iv, steer[m]); w1 = mvdr_bin_weights(iv, steer[b1]);
             w2 = mvdr_bin_weights(iv, steer[m + 512]); w3 = mvdr_bin_weights(iv, steer[b3]);
@@ -606,7 +534,6 @@ __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict_
     wave_fft512<true>(y, lds, lane, tw);
 
     const long first_emit = sh.emit_from;                           // :201-204: the first call's block is dropped
-#if JDSP_MVDR_DIRECT
     if (j >= first_emit && j < sh.emit_to) {
         // :193 rgsOutputBuffer[i] = y[i + 511] / 1024: output sample i = n - 511.  Lane l holds y[n], y[n + 1] for n = 2 l + 128 dd;
         // the dword-aligned output pairs are (n odd, n + 1): this lane's .y and the next lane's .x (lane 63: lane 0's next
@@ -628,19 +555,6 @@ __global__ __launch_bounds__(64) void mvdr_pairs_kernel(const short *__restrict_
             }
         }
     }
-#else
-    if (j >= first_emit && j < sh.emit_to) {
-        short *o = out + (j - first_emit) * 512;
-        float *pc = precast ? precast + (j - first_emit) * 512 : nullptr;
-#pragma unroll
-        for (int dd = 0; dd < 8; dd++) {
-            const int i0 = 2 * lane + 128 * dd - 511;                // :193 rgsOutputBuffer[i] = y[i + 511] / 1024
-            const float s0 = y[dd].x * (1.0f / 1024.0f), s1 = y[dd].y * (1.0f / 1024.0f);
-            if (i0 >= 0 && i0 < 512) { o[i0] = (short)cast_i16_bits(s0); if (pc) pc[i0] = s0; }
-            if (i0 + 1 >= 0 && i0 + 1 < 512) { o[i0 + 1] = (short)cast_i16_bits(s1); if (pc) pc[i0 + 1] = s1; }
-        }
-    }
-#endif
     if (j == n_blocks - 1) {
         reinterpret_cast<u32x4 *>(st_out->prev_l)[lane] = reinterpret_cast<const u32x4 *>(left + j * 512)[lane];
         reinterpret_cast<u32x4 *>(st_out->prev_r)[lane] = reinterpret_cast<const u32x4 *>(right + j * 512)[lane];
@@ -674,16 +588,10 @@ int launch_mvdr(hipStream_t s, const short *left, const short *right, long n_blo
     sh.emit_from = calls_before >= 1 ? 0 : 1;
     sh.emit_to = n_blocks;
     const long grid = (n_blocks + 7) / 8 * 8;
-#if JDSP_MVDR_PAIRS
     if (wtab)                                            // wtab: min(blocks + 1, kMvdrTableVersions) x 1024 float4, or NULL (no table)
         hipLaunchKernelGGL(mvdr_weights_kernel, dim3(4096), dim3(256), 0, s, plan, rver, steer, wtab, n_blocks);     // 1,024 versions per pass
     hipLaunchKernelGGL(mvdr_pairs_kernel, dim3((unsigned)grid), dim3(64), 0, s, left, right, n_blocks, calls_before, st_in,
                        st_out, ver_base, snap_mask, rver, steer, table, out, precast, sh, plan, (const float4 *)wtab);
-#else
-    (void)wtab;
-    hipLaunchKernelGGL(mvdr_kernel, dim3((unsigned)grid), dim3(64), 0, s, left, right, n_blocks, calls_before, st_in,
-                       st_out, ver_base, snap_mask, rver, steer, table, out, precast, sh);
-#endif
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -8,7 +8,7 @@
 //   vad_kernel / plan_kernel (denoise_kernels.hip)   as for the 2-microphone path
 //   mvdrn_event_spectra_kernel    X_m[k], k = 0..512, of every estimation frame and microphone
 //   mvdrn_chunk_sums / _prefix / mvdrn_update_kernel   R_k += X X^H / N per event, the weights after each
-//   mvdrn_apply_kernel            one wave per block: n_mics transforms, y = IDFT(w^H X)
+//   mvdrn_apply_pairs_kernel      one wave per block: n_mics transforms, y = IDFT(w^H X)
 #include "frame_io.h"
 #include "jdsp_internal.h"
 
@@ -286,91 +286,10 @@ __global__ __launch_bounds__(64) void mvdrn_update_kernel(const float2 *__restri
     }
 }
 
-__global__ __launch_bounds__(64) void mvdrn_apply_kernel(const short *__restrict__ pcm, long chan_stride, int n_mics,
-                                                         long n_blocks, long calls_before,
-                                                         const short *__restrict__ prev_in, short *__restrict__ prev_out,
-                                                         const int *__restrict__ ver_base,
-                                                         const unsigned long long *__restrict__ snap_mask,
-                                                         const float2 *__restrict__ weights,
-                                                         const float2 *__restrict__ table, short *__restrict__ out,
-                                                         float *__restrict__ precast)
-{
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    __shared__ __attribute__((aligned(16))) unsigned int stage32[520];
-    const int lane = threadIdx.x;
-    const long per_xcd = (gridDim.x + 7) >> 3;
-    const long j = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (j >= n_blocks) return;
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    const float2 wsp[2] = {table[kStftSplit + 2 * lane], table[kStftSplit + 2 * lane + 1]};
-    const bool have_prev = calls_before + j > 0;
-    const float2 *W = weights + (size_t)version_of(ver_base, snap_mask, j) * kMvnBins * 8;
-
-    float2 ylo[8], yhi[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) { ylo[q] = make_float2(0.f, 0.f); yhi[q] = make_float2(0.f, 0.f); }
-    for (int m = 0; m < n_mics; m++) {
-        const short *chan = pcm + (size_t)m * chan_stride;
-        const short *prev = prev_in + (size_t)m * 512;
-        float2 v[8], lo[8], hi[8];
-        mvdr_frame_pairs(stage32, lane, mvn_block(chan, n_blocks, prev, have_prev ? j - 1 : -2, lane),
-                         mvn_block(chan, n_blocks, prev, j, lane), v, 0.5f);
-        mvn_spectrum(v, lds, lane, tw, wsp, lo, hi);
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int bin = 128 * (q >> 1) + 2 * lane + (q & 1);            // 0..511; its partner is bin + 512
-            // Y[k] = sum_m conj(w_k[m]) X_m[k];  for k > 512, w_k = conj(w_{1024-k})
-            const float2 *Wm = W + (size_t)m * kMvnBins;
-            const float2 wl = Wm[bin];
-            ylo[q].x += wl.x * lo[q].x + wl.y * lo[q].y;
-            ylo[q].y += wl.x * lo[q].y - wl.y * lo[q].x;
-            const float2 wh = Wm[512 - bin];                                // bin + 512 mirrors to 512 - bin
-            if (bin == 0) {                                                 // k = 512 itself: not mirrored
-                yhi[q].x += wh.x * hi[q].x + wh.y * hi[q].y;
-                yhi[q].y += wh.x * hi[q].y - wh.y * hi[q].x;
-            } else {
-                yhi[q] = cadd(yhi[q], cmul(wh, hi[q]));
-            }
-        }
-        if (j == n_blocks - 1)
-            reinterpret_cast<u32x4 *>(prev_out + (size_t)m * 512)[lane] = reinterpret_cast<const u32x4 *>(chan + j * 512)[lane];
-    }
-    float2 z[8];
-    z[0] = presplit_inv<0>(ylo[0], yhi[0], wsp[0]); z[1] = presplit_inv<0>(ylo[1], yhi[1], wsp[1]);
-    z[2] = presplit_inv<1>(ylo[2], yhi[2], wsp[0]); z[3] = presplit_inv<1>(ylo[3], yhi[3], wsp[1]);
-    z[4] = presplit_inv<2>(ylo[4], yhi[4], wsp[0]); z[5] = presplit_inv<2>(ylo[5], yhi[5], wsp[1]);
-    z[6] = presplit_inv<3>(ylo[6], yhi[6], wsp[0]); z[7] = presplit_inv<3>(ylo[7], yhi[7], wsp[1]);
-#pragma unroll
-    for (int q = 0; q < 4; q++)
-        *reinterpret_cast<float4 *>(&lds[128 * q + 2 * lane]) = make_float4(z[2 * q].x, z[2 * q].y, z[2 * q + 1].x, z[2 * q + 1].y);
-    wave_lds_fence();
-    float2 y[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) y[r] = lds[lane + 64 * r];
-    wave_lds_fence();
-    wave_fft512<true>(y, lds, lane, tw);
-    const long first_emit = calls_before >= 1 ? 0 : 1;
-    if (j >= first_emit) {
-        short *o = out + (j - first_emit) * 512;
-        float *pc = precast ? precast + (j - first_emit) * 512 : nullptr;
-#pragma unroll
-        for (int dd = 0; dd < 8; dd++) {
-            const int i0 = 2 * lane + 128 * dd - 511;
-            const float s0 = y[dd].x * (1.0f / 1024.0f), s1 = y[dd].y * (1.0f / 1024.0f);
-            if (i0 >= 0 && i0 < 512) { o[i0] = (short)cast_i16_bits(s0); if (pc) pc[i0] = s0; }
-            if (i0 + 1 >= 0 && i0 + 1 < 512) { o[i0 + 1] = (short)cast_i16_bits(s1); if (pc) pc[i0 + 1] = s1; }
-        }
-    }
-}
-
-// The same with pair-owned bins (frame_io.h): lane l works on the bins m, m + 512 of m = l + 64 d, d < 5.  Y[k] =
+// One wave per block, pair-owned bins (frame_io.h): lane l works on the bins m, m + 512 of m = l + 64 d, d < 5.  Y[k] =
 // sum_m conj(w_k[m]) X_m[k] with w_k = conj(w_{1024-k}) above 512 is Hermitian when the X_m are, so the 513 bins the
-// five items cover are all of it: ten weights and ten products per lane and microphone instead of sixteen, and the
-// inverse transform's mirrored inputs come from presplit_inv_pair.
-#ifndef JDSP_MVN_APPLY_PAIRS
-#define JDSP_MVN_APPLY_PAIRS 1
-#endif
+// five items cover are all of it: ten weights and ten products per lane and microphone (sixteen with every bin a lane's
+// own), and the inverse transform's mirrored inputs come from presplit_inv_pair.
 __global__ __launch_bounds__(64) void mvdrn_apply_pairs_kernel(const short *__restrict__ pcm, long chan_stride, int n_mics,
                                                                long n_blocks, long calls_before,
                                                                const short *__restrict__ prev_in, short *__restrict__ prev_out,
@@ -477,20 +396,15 @@ int launch_mvdrn(hipStream_t s, const short *pcm, long chan_stride, int n_mics, 
                        prev_in, events, plan, table, spec);
     launch_mvdrn_update(s, spec, n_mics, kMvnBins, 1.0 / 1024.0, plan, cov_in, cov_out, chunk_ws, chunk_cap, steer, loading, weights);
     const long grid = (n_blocks + 7) / 8 * 8;
-#if JDSP_MVN_APPLY_PAIRS
     hipLaunchKernelGGL(mvdrn_apply_pairs_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, chan_stride, n_mics, n_blocks,
                        calls_before, prev_in, prev_out, ver_base, snap_mask, weights, table, out, precast);
-#else
-    hipLaunchKernelGGL(mvdrn_apply_kernel, dim3((unsigned)grid), dim3(64), 0, s, pcm, chan_stride, n_mics, n_blocks,
-                       calls_before, prev_in, prev_out, ver_base, snap_mask, weights, table, out, precast);
-#endif
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // =======================================================================================
 // FFT_PROCESSING_LEN 512 (BASELINE config 5 as worded: "8-mic array, 512-pt STFT"): blocks of 256 samples, KEEP_LEN
 // 255, frames [first 255 samples of the previous block, block, 0], 257 bins, R_k += X X^H / 512, samples 255..510 out.
-// A 512-sample real frame is half a wave transform, so frames ride it in PAIRS (z = a + j b, see denoise512_kernel):
+// A 512-sample real frame is half a wave transform, so frames ride it in PAIRS (z = a + j b, see denoise512_run_kernel):
 // two MICROPHONES per forward transform, two consecutive BLOCKS per inverse transform.
 constexpr int kMvn512Bins = 257;
 
@@ -571,9 +485,6 @@ __global__ __launch_bounds__(64) void mvdrn512_event_spectra_kernel(const short 
 
 // One wave = two consecutive blocks (j, j+1): per block ceil(n_mics / 2) forward transforms, Y_t[k] = sum_m conj(w_k[m]) X_m[k]
 // for k <= 256; then ONE inverse transform of Y_0 + j Y_1 (both Hermitian) gives the two output frames.
-#ifndef JDSP_MVN512_EARLY_WEIGHTS
-#define JDSP_MVN512_EARLY_WEIGHTS 1
-#endif
 #ifndef JDSP_MVN512_APPLY_WAVES
 #define JDSP_MVN512_APPLY_WAVES 3
 #endif
@@ -648,14 +559,12 @@ __global__ __launch_bounds__(64, JDSP_MVN512_APPLY_WAVES) void mvdrn512_apply_ke
             // this pair's weights, unguarded (a lone last microphone reads its own row twice: its B spectrum is zero)
             const float2 *Wa = W + (size_t)m0 * kMvn512Bins, *Wb = W + (size_t)(two ? m1 : m0) * kMvn512Bins;
             float2 wa[5], wb[5];
-#if JDSP_MVN512_EARLY_WEIGHTS
 #pragma unroll
             for (int q = 0; q < 5; q++) {
                 const int k = q < 4 ? lane + 64 * q : 256;
                 wa[q] = Wa[k];
                 wb[q] = Wb[k];
             }
-#endif
             float xa[8], xb[8];
 #pragma unroll
             for (int r = 0; r < 8; r++) {
@@ -666,14 +575,6 @@ __global__ __launch_bounds__(64, JDSP_MVN512_APPLY_WAVES) void mvdrn512_apply_ke
             if (m0 + 2 < n_mics) fetch(m0 + 2, ra, rb);
             float2 A[5], B[5];
             mvn512_pair_spectra(xa, xb, tw, lds, lane, A, B);
-#if !JDSP_MVN512_EARLY_WEIGHTS
-#pragma unroll
-            for (int q = 0; q < 5; q++) {
-                const int k = q < 4 ? lane + 64 * q : 256;
-                wa[q] = Wa[k];
-                wb[q] = Wb[k];
-            }
-#endif
 #pragma unroll
             for (int q = 0; q < 5; q++) {
                 Y[t][q].x += wa[q].x * A[q].x + wa[q].y * A[q].y;           // conj(w) X

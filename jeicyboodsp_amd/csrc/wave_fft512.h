@@ -185,42 +185,10 @@ __device__ __forceinline__ void load_wave_twiddles(WaveTwiddles &tw, const float
 // is conflict-free on both sides under those two bank maps (MI355X_MICROARCH.md, LDS; found by exhaustive search over
 // separable maps) and stays separable: the writer's lane part is u(k1) + b with the c part as instruction offsets, the
 // reader's is u(k1) + 72 c + (c & 3) with b = 0..7 consecutive -- no per-register address arithmetic on either side.
-#ifndef JDSP_XCHG2_PITCH73
-#define JDSP_XCHG2_PITCH73 0        // 1: rounds 1-2's k1 * 73 + 8 c + b (A/B timing)
-#endif
-#if JDSP_XCHG2_PITCH73
-__device__ __forceinline__ int xchg2_wbase(int lane) { return (lane >> 3) * 73 + (lane & 7); }
-__device__ __forceinline__ int xchg2_rbase(int lane) { return (lane & 7) * 73 + (lane >> 3) * 8; }
-constexpr int xchg2_coff(int c) { return 8 * c; }
-#else
 __device__ __forceinline__ int xchg2_u(int k1) { return 8 * (k1 & 1) + 36 * ((k1 >> 1) & 1) + 16 * (k1 >> 2); }
 __device__ __forceinline__ int xchg2_wbase(int lane) { return xchg2_u(lane >> 3) + (lane & 7); }
 __device__ __forceinline__ int xchg2_rbase(int lane) { const int c = lane >> 3; return xchg2_u(lane & 7) + 72 * c + (c & 3); }
 constexpr int xchg2_coff(int c) { return 72 * c + (c & 3); }
-#endif
-
-// XOR-swizzled second exchange (conflict-free writes and reads).  Measured in steady state, A/B/A/B:
-// the two-transform form gains 3 % with it (MFCC 96 -> 93 us), the one-transform kernels are unchanged or 2-3 %
-// slower (its extra address arithmetic), so each form has its own switch.
-#ifndef JDSP_XCHG2_SWIZZLE
-#define JDSP_XCHG2_SWIZZLE 0
-#endif
-#ifndef JDSP_XCHG2_SWIZZLE_X2
-#define JDSP_XCHG2_SWIZZLE_X2 0      // round 2 had 1 here (against the pitch-73 layout's write conflicts)
-#endif
-// Second exchange, swizzled form: element (k1, c, b) -- written by lane 8 k1 + b from register c, read by lane
-// k1 + 8 c into register b -- lives at 16 (4 c + (k1 >> 1)) + (((2 b) | (k1 & 1)) ^ 2 (k1 >> 1) ^ 8 (c & 1)).
-__device__ __forceinline__ int xchg2_write_base(int lane)
-{
-    const int k1 = lane >> 3, b = lane & 7;
-    return 16 * (k1 >> 1) + (((2 * b) | (k1 & 1)) ^ (2 * (k1 >> 1)));
-}
-__device__ __forceinline__ int xchg2_read_row(int lane) { return 16 * (4 * (lane >> 3) + ((lane & 7) >> 1)); }
-__device__ __forceinline__ int xchg2_read_xor(int lane)
-{
-    const int k1 = lane & 7, c = lane >> 3;
-    return (k1 & 1) ^ (2 * (k1 >> 1)) ^ (8 * (c & 1));
-}
 
 // v[r] = z[lane + 64 r] on entry, Z[lane + 64 d] on exit.  `lds` is this wave's
 // private kWaveLdsComplex-element scratch.  Callers that reuse `lds` afterwards
@@ -243,19 +211,6 @@ __device__ __forceinline__ void wave_fft512(float2 (&v)[8], float2 *lds, int lan
     dft8<INV>(v);
 #pragma unroll
     for (int c = 1; c < 8; c++) v[c] = INV ? cmul_conj(v[c], tw.t2[c - 1]) : cmul(v[c], tw.t2[c - 1]);
-#if JDSP_XCHG2_SWIZZLE
-    {
-        const int wl = xchg2_write_base(lane);
-#pragma unroll
-        for (int c = 0; c < 8; c++) lds[64 * c + ((c & 1) ? (wl ^ 8) : wl)] = v[c];
-    }
-    wave_lds_fence();
-    {
-        const int rm = xchg2_read_row(lane), rx = xchg2_read_xor(lane);
-#pragma unroll
-        for (int b = 0; b < 8; b++) v[b] = lds[rm + ((2 * b) ^ rx)];
-    }
-#else
     {
         const int base = xchg2_wbase(lane);
 #pragma unroll
@@ -267,7 +222,6 @@ __device__ __forceinline__ void wave_fft512(float2 (&v)[8], float2 *lds, int lan
 #pragma unroll
         for (int b = 0; b < 8; b++) v[b] = xchg_ld(lds, base + b);
     }
-#endif
     wave_lds_fence();
     dft8<INV>(v);
 }
@@ -302,27 +256,6 @@ __device__ __forceinline__ void wave_fft512_x2(float2 (&a)[8], float2 (&b)[8], f
         a[c] = INV ? cmul_conj(a[c], tw.t2[c - 1]) : cmul(a[c], tw.t2[c - 1]);
         b[c] = INV ? cmul_conj(b[c], tw.t2[c - 1]) : cmul(b[c], tw.t2[c - 1]);
     }
-#if JDSP_XCHG2_SWIZZLE_X2
-    {
-        const int wl = xchg2_write_base(lane);
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            const int i = 64 * c + ((c & 1) ? (wl ^ 8) : wl);
-            lds_a[i] = a[c];
-            lds_b[i] = b[c];
-        }
-    }
-    wave_lds_fence();
-    {
-        const int rm = xchg2_read_row(lane), rx = xchg2_read_xor(lane);
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int i = rm + ((2 * q) ^ rx);
-            a[q] = lds_a[i];
-            b[q] = lds_b[i];
-        }
-    }
-#else
     {
         const int base = xchg2_wbase(lane);
 #pragma unroll
@@ -334,7 +267,6 @@ __device__ __forceinline__ void wave_fft512_x2(float2 (&a)[8], float2 (&b)[8], f
 #pragma unroll
         for (int q = 0; q < 8; q++) { a[q] = xchg_ld(lds_a, base + q); b[q] = xchg_ld(lds_b, base + q); }
     }
-#endif
     wave_lds_fence();
     dft8<INV>(a);
     dft8<INV>(b);
@@ -346,7 +278,7 @@ __device__ __forceinline__ void wave_fft512_x2(float2 (&a)[8], float2 (&b)[8], f
 // stage behind a: a's exchange (8 writes, 8 reads) is in the LDS pipe while b's radix-8 pass and twiddles issue, and
 // the other way round -- one wave keeps the VALU and the LDS pipe busy together (LDS returns in order, so the wait
 // in front of a's next pass is a counted lgkmcnt that leaves b's exchange outstanding).  Separate scratch per
-// transform; the unswizzled second exchange (its address arithmetic is free).
+// transform.
 template <bool INV> __device__ __forceinline__ void fft512_pass1(float2 (&v)[8], const WaveTwiddles &tw)
 {
     dft8<INV>(v);
