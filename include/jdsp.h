@@ -44,7 +44,7 @@ extern "C" {
  *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added; the time-domain pitch entries
  *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added; the multi-stream IIR equaliser
  *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added;
- *    jdsp_denoise_frames_recomputed added
+ *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -250,6 +250,35 @@ int  jdsp_stftmask_flush_dev(jdsp_stftmask *h, int16_t *out_i16_dev, float *out_
 int  jdsp_stftmask_process(jdsp_stftmask *h, const int16_t *pcm_host, const void *mask_host, long mask_pitch,
                            long n_frames, int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
 int  jdsp_stftmask_flush(jdsp_stftmask *h, int16_t *out_i16_host, float *out_f32_host);  /* host path, synchronous */
+/* A batch of n_utts INDEPENDENT utterances in one launch, with the handle's configuration, windows and gain.  The
+ * two entries neither read nor write the handle's carried tail, so they may be interleaved with _process / _flush of
+ * the handle's own stream.
+ *   - Utterance u has F_u = frame_first[u + 1] - frame_first[u] frames (>= 0).  Its frame f is
+ *     pcm[sample_first[u] + hop f .. + n); its mask row is row frame_first[u] + f of `mask` (the rows of all
+ *     utterances back to back, mask_pitch elements apart; mask_pitch 0: ONE row for every frame of every utterance).
+ *   - Its result is what a fresh handle of the same configuration gives for _process of its F_u frames followed by
+ *     _flush, bit for bit (int16 and float32, for every "frames_per_wave"): hop (F_u - 1) + n samples, the length of
+ *     its PCM span, written at the SAME offset: out[sample_first[u] .. sample_first[u] + hop (F_u - 1) + n).  An
+ *     utterance with F_u = 0 writes nothing, and the device entry touches no sample outside the spans.  Either
+ *     output pointer may be NULL (both: nothing is done).
+ *   - jdsp_stftmask_batch_dev only enqueues on the context's stream: no allocation, no host synchronisation, no host
+ *     read of the two offset arrays (int64, [n_utts] and [n_utts + 1], 8-byte aligned) -- hence n_frames_total, which
+ *     must equal frame_first[n_utts].  The device-side offsets are the caller's contract, as utt_first_dev is for
+ *     jdsp_gmm_score_dev: frame_first[0] = 0 and non-decreasing; every sample_first[u] even (every access stays 4- or
+ *     8-byte aligned); the spans inside pcm and the outputs, and disjoint.  No PCM outside an utterance's span and no
+ *     mask row >= n_frames_total is read.
+ *   - jdsp_stftmask_batch (host pointers, synchronous) checks all of that and returns JDSP_EINVAL with a
+ *     jdsp_last_error text otherwise: frame_first[0] == 0, frame_first non-decreasing, sample_first even, >= 0 and
+ *     ascending with sample_first[u] + span_u <= sample_first[u + 1], the last span <= n_samples.  pcm and the
+ *     outputs are n_samples long; the outputs are ZERO outside the spans.
+ *   - n_utts == 0, n_frames_total == 0 and batches of empty utterances succeed and launch nothing.  n_utts < 0, a
+ *     mask_pitch in 1..n/2 and misaligned base pointers are JDSP_EINVAL, as in jdsp_stftmask_process_dev. */
+int  jdsp_stftmask_batch_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void *mask_dev, long mask_pitch,
+                             const int64_t *sample_first_dev, const int64_t *frame_first_dev, long n_utts,
+                             long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_stftmask_batch(jdsp_stftmask *h, const int16_t *pcm_host, long n_samples, const void *mask_host,
+                         long mask_pitch, const int64_t *sample_first_host, const int64_t *frame_first_host,
+                         long n_utts, int16_t *out_i16_host, float *out_f32_host);        /* host path, synchronous */
 
 /* ---- spectral subtraction / Wiener filter ------------------------------------- */
 /* One jdsp_denoise object holds everything the reference keeps in static locals

@@ -181,6 +181,8 @@ def _load():
         "jdsp_stftmask_flush_dev": (i, [vp, vp, vp]),
         "jdsp_stftmask_process": (i, [vp, vp, vp, l, l, vp, vp]),
         "jdsp_stftmask_flush": (i, [vp, vp, vp]),
+        "jdsp_stftmask_batch_dev": (i, [vp, vp, vp, l, vp, vp, l, l, vp, vp]),
+        "jdsp_stftmask_batch": (i, [vp, vp, l, vp, l, vp, vp, l, vp, vp]),
         "jdsp_gmm_train_create": (i, [vp, i, C.POINTER(vp)]),
         "jdsp_gmm_train_destroy": (i, [vp]),
         "jdsp_gmm_train_reset": (i, [vp]),

@@ -429,6 +429,13 @@ int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_t
 int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask, long pitch,
                     long n_frames, const float *wa, const float *ws, const float *g, const float *tail_in,
                     float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt);
+// n_utts independent streams in one launch, no tail in or out: utterance u is the frames (= mask rows) frame_first[u] ..
+// frame_first[u + 1] - 1 of n_frames_total and reads and writes from sample sample_first[u] (even) of pcm and out on
+// (device arrays, [n_utts] and [n_utts + 1])
+int launch_stftmask_batch(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
+                          long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
+                          long n_utts, const float *wa, const float *ws, const float *g, short *out, float *out_f32,
+                          const float2 *table, int run_opt);
 // mfcc_kernels.hip
 // ---- GMM / HMM (gmm_kernels.hip) ----
 // packed per-GMM record (doubles): alpa[4], mean[4][4], var[4][4], coef[4][4], eig[4][12][4], and for the

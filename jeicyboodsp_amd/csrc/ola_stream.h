@@ -12,7 +12,8 @@
 // so results are bit-identical across both.  A wave whose run starts at frame j0 > 0 recomputes the R - 1 frames
 // before it (the halo: added and shifted, not emitted); only the wave with j0 = 0 reads the tail carried in the handle,
 // and the wave that owns the call's last frame writes the new tail (ping-pong buffers: another wave may still be
-// reading the old one).
+// reading the old one).  stftmask_batch_kernel feeds many independent streams from one launch: a stream that ends
+// inside a wave's run leaves through emit_tail and the next starts after restart, with no tail in memory at all.
 #pragma once
 #include "frame_io.h"
 
@@ -130,6 +131,27 @@ template <class T, int HR> struct OlaAcc {
 #pragma unroll
             for (int d = 0; d < 8 - HR; d++) tl[lane + 64 * d] = acc[d];
         }
+    }
+    // A stream that ends inside the wave (a batch of independent streams, stftmask_batch_kernel): after the shift of
+    // its last frame, the n - hop samples left go out from the registers, to the stream's sample `at` onwards -- the
+    // flush's g[t mod hop] * s[t] (a hop is HR registers, so register d takes g[d % HR]) and emit's casts and stores
+    __device__ __forceinline__ void emit_tail(short *out, float *out_f32, long at, int lane) const
+    {
+        if (out) {
+#pragma unroll
+            for (int d = 0; d < 8 - HR; d++) nt_store_i16(ola_mul(g[d % HR], acc[d]), out + at + kPer * (lane + 64 * d));
+        }
+        if (out_f32) {
+            T *dst = reinterpret_cast<T *>(out_f32 + at) + lane;
+#pragma unroll
+            for (int d = 0; d < 8 - HR; d++) nt_store(ola_mul(g[d % HR], acc[d]), dst + 64 * d);
+        }
+    }
+    // ... and the next stream's sums start from 0, the gain stays
+    __device__ __forceinline__ void restart()
+    {
+#pragma unroll
+        for (int d = 0; d < 8; d++) acc[d] = ola_zero<T>();
     }
 };
 

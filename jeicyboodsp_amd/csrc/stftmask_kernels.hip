@@ -230,4 +230,163 @@ int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const sh
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---- a batch of independent streams (utterances) in one launch (jdsp_stftmask_batch_*) ----------------------------
+// The waves are planned over the CONCATENATED frame axis: wave w owns the global frames [w run, (w + 1) run) whatever
+// the utterances' lengths are, so the plan is plan_ola_run's host arithmetic on the total alone.  Global frame j is
+// mask row j; it belongs to utterance u with frame_first[u] <= j < frame_first[u + 1] and starts at the sample
+// sample_first[u] + hop (j - frame_first[u]) of pcm and out.  A wave finds the utterance of its first frame by a
+// binary search and then walks: its halo stops at the utterance's first frame; after an utterance's last frame it
+// writes the tail from its registers (OlaAcc::emit_tail: no flush launch, no tail in memory), zeroes the sums and
+// reads all eight raw registers at the next non-empty utterance's first sample.  All of this bookkeeping is uniform
+// across the wave: it lives in scalar registers and costs neither vector registers nor LDS.
+struct StftMaskBatchArgs {
+    const short *pcm;
+    const void *mask;
+    long pitch, n_frames;     // n_frames: of all utterances, frame_first[n_utts]
+    const float *wa, *ws, *g; // as StftMaskArgs
+    long n_utts;
+    short *out;               // may be NULL
+    float *out_f32;           // may be NULL
+    int run;
+};
+
+namespace {
+
+// an offset every lane read from the same address, pinned to scalar registers
+__device__ __forceinline__ long uniform_i64(const long long *p)
+{
+    const long long v = *p;
+    const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v);
+    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+    return (long)(((long long)hi << 32) | lo);
+}
+
+}  // namespace
+
+template <int R, int CPX>
+__global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_kernel(
+    StftMaskBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
+    const long long *__restrict__ frame_first)
+{
+    constexpr int HR = 8 / R;
+    constexpr int HOP = 1024 / R;
+    constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    long j0, j1;
+    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
+    // the utterance of frame j0: the last u with frame_first[u] <= j0 (frame_first[0] = 0 <= j0 < frame_first[n_utts]),
+    // which skips the empty ones in front of it
+    long u = 0, ue;
+    {
+        long hi = a.n_utts;
+        while (hi - u > 1) {
+            const long mid = (u + hi) >> 1;
+            if (uniform_i64(frame_first + mid) <= j0) u = mid;
+            else hi = mid;
+        }
+    }
+    const long ub = uniform_i64(frame_first + u);
+    ue = uniform_i64(frame_first + u + 1);
+    // the halo, as in stftmask_run_kernel, but never into the utterance before
+    const long js = j0 - ub < R - 1 ? ub : j0 - (R - 1);
+    long base = uniform_i64(sample_first + u) - ub * HOP;        // global frame j of this utterance starts at base + j HOP
+
+    WaveTwiddles tw;
+    load_wave_twiddles(tw, table, lane);
+    PairTwiddles pw;
+    load_pair_twiddles(pw, table, lane);
+    float2 wa[8], ws[8];
+    {
+        const float2 *wa_t = reinterpret_cast<const float2 *>(a.wa);
+        const float2 *ws_t = reinterpret_cast<const float2 *>(a.ws);
+#pragma unroll
+        for (int d = 0; d < 8; d++) { wa[d] = wa_t[lane + 64 * d]; ws[d] = ws_t[lane + 64 * d]; }
+    }
+    OlaAcc<float2, HR> ola;
+    ola.init(a.g, lane);
+    float2 y[8], o[HR];
+
+    const char *mask = static_cast<const char *>(a.mask);
+    const size_t row_bytes = (size_t)a.pitch * kElem;
+    unsigned int raw[8], nraw[HR];
+    MaskRow<CPX> m, nm;
+    {
+        const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + js * HOP) + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+        mask_load(nm, mask + (size_t)js * row_bytes, lane);
+        mask_prepare(m, nm, lane);
+    }
+    for (long j = js; j < j1; j++) {
+        // the prefetch of stftmask_run_kernel, with the PCM's clamp inside the utterance: after its last frame the
+        // next frame's samples are another span's, read whole below.  The mask rows run on across utterances.
+        const bool last = j + 1 == ue;
+        const long jp = last ? j : j + 1;
+        const long jm = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
+        {
+            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + jp * HOP) + 64 * (8 - HR) + lane;
+#pragma unroll
+            for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
+        }
+        if (a.pitch) mask_load(nm, mask + (size_t)jm * row_bytes, lane);
+        stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, ws, y);
+        ola.add(y, o);
+        // staged before this frame's stores (stftmask_run_kernel)
+#pragma unroll
+        for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
+#pragma unroll
+        for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
+        if (a.pitch) mask_prepare(m, nm, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j >= j0) ola.emit(o, a.out, a.out_f32, base + j * HOP, lane);
+        ola.shift(false, nullptr, lane);
+        if (last) {
+            // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
+            // the last frame emits the tail
+            ola.emit_tail(a.out, a.out_f32, base + (j + 1) * HOP, lane);
+            ola.restart();
+            if (j + 1 < j1) {
+                // frame j + 1 exists, so a non-empty utterance follows
+                const long nb = ue;
+                do {
+                    u++;
+                    ue = uniform_i64(frame_first + u + 1);
+                } while (ue == nb && u + 1 < a.n_utts);
+                base = uniform_i64(sample_first + u) - nb * HOP;
+                const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + nb * HOP) + lane;
+#pragma unroll
+                for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+            }
+        }
+    }
+}
+
+template <int R>
+static void launch_batch_kind(hipStream_t s, int cpx, long grid, const StftMaskBatchArgs &a, const float2 *table,
+                              const long long *sample_first, const long long *frame_first)
+{
+    if (cpx)
+        hipLaunchKernelGGL((stftmask_batch_kernel<R, 1>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
+                           frame_first);
+    else
+        hipLaunchKernelGGL((stftmask_batch_kernel<R, 0>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
+                           frame_first);
+}
+
+int launch_stftmask_batch(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
+                          long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
+                          long n_utts, const float *wa, const float *ws, const float *g, short *out, float *out_f32,
+                          const float2 *table, int run_opt)
+{
+    if (n_frames_total <= 0 || n_utts <= 0) return 0;
+    const int r = 1024 / hop;
+    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_STFTMASK_RESIDENT, r, n_frames_total, run_opt);
+    StftMaskBatchArgs a = {pcm, mask, pitch, n_frames_total, wa, ws, g, n_utts, out, out_f32, (int)p.run};
+    if (r == 1) launch_batch_kind<1>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
+    else if (r == 2) launch_batch_kind<2>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
+    else launch_batch_kind<4>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 }  // namespace jdsp

@@ -1027,6 +1027,52 @@ class StftMask(_OlaStream):
             dev = None
         return self._process(dev, (_vp(pcm), _vp(mask), pitch), n_frames, want_f32, write, out, out_f32)
 
+    def process_batch(self, pcm, mask, utt_sample_first, want_f32=False, out=None, out_f32=None):
+        """A batch of independent utterances in one launch (jdsp_stftmask_batch): each comes out as a fresh stream's
+        process + flush of its frames, bit for bit, and the handle's own stream is neither read nor advanced.
+        pcm: int16 with the utterances packed at the n_utts + 1 even sample offsets utt_sample_first (a host sequence;
+        sharding.stftmask_batch_layout gives each utterance's frame count F_u and first mask row).  mask: float32 or
+        complex64 [sum F_u, pitch >= bins] with contiguous rows, or 1-D [bins]: one row for every frame.  Both torch
+        CUDA (the device entry on torch's current stream) or both numpy (the host entry).  Returns int16 of pcm's
+        length, or (int16, float32) with want_f32: utterance u's hop (F_u - 1) + n_fft samples start at
+        utt_sample_first[u]; what lies outside the spans is zero, or is left as it was in out / out_f32 when given on
+        the device path."""
+        from .sharding import stftmask_batch_layout
+        offs = np.ascontiguousarray(utt_sample_first, np.int64).reshape(-1)
+        counts, frame_first = stftmask_batch_layout(offs, self.n_fft, self.hop)
+        n_utts, n_total, n_samples = counts.size, int(frame_first[-1]), int(pcm.shape[0])
+        assert pcm.ndim == 1 and n_samples >= int(offs[-1])
+        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_total)
+        pitch = mask.shape[1] if mask.ndim == 2 else 0
+        sample_first = np.ascontiguousarray(offs[:-1])
+        if _is_torch(pcm):
+            import torch
+            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
+            dev = pcm.device
+            key = (offs.tobytes(), dev)
+            if getattr(self, "_batch_key", None) != key:        # the offsets of the last batch stay on the device
+                self._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(frame_first).to(dev))
+                self._batch_key = key
+            d_sample, d_frame = self._batch_dev
+            if out is None:
+                out = torch.zeros(max(n_samples, 1), dtype=torch.int16, device=dev)
+            if want_f32 and out_f32 is None:
+                out_f32 = torch.zeros(max(n_samples, 1), dtype=torch.float32, device=dev)
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_stftmask_batch_dev(self._h, _vp(pcm), _vp(mask), pitch, _vp(d_sample), _vp(d_frame),
+                                                   n_utts, n_total, _vp(out), _vp(out_f32) if want_f32 else None))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
+            out = np.zeros(max(n_samples, 1), np.int16) if out is None else out
+            if want_f32 and out_f32 is None:
+                out_f32 = np.zeros(max(n_samples, 1), np.float32)
+            self.eng._ck(L.jdsp_stftmask_batch(self._h, _vp(pcm), n_samples, _vp(mask), pitch, _vp(sample_first),
+                                               _vp(frame_first), n_utts, _vp(out), _vp(out_f32) if want_f32 else None))
+        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+
 
 class GmmTrainer(_Child):
     """GMM training (jdsp_gmm_trainer): GMMAlgorithm_Train_Auto_ver2.cpp's per-class file loop on the device.

@@ -152,6 +152,34 @@ def stftmask_sharded(stftmask, pcm, mask, n_frames, world, rank, want_f32=False)
     return stftmask.process(*part(first, end), want_f32=want_f32)
 
 
+def stftmask_batch_layout(utt_sample_first, n_fft, hop):
+    """A batch of utterances packed at the n_utts + 1 sample offsets utt_sample_first (mfcc_utterance_shard's
+    convention), as jdsp_stftmask_batch frames it: utterance u of L_u = offs[u + 1] - offs[u] samples has
+    F_u = (L_u - n_fft) // hop + 1 frames when L_u >= n_fft, else none; its mask rows start at frame_first[u].
+    Returns (frame_counts [n_utts], frame_first [n_utts + 1]) as numpy int64.  Offsets must be even (the kernel's
+    aligned accesses) and must not decrease: ValueError otherwise."""
+    import numpy as np
+    offs = np.asarray(utt_sample_first, dtype=np.int64).reshape(-1)
+    if offs.size < 1:
+        raise ValueError("utt_sample_first holds n_utts + 1 offsets")
+    if np.any(offs & 1):
+        raise ValueError("utterance offsets must be even")
+    lens = offs[1:] - offs[:-1]
+    if offs[0] < 0 or np.any(lens < 0):
+        raise ValueError("utterance offsets must be >= 0 and must not decrease")
+    counts = np.where(lens >= n_fft, (lens - n_fft) // hop + 1, 0).astype(np.int64)
+    return counts, np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)])
+
+
+def stftmask_batch_shard(frame_counts, rank, world):
+    """Batched fused STFT masking (StftMask.process_batch) over `world` ranks: whole utterances per rank, contiguous,
+    balanced by frame count (utterance_shard); an utterance is a stream of its own, so there is no halo and no
+    collective.  frame_counts: stftmask_batch_layout's.  Returns (first_utt, n_utt): the rank is given the samples
+    utt_sample_first[first_utt] .. utt_sample_first[first_utt + n_utt] and the mask rows
+    frame_first[first_utt] .. frame_first[first_utt + n_utt], with the offsets rebased to its first sample."""
+    return utterance_shard([int(f) for f in frame_counts], rank, world)
+
+
 def fastconv_shard_blocks(n_blocks, hist_blocks, rank, world):
     """Input blocks a rank must be given to produce its share of an overlap-save stream.
     The stream of n_blocks input blocks emits n_blocks - hist_blocks output blocks (the first

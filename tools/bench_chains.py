@@ -81,12 +81,12 @@ def main():
     rng = np.random.default_rng(0)
     out = []
 
-    def report(name, ms, units, unit_name, bytes_per_unit, flops_per_unit, note="", cpu=None):
+    def report(name, ms, units, unit_name, bytes_per_unit, flops_per_unit, note="", cpu=None, inp=None):
         rate = units / (ms * 1e-3)
         gbs = rate * bytes_per_unit / 1e9
         tf = rate * flops_per_unit / 1e12
         line = {"chain": name, "ms": ms, "units": units, "unit": unit_name, "rate_per_s": rate,
-                "input": "re-read from one buffer (cache-resident)" if a.warm else "rotated over 6 copies (from HBM) where the chain's input is a PCM stream",
+                "input": inp or ("re-read from one buffer (cache-resident)" if a.warm else "rotated over 6 copies (from HBM) where the chain's input is a PCM stream"),
                 "algorithmic_GBps": gbs, "hbm_frac": gbs / HBM_PEAK, "fft_TFLOPs": tf, "fp32_vector_frac": tf / FP32_PEAK,
                 "note": note}
         if cpu is not None:
@@ -192,6 +192,60 @@ def main():
                       else "stft full -> torch mul_ -> istft full", ms_u, ms, ms_u / ms))
             ist.close()
             del x, mask, xr, mr, spec, full_mask, o16
+    if on("stftmask_batch"):
+        # Batched fused STFT masking (jdsp_stftmask_batch_dev): 10,000 ragged utterances (seeded, 100..500 frames at hop
+        # 512: the same PCM is 200..1000 frames at hop 256), real mask, timed three ways in this process: (a) the batch
+        # entry, one launch; (b) process + flush per utterance on one handle, 20,000 launches, the C entries called
+        # through ctypes with every pointer computed beforehand; (c) ONE stream of the same total frame count over the
+        # same buffers, the floor.  The PCM (GBs) and the mask rows (more GBs) are far past the 256 MiB Infinity Cache, so
+        # one copy of each already comes from HBM.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        flops = 2 * (5 * 512 * 9 + 512 * 14)
+        lens = 2 * np.random.default_rng(10000).integers((1024 + 99 * 512) // 2, (1024 + 500 * 512) // 2, 10000)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        gen = torch.Generator(device="cuda").manual_seed(10000)
+        x = (torch.randn(int(offs[-1]), device="cuda", generator=gen) * 3000.0).clamp_(-32768, 32767).to(torch.int16)
+        for hop in (512, 256):
+            counts, first = sharding.stftmask_batch_layout(offs, 1024, hop)
+            total = int(first[-1])
+            mask = torch.rand((total, 513), dtype=torch.float32, device="cuda", generator=gen) * 1.5
+            o16 = torch.empty(x.numel(), dtype=torch.int16, device="cuda")
+            sm = eng.stft_mask(n_fft=1024, hop=hop, analysis_window="hann", synthesis_window="hann", normalise=1)
+            nbytes = 2 * hop + 513 * 4 + 2 * hop
+            what = "10,000 ragged utterances, %d frames (%d..%d each), hop %d, real mask" % (total, counts.min(), counts.max(), hop)
+            inp = "one copy: %.1f GB of PCM and %.1f GB of mask rows per call (from HBM)" % (2e-9 * x.numel(), 4e-9 * mask.numel())
+            ms_a = timed(lambda: sm.process_batch(x, mask, offs, out=o16), max(a.iters // 4, 3))
+            ms_c = timed(lambda: sm.process(x, mask, total, out=o16), max(a.iters // 4, 3))
+            sm.flush()
+            # (b): the argument lists of the 10,000 process_dev and flush_dev calls
+            h, px, pm, po = sm._h, x.data_ptr(), mask.data_ptr(), o16.data_ptr()
+            calls = []
+            for u in range(len(counts)):
+                s, f = int(offs[u]), int(counts[u])
+                calls.append(((h, C.c_void_p(px + 2 * s), C.c_void_p(pm + 4 * 513 * int(first[u])), 513, f,
+                               C.c_void_p(po + 2 * s), None), (h, C.c_void_p(po + 2 * (s + hop * f)), None)))
+            eng._use_torch_stream()
+
+            def loop():
+                for p, fl in calls:
+                    L.jdsp_stftmask_process_dev(*p)
+                    L.jdsp_stftmask_flush_dev(*fl)
+
+            ms_b = timed(loop, 1, rounds=3, spin_ms=0.0)
+            report("stftmask_batch_1024_hop%d_real" % hop, ms_a, total, "frames", nbytes, flops,
+                   "(a) jdsp_stftmask_batch_dev, one launch: %s; %.2f x the single stream (c), %.3f of the per-utterance "
+                   "loop (b)" % (what, ms_a / ms_c, ms_a / ms_b), inp=inp)
+            report("stftmask_batch_1024_hop%d_real_per_utterance_loop" % hop, ms_b, total, "frames", nbytes, flops,
+                   "(b) the same batch as 10,000 x (jdsp_stftmask_process_dev + jdsp_stftmask_flush_dev) on one handle, "
+                   "from ctypes with precomputed arguments: %.1f x the batch entry" % (ms_b / ms_a), inp=inp)
+            report("stftmask_batch_1024_hop%d_real_single_stream" % hop, ms_c, total, "frames", nbytes, flops,
+                   "(c) the floor: ONE stream of the same %d frames over the same buffers, one jdsp_stftmask_process_dev" % total,
+                   inp=inp)
+            sm.close()
+            del mask, o16
+        del x
     if on("denoise"):
         x = pcm_of(rng, B * 512)
         x[:12 * 512] = pcm_of(rng, 12 * 512, 45.0)          # the estimate latches at block 10
