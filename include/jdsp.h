@@ -44,7 +44,8 @@ extern "C" {
  *    the GMM training entries jdsp_gmm_train_* and jdsp_gmm_param_from_train added; the time-domain pitch entries
  *    jdsp_pitch_lag* (AMDF, autocorrelation) and the LPC entries jdsp_lpc* added; the multi-stream IIR equaliser
  *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added;
- *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added
+ *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added; the ragged-batch
+ *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -77,7 +78,8 @@ const char *jdsp_last_error(const jdsp_ctx *ctx);   /* ctx may be NULL: global c
 int jdsp_set_stream(jdsp_ctx *ctx, void *hip_stream);
 int jdsp_use_own_stream(jdsp_ctx *ctx);
 /* Tuning knobs, by name; unknown names return JDSP_EINVAL.
- *   "stft.frames_per_wave"  consecutive frames one wavefront owns (0 = auto)
+ *   "stft.frames_per_wave"  consecutive frames one wavefront owns (0 = auto); for jdsp_stft_half_batch* the run of
+ *                           global frames one wavefront walks across utterances (0 = 4).  Results are identical.
  *   "stft.read_pass"        -1 (default, auto) / 0 / 1: before the hop-512 transform of a large batch, one
  *                           read-only launch streams the PCM into the 256 MiB Infinity Cache, slab by slab, so
  *                           that HBM sees a read stream and then a write stream instead of their 1 : 8 mix
@@ -148,6 +150,34 @@ int jdsp_stft_i16_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames,
 int jdsp_stft_half_i16_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames, jdsp_c32 *spec_dev, long row_pitch);
 int jdsp_stft_i16(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples,
                   int n_fft, int hop, jdsp_c32 *spec_host, long *n_frames_out);
+/* Half spectra of a batch of n_utts RAGGED utterances in one launch: the layout of jdsp_stftmask_batch_dev (below), so
+ * the rows line up with its mask rows and with jdsp_istft_batch_dev's spectrum rows.  n_fft 1024; hop 1024, 512 or 256;
+ * window by "stft.window".
+ *   - Utterance u has F_u = frame_first[u + 1] - frame_first[u] frames (>= 0); its frame f is
+ *     pcm[sample_first[u] + hop f .. + 1024) and goes to row frame_first[u] + f of `spec`, row_pitch complex64 apart,
+ *     bins 0..512.
+ *   - That row equals row f, bins 0..512, of jdsp_stft_i16_dev(pcm + sample_first[u], F_u, 1024, hop) on the utterance
+ *     alone, BIT FOR BIT, wherever the utterance sits in the batch and for every "stft.frames_per_wave".
+ *   - row_pitch must be EVEN and >= 514: every row then starts on a 16-byte boundary and takes the arithmetic of the
+ *     full-spectrum entry.  (Dense rows of 513 remain jdsp_stft_half_i16_dev's layout: its odd rows factorise their
+ *     twiddles differently and equal the full spectrum only to rounding.)  spec must be 16-byte, pcm 4-byte and the
+ *     offset arrays 8-byte aligned; anything else, another hop, n_utts < 0 or n_frames_total < 0 is JDSP_EINVAL with a
+ *     jdsp_last_error text, and nothing is launched.
+ *   - Elements 513..row_pitch-1 of a row and rows >= n_frames_total are not written; no sample outside an utterance's
+ *     span [sample_first[u], sample_first[u] + hop (F_u - 1) + 1024) is read.
+ *   - jdsp_stft_half_batch_dev only enqueues on the context's stream and never reads the offset arrays on the host
+ *     (int64, [n_utts] and [n_utts + 1]) -- hence n_frames_total, which must equal frame_first[n_utts].  The offsets
+ *     are the caller's contract, the one of jdsp_stftmask_batch_dev: frame_first[0] = 0 and non-decreasing,
+ *     sample_first even, the spans disjoint and inside pcm.
+ *   - jdsp_stft_half_batch (host pointers, synchronous) checks all of that as jdsp_stftmask_batch does (pcm is
+ *     n_samples long) and writes bins 0..512 of rows 0..frame_first[n_utts]-1 of spec_host.
+ *   - n_utts == 0, n_frames_total == 0 and batches of empty utterances succeed and launch nothing. */
+int jdsp_stft_half_batch_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, const int64_t *sample_first_dev,
+                             const int64_t *frame_first_dev, long n_utts, long n_frames_total, int hop,
+                             jdsp_c32 *spec_dev, long row_pitch);
+int jdsp_stft_half_batch(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
+                         const int64_t *frame_first_host, long n_utts, int hop, jdsp_c32 *spec_host,
+                         long row_pitch);                                                /* host path, synchronous */
 /* The same analysis in the reference's own precision (SS:218-230 computes in double): FP64 window, FP64 transform,
  * spec = n_frames x 1024 interleaved (re, im) doubles (16,384 B per frame).  n_fft = 1024, any hop >= 1.  Agrees with
  * the reference's FFTProcess on the same windowed frames to ~1e-11 of the frame peak (FFTProcess's truncated PI,
@@ -203,6 +233,31 @@ int  jdsp_istft_flush_dev(jdsp_istft *h, int16_t *out_i16_dev, float *out_f32_de
 int  jdsp_istft_process(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, long n_frames,
                         int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
 int  jdsp_istft_flush(jdsp_istft *h, int16_t *out_i16_host, float *out_f32_host);   /* host path, synchronous */
+/* A batch of n_utts INDEPENDENT utterances in one launch, with the handle's configuration (every n_fft, hop, layout
+ * and window combination create accepts), windows, gain and "frames_per_wave".  The layout is the one of
+ * jdsp_stftmask_batch_dev (below), with spectrum rows where that has mask rows.  The two entries neither read nor
+ * write the handle's carried tail, so they may be interleaved with _process / _flush of the handle's own stream.
+ *   - Utterance u has F_u = frame_first[u + 1] - frame_first[u] frames (>= 0); its frame f is row frame_first[u] + f of
+ *     `spec` (the rows of all utterances back to back, row_pitch complex64 apart).
+ *   - Its result is what a fresh handle of the same configuration gives for _process of its F_u rows followed by
+ *     _flush, bit for bit (int16 and float32, for every "frames_per_wave"): hop (F_u - 1) + n samples, written at
+ *     out[sample_first[u] .. sample_first[u] + hop (F_u - 1) + n).  An utterance with F_u = 0 writes nothing, and the
+ *     device entry touches no sample outside the spans.  Either output pointer may be NULL (both: nothing is done).
+ *   - jdsp_istft_batch_dev only enqueues on the stream _process_dev uses: no allocation, no host synchronisation, no
+ *     host read of the two offset arrays (int64, [n_utts] and [n_utts + 1], 8-byte aligned) -- hence n_frames_total,
+ *     which must equal frame_first[n_utts].  The device-side offsets are the caller's contract: frame_first[0] = 0 and
+ *     non-decreasing; every sample_first[u] even (for both frame sizes: one layout contract, although n = 512 would
+ *     not need it); the spans inside the outputs, and disjoint.  No row >= n_frames_total is read.  row_pitch and the
+ *     alignment of spec and the outputs are _process_dev's.
+ *   - jdsp_istft_batch (host pointers, synchronous) checks all of that as jdsp_stftmask_batch does and returns
+ *     JDSP_EINVAL with a jdsp_last_error text otherwise.  The outputs are n_samples long and ZERO outside the spans.
+ *   - n_utts == 0, n_frames_total == 0 and batches of empty utterances succeed and launch nothing. */
+int  jdsp_istft_batch_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitch, const int64_t *sample_first_dev,
+                          const int64_t *frame_first_dev, long n_utts, long n_frames_total, int16_t *out_i16_dev,
+                          float *out_f32_dev);
+int  jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, const int64_t *sample_first_host,
+                      const int64_t *frame_first_host, long n_utts, long n_samples, int16_t *out_i16_host,
+                      float *out_f32_host);                                               /* host path, synchronous */
 
 /* ---- fused STFT masking: PCM -> analysis -> per-bin mask -> synthesis -> PCM ------- */
 /* jdsp_stft_* followed by a multiplication of the spectrum and jdsp_istft_*, as ONE pass in which the spectrum never

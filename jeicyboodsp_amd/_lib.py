@@ -160,6 +160,8 @@ def _load():
         "jdsp_mvdrn_process": (i, [vp, vp, l, l, vp, vp, C.POINTER(l)]),
         "jdsp_stft_half_i16_dev": (i, [vp, vp, l, vp, l]),
         "jdsp_stft_i16_dev": (i, [vp, vp, l, i, i, vp]),
+        "jdsp_stft_half_batch_dev": (i, [vp, vp, vp, vp, l, l, i, vp, l]),
+        "jdsp_stft_half_batch": (i, [vp, vp, l, vp, vp, l, i, vp, l]),
         "jdsp_stft_i16": (i, [vp, vp, l, i, i, vp, C.POINTER(l)]),
         "jdsp_stft_i16_f64_dev": (i, [vp, vp, l, i, i, vp]),
         "jdsp_stft_i16_f64": (i, [vp, vp, l, i, i, vp, C.POINTER(l)]),
@@ -172,6 +174,8 @@ def _load():
         "jdsp_istft_flush_dev": (i, [vp, vp, vp]),
         "jdsp_istft_process": (i, [vp, vp, l, l, vp, vp]),
         "jdsp_istft_flush": (i, [vp, vp, vp]),
+        "jdsp_istft_batch_dev": (i, [vp, vp, l, vp, vp, l, l, vp, vp]),
+        "jdsp_istft_batch": (i, [vp, vp, l, vp, vp, l, l, vp, vp]),
         "jdsp_stftmask_create": (i, [vp, vp, C.POINTER(vp)]),
         "jdsp_stftmask_destroy": (i, [vp]),
         "jdsp_stftmask_reset": (i, [vp]),

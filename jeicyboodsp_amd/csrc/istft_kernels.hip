@@ -10,8 +10,10 @@
 //   n = 512   one 512-point complex inverse of H per frame, real part kept.  Never two frames in one transform: a
 //             frame's result must not depend on its neighbour, or on where a call or shard cut falls.
 // The halo frames run through an unrolled loop of their own in front of the run: they need no prefetch and no stores.
+// istft_batch_kernel, at the end, runs the same frame for a batch of ragged utterances (ragged_batch.h).
 #include "jdsp_internal.h"
 #include "ola_stream.h"
+#include "ragged_batch.h"
 
 namespace jdsp {
 
@@ -235,6 +237,126 @@ int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_t
     if (n_tail <= 0 || (!out && !out_f32)) return 0;
     hipLaunchKernelGGL(istft_flush_kernel, dim3((unsigned)((n_tail + 255) / 256)), dim3(256), 0, s, tail, g, n_tail, hop,
                        out, out_f32);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- a batch of independent streams (utterances) in one launch (jdsp_istft_batch_*) --------------------------------
+// istft_run_kernel's frame under the walk of ragged_batch.h (the layout of stftmask_batch_kernel): the waves are planned
+// over the concatenated frame axis, global frame j is spectrum row j.  The halo of a wave stops at its utterance's
+// first frame, so it is 0..R-1 frames long and goes through the one loop, without the stores; the rows are prefetched
+// one frame ahead, on across utterances (a row belongs to no span).  After an utterance's last frame the tail leaves
+// from the registers (OlaAcc::emit_tail) and the sums restart: no tail in memory, no flush launch, and the handle's
+// own tail is neither read nor written.
+struct IstftBatchArgs {
+    const float2 *spec;
+    long pitch, n_frames;     // n_frames: of all utterances, frame_first[n_utts]
+    long n_utts;
+    const float *ws, *g;      // as IstftArgs
+    short *out;               // may be NULL
+    float *out_f32;           // may be NULL
+    int run;
+};
+
+template <int N, int HALF, int R>
+__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_batch_kernel(
+    IstftBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
+    const long long *__restrict__ frame_first)
+{
+    typedef typename IstftSample<N>::T T;
+    constexpr int HR = 8 / R;
+    constexpr int HOP = N / R;
+    constexpr int kL = IstftLoad<N, HALF>::kLoads;
+    constexpr int kImg = HALF ? N / 2 + 1 : N + 1;               // istft_run_kernel's LDS, no more
+    __shared__ __attribute__((aligned(16))) float2 lds[kImg + 1 + kWaveLdsComplex];
+    float2 *const img = lds;
+    float2 *const scratch = lds + ((kImg + 1) & ~1);
+    const int lane = threadIdx.x;
+    long j0, j1;
+    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
+    long u = ragged_find_utt(frame_first, a.n_utts, j0);        // the utterance of frame j0
+    const long ub = uniform_i64(frame_first + u);
+    long ue = uniform_i64(frame_first + u + 1);
+    // the halo, as in istft_run_kernel, but never into the utterance before
+    const long js = j0 - ub < R - 1 ? ub : j0 - (R - 1);
+    long base = uniform_i64(sample_first + u) - ub * HOP;        // global frame j of this utterance starts at base + j HOP
+
+    WaveTwiddles tw;
+    load_wave_twiddles(tw, table, lane);
+    SplitTwiddles sw;
+    if (N == 1024) load_split_twiddles(sw, table, lane);
+    T ws[8];
+    const T *ws_t = reinterpret_cast<const T *>(a.ws);
+#pragma unroll
+    for (int d = 0; d < 8; d++) ws[d] = ws_t[lane + 64 * d];
+
+    OlaAcc<T, HR> ola;
+    ola.init(a.g, lane);
+    T y[8], o[HR];
+    float2 nx[kL], nnyq = make_float2(0.f, 0.f);
+
+    istft_load<N, HALF>(a.spec + js * a.pitch, lane, nx, nnyq);
+    istft_stage<N, HALF>(nx, nnyq, img, lane);
+    wave_lds_fence();
+    for (long j = js; j < j1; j++) {
+        // the next row, staged one frame from now: an unguarded load at a clamped frame (past the wave's run it is
+        // never used)
+        const long jn = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
+        istft_load<N, HALF>(a.spec + jn * a.pitch, lane, nx, nnyq);
+        istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
+        ola.add(y, o);
+        // staged before this frame's stores (istft_run_kernel); the image's reads are behind istft_frame's fence
+        istft_stage<N, HALF>(nx, nnyq, img, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j >= j0) ola.emit(o, a.out, a.out_f32, base + j * HOP, lane);
+        ola.shift(false, nullptr, lane);
+        if (j + 1 == ue) {
+            // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
+            // the last frame emits the tail
+            ola.emit_tail(a.out, a.out_f32, base + (j + 1) * HOP, lane);
+            ola.restart();
+            if (j + 1 < j1) {
+                // frame j + 1 exists, so a non-empty utterance follows
+                const long nb = ue;
+                ragged_next_utt(frame_first, a.n_utts, u, ue);
+                base = uniform_i64(sample_first + u) - nb * HOP;
+            }
+        }
+        wave_lds_fence();                                        // the staged row before the next frame reads it
+    }
+}
+
+template <int N, int HALF, int R>
+static void launch_batch_run(hipStream_t s, long grid, const IstftBatchArgs &a, const float2 *table,
+                             const long long *sample_first, const long long *frame_first)
+{
+    hipLaunchKernelGGL((istft_batch_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
+                       frame_first);
+}
+
+template <int N, int HALF>
+static void launch_batch_r(hipStream_t s, int r, long grid, const IstftBatchArgs &a, const float2 *table,
+                           const long long *sample_first, const long long *frame_first)
+{
+    if (r == 1) launch_batch_run<N, HALF, 1>(s, grid, a, table, sample_first, frame_first);
+    else if (r == 2) launch_batch_run<N, HALF, 2>(s, grid, a, table, sample_first, frame_first);
+    else launch_batch_run<N, HALF, 4>(s, grid, a, table, sample_first, frame_first);
+}
+
+int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
+                       long n_frames_total, const long long *sample_first, const long long *frame_first, long n_utts,
+                       const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt)
+{
+    if (n_frames_total <= 0 || n_utts <= 0) return 0;
+    const int r = n_fft / hop;
+    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, n_frames_total, run_opt);
+    IstftBatchArgs a = {spec, pitch, n_frames_total, n_utts, ws, g, out, out_f32, (int)p.run};
+    if (n_fft == 1024) {
+        if (half) launch_batch_r<1024, 1>(s, r, p.grid, a, table, sample_first, frame_first);
+        else launch_batch_r<1024, 0>(s, r, p.grid, a, table, sample_first, frame_first);
+    } else {
+        if (half) launch_batch_r<512, 1>(s, r, p.grid, a, table, sample_first, frame_first);
+        else launch_batch_r<512, 0>(s, r, p.grid, a, table, sample_first, frame_first);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

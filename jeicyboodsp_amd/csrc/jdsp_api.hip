@@ -422,6 +422,39 @@ int jdsp_stft_half_i16_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, long n_frames,
     return JDSP_OK;
 }
 
+static const char kStftBatchPitch[] =
+    "jdsp_stft_half_batch: row_pitch must be even and >= 514 (every row 16-byte aligned: the even-row store)";
+
+int jdsp_stft_half_batch_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, const int64_t *sample_first_dev,
+                             const int64_t *frame_first_dev, long n_utts, long n_frames_total, int hop, jdsp_c32 *spec_dev,
+                             long row_pitch)
+{
+    if (!ctx) return JDSP_EINVAL;
+    if (n_utts < 0 || n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: n_utts or n_frames_total < 0");
+    if (hop != 1024 && hop != 512 && hop != 256)
+        return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: hop must be 1024, 512 or 256 (n_fft, n_fft/2 or n_fft/4)");
+    if (row_pitch < 514 || (row_pitch & 1)) return fail(ctx, JDSP_EINVAL, kStftBatchPitch);
+    if (((uintptr_t)pcm_dev & 3u) || ((uintptr_t)spec_dev & 15u) || ((uintptr_t)sample_first_dev & 7u) ||
+        ((uintptr_t)frame_first_dev & 7u))
+        return fail(ctx, JDSP_EINVAL,
+                    "jdsp_stft_half_batch: pcm must be 4-byte, spec 16-byte and the offset arrays 8-byte aligned");
+    if (n_utts == 0 || n_frames_total == 0) return JDSP_OK;
+    if (!pcm_dev || !spec_dev || !sample_first_dev || !frame_first_dev)
+        return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: pcm, spec, sample_first or frame_first is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = jdsp::ensure_stft1024_table(ctx);
+    if (rc) return rc;
+    const int wk = ctx->opt_stft_window;                        // "stft.window", as jdsp_stft_i16_dev
+    if (wk == 1 && (rc = jdsp::ensure_stft1024_table_of(ctx, ctx->stft1024_table_hann, 1))) return rc;
+    const float2 *tab = wk == 1 ? ctx->stft1024_table_hann.get() : ctx->stft1024_table.get();
+    if (jdsp::launch_stft_half_batch(ctx->stream, hop, ctx->opt_stft_fpw, pcm_dev,
+                                     reinterpret_cast<const long long *>(sample_first_dev),
+                                     reinterpret_cast<const long long *>(frame_first_dev), n_utts, n_frames_total,
+                                     (float2 *)spec_dev, row_pitch, tab))
+        return fail(ctx, JDSP_EHIP, "jdsp_stft_half_batch: launch", hipGetLastError());
+    return JDSP_OK;
+}
+
 static bool is_pinned_host(const void *p)
 {
     hipPointerAttribute_t a;
@@ -553,6 +586,50 @@ int jdsp_stft_i16(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, int n_
     jdsp_c32 *d_out = hc.alloc<jdsp_c32>(out_bytes);
     if (hc.ok()) hc.result(jdsp_stft_i16_dev(ctx, d_in, n_frames, n_fft, hop, d_out));
     hc.download(spec_host, d_out, out_bytes);
+    return hc.finish();
+}
+
+int jdsp_stft_half_batch(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
+                         const int64_t *frame_first_host, long n_utts, int hop, jdsp_c32 *spec_host, long row_pitch)
+{
+    if (!ctx) return JDSP_EINVAL;
+    const long n = 1024;
+    if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: n_utts or n_samples < 0");
+    if (hop != 1024 && hop != 512 && hop != 256)
+        return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: hop must be 1024, 512 or 256 (n_fft, n_fft/2 or n_fft/4)");
+    if (row_pitch < 514 || (row_pitch & 1)) return fail(ctx, JDSP_EINVAL, kStftBatchPitch);
+    if (n_utts > 0 && (!sample_first_host || !frame_first_host))
+        return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: sample_first or frame_first is NULL");
+    // everything the kernel takes on trust from device-side offsets is checked here (as jdsp_stftmask_batch)
+    if (n_utts > 0 && frame_first_host[0] != 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: frame_first[0] must be 0");
+    long end = 0;                                              // one past the last sample of the spans so far
+    for (long u = 0; u < n_utts; u++) {
+        const long f = frame_first_host[u + 1] - frame_first_host[u], s = sample_first_host[u];
+        if (f < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: frame_first must not decrease");
+        if (s < 0 || (s & 1)) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: sample_first entries must be even and >= 0");
+        if (s < end)
+            return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: sample_first must ascend and the utterances' spans must not overlap");
+        if (s > n_samples || (f > 0 && (n_samples - s < n || f - 1 > (n_samples - s - n) / hop)))
+            return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: an utterance's span ends past n_samples");
+        end = f > 0 ? s + hop * (f - 1) + n : s;
+    }
+    const long n_total = n_utts > 0 ? frame_first_host[n_utts] : 0;
+    if (n_total == 0) return JDSP_OK;
+    if (!pcm_host || !spec_host) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: pcm or spec is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    jdsp::HostCall hc(ctx, "jdsp_stft_half_batch");
+    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));  // nothing past the last span is read
+    const int64_t *d_sample = hc.upload(sample_first_host, (size_t)n_utts * sizeof(int64_t));
+    const int64_t *d_frame = hc.upload(frame_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    jdsp_c32 *d_spec = hc.alloc<jdsp_c32>(((size_t)(n_total - 1) * row_pitch + 513) * sizeof(jdsp_c32));
+    if (hc.ok()) hc.result(jdsp_stft_half_batch_dev(ctx, d_pcm, d_sample, d_frame, n_utts, n_total, hop, d_spec, row_pitch));
+    if (hc.ok()) {
+        // the 513 bins of every row: what lies between the rows on the host stays as it is
+        const hipError_t e = hipMemcpy2DAsync(spec_host, (size_t)row_pitch * sizeof(jdsp_c32), d_spec,
+                                              (size_t)row_pitch * sizeof(jdsp_c32), 513 * sizeof(jdsp_c32), (size_t)n_total,
+                                              hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) hc.result(fail(ctx, JDSP_EHIP, "jdsp_stft_half_batch: D2H", e));
+    }
     return hc.finish();
 }
 

@@ -300,6 +300,11 @@ int launch_stft1024_half(hipStream_t stream, const short *pcm, long n_frames, fl
 int launch_stft512(hipStream_t stream, int n_cu, const short *pcm, long n_frames, long hop, float2 *spec,
                    const float2 *table, const float2 *win512);
 void fill_win512(float2 *w, int window_kind);
+// bins 0..512 of every frame of n_utts ragged utterances in one launch (the layout of launch_stftmask_batch): global
+// frame j is the row spec + j pitch (pitch even); hop 1024 | 512 | 256; run_opt 0 = auto
+int launch_stft_half_batch(hipStream_t s, int hop, int run_opt, const short *pcm, const long long *sample_first,
+                           const long long *frame_first, long n_utts, long n_frames_total, float2 *spec, long pitch,
+                           const float2 *table);
 
 // fft_c2c_kernels.hip
 int launch_bitrev_table(hipStream_t stream, short *table_dev, int n_fft, int bits);
@@ -423,6 +428,11 @@ int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const fl
                  const float *ws, const float *g, const float *tail_in, float *tail_out, short *out, float *out_f32,
                  const float2 *table, int run_opt);
 int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32);
+// n_utts independent streams in one launch, no tail in or out: the layout of launch_stftmask_batch with spectrum rows
+// where that has mask rows
+int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
+                       long n_frames_total, const long long *sample_first, const long long *frame_first, long n_utts,
+                       const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt);
 // stftmask_kernels.hip (n_fft 1024)
 // mask: rows of float or float2 (complex_mask), pitch elements apart (0: one row); wa: [1024] analysis window / 2;
 // ws: [1024] synthesis window; g: [hop] emission gain; tails: [1024 - hop] floats; run_opt 0 = auto

@@ -20,6 +20,8 @@
 //     92 -> 88 us, and PCM over-fetch disappears.
 #include "frame_io.h"
 #include "jdsp_internal.h"
+#include "ola_stream.h"
+#include "ragged_batch.h"
 
 namespace jdsp {
 
@@ -281,6 +283,111 @@ int launch_stft1024_half(hipStream_t stream, const short *pcm, long n_frames, fl
     const long grid = ((n_frames + 1) / 2 + 7) / 8 * 8;
     hipLaunchKernelGGL(stft1024_hop512_half_kernel<2>, dim3((unsigned)grid), dim3(64), 0, stream, pcm, spec, n_frames,
                        pitch, table);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ---- half spectrum of a batch of ragged utterances in one launch (jdsp_stft_half_batch_*) -----------------------
+// The layout and the walk are ragged_batch.h's, the ones stftmask_batch_kernel uses: wave w owns the global frames
+// [w run, (w + 1) run) of the concatenated frame axis (ola_run_range: the plan is arithmetic on the total alone), global
+// frame j is spectrum row j and starts at the sample sample_first[u] + hop (j - frame_first[u]) of its utterance u.
+// The PCM goes through stftmask_batch_kernel's register pipeline: raw[8] holds the frame's sample pairs, the next
+// frame's new hop (HR = 8 / R registers) is prefetched into nraw -- clamped inside the utterance, so no sample outside
+// a span is read -- and the registers shift down by a hop; at a new span all eight are read again.  An analysis frame
+// depends on no other frame, so there is no halo.
+// Every row takes the EVEN-row store (split_store_half<false>): the pitch is even, so every row is 16-byte aligned.
+// That is the arithmetic of the full-spectrum kernels' split (split_fwd<J> with t.wsp, bin 512 = hi0 of lane 0), so
+// row j equals bins 0..512 of jdsp_stft_i16_dev on the utterance alone bit for bit; the odd-row store of the dense-513
+// layout factorises its twiddles differently and equals it only to rounding, and is never used here.
+struct StftBatchArgs {
+    const short *pcm;
+    float2 *spec;
+    long pitch, n_frames;     // pitch in elements, even; n_frames: of all utterances, frame_first[n_utts]
+    long n_utts;
+    int run;
+};
+
+#ifndef JDSP_STFT_BATCH_RUN
+#define JDSP_STFT_BATCH_RUN 4     // frames per wave when "stft.frames_per_wave" is 0: short waves, as the single-stream
+#endif                            // kernels (a wave's next PCM wait also waits for its spectrum stores, see above)
+
+template <int R>
+__global__ __launch_bounds__(64, JDSP_STFT_MINWAVES) void stft_half_batch_kernel(
+    StftBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
+    const long long *__restrict__ frame_first)
+{
+    constexpr int HR = 8 / R;                                   // registers per hop
+    constexpr int HOP = 1024 / R;
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    long j0, j1;
+    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
+    long u = ragged_find_utt(frame_first, a.n_utts, j0);
+    long ue = uniform_i64(frame_first + u + 1);
+    long base = uniform_i64(sample_first + u) - uniform_i64(frame_first + u) * HOP;   // frame j starts at base + j HOP
+
+    unsigned int raw[8], nraw[HR];
+    {
+        const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + j0 * HOP) + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+    }
+    FrameTables t;
+    load_frame_tables(t, table, lane);
+    for (long j = j0; j < j1; j++) {
+        // frame j + 1's new hop, inside the utterance: after its last frame the next samples are another span's
+        const bool last = j + 1 == ue;
+        const long jp = last ? j : j + 1;
+        {
+            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + jp * HOP) + 64 * (8 - HR) + lane;
+#pragma unroll
+            for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
+        }
+        float2 v[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const float2 s = unpack_i16x2(raw[r]);
+            v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
+        }
+        wave_fft512<false>(v, lds, lane, t.tw);
+        store_natural_image(lds, lane, v);
+        wave_lds_fence();
+        // staged before this frame's stores: a wait for the prefetch behind them would wait for the stores too
+#pragma unroll
+        for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
+#pragma unroll
+        for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
+        __builtin_amdgcn_sched_barrier(0);
+        split_store_half<false>(lds, lane, t.wsp, a.spec + j * a.pitch);
+        wave_lds_fence();
+        if (last && j + 1 < j1) {
+            // frame j + 1 exists, so a non-empty utterance follows: all eight registers at its first sample
+            const long nb = ue;
+            ragged_next_utt(frame_first, a.n_utts, u, ue);
+            base = uniform_i64(sample_first + u) - nb * HOP;
+            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + nb * HOP) + lane;
+#pragma unroll
+            for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+        }
+    }
+}
+
+// run_opt: "stft.frames_per_wave" (0 = JDSP_STFT_BATCH_RUN)
+int launch_stft_half_batch(hipStream_t s, int hop, int run_opt, const short *pcm, const long long *sample_first,
+                           const long long *frame_first, long n_utts, long n_frames_total, float2 *spec, long pitch,
+                           const float2 *table)
+{
+    if (n_frames_total <= 0 || n_utts <= 0) return 0;
+    const long run = run_opt > 0 ? run_opt : JDSP_STFT_BATCH_RUN;
+    const long waves = (n_frames_total + run - 1) / run;
+    const long grid = (waves + 7) / 8 * 8;                       // whole rounds of the eight XCDs (ola_run_range)
+    StftBatchArgs a = {pcm, spec, pitch, n_frames_total, n_utts, (int)run};
+    const int r = 1024 / hop;
+    if (r == 1)
+        hipLaunchKernelGGL(stft_half_batch_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first, frame_first);
+    else if (r == 2)
+        hipLaunchKernelGGL(stft_half_batch_kernel<2>, dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first, frame_first);
+    else
+        hipLaunchKernelGGL(stft_half_batch_kernel<4>, dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first, frame_first);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -23,6 +23,7 @@
 // plus the R - 1 halo frames.
 #include "jdsp_internal.h"
 #include "ola_stream.h"
+#include "ragged_batch.h"
 
 namespace jdsp {
 
@@ -237,8 +238,8 @@ int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const sh
 // sample_first[u] + hop (j - frame_first[u]) of pcm and out.  A wave finds the utterance of its first frame by a
 // binary search and then walks: its halo stops at the utterance's first frame; after an utterance's last frame it
 // writes the tail from its registers (OlaAcc::emit_tail: no flush launch, no tail in memory), zeroes the sums and
-// reads all eight raw registers at the next non-empty utterance's first sample.  All of this bookkeeping is uniform
-// across the wave: it lives in scalar registers and costs neither vector registers nor LDS.
+// reads all eight raw registers at the next non-empty utterance's first sample.  The search and the step from one
+// utterance to the next are ragged_batch.h's, shared with the analysis and synthesis batch kernels.
 struct StftMaskBatchArgs {
     const short *pcm;
     const void *mask;
@@ -249,19 +250,6 @@ struct StftMaskBatchArgs {
     float *out_f32;           // may be NULL
     int run;
 };
-
-namespace {
-
-// an offset every lane read from the same address, pinned to scalar registers
-__device__ __forceinline__ long uniform_i64(const long long *p)
-{
-    const long long v = *p;
-    const unsigned int lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v);
-    const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-    return (long)(((long long)hi << 32) | lo);
-}
-
-}  // namespace
 
 template <int R, int CPX>
 __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_kernel(
@@ -275,19 +263,9 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     const int lane = threadIdx.x;
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
-    // the utterance of frame j0: the last u with frame_first[u] <= j0 (frame_first[0] = 0 <= j0 < frame_first[n_utts]),
-    // which skips the empty ones in front of it
-    long u = 0, ue;
-    {
-        long hi = a.n_utts;
-        while (hi - u > 1) {
-            const long mid = (u + hi) >> 1;
-            if (uniform_i64(frame_first + mid) <= j0) u = mid;
-            else hi = mid;
-        }
-    }
+    long u = ragged_find_utt(frame_first, a.n_utts, j0);       // the utterance of frame j0 (ragged_batch.h)
     const long ub = uniform_i64(frame_first + u);
-    ue = uniform_i64(frame_first + u + 1);
+    long ue = uniform_i64(frame_first + u + 1);
     // the halo, as in stftmask_run_kernel, but never into the utterance before
     const long js = j0 - ub < R - 1 ? ub : j0 - (R - 1);
     long base = uniform_i64(sample_first + u) - ub * HOP;        // global frame j of this utterance starts at base + j HOP
@@ -349,10 +327,7 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
             if (j + 1 < j1) {
                 // frame j + 1 exists, so a non-empty utterance follows
                 const long nb = ue;
-                do {
-                    u++;
-                    ue = uniform_i64(frame_first + u + 1);
-                } while (ue == nb && u + 1 < a.n_utts);
+                ragged_next_utt(frame_first, a.n_utts, u, ue);
                 base = uniform_i64(sample_first + u) - nb * HOP;
                 const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + nb * HOP) + lane;
 #pragma unroll

@@ -287,6 +287,45 @@ class Engine(_Handle):
                                           pitch))
         return out
 
+    def stft_half_batch(self, pcm, utt_sample_first, hop=512, pitch=520, out=None):
+        """Bins 0..512 of every frame of a batch of ragged utterances in one launch (jdsp_stft_half_batch): pcm is
+        int16 with the utterances packed at the n_utts + 1 even sample offsets utt_sample_first (a host sequence;
+        sharding.stftmask_batch_layout gives each utterance's frame count F_u and first row).  Returns complex64
+        [sum F_u, pitch]: row frame_first[u] + f equals Engine.stft(pcm_u, F_u, 1024, hop)[f, :513] bit for bit;
+        columns past 512 are untouched.  pitch must be even and >= 514.  hop 1024, 512 or 256; window by
+        "stft.window".  torch CUDA input (the device entry on torch's current stream) or numpy (the host entry)."""
+        from .sharding import stftmask_batch_layout
+        offs = np.ascontiguousarray(utt_sample_first, np.int64).reshape(-1)
+        counts, frame_first = stftmask_batch_layout(offs, 1024, hop)
+        n_utts, n_total, n_samples = counts.size, int(frame_first[-1]), int(pcm.shape[0])
+        assert pcm.ndim == 1 and n_samples >= int(offs[-1])
+        sample_first = np.ascontiguousarray(offs[:-1])
+        if _is_torch(pcm):
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            dev = pcm.device
+            key = (offs.tobytes(), hop, dev)
+            if getattr(self, "_stft_batch_key", None) != key:   # the offsets of the last batch stay on the device
+                self._stft_batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(frame_first).to(dev))
+                self._stft_batch_key = key
+            d_sample, d_frame = self._stft_batch_dev
+            if out is None:
+                out = torch.empty((n_total, pitch), dtype=torch.complex64, device=dev)
+            assert out.is_cuda and out.dtype == torch.complex64 and out.is_contiguous()
+            assert out.ndim == 2 and out.shape[0] >= n_total and out.shape[1] == pitch
+            self._use_torch_stream()
+            self._ck(L.jdsp_stft_half_batch_dev(self._h, _vp(pcm), _vp(d_sample), _vp(d_frame), n_utts, n_total, int(hop),
+                                                _vp(out), int(pitch)))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            if out is None:
+                out = np.zeros((n_total, pitch), np.complex64)
+            assert out.dtype == np.complex64 and out.flags.c_contiguous
+            assert out.ndim == 2 and out.shape[0] >= n_total and out.shape[1] == pitch
+            self._ck(L.jdsp_stft_half_batch(self._h, _vp(pcm), n_samples, _vp(sample_first), _vp(frame_first), n_utts,
+                                            int(hop), _vp(out), int(pitch)))
+        return out[:n_total]
+
     # ---- STFT analysis (SS:218-230 / WF:181-193 for a whole batch) ---------
     def stft(self, pcm, n_frames=None, n_fft=1024, hop=512, out=None):
         """pcm: int16 numpy array (host path) or torch CUDA int16 tensor (device path).
@@ -984,6 +1023,51 @@ class Istft(_OlaStream):
             spec = np.ascontiguousarray(spec, np.complex64)
             dev = None
         return self._process(dev, (_vp(spec), pitch), n_frames, want_f32, write, out, out_f32)
+
+    def process_batch(self, spec, frame_counts, utt_sample_first=None, want_f32=False, out=None, out_f32=None):
+        """A batch of independent utterances in one launch (jdsp_istft_batch): each comes out as a fresh stream's
+        process + flush of its rows, bit for bit, and the handle's own stream is neither read nor advanced.
+        spec: complex64 [sum F_u, row_pitch >= bins] with contiguous rows, the rows of all utterances back to back
+        (Engine.stft_half_batch's output for the half layout); frame_counts: F_u >= 0 per utterance (a host sequence).
+        utt_sample_first: the n_utts + 1 even sample offsets of the output spans (utterance u's hop (F_u - 1) + n_fft
+        samples start at utt_sample_first[u] and must end at or before utt_sample_first[u + 1]); None packs the spans
+        back to back (sharding.istft_batch_layout).  torch CUDA (the device entry on torch's current stream) or numpy
+        (the host entry).  Returns int16 of utt_sample_first[-1] samples, or (int16, float32) with want_f32; what lies
+        outside the spans is zero, or is left as it was in out / out_f32 when given on the device path."""
+        from .sharding import istft_batch_layout
+        counts = np.ascontiguousarray(frame_counts, np.int64).reshape(-1)
+        packed, frame_first = istft_batch_layout(counts, self.n_fft, self.hop)
+        offs = packed if utt_sample_first is None else np.ascontiguousarray(utt_sample_first, np.int64).reshape(-1)
+        assert offs.size == counts.size + 1 and not np.any(offs & 1)
+        assert np.all(offs[:-1] + (packed[1:] - packed[:-1]) <= offs[1:]), "an utterance's span ends past the next offset"
+        n_utts, n_total, n_samples = counts.size, int(frame_first[-1]), int(offs[-1])
+        pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
+        assert spec.ndim == 2 and spec.shape[0] >= n_total and pitch >= self.bins
+        sample_first = np.ascontiguousarray(offs[:-1])
+        if _is_torch(spec):
+            import torch
+            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
+            dev = spec.device
+            key = (offs.tobytes(), counts.tobytes(), dev)
+            if getattr(self, "_batch_key", None) != key:        # the offsets of the last batch stay on the device
+                self._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(frame_first).to(dev))
+                self._batch_key = key
+            d_sample, d_frame = self._batch_dev
+            if out is None:
+                out = torch.zeros(max(n_samples, 1), dtype=torch.int16, device=dev)
+            if want_f32 and out_f32 is None:
+                out_f32 = torch.zeros(max(n_samples, 1), dtype=torch.float32, device=dev)
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_istft_batch_dev(self._h, _vp(spec), pitch, _vp(d_sample), _vp(d_frame), n_utts, n_total,
+                                                _vp(out), _vp(out_f32) if want_f32 else None))
+        else:
+            spec = np.ascontiguousarray(spec, np.complex64)
+            out = np.zeros(max(n_samples, 1), np.int16) if out is None else out
+            if want_f32 and out_f32 is None:
+                out_f32 = np.zeros(max(n_samples, 1), np.float32)
+            self.eng._ck(L.jdsp_istft_batch(self._h, _vp(spec), pitch, _vp(sample_first), _vp(frame_first), n_utts,
+                                            n_samples, _vp(out), _vp(out_f32) if want_f32 else None))
+        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
 
 
 class StftMask(_OlaStream):

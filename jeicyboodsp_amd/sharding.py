@@ -171,12 +171,33 @@ def stftmask_batch_layout(utt_sample_first, n_fft, hop):
     return counts, np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)])
 
 
+def istft_batch_layout(frame_counts, n_fft, hop):
+    """The back-to-back packing of a batch of synthesis outputs (Istft.process_batch without utt_sample_first):
+    utterance u of F_u = frame_counts[u] >= 0 spectrum rows comes out as hop (F_u - 1) + n_fft samples (none when
+    F_u = 0), and the spans follow each other without a gap.  Returns (utt_sample_first [n_utts + 1],
+    frame_first [n_utts + 1]) as numpy int64; the offsets are even by construction (n_fft and hop are), and
+    stftmask_batch_layout(utt_sample_first, n_fft, hop) gives frame_counts and frame_first back.  Negative counts:
+    ValueError."""
+    import numpy as np
+    counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
+    if np.any(counts < 0):
+        raise ValueError("frame counts must be >= 0")
+    if n_fft % 2 or hop % 2:
+        raise ValueError("n_fft and hop must be even")
+    spans = np.where(counts > 0, hop * (counts - 1) + n_fft, 0).astype(np.int64)
+    zero = np.zeros(1, np.int64)
+    return (np.concatenate([zero, np.cumsum(spans, dtype=np.int64)]),
+            np.concatenate([zero, np.cumsum(counts, dtype=np.int64)]))
+
+
 def stftmask_batch_shard(frame_counts, rank, world):
     """Batched fused STFT masking (StftMask.process_batch) over `world` ranks: whole utterances per rank, contiguous,
     balanced by frame count (utterance_shard); an utterance is a stream of its own, so there is no halo and no
     collective.  frame_counts: stftmask_batch_layout's.  Returns (first_utt, n_utt): the rank is given the samples
     utt_sample_first[first_utt] .. utt_sample_first[first_utt + n_utt] and the mask rows
-    frame_first[first_utt] .. frame_first[first_utt + n_utt], with the offsets rebased to its first sample."""
+    frame_first[first_utt] .. frame_first[first_utt + n_utt], with the offsets rebased to its first sample.
+    The batched analysis and synthesis (Engine.stft_half_batch, Istft.process_batch) share the layout and are split by
+    this same function: their spectrum rows take the place of the mask rows."""
     return utterance_shard([int(f) for f in frame_counts], rank, world)
 
 

@@ -51,6 +51,31 @@ def timed(fn, iters, rounds=5, spin_ms=60.0):
     return statistics.median(ts)
 
 
+def timed_alternated(fns, iters, rounds=5, spin_ms=60.0):
+    """timed() for several callables in ONE sequence of alternated rounds: every round times each of them in turn
+    (iters[i] back-to-back calls of fns[i]), so a drift of the clocks or of the box falls on all of them alike.
+    Returns their medians."""
+    import time
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    while (time.perf_counter() - t0) * 1e3 < spin_ms:
+        fns[0]()
+        torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters[i]):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            ts[i].append(a.elapsed_time(b) / iters[i])
+    return [statistics.median(t) for t in ts]
+
+
 def cpu_rate(fn, units):
     """units/s of the CPU oracle (FP64, one thread, structured like the reference) on a bounded sample."""
     import time
@@ -245,6 +270,101 @@ def main():
                    inp=inp)
             sm.close()
             del mask, o16
+        del x
+    if on("stft_half_batch") or on("istft_batch"):
+        # The analysis and synthesis ends of the ragged-batch pipeline (jdsp_stft_half_batch_dev, jdsp_istft_batch_dev) on
+        # the stftmask_batch leg's 10,000 seeded utterances, half layout, pitch 520, Hann / Hann.  Each is timed three ways
+        # in this process, in alternated rounds: (a) the batch entry, one launch; (b) the per-utterance loop on the
+        # single-stream _dev entries, the C entries called through ctypes with every pointer computed beforehand; (c) ONE
+        # stream of the same total frame count over the same buffers.  Analysis (b) is jdsp_stft_i16_dev per utterance,
+        # the entry the batch rows are bit-identical to, into the utterance's rows of a full-spectrum tensor (the
+        # half-spectrum single-stream entry wants 16-byte aligned PCM, which an utterance at an even offset is not);
+        # analysis (c) is jdsp_stft_half_i16_dev at hop 512 and, at hop 256 where there is no half-spectrum single-stream
+        # entry, jdsp_stft_i16_dev, which writes 8,192 B per frame against the batch entry's 4,104.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        lens = 2 * np.random.default_rng(10000).integers((1024 + 99 * 512) // 2, (1024 + 500 * 512) // 2, 10000)
+        offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        gen = torch.Generator(device="cuda").manual_seed(10000)
+        x = (torch.randn(int(offs[-1]), device="cuda", generator=gen) * 3000.0).clamp_(-32768, 32767).to(torch.int16)
+        it = max(a.iters // 4, 3)
+        eng.set_option("stft.window", 1)
+        for hop in (512, 256):
+            counts, first = sharding.stftmask_batch_layout(offs, 1024, hop)
+            total = int(first[-1])
+            spec = torch.empty((total, 520), dtype=torch.complex64, device="cuda")
+            what = "10,000 ragged utterances, %d frames (%d..%d each), hop %d, pitch 520" % (total, counts.min(), counts.max(), hop)
+            eng.stft_half_batch(x, offs, hop=hop, pitch=520, out=spec)        # the synthesis leg's input
+            if on("stft_half_batch"):
+                flops = 5 * 512 * 9 + 512 * 14
+                nbytes = 2 * hop + 513 * 8
+                inp = "one copy: %.1f GB of PCM (from HBM), %.1f GB of spectra out" % (2e-9 * x.numel(), 8e-9 * spec.numel())
+                full = torch.empty((total, 1024), dtype=torch.complex64, device="cuda")
+                h, px, pf = eng._h, x.data_ptr(), full.data_ptr()
+                calls = [(h, C.c_void_p(px + 2 * int(offs[u])), int(counts[u]), 1024, hop, C.c_void_p(pf + 8192 * int(first[u])))
+                         for u in range(len(counts))]
+                eng._use_torch_stream()
+
+                def loop():
+                    for p in calls:
+                        L.jdsp_stft_i16_dev(*p)
+
+                batch = lambda: eng.stft_half_batch(x, offs, hop=hop, pitch=520, out=spec)  # noqa: E731
+                if hop == 512:
+                    stream, c_what = (lambda: eng.stft_half(x, total, out=spec, pitch=520)), "one jdsp_stft_half_i16_dev, pitch 520"
+                else:
+                    stream, c_what = (lambda: eng.stft(x, total, 1024, hop, out=full)), \
+                        "one jdsp_stft_i16_dev (all 1024 bins: 8,192 B per frame written)"
+                ms_a, ms_c, ms_b = timed_alternated([batch, stream, loop], [it, it, 1], rounds=3)
+                report("stft_half_batch_1024_hop%d" % hop, ms_a, total, "frames", nbytes, flops,
+                       "(a) jdsp_stft_half_batch_dev, one launch: %s; %.2f x the single stream (c), %.3f of the "
+                       "per-utterance loop (b)" % (what, ms_a / ms_c, ms_a / ms_b), inp=inp)
+                report("stft_half_batch_1024_hop%d_per_utterance_loop" % hop, ms_b, total, "frames", 2 * hop + 8192, flops,
+                       "(b) the same batch as 10,000 x jdsp_stft_i16_dev (all 1024 bins), from ctypes with precomputed "
+                       "arguments: %.1f x the batch entry" % (ms_b / ms_a), inp=inp)
+                report("stft_half_batch_1024_hop%d_single_stream" % hop, ms_c, total, "frames",
+                       nbytes if hop == 512 else 2 * hop + 8192, flops,
+                       "(c) ONE stream of the same %d frames over the same PCM: %s" % (total, c_what), inp=inp)
+                del full, calls
+                eng.stft_half_batch(x, offs, hop=hop, pitch=520, out=spec)    # (c) wrote other rows over it
+            if on("istft_batch"):
+                flops = 5 * 512 * 9 + 512 * 14
+                nbytes = 513 * 8 + 2 * hop
+                inp = "one copy: %.1f GB of spectra per call (from HBM), %.1f GB of PCM out" % (8e-9 * spec.numel(), 2e-9 * x.numel())
+                o16 = torch.empty(x.numel(), dtype=torch.int16, device="cuda")
+                ist = eng.istft(n_fft=1024, hop=hop, layout="half", synthesis_window="hann", analysis_window="hann")
+                h, ps, po = ist._h, spec.data_ptr(), o16.data_ptr()
+                calls = []
+                for u in range(len(counts)):
+                    s, f = int(offs[u]), int(counts[u])
+                    calls.append(((h, C.c_void_p(ps + 8 * 520 * int(first[u])), 520, f, C.c_void_p(po + 2 * s), None),
+                                  (h, C.c_void_p(po + 2 * (s + hop * f)), None)))
+                eng._use_torch_stream()
+
+                def loop():
+                    for p, fl in calls:
+                        L.jdsp_istft_process_dev(*p)
+                        L.jdsp_istft_flush_dev(*fl)
+
+                def stream():
+                    ist.process(spec, n_frames=total, out=o16)
+
+                ms_a, ms_c, ms_b = timed_alternated([lambda: ist.process_batch(spec, counts, offs, out=o16), stream, loop],
+                                                    [it, it, 1], rounds=3)
+                ist.flush()
+                report("istft_batch_1024_hop%d_half" % hop, ms_a, total, "frames", nbytes, flops,
+                       "(a) jdsp_istft_batch_dev, one launch: %s; %.2f x the single stream (c), %.3f of the per-utterance "
+                       "loop (b)" % (what, ms_a / ms_c, ms_a / ms_b), inp=inp)
+                report("istft_batch_1024_hop%d_half_per_utterance_loop" % hop, ms_b, total, "frames", nbytes, flops,
+                       "(b) the same batch as 10,000 x (jdsp_istft_process_dev + jdsp_istft_flush_dev) on one handle, from "
+                       "ctypes with precomputed arguments: %.1f x the batch entry" % (ms_b / ms_a), inp=inp)
+                report("istft_batch_1024_hop%d_half_single_stream" % hop, ms_c, total, "frames", nbytes, flops,
+                       "(c) ONE stream of the same %d frames over the same buffers, one jdsp_istft_process_dev" % total, inp=inp)
+                ist.close()
+                del o16, calls
+            del spec
+        eng.set_option("stft.window", 0)
         del x
     if on("denoise"):
         x = pcm_of(rng, B * 512)
