@@ -181,6 +181,7 @@ def _load():
         "jdsp_stftmask_reset": (i, [vp]),
         "jdsp_stftmask_set_option": (i, [vp, C.c_char_p, l]),
         "jdsp_stftmask_samples_out": (l, [vp, l]),
+        "jdsp_stftmask_frames_recomputed": (l, [vp]),
         "jdsp_stftmask_process_dev": (i, [vp, vp, vp, l, l, vp, vp]),
         "jdsp_stftmask_flush_dev": (i, [vp, vp, vp]),
         "jdsp_stftmask_process": (i, [vp, vp, vp, l, l, vp, vp]),

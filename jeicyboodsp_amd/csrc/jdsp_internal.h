@@ -435,17 +435,22 @@ int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, co
                        const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt);
 // stftmask_kernels.hip (n_fft 1024)
 // mask: rows of float or float2 (complex_mask), pitch elements apart (0: one row); wa: [1024] analysis window / 2;
-// ws: [1024] synthesis window; g: [hop] emission gain; tails: [1024 - hop] floats; run_opt 0 = auto
+// ws: [1024] synthesis window; g: [hop] emission gain; tails: [1024 - hop] floats; run_opt 0 = auto.  For the frames
+// FP32 cannot hold (stftmask_unsafe) -- f64: [3072] the analysis window, the synthesis window (both unrounded) and
+// exp(-2 pi i t / 1024), t < 512, as (re, im) pairs; count: two words, the emitted ones among them are added to
+// count[epoch & 1] and the other is zeroed for the next call (epoch: the host's number of the call)
 int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask, long pitch,
                     long n_frames, const float *wa, const float *ws, const float *g, const float *tail_in,
-                    float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt);
+                    float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
+                    unsigned int *count, unsigned int epoch);
 // n_utts independent streams in one launch, no tail in or out: utterance u is the frames (= mask rows) frame_first[u] ..
 // frame_first[u + 1] - 1 of n_frames_total and reads and writes from sample sample_first[u] (even) of pcm and out on
 // (device arrays, [n_utts] and [n_utts + 1])
 int launch_stftmask_batch(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
                           long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
                           long n_utts, const float *wa, const float *ws, const float *g, short *out, float *out_f32,
-                          const float2 *table, int run_opt);
+                          const float2 *table, int run_opt, const double *f64, unsigned int *count,
+                          unsigned int epoch);
 // mfcc_kernels.hip
 // ---- GMM / HMM (gmm_kernels.hip) ----
 // packed per-GMM record (doubles): alpa[4], mean[4][4], var[4][4], coef[4][4], eig[4][12][4], and for the

@@ -13,6 +13,20 @@ struct jdsp_stftmask {
     // the host entry's device copies of its inputs, grown on demand
     jdsp::DevBuf<int16_t> h_pcm;
     jdsp::DevBuf<char> h_mask;            // bytes: rows of float or jdsp_c32
+    // the FP64 pass over the frames FP32 cannot hold (stftmask_kernels.hip, stftmask_frame_f64), sized at create
+    jdsp::DevBuf<double> f64;             // w_a[n], w_s[n], exp(-2 pi i t / n) for t < n/2 as (re, im)
+    // count[epoch & 1]: the recomputed frames of the call with that number (jdsp_stftmask_frames_recomputed); every
+    // call's kernel zeroes the other word for the call after it, so nothing is enqueued to zero one
+    jdsp::DevBuf<unsigned int> count;
+    unsigned int epoch = 0;
+    int count_valid = 0;                  // the last call launched (under `epoch`) since create / reset
+
+    unsigned int next_epoch()
+    {
+        ++epoch;
+        count_valid = 1;
+        return epoch;
+    }
 };
 
 static constexpr int kBins = 513;         // n/2 + 1 of the one supported n_fft
@@ -51,7 +65,20 @@ int jdsp_stftmask_create(jdsp_ctx *ctx, const jdsp_stftmask_cfg *cfg, jdsp_stftm
     if (!h) return fail(ctx, JDSP_ENOMEM, "jdsp_stftmask_create");
     h->ctx = ctx;
     h->cfg = c;
+    std::vector<double> host64(3 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        host64[i] = OlaStream::window_at(c.analysis_window, i, n);
+        host64[(size_t)n + i] = OlaStream::window_at(c.synthesis_window, i, n);
+    }
+    for (int t = 0; t < n / 2; t++) {
+        const double a = -2.0 * 3.14159265358979323846 * t / n;
+        host64[2 * (size_t)n + 2 * t] = cos(a);
+        host64[2 * (size_t)n + 2 * t + 1] = sin(a);
+    }
     hipError_t e = h->blob.alloc(2 * (size_t)n + OlaStream::floats(n, hop));
+    if (e == hipSuccess) e = h->f64.upload(host64.data(), host64.size());
+    const unsigned int zero[2] = {0, 0};
+    if (e == hipSuccess) e = h->count.upload(zero, 2);
     if (e == hipSuccess) {
         h->wa = h->blob.get();
         h->ws = h->wa + n;
@@ -78,7 +105,24 @@ int jdsp_stftmask_destroy(jdsp_stftmask *h)
     return JDSP_OK;
 }
 
-int jdsp_stftmask_reset(jdsp_stftmask *h) { return h ? h->ola.reset() : JDSP_EINVAL; }
+int jdsp_stftmask_reset(jdsp_stftmask *h)
+{
+    if (!h) return JDSP_EINVAL;
+    h->count_valid = 0;
+    return h->ola.reset();
+}
+
+long jdsp_stftmask_frames_recomputed(const jdsp_stftmask *h)
+{
+    if (!h) return JDSP_EINVAL;
+    if (!h->count_valid) return 0;
+    jdsp_ctx *ctx = h->ctx;
+    unsigned int n = 0;
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    JDSP_HIP(ctx, hipMemcpyAsync(&n, h->count.get() + (h->epoch & 1), sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+    JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return (long)n;
+}
 
 int jdsp_stftmask_set_option(jdsp_stftmask *h, const char *name, long value)
 {
@@ -108,12 +152,16 @@ int jdsp_stftmask_process_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const vo
         return fail(ctx, JDSP_EINVAL,
                     "jdsp_stftmask_process: pcm and out_i16 must be 4-byte, out_f32 8-byte aligned, the mask 4-byte "
                     "(REAL) or 8-byte (COMPLEX)");
-    if (n_frames == 0) return JDSP_OK;
+    if (n_frames == 0) {
+        h->count_valid = 0;                                    // a call of no frames recomputed none
+        return JDSP_OK;
+    }
     if (!pcm_dev || !mask_dev) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_process: pcm or mask is NULL");
     OlaStream &o = h->ola;
     if (jdsp::launch_stftmask(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev, mask_dev,
                               mask_pitch, n_frames, h->wa, h->ws, o.g, o.tail[o.cur], o.tail[o.cur ^ 1], out_i16_dev,
-                              out_f32_dev, ctx->stft1024_table.get(), o.run_opt))
+                              out_f32_dev, ctx->stft1024_table.get(), o.run_opt, h->f64.get(), h->count.get(),
+                              h->next_epoch()))
         return fail(ctx, JDSP_EHIP, "jdsp_stftmask_process: launch", hipGetLastError());
     o.cur ^= 1;
     return JDSP_OK;
@@ -172,15 +220,22 @@ int jdsp_stftmask_batch_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void
         return fail(ctx, JDSP_EINVAL,
                     "jdsp_stftmask_batch: pcm and out_i16 must be 4-byte, out_f32 and the offset arrays 8-byte aligned, "
                     "the mask 4-byte (REAL) or 8-byte (COMPLEX)");
-    if (n_utts == 0 || n_frames_total == 0) return JDSP_OK;
+    if (n_utts == 0 || n_frames_total == 0) {
+        h->count_valid = 0;
+        return JDSP_OK;
+    }
     if (!pcm_dev || !mask_dev || !sample_first_dev || !frame_first_dev)
         return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: pcm, mask, sample_first or frame_first is NULL");
-    if (!out_i16_dev && !out_f32_dev) return JDSP_OK;          // no stream to advance: nothing to do
+    if (!out_i16_dev && !out_f32_dev) {                        // no stream to advance: nothing to do
+        h->count_valid = 0;
+        return JDSP_OK;
+    }
     if (jdsp::launch_stftmask_batch(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev,
                                     mask_dev, mask_pitch, n_frames_total,
                                     reinterpret_cast<const long long *>(sample_first_dev),
                                     reinterpret_cast<const long long *>(frame_first_dev), n_utts, h->wa, h->ws, h->ola.g,
-                                    out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt))
+                                    out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt, h->f64.get(),
+                                    h->count.get(), h->next_epoch()))
         return fail(ctx, JDSP_EHIP, "jdsp_stftmask_batch: launch", hipGetLastError());
     return JDSP_OK;
 }

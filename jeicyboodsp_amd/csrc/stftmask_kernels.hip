@@ -21,6 +21,14 @@
 // PCM.  Frame j + 1 starts one hop after frame j, and a hop is HR registers of the frame's layout, so the raw sample
 // pairs shift down like the overlap-add does: a wave reads every sample of its run once (HR dwords per lane and frame)
 // plus the R - 1 halo frames.
+//
+// Accuracy.  The forward transform rounds every bin by about 2^-23 sqrt(E), E the frame's energy, wherever the energy
+// sits, and the mask passes that rounding like anything else in a bin: under a mask that removes something loud and
+// keeps something faint it can exceed the project's bar of 1e-5 of the output.  stftmask_frame therefore forms
+// rho^2 = 2^-46 E mean|M|^2 / sum y^2 (y: the frame before the synthesis window; tests/stftmask_fp32_ref.py) and a
+// frame with rho > JDSP_STFTMASK_RHO is computed again by the same wave in FP64 (stftmask_frame_f64) before it enters
+// the overlap-add.  The decision and both results are functions of the frame's samples and mask row alone, so the
+// stream stays bit-identical across call cuts, launch geometries, shards and the batch.
 #include "jdsp_internal.h"
 #include "ola_stream.h"
 #include "ragged_batch.h"
@@ -30,11 +38,18 @@ namespace jdsp {
 #ifndef JDSP_STFTMASK_RESIDENT
 // Waves per SIMD the launch plans for and __launch_bounds__ asks for.  A wave holds two mask rows (the frame's and
 // the prefetched one: 20 registers REAL, 40 COMPLEX), both windows, the gain, the overlap-add sums, the raw PCM and
-// the transform's twiddles: 162-164 registers with a real mask, 196 with a complex one, nothing in scratch
-// (profiles/r08_stftmask_isa.txt).  That is past the 128 of four waves per SIMD and, for the complex mask, past the
-// 168 of three; two (256 registers) hold every instantiation, and two is what istft_run_kernel measured fastest for
-// the same overlap-add and store pattern (profiles/r04_istft_launch_ab.txt).
+// the transform's twiddles, and the FP64 pass below needs some forty more while it runs: 208-214 registers with a real
+// mask, 240-248 with a complex one, nothing in scratch (profiles/r13_stftmask_suppress.txt; 162-164 and 196 before that
+// pass, profiles/r08_stftmask_isa.txt).  That is past the 128 of four waves per SIMD and past the 168 of three; two
+// (256 registers) hold every instantiation, and two is what istft_run_kernel measured fastest for the same
+// overlap-add and store pattern (profiles/r04_istft_launch_ab.txt).
 #define JDSP_STFTMASK_RESIDENT 2
+#endif
+
+#ifndef JDSP_STFTMASK_RHO
+// Half the bar with a margin of two: tests/stftmask_fp32_ref.py (RHO) derives it from a plain-FP32 restatement, and
+// tests/test_stftmask_fp32_ref_cpu.py holds it there.  White input under a mask of order one has rho = 1.2e-7.
+#define JDSP_STFTMASK_RHO 8.0e-7f
 #endif
 
 namespace {
@@ -93,18 +108,44 @@ __device__ __forceinline__ float2 mask_mul(float2 x, float2 m)
     return make_float2(__builtin_fmaf(-x.y, m.y, x.x * m.x), __builtin_fmaf(x.y, m.x, x.x * m.y));
 }
 
+__device__ __forceinline__ float mask_abs2(float m) { return m * m; }
+__device__ __forceinline__ float mask_abs2(float2 m) { return __builtin_fmaf(m.x, m.x, m.y * m.y); }
+
+// A lane's share of sum |M / 1024|^2 over all 1024 bins of the Hermitian-extended row.  A lane's items hold the bins
+// k = lane + 64 d and k + 512; the mirror images of both are some other item's for k >= 193 and their own for k = 0,
+// and nobody's otherwise (those count twice).
+template <int CPX> __device__ __forceinline__ float mask_energy(const MaskRow<CPX> &m, int lane)
+{
+    float s = 0.0f;
+#pragma unroll
+    for (int d = 0; d < 5; d++) {
+        const int k = lane + 64 * d;
+        s = __builtin_fmaf(k == 0 || k >= 193 ? 1.0f : 2.0f, mask_abs2(m.lo[d]) + mask_abs2(m.hi[d]), s);
+    }
+    return s;
+}
+
+// rho^2 > RHO^2 in the kernel's own units: e_in = sum (w_a x / 2)^2 = E / 4, m_sq = sum mask_energy = mean|M|^2 / 1024,
+// so 2^-46 E mean|M|^2 = 2^-34 e_in m_sq.  False for NaN, for an all-zero mask and for silence (both exact).
+constexpr float kUnsafeK = 5.8207660913467407e-11f / (JDSP_STFTMASK_RHO * JDSP_STFTMASK_RHO);
+__device__ __forceinline__ bool stftmask_unsafe(float e_in, float m_sq, float e_out) { return e_in * m_sq * kUnsafeK > e_out; }
+
 // One frame: y[d] = w_s * IDFT(M * DFT(w_a * frame)) at the samples (2 lane + 128 d, +1).  wa = w_a / 2 (the forward
-// split's 1/2, frame_io.h), m as mask_prepare left it (so the 1/1024 is in), ws = w_s.
+// split's 1/2, frame_io.h), m as mask_prepare left it (so the 1/1024 is in), m_sq the lane's mask_energy of it,
+// ws = w_s.  Returns stftmask_unsafe (wave-uniform): FP32 cannot hold this frame.  The criterion's three sums are
+// reduced over the wave side by side at the end, where their dependent DPP chains interleave.
 template <int CPX>
-__device__ __forceinline__ void stftmask_frame(const unsigned int (&raw)[8], const float2 (&wa)[8], const WaveTwiddles &tw,
+__device__ __forceinline__ bool stftmask_frame(const unsigned int (&raw)[8], const float2 (&wa)[8], const WaveTwiddles &tw,
                                                const PairTwiddles &pw, float2 *lds, int lane, const MaskRow<CPX> &m,
-                                               const float2 (&ws)[8], float2 (&y)[8])
+                                               float m_sq, const float2 (&ws)[8], float2 (&y)[8])
 {
     float2 v[8];
+    float e_in = 0.0f;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const float2 s = unpack_i16x2(raw[r]);
         v[r] = make_float2(s.x * wa[r].x, s.y * wa[r].y);
+        e_in = __builtin_fmaf(v[r].x, v[r].x, __builtin_fmaf(v[r].y, v[r].y, e_in));
     }
     wave_fft512<false>(v, lds, lane, tw);
     float2 zr[5], ret[4];
@@ -123,8 +164,114 @@ __device__ __forceinline__ void stftmask_frame(const unsigned int (&raw)[8], con
     pair_return_lds(ret, lds, lane, y);
     wave_fft512<true>(y, lds, lane, tw);
     wave_lds_fence();                                            // the scratch is free for the next frame
+    float e_out = 0.0f;
 #pragma unroll
-    for (int d = 0; d < 8; d++) y[d] = make_float2(y[d].x * ws[d].x, y[d].y * ws[d].y);
+    for (int d = 0; d < 8; d++) {
+        e_out = __builtin_fmaf(y[d].x, y[d].x, __builtin_fmaf(y[d].y, y[d].y, e_out));
+        y[d] = make_float2(y[d].x * ws[d].x, y[d].y * ws[d].y);
+    }
+    return stftmask_unsafe(wave_sum_f32(e_in), wave_sum_f32(m_sq), wave_sum_f32(e_out));
+}
+
+// ---- the same frame in FP64 ----------------------------------------------------------------------------------------
+// What the handle keeps for it (stftmask_api.hip): the windows as OlaStream::window_at gives them, unrounded, the
+// twiddles tw[t] = exp(-2 pi i t / 1024), t < 512, and the count of recomputed frames: two words, of which the call
+// number `epoch` (from the host) adds to count[epoch & 1] -- one atomic per wave, at the end of its run -- and zeroes
+// the other for the next call.  Calls on a stream follow each other, so a call finds its word zero without anything
+// being enqueued ahead of the launch.
+struct StftMaskF64 {
+    const double *wa, *ws;    // [1024] each
+    const double2 *tw;        // [512]
+    unsigned int *count;      // [2]
+    unsigned int epoch;
+};
+
+__device__ __forceinline__ void stftmask_count_begin(const StftMaskF64 &q, int lane)
+{
+    if (blockIdx.x == 0 && lane == 0) q.count[(q.epoch + 1) & 1] = 0;
+}
+__device__ __forceinline__ void stftmask_count_end(const StftMaskF64 &q, int n, int lane)
+{
+    if (n && lane == 0) atomicAdd(q.count + (q.epoch & 1), (unsigned int)n);
+}
+
+__device__ __forceinline__ double2 cmul64(double2 a, double2 b)
+{
+    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+// One wave, a plain 1024-point complex radix-2 in LDS (buf: 1024 double2): decimation in frequency forward (natural
+// order in, bit-reversed out), the mask applied where the bins lie, decimation in time back (bit-reversed in, natural
+// out) -- no reordering pass.  The inverse runs as the forward transform of conj(Y): the output is real, so its real
+// part is the frame.  row: the frame's mask row as the caller gave it.  Loops over registers are unrolled, the passes
+// are not: the branch is rare and must not grow the kernel's registers.
+template <int CPX>
+__device__ __forceinline__ void stftmask_frame_f64(const unsigned int (&raw)[8], const StftMaskF64 &q, const void *row,
+                                                   double2 *buf, int lane, float2 (&y)[8])
+{
+    // opaque from here on: what this rare pass derives from the lane (sixteen window addresses and more) must not be
+    // hoisted out of the frame loop into registers the FP32 frames then carry
+    asm volatile("" : "+v"(lane));
+    wave_lds_fence();
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        const int i = 2 * lane + 128 * d;
+        const float2 s = unpack_i16x2(raw[d]);
+        buf[i] = make_double2((double)s.x * q.wa[i], 0.0);
+        buf[i + 1] = make_double2((double)s.y * q.wa[i + 1], 0.0);
+        asm volatile("" ::: "memory");                           // one register's loads in flight, not eight
+    }
+#pragma unroll 1
+    for (int half = 512; half >= 1; half >>= 1) {
+        wave_lds_fence();
+        const int step = 512 / half;
+#pragma unroll 1
+        for (int t = lane; t < 512; t += 64) {
+            const int j = t & (half - 1), i = ((t - j) << 1) + j;
+            const double2 a = buf[i], b = buf[i + half];
+            buf[i] = make_double2(a.x + b.x, a.y + b.y);
+            buf[i + half] = cmul64(make_double2(a.x - b.x, a.y - b.y), q.tw[j * step]);
+        }
+    }
+    wave_lds_fence();
+    // bin k <= 512 sits at brev(k); conj(Y[k]) goes back there and conj(Y[1024 - k]) = Y[k] to brev(1024 - k), which
+    // no lane reads in this pass
+#pragma unroll 1
+    for (int k = lane; k <= 512; k += 64) {
+        const int at = (int)(__brev((unsigned int)k) >> 22);
+        const double2 x = buf[at];
+        double2 m;
+        if (CPX) {
+            const float2 mv = static_cast<const float2 *>(row)[k];
+            m = make_double2((double)mv.x, (double)mv.y);
+        } else {
+            m = make_double2((double)static_cast<const float *>(row)[k], 0.0);
+        }
+        const bool real_bin = k == 0 || k == 512;                // Im M ignored, the bin is real
+        const double2 yk = real_bin ? make_double2(m.x * x.x, 0.0) : cmul64(x, m);
+        buf[at] = make_double2(yk.x, -yk.y);
+        if (!real_bin) buf[(int)(__brev((unsigned int)(1024 - k)) >> 22)] = yk;
+    }
+#pragma unroll 1
+    for (int half = 1; half <= 512; half <<= 1) {
+        wave_lds_fence();
+        const int step = 512 / half;
+#pragma unroll 1
+        for (int t = lane; t < 512; t += 64) {
+            const int j = t & (half - 1), i = ((t - j) << 1) + j;
+            const double2 a = buf[i], b = cmul64(buf[i + half], q.tw[j * step]);
+            buf[i] = make_double2(a.x + b.x, a.y + b.y);
+            buf[i + half] = make_double2(a.x - b.x, a.y - b.y);
+        }
+    }
+    wave_lds_fence();
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        const int i = 2 * lane + 128 * d;
+        y[d] = make_float2((float)(buf[i].x * (1.0 / 1024.0) * q.ws[i]), (float)(buf[i + 1].x * (1.0 / 1024.0) * q.ws[i + 1]));
+        asm volatile("" ::: "memory");
+    }
+    wave_lds_fence();                                            // the scratch is free for the next frame
 }
 
 }  // namespace
@@ -141,7 +288,15 @@ struct StftMaskArgs {
     short *out;               // may be NULL
     float *out_f32;           // may be NULL
     int run;
+    StftMaskF64 f64;
 };
+
+// the FP32 transform's scratch and the FP64 pass's 1024 complex doubles share one LDS array (16 KiB a wave: eight
+// workgroups of one wave a CU at JDSP_STFTMASK_RESIDENT 2, 128 of the CU's 160 KiB)
+#define JDSP_STFTMASK_LDS                                           \
+    __shared__ __attribute__((aligned(16))) double2 lds64[1024];    \
+    static_assert(sizeof(double2) * 1024 >= sizeof(float2) * kWaveLdsComplex, "the FP32 scratch fits"); \
+    float2 *lds = reinterpret_cast<float2 *>(lds64)
 
 template <int R, int CPX>
 __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kernel(StftMaskArgs a,
@@ -150,8 +305,10 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
     constexpr int HR = 8 / R;                                   // registers per hop
     constexpr int HOP = 1024 / R;
     constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    JDSP_STFTMASK_LDS;
     const int lane = threadIdx.x;
+    stftmask_count_begin(a.f64, lane);
+    int n_redo = 0;                                              // emitted frames of this run computed again in FP64
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
     // the halo: frames j0 - R + 1 .. j0 - 1 are transformed and added, not emitted (all >= 0: the launch keeps
@@ -185,6 +342,7 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
         mask_load(nm, mask + (size_t)js * row_bytes, lane);
         mask_prepare(m, nm, lane);
     }
+    float m_sq = mask_energy(m, lane);
     for (long j = js; j < j1; j++) {
         // frame j + 1's new hop of PCM and its mask row, needed one iteration from now: unguarded loads at a clamped
         // frame (past the wave's run they are never used), raw until they are staged below
@@ -195,7 +353,11 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
             for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
         }
         if (a.pitch) mask_load(nm, mask + (size_t)jn * row_bytes, lane);     // pitch 0: the row stays in registers
-        stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, ws, y);
+        if (stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, m_sq, ws, y)) {
+            // a frame FP32 cannot hold: again, in FP64; counted by the wave that emits it
+            stftmask_frame_f64<CPX>(raw, a.f64, mask + (size_t)(a.pitch ? j : 0) * row_bytes, lds64, lane, y);
+            n_redo += j >= j0;
+        }
         ola.add(y, o);
         // stage the prefetched values before this frame's stores: vmcnt counts loads and stores in issue order, and a
         // wait for them at the top of the next iteration would also wait for these stores (istft_run_kernel)
@@ -203,11 +365,15 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_run_kerne
         for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
 #pragma unroll
         for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
-        if (a.pitch) mask_prepare(m, nm, lane);
+        if (a.pitch) {
+            mask_prepare(m, nm, lane);
+            m_sq = mask_energy(m, lane);
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (j >= j0) ola.emit(o, a.out, a.out_f32, j * HOP, lane);
         ola.shift(j == a.n_frames - 1, a.tail_out, lane);
     }
+    stftmask_count_end(a.f64, n_redo, lane);
 }
 
 template <int R>
@@ -219,12 +385,14 @@ static void launch_kind(hipStream_t s, int cpx, long grid, const StftMaskArgs &a
 
 int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask, long pitch,
                     long n_frames, const float *wa, const float *ws, const float *g, const float *tail_in,
-                    float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt)
+                    float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
+                    unsigned int *count, unsigned int epoch)
 {
     if (n_frames <= 0) return 0;
     const int r = 1024 / hop;
     const OlaRunPlan p = plan_ola_run(n_cu, JDSP_STFTMASK_RESIDENT, r, n_frames, run_opt);
-    StftMaskArgs a = {pcm, mask, pitch, n_frames, wa, ws, g, tail_in, tail_out, out, out_f32, (int)p.run};
+    StftMaskArgs a = {pcm, mask, pitch, n_frames, wa, ws, g, tail_in, tail_out, out, out_f32, (int)p.run,
+                      {f64, f64 + 1024, reinterpret_cast<const double2 *>(f64 + 2048), count, epoch}};
     if (r == 1) launch_kind<1>(s, complex_mask, p.grid, a, table);
     else if (r == 2) launch_kind<2>(s, complex_mask, p.grid, a, table);
     else launch_kind<4>(s, complex_mask, p.grid, a, table);
@@ -249,6 +417,7 @@ struct StftMaskBatchArgs {
     short *out;               // may be NULL
     float *out_f32;           // may be NULL
     int run;
+    StftMaskF64 f64;
 };
 
 template <int R, int CPX>
@@ -259,8 +428,10 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     constexpr int HR = 8 / R;
     constexpr int HOP = 1024 / R;
     constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    JDSP_STFTMASK_LDS;
     const int lane = threadIdx.x;
+    stftmask_count_begin(a.f64, lane);
+    int n_redo = 0;                                              // emitted frames of this run computed again in FP64
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
     long u = ragged_find_utt(frame_first, a.n_utts, j0);       // the utterance of frame j0 (ragged_batch.h)
@@ -296,6 +467,7 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
         mask_load(nm, mask + (size_t)js * row_bytes, lane);
         mask_prepare(m, nm, lane);
     }
+    float m_sq = mask_energy(m, lane);
     for (long j = js; j < j1; j++) {
         // the prefetch of stftmask_run_kernel, with the PCM's clamp inside the utterance: after its last frame the
         // next frame's samples are another span's, read whole below.  The mask rows run on across utterances.
@@ -308,14 +480,21 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
             for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
         }
         if (a.pitch) mask_load(nm, mask + (size_t)jm * row_bytes, lane);
-        stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, ws, y);
+        if (stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, m_sq, ws, y)) {
+            // again, in FP64 (stftmask_run_kernel)
+            stftmask_frame_f64<CPX>(raw, a.f64, mask + (size_t)(a.pitch ? j : 0) * row_bytes, lds64, lane, y);
+            n_redo += j >= j0;
+        }
         ola.add(y, o);
         // staged before this frame's stores (stftmask_run_kernel)
 #pragma unroll
         for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
 #pragma unroll
         for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
-        if (a.pitch) mask_prepare(m, nm, lane);
+        if (a.pitch) {
+            mask_prepare(m, nm, lane);
+            m_sq = mask_energy(m, lane);
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (j >= j0) ola.emit(o, a.out, a.out_f32, base + j * HOP, lane);
         ola.shift(false, nullptr, lane);
@@ -335,6 +514,7 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
             }
         }
     }
+    stftmask_count_end(a.f64, n_redo, lane);
 }
 
 template <int R>
@@ -352,12 +532,14 @@ static void launch_batch_kind(hipStream_t s, int cpx, long grid, const StftMaskB
 int launch_stftmask_batch(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
                           long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
                           long n_utts, const float *wa, const float *ws, const float *g, short *out, float *out_f32,
-                          const float2 *table, int run_opt)
+                          const float2 *table, int run_opt, const double *f64, unsigned int *count,
+                          unsigned int epoch)
 {
     if (n_frames_total <= 0 || n_utts <= 0) return 0;
     const int r = 1024 / hop;
     const OlaRunPlan p = plan_ola_run(n_cu, JDSP_STFTMASK_RESIDENT, r, n_frames_total, run_opt);
-    StftMaskBatchArgs a = {pcm, mask, pitch, n_frames_total, wa, ws, g, n_utts, out, out_f32, (int)p.run};
+    StftMaskBatchArgs a = {pcm, mask, pitch, n_frames_total, wa, ws, g, n_utts, out, out_f32, (int)p.run,
+                           {f64, f64 + 1024, reinterpret_cast<const double2 *>(f64 + 2048), count, epoch}};
     if (r == 1) launch_batch_kind<1>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
     else if (r == 2) launch_batch_kind<2>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
     else launch_batch_kind<4>(s, complex_mask, p.grid, a, table, sample_first, frame_first);

@@ -1111,6 +1111,14 @@ class StftMask(_OlaStream):
             dev = None
         return self._process(dev, (_vp(pcm), _vp(mask), pitch), n_frames, want_f32, write, out, out_f32)
 
+    def frames_recomputed(self):
+        """Frames of the last process / process_batch call that went through the FP64 pass
+        (jdsp_stftmask_frames_recomputed); waits for the stream."""
+        n = L.jdsp_stftmask_frames_recomputed(self._h)
+        if n < 0:
+            self.eng._ck(int(n))
+        return int(n)
+
     def process_batch(self, pcm, mask, utt_sample_first, want_f32=False, out=None, out_f32=None):
         """A batch of independent utterances in one launch (jdsp_stftmask_batch): each comes out as a fresh stream's
         process + flush of its frames, bit for bit, and the handle's own stream is neither read nor advanced.
