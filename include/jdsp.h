@@ -46,7 +46,7 @@ extern "C" {
  *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added;
  *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added; the ragged-batch
  *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added;
- *    jdsp_stftmask_frames_recomputed added
+ *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -389,7 +389,7 @@ int jdsp_denoise_process(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks
                          float *precast_host, long *n_out_blocks);
 /* Current rgdEstimatedNS (n_fft doubles, host).  Synchronises. */
 int jdsp_denoise_noise(jdsp_denoise *h, double *noise_host);
-/* How many frames of the last call (process, apply or shard_finish) the FP32 kernels handed to the FP64 pass: in
+/* How many frames of the last call (process, apply, shard_finish or batch) the FP32 kernels handed to the FP64 pass: in
  * spectral subtraction because transform rounding could show through the phase of bins far below the noise estimate
  * (exactly periodic input), and at 512-point frames, in both modes, because a quiet frame shares its transform with a
  * loud one.  1024-point Wiener: always 0.  Negative: an error code.
@@ -402,6 +402,56 @@ long jdsp_denoise_frames_recomputed(jdsp_denoise *h);
  * trace appear).  Synchronises. */
 int jdsp_denoise_vad_trace(jdsp_denoise *h, long n, uint8_t *voice_host, int64_t *energy_sum_host,
                            int32_t *zcr_host);
+
+/* Batched denoise: n_utts INDEPENDENT utterances in one launch sequence, each a fresh stream of the reference's
+ * main() with the handle's mode.  The entries neither read nor write the handle's own stream state (run length,
+ * average, estimate, previous block, overlap, call count), so they may be interleaved with _process on the same
+ * handle; jdsp_denoise_frames_recomputed reports the batch call's count when it was the last call.  (1024, 512)
+ * handles only: on a (512, 256) handle the three entries return JDSP_EINVAL with a text (two 512-point frames share
+ * one transform, and the pairing across utterance boundaries is not built).
+ *   - Utterance u has B_u = block_first[u + 1] - block_first[u] blocks (>= 0) of hop = jdsp_denoise_block_len(h)
+ *     samples; its block b is pcm[sample_first[u] + hop b .. + hop).
+ *   - Its result is what a fresh handle of the same mode gives for _process of its B_u blocks: max(B_u - 2, 0) emitted
+ *     blocks.  Emitted block k is the overlap buffer's first half after the frame [block k + 1, block k + 2] was added
+ *     (SS:247-263: the call that consumes block k + 2 is the stream's call k + 3, the first that returns TRUE for
+ *     k = 0), i.e. the enhanced signal at the time of input block k + 1, and it is written TIME-ALIGNED, at
+ *     out[sample_first[u] + hop (k + 1) .. + hop); precast (the same samples before the (short) cast) likewise.  Indices
+ *     computed for the noisy PCM (MFCC frame_start, ...) therefore apply to the output unchanged.  The first and the
+ *     last block of each span are never written, and the device entry touches no sample outside the spans.
+ *   - flags [n_blocks_total] uint8: the VAD decision of every block, in concatenated block order (block b of
+ *     utterance u at block_first[u] + b).  noise_last [n_utts][1024] float32: the estimate in force after the
+ *     utterance's last block, zeros if none was latched.  Any of the four output pointers may be NULL.
+ *   - An utterance's out, precast, flags and noise_last do not depend, bit for bit, on where it stands in the batch,
+ *     on its neighbours, on how the batch is split into calls, or on the "blocks_per_wave" option (here: the blocks a
+ *     wave of the run kernel walks; 0 = one round of resident waves).  Against the oracle they are held to _process's
+ *     bars; against _process itself they agree to those bars, not bit for bit (the single stream sums its noise
+ *     average in chunks).
+ *   - jdsp_denoise_batch_dev only enqueues on the context's stream: no allocation, no host synchronisation, no host
+ *     read of the two offset arrays (int64, [n_utts] and [n_utts + 1], 8-byte aligned) -- hence n_blocks_total, which
+ *     must equal block_first[n_utts].  It is graph-capturable.  The device-side offsets are the caller's contract, the
+ *     one of jdsp_stftmask_batch_dev: block_first[0] = 0 and non-decreasing; every sample_first[u] even, >= 0 and
+ *     ascending; the spans, hop B_u long, disjoint and inside pcm and the outputs.  No PCM outside the spans is read.
+ *     pcm and out 16-byte, precast 8-byte aligned, as in jdsp_denoise_process_dev.
+ *   - Its workspace comes from jdsp_denoise_batch_reserve, the only call that allocates (and synchronises): per
+ *     reserved block 1 (flag) + 4 (row index) + 4 (FP64 list) + 409.6 bytes (latched rows: an utterance of B blocks
+ *     latches at most floor(B / 10) times, so 1 + floor(max_blocks_total / 10) rows of 4 KB hold any batch) = 419
+ *     bytes; nothing per utterance.  A _dev call with more blocks or utterances than reserved is JDSP_EINVAL with a
+ *     text.
+ *   - jdsp_denoise_batch (host pointers, synchronous) reserves on demand, checks the offsets and returns JDSP_EINVAL
+ *     with a jdsp_last_error text otherwise: block_first[0] == 0, block_first non-decreasing, sample_first even, >= 0
+ *     and ascending with sample_first[u] + hop B_u <= sample_first[u + 1], the last span <= n_samples.  pcm, out and
+ *     precast are n_samples long; the outputs are ZERO wherever the device entry would not write.
+ *   - n_utts == 0, batches of empty utterances and all four outputs NULL succeed and launch nothing; so does a host
+ *     batch in which every B_u <= 2, except for the VAD when flags are asked for (the device entry cannot know: its
+ *     kernels then write nothing but flags and zero estimates).  n_utts < 0 and misaligned base pointers are
+ *     JDSP_EINVAL. */
+int jdsp_denoise_batch_reserve(jdsp_denoise *h, long max_blocks_total, long max_utts);
+int jdsp_denoise_batch_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_t *sample_first_dev,
+                           const int64_t *block_first_dev, long n_utts, long n_blocks_total, int16_t *out_dev,
+                           float *precast_dev, uint8_t *flags_dev, float *noise_last_dev);
+int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
+                       const int64_t *block_first_host, long n_utts, int16_t *out_host, float *precast_host,
+                       uint8_t *flags_host, float *noise_last_host);                   /* host path, synchronous */
 
 /* Sharded denoise: one rank's share of ONE global stream of n_total blocks (multi-GPU,
  * SURVEY §8e).  The rank owns global blocks [b0, b1); pcm_ext_dev holds global blocks

@@ -92,6 +92,9 @@ def _load():
         "jdsp_denoise_noise": (i, [vp, vp]),
         "jdsp_denoise_frames_recomputed": (l, [vp]),
         "jdsp_denoise_vad_trace": (i, [vp, l, vp, vp, vp]),
+        "jdsp_denoise_batch_reserve": (i, [vp, l, l]),
+        "jdsp_denoise_batch_dev": (i, [vp, vp, vp, vp, l, l, vp, vp, vp, vp]),
+        "jdsp_denoise_batch": (i, [vp, vp, l, vp, vp, l, vp, vp, vp, vp]),
         "jdsp_gmm_create": (i, [vp, vp, i, C.POINTER(vp)]),
         "jdsp_gmm_destroy": (i, [vp]),
         "jdsp_gmm_set_option": (i, [vp, C.c_char_p, l]),

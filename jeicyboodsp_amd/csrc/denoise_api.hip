@@ -146,7 +146,7 @@ static int reserve2(jdsp_denoise *h, long max_blocks)
     if (e == hipSuccess) e = w.chunk_beta.alloc(n_chunks * 1024);
     if (e == hipSuccess) e = w.a_start.alloc(n_chunks * 1024);
     if (e == hipSuccess) e = w.redo.alloc(n + 1);
-    h->redo_valid = 0;
+    if (h->redo_valid == 1) h->redo_valid = 0;
     if (e != hipSuccess) {
         w = {};
         return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_denoise_reserve", e);
@@ -388,6 +388,155 @@ int jdsp_denoise_shard_finish_dev(jdsp_denoise *h, const float *last_all_dev, in
     return JDSP_OK;
 }
 
+/* ---- a batch of ragged utterances, each a fresh stream (include/jdsp.h "batched denoise") --- */
+static int batch_supported(jdsp_denoise *h, const char *what)
+{
+    if (h->n_fft == 1024) return JDSP_OK;
+    return fail(h->ctx, JDSP_EINVAL, (std::string(what) + ": (1024, 512) handles only; a (512, 256) handle pairs two frames "
+                                      "in one transform, which is not built across utterance boundaries").c_str());
+}
+
+int jdsp_denoise_batch_reserve(jdsp_denoise *h, long max_blocks_total, long max_utts)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    if (max_blocks_total < 0 || max_utts < 0 || max_blocks_total > 0x7ffffff0L)
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch_reserve: max_blocks_total must be 0 .. 2^31 - 16, max_utts >= 0");
+    int rc = batch_supported(h, "jdsp_denoise_batch_reserve");
+    if (rc) return rc;
+    jdsp_denoise::BatchWs &w = h->bws;
+    if (max_blocks_total <= w.cap_blocks) {                     // the utterances need no memory of their own
+        if (max_utts > w.cap_utts) w.cap_utts = max_utts;
+        return JDSP_OK;
+    }
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    w = {};                                                     // freed before anything is allocated
+    if (h->redo_valid == 2) h->redo_valid = 0;
+    const size_t n = (size_t)max_blocks_total, n_rows = n / 10 + 1;
+    hipError_t e = w.flags.alloc(n + 1);
+    if (e == hipSuccess) e = w.row_idx.alloc(n + 1);
+    if (e == hipSuccess) e = w.redo.alloc(n + 1);
+    if (e == hipSuccess) e = w.rows.alloc(n_rows * 1024);
+    if (e == hipSuccess) e = hipMemset(w.rows.get(), 0, 1024 * sizeof(float));       // row 0: nothing latched yet
+    if (e != hipSuccess) {
+        w = {};
+        return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_denoise_batch_reserve", e);
+    }
+    w.cap_blocks = max_blocks_total;
+    w.cap_utts = max_utts;
+    return JDSP_OK;
+}
+
+// vad_only: no utterance has a third block (the host entry knows; nothing but the flags can come out)
+static int batch_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_t *sample_first_dev,
+                     const int64_t *block_first_dev, long n_utts, long n_blocks_total, int16_t *out_dev,
+                     float *precast_dev, uint8_t *flags_dev, float *noise_last_dev, int vad_only)
+{
+    jdsp_ctx *ctx = h->ctx;
+    if (n_utts < 0 || n_blocks_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: n_utts or n_blocks_total < 0");
+    int rc = batch_supported(h, "jdsp_denoise_batch");
+    if (rc) return rc;
+    if (((uintptr_t)pcm_dev & 15u) || ((uintptr_t)out_dev & 15u) || ((uintptr_t)precast_dev & 7u) ||
+        ((uintptr_t)noise_last_dev & 3u) || ((uintptr_t)sample_first_dev & 7u) || ((uintptr_t)block_first_dev & 7u))
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: pcm and out must be 16-byte, precast and the offset arrays "
+                                      "8-byte, noise_last 4-byte aligned");
+    h->redo_valid = 0;
+    if (n_utts == 0) return JDSP_OK;
+    if (n_blocks_total == 0) {                                 // only empty utterances: no kernel, their estimates are zero
+        if (noise_last_dev)
+            JDSP_HIP(ctx, hipMemsetAsync(noise_last_dev, 0, (size_t)n_utts * 1024 * sizeof(float), ctx->stream));
+        return JDSP_OK;
+    }
+    if (!out_dev && !precast_dev && !flags_dev && !noise_last_dev) return JDSP_OK;     // nothing to write
+    if (!pcm_dev || !sample_first_dev || !block_first_dev)
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: pcm, sample_first or block_first is NULL");
+    const jdsp_denoise::BatchWs &w = h->bws;
+    if (n_blocks_total > w.cap_blocks || n_utts > w.cap_utts)
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch_dev: the batch exceeds what jdsp_denoise_batch_reserve sized "
+                                      "(the device entry does not allocate)");
+    hipStream_t s = ctx->stream;
+    if (jdsp::launch_denoise_batch(s, h->mode, h->opt_k, ctx->n_cu, pcm_dev,
+                                   reinterpret_cast<const long long *>(sample_first_dev),
+                                   reinterpret_cast<const long long *>(block_first_dev), n_utts, n_blocks_total, h->w_hi,
+                                   ctx->stft1024_table.get(), flags_dev ? flags_dev : w.flags.get(), w.row_idx.get(),
+                                   w.rows.get(), w.redo.get(), out_dev, precast_dev, noise_last_dev,
+                                   vad_only || (!out_dev && !precast_dev && !noise_last_dev)))
+        return fail(ctx, JDSP_EHIP, "jdsp_denoise_batch: launch", hipGetLastError());
+    if (!vad_only && (out_dev || precast_dev)) h->redo_valid = 2;
+    return JDSP_OK;
+}
+
+int jdsp_denoise_batch_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_t *sample_first_dev,
+                           const int64_t *block_first_dev, long n_utts, long n_blocks_total, int16_t *out_dev,
+                           float *precast_dev, uint8_t *flags_dev, float *noise_last_dev)
+{
+    if (!h) return JDSP_EINVAL;
+    JDSP_HIP(h->ctx, hipSetDevice(h->ctx->device));
+    return batch_dev(h, pcm_dev, sample_first_dev, block_first_dev, n_utts, n_blocks_total, out_dev, precast_dev, flags_dev,
+                     noise_last_dev, 0);
+}
+
+int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
+                       const int64_t *block_first_host, long n_utts, int16_t *out_host, float *precast_host,
+                       uint8_t *flags_host, float *noise_last_host)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    const long hop = h->block;
+    if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: n_utts or n_samples < 0");
+    int rc = batch_supported(h, "jdsp_denoise_batch");
+    if (rc) return rc;
+    if (n_utts > 0 && (!sample_first_host || !block_first_host))
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: sample_first or block_first is NULL");
+    // everything the kernels take on trust from device-side offsets is checked here (as jdsp_stftmask_batch)
+    if (n_utts > 0 && block_first_host[0] != 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: block_first[0] must be 0");
+    long end = 0, longest = 0;                                 // one past the last sample of the spans so far
+    for (long u = 0; u < n_utts; u++) {
+        const long b = block_first_host[u + 1] - block_first_host[u], s = sample_first_host[u];
+        if (b < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: block_first must not decrease");
+        if (s < 0 || (s & 1)) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: sample_first entries must be even and >= 0");
+        if (s < end)
+            return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: sample_first must ascend and the utterances' spans must not overlap");
+        if (s > n_samples || b > (n_samples - s) / hop)
+            return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: an utterance's span ends past n_samples");
+        end = s + hop * b;
+        if (b > longest) longest = b;
+    }
+    const long n_total = n_utts > 0 ? block_first_host[n_utts] : 0;
+    // what no launch writes is zero: everything outside the spans, the spans' first and last blocks, the estimate of
+    // an utterance too short to latch
+    if (out_host && n_samples) memset(out_host, 0, (size_t)n_samples * sizeof(int16_t));
+    if (precast_host && n_samples) memset(precast_host, 0, (size_t)n_samples * sizeof(float));
+    if (noise_last_host && n_utts) memset(noise_last_host, 0, (size_t)n_utts * 1024 * sizeof(float));
+    h->redo_valid = 0;
+    const bool vad_only = longest <= 2;
+    if (n_total == 0 || (vad_only ? !flags_host : (!out_host && !precast_host && !flags_host && !noise_last_host)))
+        return JDSP_OK;                                        // nothing to launch
+    if (!pcm_host) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: pcm is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    rc = jdsp_denoise_batch_reserve(h, n_total, n_utts);
+    if (rc) return rc;
+    jdsp::HostCall hc(ctx, "jdsp_denoise_batch");
+    const int64_t *d_sample = hc.upload(sample_first_host, (size_t)n_utts * sizeof(int64_t));
+    const int64_t *d_block = hc.upload(block_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));         // nothing past the last span is read
+    const bool run = !vad_only;
+    int16_t *d_out = run && out_host ? hc.alloc<int16_t>((size_t)end * sizeof(int16_t)) : nullptr;
+    float *d_pre = run && precast_host ? hc.alloc<float>((size_t)end * sizeof(float)) : nullptr;
+    uint8_t *d_flags = flags_host ? hc.alloc<uint8_t>((size_t)n_total) : nullptr;
+    float *d_noise = run && noise_last_host ? hc.alloc<float>((size_t)n_utts * 1024 * sizeof(float)) : nullptr;
+    if (d_out) hc.zero(d_out, (size_t)end * sizeof(int16_t));
+    if (d_pre) hc.zero(d_pre, (size_t)end * sizeof(float));
+    if (hc.ok())
+        hc.result(batch_dev(h, d_pcm, d_sample, d_block, n_utts, n_total, d_out, d_pre, d_flags, d_noise, vad_only));
+    hc.download(out_host, d_out, d_out ? (size_t)end * sizeof(int16_t) : 0);
+    hc.download(precast_host, d_pre, d_pre ? (size_t)end * sizeof(float) : 0);
+    hc.download(flags_host, d_flags, (size_t)n_total);
+    hc.download(noise_last_host, d_noise, d_noise ? (size_t)n_utts * 1024 * sizeof(float) : 0);
+    return hc.finish();
+}
+
 int jdsp_denoise_noise(jdsp_denoise *h, double *noise_host)
 {
     if (!h || !noise_host) return JDSP_EINVAL;
@@ -406,7 +555,8 @@ long jdsp_denoise_frames_recomputed(jdsp_denoise *h)
     if (!h->redo_valid || (h->mode != JDSP_SPECSUB && h->n_fft == 1024)) return 0;   // 1024-point Wiener lists nothing
     int n = 0;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    JDSP_HIP(ctx, hipMemcpyAsync(&n, h->ws.redo.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    const int *count = h->redo_valid == 2 ? h->bws.redo.get() : h->ws.redo.get();
+    JDSP_HIP(ctx, hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return n;
 }

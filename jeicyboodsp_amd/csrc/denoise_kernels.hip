@@ -15,12 +15,15 @@
 //                            walks a run of consecutive output blocks and recomputes one halo frame
 // (512-point frames: vad_*<4>, noise_accum512_kernel, denoise512_run_kernel; sharded runs use the same kernels on a
 // rank's range of events.)
+// (A batch of ragged utterances, each a fresh stream: vad_flags_batch_kernel, noise_batch_kernel, denoise_batch_kernel,
+// denoise_redo_f64_batch_kernel, further down.)
 //
 // All of the reference's statics live in DenoiseState (ping-ponged between calls so a launch
 // never reads state it is also writing), which makes batches of any size -- down to the
 // reference's one block per call -- produce the same stream.
 #include "frame_io.h"
 #include "jdsp_internal.h"
+#include "ragged_batch.h"
 
 namespace jdsp {
 
@@ -152,6 +155,72 @@ __global__ __launch_bounds__(64) void vad_flags_kernel(const short *__restrict__
         const unsigned int e = wave_sum_u32((qa < cap ? qa : cap) + (qb < cap ? qb : cap));
         if (e > 700u * 128u * SPL || (use_zcr && z < 200)) voice_bits |= 1u << i;
     }
+    if (lane < kVadBlocksPerWave && b0 + lane < n_blocks) flags[b0 + lane] = (voice_bits >> lane) & 1u;
+}
+
+// The same flags over the CONCATENATED block axis of a batch of ragged utterances (ragged_batch.h; the layout
+// include/jdsp.h gives for jdsp_denoise_batch_dev): global block j of utterance u is the 512 samples at
+// sample_first[u] + 512 (j - block_first[u]).  The VAD has no state (the frame is [zeros, block]), so only the block's
+// address is new; sample_first is even, so a lane's 16 bytes are 4-byte aligned and no more.
+typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
+// vad_flags_kernel's decision for the blocks of a wave: bit i = block i (its image in img[i]) is voice.  The arithmetic
+// is that kernel's, statement for statement; it is restated and not shared because calling a common function from
+// vad_flags_kernel changes that kernel's own instruction selection (profiles/r14_denoise_batch_isa.txt).
+template <int SPL>
+__device__ __forceinline__ unsigned int vad_voice_bits(const u32x4 (&img)[kVadBlocksPerWave], const double (&w)[SPL],
+                                                       int use_zcr)
+{
+    unsigned int voice_bits = 0;
+#pragma unroll
+    for (int i = 0; i < kVadBlocksPerWave; i++) {
+        int x[9];
+        x[0] = (short)(img[i].x & 0xffffu); x[1] = (int)img[i].x >> 16;
+        x[2] = (short)(img[i].y & 0xffffu); x[3] = (int)img[i].y >> 16;
+        x[4] = (short)(img[i].z & 0xffffu); x[5] = (int)img[i].z >> 16;
+        x[6] = (short)(img[i].w & 0xffffu); x[7] = (int)img[i].w >> 16;
+        x[SPL] = __builtin_amdgcn_update_dpp(0, x[0], 0x130, 0xf, 0xf, true);    // wave_shl:1 -- lane i takes lane i+1; lane 63 gets 0
+        unsigned int qa = 0, qb = 0;
+        int z = 0;                                                  // wave-uniform: counted on the scalar unit
+#pragma unroll
+        for (int k = 0; k < SPL; k++) {
+            const int sv = (int)((double)x[k] * w[k]);              // (short)(short * double), in range
+            if (k < 4) qa += (unsigned int)__mul24(sv, sv); else qb += (unsigned int)__mul24(sv, sv);
+            z += __popcll(__ballot(__mul24(sv, x[k + 1]) < 0));
+        }
+        const unsigned int cap = 1u << 20;
+        const unsigned int e = wave_sum_u32((qa < cap ? qa : cap) + (qb < cap ? qb : cap));
+        if (e > 700u * 128u * SPL || (use_zcr && z < 200)) voice_bits |= 1u << i;
+    }
+    return voice_bits;
+}
+
+__global__ __launch_bounds__(64) void vad_flags_batch_kernel(const short *__restrict__ pcm,
+                                                             const long long *__restrict__ sample_first,
+                                                             const long long *__restrict__ block_first, long n_utts,
+                                                             long n_blocks, const double *__restrict__ w_hi,
+                                                             unsigned char *__restrict__ flags)
+{
+    const int lane = threadIdx.x;
+    const long b0 = (long)blockIdx.x * kVadBlocksPerWave;
+    if (b0 >= n_blocks) return;
+    double w[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = w_hi[8 * lane + k];
+    long u = ragged_find_utt(block_first, n_utts, b0);
+    long ue = uniform_i64(block_first + u + 1);
+    long base = uniform_i64(sample_first + u) - uniform_i64(block_first + u) * 512;   // global block j starts at base + 512 j
+    u32x4 img[kVadBlocksPerWave];
+#pragma unroll
+    for (int i = 0; i < kVadBlocksPerWave; i++) {
+        const long b = b0 + i < n_blocks ? b0 + i : n_blocks - 1;
+        if (b >= ue) {                                          // block b exists, so a non-empty utterance follows
+            const long nb = ue;
+            ragged_next_utt(block_first, n_utts, u, ue);
+            base = uniform_i64(sample_first + u) - nb * 512;
+        }
+        img[i] = reinterpret_cast<const u32x4_a4 *>(pcm + base + b * 512)[lane];
+    }
+    const unsigned int voice_bits = vad_voice_bits<8>(img, w, 1);              // wave-uniform
     if (lane < kVadBlocksPerWave && b0 + lane < n_blocks) flags[b0 + lane] = (voice_bits >> lane) & 1u;
 }
 
@@ -1502,6 +1571,42 @@ __device__ __forceinline__ void redo_fft_lds(double2 *buf, const double2 *tw, in
     __syncthreads();
 }
 
+// buf holds a frame's windowed samples in bit-reversed order: its transform, the gain against `row`, the inverse
+// transform, and its real part / n_fft (SS:248) into y[0 .. NFFT); every thread of the workgroup calls it
+template <int NFFT>
+__device__ __forceinline__ void redo_gain_frame(double2 *buf, const double2 *tw, const float *__restrict__ row, int mode,
+                                                int tid, double *y)
+{
+    constexpr int R = NFFT / 256, LOG = NFFT == 1024 ? 10 : 9;
+    redo_fft_lds<NFFT, false>(buf, tw, tid);
+    double2 Y[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int k = tid + 256 * r;
+        const double2 X = buf[k];
+        const double nk = (double)row[k];
+        if (mode == 1) {                                     // WF:196-213; 0 / 0 stays NaN as in the reference
+            double rk = nk * nk / (X.x * X.x + X.y * X.y);
+            if (rk >= 1.0) rk = 1.0;                         // (a NaN stays one: fmin would drop it)
+            Y[r] = make_double2(X.x * (1.0 - rk), X.y * (1.0 - rk));
+        } else {
+            const double mag = sqrt(X.x * X.x + X.y * X.y);
+            if (mag == 0.0) {
+                Y[r] = make_double2(-nk, 0.0);               // phase 0 (SS:233-242)
+            } else {
+                const double g = 1.0 - nk / mag;
+                Y[r] = make_double2(X.x * g, X.y * g);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; r++) buf[__brev((unsigned)(tid + 256 * r)) >> (32 - LOG)] = Y[r];
+    redo_fft_lds<NFFT, true>(buf, tw, tid);
+#pragma unroll
+    for (int r = 0; r < R; r++) y[tid + 256 * r] = buf[tid + 256 * r].x * (1.0 / NFFT);     // SS:248
+}
+
 template <int NFFT>
 __global__ __launch_bounds__(256) void denoise_redo_f64_kernel(
     const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
@@ -1548,33 +1653,7 @@ __global__ __launch_bounds__(256) void denoise_redo_f64_kernel(
                 const double v = redo_sample<NFFT>(pcm, n_samples, st_in, (j - 1) * B + i) * win[r];
                 buf[__brev((unsigned)i) >> (32 - LOG)] = make_double2(v, 0.0);
             }
-            redo_fft_lds<NFFT, false>(buf, tw, tid);
-            double2 Y[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const int k = tid + 256 * r;
-                const double2 X = buf[k];
-                const double nk = (double)row[k];
-                if (mode == 1) {                                     // WF:196-213; 0 / 0 stays NaN as in the reference
-                    double rk = nk * nk / (X.x * X.x + X.y * X.y);
-                    if (rk >= 1.0) rk = 1.0;                         // (a NaN stays one: fmin would drop it)
-                    Y[r] = make_double2(X.x * (1.0 - rk), X.y * (1.0 - rk));
-                } else {
-                    const double mag = sqrt(X.x * X.x + X.y * X.y);
-                    if (mag == 0.0) {
-                        Y[r] = make_double2(-nk, 0.0);               // phase 0 (SS:233-242)
-                    } else {
-                        const double g = 1.0 - nk / mag;
-                        Y[r] = make_double2(X.x * g, X.y * g);
-                    }
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < R; r++) buf[__brev((unsigned)(tid + 256 * r)) >> (32 - LOG)] = Y[r];
-            redo_fft_lds<NFFT, true>(buf, tw, tid);
-#pragma unroll
-            for (int r = 0; r < R; r++) yy[q][tid + 256 * r] = buf[tid + 256 * r].x * (1.0 / NFFT);     // SS:248
+            redo_gain_frame<NFFT>(buf, tw, row, mode, tid, yy[q]);
         }
         __syncthreads();
         for (int q = 0; q < 2; q++) {
@@ -1612,6 +1691,315 @@ static void launch_denoise_redo(hipStream_t s, int n_fft, const short *pcm, long
     else
         hipLaunchKernelGGL(denoise_redo_f64_kernel<1024>, grid, dim3(256), 0, s, pcm, n_blocks, calls_before, st_in, st_out,
                            ver_base, snap_mask, noise_rows, out, precast, sh, redo, mode);
+}
+
+// =======================================================================================
+// A batch of ragged utterances, each a fresh stream of main() (jdsp_denoise_batch*, include/jdsp.h): the VAD over the
+// concatenated block axis (vad_flags_batch_kernel above), then
+//   noise_batch_kernel         one wave per UTTERANCE walks its flags in order: main()'s run-length counter (SS:98-109),
+//                              the running average A <- h (A + |X|) of its events in registers (SS:165-187), a latch at
+//                              run length 10 (SS:189-193) into the row table, and per block the index of the row in
+//                              force.  All three start from zero at the utterance's first block.
+//   denoise_batch_kernel       denoise_run_kernel's frame over the concatenated block axis: the waves are planned over
+//                              all blocks, a wave finds its utterance by ragged_batch.h's search and walks on
+//   denoise_redo_f64_batch_kernel   the listed frames again in FP64, inside their utterance's bounds
+// An utterance holds a few hundred events where a stream holds tens of thousands, so the chain is not cut into affine
+// maps here: cutting it at positions of the batch would make an utterance's bits depend on where it stands.  Row 0 of
+// the table is zeros (nothing latched yet), shared by all utterances; an utterance of B blocks latches at most
+// floor(B / 10) times and sum floor(B_u / 10) <= floor(sum B_u / 10), so utterance u's rows start at
+// 1 + block_first[u] / 10 and no prefix sum over the utterances is needed.
+__device__ __forceinline__ void load_pairs(const short *__restrict__ block, int lane, unsigned int (&q)[4])
+{
+    const unsigned int *src = reinterpret_cast<const unsigned int *>(block) + lane;
+#pragma unroll
+    for (int r = 0; r < 4; r++) q[r] = src[64 * r];
+}
+
+__global__ __launch_bounds__(64) void noise_batch_kernel(const short *__restrict__ pcm,
+                                                         const long long *__restrict__ sample_first,
+                                                         const long long *__restrict__ block_first,
+                                                         const unsigned char *__restrict__ flags,
+                                                         const float2 *__restrict__ table, float *__restrict__ rows,
+                                                         int *__restrict__ row_idx, float *__restrict__ noise_last)
+{
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    const long u = blockIdx.x;
+    const long ub = uniform_i64(block_first + u), n_own = uniform_i64(block_first + u + 1) - ub;
+    const short *own = pcm + uniform_i64(sample_first + u);
+    FrameTables t;
+    load_frame_tables(t, table, lane);
+    PairTwiddles pw;
+    load_pair_twiddles(pw, table, lane);
+    // the average in noise_accum_kernel's pair-owned layout: bins m, m + 512 of m = lane + 64 d; a row is stored as its
+    // ten own values plus the mirrors of m = 1..192
+    constexpr int ND = 5;
+    float alo[ND], ahi[ND];
+#pragma unroll
+    for (int d = 0; d < ND; d++) alo[d] = ahi[d] = 0.0f;
+    auto store_row = [&](float *row) {
+#pragma unroll
+        for (int d = 0; d < ND; d++) { row[lane + 64 * d] = alo[d]; row[lane + 64 * d + 512] = ahi[d]; }
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int m = lane + 64 * d;
+            if (m >= 1 && m <= 192) { row[1024 - m] = alo[d]; row[512 - m] = ahi[d]; }
+        }
+    };
+    int run_len = 0, row = 0;                                    // iNumOfIteration (SS:72); the row in force
+    int next_row = 1 + (int)(ub / 10);
+    for (long c = 0; c < n_own; c += 64) {
+        const int n = n_own - c < 64 ? (int)(n_own - c) : 64;
+        const unsigned long long voice = __ballot(lane < n && flags[ub + c + lane] != 0);
+        int mine = 0;                                            // the row of block c + lane
+        for (int i = 0; i < n; i++) {
+            if ((voice >> i) & 1ull) {
+                run_len = 0;                                     // SS:108
+            } else if (++run_len >= 2) {                         // SS:103-105: EstimateNoiseSpectrum
+                const short *cur_block = own + (c + i) * 512;    // run length 2 at least: block c + i - 1 is the utterance's
+                unsigned int prev[4], cur[4];
+                load_pairs(cur_block - 512, lane, prev);         // rgssKeepBuffer (SS:165-170)
+                load_pairs(cur_block, lane, cur);
+                float2 v[8], zr[ND];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
+                    v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
+                    v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
+                }
+                wave_fft512<false>(v, lds, lane, t.tw);
+                wave_lds_fence();
+                pair_fetch_lds(v, lds, lane, zr);
+                const float h = run_len >= 3 ? 0.5f : 1.0f;      // SS:182-187
+#pragma unroll
+                for (int d = 0; d < ND; d++) {
+                    const float2 ev = cadd_conj(v[d], zr[d]), od = csub_conj_mj(v[d], zr[d]);
+                    const float2 tw = cmul(pw.w[d], od);
+                    const float2 lo = cadd(ev, tw), hi = csub(ev, tw);
+                    // hardware square root, 1 ulp (see noise_accum_kernel)
+                    alo[d] = (alo[d] + __builtin_amdgcn_sqrtf(lo.x * lo.x + lo.y * lo.y)) * h;
+                    ahi[d] = (ahi[d] + __builtin_amdgcn_sqrtf(hi.x * hi.x + hi.y * hi.y)) * h;
+                }
+                if (run_len == 10) {                             // SS:189-193; it applies to this block already
+                    row = next_row++;
+                    store_row(rows + (size_t)row * 1024);
+                    if (noise_last) store_row(noise_last + (size_t)u * 1024);
+                }
+            }
+            if (lane == i) mine = row;
+        }
+        if (lane < n) row_idx[ub + c + lane] = mine;
+    }
+    if (noise_last && row == 0) {                                // nothing latched: rgdEstimatedNS is still zero (SS:70)
+#pragma unroll
+        for (int r = 0; r < 16; r++) noise_last[(size_t)u * 1024 + lane + 64 * r] = 0.0f;
+    }
+}
+
+// denoise_run_kernel over the concatenated block axis.  Wave w owns the global blocks [w run, (w + 1) run); global
+// block j of utterance u (block_first[u] <= j < block_first[u + 1]) is its local block b = j - block_first[u] at the
+// samples base + 512 j.  Local block 0 only stashes its samples (SS:211-216), so the overlap restarts from zero by
+// itself where an utterance begins; the frame of local block b >= 1 is [block b - 1, block b], and with the overlap
+// it gives the enhanced samples at the time of block b - 1, written there when b >= 2 (SS:260-263: the first two
+// calls emit nothing).  So an utterance's first and last blocks are never written.  The halo frame in front of the
+// wave's first block goes through the SAME loop body as every other frame (emission off), never into the utterance
+// before: one inlined copy of the arithmetic, so the samples do not depend on where the waves are cut.
+template <int MODE>
+__global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_batch_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
+    long n_utts, long n_blocks, const int *__restrict__ row_idx, const float *__restrict__ noise_rows,
+    const float2 *__restrict__ table, short *__restrict__ out, float *__restrict__ precast, int run, int *__restrict__ redo)
+{
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    PhaseStat ps;
+    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
+    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * run;
+    if (j0 >= n_blocks) return;
+    const long j1 = j0 + run < n_blocks ? j0 + run : n_blocks;
+    long u = ragged_find_utt(block_first, n_utts, j0);
+    long ub = uniform_i64(block_first + u), ue = uniform_i64(block_first + u + 1);
+    long base = uniform_i64(sample_first + u) - ub * 512;      // global block j of this utterance starts at base + 512 j
+    // local block 0 or 1: the overlap entering block j0 is empty; else the frame of block j0 - 1 rebuilds it
+    const long js = j0 - ub >= 2 ? j0 - 1 : j0;
+
+    FrameTables t;
+    load_frame_tables(t, table, lane);
+    PairTwiddles sw;
+    load_pair_twiddles(sw, table, lane);
+    NoisePairRegs nz;
+    unsigned int raw[8], nxt[4], tk[4];
+    float2 tail[4], y[8];
+#pragma unroll
+    for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
+    // the block in front of js, clamped into the utterance (unused where it is clamped: local block 0 has no frame)
+    load_pairs(pcm + base + (js > ub ? js - 1 : ub) * 512, lane, nxt);
+#pragma unroll
+    for (int r = 0; r < 4; r++) raw[r + 4] = nxt[r];
+    load_pairs(pcm + base + js * 512, lane, tk);
+    int cur_row = -1;
+    int next_idx = __builtin_amdgcn_readfirstlane(row_idx[js]);
+    unsigned prio_step = blockIdx.x >> 10;                    // as in denoise_run_kernel
+    for (long j = js; j < j1; j++) {
+        switch (prio_step++ & 3u) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) { raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
+        const int idx = next_idx;
+        // the next block, needed one iteration from now (denoise_run_kernel); after an utterance's last block it is
+        // the first block of the next non-empty one
+        long un = u, ubn = ub, uen = ue, basen = base;
+        if (j + 1 < j1) {
+            if (j + 1 == ue) {
+                ubn = ue;
+                ragged_next_utt(block_first, n_utts, un, uen);
+                basen = uniform_i64(sample_first + un) - ubn * 512;
+            }
+            next_idx = row_idx[j + 1];
+            load_pairs(pcm + basen + (j + 1) * 512, lane, nxt);
+        }
+        const long b = j - ub;
+        if (b == 0) {
+            // the first call of a stream only stashes its block (SS:211-216): no output, empty overlap
+#pragma unroll
+            for (int d = 0; d < 8; d++) y[d] = make_float2(0.f, 0.f);
+        } else {
+            if (idx != cur_row) {                                // wave-uniform: another estimate is in force
+                cur_row = idx;
+                load_noise_pair_regs<MODE>(nz, noise_rows + (size_t)idx * 1024, lane);
+            }
+            denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);
+            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
+            if (MODE == 0 && j >= j0 && ue - ub >= 3 && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
+        }
+        float2 o[4];
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            o[d] = make_float2(tail[d].x + y[d].x, tail[d].y + y[d].y);      // SS:248 overlap-add
+            tail[d] = y[d + 4];                                               // SS:255-256
+        }
+        // taken before this block's stores (denoise_run_kernel)
+#pragma unroll
+        for (int r = 0; r < 4; r++) { tk[r] = nxt[r]; asm volatile("" : "+v"(tk[r])); }
+        next_idx = __builtin_amdgcn_readfirstlane(next_idx);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j >= j0 && b >= 2) {
+            const long at = base + (j - 1) * 512;                // the time of local block b - 1
+            if (out) {
+                unsigned int *dst = reinterpret_cast<unsigned int *>(out + at) + lane;
+#pragma unroll
+                for (int d = 0; d < 4; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
+            }
+            if (precast) {
+#pragma unroll
+                for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(precast + at + 2 * lane + 128 * d) = o[d];
+            }
+        }
+        u = un; ub = ubn; ue = uen; base = basen;
+    }
+}
+
+// denoise_redo_f64_kernel<1024> for the batch: a listed global frame f of utterance u (local b) adds into the outputs
+// of the local blocks b and b + 1, so the workgroup computes the frames b - 1, b, b + 1 that exist (local blocks
+// 1 .. B_u - 1: never the previous utterance's last frame, never the next one's first) and writes both outputs again
+// where the run kernel writes them: at the time of the local blocks b - 1 and b, if those are 1 .. B_u - 2.
+__global__ __launch_bounds__(256) void denoise_redo_f64_batch_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
+    long n_utts, const int *__restrict__ row_idx, const float *__restrict__ noise_rows, short *__restrict__ out,
+    float *__restrict__ precast, const int *__restrict__ redo, int mode)
+{
+    __shared__ double2 tw[512];
+    __shared__ double2 buf[1024];
+    __shared__ double yy[3][1024];
+    const int tid = threadIdx.x;
+    const long n_redo = redo[0];
+    if ((long)blockIdx.x >= n_redo) return;                     // (the whole workgroup)
+    double win[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int i = tid + 256 * r;
+        if (i < 512) {
+            double sn, cs;
+            sincospi(2.0 * (double)i / 1024.0, &sn, &cs);
+            tw[i] = make_double2(cs, -sn);
+        }
+        win[r] = 0.54 - 0.46 * cos(2 * 3.141592 * i / (1024 - 1));    // SS:226
+    }
+    for (long it = blockIdx.x; it < n_redo; it += gridDim.x) {
+        const long f = redo[1 + it];
+        const long u = ragged_find_utt(block_first, n_utts, f);
+        const long ub = uniform_i64(block_first + u), n_own = uniform_i64(block_first + u + 1) - ub;
+        const long first = uniform_i64(sample_first + u), b = f - ub;
+        for (int q = 0; q < 3; q++) {
+            const long bq = b - 1 + q;
+            const bool have = bq >= 1 && bq < n_own;              // (uniform) local block 0 only stashes its samples
+            __syncthreads();
+            if (!have) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) yy[q][tid + 256 * r] = 0.0;
+                continue;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int i = tid + 256 * r;
+                buf[__brev((unsigned)i) >> 22] = make_double2((double)pcm[first + (bq - 1) * 512 + i] * win[r], 0.0);
+            }
+            redo_gain_frame<1024>(buf, tw, noise_rows + (size_t)row_idx[ub + bq] * 1024, mode, tid, yy[q]);
+        }
+        __syncthreads();
+        for (int q = 0; q < 2; q++) {
+            const long bo = b + q;                                // its output lies at the time of local block bo - 1
+            if (bo < 2 || bo >= n_own) continue;
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const int i = tid + 256 * r;
+                const float o = (float)(yy[q][512 + i] + yy[q + 1][i]);                 // SS:248 overlap-add
+                const long at = first + (bo - 1) * 512 + i;
+                if (out) out[at] = (short)cast_i16_bits(o);
+                if (precast) precast[at] = o;
+            }
+        }
+    }
+}
+
+// run_opt: blocks per wave, 0 = one round of resident waves as launch_denoise1024 plans it.  flags / row_idx
+// [n_blocks], rows [n_blocks / 10 + 1][1024] with row 0 zero, redo [n_blocks + 1]: the handle's batch workspace.
+// out and precast may be NULL (both: the run kernel is not launched); noise_last may be NULL.
+int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *sample_first,
+                         const long long *block_first, long n_utts, long n_blocks, const double *w_hi,
+                         const float2 *table, unsigned char *flags, int *row_idx, float *rows, int *redo, short *out,
+                         float *precast, float *noise_last, int vad_only)
+{
+    if (n_blocks <= 0 || n_utts <= 0) return 0;
+    hipLaunchKernelGGL(vad_flags_batch_kernel, dim3((unsigned)((n_blocks + kVadBlocksPerWave - 1) / kVadBlocksPerWave)),
+                       dim3(64), 0, s, pcm, sample_first, block_first, n_utts, n_blocks, w_hi, flags);
+    if (vad_only) return hipGetLastError() == hipSuccess ? 0 : -1;
+    hipLaunchKernelGGL(noise_batch_kernel, dim3((unsigned)n_utts), dim3(64), 0, s, pcm, sample_first, block_first, flags,
+                       table, rows, row_idx, noise_last);
+    if (!out && !precast) return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (mode == 0 && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
+    long run = run_opt;
+    if (run <= 0) {
+        const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_DENOISE_RESIDENT;
+        long waves = (n_blocks + 3) / 4;
+        if (waves > slots) waves = slots;
+        run = (n_blocks + waves - 1) / waves;
+    }
+    const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
+    if (mode == 0)
+        hipLaunchKernelGGL(denoise_batch_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, sample_first, block_first,
+                           n_utts, n_blocks, row_idx, rows, table, out, precast, (int)run, redo);
+    else
+        hipLaunchKernelGGL(denoise_batch_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, sample_first, block_first,
+                           n_utts, n_blocks, row_idx, rows, table, out, precast, (int)run, redo);
+    if (mode == 0)
+        hipLaunchKernelGGL(denoise_redo_f64_batch_kernel, dim3((unsigned)(n_blocks < kRedoGrid ? n_blocks : kRedoGrid)),
+                           dim3(256), 0, s, pcm, sample_first, block_first, n_utts, row_idx, rows, out, precast, redo, mode);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 // ---- launchers of both frame sizes --------------------------------------------------------------

@@ -345,6 +345,12 @@ int launch_shard_rows(hipStream_t s, DenoiseGeom g, const float *summaries_all, 
                       const DenoisePlan *plan, const int *range, const NoiseAccum &acc, float *a_in, float *rows,
                       float *last);
 int launch_shard_row0(hipStream_t s, DenoiseGeom g, const float *last_all, int rank, float *rows);
+// a batch of ragged utterances, each a fresh 1024-point stream (jdsp_denoise_batch_dev's layout): the VAD, the noise
+// pass (one wave per utterance), the run kernel and, for spectral subtraction, the FP64 pass
+int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *sample_first,
+                         const long long *block_first, long n_utts, long n_blocks, const double *w_hi,
+                         const float2 *table, unsigned char *flags, int *row_idx, float *rows, int *redo, short *out,
+                         float *precast, float *noise_last, int vad_only);
 int ensure_stft1024_table(jdsp_ctx *ctx);
 int ensure_vad_window(jdsp_ctx *ctx);
 // FP64 Hamming(2 block_len) over the positions a block occupies in the VAD's frame: keep + i, keep = block_len (SS:127-128)
@@ -607,8 +613,16 @@ struct jdsp_denoise {
         jdsp::DevBuf<int> lat_chunk;
         jdsp::DevBuf<int> redo;           // [n + 1] {count, frames...}: spectral-subtraction frames computed again in FP64
     } ws;
+    // sized by jdsp_denoise_batch_reserve for batches of up to cap_blocks blocks in up to cap_utts utterances
+    struct BatchWs {
+        jdsp::DevBuf<unsigned char> flags; // [n] the VAD's decision per block of the batch
+        jdsp::DevBuf<int> row_idx;         // [n] the latched row in force at each block
+        jdsp::DevBuf<float> rows;          // [n / 10 + 1][1024]; row 0 stays zero: no estimate latched yet
+        jdsp::DevBuf<int> redo;            // [n + 1] {count, frames...} as ws.redo
+        long cap_blocks = -1, cap_utts = -1;
+    } bws;
     long last_blocks = 0;
-    int redo_valid = 0;                   // ws.redo[0] is the last call's count (jdsp_denoise_frames_recomputed)
+    int redo_valid = 0;                   // the last call's count is there for jdsp_denoise_frames_recomputed: 1 in ws.redo[0], 2 in bws.redo[0]
     int opt_k = 0;
     int opt_vad_trace = 0;                // 1: keep every block's energy sum and ZCR for jdsp_denoise_vad_trace (slower VAD kernel)
     int last_trace_valid = 0;             // the option's value when the last call ran: what jdsp_denoise_vad_trace may hand out

@@ -436,6 +436,77 @@ class Denoiser(_Child):
         assert got.value == n_out
         return (out[:n_out * B], pre[:n_out * B]) if want_precast else out[:n_out * B]
 
+    def reserve_batch(self, max_blocks_total, max_utts):
+        """Sizes the workspace of process_batch's device path (jdsp_denoise_batch_reserve): the only call of the batch
+        entries that allocates.  Call it before capturing process_batch in a graph."""
+        self.eng._ck(L.jdsp_denoise_batch_reserve(self._h, int(max_blocks_total), int(max_utts)))
+
+    def process_batch(self, pcm, block_counts, utt_sample_first=None, want_precast=False, want_flags=False,
+                      want_noise=False, out=None):
+        """A batch of independent utterances in one launch sequence (jdsp_denoise_batch): each comes out as a fresh
+        handle's process of its blocks, and the handle's own stream is neither read nor advanced.  (1024, 512) handles.
+        pcm: int16; block_counts: B_u >= 0 blocks of self.block samples per utterance (a host sequence);
+        utt_sample_first: the n_utts even sample offsets of the spans, ascending and disjoint (None: packed back to
+        back, sharding.denoise_batch_layout).  torch CUDA (the device entry on torch's current stream; it reserves on
+        demand, so call reserve_batch first under graph capture) or numpy (the host entry).  Returns int16 of pcm's
+        length, TIME-ALIGNED with pcm: the enhanced samples of utterance u's blocks 1 .. B_u - 2 lie where those blocks
+        lie in pcm; everything else is zero, or is left as it was in `out` when given on the device path.  With
+        want_precast / want_flags / want_noise a tuple follows the same order: float32 samples before the cast, uint8
+        VAD decisions [sum B_u] in concatenated block order, float32 [n_utts, 1024] estimates in force after each
+        utterance's last block."""
+        from .sharding import denoise_batch_layout
+        counts = np.ascontiguousarray(block_counts, np.int64).reshape(-1)
+        packed, block_first, n_packed = denoise_batch_layout(counts, self.block)
+        if utt_sample_first is None:
+            sample_first = packed
+        else:
+            sample_first = np.ascontiguousarray(utt_sample_first, np.int64).reshape(-1)[:counts.size]
+            assert sample_first.size == counts.size
+        n_utts, n_total, n_samples = counts.size, int(block_first[-1]), int(pcm.shape[0])
+        assert pcm.ndim == 1
+        pre = flags = noise = None
+        if _is_torch(pcm):
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            dev = pcm.device
+            assert n_utts == 0 or int((sample_first + counts * self.block).max()) <= n_samples
+            key = (sample_first.tobytes(), counts.tobytes(), dev)
+            if getattr(self, "_batch_key", None) != key:        # the offsets of the last batch stay on the device
+                self._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(block_first).to(dev))
+                self._batch_key = key
+                self.reserve_batch(n_total, n_utts)             # a no-op once sized
+            d_sample, d_block = self._batch_dev
+            if out is None:
+                out = torch.zeros(max(n_samples, 1), dtype=torch.int16, device=dev)
+            if want_precast:
+                pre = torch.zeros(max(n_samples, 1), dtype=torch.float32, device=dev)
+            if want_flags:
+                flags = torch.zeros(max(n_total, 1), dtype=torch.uint8, device=dev)
+            if want_noise:
+                noise = torch.zeros(max(n_utts, 1), 1024, dtype=torch.float32, device=dev)
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_denoise_batch_dev(self._h, _vp(pcm), _vp(d_sample), _vp(d_block), n_utts, n_total, _vp(out),
+                                                  _vp(pre), _vp(flags), _vp(noise)))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            out = np.zeros(max(n_samples, 1), np.int16) if out is None else out
+            if want_precast:
+                pre = np.zeros(max(n_samples, 1), np.float32)
+            if want_flags:
+                flags = np.zeros(max(n_total, 1), np.uint8)
+            if want_noise:
+                noise = np.zeros((max(n_utts, 1), 1024), np.float32)
+            self.eng._ck(L.jdsp_denoise_batch(self._h, _vp(pcm), n_samples, _vp(sample_first), _vp(block_first), n_utts,
+                                              _vp(out), _vp(pre), _vp(flags), _vp(noise)))
+        res = [out[:n_samples]]
+        if want_precast:
+            res.append(pre[:n_samples])
+        if want_flags:
+            res.append(flags[:n_total])
+        if want_noise:
+            res.append(noise[:n_utts])
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ---- one rank's share of a global stream (jdsp_denoise_shard_*; driver: sharding.denoise_sharded)
     def shard_vad(self, pcm_ext, ext0, b0, b1, n_total):
         import torch

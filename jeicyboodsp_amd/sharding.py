@@ -190,6 +190,21 @@ def istft_batch_layout(frame_counts, n_fft, hop):
             np.concatenate([zero, np.cumsum(counts, dtype=np.int64)]))
 
 
+def denoise_batch_layout(block_counts, hop):
+    """The back-to-back packing of a batch of utterances for Denoiser.process_batch (jdsp_denoise_batch): utterance u
+    of B_u = block_counts[u] >= 0 blocks of hop samples takes hop B_u samples, and the spans follow each other
+    without a gap.  Returns (sample_first [n_utts], block_first [n_utts + 1], n_samples) with the two arrays as numpy
+    int64; the offsets are even because hop is.  Negative counts or an odd hop: ValueError."""
+    import numpy as np
+    counts = np.asarray(block_counts, dtype=np.int64).reshape(-1)
+    if np.any(counts < 0):
+        raise ValueError("block counts must be >= 0")
+    if hop <= 0 or hop % 2:
+        raise ValueError("hop must be even and > 0")
+    block_first = np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)])
+    return np.ascontiguousarray(block_first[:-1] * hop), block_first, int(block_first[-1]) * int(hop)
+
+
 def stftmask_batch_shard(frame_counts, rank, world):
     """Batched fused STFT masking (StftMask.process_batch) over `world` ranks: whole utterances per rank, contiguous,
     balanced by frame count (utterance_shard); an utterance is a stream of its own, so there is no halo and no
@@ -197,7 +212,8 @@ def stftmask_batch_shard(frame_counts, rank, world):
     utt_sample_first[first_utt] .. utt_sample_first[first_utt + n_utt] and the mask rows
     frame_first[first_utt] .. frame_first[first_utt + n_utt], with the offsets rebased to its first sample.
     The batched analysis and synthesis (Engine.stft_half_batch, Istft.process_batch) share the layout and are split by
-    this same function: their spectrum rows take the place of the mask rows."""
+    this same function: their spectrum rows take the place of the mask rows.  So is the batched denoiser
+    (Denoiser.process_batch): pass its block counts, and rebase denoise_batch_layout's offsets the same way."""
     return utterance_shard([int(f) for f in frame_counts], rank, world)
 
 

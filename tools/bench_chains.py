@@ -396,6 +396,68 @@ def main():
                    "BASELINE config 3 as worded: FFT_PROCESSING_SIZE 512, BLOCK_LEN 256; 65,536 blocks of 256",
                    cpu=cpu_rate(lambda: orc.denoise_stream(mode, x5[:1024 * 256], block=256), 1024))
             d.close()
+    if on("denoise_batch"):
+        # Batched spectral subtraction / Wiener (jdsp_denoise_batch_dev) on the stftmask_batch leg's 10,000 seeded
+        # utterances (100..500 blocks of 512 each, packed), every utterance with a quiet lead of 12 blocks so that an
+        # estimate latches at its block 9.  Timed three ways in this process, in alternated rounds: (a) the batch entry;
+        # (b) jdsp_denoise_reset + jdsp_denoise_process_dev per utterance on one handle, from ctypes with every argument
+        # computed beforehand; (c) ONE jdsp_denoise_process_dev over the same buffer as a single stream of the same
+        # block count (a continuing stream: its pre-passes run in their long-stream forms, and its output differs).
+        # The PCM (3 GB) is far past the 256 MiB Infinity Cache, so one copy already comes from HBM.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        lens = 2 * np.random.default_rng(10000).integers((1024 + 99 * 512) // 2, (1024 + 500 * 512) // 2, 10000)
+        counts, _ = sharding.stftmask_batch_layout(np.concatenate([[0], np.cumsum(lens)]), 1024, 512)
+        sample_first, block_first, n_samples = sharding.denoise_batch_layout(counts, 512)
+        total = int(block_first[-1])
+        gen = torch.Generator(device="cuda").manual_seed(10000)
+        sigma = torch.full((total,), 3000.0, device="cuda")
+        lead = torch.from_numpy((block_first[:-1, None] + np.arange(12)[None, :]).ravel()).cuda()
+        sigma[lead] = 45.0
+        x = torch.empty(n_samples, dtype=torch.int16, device="cuda")
+        for lo in range(0, total, 1 << 18):                     # in slabs: the float32 draft of 1.5 G samples is 6 GB
+            hi = min(lo + (1 << 18), total)
+            draft = torch.randn((hi - lo, 512), device="cuda", generator=gen) * sigma[lo:hi, None]
+            x[lo * 512:hi * 512] = draft.round_().clamp_(-32768, 32767).to(torch.int16).view(-1)
+        del draft, sigma, lead
+        o16 = torch.empty(n_samples, dtype=torch.int16, device="cuda")
+        it = max(a.iters // 4, 3)
+        what = "10,000 ragged utterances, %d blocks (%d..%d each), 12 quiet blocks in front of each" % (total, counts.min(), counts.max())
+        inp = "one copy: %.1f GB of PCM per call (from HBM)" % (2e-9 * n_samples)
+        flops = 2 * 5 * 512 * 9 + 2 * 512 * 14
+        for mode, nm in ((0, "specsub"), (1, "wiener")):
+            d_a, d_b, d_c = eng.denoiser(mode), eng.denoiser(mode), eng.denoiser(mode)
+            d_a.reserve_batch(total, len(counts))
+            eng._ck(L.jdsp_denoise_reserve(d_b._h, int(counts.max())))
+            eng._ck(L.jdsp_denoise_reserve(d_c._h, total))
+            px, po = x.data_ptr(), o16.data_ptr()
+            calls = [(d_b._h, C.c_void_p(px + 2 * int(sample_first[u])), int(counts[u]),
+                      C.c_void_p(po + 2 * int(sample_first[u])), None, None) for u in range(len(counts))]
+            stream_args = (d_c._h, C.c_void_p(px), total, C.c_void_p(po), None, None)
+            eng._use_torch_stream()
+
+            def loop():
+                for p in calls:
+                    L.jdsp_denoise_reset(p[0])
+                    L.jdsp_denoise_process_dev(*p)
+
+            batch = lambda: d_a.process_batch(x, counts, sample_first, out=o16)  # noqa: E731
+            stream = lambda: L.jdsp_denoise_process_dev(*stream_args)  # noqa: E731
+            ms_a, ms_c, ms_b = timed_alternated([batch, stream, loop], [it, it, 1], rounds=3)
+            n_redo = d_a.frames_recomputed()
+            report("denoise_batch_" + nm, ms_a, total, "blocks", 2048, flops,
+                   "(a) jdsp_denoise_batch_dev: %s; %.2f x the single stream (c), %.3f of the per-utterance loop (b); "
+                   "%d frames through the FP64 pass" % (what, ms_a / ms_c, ms_a / ms_b, n_redo), inp=inp)
+            report("denoise_batch_" + nm + "_per_utterance_loop", ms_b, total, "blocks", 2048, flops,
+                   "(b) the same batch as 10,000 x (jdsp_denoise_reset + jdsp_denoise_process_dev) on one handle, from "
+                   "ctypes with precomputed arguments: %.1f x the batch entry" % (ms_b / ms_a), inp=inp)
+            report("denoise_batch_" + nm + "_single_stream", ms_c, total, "blocks", 2048, flops,
+                   "(c) ONE continuing stream of the same %d blocks over the same buffer, one jdsp_denoise_process_dev" % total,
+                   inp=inp)
+            for d in (d_a, d_b, d_c):
+                d.close()
+        del x, o16
     if on("mfcc"):
         x = torch.from_numpy(pcm_of(rng, 512 * (B + 1))).cuda()
         xr = rot(x)
