@@ -437,8 +437,8 @@ static int batch_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_t *sam
     if (n_utts < 0 || n_blocks_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: n_utts or n_blocks_total < 0");
     int rc = batch_supported(h, "jdsp_denoise_batch");
     if (rc) return rc;
-    if (((uintptr_t)pcm_dev & 15u) || ((uintptr_t)out_dev & 15u) || ((uintptr_t)precast_dev & 7u) ||
-        ((uintptr_t)noise_last_dev & 3u) || ((uintptr_t)sample_first_dev & 7u) || ((uintptr_t)block_first_dev & 7u))
+    if (!jdsp::aligned(pcm_dev, 16) || !jdsp::aligned(out_dev, 16) || !jdsp::aligned(precast_dev, 8) ||
+        !jdsp::aligned(noise_last_dev, 4) || !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(block_first_dev, 8))
         return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: pcm and out must be 16-byte, precast and the offset arrays "
                                       "8-byte, noise_last 4-byte aligned");
     h->redo_valid = 0;
@@ -483,34 +483,23 @@ int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples,
 {
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
-    const long hop = h->block;
     if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: n_utts or n_samples < 0");
     int rc = batch_supported(h, "jdsp_denoise_batch");
     if (rc) return rc;
     if (n_utts > 0 && (!sample_first_host || !block_first_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: sample_first or block_first is NULL");
-    // everything the kernels take on trust from device-side offsets is checked here (as jdsp_stftmask_batch)
-    if (n_utts > 0 && block_first_host[0] != 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: block_first[0] must be 0");
-    long end = 0, longest = 0;                                 // one past the last sample of the spans so far
-    for (long u = 0; u < n_utts; u++) {
-        const long b = block_first_host[u + 1] - block_first_host[u], s = sample_first_host[u];
-        if (b < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: block_first must not decrease");
-        if (s < 0 || (s & 1)) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: sample_first entries must be even and >= 0");
-        if (s < end)
-            return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: sample_first must ascend and the utterances' spans must not overlap");
-        if (s > n_samples || b > (n_samples - s) / hop)
-            return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: an utterance's span ends past n_samples");
-        end = s + hop * b;
-        if (b > longest) longest = b;
-    }
-    const long n_total = n_utts > 0 ? block_first_host[n_utts] : 0;
+    jdsp::RaggedOffsets offs;                                  // a span of b blocks is b hops: n = hop
+    if (offs.check(ctx, "jdsp_denoise_batch", "block_first", sample_first_host, block_first_host, n_utts, n_samples,
+                   h->block, h->block))
+        return JDSP_EINVAL;
+    const long n_total = offs.lay.n_total, end = offs.lay.end;
     // what no launch writes is zero: everything outside the spans, the spans' first and last blocks, the estimate of
     // an utterance too short to latch
     if (out_host && n_samples) memset(out_host, 0, (size_t)n_samples * sizeof(int16_t));
     if (precast_host && n_samples) memset(precast_host, 0, (size_t)n_samples * sizeof(float));
     if (noise_last_host && n_utts) memset(noise_last_host, 0, (size_t)n_utts * 1024 * sizeof(float));
     h->redo_valid = 0;
-    const bool vad_only = longest <= 2;
+    const bool vad_only = offs.lay.longest <= 2;
     if (n_total == 0 || (vad_only ? !flags_host : (!out_host && !precast_host && !flags_host && !noise_last_host)))
         return JDSP_OK;                                        // nothing to launch
     if (!pcm_host) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_batch: pcm is NULL");
@@ -518,8 +507,7 @@ int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples,
     rc = jdsp_denoise_batch_reserve(h, n_total, n_utts);
     if (rc) return rc;
     jdsp::HostCall hc(ctx, "jdsp_denoise_batch");
-    const int64_t *d_sample = hc.upload(sample_first_host, (size_t)n_utts * sizeof(int64_t));
-    const int64_t *d_block = hc.upload(block_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    offs.upload(hc);
     const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));         // nothing past the last span is read
     const bool run = !vad_only;
     int16_t *d_out = run && out_host ? hc.alloc<int16_t>((size_t)end * sizeof(int16_t)) : nullptr;
@@ -529,7 +517,7 @@ int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples,
     if (d_out) hc.zero(d_out, (size_t)end * sizeof(int16_t));
     if (d_pre) hc.zero(d_pre, (size_t)end * sizeof(float));
     if (hc.ok())
-        hc.result(batch_dev(h, d_pcm, d_sample, d_block, n_utts, n_total, d_out, d_pre, d_flags, d_noise, vad_only));
+        hc.result(batch_dev(h, d_pcm, offs.d_sample, offs.d_unit, n_utts, n_total, d_out, d_pre, d_flags, d_noise, vad_only));
     hc.download(out_host, d_out, d_out ? (size_t)end * sizeof(int16_t) : 0);
     hc.download(precast_host, d_pre, d_pre ? (size_t)end * sizeof(float) : 0);
     hc.download(flags_host, d_flags, (size_t)n_total);

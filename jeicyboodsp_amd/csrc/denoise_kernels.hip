@@ -1125,6 +1125,17 @@ int launch_run_plan(hipStream_t s, const unsigned char *flags, long n_blocks, co
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// Blocks per wave of the run kernels (denoise_run_kernel, denoise_batch_kernel) for one round of resident waves:
+// JDSP_DENOISE_RESIDENT per SIMD, 4 SIMDs per CU; never fewer than 4 blocks per wave (a quarter of halo overhead at
+// most).  The grid is ceil(n_blocks / run) waves, rounded up to eight.
+static long resident_run(int n_cu, long n_blocks)
+{
+    const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_DENOISE_RESIDENT;
+    long waves = (n_blocks + 3) / 4;
+    if (waves > slots) waves = slots;
+    return (n_blocks + waves - 1) / waves;
+}
+
 template <int MODE, int K>
 static void launch_dn(hipStream_t s, const short *pcm, long n_blocks, long calls_before, const DenoiseState *st_in,
                       DenoiseState *st_out, const int *ver_base, const unsigned long long *snap_mask,
@@ -1142,14 +1153,8 @@ static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, cons
                              float *precast, const DenoiseShard &sh, int *redo)
 {
     if (k_opt == 0) {
-        // one round of resident waves: JDSP_DENOISE_RESIDENT per SIMD, 4 SIMDs per CU; never fewer than 4 blocks
-        // per wave (a quarter of halo overhead at most)
-        const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_DENOISE_RESIDENT;
-        long waves = (n_blocks + 3) / 4;
-        if (waves > slots) waves = slots;
-        long run = (n_blocks + waves - 1) / waves;
-        waves = (n_blocks + run - 1) / run;
-        const long grid = (waves + 7) / 8 * 8;
+        const long run = resident_run(n_cu, n_blocks);
+        const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
         if (mode == 0)
             hipLaunchKernelGGL(denoise_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
                                st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
@@ -1966,7 +1971,7 @@ __global__ __launch_bounds__(256) void denoise_redo_f64_batch_kernel(
     }
 }
 
-// run_opt: blocks per wave, 0 = one round of resident waves as launch_denoise1024 plans it.  flags / row_idx
+// run_opt: blocks per wave, 0 = one round of resident waves (resident_run).  flags / row_idx
 // [n_blocks], rows [n_blocks / 10 + 1][1024] with row 0 zero, redo [n_blocks + 1]: the handle's batch workspace.
 // out and precast may be NULL (both: the run kernel is not launched); noise_last may be NULL.
 int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *sample_first,
@@ -1982,13 +1987,7 @@ int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const s
                        table, rows, row_idx, noise_last);
     if (!out && !precast) return hipGetLastError() == hipSuccess ? 0 : -1;
     if (mode == 0 && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
-    long run = run_opt;
-    if (run <= 0) {
-        const long slots = (long)(n_cu > 0 ? n_cu : 256) * 4 * JDSP_DENOISE_RESIDENT;
-        long waves = (n_blocks + 3) / 4;
-        if (waves > slots) waves = slots;
-        run = (n_blocks + waves - 1) / waves;
-    }
+    const long run = run_opt > 0 ? run_opt : resident_run(n_cu, n_blocks);
     const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
     if (mode == 0)
         hipLaunchKernelGGL(denoise_batch_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, sample_first, block_first,

@@ -91,7 +91,7 @@ int jdsp_istft_process_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pit
     jdsp_ctx *ctx = h->ctx;
     if (n_frames < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_process: n_frames < 0");
     if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_process: row_pitch below the layout's bins");
-    if (!OlaStream::aligned(spec_dev, 8) || !OlaStream::aligned(out_i16_dev, 4) || !OlaStream::aligned(out_f32_dev, 8))
+    if (!jdsp::aligned(spec_dev, 8) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8))
         return fail(ctx, JDSP_EINVAL, "jdsp_istft_process: spec must be 8-byte, out_i16 4-byte, out_f32 8-byte aligned");
     if (n_frames == 0) return JDSP_OK;
     if (!spec_dev) return fail(ctx, JDSP_EINVAL, "jdsp_istft_process: spec is NULL");
@@ -146,8 +146,8 @@ int jdsp_istft_batch_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitch
     jdsp_ctx *ctx = h->ctx;
     if (n_utts < 0 || n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: n_utts or n_frames_total < 0");
     if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: row_pitch below the layout's bins");
-    if (!OlaStream::aligned(spec_dev, 8) || !OlaStream::aligned(out_i16_dev, 4) || !OlaStream::aligned(out_f32_dev, 8) ||
-        !OlaStream::aligned(sample_first_dev, 8) || !OlaStream::aligned(frame_first_dev, 8))
+    if (!jdsp::aligned(spec_dev, 8) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
+        !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(frame_first_dev, 8))
         return fail(ctx, JDSP_EINVAL,
                     "jdsp_istft_batch: spec, out_f32 and the offset arrays must be 8-byte, out_i16 4-byte aligned");
     if (n_utts == 0 || n_frames_total == 0) return JDSP_OK;
@@ -169,25 +169,15 @@ int jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, c
 {
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
-    const long n = h->cfg.n_fft, hop = h->cfg.hop;
     if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: n_utts or n_samples < 0");
     if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: row_pitch below the layout's bins");
     if (n_utts > 0 && (!sample_first_host || !frame_first_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: sample_first or frame_first is NULL");
-    // everything the kernel takes on trust from device-side offsets is checked here (as jdsp_stftmask_batch)
-    if (n_utts > 0 && frame_first_host[0] != 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: frame_first[0] must be 0");
-    long end = 0;                                              // one past the last sample of the spans so far
-    for (long u = 0; u < n_utts; u++) {
-        const long f = frame_first_host[u + 1] - frame_first_host[u], s = sample_first_host[u];
-        if (f < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: frame_first must not decrease");
-        if (s < 0 || (s & 1)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: sample_first entries must be even and >= 0");
-        if (s < end)
-            return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: sample_first must ascend and the utterances' spans must not overlap");
-        if (s > n_samples || (f > 0 && (n_samples - s < n || f - 1 > (n_samples - s - n) / hop)))
-            return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: an utterance's span ends past n_samples");
-        end = f > 0 ? s + hop * (f - 1) + n : s;
-    }
-    const long n_total = n_utts > 0 ? frame_first_host[n_utts] : 0;
+    jdsp::RaggedOffsets offs;
+    if (offs.check(ctx, "jdsp_istft_batch", "frame_first", sample_first_host, frame_first_host, n_utts, n_samples,
+                   h->cfg.n_fft, h->cfg.hop))
+        return JDSP_EINVAL;
+    const long n_total = offs.lay.n_total;
     if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
         if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
         if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
@@ -202,13 +192,13 @@ int jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, c
     if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
     if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_istft_batch: buffers", e);
     jdsp::HostCall hc(ctx, "jdsp_istft_batch");
-    const int64_t *d_sample = hc.upload(sample_first_host, (size_t)n_utts * sizeof(int64_t));
-    const int64_t *d_frame = hc.upload(frame_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    offs.upload(hc);
     hc.upload_to(h->h_spec.get(), spec_host, n_in * sizeof(jdsp_c32));
     if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the spans
     if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
     if (hc.ok())
-        hc.result(jdsp_istft_batch_dev(h, h->h_spec.get(), row_pitch, d_sample, d_frame, n_utts, n_total, d_i16, d_f32));
+        hc.result(jdsp_istft_batch_dev(h, h->h_spec.get(), row_pitch, offs.d_sample, offs.d_unit, n_utts, n_total, d_i16,
+                                       d_f32));
     h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
     return hc.finish();
 }

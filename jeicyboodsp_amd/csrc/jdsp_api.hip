@@ -434,8 +434,8 @@ int jdsp_stft_half_batch_dev(jdsp_ctx *ctx, const int16_t *pcm_dev, const int64_
     if (hop != 1024 && hop != 512 && hop != 256)
         return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: hop must be 1024, 512 or 256 (n_fft, n_fft/2 or n_fft/4)");
     if (row_pitch < 514 || (row_pitch & 1)) return fail(ctx, JDSP_EINVAL, kStftBatchPitch);
-    if (((uintptr_t)pcm_dev & 3u) || ((uintptr_t)spec_dev & 15u) || ((uintptr_t)sample_first_dev & 7u) ||
-        ((uintptr_t)frame_first_dev & 7u))
+    if (!jdsp::aligned(pcm_dev, 4) || !jdsp::aligned(spec_dev, 16) || !jdsp::aligned(sample_first_dev, 8) ||
+        !jdsp::aligned(frame_first_dev, 8))
         return fail(ctx, JDSP_EINVAL,
                     "jdsp_stft_half_batch: pcm must be 4-byte, spec 16-byte and the offset arrays 8-byte aligned");
     if (n_utts == 0 || n_frames_total == 0) return JDSP_OK;
@@ -593,36 +593,26 @@ int jdsp_stft_half_batch(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples,
                          const int64_t *frame_first_host, long n_utts, int hop, jdsp_c32 *spec_host, long row_pitch)
 {
     if (!ctx) return JDSP_EINVAL;
-    const long n = 1024;
     if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: n_utts or n_samples < 0");
     if (hop != 1024 && hop != 512 && hop != 256)
         return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: hop must be 1024, 512 or 256 (n_fft, n_fft/2 or n_fft/4)");
     if (row_pitch < 514 || (row_pitch & 1)) return fail(ctx, JDSP_EINVAL, kStftBatchPitch);
     if (n_utts > 0 && (!sample_first_host || !frame_first_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: sample_first or frame_first is NULL");
-    // everything the kernel takes on trust from device-side offsets is checked here (as jdsp_stftmask_batch)
-    if (n_utts > 0 && frame_first_host[0] != 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: frame_first[0] must be 0");
-    long end = 0;                                              // one past the last sample of the spans so far
-    for (long u = 0; u < n_utts; u++) {
-        const long f = frame_first_host[u + 1] - frame_first_host[u], s = sample_first_host[u];
-        if (f < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: frame_first must not decrease");
-        if (s < 0 || (s & 1)) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: sample_first entries must be even and >= 0");
-        if (s < end)
-            return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: sample_first must ascend and the utterances' spans must not overlap");
-        if (s > n_samples || (f > 0 && (n_samples - s < n || f - 1 > (n_samples - s - n) / hop)))
-            return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: an utterance's span ends past n_samples");
-        end = f > 0 ? s + hop * (f - 1) + n : s;
-    }
-    const long n_total = n_utts > 0 ? frame_first_host[n_utts] : 0;
+    jdsp::RaggedOffsets offs;
+    if (offs.check(ctx, "jdsp_stft_half_batch", "frame_first", sample_first_host, frame_first_host, n_utts, n_samples, 1024,
+                   hop))
+        return JDSP_EINVAL;
+    const long n_total = offs.lay.n_total;
     if (n_total == 0) return JDSP_OK;
     if (!pcm_host || !spec_host) return fail(ctx, JDSP_EINVAL, "jdsp_stft_half_batch: pcm or spec is NULL");
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
     jdsp::HostCall hc(ctx, "jdsp_stft_half_batch");
-    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));  // nothing past the last span is read
-    const int64_t *d_sample = hc.upload(sample_first_host, (size_t)n_utts * sizeof(int64_t));
-    const int64_t *d_frame = hc.upload(frame_first_host, (size_t)(n_utts + 1) * sizeof(int64_t));
+    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)offs.lay.end * sizeof(int16_t));   // nothing past the last span is read
+    offs.upload(hc);
     jdsp_c32 *d_spec = hc.alloc<jdsp_c32>(((size_t)(n_total - 1) * row_pitch + 513) * sizeof(jdsp_c32));
-    if (hc.ok()) hc.result(jdsp_stft_half_batch_dev(ctx, d_pcm, d_sample, d_frame, n_utts, n_total, hop, d_spec, row_pitch));
+    if (hc.ok())
+        hc.result(jdsp_stft_half_batch_dev(ctx, d_pcm, offs.d_sample, offs.d_unit, n_utts, n_total, hop, d_spec, row_pitch));
     if (hc.ok()) {
         // the 513 bins of every row: what lies between the rows on the host stays as it is
         const hipError_t e = hipMemcpy2DAsync(spec_host, (size_t)row_pitch * sizeof(jdsp_c32), d_spec,

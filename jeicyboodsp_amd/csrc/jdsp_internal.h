@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/jdsp.h"
+#include "ragged_layout.h"
 
 namespace jdsp {
 
@@ -179,6 +180,8 @@ struct MfccDev {
 };
 
 int fail(jdsp_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
+// a: a power of two.  NULL is aligned to anything: whether a pointer may be NULL is a question of its own
+inline bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 #define JDSP_HIP(ctx, call)                                             \
     do {                                                                \
@@ -252,6 +255,33 @@ private:
     DevBuf<char> buf_[kMaxBufs];
     int n_ = 0;
     int rc_ = JDSP_OK;
+};
+
+// The two offset arrays of a host entry over a batch of ragged utterances (ragged_layout.h; the kernels' walk over
+// them: ragged_batch.h).  check() comes behind the entry's own argument checks and reports a bad layout as the
+// entry's JDSP_EINVAL; upload() then brings both arrays to the device for the *_dev twin.
+struct RaggedOffsets {
+    RaggedLayout lay;                                      // check()'s end, n_total and longest
+    const int64_t *d_sample = nullptr, *d_unit = nullptr;  // upload()'s: [n_utts] and [n_utts + 1]
+
+    // axis: the unit array's name in the entry's messages, "frame_first" or "block_first"
+    int check(jdsp_ctx *ctx, const char *entry, const char *axis, const int64_t *sample_first, const int64_t *unit_first,
+              long n_utts, long n_samples, long n, long hop)
+    {
+        sample_ = sample_first, unit_ = unit_first, n_utts_ = n_utts;
+        lay = ragged_layout_check(sample_first, unit_first, n_utts, n_samples, n, hop);
+        if (lay.verdict == RaggedVerdict::kOk) return JDSP_OK;
+        return fail(ctx, JDSP_EINVAL, ragged_layout_message(lay.verdict, entry, axis).c_str());
+    }
+    void upload(HostCall &hc)
+    {
+        d_sample = hc.upload(sample_, (size_t)n_utts_ * sizeof(int64_t));
+        d_unit = hc.upload(unit_, (size_t)(n_utts_ + 1) * sizeof(int64_t));
+    }
+
+private:
+    const int64_t *sample_ = nullptr, *unit_ = nullptr;
+    long n_utts_ = 0;
 };
 
 // A device table made on first use: JDSP_OK at once when `buf` holds it; otherwise fill(host) writes its `count`
@@ -528,8 +558,6 @@ struct OlaStream {
         for (int i = 0; i < hop; i++) gain[i] = (float)(1.0 / den[i]);
         return true;
     }
-    static bool aligned(const void *p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
     // the stream's share of the handle's blob, the gain first
     static size_t floats(int n, int hop) { return (size_t)hop + 2 * (size_t)n; }
     void attach(jdsp_ctx *c, int n_fft, int hop_len, float *base)

@@ -1,6 +1,8 @@
 // ragged_batch.h -- the utterance walk of the kernels that take a batch of ragged utterances in one launch:
-// stftmask_batch_kernel (stftmask_kernels.hip), istft_batch_kernel (istft_kernels.hip) and stft_half_batch_kernel
-// (stft_kernels.hip).  The layout is the one include/jdsp.h gives for jdsp_stftmask_batch_dev: the waves are planned
+// stftmask_batch_kernel (stftmask_kernels.hip), istft_batch_kernel (istft_kernels.hip), stft_half_batch_kernel
+// (stft_kernels.hip) and, with blocks for frames, vad_flags_batch_kernel, denoise_batch_kernel and
+// denoise_redo_f64_batch_kernel (denoise_kernels.hip).  The host half, the check of the offset arrays before they reach
+// the device, is ragged_layout.h.  The layout is the one include/jdsp.h gives for jdsp_stftmask_batch_dev: the waves are planned
 // over the CONCATENATED frame axis, global frame j is row j of the spectrum (or mask) tensor, it belongs to utterance u
 // with frame_first[u] <= j < frame_first[u + 1] and starts at the sample sample_first[u] + hop (j - frame_first[u]).
 // A wave finds the utterance of its first frame by a binary search and then walks from utterance to utterance.  All

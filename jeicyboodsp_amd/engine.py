@@ -18,6 +18,30 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _batch_offsets(holder, key, sample_first, unit_first, dev):
+    """The offsets of the last batch stay on the device: the device copies of the two int64 host arrays, made anew when
+    (key, dev) differs from the last call's and kept on `holder` -- the Engine or the stream object itself, so the
+    batch entries of two objects never share a cache.  Returns (d_sample, d_unit, fresh)."""
+    fresh = getattr(holder, "_batch_key", None) != (key, dev)
+    if fresh:
+        import torch
+        holder._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(unit_first).to(dev))
+        holder._batch_key = (key, dev)
+    return holder._batch_dev + (fresh,)
+
+
+def _batch_out(n, dtype, dev, given=None, tail=()):
+    """One output buffer of a batch entry: `given` as it is, else zeros [max(n, 1), *tail] of the numpy dtype `dtype`,
+    on the torch device dev or, with dev None, in numpy."""
+    if given is not None:
+        return given
+    shape = (max(n, 1),) + tuple(tail)
+    if dev is None:
+        return np.zeros(shape, dtype)
+    import torch
+    return torch.zeros(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+
+
 class _Handle:
     """Owns one C handle in `_h`: closed when collected."""
 
@@ -304,11 +328,7 @@ class Engine(_Handle):
             import torch
             assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
             dev = pcm.device
-            key = (offs.tobytes(), hop, dev)
-            if getattr(self, "_stft_batch_key", None) != key:   # the offsets of the last batch stay on the device
-                self._stft_batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(frame_first).to(dev))
-                self._stft_batch_key = key
-            d_sample, d_frame = self._stft_batch_dev
+            d_sample, d_frame, _ = _batch_offsets(self, (offs.tobytes(), hop), sample_first, frame_first, dev)
             if out is None:
                 out = torch.empty((n_total, pitch), dtype=torch.complex64, device=dev)
             assert out.is_cuda and out.dtype == torch.complex64 and out.is_contiguous()
@@ -464,38 +484,26 @@ class Denoiser(_Child):
             assert sample_first.size == counts.size
         n_utts, n_total, n_samples = counts.size, int(block_first[-1]), int(pcm.shape[0])
         assert pcm.ndim == 1
-        pre = flags = noise = None
-        if _is_torch(pcm):
+        dev = pcm.device if _is_torch(pcm) else None
+        if dev is not None:
             import torch
             assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
-            dev = pcm.device
             assert n_utts == 0 or int((sample_first + counts * self.block).max()) <= n_samples
-            key = (sample_first.tobytes(), counts.tobytes(), dev)
-            if getattr(self, "_batch_key", None) != key:        # the offsets of the last batch stay on the device
-                self._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(block_first).to(dev))
-                self._batch_key = key
+            key = (sample_first.tobytes(), counts.tobytes())
+            d_sample, d_block, fresh = _batch_offsets(self, key, sample_first, block_first, dev)
+            if fresh:
                 self.reserve_batch(n_total, n_utts)             # a no-op once sized
-            d_sample, d_block = self._batch_dev
-            if out is None:
-                out = torch.zeros(max(n_samples, 1), dtype=torch.int16, device=dev)
-            if want_precast:
-                pre = torch.zeros(max(n_samples, 1), dtype=torch.float32, device=dev)
-            if want_flags:
-                flags = torch.zeros(max(n_total, 1), dtype=torch.uint8, device=dev)
-            if want_noise:
-                noise = torch.zeros(max(n_utts, 1), 1024, dtype=torch.float32, device=dev)
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+        out = _batch_out(n_samples, np.int16, dev, out)
+        pre = _batch_out(n_samples, np.float32, dev) if want_precast else None
+        flags = _batch_out(n_total, np.uint8, dev) if want_flags else None
+        noise = _batch_out(n_utts, np.float32, dev, tail=(1024,)) if want_noise else None
+        if dev is not None:
             self.eng._use_torch_stream()
             self.eng._ck(L.jdsp_denoise_batch_dev(self._h, _vp(pcm), _vp(d_sample), _vp(d_block), n_utts, n_total, _vp(out),
                                                   _vp(pre), _vp(flags), _vp(noise)))
         else:
-            pcm = np.ascontiguousarray(pcm, np.int16)
-            out = np.zeros(max(n_samples, 1), np.int16) if out is None else out
-            if want_precast:
-                pre = np.zeros(max(n_samples, 1), np.float32)
-            if want_flags:
-                flags = np.zeros(max(n_total, 1), np.uint8)
-            if want_noise:
-                noise = np.zeros((max(n_utts, 1), 1024), np.float32)
             self.eng._ck(L.jdsp_denoise_batch(self._h, _vp(pcm), n_samples, _vp(sample_first), _vp(block_first), n_utts,
                                               _vp(out), _vp(pre), _vp(flags), _vp(noise)))
         res = [out[:n_samples]]
@@ -1115,29 +1123,23 @@ class Istft(_OlaStream):
         pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
         assert spec.ndim == 2 and spec.shape[0] >= n_total and pitch >= self.bins
         sample_first = np.ascontiguousarray(offs[:-1])
-        if _is_torch(spec):
+        dev = spec.device if _is_torch(spec) else None
+        if dev is not None:
             import torch
             assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
-            dev = spec.device
-            key = (offs.tobytes(), counts.tobytes(), dev)
-            if getattr(self, "_batch_key", None) != key:        # the offsets of the last batch stay on the device
-                self._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(frame_first).to(dev))
-                self._batch_key = key
-            d_sample, d_frame = self._batch_dev
-            if out is None:
-                out = torch.zeros(max(n_samples, 1), dtype=torch.int16, device=dev)
-            if want_f32 and out_f32 is None:
-                out_f32 = torch.zeros(max(n_samples, 1), dtype=torch.float32, device=dev)
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_istft_batch_dev(self._h, _vp(spec), pitch, _vp(d_sample), _vp(d_frame), n_utts, n_total,
-                                                _vp(out), _vp(out_f32) if want_f32 else None))
+            key = (offs.tobytes(), counts.tobytes())
+            d_sample, d_frame, _ = _batch_offsets(self, key, sample_first, frame_first, dev)
         else:
             spec = np.ascontiguousarray(spec, np.complex64)
-            out = np.zeros(max(n_samples, 1), np.int16) if out is None else out
-            if want_f32 and out_f32 is None:
-                out_f32 = np.zeros(max(n_samples, 1), np.float32)
+        out = _batch_out(n_samples, np.int16, dev, out)
+        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_istft_batch_dev(self._h, _vp(spec), pitch, _vp(d_sample), _vp(d_frame), n_utts, n_total,
+                                                _vp(out), _vp(out_f32)))
+        else:
             self.eng._ck(L.jdsp_istft_batch(self._h, _vp(spec), pitch, _vp(sample_first), _vp(frame_first), n_utts,
-                                            n_samples, _vp(out), _vp(out_f32) if want_f32 else None))
+                                            n_samples, _vp(out), _vp(out_f32)))
         return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
 
 
@@ -1208,32 +1210,25 @@ class StftMask(_OlaStream):
         assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_total)
         pitch = mask.shape[1] if mask.ndim == 2 else 0
         sample_first = np.ascontiguousarray(offs[:-1])
-        if _is_torch(pcm):
+        dev = pcm.device if _is_torch(pcm) else None
+        if dev is not None:
             import torch
             want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
             assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
             assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
-            dev = pcm.device
-            key = (offs.tobytes(), dev)
-            if getattr(self, "_batch_key", None) != key:        # the offsets of the last batch stay on the device
-                self._batch_dev = (torch.from_numpy(sample_first).to(dev), torch.from_numpy(frame_first).to(dev))
-                self._batch_key = key
-            d_sample, d_frame = self._batch_dev
-            if out is None:
-                out = torch.zeros(max(n_samples, 1), dtype=torch.int16, device=dev)
-            if want_f32 and out_f32 is None:
-                out_f32 = torch.zeros(max(n_samples, 1), dtype=torch.float32, device=dev)
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_stftmask_batch_dev(self._h, _vp(pcm), _vp(mask), pitch, _vp(d_sample), _vp(d_frame),
-                                                   n_utts, n_total, _vp(out), _vp(out_f32) if want_f32 else None))
+            d_sample, d_frame, _ = _batch_offsets(self, offs.tobytes(), sample_first, frame_first, dev)
         else:
             pcm = np.ascontiguousarray(pcm, np.int16)
             mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
-            out = np.zeros(max(n_samples, 1), np.int16) if out is None else out
-            if want_f32 and out_f32 is None:
-                out_f32 = np.zeros(max(n_samples, 1), np.float32)
+        out = _batch_out(n_samples, np.int16, dev, out)
+        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_stftmask_batch_dev(self._h, _vp(pcm), _vp(mask), pitch, _vp(d_sample), _vp(d_frame),
+                                                   n_utts, n_total, _vp(out), _vp(out_f32)))
+        else:
             self.eng._ck(L.jdsp_stftmask_batch(self._h, _vp(pcm), n_samples, _vp(mask), pitch, _vp(sample_first),
-                                               _vp(frame_first), n_utts, _vp(out), _vp(out_f32) if want_f32 else None))
+                                               _vp(frame_first), n_utts, _vp(out), _vp(out_f32)))
         return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
 
 

@@ -171,6 +171,20 @@ def stftmask_batch_layout(utt_sample_first, n_fft, hop):
     return counts, np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)])
 
 
+def _pack_back_to_back(counts, n, hop, what):
+    """Utterance u of counts[u] >= 0 units (what: their name in the ValueError) takes hop (counts[u] - 1) + n samples,
+    none when it has no unit, and the spans follow each other without a gap.  Returns (sample_first [n_utts + 1],
+    unit_first [n_utts + 1]) as numpy int64."""
+    import numpy as np
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    if np.any(counts < 0):
+        raise ValueError("%s counts must be >= 0" % what)
+    spans = np.where(counts > 0, hop * (counts - 1) + n, 0).astype(np.int64)
+    zero = np.zeros(1, np.int64)
+    return (np.concatenate([zero, np.cumsum(spans, dtype=np.int64)]),
+            np.concatenate([zero, np.cumsum(counts, dtype=np.int64)]))
+
+
 def istft_batch_layout(frame_counts, n_fft, hop):
     """The back-to-back packing of a batch of synthesis outputs (Istft.process_batch without utt_sample_first):
     utterance u of F_u = frame_counts[u] >= 0 spectrum rows comes out as hop (F_u - 1) + n_fft samples (none when
@@ -178,16 +192,10 @@ def istft_batch_layout(frame_counts, n_fft, hop):
     frame_first [n_utts + 1]) as numpy int64; the offsets are even by construction (n_fft and hop are), and
     stftmask_batch_layout(utt_sample_first, n_fft, hop) gives frame_counts and frame_first back.  Negative counts:
     ValueError."""
-    import numpy as np
-    counts = np.asarray(frame_counts, dtype=np.int64).reshape(-1)
-    if np.any(counts < 0):
-        raise ValueError("frame counts must be >= 0")
+    packed = _pack_back_to_back(frame_counts, n_fft, hop, "frame")
     if n_fft % 2 or hop % 2:
         raise ValueError("n_fft and hop must be even")
-    spans = np.where(counts > 0, hop * (counts - 1) + n_fft, 0).astype(np.int64)
-    zero = np.zeros(1, np.int64)
-    return (np.concatenate([zero, np.cumsum(spans, dtype=np.int64)]),
-            np.concatenate([zero, np.cumsum(counts, dtype=np.int64)]))
+    return packed
 
 
 def denoise_batch_layout(block_counts, hop):
@@ -195,14 +203,10 @@ def denoise_batch_layout(block_counts, hop):
     of B_u = block_counts[u] >= 0 blocks of hop samples takes hop B_u samples, and the spans follow each other
     without a gap.  Returns (sample_first [n_utts], block_first [n_utts + 1], n_samples) with the two arrays as numpy
     int64; the offsets are even because hop is.  Negative counts or an odd hop: ValueError."""
-    import numpy as np
-    counts = np.asarray(block_counts, dtype=np.int64).reshape(-1)
-    if np.any(counts < 0):
-        raise ValueError("block counts must be >= 0")
+    sample_first, block_first = _pack_back_to_back(block_counts, hop, hop, "block")
     if hop <= 0 or hop % 2:
         raise ValueError("hop must be even and > 0")
-    block_first = np.concatenate([np.zeros(1, np.int64), np.cumsum(counts, dtype=np.int64)])
-    return np.ascontiguousarray(block_first[:-1] * hop), block_first, int(block_first[-1]) * int(hop)
+    return sample_first[:-1].copy(), block_first, int(sample_first[-1])
 
 
 def stftmask_batch_shard(frame_counts, rank, world):
