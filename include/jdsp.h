@@ -375,8 +375,10 @@ int jdsp_denoise_create_cfg(jdsp_ctx *ctx, int mode, int n_fft, int hop, jdsp_de
 int jdsp_denoise_block_len(const jdsp_denoise *h);
 int jdsp_denoise_destroy(jdsp_denoise *h);
 int jdsp_denoise_reset(jdsp_denoise *h);                       /* back to a fresh stream */
-/* "blocks_per_wave": 0 (default: one round of resident waves walks the batch) or 1 / 2 / 4 / 8 (the compile-time
- * variants, kept for A/B timing); "vad_trace": 1 keeps every block's energy sum and zero-crossing count for
+/* "blocks_per_wave": the number of consecutive blocks one wave of the run kernel walks, on the stream entries and the
+ * batch entries alike: 1 / 2 / 4 / 8, or 0 (default) for one round of resident waves over the call's blocks.  A tuning
+ * knob only: the output bits do not depend on it ((1024, 512) handles; (512, 256) handles accept and ignore it).
+ * "vad_trace": 1 keeps every block's energy sum and zero-crossing count for
  * jdsp_denoise_vad_trace (a slower VAD kernel: two exact wave reductions per block); 0 (default) keeps the flags only. */
 int jdsp_denoise_set_option(jdsp_denoise *h, const char *name, long value);
 long jdsp_denoise_blocks_out(const jdsp_denoise *h, long n_blocks);
@@ -422,10 +424,9 @@ int jdsp_denoise_vad_trace(jdsp_denoise *h, long n, uint8_t *voice_host, int64_t
  *     utterance u at block_first[u] + b).  noise_last [n_utts][1024] float32: the estimate in force after the
  *     utterance's last block, zeros if none was latched.  Any of the four output pointers may be NULL.
  *   - An utterance's out, precast, flags and noise_last do not depend, bit for bit, on where it stands in the batch,
- *     on its neighbours, on how the batch is split into calls, or on the "blocks_per_wave" option (here: the blocks a
- *     wave of the run kernel walks; 0 = one round of resident waves).  Against the oracle they are held to _process's
- *     bars; against _process itself they agree to those bars, not bit for bit (the single stream sums its noise
- *     average in chunks).
+ *     on its neighbours, on how the batch is split into calls, or on the "blocks_per_wave" option.  Against the oracle
+ *     they are held to _process's bars; against _process itself they agree to those bars, not bit for bit (the single
+ *     stream sums its noise average in chunks).
  *   - jdsp_denoise_batch_dev only enqueues on the context's stream: no allocation, no host synchronisation, no host
  *     read of the two offset arrays (int64, [n_utts] and [n_utts + 1], 8-byte aligned) -- hence n_blocks_total, which
  *     must equal block_first[n_utts].  It is graph-capturable.  The device-side offsets are the caller's contract, the

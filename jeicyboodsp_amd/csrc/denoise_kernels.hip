@@ -12,7 +12,8 @@
 //                            affine map of the running average (SS:182-187) per chunk of events, in registers
 //   noise_combine_kernel A12 the chunk maps composed: the average entering every chunk, the latched rows, the state
 //   denoise_run_kernel  A8/A9/A10  window -> FFT -> gain -> IFFT -> overlap-add -> (short), fused; one wavefront
-//                            walks a run of consecutive output blocks and recomputes one halo frame
+//                            walks a run of consecutive output blocks (one round of resident waves, or the handle's
+//                            "blocks_per_wave") and recomputes one halo frame, in the same loop body as every other
 // (512-point frames: vad_*<4>, noise_accum512_kernel, denoise512_run_kernel; sharded runs use the same kernels on a
 // rank's range of events.)
 // (A batch of ragged utterances, each a fresh stream: vad_flags_batch_kernel, noise_batch_kernel, denoise_batch_kernel,
@@ -662,73 +663,14 @@ __device__ __forceinline__ void phase_redo(int *__restrict__ redo, long j, int l
     if (lane == 0) redo[1 + atomicAdd(redo, 1)] = (int)j;
 }
 
-// w: how many bins of the spectrum this value stands for (a lane that owns a mirror pair evaluates one of the two)
-template <int MODE>
-__device__ __forceinline__ float2 apply_gain(float2 x, float n, float &err, float w, bool maybe_real = false,
-                                             float rthr = 0.0f)
-{
-    // hardware reciprocal / reciprocal square root (1 ulp): the bar is 1e-5, not IEEE division
-    const float p = x.x * x.x + x.y * x.y;
-    if (MODE == 0) {
-        const float q = n * __frsqrt_rn(p);                   // N / |X|; p == 0 gives inf / NaN: the frame goes to FP64
-        const float g = 1.0f - q;                               // (|X| - N) / |X|; p == 0: replaced below
-        const bool zero = p == 0.0f;
-        if (maybe_real) w = p < rthr ? w : 0.0f;                // (maybe_real is a compile-time fact of every call)
-        err += w * (q * q + 1.0f);
-        return make_float2(zero ? -n : x.x * g, zero ? 0.0f : x.y * g);
-    } else {
-        float r = (n * n) * __builtin_amdgcn_rcpf(p);                    // 0 * inf = NaN keeps the reference's 0/0
-        if (r >= 1.0f) r = 1.0f;
-        const float g = 1.0f - r;
-        const float t = 1.0f + 2.0f * r;                        // Wiener: rounding eps in X moves Y by at most (1 + 2 r) eps
-        err += w * (t * t);
-        return make_float2(x.x * g, x.y * g);
-    }
-}
-
 // One frame: samples -> y = IDFT(gain(DFT(window * frame))) / 1024, returned in the transform layout: y[d] =
-// (y[2 lane + 128 d], y[2 lane + 128 d + 1]).  The bins stay in "lane + 64 d" registers from the forward transform to
-// the inverse one: no natural-order image, no Z' image (frame_io.h).  noise[m] is read at m = lane + 64 d.
-template <int MODE>
-__device__ __forceinline__ void denoise_frame_reg(const unsigned int *raw, const FrameTables &t, const SplitTwiddles &sw,
-                                                  float2 *lds, int lane, const float *__restrict__ noise, float2 (&y)[8],
-                                                  PhaseStat &ps)
-{
-    float2 v[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        const float2 s = unpack_i16x2(raw[r]);
-        v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
-    }
-    if (MODE == 0) ps.e = wave_sum_f32(sumsq(v));
-    float err = 0.0f;
-    wave_fft512<false>(v, lds, lane, t.tw);
-    float2 zr[8], lo[8], hi[8];
-    mirror_fetch(v, lane, zr);
-    split_fwd_reg(v, zr, sw, lo, hi);
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        const int m = lane + 64 * d;
-        const float rthr = real_bin_thr(ps.e, lane == 0);       // d == 0, lane 0: the bins 0 and 512
-        lo[d] = apply_gain<MODE>(lo[d], noise[m], err, 1.0f, d == 0, rthr);
-        hi[d] = apply_gain<MODE>(hi[d], noise[m + 512], err, 1.0f, d == 0, rthr);
-        y[d] = presplit_inv_reg(lo[d], hi[d], sw.w[d]);
-    }
-    if (MODE == 0) ps.err = wave_sum_f32(err);
-    wave_lds_fence();                                            // the forward transform's last exchange reads are done
-    wave_fft512<true>(y, lds, lane, t.tw);
-    // the reference's 1/N after FFTW's unnormalised inverse (SS:248); a power of two, exact
-#pragma unroll
-    for (int d = 0; d < 8; d++) y[d] = make_float2(y[d].x * (1.0f / 1024.0f), y[d].y * (1.0f / 1024.0f));
-    wave_lds_fence();
-}
-
-// The frame with every mirror pair of bins owned by one lane (frame_io.h, PairTwiddles): five items per lane, the gain
-// evaluated on the 640 bins m, m + 512 (m = lane + 64 d, d < 5) and the rest of the inverse transform's input taken
-// from the Hermitian symmetry -- which holds because the gain is real and N[1024 - k] = N[k] up to the rounding of the
-// estimate (|X[k]| and |X[1024 - k]| of a real frame, 1e-7 apart in FP32; the reference's own FFTW spectrum is
-// symmetric to 1e-16).  The reference's 1/1024 after the inverse transform (SS:248, a power of two: exact wherever it
-// is applied) is folded into the gain, so the noise values arrive pre-multiplied by it.
+// (y[2 lane + 128 d], y[2 lane + 128 d + 1]).  Every mirror pair of bins is owned by one lane (frame_io.h,
+// PairTwiddles): five items per lane, the gain evaluated on the 640 bins m, m + 512 (m = lane + 64 d, d < 5) and the
+// rest of the inverse transform's input taken from the Hermitian symmetry -- which holds because the gain is real and
+// N[1024 - k] = N[k] up to the rounding of the estimate (|X[k]| and |X[1024 - k]| of a real frame, 1e-7 apart in
+// FP32; the reference's own FFTW spectrum is symmetric to 1e-16).  The reference's 1/1024 after the inverse transform
+// (SS:248, a power of two: exact wherever it is applied) is folded into the gain, so the noise values arrive
+// pre-multiplied by it.
 struct NoisePairRegs { float lo[5], hi[5]; };
 template <int MODE>
 __device__ __forceinline__ void load_noise_pair_regs(NoisePairRegs &n, const float *__restrict__ row, int lane)
@@ -739,8 +681,11 @@ __device__ __forceinline__ void load_noise_pair_regs(NoisePairRegs &n, const flo
     for (int d = 0; d < 5; d++) { n.lo[d] = sc * row[lane + 64 * d]; n.hi[d] = sc * row[lane + 64 * d + 512]; }
 }
 
-// apply_gain<MODE>(x, n) / 2^LOG2N (1024 or 512) with n as load_noise_pair_regs left it
-// (err comes out scaled by 2^-2 LOG2N)
+// The gain of one bin (A8 / A9 above) times 2^-LOG2N, the reference's 1/n_fft (1024 or 512): x is the bin, n its noise
+// value as load_noise_pair_regs left it (spectral subtraction: already scaled).  err collects the bin's term of
+// phase_unsafe's sum, scaled by 2^-2 LOG2N; w: how many bins of the spectrum this value stands for (a lane that owns a
+// mirror pair evaluates one of the two); maybe_real: the bin may be one of the two real ones, which count only under
+// rthr (real_bin_thr).  Hardware reciprocal / reciprocal square root (1 ulp): the bar is 1e-5, not IEEE division.
 template <int MODE, int LOG2N = 10>
 __device__ __forceinline__ float2 apply_gain_scaled(float2 x, float n, float &err, float w, bool maybe_real = false,
                                                     float rthr = 0.0f)
@@ -816,9 +761,17 @@ __device__ __forceinline__ void denoise_frame_pairs(const unsigned int *raw, con
     wave_lds_fence();
 }
 
-#ifndef JDSP_DENOISE_MINWAVES
-#define JDSP_DENOISE_MINWAVES 3
-#endif
+// Every wave of a run kernel walks the priority levels, one step per loop iteration (see fastconv1024_pairs_kernel: a
+// SIMD serves equal-priority waves by age, and equal shares then finish far apart).  s_setprio takes an immediate.
+__device__ __forceinline__ void step_priority(unsigned &prio_step)
+{
+    switch (prio_step++ & 3u) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
 
 // Which noise row block j (local index) uses.  Single-GPU: the plan's version.  Sharded
 // (DenoiseShard): the plan is indexed by GLOBAL block number and the local row table starts at
@@ -843,94 +796,16 @@ __device__ __forceinline__ const float *noise_row_at(const float *__restrict__ r
     return rows + (size_t)v * 1024;
 }
 
-template <int MODE, int K>
-__global__ __launch_bounds__(64, JDSP_DENOISE_MINWAVES) void denoise_kernel(
-    const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
-    DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
-    const float *__restrict__ noise_rows, const float2 *__restrict__ table, short *__restrict__ out,
-    float *__restrict__ precast, DenoiseShard sh, int *__restrict__ redo)
-{
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    const int lane = threadIdx.x;
-    PhaseStat ps;
-    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware chunk order (speed only)
-    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * K;
-    if (j0 >= n_blocks) return;
-
-    unsigned int half[K + 2][4];                              // blocks j0-2 .. j0+K-1, pairs 2 lane + 128 r
-#pragma unroll
-    for (int h = 0; h < K + 2; h++) load_block_pairs(pcm, n_blocks, st_in, j0 - 2 + h, lane, half[h]);
-    FrameTables t;
-    load_frame_tables(t, table, lane);
-    SplitTwiddles sw;
-    load_split_twiddles(sw, table, lane);
-
-    const long first_emit = sh.emit_from;                     // SS:260-263: calls 1 and 2 emit nothing
-    unsigned int raw[8];
-    float2 tail[4], y[8];
-#pragma unroll
-    for (int r = 0; r < 4; r++) { raw[r] = half[0][r]; raw[r + 4] = half[1][r]; }
-    if (j0 == 0) {
-        // rgsdOveraped[512..1023] carried over from the previous call
-#pragma unroll
-        for (int d = 0; d < 4; d++) tail[d] = *reinterpret_cast<const float2 *>(&st_in->tail[2 * lane + 128 * d]);
-    } else if (calls_before + j0 - 1 == 0) {
-        // the very first call of a stream only stashes its block (SS:211-216): no output, empty overlap
-#pragma unroll
-        for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
-    } else {
-        denoise_frame_reg<MODE>(raw, t, sw, lds, lane, noise_row(noise_rows, ver_base, snap_mask, j0 - 1, sh), y, ps);   // halo frame
-#pragma unroll
-        for (int d = 0; d < 4; d++) tail[d] = y[d + 4];
-    }
-
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        const long j = j0 + i;
-        if (j >= n_blocks) break;
-#pragma unroll
-        for (int r = 0; r < 4; r++) { raw[r] = raw[r + 4]; raw[r + 4] = half[i + 2][r]; }
-        if (calls_before + j == 0) {
-#pragma unroll
-            for (int d = 0; d < 8; d++) y[d] = make_float2(0.f, 0.f);
-        } else {
-            denoise_frame_reg<MODE>(raw, t, sw, lds, lane, noise_row(noise_rows, ver_base, snap_mask, j, sh), y, ps);
-            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
-            if (MODE == 0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
-        }
-        float2 o[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            o[d] = make_float2(tail[d].x + y[d].x, tail[d].y + y[d].y);      // SS:248 overlap-add
-            tail[d] = y[d + 4];                                               // SS:255-256
-        }
-        if (j >= first_emit && j < sh.emit_to) {
-            const long oi = j - first_emit;
-            unsigned int *dst = reinterpret_cast<unsigned int *>(out + oi * 512) + lane;
-#pragma unroll
-            for (int d = 0; d < 4; d++)                      // four coalesced 256-byte stores, in the layout as is
-                __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
-            if (precast) {
-#pragma unroll
-                for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(precast + oi * 512 + 2 * lane + 128 * d) = o[d];
-            }
-        }
-        if (j == n_blocks - 1) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) reinterpret_cast<unsigned int *>(st_out->prev)[lane + 64 * r] = half[i + 2][r];   // SS:257
-#pragma unroll
-            for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(&st_out->tail[2 * lane + 128 * d]) = tail[d];
-        }
-    }
-}
-
-// The same work as denoise_kernel<MODE, K> with the run length chosen at launch instead of at compile time: one wave
-// walks `run` consecutive blocks (one recomputed halo frame in front), and the launch picks `run` so that the whole
-// batch is ONE round of resident waves (three per SIMD when this was measured).  With K = 8 a 65,536-block batch is
-// 8,192 waves = 2.67 rounds of the 3,072 resident ones, i.e. 3 rounds of 9 frames = 27 frame times per wave slot for
-// 24 of work; with run = 22 it is 2,979 waves, one round, 23 frame times -- and the halo overhead falls from 1/8 to
-// 1/22.  A wave needs the next block's samples only one iteration later, so they are loaded at the top of the
-// iteration that precedes their use (4 dwords per lane) instead of all K + 2 blocks up front (40 VGPRs at K = 8).
+// A8/A9/A10 for a call's blocks: one wave walks `run` consecutive blocks, and the launch picks `run` so that the whole
+// batch is ONE round of resident waves (resident_run; the handle's "blocks_per_wave" option sets it instead).  Waves
+// that come in several rounds leave wave slots idle at the end of the last one -- with 8 blocks per wave a 65,536-block
+// batch was 8,192 waves = 2.67 rounds of the 3,072 then resident, 27 frame times per wave slot for 24 of work -- and
+// every wave pays one halo frame, 1/run of its work.  The frame of block j is [block j - 1, block j]; a wave's first
+// output needs the second half of the frame before it, so that halo frame (js = j0 - 1) goes through the SAME loop
+// body as every other frame with emission off: one inlined copy of the arithmetic, so the samples do not depend on
+// where the waves, or the calls, are cut.  No halo where the call's first block takes the carried overlap (j0 == 0)
+// or the frame before is the stream's void first one.  A wave needs the next block's samples only one iteration
+// later, so they are loaded at the top of the iteration that precedes their use (4 dwords per lane).
 #ifndef JDSP_DENOISE_RESIDENT
 #define JDSP_DENOISE_RESIDENT 4      // waves per SIMD the run kernel's register budget allows
 #endif
@@ -955,49 +830,31 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
     load_pair_twiddles(sw, table, lane);
     NoisePairRegs nz;
 
-    unsigned int raw[8], nxt[4];
+    unsigned int raw[8], nxt[4], tk[4];
     float2 tail[4], y[8];
     const float *cur_row = nullptr;
     const int row_off = sh.ver_row_off ? *sh.ver_row_off : 0;          // once: see noise_row_at
-    load_block_pairs(pcm, n_blocks, st_in, j0 - 2, lane, nxt);
-#pragma unroll
-    for (int r = 0; r < 4; r++) raw[r] = nxt[r];
-    load_block_pairs(pcm, n_blocks, st_in, j0 - 1, lane, nxt);
-#pragma unroll
-    for (int r = 0; r < 4; r++) raw[r + 4] = nxt[r];
-    load_block_pairs(pcm, n_blocks, st_in, j0, lane, nxt);
+    const long js = (j0 == 0 || calls_before + j0 - 1 == 0) ? j0 : j0 - 1;
     if (j0 == 0) {
         // rgsdOveraped[512..1023] carried over from the previous call
 #pragma unroll
         for (int d = 0; d < 4; d++) tail[d] = *reinterpret_cast<const float2 *>(&st_in->tail[2 * lane + 128 * d]);
-    } else if (calls_before + j0 - 1 == 0) {
-        // the very first call of a stream only stashes its block (SS:211-216): no output, empty overlap
+    } else {
+        // empty: the halo frame fills it, or the stream's first call only stashed its block (SS:211-216)
 #pragma unroll
         for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
-    } else {
-        cur_row = noise_row_at(noise_rows, ver_base, snap_mask, j0 - 1, sh.ver_block_off, row_off);
-        load_noise_pair_regs<MODE>(nz, cur_row, lane);
-        denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);   // halo frame
-#pragma unroll
-        for (int d = 0; d < 4; d++) tail[d] = y[d + 4];
     }
+    load_block_pairs(pcm, n_blocks, st_in, js - 1, lane, nxt);
+#pragma unroll
+    for (int r = 0; r < 4; r++) raw[r + 4] = nxt[r];
+    load_block_pairs(pcm, n_blocks, st_in, js, lane, tk);
     const long first_emit = sh.emit_from;                     // SS:260-263: calls 1 and 2 emit nothing
-    // every wave walks the priority levels, one step per block (see fastconv1024_pairs_kernel: a SIMD serves equal-priority
-    // waves by age, and equal shares then finish far apart)
-    unsigned prio_step = blockIdx.x >> 10;
+    unsigned prio_step = blockIdx.x >> 10;                    // step_priority: one step per block
     // vmcnt counts loads and stores together, in issue order, and across the loop's back edge the compiler waits for
     // vmcnt(0): taking the prefetched block at the TOP of an iteration waited for the previous block's output stores to
     // complete, every block.  It is taken (tk <- nxt) just before this block's stores instead (see fastconv1024_pairs_kernel).
-    unsigned int tk[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) tk[r] = nxt[r];
-    for (long j = j0; j < j1; j++) {
-        switch (prio_step++ & 3u) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-        }
+    for (long j = js; j < j1; j++) {
+        step_priority(prio_step);
         unsigned int cur[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) { cur[r] = tk[r]; raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
@@ -1012,8 +869,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
                 load_noise_pair_regs<MODE>(nz, row, lane);
             }
             denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);
-            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
-            if (MODE == 0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
+            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted (the halo
+            // frame is listed by the wave that owns it)
+            if (MODE == 0 && j >= j0 && j + 1 >= sh.emit_from && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
         }
         float2 o[4];
 #pragma unroll
@@ -1024,7 +882,7 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_run_kernel(
 #pragma unroll
         for (int r = 0; r < 4; r++) { tk[r] = nxt[r]; asm volatile("" : "+v"(tk[r])); }
         __builtin_amdgcn_sched_barrier(0);
-        if (j >= first_emit && j < sh.emit_to) {
+        if (j >= j0 && j >= first_emit && j < sh.emit_to) {
             const long oi = j - first_emit;
             unsigned int *dst = reinterpret_cast<unsigned int *>(out + oi * 512) + lane;
 #pragma unroll
@@ -1136,50 +994,19 @@ static long resident_run(int n_cu, long n_blocks)
     return (n_blocks + waves - 1) / waves;
 }
 
-template <int MODE, int K>
-static void launch_dn(hipStream_t s, const short *pcm, long n_blocks, long calls_before, const DenoiseState *st_in,
-                      DenoiseState *st_out, const int *ver_base, const unsigned long long *snap_mask,
-                      const float *noise_rows, const float2 *table, short *out, float *precast, const DenoiseShard &sh,
-                      int *redo)
-{
-    long grid = ((n_blocks + K - 1) / K + 7) / 8 * 8;
-    hipLaunchKernelGGL((denoise_kernel<MODE, K>), dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before,
-                       st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, redo);
-}
-
 static int launch_denoise1024(hipStream_t s, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
                              long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                              const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,
                              float *precast, const DenoiseShard &sh, int *redo)
 {
-    if (k_opt == 0) {
-        const long run = resident_run(n_cu, n_blocks);
-        const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
-        if (mode == 0)
-            hipLaunchKernelGGL(denoise_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
-        else
-            hipLaunchKernelGGL(denoise_run_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
-                               st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-#define JDSP_DN(M, KK) launch_dn<M, KK>(s, pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, redo)
-    if (mode == 0) {
-        switch (k_opt) {
-        case 1: JDSP_DN(0, 1); break;
-        case 2: JDSP_DN(0, 2); break;
-        case 4: JDSP_DN(0, 4); break;
-        default: JDSP_DN(0, 8); break;
-        }
-    } else {
-        switch (k_opt) {
-        case 1: JDSP_DN(1, 1); break;
-        case 2: JDSP_DN(1, 2); break;
-        case 4: JDSP_DN(1, 4); break;
-        default: JDSP_DN(1, 8); break;
-        }
-    }
-#undef JDSP_DN
+    const long run = k_opt > 0 ? k_opt : resident_run(n_cu, n_blocks);
+    const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
+    if (mode == 0)
+        hipLaunchKernelGGL(denoise_run_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
+                           st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
+    else
+        hipLaunchKernelGGL(denoise_run_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, n_blocks, calls_before, st_in,
+                           st_out, ver_base, snap_mask, noise_rows, table, out, precast, sh, (int)run, redo);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1366,14 +1193,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE512_WAVES(MODE)) void denoise512_ru
     const float *row_a = nullptr, *row_b = nullptr;
     const long first_emit = sh.emit_from;
     bool halo = true;                                         // frame j0 - 1 only rebuilds the overlap tail
-    unsigned prio_step = blockIdx.x >> 10;                    // as in denoise_run_kernel: one priority step per frame pair
+    unsigned prio_step = blockIdx.x >> 10;                    // step_priority: one step per frame pair
     for (long ja = j0 - 1; ja < j1; ja += 2) {
-        switch (prio_step++ & 3u) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-        }
+        step_priority(prio_step);
         const long jb = ja + 1;
         if (ja + 2 < j1) {                                    // the next pair's two new blocks, needed one iteration from now
             if (ja + 2 >= 0 && ja + 4 <= n_blocks) {            // both inside this call's buffer (wave-uniform)
@@ -1844,14 +1666,9 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_batch_kerne
     load_pairs(pcm + base + js * 512, lane, tk);
     int cur_row = -1;
     int next_idx = __builtin_amdgcn_readfirstlane(row_idx[js]);
-    unsigned prio_step = blockIdx.x >> 10;                    // as in denoise_run_kernel
+    unsigned prio_step = blockIdx.x >> 10;                    // step_priority: one step per block
     for (long j = js; j < j1; j++) {
-        switch (prio_step++ & 3u) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-        }
+        step_priority(prio_step);
 #pragma unroll
         for (int r = 0; r < 4; r++) { raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
         const int idx = next_idx;

@@ -122,7 +122,8 @@ struct NoiseAccum {
     int *lat_chunk;        // [rows]                 ... and its chunk
 };
 
-// How denoise_kernel maps local block indices onto the (possibly global) plan and what it emits.
+// How the run kernels (denoise_run_kernel, denoise512_run_kernel) and the FP64 pass map local block indices onto the
+// (possibly global) plan and what they emit.
 struct DenoiseShard {
     long ver_block_off;        // global index of local block 0 (0 when not sharded)
     const int *ver_row_off;    // device int: latches before the shard, subtracted from the version (or NULL)
@@ -362,7 +363,8 @@ int launch_noise_estimate(hipStream_t s, DenoiseGeom g, const short *pcm, long n
                           DenoiseState *st_out, const int *events, const int *ev_n, const DenoisePlan *plan,
                           const int *ver_base, const unsigned long long *snap_mask, const float2 *table,
                           const NoiseAccum &acc, float *noise_rows);
-// k_opt: the handle's blocks_per_wave option (1024-point frames only)
+// k_opt: the handle's blocks_per_wave option, the run kernel's blocks per wave (0: one round of resident waves;
+// 1024-point frames only)
 int launch_denoise(hipStream_t s, DenoiseGeom g, int mode, int k_opt, int n_cu, const short *pcm, long n_blocks,
                    long calls_before, const DenoiseState *st_in, DenoiseState *st_out, const int *ver_base,
                    const unsigned long long *snap_mask, const float *noise_rows, const float2 *table, short *out,

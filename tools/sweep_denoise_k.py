@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Blocks-per-wave sweep of the fused denoise kernel (GPU box only)."""
+"""Run-length sweep of the denoise run kernel: the "blocks_per_wave" option at 0 (one round of resident waves) and at
+1 / 2 / 4 / 8 blocks per wave, 65,536 blocks, both modes (GPU box only)."""
 import os, sys, statistics
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,7 +12,7 @@ x = np.clip(np.rint(rng.normal(0, 3000, B * 512)), -32768, 32767).astype(np.int1
 x[:12 * 512] = np.clip(np.rint(rng.normal(0, 45, 12 * 512)), -32768, 32767)
 t = torch.from_numpy(x).cuda()
 for mode in (0, 1):
-    for k in (1, 2, 4, 8):
+    for k in (0, 1, 2, 4, 8):
         d = eng.denoiser(mode)
         d.set_option("blocks_per_wave", k)
         d.process(t)
