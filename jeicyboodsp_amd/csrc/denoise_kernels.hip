@@ -1434,12 +1434,93 @@ __device__ __forceinline__ void redo_gain_frame(double2 *buf, const double2 *tw,
     for (int r = 0; r < R; r++) y[tid + 256 * r] = buf[tid + 256 * r].x * (1.0 / NFFT);     // SS:248
 }
 
-template <int NFFT>
-__global__ __launch_bounds__(256) void denoise_redo_f64_kernel(
-    const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
-    DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
-    const float *__restrict__ noise_rows, short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh,
-    const int *__restrict__ redo, int mode)
+// What differs between a stream and a batch in the pass below.  seek(f): at the listed frame f.  Then for q < 3, the
+// frames f - 1 + q: have(q), whether the frame exists and adds anything; sample(q, i), its sample i; row(q), its noise
+// row.  And for q < 2, the blocks f + q: writes(q), whether this launch may write the block; carried(q) / carry(i), an
+// overlap that comes from outside the call instead of from frame f - 1 + q; store(q, i, o); finish(), after both.
+//
+// A stream: frames outside the call add nothing here, block 0 takes the overlap carried in instead; the very first
+// call of a stream only stashes its block (SS:211-216).  Samples before the call come from the state's previous block.
+template <int NFFT> struct RedoStream {
+    static constexpr int B = NFFT / 2;
+    const short *pcm;
+    long n_blocks, calls_before;
+    const DenoiseState *st_in;
+    DenoiseState *st_out;
+    const int *ver_base;
+    const unsigned long long *snap_mask;
+    const float *noise_rows;
+    short *out;
+    float *precast;
+    const DenoiseShard &sh;
+    long f;
+    __device__ __forceinline__ void seek(long f_) { f = f_; }
+    __device__ __forceinline__ bool have(int q) const
+    {
+        const long j = f - 1 + q;
+        return j >= 0 && j < n_blocks && calls_before + j > 0;
+    }
+    __device__ __forceinline__ double sample(int q, int i) const
+    {
+        return redo_sample<NFFT>(pcm, n_blocks * B, st_in, (f - 2 + q) * B + i);
+    }
+    __device__ __forceinline__ const float *row(int q) const { return noise_row(noise_rows, ver_base, snap_mask, f - 1 + q, sh); }
+    __device__ __forceinline__ bool writes(int q) const { return f + q < n_blocks && f + q >= sh.emit_from && f + q < sh.emit_to; }
+    __device__ __forceinline__ bool carried(int q) const { return f + q == 0; }
+    __device__ __forceinline__ double carry(int i) const { return (double)st_in->tail[i]; }     // rgsdOveraped carried over
+    __device__ __forceinline__ void store(int q, int i, float o) const
+    {
+        const long at = (f + q - sh.emit_from) * B + i;
+        out[at] = (short)cast_i16_bits(o);
+        if (precast) precast[at] = o;
+    }
+    __device__ __forceinline__ void finish(const double *rest, int tid) const
+    {
+        if (f != n_blocks - 1) return;
+#pragma unroll
+        for (int r = 0; r < NFFT / 512; r++) st_out->tail[tid + 256 * r] = (float)rest[tid + 256 * r];   // SS:255-256
+    }
+};
+
+// A batch: a listed global frame f of utterance u (local b) adds into the outputs of the local blocks b and b + 1, so
+// the frames b - 1, b, b + 1 that exist are the local blocks 1 .. B_u - 1 (block 0 only stashes its samples): never the
+// previous utterance's last frame, never the next one's first.  Both outputs are written where the run kernel writes
+// them: at the time of the local blocks b - 1 and b, if those are 1 .. B_u - 2.
+struct RedoBatch {
+    const short *pcm;
+    const long long *sample_first, *block_first;
+    long n_utts;
+    const int *row_idx;
+    const float *noise_rows;
+    short *out;               // may be NULL
+    float *precast;           // may be NULL
+    long ub, n_own, first, b;
+    __device__ __forceinline__ void seek(long f)
+    {
+        const long u = ragged_find_utt(block_first, n_utts, f);
+        ub = uniform_i64(block_first + u);
+        n_own = uniform_i64(block_first + u + 1) - ub;
+        first = uniform_i64(sample_first + u);
+        b = f - ub;
+    }
+    __device__ __forceinline__ bool have(int q) const { return b - 1 + q >= 1 && b - 1 + q < n_own; }
+    __device__ __forceinline__ double sample(int q, int i) const { return (double)pcm[first + (b - 2 + q) * 512 + i]; }
+    __device__ __forceinline__ const float *row(int q) const { return noise_rows + (size_t)row_idx[ub + b - 1 + q] * 1024; }
+    __device__ __forceinline__ bool writes(int q) const { return b + q >= 2 && b + q < n_own; }
+    __device__ __forceinline__ bool carried(int) const { return false; }
+    __device__ __forceinline__ double carry(int) const { return 0.0; }
+    __device__ __forceinline__ void store(int q, int i, float o) const
+    {
+        const long at = first + (b + q - 1) * 512 + i;
+        if (out) out[at] = (short)cast_i16_bits(o);
+        if (precast) precast[at] = o;
+    }
+    __device__ __forceinline__ void finish(const double *, int) const {}
+};
+
+// One workgroup per listed frame (grid-stride over the list)
+template <int NFFT, class Src>
+__device__ __forceinline__ void redo_f64_run(const int *__restrict__ redo, int mode, Src src)
 {
     constexpr int B = NFFT / 2, R = NFFT / 256, LOG = NFFT == 1024 ? 10 : 9;
     __shared__ double2 tw[B];
@@ -1459,50 +1540,47 @@ __global__ __launch_bounds__(256) void denoise_redo_f64_kernel(
         }
         win[r] = 0.54 - 0.46 * cos(2 * 3.141592 * i / (NFFT - 1));    // SS:226
     }
-    const long n_samples = n_blocks * B;
     for (long it = blockIdx.x; it < n_redo; it += gridDim.x) {
-        const long f = redo[1 + it];
+        src.seek(redo[1 + it]);
         for (int q = 0; q < 3; q++) {
-            const long j = f - 1 + q;
-            // (uniform) frames outside the call add nothing here: block 0 takes the overlap carried in instead;
-            // the very first call of a stream only stashes its block (SS:211-216)
-            const bool have = j >= 0 && j < n_blocks && calls_before + j > 0;
+            const bool have = src.have(q);                       // (uniform)
             __syncthreads();
             if (!have) {
 #pragma unroll
                 for (int r = 0; r < R; r++) yy[q][tid + 256 * r] = 0.0;
                 continue;
             }
-            const float *row = noise_row(noise_rows, ver_base, snap_mask, j, sh);
+            const float *row = src.row(q);
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const int i = tid + 256 * r;
-                const double v = redo_sample<NFFT>(pcm, n_samples, st_in, (j - 1) * B + i) * win[r];
-                buf[__brev((unsigned)i) >> (32 - LOG)] = make_double2(v, 0.0);
+                buf[__brev((unsigned)i) >> (32 - LOG)] = make_double2(src.sample(q, i) * win[r], 0.0);
             }
             redo_gain_frame<NFFT>(buf, tw, row, mode, tid, yy[q]);
         }
         __syncthreads();
         for (int q = 0; q < 2; q++) {
-            const long b = f + q;
-            if (b >= n_blocks) break;
+            if (!src.writes(q)) continue;
 #pragma unroll
             for (int r = 0; r < R / 2; r++) {
                 const int i = tid + 256 * r;
-                const double t = b == 0 ? (double)st_in->tail[i] : yy[q][B + i];        // rgsdOveraped carried over
-                const float o = (float)(t + yy[q + 1][i]);                              // SS:248 overlap-add
-                if (b >= sh.emit_from && b < sh.emit_to) {
-                    const long oi = b - sh.emit_from;
-                    out[oi * B + i] = (short)cast_i16_bits(o);
-                    if (precast) precast[oi * B + i] = o;
-                }
+                const double t = src.carried(q) ? src.carry(i) : yy[q][B + i];
+                src.store(q, i, (float)(t + yy[q + 1][i]));      // SS:248 overlap-add
             }
         }
-        if (f == n_blocks - 1) {
-#pragma unroll
-            for (int r = 0; r < R / 2; r++) st_out->tail[tid + 256 * r] = (float)yy[1][B + tid + 256 * r];   // SS:255-256
-        }
+        src.finish(yy[1] + B, tid);
     }
+}
+
+template <int NFFT>
+__global__ __launch_bounds__(256) void denoise_redo_f64_kernel(
+    const short *__restrict__ pcm, long n_blocks, long calls_before, const DenoiseState *__restrict__ st_in,
+    DenoiseState *st_out, const int *__restrict__ ver_base, const unsigned long long *__restrict__ snap_mask,
+    const float *__restrict__ noise_rows, short *__restrict__ out, float *__restrict__ precast, DenoiseShard sh,
+    const int *__restrict__ redo, int mode)
+{
+    redo_f64_run<NFFT>(redo, mode, RedoStream<NFFT>{pcm, n_blocks, calls_before, st_in, st_out, ver_base, snap_mask,
+                                                    noise_rows, out, precast, sh, 0});
 }
 
 constexpr int kRedoGrid = 1024;
@@ -1725,67 +1803,13 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_batch_kerne
     }
 }
 
-// denoise_redo_f64_kernel<1024> for the batch: a listed global frame f of utterance u (local b) adds into the outputs
-// of the local blocks b and b + 1, so the workgroup computes the frames b - 1, b, b + 1 that exist (local blocks
-// 1 .. B_u - 1: never the previous utterance's last frame, never the next one's first) and writes both outputs again
-// where the run kernel writes them: at the time of the local blocks b - 1 and b, if those are 1 .. B_u - 2.
 __global__ __launch_bounds__(256) void denoise_redo_f64_batch_kernel(
     const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
     long n_utts, const int *__restrict__ row_idx, const float *__restrict__ noise_rows, short *__restrict__ out,
     float *__restrict__ precast, const int *__restrict__ redo, int mode)
 {
-    __shared__ double2 tw[512];
-    __shared__ double2 buf[1024];
-    __shared__ double yy[3][1024];
-    const int tid = threadIdx.x;
-    const long n_redo = redo[0];
-    if ((long)blockIdx.x >= n_redo) return;                     // (the whole workgroup)
-    double win[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int i = tid + 256 * r;
-        if (i < 512) {
-            double sn, cs;
-            sincospi(2.0 * (double)i / 1024.0, &sn, &cs);
-            tw[i] = make_double2(cs, -sn);
-        }
-        win[r] = 0.54 - 0.46 * cos(2 * 3.141592 * i / (1024 - 1));    // SS:226
-    }
-    for (long it = blockIdx.x; it < n_redo; it += gridDim.x) {
-        const long f = redo[1 + it];
-        const long u = ragged_find_utt(block_first, n_utts, f);
-        const long ub = uniform_i64(block_first + u), n_own = uniform_i64(block_first + u + 1) - ub;
-        const long first = uniform_i64(sample_first + u), b = f - ub;
-        for (int q = 0; q < 3; q++) {
-            const long bq = b - 1 + q;
-            const bool have = bq >= 1 && bq < n_own;              // (uniform) local block 0 only stashes its samples
-            __syncthreads();
-            if (!have) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) yy[q][tid + 256 * r] = 0.0;
-                continue;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int i = tid + 256 * r;
-                buf[__brev((unsigned)i) >> 22] = make_double2((double)pcm[first + (bq - 1) * 512 + i] * win[r], 0.0);
-            }
-            redo_gain_frame<1024>(buf, tw, noise_rows + (size_t)row_idx[ub + bq] * 1024, mode, tid, yy[q]);
-        }
-        __syncthreads();
-        for (int q = 0; q < 2; q++) {
-            const long bo = b + q;                                // its output lies at the time of local block bo - 1
-            if (bo < 2 || bo >= n_own) continue;
-#pragma unroll
-            for (int r = 0; r < 2; r++) {
-                const int i = tid + 256 * r;
-                const float o = (float)(yy[q][512 + i] + yy[q + 1][i]);                 // SS:248 overlap-add
-                const long at = first + (bo - 1) * 512 + i;
-                if (out) out[at] = (short)cast_i16_bits(o);
-                if (precast) precast[at] = o;
-            }
-        }
-    }
+    redo_f64_run<1024>(redo, mode, RedoBatch{pcm, sample_first, block_first, n_utts, row_idx, noise_rows, out, precast,
+                                             0, 0, 0, 0});
 }
 
 // run_opt: blocks per wave, 0 = one round of resident waves (resident_run).  flags / row_idx

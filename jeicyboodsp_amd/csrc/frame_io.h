@@ -23,6 +23,36 @@ __device__ __forceinline__ float2 unpack_i16x2(unsigned int raw)
     return make_float2((float)(short)(raw & 0xffffu), (float)((int)raw >> 16));
 }
 
+// The PCM of consecutive frames one hop apart, in the transform's layout (lane l holds the sample pairs 2 l + 128 r, +1
+// in raw[r]): a hop is HR = 8 hop / 1024 registers, so frame j + 1 is frame j shifted down by HR registers plus one new
+// hop, and a wave reads every sample of a span once.  Per frame: prefetch() the next frame's new hop (the caller clamps
+// `at` inside the span, so no sample outside it is read: at a span's last frame it names that frame again), use raw,
+// advance().  advance() goes BEFORE the frame's stores: vmcnt counts loads and stores in issue order, so a wait for the
+// prefetch at the top of the next iteration would also wait for every store issued in between.  At a new span load()
+// reads all eight registers again.  `at`: the frame's first sample.
+template <int HR> struct PcmHops {
+    unsigned int raw[8], nraw[HR];
+    __device__ __forceinline__ void load(const short *pcm, long at, int lane)
+    {
+        const unsigned int *p = reinterpret_cast<const unsigned int *>(pcm + at) + lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+    }
+    __device__ __forceinline__ void prefetch(const short *pcm, long at, int lane)
+    {
+        const unsigned int *p = reinterpret_cast<const unsigned int *>(pcm + at) + 64 * (8 - HR) + lane;
+#pragma unroll
+        for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
+    }
+    __device__ __forceinline__ void advance()
+    {
+#pragma unroll
+        for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
+#pragma unroll
+        for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
+    }
+};
+
 // (short)double of the reference (e.g. SpectralSubtraction_final.cpp:252): truncate toward
 // zero, keep the low 16 bits (what x86 does for in-int32-range values); NaN -> 0.
 __device__ __forceinline__ unsigned int cast_i16_bits(float v)

@@ -9,8 +9,10 @@
 //             through the same image), so a non-Hermitian row gives exactly the real part of its full inverse.
 //   n = 512   one 512-point complex inverse of H per frame, real part kept.  Never two frames in one transform: a
 //             frame's result must not depend on its neighbour, or on where a call or shard cut falls.
-// The halo frames run through an unrolled loop of their own in front of the run: they need no prefetch and no stores.
-// istft_batch_kernel, at the end, runs the same frame for a batch of ragged utterances (ragged_batch.h).
+// istft_run_kernel (one stream) and istft_batch_kernel (a batch of ragged utterances) are one body, istft_run, over the
+// two forms of ragged_batch.h's span walk.  They share the setup, the frame, the staging and the loop's tail; two things
+// stay forked at compile time, both for speed: the stream's halo runs unrolled in front of the loop where the batch's
+// goes through it with emission off, and the stream skips the row prefetch on its run's last frame.
 #include "jdsp_internal.h"
 #include "ola_stream.h"
 #include "ragged_batch.h"
@@ -114,24 +116,33 @@ __device__ __forceinline__ void istft_frame(const float2 *img, float2 *scratch, 
     }
 }
 
+// A single stream (jdsp_istft_*) or a batch of independent streams, the utterances, in one launch (jdsp_istft_batch_*):
+// the waves are planned over the frame axis (of the batch the concatenated one), global frame j is spectrum row j, and
+// the span walk of ragged_batch.h says where its samples go, where a wave's halo stops and where a span ends.
 struct IstftArgs {
     const float2 *spec;
-    long pitch, n_frames;
+    long pitch, n_frames;     // n_frames: of all utterances
+    long n_utts;              // a batch
     const float *ws;          // [n]   w_s[i] / n, natural order
     const float *g;           // [hop] WOLA gain (1 without an analysis window)
-    const float *tail_in;     // [n - hop] partial sums of the samples after the last emitted one
-    float *tail_out;
     short *out;               // may be NULL
     float *out_f32;           // may be NULL
     int run;
+    const float *tail_in;     // a stream: [n - hop] partial sums of the samples after the last emitted one
+    float *tail_out;
 };
+// the same under the name the batch kernels' symbols carry (profiles and tools find a kernel by its symbol)
+struct IstftBatchArgs : IstftArgs {};
 
-template <int N, int HALF, int R>
-__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(IstftArgs a, const float2 *__restrict__ table)
+// One wave's run.  The rows are prefetched one frame ahead, on across utterances (a row belongs to no span).  A
+// stream's tail is read by the wave that starts at frame 0 and written by the one that owns the call's last frame
+// (OlaAcc::shift); after an utterance's last frame the tail leaves from the registers (OlaAcc::emit_tail) and the sums restart: no tail in
+// memory, no flush launch, and the handle's own tail is neither read nor written.
+template <int N, int HALF, int R, class Span>
+__device__ __forceinline__ void istft_run(const IstftArgs &a, const float2 *__restrict__ table, Span span)
 {
     typedef typename IstftSample<N>::T T;
     constexpr int HR = 8 / R;                                   // registers per hop
-    constexpr int HOP = N / R;
     constexpr int kL = IstftLoad<N, HALF>::kLoads;
     // the row's natural-order image, then the transform's scratch: 12.9 KB per wave at n = 1024 FULL (three waves
     // per SIMD, what its registers allow), 8.8 KB otherwise
@@ -142,6 +153,7 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(Istf
     const int lane = threadIdx.x;
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
+    span.begin(j0);
 
     WaveTwiddles tw;
     load_wave_twiddles(tw, table, lane);
@@ -156,10 +168,17 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(Istf
     ola.init(a.g, lane);
     T y[8], o[HR];
     float2 nx[kL], nnyq = make_float2(0.f, 0.f);
-    if (j0 == 0) {
+
+    // The halo: transformed and added, not emitted.  A batch's is 0..R-1 frames long and goes through the loop below with
+    // the stores off.  A stream's is R - 1 frames wherever j0 > 0 and runs here, in front of the loop, unrolled, with no
+    // prefetch: through the loop the stream's half-spectrum leg was 1.2-2 % slower than before in every round measured
+    // (profiles/r17_one_frame_walk.txt), so the stream keeps this second copy of the frame.
+    long js = j0;
+    if constexpr (Span::kBatch) {
+        js = span.first(j0, R);
+    } else if (j0 == 0) {
         ola.load_tail(a.tail_in, lane);
     } else {
-        // halo: frames j0 - R + 1 .. j0 - 1 (all >= 0: the launch keeps run >= R - 1)
 #pragma unroll
         for (int k = R - 1; k >= 1; k--) {
             istft_load<N, HALF>(a.spec + (j0 - k) * a.pitch, lane, nx, nnyq);
@@ -170,22 +189,49 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(Istf
             ola.shift(false, nullptr, lane);
         }
     }
-
-    istft_load<N, HALF>(a.spec + j0 * a.pitch, lane, nx, nnyq);
+    istft_load<N, HALF>(a.spec + js * a.pitch, lane, nx, nnyq);
     istft_stage<N, HALF>(nx, nnyq, img, lane);
     wave_lds_fence();
-    for (long j = j0; j < j1; j++) {
-        if (j + 1 < j1) istft_load<N, HALF>(a.spec + (j + 1) * a.pitch, lane, nx, nnyq);   // staged one frame from now
+    for (long j = js; j < j1; j++) {
+        // the next row, staged one frame from now.  A stream has none on its run's last frame (with the halo in the
+        // loop and this load unguarded its full-spectrum legs were 4-5 % slower: one more row per run, in a kernel its
+        // reads bound); a batch loads on, unguarded, at a clamped row (past the wave's run it is never used)
+        const bool more = Span::kBatch || j + 1 < j1;
+        const long jn = Span::kBatch && j + 1 >= a.n_frames ? a.n_frames - 1 : j + 1;
+        if (more) istft_load<N, HALF>(a.spec + jn * a.pitch, lane, nx, nnyq);
         istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
         ola.add(y, o);
         // stage the prefetched row before this frame's stores: vmcnt counts loads and stores in issue order, and a wait
-        // for the row at the top of the next iteration would also wait for these stores (denoise_run_kernel)
-        if (j + 1 < j1) istft_stage<N, HALF>(nx, nnyq, img, lane);    // the image's reads are behind istft_frame's fence
+        // for the row at the top of the next iteration would also wait for these stores.  The image's reads are behind
+        // istft_frame's fence.
+        if (more) istft_stage<N, HALF>(nx, nnyq, img, lane);
         __builtin_amdgcn_sched_barrier(0);
-        ola.emit(o, a.out, a.out_f32, j * HOP, lane);
-        ola.shift(j == a.n_frames - 1, a.tail_out, lane);
+        if (!Span::kBatch || j >= j0) ola.emit(o, a.out, a.out_f32, span.at(j), lane);
+        const bool last = span.last(j);
+        ola.shift(!Span::kBatch && last, a.tail_out, lane);
+        if (Span::kBatch && last) {
+            // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
+            // the last frame emits the tail
+            ola.emit_tail(a.out, a.out_f32, span.at(j + 1), lane);
+            ola.restart();
+            if (j + 1 < j1) span.next();                         // frame j + 1 exists, so a non-empty utterance follows
+        }
         wave_lds_fence();                                        // the staged row before the next frame reads it
     }
+}
+
+template <int N, int HALF, int R>
+__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_run_kernel(IstftArgs a, const float2 *__restrict__ table)
+{
+    istft_run<N, HALF, R>(a, table, StreamSpan<N / R>(a.n_frames));
+}
+
+template <int N, int HALF, int R>
+__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_batch_kernel(
+    IstftBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
+    const long long *__restrict__ frame_first)
+{
+    istft_run<N, HALF, R>(a, table, RaggedSpan<N / R>(sample_first, frame_first, a.n_utts));
 }
 
 // flush: the n - hop samples still in the tail, g[t mod hop] * s[t], then the same cast
@@ -200,18 +246,41 @@ __global__ __launch_bounds__(256) void istft_flush_kernel(const float *__restric
     if (out_f32) out_f32[i] = o;
 }
 
+// sample_first == NULL: a single stream
 template <int N, int HALF, int R>
-static void launch_run(hipStream_t s, long grid, const IstftArgs &a, const float2 *table)
+static void launch_one(hipStream_t s, long grid, const IstftArgs &a, const float2 *table, const long long *sample_first,
+                       const long long *frame_first)
 {
-    hipLaunchKernelGGL((istft_run_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, a, table);
+    if (sample_first)
+        hipLaunchKernelGGL((istft_batch_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, IstftBatchArgs{a}, table,
+                           sample_first, frame_first);
+    else
+        hipLaunchKernelGGL((istft_run_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, a, table);
 }
 
 template <int N, int HALF>
-static void launch_r(hipStream_t s, int r, long grid, const IstftArgs &a, const float2 *table)
+static void launch_r(hipStream_t s, int r, long grid, const IstftArgs &a, const float2 *table,
+                     const long long *sample_first, const long long *frame_first)
 {
-    if (r == 1) launch_run<N, HALF, 1>(s, grid, a, table);
-    else if (r == 2) launch_run<N, HALF, 2>(s, grid, a, table);
-    else launch_run<N, HALF, 4>(s, grid, a, table);
+    if (r == 1) launch_one<N, HALF, 1>(s, grid, a, table, sample_first, frame_first);
+    else if (r == 2) launch_one<N, HALF, 2>(s, grid, a, table, sample_first, frame_first);
+    else launch_one<N, HALF, 4>(s, grid, a, table, sample_first, frame_first);
+}
+
+static int launch_any(hipStream_t s, int n_cu, int n_fft, int hop, int half, IstftArgs a, const float2 *table,
+                      int run_opt, const long long *sample_first, const long long *frame_first)
+{
+    const int r = n_fft / hop;
+    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, a.n_frames, run_opt);
+    a.run = (int)p.run;
+    if (n_fft == 1024) {
+        if (half) launch_r<1024, 1>(s, r, p.grid, a, table, sample_first, frame_first);
+        else launch_r<1024, 0>(s, r, p.grid, a, table, sample_first, frame_first);
+    } else {
+        if (half) launch_r<512, 1>(s, r, p.grid, a, table, sample_first, frame_first);
+        else launch_r<512, 0>(s, r, p.grid, a, table, sample_first, frame_first);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch, long n_frames,
@@ -219,17 +288,8 @@ int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const fl
                  const float2 *table, int run_opt)
 {
     if (n_frames <= 0) return 0;
-    const int r = n_fft / hop;
-    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, n_frames, run_opt);
-    IstftArgs a = {spec, pitch, n_frames, ws, g, tail_in, tail_out, out, out_f32, (int)p.run};
-    if (n_fft == 1024) {
-        if (half) launch_r<1024, 1>(s, r, p.grid, a, table);
-        else launch_r<1024, 0>(s, r, p.grid, a, table);
-    } else {
-        if (half) launch_r<512, 1>(s, r, p.grid, a, table);
-        else launch_r<512, 0>(s, r, p.grid, a, table);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const IstftArgs a = {spec, pitch, n_frames, 1, ws, g, out, out_f32, 0, tail_in, tail_out};
+    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, nullptr, nullptr);
 }
 
 int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32)
@@ -240,124 +300,13 @@ int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_t
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// ---- a batch of independent streams (utterances) in one launch (jdsp_istft_batch_*) --------------------------------
-// istft_run_kernel's frame under the walk of ragged_batch.h (the layout of stftmask_batch_kernel): the waves are planned
-// over the concatenated frame axis, global frame j is spectrum row j.  The halo of a wave stops at its utterance's
-// first frame, so it is 0..R-1 frames long and goes through the one loop, without the stores; the rows are prefetched
-// one frame ahead, on across utterances (a row belongs to no span).  After an utterance's last frame the tail leaves
-// from the registers (OlaAcc::emit_tail) and the sums restart: no tail in memory, no flush launch, and the handle's
-// own tail is neither read nor written.
-struct IstftBatchArgs {
-    const float2 *spec;
-    long pitch, n_frames;     // n_frames: of all utterances, frame_first[n_utts]
-    long n_utts;
-    const float *ws, *g;      // as IstftArgs
-    short *out;               // may be NULL
-    float *out_f32;           // may be NULL
-    int run;
-};
-
-template <int N, int HALF, int R>
-__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_batch_kernel(
-    IstftBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
-    const long long *__restrict__ frame_first)
-{
-    typedef typename IstftSample<N>::T T;
-    constexpr int HR = 8 / R;
-    constexpr int HOP = N / R;
-    constexpr int kL = IstftLoad<N, HALF>::kLoads;
-    constexpr int kImg = HALF ? N / 2 + 1 : N + 1;               // istft_run_kernel's LDS, no more
-    __shared__ __attribute__((aligned(16))) float2 lds[kImg + 1 + kWaveLdsComplex];
-    float2 *const img = lds;
-    float2 *const scratch = lds + ((kImg + 1) & ~1);
-    const int lane = threadIdx.x;
-    long j0, j1;
-    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
-    long u = ragged_find_utt(frame_first, a.n_utts, j0);        // the utterance of frame j0
-    const long ub = uniform_i64(frame_first + u);
-    long ue = uniform_i64(frame_first + u + 1);
-    // the halo, as in istft_run_kernel, but never into the utterance before
-    const long js = j0 - ub < R - 1 ? ub : j0 - (R - 1);
-    long base = uniform_i64(sample_first + u) - ub * HOP;        // global frame j of this utterance starts at base + j HOP
-
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    SplitTwiddles sw;
-    if (N == 1024) load_split_twiddles(sw, table, lane);
-    T ws[8];
-    const T *ws_t = reinterpret_cast<const T *>(a.ws);
-#pragma unroll
-    for (int d = 0; d < 8; d++) ws[d] = ws_t[lane + 64 * d];
-
-    OlaAcc<T, HR> ola;
-    ola.init(a.g, lane);
-    T y[8], o[HR];
-    float2 nx[kL], nnyq = make_float2(0.f, 0.f);
-
-    istft_load<N, HALF>(a.spec + js * a.pitch, lane, nx, nnyq);
-    istft_stage<N, HALF>(nx, nnyq, img, lane);
-    wave_lds_fence();
-    for (long j = js; j < j1; j++) {
-        // the next row, staged one frame from now: an unguarded load at a clamped frame (past the wave's run it is
-        // never used)
-        const long jn = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
-        istft_load<N, HALF>(a.spec + jn * a.pitch, lane, nx, nnyq);
-        istft_frame<N, HALF>(img, scratch, lane, tw, sw, ws, y);
-        ola.add(y, o);
-        // staged before this frame's stores (istft_run_kernel); the image's reads are behind istft_frame's fence
-        istft_stage<N, HALF>(nx, nnyq, img, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        if (j >= j0) ola.emit(o, a.out, a.out_f32, base + j * HOP, lane);
-        ola.shift(false, nullptr, lane);
-        if (j + 1 == ue) {
-            // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
-            // the last frame emits the tail
-            ola.emit_tail(a.out, a.out_f32, base + (j + 1) * HOP, lane);
-            ola.restart();
-            if (j + 1 < j1) {
-                // frame j + 1 exists, so a non-empty utterance follows
-                const long nb = ue;
-                ragged_next_utt(frame_first, a.n_utts, u, ue);
-                base = uniform_i64(sample_first + u) - nb * HOP;
-            }
-        }
-        wave_lds_fence();                                        // the staged row before the next frame reads it
-    }
-}
-
-template <int N, int HALF, int R>
-static void launch_batch_run(hipStream_t s, long grid, const IstftBatchArgs &a, const float2 *table,
-                             const long long *sample_first, const long long *frame_first)
-{
-    hipLaunchKernelGGL((istft_batch_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
-                       frame_first);
-}
-
-template <int N, int HALF>
-static void launch_batch_r(hipStream_t s, int r, long grid, const IstftBatchArgs &a, const float2 *table,
-                           const long long *sample_first, const long long *frame_first)
-{
-    if (r == 1) launch_batch_run<N, HALF, 1>(s, grid, a, table, sample_first, frame_first);
-    else if (r == 2) launch_batch_run<N, HALF, 2>(s, grid, a, table, sample_first, frame_first);
-    else launch_batch_run<N, HALF, 4>(s, grid, a, table, sample_first, frame_first);
-}
-
 int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
                        long n_frames_total, const long long *sample_first, const long long *frame_first, long n_utts,
                        const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt)
 {
     if (n_frames_total <= 0 || n_utts <= 0) return 0;
-    const int r = n_fft / hop;
-    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, n_frames_total, run_opt);
-    IstftBatchArgs a = {spec, pitch, n_frames_total, n_utts, ws, g, out, out_f32, (int)p.run};
-    if (n_fft == 1024) {
-        if (half) launch_batch_r<1024, 1>(s, r, p.grid, a, table, sample_first, frame_first);
-        else launch_batch_r<1024, 0>(s, r, p.grid, a, table, sample_first, frame_first);
-    } else {
-        if (half) launch_batch_r<512, 1>(s, r, p.grid, a, table, sample_first, frame_first);
-        else launch_batch_r<512, 0>(s, r, p.grid, a, table, sample_first, frame_first);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const IstftArgs a = {spec, pitch, n_frames_total, n_utts, ws, g, out, out_f32, 0, nullptr, nullptr};
+    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, sample_first, frame_first);
 }
 
 }  // namespace jdsp

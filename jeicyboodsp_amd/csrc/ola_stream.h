@@ -1,7 +1,7 @@
-// ola_stream.h -- the overlap-add output stream of the streaming synthesis kernels: istft_run_kernel (istft_kernels.hip)
-// and stftmask_run_kernel (stftmask_kernels.hip) compute a windowed frame each in their own way and hand it to the
-// one stream defined here.  Its host side, what a handle carries from call to call, is jdsp::OlaStream
-// (jdsp_internal.h).
+// ola_stream.h -- the overlap-add output stream of the streaming synthesis kernels: istft_run (istft_kernels.hip, the
+// body under istft_run_kernel and istft_batch_kernel) and stftmask_run_kernel / stftmask_batch_kernel
+// (stftmask_kernels.hip) compute a windowed frame in their own way and hand it to the one stream defined here.  Its host side, what a handle carries from call to
+// call, is jdsp::OlaStream (jdsp_internal.h).
 //
 // One wave per run of consecutive frames (persistent: the launch picks the run so that the batch is about one round of
 // resident waves, in XCD-aware order, as denoise_run_kernel).  Lane l holds frame samples 2 l + 128 d, +1 (n = 1024, one
@@ -10,10 +10,10 @@
 // move down.  Every output sample is the FP32 sum of its frames in ascending order, starting from 0 (or from the tail),
 // then one multiply by the gain g, then the cast -- the same operations whatever the call cuts or the launch geometry,
 // so results are bit-identical across both.  A wave whose run starts at frame j0 > 0 recomputes the R - 1 frames
-// before it (the halo: added and shifted, not emitted); only the wave with j0 = 0 reads the tail carried in the handle,
-// and the wave that owns the call's last frame writes the new tail (ping-pong buffers: another wave may still be
-// reading the old one).  stftmask_batch_kernel feeds many independent streams from one launch: a stream that ends
-// inside a wave's run leaves through emit_tail and the next starts after restart, with no tail in memory at all.
+// before it (the halo: added and shifted, not emitted; in a batch it stops at the utterance's first frame,
+// ragged_batch.h).  A single stream: only the wave with j0 = 0 reads the tail carried in the handle, and the wave that owns
+// the call's last frame writes the new tail (ping-pong buffers: another wave may still be reading the old one).  A batch (RaggedSpan) feeds many independent streams from one launch: a stream that ends inside a
+// wave's run leaves through emit_tail and the next starts after restart, with no tail in memory at all.
 #pragma once
 #include "frame_io.h"
 
@@ -132,7 +132,7 @@ template <class T, int HR> struct OlaAcc {
             for (int d = 0; d < 8 - HR; d++) tl[lane + 64 * d] = acc[d];
         }
     }
-    // A stream that ends inside the wave (a batch of independent streams, stftmask_batch_kernel): after the shift of
+    // A stream that ends inside the wave (a batch of independent streams, the *_batch_kernel): after the shift of
     // its last frame, the n - hop samples left go out from the registers, to the stream's sample `at` onwards -- the
     // flush's g[t mod hop] * s[t] (a hop is HR registers, so register d takes g[d % HR]) and emit's casts and stores
     __device__ __forceinline__ void emit_tail(short *out, float *out_f32, long at, int lane) const

@@ -7,6 +7,11 @@
 // with frame_first[u] <= j < frame_first[u + 1] and starts at the sample sample_first[u] + hop (j - frame_first[u]).
 // A wave finds the utterance of its first frame by a binary search and then walks from utterance to utterance.  All
 // of it is uniform across the wave: it lives in scalar registers and costs neither vector registers nor LDS.
+//
+// The span walk at the end is that state behind the questions a frame loop asks: RaggedSpan, the above, walked by
+// stftmask_batch_kernel, stft_half_batch_kernel and istft_batch_kernel, and StreamSpan, a single stream -- a batch of
+// one span [0, n_frames) at sample 0 whose tail is carried by the handle instead of leaving from the registers -- under
+// which the same body (istft_run) is istft_run_kernel.
 #pragma once
 
 namespace jdsp {
@@ -43,5 +48,52 @@ __device__ __forceinline__ void ragged_next_utt(const long long *frame_first, lo
         ue = uniform_i64(frame_first + u + 1);
     } while (ue == nb && u + 1 < n_utts);
 }
+
+// ---- the span walk ---------------------------------------------------------------------------------------------
+// The first frame a wave computes when its run starts at j0, r frames overlap and its span starts at frame ub: the
+// r - 1 frames before j0 (the halo: added, not emitted), but never a frame of the span before.  For a single stream
+// (ub = 0) this is j0 == 0 ? 0 : j0 - (r - 1): the launch keeps run >= r - 1 (plan_ola_run), so a run that does not
+// start at 0 starts at r - 1 or later and only j0 = 0 takes the first branch.
+__device__ __forceinline__ long span_halo_first(long j0, long ub, int r) { return j0 - ub < r - 1 ? ub : j0 - (r - 1); }
+
+// begin(j0): at the span of frame j0.  first(j0, r): see above.  at(j): the sample where global frame j of the current
+// span starts.  last(j): j is the current span's last frame.  next_inside(j): frame j + 1, or at the span's end a frame
+// of the span again (where a prefetch may read when nothing follows).  next(): after the span's last frame j, when
+// frame j + 1 exists, into the span that holds it.  StreamSpan has what istft_run asks of a stream: its halo stands in
+// front of the loop and its prefetch needs no clamp.
+template <int HOP> struct StreamSpan {
+    static constexpr bool kBatch = false;
+    long n_frames;
+    __device__ __forceinline__ explicit StreamSpan(long n) : n_frames(n) {}
+    __device__ __forceinline__ void begin(long) {}
+    __device__ __forceinline__ long at(long j) const { return j * HOP; }
+    __device__ __forceinline__ bool last(long j) const { return j + 1 == n_frames; }
+    __device__ __forceinline__ void next() {}
+};
+
+template <int HOP> struct RaggedSpan {
+    static constexpr bool kBatch = true;
+    const long long *sample_first, *frame_first;
+    long n_utts, u, ub, ue, base;                                // global frame j of utterance u starts at base + j HOP
+    __device__ __forceinline__ RaggedSpan(const long long *sf, const long long *ff, long n)
+        : sample_first(sf), frame_first(ff), n_utts(n) {}
+    __device__ __forceinline__ void begin(long j0)
+    {
+        u = ragged_find_utt(frame_first, n_utts, j0);
+        ub = uniform_i64(frame_first + u);
+        ue = uniform_i64(frame_first + u + 1);
+        base = uniform_i64(sample_first + u) - ub * HOP;
+    }
+    __device__ __forceinline__ long first(long j0, int r) const { return span_halo_first(j0, ub, r); }
+    __device__ __forceinline__ long at(long j) const { return base + j * HOP; }
+    __device__ __forceinline__ bool last(long j) const { return j + 1 == ue; }
+    __device__ __forceinline__ long next_inside(long j) const { return j + 1 == ue ? j : j + 1; }
+    __device__ __forceinline__ void next()
+    {
+        ub = ue;
+        ragged_next_utt(frame_first, n_utts, u, ue);
+        base = uniform_i64(sample_first + u) - ub * HOP;
+    }
+};
 
 }  // namespace jdsp

@@ -287,13 +287,11 @@ int launch_stft1024_half(hipStream_t stream, const short *pcm, long n_frames, fl
 }
 
 // ---- half spectrum of a batch of ragged utterances in one launch (jdsp_stft_half_batch_*) -----------------------
-// The layout and the walk are ragged_batch.h's, the ones stftmask_batch_kernel uses: wave w owns the global frames
-// [w run, (w + 1) run) of the concatenated frame axis (ola_run_range: the plan is arithmetic on the total alone), global
-// frame j is spectrum row j and starts at the sample sample_first[u] + hop (j - frame_first[u]) of its utterance u.
-// The PCM goes through stftmask_batch_kernel's register pipeline: raw[8] holds the frame's sample pairs, the next
-// frame's new hop (HR = 8 / R registers) is prefetched into nraw -- clamped inside the utterance, so no sample outside
-// a span is read -- and the registers shift down by a hop; at a new span all eight are read again.  An analysis frame
-// depends on no other frame, so there is no halo.
+// The layout and the walk are ragged_batch.h's (RaggedSpan): wave w owns the global frames [w run, (w + 1) run) of the
+// concatenated frame axis (ola_run_range: the plan is arithmetic on the total alone), global frame j is spectrum row j
+// and starts at the sample sample_first[u] + hop (j - frame_first[u]) of its utterance u.  The PCM goes through the
+// register pipeline of frame_io.h (PcmHops), clamped inside the utterance, so no sample outside a span is read.  An
+// analysis frame depends on no other frame, so there is no halo.
 // Every row takes the EVEN-row store (split_store_half<false>): the pitch is even, so every row is 16-byte aligned.
 // That is the arithmetic of the full-spectrum kernels' split (split_fwd<J> with t.wsp, bin 512 = hi0 of lane 0), so
 // row j equals bins 0..512 of jdsp_stft_i16_dev on the utterance alone bit for bit; the odd-row store of the dense-513
@@ -315,58 +313,36 @@ __global__ __launch_bounds__(64, JDSP_STFT_MINWAVES) void stft_half_batch_kernel
     StftBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
     const long long *__restrict__ frame_first)
 {
-    constexpr int HR = 8 / R;                                   // registers per hop
-    constexpr int HOP = 1024 / R;
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
-    long u = ragged_find_utt(frame_first, a.n_utts, j0);
-    long ue = uniform_i64(frame_first + u + 1);
-    long base = uniform_i64(sample_first + u) - uniform_i64(frame_first + u) * HOP;   // frame j starts at base + j HOP
+    RaggedSpan<1024 / R> span(sample_first, frame_first, a.n_utts);
+    span.begin(j0);
 
-    unsigned int raw[8], nraw[HR];
-    {
-        const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + j0 * HOP) + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
-    }
+    PcmHops<8 / R> pcm;
+    pcm.load(a.pcm, span.at(j0), lane);
     FrameTables t;
     load_frame_tables(t, table, lane);
     for (long j = j0; j < j1; j++) {
-        // frame j + 1's new hop, inside the utterance: after its last frame the next samples are another span's
-        const bool last = j + 1 == ue;
-        const long jp = last ? j : j + 1;
-        {
-            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + jp * HOP) + 64 * (8 - HR) + lane;
-#pragma unroll
-            for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
-        }
+        const bool last = span.last(j);
+        pcm.prefetch(a.pcm, span.at(span.next_inside(j)), lane);  // frame j + 1's new hop, inside the utterance
         float2 v[8];
 #pragma unroll
         for (int r = 0; r < 8; r++) {
-            const float2 s = unpack_i16x2(raw[r]);
+            const float2 s = unpack_i16x2(pcm.raw[r]);
             v[r] = make_float2(s.x * t.win[r].x, s.y * t.win[r].y);
         }
         wave_fft512<false>(v, lds, lane, t.tw);
         store_natural_image(lds, lane, v);
         wave_lds_fence();
-        // staged before this frame's stores: a wait for the prefetch behind them would wait for the stores too
-#pragma unroll
-        for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
-#pragma unroll
-        for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
+        pcm.advance();                                           // staged before this frame's stores (frame_io.h)
         __builtin_amdgcn_sched_barrier(0);
         split_store_half<false>(lds, lane, t.wsp, a.spec + j * a.pitch);
         wave_lds_fence();
         if (last && j + 1 < j1) {
-            // frame j + 1 exists, so a non-empty utterance follows: all eight registers at its first sample
-            const long nb = ue;
-            ragged_next_utt(frame_first, a.n_utts, u, ue);
-            base = uniform_i64(sample_first + u) - nb * HOP;
-            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + nb * HOP) + lane;
-#pragma unroll
-            for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+            span.next();                                         // frame j + 1 exists, so a non-empty utterance follows
+            pcm.load(a.pcm, span.at(j + 1), lane);
         }
     }
 }

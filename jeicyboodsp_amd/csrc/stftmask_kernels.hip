@@ -406,8 +406,12 @@ int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const sh
 // sample_first[u] + hop (j - frame_first[u]) of pcm and out.  A wave finds the utterance of its first frame by a
 // binary search and then walks: its halo stops at the utterance's first frame; after an utterance's last frame it
 // writes the tail from its registers (OlaAcc::emit_tail: no flush launch, no tail in memory), zeroes the sums and
-// reads all eight raw registers at the next non-empty utterance's first sample.  The search and the step from one
-// utterance to the next are ragged_batch.h's, shared with the analysis and synthesis batch kernels.
+// reads all eight raw registers at the next non-empty utterance's first sample.  That walk is RaggedSpan
+// (ragged_batch.h) and the raw registers are PcmHops (frame_io.h), both shared with the analysis and synthesis batch
+// kernels.  The stream kernel above keeps its own loop, statement for statement: every restatement of it tried -- the
+// merged loop under either args layout or with two args structs, the hop pipeline alone -- moved its instruction
+// schedule, and with it two to four benchmark legs by 0.2-0.9 % past the parent's spread
+// (profiles/r17_one_frame_walk.txt).
 struct StftMaskBatchArgs {
     const short *pcm;
     const void *mask;
@@ -426,7 +430,6 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     const long long *__restrict__ frame_first)
 {
     constexpr int HR = 8 / R;
-    constexpr int HOP = 1024 / R;
     constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
     JDSP_STFTMASK_LDS;
     const int lane = threadIdx.x;
@@ -434,12 +437,9 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     int n_redo = 0;                                              // emitted frames of this run computed again in FP64
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
-    long u = ragged_find_utt(frame_first, a.n_utts, j0);       // the utterance of frame j0 (ragged_batch.h)
-    const long ub = uniform_i64(frame_first + u);
-    long ue = uniform_i64(frame_first + u + 1);
-    // the halo, as in stftmask_run_kernel, but never into the utterance before
-    const long js = j0 - ub < R - 1 ? ub : j0 - (R - 1);
-    long base = uniform_i64(sample_first + u) - ub * HOP;        // global frame j of this utterance starts at base + j HOP
+    RaggedSpan<1024 / R> span(sample_first, frame_first, a.n_utts);
+    span.begin(j0);
+    const long js = span.first(j0, R);                           // the halo, never into the utterance before
 
     WaveTwiddles tw;
     load_wave_twiddles(tw, table, lane);
@@ -458,59 +458,40 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
 
     const char *mask = static_cast<const char *>(a.mask);
     const size_t row_bytes = (size_t)a.pitch * kElem;
-    unsigned int raw[8], nraw[HR];
+    PcmHops<HR> pcm;
     MaskRow<CPX> m, nm;
-    {
-        const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + js * HOP) + lane;
-#pragma unroll
-        for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
-        mask_load(nm, mask + (size_t)js * row_bytes, lane);
-        mask_prepare(m, nm, lane);
-    }
+    pcm.load(a.pcm, span.at(js), lane);
+    mask_load(nm, mask + (size_t)js * row_bytes, lane);
+    mask_prepare(m, nm, lane);
     float m_sq = mask_energy(m, lane);
     for (long j = js; j < j1; j++) {
-        // the prefetch of stftmask_run_kernel, with the PCM's clamp inside the utterance: after its last frame the
-        // next frame's samples are another span's, read whole below.  The mask rows run on across utterances.
-        const bool last = j + 1 == ue;
-        const long jp = last ? j : j + 1;
+        // the PCM's prefetch clamps inside the utterance: after its last frame the next frame's samples are another
+        // span's, read whole below.  The mask rows run on across utterances.
+        const bool last = span.last(j);
         const long jm = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
-        {
-            const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + jp * HOP) + 64 * (8 - HR) + lane;
-#pragma unroll
-            for (int r = 0; r < HR; r++) nraw[r] = p[64 * r];
-        }
+        pcm.prefetch(a.pcm, span.at(span.next_inside(j)), lane);
         if (a.pitch) mask_load(nm, mask + (size_t)jm * row_bytes, lane);
-        if (stftmask_frame<CPX>(raw, wa, tw, pw, lds, lane, m, m_sq, ws, y)) {
-            // again, in FP64 (stftmask_run_kernel)
-            stftmask_frame_f64<CPX>(raw, a.f64, mask + (size_t)(a.pitch ? j : 0) * row_bytes, lds64, lane, y);
+        if (stftmask_frame<CPX>(pcm.raw, wa, tw, pw, lds, lane, m, m_sq, ws, y)) {
+            stftmask_frame_f64<CPX>(pcm.raw, a.f64, mask + (size_t)(a.pitch ? j : 0) * row_bytes, lds64, lane, y);
             n_redo += j >= j0;
         }
         ola.add(y, o);
-        // staged before this frame's stores (stftmask_run_kernel)
-#pragma unroll
-        for (int r = 0; r < 8 - HR; r++) raw[r] = raw[r + HR];
-#pragma unroll
-        for (int r = 0; r < HR; r++) raw[8 - HR + r] = nraw[r];
+        pcm.advance();                                           // staged before this frame's stores (frame_io.h)
         if (a.pitch) {
             mask_prepare(m, nm, lane);
             m_sq = mask_energy(m, lane);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (j >= j0) ola.emit(o, a.out, a.out_f32, base + j * HOP, lane);
+        if (j >= j0) ola.emit(o, a.out, a.out_f32, span.at(j), lane);
         ola.shift(false, nullptr, lane);
         if (last) {
             // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
             // the last frame emits the tail
-            ola.emit_tail(a.out, a.out_f32, base + (j + 1) * HOP, lane);
+            ola.emit_tail(a.out, a.out_f32, span.at(j + 1), lane);
             ola.restart();
             if (j + 1 < j1) {
-                // frame j + 1 exists, so a non-empty utterance follows
-                const long nb = ue;
-                ragged_next_utt(frame_first, a.n_utts, u, ue);
-                base = uniform_i64(sample_first + u) - nb * HOP;
-                const unsigned int *p = reinterpret_cast<const unsigned int *>(a.pcm + base + nb * HOP) + lane;
-#pragma unroll
-                for (int r = 0; r < 8; r++) raw[r] = p[64 * r];
+                span.next();                                     // frame j + 1 exists, so a non-empty utterance follows
+                pcm.load(a.pcm, span.at(j + 1), lane);
             }
         }
     }

@@ -206,6 +206,38 @@ def test_launch_geometry_bit_identical(eng, n, hop):
     ist.close()
 
 
+@pytest.mark.parametrize("n,hop,layout", [(1024, 256, "half"), (512, 128, "full")])
+def test_short_calls_at_short_runs_bit_identical(eng, n, hop, layout):
+    """Call cuts and launch geometry together: calls of 1, R - 2, R - 1 frames and the rest at runs of R - 1, R and 5
+    frames -- a call shorter than the halo, a call that ends inside a wave's halo, and the tail written by a wave other
+    than wave 0 -- against one call at the default geometry, bit for bit"""
+    import torch
+    R = n // hop
+    F = 13
+    rng = np.random.default_rng(7 * n + hop)
+    pitch = n if layout == "full" else n // 2 + 1
+    spec = torch.from_numpy(rows(rng, F, n, pitch)).cuda()
+    ist = eng.istft(n_fft=n, hop=hop, layout=layout, synthesis_window="hann", analysis_window="hann")
+    o1, f1 = ist.process(spec, want_f32=True)
+    t1, tf1 = ist.flush(want_f32=True)
+    cuts = [1, R - 2, R - 1]
+    cuts.append(F - sum(cuts))
+    for fpw in (R - 1, R, 5):
+        ist.set_option("frames_per_wave", fpw)
+        parts, fparts, j = [], [], 0
+        for c in cuts:
+            o, f = ist.process(spec[j:j + c], want_f32=True)
+            parts.append(o.clone())
+            fparts.append(f.clone())
+            j += c
+        t2, tf2 = ist.flush(want_f32=True)
+        torch.cuda.synchronize()
+        assert torch.equal(torch.cat(parts), o1), fpw
+        assert torch.equal(torch.cat(fparts).view(torch.int32), f1.view(torch.int32)), fpw
+        assert torch.equal(t2, t1) and torch.equal(tf2.view(torch.int32), tf1.view(torch.int32)), fpw
+    ist.close()
+
+
 # ---- 4. round trip through the analysis ----------------------------------------------------------------------------
 def pcm_of(rng, n, sigma=3000.0):
     return np.clip(np.rint(rng.normal(0, sigma, n)), -32768, 32767).astype(np.int16)

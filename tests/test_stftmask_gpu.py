@@ -281,6 +281,40 @@ def test_cuts_geometries_and_shards_bit_identical(eng, hop, kind):
     sm.close()
 
 
+@pytest.mark.parametrize("kind", KINDS)
+def test_short_calls_at_short_runs_bit_identical(eng, kind):
+    """Call cuts and launch geometry together at hop 256 (R = 4): calls of 1, R - 2, R - 1 frames and the rest at runs of
+    R - 1, R and 5 frames -- a call shorter than the halo, a call that ends inside a wave's halo, and the tail written by
+    a wave other than wave 0 -- against one call at the default geometry, bit for bit"""
+    import torch
+    hop = 256
+    R = N // hop
+    F = 13
+    rng = np.random.default_rng(4100 + len(kind))
+    h_pcm, h_mask = pcm_of(rng, F, hop), mask_of(rng, kind, F)
+    restate(h_pcm, h_mask, F, hop, *stream_combo(hop))             # the magnitude guard
+    pcm, mask = torch.from_numpy(h_pcm).cuda(), torch.from_numpy(h_mask).cuda()
+    sm = eng.stft_mask(**cfg_of(hop, kind, stream_combo(hop)))
+    o1, f1 = sm.process(pcm, mask, F, want_f32=True)
+    t1, tf1 = sm.flush(want_f32=True)
+    cuts = [1, R - 2, R - 1]
+    cuts.append(F - sum(cuts))
+    for fpw in (R - 1, R, 5):
+        sm.set_option("frames_per_wave", fpw)
+        parts, fparts, j = [], [], 0
+        for c in cuts:
+            o, f = sm.process(pcm[hop * j:], mask[j:j + c], c, want_f32=True)
+            parts.append(o.clone())
+            fparts.append(f.clone())
+            j += c
+        t2, tf2 = sm.flush(want_f32=True)
+        torch.cuda.synchronize()
+        assert torch.equal(torch.cat(parts), o1), fpw
+        assert torch.equal(bits(torch.cat(fparts)), bits(f1)), fpw
+        assert torch.equal(t2, t1) and torch.equal(bits(tf2), bits(tf1)), fpw
+    sm.close()
+
+
 # ---- 5. mask pitch -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("hop", HOPS)

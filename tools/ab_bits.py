@@ -1,0 +1,229 @@
+#!/usr/bin/env python3
+"""Bit comparison of builds of libjdsp.so on the overlap-add chains (GPU box only):
+    python tools/ab_bits.py build/variants/parent.so jeicyboodsp_amd/libjdsp.so ...
+Every library runs in a fresh child process (JDSP_LIB) over the same seeded inputs and prints one SHA-256 per case over
+the raw bytes of every output: int16, the float32 before the cast, the flushed tail and the recompute count where the
+entry has them.  The parent prints the table and exits non-zero when a digest differs from the first library's.
+    python tools/ab_bits.py --time ROUNDS LIB LIB ...
+times the denoiser on the periodic stream (the only chain whose FP64 recompute pass runs: no benchmark leg has it),
+the libraries alternated as named, ROUNDS times: median microseconds of 20 calls after 5."""
+import hashlib
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def digest(*arrays):
+    import numpy as np
+    import torch
+    h = hashlib.sha256()
+    for a in arrays:
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def cut_calls(F, R):
+    cuts = [1, R - 1, 7]
+    return [c for c in cuts + [F - sum(cuts)] if c >= 0]
+
+
+def geometries(R):
+    return sorted({0, max(R - 1, 1), 5})
+
+
+def synthesis(eng):
+    import numpy as np
+    import torch
+    F = 29
+    for n, hop in ((1024, 1024), (1024, 512), (1024, 256), (512, 512), (512, 256), (512, 128)):
+        for layout in ("full", "half"):
+            R = n // hop
+            rng = np.random.default_rng(n + hop + len(layout))
+            pitch = n if layout == "full" else n // 2 + 1
+            x = (rng.normal(size=(F, pitch)) + 1j * rng.normal(size=(F, pitch))) * 3000.0 * np.sqrt(n) / 2
+            spec = torch.from_numpy(x.astype(np.complex64)).cuda()
+            ist = eng.istft(n_fft=n, hop=hop, layout=layout, synthesis_window="hann",
+                            analysis_window="hann" if R > 1 else "none")
+            for fpw in geometries(R):
+                ist.set_option("frames_per_wave", fpw)
+                outs, j = [], 0
+                for c in cut_calls(F, R):
+                    o, f = ist.process(spec[j:j + c], want_f32=True)
+                    outs += [o.clone(), f.clone()]
+                    j += c
+                outs += list(ist.flush(want_f32=True))
+                yield "istft %d/%d %s fpw %d" % (n, hop, layout, fpw), digest(*outs)
+            ist.close()
+
+
+def mask_cfg(hop, kind, combo):
+    """StftMask's arguments for a (analysis, synthesis, normalise) combination, as the masking tests open it"""
+    ana, syn, norm = combo
+    return dict(n_fft=1024, hop=hop, analysis_window=ana, synthesis_window=syn, normalise=norm, mask_kind=kind)
+
+
+def mask_streams():
+    """(name, case) per hop and mask kind: the white stream and a notched tone known to recompute frames"""
+    import stftmask_fp32_ref as S
+    for c in S.cases():
+        if c["white"] or c["name"].startswith(("notch_on", "notch_off", "local")):
+            yield c
+
+
+def masking(eng):
+    import numpy as np
+    import torch
+    import stftmask_fp32_ref as S
+    seen = set()
+    for c in mask_streams():
+        tag = ("white" if c["white"] else "tone", c["hop"], c["kind"])
+        if tag in seen or c["mask_pitch"] == 0:
+            continue
+        seen.add(tag)
+        hop, F, R = c["hop"], min(29, c["F"]), S.N // c["hop"]
+        pcm, mask = torch.from_numpy(np.array(c["pcm"])).cuda(), torch.from_numpy(np.array(c["mask"])).cuda()
+        sm = eng.stft_mask(**mask_cfg(hop, c["kind"], c["combo"]))
+        for fpw in geometries(R):
+            sm.set_option("frames_per_wave", fpw)
+            outs, j, n_redo = [], 0, []
+            for k in cut_calls(F, R):
+                o, f = sm.process(pcm[hop * j:], mask[j:j + k], k, want_f32=True)
+                outs += [o.clone(), f.clone()]
+                n_redo.append(sm.frames_recomputed())
+                j += k
+            outs += list(sm.flush(want_f32=True))
+            yield "stftmask %s fpw %d (%d recomputed)" % (c["name"], fpw, sum(n_redo)), digest(*outs, np.array(n_redo))
+        sm.close()
+    # tones exist for some (hop, kind) only: say which
+    yield "stftmask streams", hashlib.sha256(repr(sorted(seen)).encode()).hexdigest()
+
+
+def batches(eng):
+    import numpy as np
+    import torch
+    import stftmask_fp32_ref as S
+    from jeicyboodsp_amd import sharding
+    for hop in (1024, 512, 256):
+        R = 1024 // hop
+        for counts in ([1, 0, R - 1, R, 2, 0, 0, 9, 1, 1, 37], [0, 0, 5, 4]):
+            counts = np.array(counts, np.int64)
+            rng = np.random.default_rng(hop + counts.size)
+            packed, frame_first = sharding.istft_batch_layout(counts, 1024, hop)
+            n_total = int(frame_first[-1])
+            pcm = torch.from_numpy(np.clip(np.rint(rng.normal(0, 3000.0, int(packed[-1]))), -32768, 32767).astype(np.int16)).cuda()
+            assert np.array_equal(sharding.stftmask_batch_layout(packed, 1024, hop)[0], counts)
+            what = "hop %d x %d utterances" % (hop, counts.size)
+            for fpw in geometries(R):
+                eng.set_option("stft.frames_per_wave", fpw)
+                spec = eng.stft_half_batch(pcm, packed, hop=hop, pitch=520)
+                yield "stft_half_batch %s fpw %d" % (what, fpw), digest(torch.view_as_real(spec)[:, :513])
+            eng.set_option("stft.frames_per_wave", 0)
+            ist = eng.istft(n_fft=1024, hop=hop, layout="half", synthesis_window="hann",
+                            analysis_window="hann" if R > 1 else "none")
+            for fpw in geometries(R):
+                ist.set_option("frames_per_wave", fpw)
+                yield "istft_batch %s fpw %d" % (what, fpw), digest(*ist.process_batch(spec, counts, packed, want_f32=True))
+            ist.close()
+            for kind in ("real", "complex"):
+                mask = torch.from_numpy(S.mask_of(rng, kind, n_total)).cuda()
+                sm = eng.stft_mask(**mask_cfg(hop, kind, S.stream_combo(hop)))
+                for fpw in geometries(R):
+                    sm.set_option("frames_per_wave", fpw)
+                    outs = sm.process_batch(pcm, mask, packed, want_f32=True)
+                    yield "stftmask_batch %s %s fpw %d" % (what, kind, fpw), digest(*outs, np.array(sm.frames_recomputed()))
+                sm.close()
+
+
+def periodic(n_fft):
+    import denoise_fp32_ref as R
+    return next(c for c in R.cases() if c["periodic"] and c["n_fft"] == n_fft)
+
+
+def denoise(eng):
+    import numpy as np
+    for n_fft in (1024, 512):
+        c = periodic(n_fft)
+        B, nb = c["block"], c["pcm"].size // c["block"]
+        d = eng.denoiser(0, n_fft, B)
+        outs, n_redo = [], []
+        for a, b in ((0, nb // 2), (nb // 2, nb)):
+            outs += list(d.process(c["pcm"][a * B:b * B], want_precast=True))
+            n_redo.append(d.frames_recomputed())
+        d.close()
+        assert sum(n_redo) > 0
+        yield "denoise %s in two calls (%d recomputed)" % (c["name"], sum(n_redo)), digest(*outs, np.array(n_redo))
+    c = periodic(1024)
+    nb = c["pcm"].size // 512
+    counts = [nb, nb - 7, nb // 2 + 3]
+    pcm = np.concatenate([c["pcm"][:k * 512] for k in counts])
+    d = eng.denoiser(0, 1024, 512)
+    outs = d.process_batch(pcm, counts, want_precast=True)
+    d.close()
+    yield "denoise_batch %s x 3 utterances" % c["name"], digest(*outs)
+
+
+def child():
+    import jeicyboodsp_amd
+    eng = jeicyboodsp_amd.Engine(0)
+    if sys.argv[2:3] == ["time"]:
+        import statistics
+        import time
+        import numpy as np
+        import torch
+        c = periodic(1024)
+        pcm = torch.from_numpy(np.array(c["pcm"])).cuda()
+        d = eng.denoiser(0, 1024, 512)
+        t = []
+        for i in range(25):
+            d.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            d.process(pcm)
+            torch.cuda.synchronize()
+            t.append((time.perf_counter() - t0) * 1e6)
+        print("%s\t%.1f" % (c["name"], statistics.median(t[5:])))
+        d.close()
+    else:
+        for chain in (synthesis, masking, batches, denoise):
+            for name, sha in chain(eng):
+                print("%s\t%s" % (name, sha), flush=True)
+    eng.close()
+
+
+def run_child(lib, *args):
+    env = dict(os.environ, JDSP_LIB=os.path.abspath(lib))
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + list(args), env=env, check=True,
+                         stdout=subprocess.PIPE, text=True, timeout=600).stdout
+    return [line.split("\t") for line in out.splitlines() if "\t" in line]
+
+
+def main():
+    if sys.argv[1] == "--child":
+        return child()
+    if sys.argv[1] == "--time":
+        for r in range(int(sys.argv[2])):
+            for lib in sys.argv[3:]:
+                for name, us in run_child(lib, "time"):
+                    print("round %d  %-40s %-24s %9s us" % (r, lib, name, us), flush=True)
+        return 0
+    libs = sys.argv[1:]
+    tables = [run_child(lib) for lib in libs]
+    assert all(len(t) == len(tables[0]) for t in tables), [len(t) for t in tables]
+    bad = 0
+    for rows in zip(*tables):
+        names, shas = {r[0] for r in rows}, [r[1] for r in rows]
+        same = len(names) == 1 and len(set(shas)) == 1
+        bad += not same
+        print("%-64s %s  %s" % (rows[0][0], "  ".join(s[:16] for s in shas), "equal" if same else "DIFFER"))
+    print("%d cases, %d libraries: %s" % (len(tables[0]), len(libs), "FAIL: %d differ" % bad if bad else "all equal"))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
