@@ -46,7 +46,8 @@ extern "C" {
  *    jdsp_geq_* and NLMS filter jdsp_nlms_* added; the fused STFT masking entries jdsp_stftmask_* added;
  *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added; the ragged-batch
  *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added;
- *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added
+ *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
+ *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -259,6 +260,25 @@ int  jdsp_istft_batch_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitc
 int  jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, const int64_t *sample_first_host,
                       const int64_t *frame_first_host, long n_utts, long n_samples, int16_t *out_i16_host,
                       float *out_f32_host);                                               /* host path, synchronous */
+/* LIVE STREAMS on the synthesis handle: the six entries of jdsp_stftmask_streams_* (below, where the vocabulary and
+ * the rules are written out) with spec_dev, row_pitch where those have pcm_dev, mask_dev, mask_pitch.  Chunk c of
+ * stream stream_id[c] is the F_c spectrum rows frame_first[c] .. frame_first[c + 1] - 1; there is no PCM, so its span
+ * is its hop F_c output samples, written at out[sample_first[c] .. + hop F_c).  Stream s's chunks in call order
+ * followed by its _streams_flush equal a fresh handle's _process of all those rows, then _flush, bit for bit (int16
+ * and float32, every "frames_per_wave", every order of chunks, every cut).  Every configuration create accepts. */
+int  jdsp_istft_streams_reserve(jdsp_istft *h, long n_streams);
+int  jdsp_istft_streams_reset_dev(jdsp_istft *h, const int64_t *stream_id_dev, long n_ids);        /* NULL: all */
+int  jdsp_istft_streams_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitch, const int64_t *stream_id_dev,
+                            const int64_t *sample_first_dev, const int64_t *frame_first_dev, long n_chunks,
+                            long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_istft_streams_flush_dev(jdsp_istft *h, const int64_t *stream_id_dev, const int64_t *sample_first_dev,
+                                  long n_ids, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_istft_streams(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, const int64_t *stream_id_host,
+                        const int64_t *sample_first_host, const int64_t *frame_first_host, long n_chunks,
+                        long n_samples, int16_t *out_i16_host, float *out_f32_host);      /* host path, synchronous */
+int  jdsp_istft_streams_flush(jdsp_istft *h, const int64_t *stream_id_host, const int64_t *sample_first_host,
+                              long n_ids, long n_samples, int16_t *out_i16_host,
+                              float *out_f32_host);                                       /* host path, synchronous */
 
 /* ---- fused STFT masking: PCM -> analysis -> per-bin mask -> synthesis -> PCM ------- */
 /* jdsp_stft_* followed by a multiplication of the spectrum and jdsp_istft_*, as ONE pass in which the spectrum never
@@ -347,6 +367,61 @@ int  jdsp_stftmask_batch_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const voi
 int  jdsp_stftmask_batch(jdsp_stftmask *h, const int16_t *pcm_host, long n_samples, const void *mask_host,
                          long mask_pitch, const int64_t *sample_first_host, const int64_t *frame_first_host,
                          long n_utts, int16_t *out_i16_host, float *out_f32_host);        /* host path, synchronous */
+/* LIVE STREAMS: n_streams independent output streams in the handle, next to its own one, whose overlap-add tails are
+ * carried from call to call; one call advances any subset of them by a ragged number of frames each, in ONE transform
+ * launch (plus one O(n_chunks) bookkeeping launch).  A CHUNK is what one live stream contributes to one call: chunk c
+ * has its stream stream_id[c], F_c = frame_first[c + 1] - frame_first[c] frames (>= 0) and its first sample
+ * sample_first[c].  The concatenated frame axis, the mask rows and the two offset arrays are those of
+ * jdsp_stftmask_batch_dev with chunks where that has utterances; stream_id (int64, [n_chunks], 8-byte aligned) is new.
+ *   - _streams_reserve is the only call that allocates, and it synchronises: the handle gets n_streams >= 1 live
+ *     streams, all fresh; calling it again discards every live stream's state.  Before it the other five entries
+ *     return JDSP_EINVAL with a text.  The state is the tail, n - hop floats per stream, held twice with one word per
+ *     stream that says which copy is current: within a launch the waves that read a stream's carried tail and the
+ *     wave that writes its new one never touch the same memory, and the word lives on the device.
+ *   - _streams_dev, inputs of chunk c: frame f is pcm[sample_first[c] + hop f .. + n), its mask row is row
+ *     frame_first[c] + f (mask_pitch 0: one row for everything).  As on _process_dev the caller presents the overlap
+ *     again -- the handle keeps no PCM: the chunk's PCM span is hop (F_c - 1) + n samples and begins with the last
+ *     n - hop samples of the stream's previous chunk.
+ *   - _streams_dev, output of chunk c: hop F_c samples at out[sample_first[c] .. + hop F_c), the first hop F_c samples
+ *     of its own PCM span, so one set of offsets serves input and output.  The remaining n - hop samples of the span
+ *     are not written; nothing outside the spans is written or read.
+ *   - Equivalence: the outputs of stream s's chunks in call order, followed by its _streams_flush, equal what a fresh
+ *     single-stream handle of the same configuration gives for _process of all those frames, then _flush -- bit for
+ *     bit, in int16 and float32, for every "frames_per_wave", every order of chunks within a call and every way the
+ *     frames are cut into chunks and calls.  A stream with no chunk in a call, or with a chunk of 0 frames, keeps its
+ *     state untouched.  jdsp_stftmask_frames_recomputed reports a _streams call like any other.
+ *   - The handle's own stream (_process / _flush) and the stateless _batch entries are neither read nor written by any
+ *     of this and may be interleaved with it on the same handle.
+ *   - The caller's contract on the device: stream ids in [0, n_streams) and distinct within a call; n_chunks <=
+ *     n_streams (a scalar: checked by the device entry too); frame_first[0] = 0, non-decreasing, frame_first[n_chunks]
+ *     = n_frames_total; sample_first even; the spans disjoint and inside the buffers.  The host entries check all of
+ *     it (sample_first ascending, as jdsp_stftmask_batch) and return JDSP_EINVAL with a jdsp_last_error text, every
+ *     stream left as it was.  Alignments are those of the batch entries.  n_chunks == 0, n_frames_total == 0 and both
+ *     outputs NULL behave as in the batch entries: they launch nothing and change no state.
+ *   - _streams_flush_dev writes, for each of the n_ids listed streams, the n - hop tail samples at
+ *     out[sample_first[i] .. + n - hop), g[t mod hop] * s[t] with the same cast, and then resets those streams (with
+ *     both outputs NULL it only resets them).  _streams_reset_dev zeroes the listed streams, or all when stream_id_dev
+ *     is NULL (n_ids is then ignored).  Ids are distinct and in range, as above.
+ *   - Every _dev entry only enqueues on the stream _process_dev uses: no allocation, no host synchronisation, no host
+ *     read of the arrays, and nothing baked into a launch that would make a replayed capture wrong.
+ *   - jdsp_stftmask_streams / _streams_flush: host pointers, synchronous, check everything; pcm and the outputs are
+ *     n_samples long and the outputs ZERO outside the written ranges.  For the flush the spans are the n - hop
+ *     samples at each sample_first[i] (even, ascending, disjoint, inside n_samples). */
+int  jdsp_stftmask_streams_reserve(jdsp_stftmask *h, long n_streams);
+int  jdsp_stftmask_streams_reset_dev(jdsp_stftmask *h, const int64_t *stream_id_dev, long n_ids);  /* NULL: all */
+int  jdsp_stftmask_streams_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void *mask_dev, long mask_pitch,
+                               const int64_t *stream_id_dev, const int64_t *sample_first_dev,
+                               const int64_t *frame_first_dev, long n_chunks, long n_frames_total,
+                               int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_stftmask_streams_flush_dev(jdsp_stftmask *h, const int64_t *stream_id_dev, const int64_t *sample_first_dev,
+                                     long n_ids, int16_t *out_i16_dev, float *out_f32_dev);
+int  jdsp_stftmask_streams(jdsp_stftmask *h, const int16_t *pcm_host, long n_samples, const void *mask_host,
+                           long mask_pitch, const int64_t *stream_id_host, const int64_t *sample_first_host,
+                           const int64_t *frame_first_host, long n_chunks, int16_t *out_i16_host,
+                           float *out_f32_host);                                          /* host path, synchronous */
+int  jdsp_stftmask_streams_flush(jdsp_stftmask *h, const int64_t *stream_id_host, const int64_t *sample_first_host,
+                                 long n_ids, long n_samples, int16_t *out_i16_host,
+                                 float *out_f32_host);                                    /* host path, synchronous */
 
 /* ---- spectral subtraction / Wiener filter ------------------------------------- */
 /* One jdsp_denoise object holds everything the reference keeps in static locals

@@ -179,6 +179,12 @@ def _load():
         "jdsp_istft_flush": (i, [vp, vp, vp]),
         "jdsp_istft_batch_dev": (i, [vp, vp, l, vp, vp, l, l, vp, vp]),
         "jdsp_istft_batch": (i, [vp, vp, l, vp, vp, l, l, vp, vp]),
+        "jdsp_istft_streams_reserve": (i, [vp, l]),
+        "jdsp_istft_streams_reset_dev": (i, [vp, vp, l]),
+        "jdsp_istft_streams_dev": (i, [vp, vp, l, vp, vp, vp, l, l, vp, vp]),
+        "jdsp_istft_streams_flush_dev": (i, [vp, vp, vp, l, vp, vp]),
+        "jdsp_istft_streams": (i, [vp, vp, l, vp, vp, vp, l, l, vp, vp]),
+        "jdsp_istft_streams_flush": (i, [vp, vp, vp, l, l, vp, vp]),
         "jdsp_stftmask_create": (i, [vp, vp, C.POINTER(vp)]),
         "jdsp_stftmask_destroy": (i, [vp]),
         "jdsp_stftmask_reset": (i, [vp]),
@@ -191,6 +197,12 @@ def _load():
         "jdsp_stftmask_flush": (i, [vp, vp, vp]),
         "jdsp_stftmask_batch_dev": (i, [vp, vp, vp, l, vp, vp, l, l, vp, vp]),
         "jdsp_stftmask_batch": (i, [vp, vp, l, vp, l, vp, vp, l, vp, vp]),
+        "jdsp_stftmask_streams_reserve": (i, [vp, l]),
+        "jdsp_stftmask_streams_reset_dev": (i, [vp, vp, l]),
+        "jdsp_stftmask_streams_dev": (i, [vp, vp, vp, l, vp, vp, vp, l, l, vp, vp]),
+        "jdsp_stftmask_streams_flush_dev": (i, [vp, vp, vp, l, vp, vp]),
+        "jdsp_stftmask_streams": (i, [vp, vp, l, vp, l, vp, vp, vp, l, vp, vp]),
+        "jdsp_stftmask_streams_flush": (i, [vp, vp, vp, l, l, vp, vp]),
         "jdsp_gmm_train_create": (i, [vp, i, C.POINTER(vp)]),
         "jdsp_gmm_train_destroy": (i, [vp]),
         "jdsp_gmm_train_reset": (i, [vp]),

@@ -10,6 +10,7 @@ struct jdsp_istft {
     jdsp::DevBuf<float> blob;             // ws[n_fft] (w_s / n_fft), then the stream's share
     float *ws = nullptr;                  // view into blob
     OlaStream ola;
+    jdsp::OlaStreams live;                // the live streams (jdsp_istft_streams_*), none until _streams_reserve
     jdsp::DevBuf<jdsp_c32> h_spec;        // the host entry's device copy of the spectra, grown on demand
 };
 
@@ -46,6 +47,7 @@ int jdsp_istft_create(jdsp_ctx *ctx, const jdsp_istft_cfg *cfg, jdsp_istft **out
     if (e == hipSuccess) {
         h->ws = h->blob.get();
         h->ola.attach(ctx, n, hop, h->ws + n);
+        h->live.ola = &h->ola;
         e = hipMemcpy(h->ws, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
@@ -201,6 +203,103 @@ int jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, c
                                        d_f32));
     h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
     return hc.finish();
+}
+
+// ---- live streams ---------------------------------------------------------------------------------------------------
+
+int jdsp_istft_streams_reserve(jdsp_istft *h, long n_streams)
+{
+    return h ? h->live.reserve("jdsp_istft_streams_reserve", n_streams) : JDSP_EINVAL;
+}
+
+int jdsp_istft_streams_reset_dev(jdsp_istft *h, const int64_t *stream_id_dev, long n_ids)
+{
+    return h ? h->live.reset_dev("jdsp_istft_streams_reset", stream_id_dev, n_ids) : JDSP_EINVAL;
+}
+
+int jdsp_istft_streams_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitch, const int64_t *stream_id_dev,
+                           const int64_t *sample_first_dev, const int64_t *frame_first_dev, long n_chunks,
+                           long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    if (int rc = h->live.check_count("jdsp_istft_streams", n_chunks)) return rc;
+    if (n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: n_frames_total < 0");
+    if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: row_pitch below the layout's bins");
+    if (!jdsp::aligned(spec_dev, 8) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
+        !jdsp::aligned(stream_id_dev, 8) || !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(frame_first_dev, 8))
+        return fail(ctx, JDSP_EINVAL,
+                    "jdsp_istft_streams: spec, out_f32, the stream ids and the offset arrays must be 8-byte, out_i16 "
+                    "4-byte aligned");
+    if (n_chunks == 0 || n_frames_total == 0) return JDSP_OK;
+    if (!spec_dev || !stream_id_dev || !sample_first_dev || !frame_first_dev)
+        return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: spec, stream_id, sample_first or frame_first is NULL");
+    if (!out_i16_dev && !out_f32_dev) return JDSP_OK;          // as the batch entry: nothing is done, no stream advances
+    if (jdsp::launch_istft_live(ctx->stream, ctx->n_cu, h->cfg.n_fft, h->cfg.hop, h->cfg.layout == JDSP_SPEC_HALF,
+                                reinterpret_cast<const float2 *>(spec_dev), row_pitch, n_frames_total,
+                                reinterpret_cast<const long long *>(sample_first_dev),
+                                reinterpret_cast<const long long *>(frame_first_dev), n_chunks, h->live.view(stream_id_dev),
+                                h->ws, h->ola.g, out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt))
+        return fail(ctx, JDSP_EHIP, "jdsp_istft_streams: launch", hipGetLastError());
+    return h->live.commit("jdsp_istft_streams", stream_id_dev, frame_first_dev, n_chunks);
+}
+
+int jdsp_istft_streams_flush_dev(jdsp_istft *h, const int64_t *stream_id_dev, const int64_t *sample_first_dev, long n_ids,
+                                 int16_t *out_i16_dev, float *out_f32_dev)
+{
+    return h ? h->live.flush_dev("jdsp_istft_streams_flush", stream_id_dev, sample_first_dev, n_ids, out_i16_dev, out_f32_dev)
+             : JDSP_EINVAL;
+}
+
+int jdsp_istft_streams(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, const int64_t *stream_id_host,
+                       const int64_t *sample_first_host, const int64_t *frame_first_host, long n_chunks, long n_samples,
+                       int16_t *out_i16_host, float *out_f32_host)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    if (int rc = h->live.check_count("jdsp_istft_streams", n_chunks)) return rc;
+    if (n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: n_samples < 0");
+    if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: row_pitch below the layout's bins");
+    if (n_chunks > 0 && (!stream_id_host || !sample_first_host || !frame_first_host))
+        return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: stream_id, sample_first or frame_first is NULL");
+    if (int rc = h->live.check_ids("jdsp_istft_streams", stream_id_host, n_chunks)) return rc;
+    jdsp::RaggedOffsets offs;                                  // a chunk's span is its hop F_c output samples
+    if (offs.check(ctx, "jdsp_istft_streams", "frame_first", sample_first_host, frame_first_host, n_chunks, n_samples,
+                   h->cfg.hop, h->cfg.hop))
+        return JDSP_EINVAL;
+    const long n_total = offs.lay.n_total;
+    if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
+        if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
+        if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
+        return JDSP_OK;
+    }
+    if (!spec_host) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: spec is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n_in = (size_t)(n_total - 1) * row_pitch + bins_of(h->cfg);
+    int16_t *d_i16 = nullptr;
+    float *d_f32 = nullptr;
+    hipError_t e = h->h_spec.grow(n_in);
+    if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
+    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_istft_streams: buffers", e);
+    jdsp::HostCall hc(ctx, "jdsp_istft_streams");
+    offs.upload(hc);
+    const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_chunks * sizeof(int64_t));
+    hc.upload_to(h->h_spec.get(), spec_host, n_in * sizeof(jdsp_c32));
+    if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the written ranges
+    if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
+    if (hc.ok())
+        hc.result(jdsp_istft_streams_dev(h, h->h_spec.get(), row_pitch, d_id, offs.d_sample, offs.d_unit, n_chunks, n_total,
+                                         d_i16, d_f32));
+    h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
+    return hc.finish();
+}
+
+int jdsp_istft_streams_flush(jdsp_istft *h, const int64_t *stream_id_host, const int64_t *sample_first_host, long n_ids,
+                             long n_samples, int16_t *out_i16_host, float *out_f32_host)
+{
+    return h ? h->live.flush("jdsp_istft_streams_flush", stream_id_host, sample_first_host, n_ids, n_samples, out_i16_host,
+                             out_f32_host)
+             : JDSP_EINVAL;
 }
 
 }  // extern "C"

@@ -9,10 +9,12 @@
 //             through the same image), so a non-Hermitian row gives exactly the real part of its full inverse.
 //   n = 512   one 512-point complex inverse of H per frame, real part kept.  Never two frames in one transform: a
 //             frame's result must not depend on its neighbour, or on where a call or shard cut falls.
-// istft_run_kernel (one stream) and istft_batch_kernel (a batch of ragged utterances) are one body, istft_run, over the
-// two forms of ragged_batch.h's span walk.  They share the setup, the frame, the staging and the loop's tail; two things
-// stay forked at compile time, both for speed: the stream's halo runs unrolled in front of the loop where the batch's
-// goes through it with emission off, and the stream skips the row prefetch on its run's last frame.
+// istft_run_kernel (one stream), istft_batch_kernel (a batch of ragged utterances) and istft_live_kernel (the chunks of
+// live streams, whose tails the handle carries) are one body, istft_run, over the three forms of ragged_batch.h's span
+// walk.  They share the setup, the frame, the staging and the loop's tail; two things stay forked at compile time
+// between the stream and the other two, both for speed: the stream's halo runs unrolled in front of the loop where the
+// batch's goes through it with emission off, and the stream skips the row prefetch on its run's last frame.  The live
+// form is the batch's with a tail loaded where a chunk starts and stored where it ends.
 #include "jdsp_internal.h"
 #include "ola_stream.h"
 #include "ragged_batch.h"
@@ -176,6 +178,10 @@ __device__ __forceinline__ void istft_run(const IstftArgs &a, const float2 *__re
     long js = j0;
     if constexpr (Span::kBatch) {
         js = span.first(j0, R);
+        // live streams: a halo that stops at the chunk's first frame starts from the stream's carried tail
+        if constexpr (Span::kLive) {
+            if (span.starts_span(js)) ola.load_tail(span.tail_in(), lane);
+        }
     } else if (j0 == 0) {
         ola.load_tail(a.tail_in, lane);
     } else {
@@ -208,13 +214,23 @@ __device__ __forceinline__ void istft_run(const IstftArgs &a, const float2 *__re
         __builtin_amdgcn_sched_barrier(0);
         if (!Span::kBatch || j >= j0) ola.emit(o, a.out, a.out_f32, span.at(j), lane);
         const bool last = span.last(j);
-        ola.shift(!Span::kBatch && last, a.tail_out, lane);
-        if (Span::kBatch && last) {
-            // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
-            // the last frame emits the tail
-            ola.emit_tail(a.out, a.out_f32, span.at(j + 1), lane);
-            ola.restart();
-            if (j + 1 < j1) span.next();                         // frame j + 1 exists, so a non-empty utterance follows
+        if constexpr (Span::kLive) {
+            // a chunk's last frame leaves the stream's new tail in memory (the other of its two, ragged_batch.h), and
+            // the chunk that follows in the run starts from its own stream's
+            ola.shift(last, span.tail_out(), lane);
+            if (last && j + 1 < j1) {
+                span.next();
+                ola.load_tail(span.tail_in(), lane);
+            }
+        } else {
+            ola.shift(!Span::kBatch && last, a.tail_out, lane);
+            if (Span::kBatch && last) {
+                // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
+                // the last frame emits the tail
+                ola.emit_tail(a.out, a.out_f32, span.at(j + 1), lane);
+                ola.restart();
+                if (j + 1 < j1) span.next();                     // frame j + 1 exists, so a non-empty utterance follows
+            }
         }
         wave_lds_fence();                                        // the staged row before the next frame reads it
     }
@@ -234,6 +250,46 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_batch_kernel(
     istft_run<N, HALF, R>(a, table, RaggedSpan<N / R>(sample_first, frame_first, a.n_utts));
 }
 
+// the chunks of live streams (jdsp_istft_streams_*): the batch's walk with tails carried in the handle
+template <int N, int HALF, int R>
+__global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_live_kernel(
+    IstftBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
+    const long long *__restrict__ frame_first, const long long *__restrict__ stream_id, const int *__restrict__ parity,
+    LiveStreams live)
+{
+    istft_run<N, HALF, R>(a, table, LiveSpan<N / R>(sample_first, frame_first, a.n_utts, stream_id, parity, live));
+}
+
+// ---- the state of live streams (jdsp::OlaStreams; the layout: LiveStreams, ragged_batch.h) ------------------------
+// flush of the listed streams: one workgroup per stream writes its n_tail samples, g[t mod hop] * s[t] and the same
+// cast, at sample_first[i] onwards and zeroes the tail behind it -- the stream is fresh again, its parity as it is.
+// Both outputs NULL: the reset of the listed streams.
+__global__ __launch_bounds__(256) void ola_streams_flush_kernel(LiveStreams live, const long long *__restrict__ sample_first,
+                                                                const float *__restrict__ g, int hop,
+                                                                short *__restrict__ out, float *__restrict__ out_f32)
+{
+    const long s = uniform_i64(live.stream_id + blockIdx.x);
+    const int p = __builtin_amdgcn_readfirstlane(live.parity[s]) & 1;
+    float *tail = live.tails + ((long)p * live.n_streams + s) * live.n_tail;
+    const long at = out || out_f32 ? uniform_i64(sample_first + blockIdx.x) : 0;
+    for (int i = threadIdx.x; i < live.n_tail; i += blockDim.x) {
+        const float o = g[i % hop] * tail[i];
+        if (out) out[at + i] = (short)cast_i16_bits(o);
+        if (out_f32) out_f32[at + i] = o;
+        tail[i] = 0.0f;
+    }
+}
+
+// after a launch over chunks: the streams that were given frames start their next chunk from the tail it wrote
+__global__ __launch_bounds__(256) void ola_streams_commit_kernel(const long long *__restrict__ stream_id,
+                                                                 const long long *__restrict__ frame_first, long n_chunks,
+                                                                 int *__restrict__ parity)
+{
+    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_chunks) return;
+    if (frame_first[c + 1] > frame_first[c]) parity[stream_id[c]] ^= 1;    // ids are distinct within a call
+}
+
 // flush: the n - hop samples still in the tail, g[t mod hop] * s[t], then the same cast
 __global__ __launch_bounds__(256) void istft_flush_kernel(const float *__restrict__ tail, const float *__restrict__ g,
                                                           int n_tail, int hop, short *__restrict__ out,
@@ -246,12 +302,15 @@ __global__ __launch_bounds__(256) void istft_flush_kernel(const float *__restric
     if (out_f32) out_f32[i] = o;
 }
 
-// sample_first == NULL: a single stream
+// sample_first == NULL: a single stream; live != NULL: the chunks of live streams
 template <int N, int HALF, int R>
 static void launch_one(hipStream_t s, long grid, const IstftArgs &a, const float2 *table, const long long *sample_first,
-                       const long long *frame_first)
+                       const long long *frame_first, const LiveStreams *live)
 {
-    if (sample_first)
+    if (live)
+        hipLaunchKernelGGL((istft_live_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, IstftBatchArgs{a}, table,
+                           sample_first, frame_first, live->stream_id, live->parity, *live);
+    else if (sample_first)
         hipLaunchKernelGGL((istft_batch_kernel<N, HALF, R>), dim3((unsigned)grid), dim3(64), 0, s, IstftBatchArgs{a}, table,
                            sample_first, frame_first);
     else
@@ -260,25 +319,26 @@ static void launch_one(hipStream_t s, long grid, const IstftArgs &a, const float
 
 template <int N, int HALF>
 static void launch_r(hipStream_t s, int r, long grid, const IstftArgs &a, const float2 *table,
-                     const long long *sample_first, const long long *frame_first)
+                     const long long *sample_first, const long long *frame_first, const LiveStreams *live)
 {
-    if (r == 1) launch_one<N, HALF, 1>(s, grid, a, table, sample_first, frame_first);
-    else if (r == 2) launch_one<N, HALF, 2>(s, grid, a, table, sample_first, frame_first);
-    else launch_one<N, HALF, 4>(s, grid, a, table, sample_first, frame_first);
+    if (r == 1) launch_one<N, HALF, 1>(s, grid, a, table, sample_first, frame_first, live);
+    else if (r == 2) launch_one<N, HALF, 2>(s, grid, a, table, sample_first, frame_first, live);
+    else launch_one<N, HALF, 4>(s, grid, a, table, sample_first, frame_first, live);
 }
 
 static int launch_any(hipStream_t s, int n_cu, int n_fft, int hop, int half, IstftArgs a, const float2 *table,
-                      int run_opt, const long long *sample_first, const long long *frame_first)
+                      int run_opt, const long long *sample_first, const long long *frame_first,
+                      const LiveStreams *live = nullptr)
 {
     const int r = n_fft / hop;
     const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, a.n_frames, run_opt);
     a.run = (int)p.run;
     if (n_fft == 1024) {
-        if (half) launch_r<1024, 1>(s, r, p.grid, a, table, sample_first, frame_first);
-        else launch_r<1024, 0>(s, r, p.grid, a, table, sample_first, frame_first);
+        if (half) launch_r<1024, 1>(s, r, p.grid, a, table, sample_first, frame_first, live);
+        else launch_r<1024, 0>(s, r, p.grid, a, table, sample_first, frame_first, live);
     } else {
-        if (half) launch_r<512, 1>(s, r, p.grid, a, table, sample_first, frame_first);
-        else launch_r<512, 0>(s, r, p.grid, a, table, sample_first, frame_first);
+        if (half) launch_r<512, 1>(s, r, p.grid, a, table, sample_first, frame_first, live);
+        else launch_r<512, 0>(s, r, p.grid, a, table, sample_first, frame_first, live);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -307,6 +367,34 @@ int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, co
     if (n_frames_total <= 0 || n_utts <= 0) return 0;
     const IstftArgs a = {spec, pitch, n_frames_total, n_utts, ws, g, out, out_f32, 0, nullptr, nullptr};
     return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, sample_first, frame_first);
+}
+
+int launch_istft_live(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
+                      long n_frames_total, const long long *sample_first, const long long *frame_first, long n_chunks,
+                      const LiveStreams &live, const float *ws, const float *g, short *out, float *out_f32,
+                      const float2 *table, int run_opt)
+{
+    if (n_frames_total <= 0 || n_chunks <= 0) return 0;
+    const IstftArgs a = {spec, pitch, n_frames_total, n_chunks, ws, g, out, out_f32, 0, nullptr, nullptr};
+    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, sample_first, frame_first, &live);
+}
+
+int launch_ola_streams_flush(hipStream_t s, const LiveStreams &live, long n_ids, const long long *sample_first,
+                             const float *g, int hop, short *out, float *out_f32)
+{
+    if (n_ids <= 0 || live.n_tail <= 0) return 0;
+    hipLaunchKernelGGL(ola_streams_flush_kernel, dim3((unsigned)n_ids), dim3(256), 0, s, live, sample_first, g, hop, out,
+                       out_f32);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_ola_streams_commit(hipStream_t s, const long long *stream_id, const long long *frame_first, long n_chunks,
+                              int *parity)
+{
+    if (n_chunks <= 0) return 0;
+    hipLaunchKernelGGL(ola_streams_commit_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, stream_id,
+                       frame_first, n_chunks, parity);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }  // namespace jdsp

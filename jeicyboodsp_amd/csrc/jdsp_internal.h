@@ -471,6 +471,43 @@ int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_t
 int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
                        long n_frames_total, const long long *sample_first, const long long *frame_first, long n_utts,
                        const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt);
+// The live streams of a handle as a kernel sees them (the host side: OlaStreams below).  Stream s keeps two tails of
+// n_tail = n - hop floats, tails[(p n_streams + s) n_tail ..) for p = 0, 1, and the word parity[s] says which of them
+// holds the partial sums the stream's next chunk starts from.  A transform launch only READS parity: every wave of it
+// sees the same value, loads from tail p and stores to tail p ^ 1, so the waves that read a chunk's carried tail (all
+// whose halo starts at the chunk's first frame) and the one wave that writes its new tail (the owner of its last
+// frame) never touch the same memory, whatever order they run in.  launch_ola_streams_commit, enqueued behind the
+// launch, flips parity[s] for the streams that were given frames.  Nothing of it is host state, so a captured launch
+// replays correctly, and a stream without a chunk in a call is not touched at all.  (A word, not a byte: gfx950 has no
+// scalar byte load.  The live kernels take stream_id and parity a second time as __restrict__ arguments of their own:
+// through this struct the compiler cannot tell them from the tails the kernel stores to, and fetched both with vector
+// loads and v_readfirstlane at every chunk boundary inside a run: profiles/r18_ola_live_streams_isa.txt.)
+struct LiveStreams {
+    const long long *stream_id;   // [n_chunks] the stream of chunk c; distinct within a call, in [0, n_streams)
+    const int *parity;            // [n_streams] 0 | 1
+    float *tails;                 // [2][n_streams][n_tail]
+    long n_streams;
+    int n_tail;
+};
+// the chunks of live streams in one launch: launch_istft_batch's layout with chunks for utterances; chunk c starts from
+// the tail of stream live.stream_id[c], writes its hop F_c samples and leaves the new tail in the stream's other buffer
+int launch_istft_live(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
+                      long n_frames_total, const long long *sample_first, const long long *frame_first, long n_chunks,
+                      const LiveStreams &live, const float *ws, const float *g, short *out, float *out_f32,
+                      const float2 *table, int run_opt);
+// the n_tail samples of the n_ids listed streams (live.stream_id) to sample_first[i] onwards, their tails zeroed behind
+// them; out and out_f32 both NULL (sample_first is then not read): the reset of those streams
+int launch_ola_streams_flush(hipStream_t s, const LiveStreams &live, long n_ids, const long long *sample_first,
+                             const float *g, int hop, short *out, float *out_f32);
+// parity[stream_id[c]] ^= 1 for the chunks with frames
+int launch_ola_streams_commit(hipStream_t s, const long long *stream_id, const long long *frame_first, long n_chunks,
+                              int *parity);
+// as launch_stftmask_batch, over chunks of live streams (launch_istft_live)
+int launch_stftmask_live(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
+                         long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
+                         long n_chunks, const LiveStreams &live, const float *wa, const float *ws, const float *g,
+                         short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
+                         unsigned int *count, unsigned int epoch);
 // stftmask_kernels.hip (n_fft 1024)
 // mask: rows of float or float2 (complex_mask), pitch elements apart (0: one row); wa: [1024] analysis window / 2;
 // ws: [1024] synthesis window; g: [hop] emission gain; tails: [1024 - hop] floats; run_opt 0 = auto.  For the frames
@@ -618,6 +655,142 @@ struct OlaStream {
         HostCall hc(ctx, entry);
         hc.result(flush_dev(entry, d_i16, d_f32));
         download_out(hc, n_tail, out_i16_host, out_f32_host);
+        return hc.finish();
+    }
+};
+
+// The live streams of a jdsp_istft or jdsp_stftmask handle (jdsp_*_streams_*), next to its own OlaStream: n_streams
+// tails carried from call to call, of which one call advances any subset by a chunk of frames each in one launch
+// (LiveStreams above, LiveSpan in ragged_batch.h).  Nothing here is read or written by the handle's own stream or by
+// the stateless batch entries.  `entry` is the calling entry's name, the prefix of its messages.
+struct OlaStreams {
+    OlaStream *ola = nullptr;             // the handle's own: the context, n, hop, the gain and the output staging
+    long n_streams = 0;                   // 0: not reserved
+    DevBuf<float> tails;                  // [2][n_streams][n - hop]
+    DevBuf<int> parity;                   // [n_streams]
+
+    int n_tail() const { return ola->n - ola->hop; }
+    LiveStreams view(const int64_t *stream_id_dev) const
+    {
+        return {reinterpret_cast<const long long *>(stream_id_dev), parity.get(), tails.get(), n_streams, n_tail()};
+    }
+    int closed(const char *entry) const
+    {
+        return fail(ola->ctx, JDSP_EINVAL, (std::string(entry) + ": no live streams (call _streams_reserve first)").c_str());
+    }
+    // the only call that allocates; every stream is fresh afterwards
+    int reserve(const char *entry, long n)
+    {
+        jdsp_ctx *ctx = ola->ctx;
+        const std::string e(entry);
+        if (n < 1) return fail(ctx, JDSP_EINVAL, (e + ": n_streams must be >= 1").c_str());
+        JDSP_HIP(ctx, hipSetDevice(ctx->device));
+        JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // nothing enqueued still uses the old buffers
+        n_streams = 0;
+        const size_t n_floats = 2 * (size_t)n * (size_t)n_tail();
+        hipError_t err = tails.alloc(n_floats ? n_floats : 1);
+        if (err == hipSuccess) err = parity.alloc((size_t)n);
+        if (err == hipSuccess) err = hipMemsetAsync(tails.get(), 0, tails.count() * sizeof(float), ctx->stream);
+        if (err == hipSuccess) err = hipMemsetAsync(parity.get(), 0, (size_t)n * sizeof(int), ctx->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+        if (err != hipSuccess) {
+            tails.reset();
+            parity.reset();
+            return fail(ctx, err == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, (e + ": buffers").c_str(), err);
+        }
+        n_streams = n;
+        return JDSP_OK;
+    }
+    // the checks every entry over a list of ids makes before anything else: reserved, 0 <= n_ids <= n_streams
+    int check_count(const char *entry, long n_ids) const
+    {
+        if (!n_streams) return closed(entry);
+        const std::string e(entry);
+        if (n_ids < 0) return fail(ola->ctx, JDSP_EINVAL, (e + ": a count is < 0").c_str());
+        if (n_ids > n_streams)
+            return fail(ola->ctx, JDSP_EINVAL, (e + ": more ids than live streams (ids are distinct within a call)").c_str());
+        return JDSP_OK;
+    }
+    // host arrays only: every id in range, none twice
+    int check_ids(const char *entry, const int64_t *stream_id_host, long n_ids) const
+    {
+        const StreamIdVerdict v = stream_ids_check(stream_id_host, n_ids, n_streams);
+        return v == StreamIdVerdict::kOk ? JDSP_OK : fail(ola->ctx, JDSP_EINVAL, stream_ids_message(v, entry).c_str());
+    }
+    // the listed streams fresh again; stream_id_dev NULL: all of them
+    int reset_dev(const char *entry, const int64_t *stream_id_dev, long n_ids)
+    {
+        jdsp_ctx *ctx = ola->ctx;
+        if (!n_streams) return closed(entry);
+        const std::string e(entry);
+        if (!stream_id_dev) {
+            JDSP_HIP(ctx, hipMemsetAsync(tails.get(), 0, tails.count() * sizeof(float), ctx->stream));
+            JDSP_HIP(ctx, hipMemsetAsync(parity.get(), 0, (size_t)n_streams * sizeof(int), ctx->stream));
+            return JDSP_OK;
+        }
+        if (int rc = check_count(entry, n_ids)) return rc;
+        if (!aligned(stream_id_dev, 8)) return fail(ctx, JDSP_EINVAL, (e + ": stream_id must be 8-byte aligned").c_str());
+        if (launch_ola_streams_flush(ctx->stream, view(stream_id_dev), n_ids, nullptr, ola->g, ola->hop, nullptr, nullptr))
+            return fail(ctx, JDSP_EHIP, (e + ": launch").c_str(), hipGetLastError());
+        return JDSP_OK;
+    }
+    // the n - hop samples still in each listed stream's tail, at sample_first[i] onwards, then its reset
+    int flush_dev(const char *entry, const int64_t *stream_id_dev, const int64_t *sample_first_dev, long n_ids,
+                  int16_t *out_i16_dev, float *out_f32_dev)
+    {
+        jdsp_ctx *ctx = ola->ctx;
+        if (int rc = check_count(entry, n_ids)) return rc;
+        const std::string e(entry);
+        if (!aligned(stream_id_dev, 8) || !aligned(sample_first_dev, 8) || !aligned(out_i16_dev, 4) || !aligned(out_f32_dev, 8))
+            return fail(ctx, JDSP_EINVAL,
+                        (e + ": stream_id, sample_first and out_f32 must be 8-byte, out_i16 4-byte aligned").c_str());
+        if (n_ids == 0) return JDSP_OK;
+        if (!stream_id_dev || ((out_i16_dev || out_f32_dev) && !sample_first_dev))
+            return fail(ctx, JDSP_EINVAL, (e + ": stream_id or sample_first is NULL").c_str());
+        if (launch_ola_streams_flush(ctx->stream, view(stream_id_dev), n_ids,
+                                     reinterpret_cast<const long long *>(sample_first_dev), ola->g, ola->hop, out_i16_dev,
+                                     out_f32_dev))
+            return fail(ctx, JDSP_EHIP, (e + ": launch").c_str(), hipGetLastError());
+        return JDSP_OK;
+    }
+    // behind the transform launch over the chunks: the streams that were given frames carry their new tails
+    int commit(const char *entry, const int64_t *stream_id_dev, const int64_t *frame_first_dev, long n_chunks)
+    {
+        if (launch_ola_streams_commit(ola->ctx->stream, reinterpret_cast<const long long *>(stream_id_dev),
+                                      reinterpret_cast<const long long *>(frame_first_dev), n_chunks, parity.get()))
+            return fail(ola->ctx, JDSP_EHIP, (std::string(entry) + ": commit launch").c_str(), hipGetLastError());
+        return JDSP_OK;
+    }
+    // host pointers, synchronous: checks the ids and the n - hop long spans (even, ascending, disjoint, inside
+    // n_samples); the outputs are n_samples long and zero outside the spans
+    int flush(const char *entry, const int64_t *stream_id_host, const int64_t *sample_first_host, long n_ids,
+              long n_samples, int16_t *out_i16_host, float *out_f32_host)
+    {
+        jdsp_ctx *ctx = ola->ctx;
+        if (int rc = check_count(entry, n_ids)) return rc;
+        const std::string e(entry);
+        if (n_samples < 0) return fail(ctx, JDSP_EINVAL, (e + ": n_samples < 0").c_str());
+        if (n_ids > 0 && (!stream_id_host || !sample_first_host))
+            return fail(ctx, JDSP_EINVAL, (e + ": stream_id or sample_first is NULL").c_str());
+        if (int rc = check_ids(entry, stream_id_host, n_ids)) return rc;
+        std::vector<int64_t> unit((size_t)n_ids + 1);
+        for (long i = 0; i <= n_ids; i++) unit[(size_t)i] = i;
+        const int nt = n_tail();
+        const RaggedLayout lay = ragged_layout_check(sample_first_host, unit.data(), n_ids, n_samples, nt, nt ? nt : 1);
+        if (lay.verdict != RaggedVerdict::kOk)
+            return fail(ctx, JDSP_EINVAL, ragged_layout_message(lay.verdict, entry, "stream_id").c_str());
+        JDSP_HIP(ctx, hipSetDevice(ctx->device));
+        int16_t *d_i16 = nullptr;
+        float *d_f32 = nullptr;
+        const hipError_t err = ola->stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
+        if (err != hipSuccess) return fail(ctx, JDSP_EHIP, (e + ": buffers").c_str(), err);
+        HostCall hc(ctx, entry);
+        const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_ids * sizeof(int64_t));
+        const int64_t *d_sf = hc.upload(sample_first_host, (size_t)n_ids * sizeof(int64_t));
+        if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));
+        if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
+        if (hc.ok()) hc.result(flush_dev(entry, d_id, d_sf, n_ids, d_i16, d_f32));
+        ola->download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
         return hc.finish();
     }
 };

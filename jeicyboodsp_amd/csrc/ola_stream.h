@@ -13,7 +13,10 @@
 // before it (the halo: added and shifted, not emitted; in a batch it stops at the utterance's first frame,
 // ragged_batch.h).  A single stream: only the wave with j0 = 0 reads the tail carried in the handle, and the wave that owns
 // the call's last frame writes the new tail (ping-pong buffers: another wave may still be reading the old one).  A batch (RaggedSpan) feeds many independent streams from one launch: a stream that ends inside a
-// wave's run leaves through emit_tail and the next starts after restart, with no tail in memory at all.
+// wave's run leaves through emit_tail and the next starts after restart, with no tail in memory at all.  Live streams
+// (LiveSpan; stftmask_live_kernel, istft_live_kernel) are the batch with carried tails: load_tail wherever a wave's first
+// computed frame is a chunk's first, shift(true, ...) to the stream's OTHER tail buffer after the chunk's last frame
+// (LiveStreams, jdsp_internal.h).
 #pragma once
 #include "frame_io.h"
 

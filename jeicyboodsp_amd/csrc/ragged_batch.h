@@ -11,7 +11,8 @@
 // The span walk at the end is that state behind the questions a frame loop asks: RaggedSpan, the above, walked by
 // stftmask_batch_kernel, stft_half_batch_kernel and istft_batch_kernel, and StreamSpan, a single stream -- a batch of
 // one span [0, n_frames) at sample 0 whose tail is carried by the handle instead of leaving from the registers -- under
-// which the same body (istft_run) is istft_run_kernel.
+// which the same body (istft_run) is istft_run_kernel.  LiveSpan is RaggedSpan over the chunks of live streams: a span
+// that starts from a tail carried in memory and ends by writing the tail back (stftmask_live_kernel, istft_live_kernel).
 #pragma once
 
 namespace jdsp {
@@ -62,7 +63,7 @@ __device__ __forceinline__ long span_halo_first(long j0, long ub, int r) { retur
 // frame j + 1 exists, into the span that holds it.  StreamSpan has what istft_run asks of a stream: its halo stands in
 // front of the loop and its prefetch needs no clamp.
 template <int HOP> struct StreamSpan {
-    static constexpr bool kBatch = false;
+    static constexpr bool kBatch = false, kLive = false;
     long n_frames;
     __device__ __forceinline__ explicit StreamSpan(long n) : n_frames(n) {}
     __device__ __forceinline__ void begin(long) {}
@@ -72,7 +73,7 @@ template <int HOP> struct StreamSpan {
 };
 
 template <int HOP> struct RaggedSpan {
-    static constexpr bool kBatch = true;
+    static constexpr bool kBatch = true, kLive = false;
     const long long *sample_first, *frame_first;
     long n_utts, u, ub, ue, base;                                // global frame j of utterance u starts at base + j HOP
     __device__ __forceinline__ RaggedSpan(const long long *sf, const long long *ff, long n)
@@ -94,6 +95,41 @@ template <int HOP> struct RaggedSpan {
         ragged_next_utt(frame_first, n_utts, u, ue);
         base = uniform_i64(sample_first + u) - ub * HOP;
     }
+};
+
+// RaggedSpan's walk over the chunks of live streams (LiveStreams, jdsp_internal.h: the layout of the carried tails and
+// why a launch may read and write them without a race), plus the stream and the parity of the current chunk in scalar
+// registers.  It answers what the frame loops of a batch never ask: tail_in(), where the sums come from when the first
+// frame a wave computes is the chunk's first (starts_span(js)), and tail_out(), where they go after the chunk's last
+// frame.
+template <int HOP> struct LiveSpan : RaggedSpan<HOP> {
+    static constexpr bool kLive = true;
+    const long long *stream_id;                                  // the kernel's own __restrict__ arguments, not the
+    const int *parity;                                           // struct's members: scalar loads in the walk too
+    LiveStreams live;
+    long s;                                                      // the current chunk's stream
+    int p;                                                       // ... and the tail it starts from
+    __device__ __forceinline__ LiveSpan(const long long *sf, const long long *ff, long n, const long long *ids,
+                                        const int *par, const LiveStreams &l)
+        : RaggedSpan<HOP>(sf, ff, n), stream_id(ids), parity(par), live(l) {}
+    __device__ __forceinline__ void load_stream()
+    {
+        s = uniform_i64(stream_id + this->u);
+        p = __builtin_amdgcn_readfirstlane(parity[s]) & 1;
+    }
+    __device__ __forceinline__ void begin(long j0)
+    {
+        RaggedSpan<HOP>::begin(j0);
+        load_stream();
+    }
+    __device__ __forceinline__ void next()
+    {
+        RaggedSpan<HOP>::next();
+        load_stream();
+    }
+    __device__ __forceinline__ bool starts_span(long js) const { return js == this->ub; }
+    __device__ __forceinline__ const float *tail_in() const { return live.tails + ((long)p * live.n_streams + s) * live.n_tail; }
+    __device__ __forceinline__ float *tail_out() const { return live.tails + ((long)(p ^ 1) * live.n_streams + s) * live.n_tail; }
 };
 
 }  // namespace jdsp

@@ -3,8 +3,10 @@
 // on trust, so this is all that stands between a caller's offsets and reads or writes outside the buffers.
 // Host only and free of HIP: a plain C++ compiler builds it (tests/ragged_layout_selftest.cpp does).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 namespace jdsp {
 
@@ -56,6 +58,33 @@ inline std::string ragged_layout_message(RaggedVerdict v, const char *entry, con
     case RaggedVerdict::kSampleParity: return e + "sample_first entries must be even and >= 0";
     case RaggedVerdict::kOverlap: return e + "sample_first must ascend and the utterances' spans must not overlap";
     case RaggedVerdict::kPastEnd: return e + "an utterance's span ends past n_samples";
+    }
+    return std::string();
+}
+
+// ---- live streams: the stream ids that come with a list of chunks (or of streams to flush) -------------------------
+enum class StreamIdVerdict { kOk, kRange, kDuplicate };
+
+// Every id in [0, n_streams) and no id twice: a kernel indexes the handle's tails by them, and two chunks of one stream
+// in a call would both start from the same tail.  The first id that fails is the verdict, range before duplicate.
+inline StreamIdVerdict stream_ids_check(const int64_t *stream_id, int64_t n_ids, int64_t n_streams)
+{
+    if (n_ids <= 0) return StreamIdVerdict::kOk;
+    std::vector<int64_t> sorted(stream_id, stream_id + n_ids);
+    for (int64_t id : sorted)
+        if (id < 0 || id >= n_streams) return StreamIdVerdict::kRange;
+    std::sort(sorted.begin(), sorted.end());
+    return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end() ? StreamIdVerdict::kOk
+                                                                            : StreamIdVerdict::kDuplicate;
+}
+
+inline std::string stream_ids_message(StreamIdVerdict v, const char *entry)
+{
+    const std::string e = std::string(entry) + ": ";
+    switch (v) {
+    case StreamIdVerdict::kOk: break;
+    case StreamIdVerdict::kRange: return e + "a stream id lies outside [0, n_streams)";
+    case StreamIdVerdict::kDuplicate: return e + "a stream id occurs twice";
     }
     return std::string();
 }

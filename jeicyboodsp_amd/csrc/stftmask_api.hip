@@ -10,6 +10,7 @@ struct jdsp_stftmask {
     jdsp::DevBuf<float> blob;             // wa[n] (w_a / 2), ws[n] (w_s), then the stream's share
     float *wa = nullptr, *ws = nullptr;   // views into blob
     OlaStream ola;
+    jdsp::OlaStreams live;                // the live streams (jdsp_stftmask_streams_*), none until _streams_reserve
     // the host entry's device copies of its inputs, grown on demand
     jdsp::DevBuf<int16_t> h_pcm;
     jdsp::DevBuf<char> h_mask;            // bytes: rows of float or jdsp_c32
@@ -83,6 +84,7 @@ int jdsp_stftmask_create(jdsp_ctx *ctx, const jdsp_stftmask_cfg *cfg, jdsp_stftm
         h->wa = h->blob.get();
         h->ws = h->wa + n;
         h->ola.attach(ctx, n, hop, h->ws + n);
+        h->live.ola = &h->ola;
         e = hipMemcpy(h->wa, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
@@ -281,6 +283,118 @@ int jdsp_stftmask_batch(jdsp_stftmask *h, const int16_t *pcm_host, long n_sample
                                           n_total, d_i16, d_f32));
     h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
     return hc.finish();
+}
+
+// ---- live streams ---------------------------------------------------------------------------------------------------
+
+int jdsp_stftmask_streams_reserve(jdsp_stftmask *h, long n_streams)
+{
+    return h ? h->live.reserve("jdsp_stftmask_streams_reserve", n_streams) : JDSP_EINVAL;
+}
+
+int jdsp_stftmask_streams_reset_dev(jdsp_stftmask *h, const int64_t *stream_id_dev, long n_ids)
+{
+    return h ? h->live.reset_dev("jdsp_stftmask_streams_reset", stream_id_dev, n_ids) : JDSP_EINVAL;
+}
+
+int jdsp_stftmask_streams_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void *mask_dev, long mask_pitch,
+                              const int64_t *stream_id_dev, const int64_t *sample_first_dev,
+                              const int64_t *frame_first_dev, long n_chunks, long n_frames_total, int16_t *out_i16_dev,
+                              float *out_f32_dev)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    if (int rc = h->live.check_count("jdsp_stftmask_streams", n_chunks)) return rc;
+    if (n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: n_frames_total < 0");
+    if (mask_pitch != 0 && mask_pitch < kBins)
+        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: mask_pitch must be 0 (one row) or >= n_fft/2 + 1");
+    if (!jdsp::aligned(pcm_dev, 4) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
+        !jdsp::aligned(mask_dev, mask_elem(h)) || !jdsp::aligned(stream_id_dev, 8) ||
+        !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(frame_first_dev, 8))
+        return fail(ctx, JDSP_EINVAL,
+                    "jdsp_stftmask_streams: pcm and out_i16 must be 4-byte, out_f32, the stream ids and the offset arrays "
+                    "8-byte aligned, the mask 4-byte (REAL) or 8-byte (COMPLEX)");
+    if (n_chunks == 0 || n_frames_total == 0) {
+        h->count_valid = 0;
+        return JDSP_OK;
+    }
+    if (!pcm_dev || !mask_dev || !stream_id_dev || !sample_first_dev || !frame_first_dev)
+        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: pcm, mask, stream_id, sample_first or frame_first is NULL");
+    if (!out_i16_dev && !out_f32_dev) {                        // as the batch entry: nothing is done, no stream advances
+        h->count_valid = 0;
+        return JDSP_OK;
+    }
+    if (jdsp::launch_stftmask_live(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev,
+                                   mask_dev, mask_pitch, n_frames_total,
+                                   reinterpret_cast<const long long *>(sample_first_dev),
+                                   reinterpret_cast<const long long *>(frame_first_dev), n_chunks,
+                                   h->live.view(stream_id_dev), h->wa, h->ws, h->ola.g, out_i16_dev, out_f32_dev,
+                                   ctx->stft1024_table.get(), h->ola.run_opt, h->f64.get(), h->count.get(),
+                                   h->next_epoch()))
+        return fail(ctx, JDSP_EHIP, "jdsp_stftmask_streams: launch", hipGetLastError());
+    return h->live.commit("jdsp_stftmask_streams", stream_id_dev, frame_first_dev, n_chunks);
+}
+
+int jdsp_stftmask_streams_flush_dev(jdsp_stftmask *h, const int64_t *stream_id_dev, const int64_t *sample_first_dev,
+                                    long n_ids, int16_t *out_i16_dev, float *out_f32_dev)
+{
+    return h ? h->live.flush_dev("jdsp_stftmask_streams_flush", stream_id_dev, sample_first_dev, n_ids, out_i16_dev,
+                                 out_f32_dev)
+             : JDSP_EINVAL;
+}
+
+int jdsp_stftmask_streams(jdsp_stftmask *h, const int16_t *pcm_host, long n_samples, const void *mask_host,
+                          long mask_pitch, const int64_t *stream_id_host, const int64_t *sample_first_host,
+                          const int64_t *frame_first_host, long n_chunks, int16_t *out_i16_host, float *out_f32_host)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    if (int rc = h->live.check_count("jdsp_stftmask_streams", n_chunks)) return rc;
+    if (n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: n_samples < 0");
+    if (mask_pitch != 0 && mask_pitch < kBins)
+        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: mask_pitch must be 0 (one row) or >= n_fft/2 + 1");
+    if (n_chunks > 0 && (!stream_id_host || !sample_first_host || !frame_first_host))
+        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: stream_id, sample_first or frame_first is NULL");
+    if (int rc = h->live.check_ids("jdsp_stftmask_streams", stream_id_host, n_chunks)) return rc;
+    jdsp::RaggedOffsets offs;
+    if (offs.check(ctx, "jdsp_stftmask_streams", "frame_first", sample_first_host, frame_first_host, n_chunks, n_samples,
+                   h->cfg.n_fft, h->cfg.hop))
+        return JDSP_EINVAL;
+    const long n_total = offs.lay.n_total;
+    if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
+        if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
+        if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
+        return JDSP_OK;
+    }
+    if (!pcm_host || !mask_host) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: pcm or mask is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t mask_bytes = ((size_t)(n_total - 1) * mask_pitch + kBins) * mask_elem(h);
+    int16_t *d_i16 = nullptr;
+    float *d_f32 = nullptr;
+    hipError_t e = h->h_pcm.grow((size_t)n_samples);
+    if (e == hipSuccess) e = h->h_mask.grow(mask_bytes);
+    if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
+    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_stftmask_streams: buffers", e);
+    jdsp::HostCall hc(ctx, "jdsp_stftmask_streams");
+    offs.upload(hc);
+    const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_chunks * sizeof(int64_t));
+    hc.upload_to(h->h_pcm.get(), pcm_host, (size_t)offs.lay.end * sizeof(int16_t));   // nothing past the last span is read
+    hc.upload_to(h->h_mask.get(), mask_host, mask_bytes);
+    if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the written ranges
+    if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
+    if (hc.ok())
+        hc.result(jdsp_stftmask_streams_dev(h, h->h_pcm.get(), h->h_mask.get(), mask_pitch, d_id, offs.d_sample, offs.d_unit,
+                                            n_chunks, n_total, d_i16, d_f32));
+    h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
+    return hc.finish();
+}
+
+int jdsp_stftmask_streams_flush(jdsp_stftmask *h, const int64_t *stream_id_host, const int64_t *sample_first_host,
+                                long n_ids, long n_samples, int16_t *out_i16_host, float *out_f32_host)
+{
+    return h ? h->live.flush("jdsp_stftmask_streams_flush", stream_id_host, sample_first_host, n_ids, n_samples,
+                             out_i16_host, out_f32_host)
+             : JDSP_EINVAL;
 }
 
 }  // extern "C"

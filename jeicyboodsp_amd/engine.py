@@ -1020,6 +1020,7 @@ class _OlaStream(_Child):
         self._h = h
         self.n_fft, self.hop = cfg.n_fft, cfg.hop
         self._torch = None              # the kind of the last process() input: flush() answers in the same kind
+        self.n_streams, self._streams_torch, self._streams_key = 0, None, None     # live streams: open_streams()
         engine._children.append(self)
 
     def reset(self):
@@ -1070,6 +1071,84 @@ class _OlaStream(_Child):
             f = np.zeros(max(n, 1), np.float32) if want_f32 else None
             self.eng._ck(self._c("_flush")(self._h, _vp(out), _vp(f)))
         return (out[:n], f[:n]) if want_f32 else out[:n]
+
+    # ---- live streams: n independent output streams in the handle, advanced a chunk each by one call ----------------
+    def open_streams(self, n_streams):
+        """Gives the handle n_streams live streams, all fresh (jdsp_*_streams_reserve): the only call of the live
+        entries that allocates, and it synchronises.  Calling it again discards every live stream's state."""
+        self.eng._ck(self._c("_streams_reserve")(self._h, int(n_streams)))
+        self.n_streams = int(n_streams)
+        self._streams_torch = None      # the kind of the last process_streams() input: flush_streams() answers in it
+        self._streams_key = None
+
+    def _stream_device(self):
+        import torch
+        return self._streams_torch if self._streams_torch is not None else torch.device("cuda", self.eng.device)
+
+    def _chunks(self, stream_ids, frame_counts, chunk_sample_first, with_pcm, dev):
+        """The arrays of one process_streams call: (ids, sample_first, frame_first) as numpy int64, their device
+        copies on `dev` (None with dev None; kept until the layout changes, as _batch_offsets keeps a batch's) and the
+        samples the spans reach."""
+        from .sharding import stream_chunks_layout
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        counts = np.ascontiguousarray(frame_counts, np.int64).reshape(-1)
+        assert ids.size == counts.size, "one frame count per chunk"
+        packed, frame_first, _ = stream_chunks_layout(counts, self.n_fft, self.hop, with_pcm)
+        if chunk_sample_first is None:
+            sample_first = packed
+        else:
+            sample_first = np.ascontiguousarray(chunk_sample_first, np.int64).reshape(-1)
+            assert sample_first.size == ids.size and not np.any(sample_first & 1)
+        n = self.n_fft if with_pcm else self.hop
+        ends = sample_first + np.where(counts > 0, self.hop * (counts - 1) + n, 0)
+        d = None
+        if dev is not None:
+            import torch
+            key = (ids.tobytes(), sample_first.tobytes(), counts.tobytes(), dev)
+            if self._streams_key != key:
+                self._streams_dev = tuple(torch.from_numpy(a).to(dev) for a in (ids, sample_first, frame_first))
+                self._streams_key = key
+            d = self._streams_dev
+        return ids, sample_first, frame_first, d, int(ends.max()) if ends.size else 0
+
+    def flush_streams(self, stream_ids, want_f32=False):
+        """The n_fft - hop samples still in the tail of each listed live stream, then their reset
+        (jdsp_*_streams_flush).  Returns int16 [n_ids, n_fft - hop], or (int16, float32) with want_f32, in the kind
+        (torch CUDA or numpy) of the last process_streams input."""
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        n = self.n_fft - self.hop
+        sample_first = np.arange(ids.size, dtype=np.int64) * n
+        total = int(ids.size) * n
+        if self._streams_torch is not None:
+            import torch
+            dev = self._streams_torch
+            out = torch.zeros(max(total, 1), dtype=torch.int16, device=dev)
+            f = torch.zeros(max(total, 1), dtype=torch.float32, device=dev) if want_f32 else None
+            d_ids, d_first = torch.from_numpy(ids).to(dev), torch.from_numpy(sample_first).to(dev)
+            self.eng._use_torch_stream()
+            self.eng._ck(self._c("_streams_flush_dev")(self._h, _vp(d_ids), _vp(d_first), ids.size, _vp(out), _vp(f)))
+            self._flush_args = (d_ids, d_first)                 # alive until the stream has run the call
+        else:
+            out = np.zeros(max(total, 1), np.int16)
+            f = np.zeros(max(total, 1), np.float32) if want_f32 else None
+            self.eng._ck(self._c("_streams_flush")(self._h, _vp(ids), _vp(sample_first), ids.size, total, _vp(out),
+                                                  _vp(f)))
+        out = out[:total].reshape(ids.size, n)
+        return (out, f[:total].reshape(ids.size, n)) if want_f32 else out
+
+    def reset_streams(self, stream_ids=None):
+        """The listed live streams fresh again, or all of them with None (jdsp_*_streams_reset_dev; enqueue-only)."""
+        if stream_ids is None:
+            if self._streams_torch is not None:
+                self.eng._use_torch_stream()
+            self.eng._ck(self._c("_streams_reset_dev")(self._h, None, 0))
+            return
+        import torch
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        d_ids = torch.from_numpy(ids).to(self._stream_device())
+        self.eng._use_torch_stream()
+        self.eng._ck(self._c("_streams_reset_dev")(self._h, _vp(d_ids), ids.size))
+        self._reset_args = d_ids                                # alive until the stream has run the call
 
 
 class Istft(_OlaStream):
@@ -1140,6 +1219,39 @@ class Istft(_OlaStream):
         else:
             self.eng._ck(L.jdsp_istft_batch(self._h, _vp(spec), pitch, _vp(sample_first), _vp(frame_first), n_utts,
                                             n_samples, _vp(out), _vp(out_f32)))
+        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+
+    def process_streams(self, spec, stream_ids, frame_counts, chunk_sample_first=None, n_samples=None, want_f32=False,
+                        out=None, out_f32=None):
+        """One call over live streams (jdsp_istft_streams; open_streams first): chunk c advances the live stream
+        stream_ids[c] by the frame_counts[c] >= 0 rows that follow the chunk before it in spec (complex64
+        [sum F_c, row_pitch >= bins], contiguous rows) and writes its hop F_c samples at chunk_sample_first[c] (even;
+        None packs the chunks back to back, sharding.stream_chunks_layout).  A stream's chunks over the calls followed
+        by flush_streams equal a fresh handle's process + flush of the same rows, bit for bit.  Ids are distinct
+        within a call.  torch CUDA (the device entry on torch's current stream) or numpy (the host entry).  Returns
+        int16 of n_samples (default: up to the last span's end), or (int16, float32) with want_f32; what lies outside
+        the written ranges is zero, or is left as it was in out / out_f32 when given on the device path."""
+        dev = spec.device if _is_torch(spec) else None
+        ids, sample_first, frame_first, d, end = self._chunks(stream_ids, frame_counts, chunk_sample_first, False, dev)
+        n_chunks, n_total = ids.size, int(frame_first[-1])
+        n_samples = end if n_samples is None else int(n_samples)
+        pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
+        assert spec.ndim == 2 and spec.shape[0] >= n_total and pitch >= self.bins and n_samples >= end
+        self._streams_torch = dev
+        if dev is not None:
+            import torch
+            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
+        else:
+            spec = np.ascontiguousarray(spec, np.complex64)
+        out = _batch_out(n_samples, np.int16, dev, out)
+        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_istft_streams_dev(self._h, _vp(spec), pitch, _vp(d[0]), _vp(d[1]), _vp(d[2]), n_chunks,
+                                                  n_total, _vp(out), _vp(out_f32)))
+        else:
+            self.eng._ck(L.jdsp_istft_streams(self._h, _vp(spec), pitch, _vp(ids), _vp(sample_first), _vp(frame_first),
+                                              n_chunks, n_samples, _vp(out), _vp(out_f32)))
         return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
 
 
@@ -1229,6 +1341,44 @@ class StftMask(_OlaStream):
         else:
             self.eng._ck(L.jdsp_stftmask_batch(self._h, _vp(pcm), n_samples, _vp(mask), pitch, _vp(sample_first),
                                                _vp(frame_first), n_utts, _vp(out), _vp(out_f32)))
+        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+
+    def process_streams(self, pcm, mask, stream_ids, frame_counts, chunk_sample_first=None, want_f32=False, out=None,
+                        out_f32=None):
+        """One call over live streams (jdsp_stftmask_streams; open_streams first): chunk c advances the live stream
+        stream_ids[c] by frame_counts[c] >= 0 frames.  Its PCM span, hop (F_c - 1) + n_fft samples of pcm from
+        chunk_sample_first[c] (even; None: the chunks back to back, sharding.stream_chunks_layout), begins with the
+        last n_fft - hop samples of the stream's previous chunk -- the handle keeps no PCM -- and its hop F_c output
+        samples come out at the same offset; its mask rows follow the chunk before it in mask (float32 or complex64
+        [sum F_c, pitch >= bins] with contiguous rows, or 1-D [bins]: one row for everything).  A stream's chunks over
+        the calls followed by flush_streams equal a fresh handle's process + flush of the same frames, bit for bit.
+        Ids are distinct within a call.  Both torch CUDA (the device entry on torch's current stream) or both numpy
+        (the host entry).  Returns int16 of pcm's length, or (int16, float32) with want_f32; what lies outside the
+        written ranges is zero, or is left as it was in out / out_f32 when given on the device path."""
+        dev = pcm.device if _is_torch(pcm) else None
+        ids, sample_first, frame_first, d, end = self._chunks(stream_ids, frame_counts, chunk_sample_first, True, dev)
+        n_chunks, n_total, n_samples = ids.size, int(frame_first[-1]), int(pcm.shape[0])
+        assert pcm.ndim == 1 and n_samples >= end
+        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_total)
+        pitch = mask.shape[1] if mask.ndim == 2 else 0
+        self._streams_torch = dev
+        if dev is not None:
+            import torch
+            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
+        out = _batch_out(n_samples, np.int16, dev, out)
+        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_stftmask_streams_dev(self._h, _vp(pcm), _vp(mask), pitch, _vp(d[0]), _vp(d[1]), _vp(d[2]),
+                                                     n_chunks, n_total, _vp(out), _vp(out_f32)))
+        else:
+            self.eng._ck(L.jdsp_stftmask_streams(self._h, _vp(pcm), n_samples, _vp(mask), pitch, _vp(ids),
+                                                 _vp(sample_first), _vp(frame_first), n_chunks, _vp(out), _vp(out_f32)))
         return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
 
 

@@ -198,6 +198,20 @@ def istft_batch_layout(frame_counts, n_fft, hop):
     return packed
 
 
+def stream_chunks_layout(frame_counts, n_fft, hop, with_pcm):
+    """The back-to-back packing of the chunks of one live-streams call (StftMask.process_streams,
+    Istft.process_streams): chunk c of F_c = frame_counts[c] >= 0 frames takes, with_pcm (fused masking: the chunk's
+    PCM span, of which the first hop F_c samples are its output), hop (F_c - 1) + n_fft samples and none when F_c = 0,
+    or, without (synthesis: the output alone), hop F_c samples; the spans follow each other without a gap.  Returns
+    (sample_first [n_chunks], frame_first [n_chunks + 1], n_samples) with the two arrays as numpy int64; the offsets
+    are even because n_fft and hop are.  A live stream lives on one device: over ranks the stream ids are split with
+    stream_shard.  Negative counts, an odd or non-positive hop or n_fft, or n_fft < hop: ValueError."""
+    if hop <= 0 or n_fft < hop or n_fft % 2 or hop % 2:
+        raise ValueError("n_fft and hop must be even, hop > 0 and n_fft >= hop")
+    sample_first, frame_first = _pack_back_to_back(frame_counts, n_fft if with_pcm else hop, hop, "frame")
+    return sample_first[:-1].copy(), frame_first, int(sample_first[-1])
+
+
 def denoise_batch_layout(block_counts, hop):
     """The back-to-back packing of a batch of utterances for Denoiser.process_batch (jdsp_denoise_batch): utterance u
     of B_u = block_counts[u] >= 0 blocks of hop samples takes hop B_u samples, and the spans follow each other

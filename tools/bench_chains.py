@@ -458,6 +458,107 @@ def main():
             for d in (d_a, d_b, d_c):
                 d.close()
         del x, o16
+    if on("stftmask_streams") or on("istft_streams"):
+        # Live streams (jdsp_stftmask_streams_dev, jdsp_istft_streams_dev): 10,000 live streams, every call brings each
+        # of them a chunk of 4 frames, hop 256 and 512, real mask / half layout (pitch 513).  Timed three ways in this
+        # process, in alternated rounds, every C entry called through ctypes with its arguments computed beforehand:
+        # (a) the streams entry, the transform launch plus the commit launch; (b) one single-stream handle per stream in
+        # a loop of _process_dev -- over the first 1,000 streams, the figure scaled by 10 --; (c) the stateless _batch_dev
+        # entry over the same chunks as utterances, the yardstick.  The inputs rotate over 6 copies (0.7-1.0 GB in all,
+        # past the 256 MiB Infinity Cache); the calls of (a) follow each other as the calls of a service do, every
+        # stream carrying its tail on.  Bytes per chunk come from the shapes: against (c), (a) reads and writes a tail
+        # of 4 (n - hop) bytes and does not write (c)'s emitted tail of 2 (n - hop).
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        S, F, n, n_loop, pitch = 10000, 4, 1024, 1000, 513
+        gen = torch.Generator(device="cuda").manual_seed(18)
+        ids = torch.from_numpy(np.random.default_rng(18).permutation(S).astype(np.int64)).cuda()
+        vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)   # noqa: E731
+        it, rounds = max(100 * a.iters, 200), 3
+        for kind in ("stftmask", "istft"):
+            if not on(kind + "_streams"):
+                continue
+            for hop in (256, 512):
+                counts = np.full(S, F, np.int64)
+                sf_a, ff, n_a = sharding.stream_chunks_layout(counts, n, hop, kind == "stftmask")
+                d_ff = torch.from_numpy(ff).cuda()
+                d_sf_a = torch.from_numpy(sf_a).cuda()
+                total = S * F
+                tail = 4 * (n - hop)
+                span = hop * (F - 1) + n
+                if kind == "stftmask":
+                    sm = eng.stft_mask(n_fft=n, hop=hop, analysis_window="hann", synthesis_window="hann", normalise=1)
+                    sm.open_streams(S)
+                    ins = [((torch.randn(n_a, device="cuda", generator=gen) * 3000.0).clamp_(-32768, 32767).to(torch.int16),
+                            torch.rand((total, pitch), dtype=torch.float32, device="cuda", generator=gen) * 1.5)
+                           for _ in range(1 if a.warm else 6)]
+                    o16 = torch.empty(n_a, dtype=torch.int16, device="cuda")
+                    args_a = [(sm._h, vp(x), vp(m), pitch, vp(ids), vp(d_sf_a), vp(d_ff), S, total, vp(o16), None) for x, m in ins]
+                    args_c = [(sm._h, vp(x), vp(m), pitch, vp(d_sf_a), vp(d_ff), S, total, vp(o16), None) for x, m in ins]
+                    ent_a, ent_c, ent_b = L.jdsp_stftmask_streams_dev, L.jdsp_stftmask_batch_dev, L.jdsp_stftmask_process_dev
+                    singles = [eng.stft_mask(n_fft=n, hop=hop, analysis_window="hann", synthesis_window="hann", normalise=1)
+                               for _ in range(n_loop)]
+                    x0, m0 = ins[0]
+                    args_b = [(h._h, vp(x0, 2 * int(sf_a[u])), vp(m0, 4 * pitch * F * u), pitch, F, vp(o16, 2 * int(sf_a[u])), None)
+                              for u, h in enumerate(singles)]
+                    common = 2 * span + F * pitch * 4
+                    bytes_a, bytes_c = common + 2 * hop * F + 2 * tail, common + 2 * span
+                    what = "real mask"
+                else:
+                    sm = eng.istft(n_fft=n, hop=hop, layout="half", synthesis_window="hann", analysis_window="hann")
+                    sm.open_streams(S)
+                    ins = [torch.randn((total, pitch), dtype=torch.complex64, device="cuda", generator=gen) * 3000.0 * np.sqrt(n)
+                           for _ in range(1 if a.warm else 6)]
+                    sf_c, _ = sharding.istft_batch_layout(counts, n, hop)
+                    d_sf_c = torch.from_numpy(np.ascontiguousarray(sf_c[:-1])).cuda()
+                    o16 = torch.empty(int(sf_c[-1]), dtype=torch.int16, device="cuda")
+                    args_a = [(sm._h, vp(s), pitch, vp(ids), vp(d_sf_a), vp(d_ff), S, total, vp(o16), None) for s in ins]
+                    args_c = [(sm._h, vp(s), pitch, vp(d_sf_c), vp(d_ff), S, total, vp(o16), None) for s in ins]
+                    ent_a, ent_c, ent_b = L.jdsp_istft_streams_dev, L.jdsp_istft_batch_dev, L.jdsp_istft_process_dev
+                    singles = [eng.istft(n_fft=n, hop=hop, layout="half", synthesis_window="hann", analysis_window="hann")
+                               for _ in range(n_loop)]
+                    args_b = [(h._h, vp(ins[0], 8 * pitch * F * u), pitch, F, vp(o16, 2 * int(sf_a[u])), None)
+                              for u, h in enumerate(singles)]
+                    common = F * pitch * 8
+                    bytes_a, bytes_c = common + 2 * hop * F + 2 * tail, common + 2 * span
+                    what = "half layout"
+                eng._use_torch_stream()
+                turn = [0]
+
+                def call_a():
+                    turn[0] += 1
+                    ent_a(*args_a[turn[0] % len(args_a)])
+
+                def call_c():
+                    turn[0] += 1
+                    ent_c(*args_c[turn[0] % len(args_c)])
+
+                def loop():
+                    for p in args_b:
+                        ent_b(*p)
+
+                assert ent_a(*args_a[0]) == 0 and ent_c(*args_c[0]) == 0 and ent_b(*args_b[0]) == 0
+                ms_a, ms_c, ms_b = timed_alternated([call_a, call_c, loop], [it, it, 1], rounds=rounds)
+                ms_b *= S / n_loop
+                flops = (2 if kind == "stftmask" else 1) * (5 * 512 * 9 + 512 * 14)
+                inp = "rotated over %d copies of %.0f MB (from HBM)" % (len(ins), 1e-6 * S * common)
+                shape = "10,000 live streams x 4 frames per call, hop %d, %s" % (hop, what)
+                report("%s_streams_1024_hop%d" % (kind, hop), ms_a, total, "frames", bytes_a / F, flops,
+                       "(a) jdsp_%s_streams_dev, the transform launch and the commit launch: %s; (a)/(c) = %.3f against a "
+                       "byte ratio of %.3f (%d against %d bytes per chunk); %.4f of the per-stream loop (b); %d calls per "
+                       "round, %d rounds" % (kind, shape, ms_a / ms_c, bytes_a / bytes_c, bytes_a, bytes_c, ms_a / ms_b, it, rounds),
+                       inp=inp)
+                report("%s_streams_1024_hop%d_per_stream_loop" % (kind, hop), ms_b, total, "frames", bytes_a / F, flops,
+                       "(b) one single-stream handle per stream, a loop of jdsp_%s_process_dev from ctypes with precomputed "
+                       "arguments: measured over %d streams and scaled by %d; %.1f x the streams entry"
+                       % (kind, n_loop, S // n_loop, ms_b / ms_a), inp=inp)
+                report("%s_streams_1024_hop%d_stateless_batch" % (kind, hop), ms_c, total, "frames", bytes_c / F, flops,
+                       "(c) the yardstick: jdsp_%s_batch_dev over the same chunks as utterances, nothing carried" % kind, inp=inp)
+                for h in singles:
+                    h.close()
+                sm.close()
+                del ins, o16, args_a, args_b, args_c, singles
     if on("mfcc"):
         x = torch.from_numpy(pcm_of(rng, 512 * (B + 1))).cuda()
         xr = rot(x)
