@@ -1,5 +1,5 @@
 // istft_api.hip -- C ABI of the STFT synthesis stream object (include/jdsp.h, jdsp_istft_*).
-#include "jdsp_internal.h"
+#include "ola_api.h"
 
 using jdsp::fail;
 using jdsp::OlaStream;
@@ -15,6 +15,60 @@ struct jdsp_istft {
 };
 
 static int bins_of(const jdsp_istft_cfg &c) { return c.layout == JDSP_SPEC_HALF ? c.n_fft / 2 + 1 : c.n_fft; }
+
+// what the handle checks of the input of a ragged call itself (jdsp::OwnRules, ola_api.h)
+static jdsp::OwnRules own_rules(const jdsp_istft *h, const void *spec, long row_pitch)
+{
+    jdsp::OwnRules own;
+    if (row_pitch < bins_of(h->cfg)) own.pitch = "row_pitch below the layout's bins";
+    if (!jdsp::aligned(spec, 8)) own.align = "spec must be 8-byte aligned";
+    if (!spec) own.null = "spec is NULL";
+    return own;
+}
+
+// jdsp_istft_batch_dev (live == NULL) and jdsp_istft_streams_dev
+static int ragged_dev(jdsp_istft *h, jdsp::OlaStreams *live, const jdsp_c32 *spec_dev, long row_pitch,
+                      const int64_t *stream_id_dev, const int64_t *sample_first_dev, const int64_t *frame_first_dev, long n,
+                      long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev)
+{
+    jdsp_ctx *ctx = h->ctx;
+    const char *entry = live ? "jdsp_istft_streams" : "jdsp_istft_batch";
+    switch (jdsp::ragged_call_check(ctx, live, entry, own_rules(h, spec_dev, row_pitch), stream_id_dev, sample_first_dev,
+                                    frame_first_dev, n, n_frames_total, out_i16_dev, out_f32_dev)) {
+    case jdsp::RaggedCall::kRejected: return JDSP_EINVAL;
+    case jdsp::RaggedCall::kNothing: return JDSP_OK;
+    case jdsp::RaggedCall::kLaunch: break;
+    }
+    jdsp::LiveStreams view;
+    if (live) view = live->view(stream_id_dev);
+    if (jdsp::launch_istft_ragged(ctx->stream, ctx->n_cu, h->cfg.n_fft, h->cfg.hop, h->cfg.layout == JDSP_SPEC_HALF,
+                                  reinterpret_cast<const float2 *>(spec_dev), row_pitch, n_frames_total,
+                                  reinterpret_cast<const long long *>(sample_first_dev),
+                                  reinterpret_cast<const long long *>(frame_first_dev), n, live ? &view : nullptr, h->ws,
+                                  h->ola.g, out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt))
+        return fail(ctx, JDSP_EHIP, (std::string(entry) + ": launch").c_str(), hipGetLastError());
+    return live ? live->commit(entry, stream_id_dev, frame_first_dev, n) : JDSP_OK;
+}
+
+// jdsp_istft_batch (live == NULL: an utterance's span is its hop (F_u - 1) + n_fft samples) and jdsp_istft_streams (a
+// chunk's span is its hop F_c output samples)
+static int ragged_host(jdsp_istft *h, jdsp::OlaStreams *live, const jdsp_c32 *spec_host, long row_pitch,
+                       const int64_t *stream_id_host, const int64_t *sample_first_host, const int64_t *frame_first_host,
+                       long n, long n_samples, int16_t *out_i16_host, float *out_f32_host)
+{
+    return jdsp::ragged_host_call(
+        h->ola, live, live ? "jdsp_istft_streams" : "jdsp_istft_batch", own_rules(h, spec_host, row_pitch), stream_id_host,
+        sample_first_host, frame_first_host, n, n_samples, live ? h->cfg.hop : h->cfg.n_fft, out_i16_host, out_f32_host,
+        [&](jdsp::HostCall &hc, long n_total, long) {
+            const size_t n_in = (size_t)(n_total - 1) * row_pitch + bins_of(h->cfg);
+            const hipError_t e = h->h_spec.grow(n_in);
+            if (e == hipSuccess) hc.upload_to(h->h_spec.get(), spec_host, n_in * sizeof(jdsp_c32));
+            return e;
+        },
+        [&](const int64_t *d_id, const int64_t *d_sample, const int64_t *d_frame, long n_total, int16_t *d_i16, float *d_f32) {
+            return ragged_dev(h, live, h->h_spec.get(), row_pitch, d_id, d_sample, d_frame, n, n_total, d_i16, d_f32);
+        });
+}
 
 extern "C" {
 
@@ -145,24 +199,8 @@ int jdsp_istft_batch_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pitch
                          float *out_f32_dev)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (n_utts < 0 || n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: n_utts or n_frames_total < 0");
-    if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: row_pitch below the layout's bins");
-    if (!jdsp::aligned(spec_dev, 8) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
-        !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(frame_first_dev, 8))
-        return fail(ctx, JDSP_EINVAL,
-                    "jdsp_istft_batch: spec, out_f32 and the offset arrays must be 8-byte, out_i16 4-byte aligned");
-    if (n_utts == 0 || n_frames_total == 0) return JDSP_OK;
-    if (!spec_dev || !sample_first_dev || !frame_first_dev)
-        return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: spec, sample_first or frame_first is NULL");
-    if (!out_i16_dev && !out_f32_dev) return JDSP_OK;          // no stream to advance: nothing to do
-    if (jdsp::launch_istft_batch(ctx->stream, ctx->n_cu, h->cfg.n_fft, h->cfg.hop, h->cfg.layout == JDSP_SPEC_HALF,
-                                 reinterpret_cast<const float2 *>(spec_dev), row_pitch, n_frames_total,
-                                 reinterpret_cast<const long long *>(sample_first_dev),
-                                 reinterpret_cast<const long long *>(frame_first_dev), n_utts, h->ws, h->ola.g, out_i16_dev,
-                                 out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt))
-        return fail(ctx, JDSP_EHIP, "jdsp_istft_batch: launch", hipGetLastError());
-    return JDSP_OK;
+    return ragged_dev(h, nullptr, spec_dev, row_pitch, nullptr, sample_first_dev, frame_first_dev, n_utts, n_frames_total,
+                      out_i16_dev, out_f32_dev);
 }
 
 int jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, const int64_t *sample_first_host,
@@ -170,39 +208,8 @@ int jdsp_istft_batch(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch, c
                      float *out_f32_host)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: n_utts or n_samples < 0");
-    if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: row_pitch below the layout's bins");
-    if (n_utts > 0 && (!sample_first_host || !frame_first_host))
-        return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: sample_first or frame_first is NULL");
-    jdsp::RaggedOffsets offs;
-    if (offs.check(ctx, "jdsp_istft_batch", "frame_first", sample_first_host, frame_first_host, n_utts, n_samples,
-                   h->cfg.n_fft, h->cfg.hop))
-        return JDSP_EINVAL;
-    const long n_total = offs.lay.n_total;
-    if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
-        if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
-        if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
-        return JDSP_OK;
-    }
-    if (!spec_host) return fail(ctx, JDSP_EINVAL, "jdsp_istft_batch: spec is NULL");
-    JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n_in = (size_t)(n_total - 1) * row_pitch + bins_of(h->cfg);
-    int16_t *d_i16 = nullptr;
-    float *d_f32 = nullptr;
-    hipError_t e = h->h_spec.grow(n_in);
-    if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_istft_batch: buffers", e);
-    jdsp::HostCall hc(ctx, "jdsp_istft_batch");
-    offs.upload(hc);
-    hc.upload_to(h->h_spec.get(), spec_host, n_in * sizeof(jdsp_c32));
-    if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the spans
-    if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
-    if (hc.ok())
-        hc.result(jdsp_istft_batch_dev(h, h->h_spec.get(), row_pitch, offs.d_sample, offs.d_unit, n_utts, n_total, d_i16,
-                                       d_f32));
-    h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
-    return hc.finish();
+    return ragged_host(h, nullptr, spec_host, row_pitch, nullptr, sample_first_host, frame_first_host, n_utts, n_samples,
+                       out_i16_host, out_f32_host);
 }
 
 // ---- live streams ---------------------------------------------------------------------------------------------------
@@ -222,26 +229,8 @@ int jdsp_istft_streams_dev(jdsp_istft *h, const jdsp_c32 *spec_dev, long row_pit
                            long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (int rc = h->live.check_count("jdsp_istft_streams", n_chunks)) return rc;
-    if (n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: n_frames_total < 0");
-    if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: row_pitch below the layout's bins");
-    if (!jdsp::aligned(spec_dev, 8) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
-        !jdsp::aligned(stream_id_dev, 8) || !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(frame_first_dev, 8))
-        return fail(ctx, JDSP_EINVAL,
-                    "jdsp_istft_streams: spec, out_f32, the stream ids and the offset arrays must be 8-byte, out_i16 "
-                    "4-byte aligned");
-    if (n_chunks == 0 || n_frames_total == 0) return JDSP_OK;
-    if (!spec_dev || !stream_id_dev || !sample_first_dev || !frame_first_dev)
-        return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: spec, stream_id, sample_first or frame_first is NULL");
-    if (!out_i16_dev && !out_f32_dev) return JDSP_OK;          // as the batch entry: nothing is done, no stream advances
-    if (jdsp::launch_istft_live(ctx->stream, ctx->n_cu, h->cfg.n_fft, h->cfg.hop, h->cfg.layout == JDSP_SPEC_HALF,
-                                reinterpret_cast<const float2 *>(spec_dev), row_pitch, n_frames_total,
-                                reinterpret_cast<const long long *>(sample_first_dev),
-                                reinterpret_cast<const long long *>(frame_first_dev), n_chunks, h->live.view(stream_id_dev),
-                                h->ws, h->ola.g, out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt))
-        return fail(ctx, JDSP_EHIP, "jdsp_istft_streams: launch", hipGetLastError());
-    return h->live.commit("jdsp_istft_streams", stream_id_dev, frame_first_dev, n_chunks);
+    return ragged_dev(h, &h->live, spec_dev, row_pitch, stream_id_dev, sample_first_dev, frame_first_dev, n_chunks,
+                      n_frames_total, out_i16_dev, out_f32_dev);
 }
 
 int jdsp_istft_streams_flush_dev(jdsp_istft *h, const int64_t *stream_id_dev, const int64_t *sample_first_dev, long n_ids,
@@ -256,42 +245,8 @@ int jdsp_istft_streams(jdsp_istft *h, const jdsp_c32 *spec_host, long row_pitch,
                        int16_t *out_i16_host, float *out_f32_host)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (int rc = h->live.check_count("jdsp_istft_streams", n_chunks)) return rc;
-    if (n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: n_samples < 0");
-    if (row_pitch < bins_of(h->cfg)) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: row_pitch below the layout's bins");
-    if (n_chunks > 0 && (!stream_id_host || !sample_first_host || !frame_first_host))
-        return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: stream_id, sample_first or frame_first is NULL");
-    if (int rc = h->live.check_ids("jdsp_istft_streams", stream_id_host, n_chunks)) return rc;
-    jdsp::RaggedOffsets offs;                                  // a chunk's span is its hop F_c output samples
-    if (offs.check(ctx, "jdsp_istft_streams", "frame_first", sample_first_host, frame_first_host, n_chunks, n_samples,
-                   h->cfg.hop, h->cfg.hop))
-        return JDSP_EINVAL;
-    const long n_total = offs.lay.n_total;
-    if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
-        if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
-        if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
-        return JDSP_OK;
-    }
-    if (!spec_host) return fail(ctx, JDSP_EINVAL, "jdsp_istft_streams: spec is NULL");
-    JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t n_in = (size_t)(n_total - 1) * row_pitch + bins_of(h->cfg);
-    int16_t *d_i16 = nullptr;
-    float *d_f32 = nullptr;
-    hipError_t e = h->h_spec.grow(n_in);
-    if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_istft_streams: buffers", e);
-    jdsp::HostCall hc(ctx, "jdsp_istft_streams");
-    offs.upload(hc);
-    const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_chunks * sizeof(int64_t));
-    hc.upload_to(h->h_spec.get(), spec_host, n_in * sizeof(jdsp_c32));
-    if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the written ranges
-    if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
-    if (hc.ok())
-        hc.result(jdsp_istft_streams_dev(h, h->h_spec.get(), row_pitch, d_id, offs.d_sample, offs.d_unit, n_chunks, n_total,
-                                         d_i16, d_f32));
-    h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
-    return hc.finish();
+    return ragged_host(h, &h->live, spec_host, row_pitch, stream_id_host, sample_first_host, frame_first_host, n_chunks,
+                       n_samples, out_i16_host, out_f32_host);
 }
 
 int jdsp_istft_streams_flush(jdsp_istft *h, const int64_t *stream_id_host, const int64_t *sample_first_host, long n_ids,

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(64, JDSP_ISTFT_RESIDENT) void istft_live_kernel(
     istft_run<N, HALF, R>(a, table, LiveSpan<N / R>(sample_first, frame_first, a.n_utts, stream_id, parity, live));
 }
 
-// ---- the state of live streams (jdsp::OlaStreams; the layout: LiveStreams, ragged_batch.h) ------------------------
+// ---- the state of live streams (jdsp::OlaStreams, ola_api.h; the layout: LiveStreams, jdsp_internal.h) -----------
 // flush of the listed streams: one workgroup per stream writes its n_tail samples, g[t mod hop] * s[t] and the same
 // cast, at sample_first[i] onwards and zeroes the tail behind it -- the stream is fresh again, its parity as it is.
 // Both outputs NULL: the reset of the listed streams.
@@ -328,7 +328,7 @@ static void launch_r(hipStream_t s, int r, long grid, const IstftArgs &a, const 
 
 static int launch_any(hipStream_t s, int n_cu, int n_fft, int hop, int half, IstftArgs a, const float2 *table,
                       int run_opt, const long long *sample_first, const long long *frame_first,
-                      const LiveStreams *live = nullptr)
+                      const LiveStreams *live)
 {
     const int r = n_fft / hop;
     const OlaRunPlan p = plan_ola_run(n_cu, JDSP_ISTFT_RESIDENT, r, a.n_frames, run_opt);
@@ -349,7 +349,7 @@ int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const fl
 {
     if (n_frames <= 0) return 0;
     const IstftArgs a = {spec, pitch, n_frames, 1, ws, g, out, out_f32, 0, tail_in, tail_out};
-    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, nullptr, nullptr);
+    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, nullptr, nullptr, nullptr);
 }
 
 int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32)
@@ -360,23 +360,14 @@ int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_t
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
-                       long n_frames_total, const long long *sample_first, const long long *frame_first, long n_utts,
-                       const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt)
+int launch_istft_ragged(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
+                        long n_frames_total, const long long *sample_first, const long long *frame_first, long n_spans,
+                        const LiveStreams *live, const float *ws, const float *g, short *out, float *out_f32,
+                        const float2 *table, int run_opt)
 {
-    if (n_frames_total <= 0 || n_utts <= 0) return 0;
-    const IstftArgs a = {spec, pitch, n_frames_total, n_utts, ws, g, out, out_f32, 0, nullptr, nullptr};
-    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, sample_first, frame_first);
-}
-
-int launch_istft_live(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
-                      long n_frames_total, const long long *sample_first, const long long *frame_first, long n_chunks,
-                      const LiveStreams &live, const float *ws, const float *g, short *out, float *out_f32,
-                      const float2 *table, int run_opt)
-{
-    if (n_frames_total <= 0 || n_chunks <= 0) return 0;
-    const IstftArgs a = {spec, pitch, n_frames_total, n_chunks, ws, g, out, out_f32, 0, nullptr, nullptr};
-    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, sample_first, frame_first, &live);
+    if (n_frames_total <= 0 || n_spans <= 0) return 0;
+    const IstftArgs a = {spec, pitch, n_frames_total, n_spans, ws, g, out, out_f32, 0, nullptr, nullptr};
+    return launch_any(s, n_cu, n_fft, hop, half, a, table, run_opt, sample_first, frame_first, live);
 }
 
 int launch_ola_streams_flush(hipStream_t s, const LiveStreams &live, long n_ids, const long long *sample_first,

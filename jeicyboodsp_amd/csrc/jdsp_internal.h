@@ -331,7 +331,7 @@ int launch_stft1024_half(hipStream_t stream, const short *pcm, long n_frames, fl
 int launch_stft512(hipStream_t stream, int n_cu, const short *pcm, long n_frames, long hop, float2 *spec,
                    const float2 *table, const float2 *win512);
 void fill_win512(float2 *w, int window_kind);
-// bins 0..512 of every frame of n_utts ragged utterances in one launch (the layout of launch_stftmask_batch): global
+// bins 0..512 of every frame of n_utts ragged utterances in one launch (the layout of launch_stftmask_ragged): global
 // frame j is the row spec + j pitch (pitch even); hop 1024 | 512 | 256; run_opt 0 = auto
 int launch_stft_half_batch(hipStream_t s, int hop, int run_opt, const short *pcm, const long long *sample_first,
                            const long long *frame_first, long n_utts, long n_frames_total, float2 *spec, long pitch,
@@ -466,12 +466,7 @@ int launch_istft(hipStream_t s, int n_cu, int n_fft, int hop, int half, const fl
                  const float *ws, const float *g, const float *tail_in, float *tail_out, short *out, float *out_f32,
                  const float2 *table, int run_opt);
 int launch_istft_flush(hipStream_t s, const float *tail, const float *g, int n_tail, int hop, short *out, float *out_f32);
-// n_utts independent streams in one launch, no tail in or out: the layout of launch_stftmask_batch with spectrum rows
-// where that has mask rows
-int launch_istft_batch(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
-                       long n_frames_total, const long long *sample_first, const long long *frame_first, long n_utts,
-                       const float *ws, const float *g, short *out, float *out_f32, const float2 *table, int run_opt);
-// The live streams of a handle as a kernel sees them (the host side: OlaStreams below).  Stream s keeps two tails of
+// The live streams of a handle as a kernel sees them (the host side: OlaStreams, ola_api.h).  Stream s keeps two tails of
 // n_tail = n - hop floats, tails[(p n_streams + s) n_tail ..) for p = 0, 1, and the word parity[s] says which of them
 // holds the partial sums the stream's next chunk starts from.  A transform launch only READS parity: every wave of it
 // sees the same value, loads from tail p and stores to tail p ^ 1, so the waves that read a chunk's carried tail (all
@@ -489,12 +484,13 @@ struct LiveStreams {
     long n_streams;
     int n_tail;
 };
-// the chunks of live streams in one launch: launch_istft_batch's layout with chunks for utterances; chunk c starts from
-// the tail of stream live.stream_id[c], writes its hop F_c samples and leaves the new tail in the stream's other buffer
-int launch_istft_live(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
-                      long n_frames_total, const long long *sample_first, const long long *frame_first, long n_chunks,
-                      const LiveStreams &live, const float *ws, const float *g, short *out, float *out_f32,
-                      const float2 *table, int run_opt);
+// n_spans independent streams in one launch, no tail in or out: the layout of launch_stftmask_ragged with spectrum rows
+// where that has mask rows.  live != NULL: the spans are chunks of live streams; chunk c starts from the tail of stream
+// live->stream_id[c], writes its hop F_c samples and leaves the new tail in the stream's other buffer
+int launch_istft_ragged(hipStream_t s, int n_cu, int n_fft, int hop, int half, const float2 *spec, long pitch,
+                        long n_frames_total, const long long *sample_first, const long long *frame_first, long n_spans,
+                        const LiveStreams *live, const float *ws, const float *g, short *out, float *out_f32,
+                        const float2 *table, int run_opt);
 // the n_tail samples of the n_ids listed streams (live.stream_id) to sample_first[i] onwards, their tails zeroed behind
 // them; out and out_f32 both NULL (sample_first is then not read): the reset of those streams
 int launch_ola_streams_flush(hipStream_t s, const LiveStreams &live, long n_ids, const long long *sample_first,
@@ -502,12 +498,6 @@ int launch_ola_streams_flush(hipStream_t s, const LiveStreams &live, long n_ids,
 // parity[stream_id[c]] ^= 1 for the chunks with frames
 int launch_ola_streams_commit(hipStream_t s, const long long *stream_id, const long long *frame_first, long n_chunks,
                               int *parity);
-// as launch_stftmask_batch, over chunks of live streams (launch_istft_live)
-int launch_stftmask_live(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
-                         long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
-                         long n_chunks, const LiveStreams &live, const float *wa, const float *ws, const float *g,
-                         short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
-                         unsigned int *count, unsigned int epoch);
 // stftmask_kernels.hip (n_fft 1024)
 // mask: rows of float or float2 (complex_mask), pitch elements apart (0: one row); wa: [1024] analysis window / 2;
 // ws: [1024] synthesis window; g: [hop] emission gain; tails: [1024 - hop] floats; run_opt 0 = auto.  For the frames
@@ -518,14 +508,14 @@ int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const sh
                     long n_frames, const float *wa, const float *ws, const float *g, const float *tail_in,
                     float *tail_out, short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
                     unsigned int *count, unsigned int epoch);
-// n_utts independent streams in one launch, no tail in or out: utterance u is the frames (= mask rows) frame_first[u] ..
+// n_spans independent streams in one launch, no tail in or out: utterance u is the frames (= mask rows) frame_first[u] ..
 // frame_first[u + 1] - 1 of n_frames_total and reads and writes from sample sample_first[u] (even) of pcm and out on
-// (device arrays, [n_utts] and [n_utts + 1])
-int launch_stftmask_batch(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
-                          long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
-                          long n_utts, const float *wa, const float *ws, const float *g, short *out, float *out_f32,
-                          const float2 *table, int run_opt, const double *f64, unsigned int *count,
-                          unsigned int epoch);
+// (device arrays, [n_spans] and [n_spans + 1]).  live != NULL: the spans are chunks of live streams, as launch_istft_ragged's
+int launch_stftmask_ragged(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
+                           long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
+                           long n_spans, const LiveStreams *live, const float *wa, const float *ws, const float *g,
+                           short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
+                           unsigned int *count, unsigned int epoch);
 // mfcc_kernels.hip
 // ---- GMM / HMM (gmm_kernels.hip) ----
 // packed per-GMM record (doubles): alpa[4], mean[4][4], var[4][4], coef[4][4], eig[4][12][4], and for the
@@ -556,244 +546,6 @@ int launch_gmm_train(hipStream_t s, int threads, int n_classes, const double *fe
                      const long long *file_first, const int *file_class, long n_files, int kmeans_max_passes,
                      GmmTrainState *state, unsigned char *sel, double *wbuf);
 int launch_gmm_train_params(hipStream_t s, int n_classes, const GmmTrainState *state, jdsp_gmm_train_param *out);
-
-// What a jdsp_istft or jdsp_stftmask handle carries of its overlap-add output stream between calls (the kernels' side
-// and the stream's rules: ola_stream.h): the emission gain, the ping-pong tail, the "frames_per_wave" option and the
-// host entries' output staging.  `entry` is the calling entry's name, the prefix of its messages.
-struct OlaStream {
-    jdsp_ctx *ctx = nullptr;
-    int n = 0, hop = 0;
-    float *g = nullptr, *tail[2] = {nullptr, nullptr};   // views into the handle's blob: g[hop], tail[2][n]
-    int cur = 0;                          // tail[cur] holds the partial sums the next call starts from
-    int run_opt = 0;                      // "frames_per_wave": 0 = auto
-    // host entry points' device buffers, grown on demand (those entries end with a synchronise: none is in use then)
-    DevBuf<int16_t> h_i16;
-    DevBuf<float> h_f32;
-
-    // "stft.window"'s formulas (fill_stft1024_table / fill_win512): PI 3.141592 as the reference writes it
-    static double window_at(int kind, int i, int n)
-    {
-        if (kind == JDSP_WIN_NONE) return 1.0;
-        const double a = kind == JDSP_WIN_HANN ? 0.5 : 0.54, b = kind == JDSP_WIN_HANN ? 0.5 : 0.46;
-        return a - b * cos(2 * 3.141592 * i / (n - 1));
-    }
-    // WOLA: gain[i] = 1 / sum_r w_a[i + r hop] w_s[i + r hop], i < hop; 1 when not normalising.  false: the windows'
-    // overlap-add vanishes somewhere (no WOLA inverse), for the caller to report
-    static bool wola_gain(int wa_kind, int ws_kind, int n, int hop, bool normalise, float *gain)
-    {
-        std::vector<double> den((size_t)hop, 1.0);
-        if (normalise) {
-            double mx = 0;
-            for (int i = 0; i < hop; i++) {
-                double s = 0;
-                for (int r = 0; r < n / hop; r++)
-                    s += window_at(wa_kind, i + r * hop, n) * window_at(ws_kind, i + r * hop, n);
-                den[i] = s;
-                mx = s > mx ? s : mx;
-            }
-            for (int i = 0; i < hop; i++)
-                if (!(den[i] >= 1e-6 * mx)) return false;
-        }
-        for (int i = 0; i < hop; i++) gain[i] = (float)(1.0 / den[i]);
-        return true;
-    }
-    // the stream's share of the handle's blob, the gain first
-    static size_t floats(int n, int hop) { return (size_t)hop + 2 * (size_t)n; }
-    void attach(jdsp_ctx *c, int n_fft, int hop_len, float *base)
-    {
-        ctx = c, n = n_fft, hop = hop_len;
-        g = base, tail[0] = g + hop, tail[1] = tail[0] + n;
-    }
-    long least_run() const { return n / hop > 1 ? n / hop - 1 : 1; }     // max(R - 1, 1): the halo stays above frame 0
-    long samples_out(long n_frames) const { return n_frames < 0 ? 0 : n_frames * hop; }
-    int reset()
-    {
-        JDSP_HIP(ctx, hipMemsetAsync(tail[0], 0, 2 * (size_t)n * sizeof(float), ctx->stream));
-        cur = 0;
-        return JDSP_OK;
-    }
-    // before the handle is deleted: the stream's work on its memory is done
-    void drain() const
-    {
-        (void)hipSetDevice(ctx->device);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    // the n - hop samples still in the tail (g[t mod hop] * s[t], the same cast), then the reset
-    int flush_dev(const char *entry, int16_t *out_i16_dev, float *out_f32_dev)
-    {
-        const std::string e(entry);
-        if (!aligned(out_i16_dev, 4) || !aligned(out_f32_dev, 8))
-            return fail(ctx, JDSP_EINVAL, (e + ": out_i16 must be 4-byte, out_f32 8-byte aligned").c_str());
-        if (launch_istft_flush(ctx->stream, tail[cur], g, n - hop, hop, out_i16_dev, out_f32_dev))
-            return fail(ctx, JDSP_EHIP, (e + ": launch").c_str(), hipGetLastError());
-        return reset();
-    }
-    // The output half of a host entry: device staging for n_samples of each output the caller wants (d_* NULL where
-    // it wants none, or for no samples), and after the *_dev call the copies back.
-    hipError_t stage_out(size_t n_samples, const void *want_i16, const void *want_f32, int16_t *&d_i16, float *&d_f32)
-    {
-        hipError_t e = hipSuccess;
-        if (n_samples && want_i16) e = h_i16.grow(n_samples);
-        if (e == hipSuccess && n_samples && want_f32) e = h_f32.grow(n_samples);
-        d_i16 = n_samples && want_i16 ? h_i16.get() : nullptr;
-        d_f32 = n_samples && want_f32 ? h_f32.get() : nullptr;
-        return e;
-    }
-    void download_out(HostCall &hc, size_t n_samples, int16_t *out_i16_host, float *out_f32_host) const
-    {
-        hc.download(out_i16_host, h_i16.get(), n_samples * sizeof(int16_t));
-        hc.download(out_f32_host, h_f32.get(), n_samples * sizeof(float));
-    }
-    int flush(const char *entry, int16_t *out_i16_host, float *out_f32_host)
-    {
-        const size_t n_tail = (size_t)(n - hop);
-        JDSP_HIP(ctx, hipSetDevice(ctx->device));
-        int16_t *d_i16;
-        float *d_f32;
-        const hipError_t e = stage_out(n_tail, out_i16_host, out_f32_host, d_i16, d_f32);
-        if (e != hipSuccess) return fail(ctx, JDSP_EHIP, (std::string(entry) + ": buffers").c_str(), e);
-        HostCall hc(ctx, entry);
-        hc.result(flush_dev(entry, d_i16, d_f32));
-        download_out(hc, n_tail, out_i16_host, out_f32_host);
-        return hc.finish();
-    }
-};
-
-// The live streams of a jdsp_istft or jdsp_stftmask handle (jdsp_*_streams_*), next to its own OlaStream: n_streams
-// tails carried from call to call, of which one call advances any subset by a chunk of frames each in one launch
-// (LiveStreams above, LiveSpan in ragged_batch.h).  Nothing here is read or written by the handle's own stream or by
-// the stateless batch entries.  `entry` is the calling entry's name, the prefix of its messages.
-struct OlaStreams {
-    OlaStream *ola = nullptr;             // the handle's own: the context, n, hop, the gain and the output staging
-    long n_streams = 0;                   // 0: not reserved
-    DevBuf<float> tails;                  // [2][n_streams][n - hop]
-    DevBuf<int> parity;                   // [n_streams]
-
-    int n_tail() const { return ola->n - ola->hop; }
-    LiveStreams view(const int64_t *stream_id_dev) const
-    {
-        return {reinterpret_cast<const long long *>(stream_id_dev), parity.get(), tails.get(), n_streams, n_tail()};
-    }
-    int closed(const char *entry) const
-    {
-        return fail(ola->ctx, JDSP_EINVAL, (std::string(entry) + ": no live streams (call _streams_reserve first)").c_str());
-    }
-    // the only call that allocates; every stream is fresh afterwards
-    int reserve(const char *entry, long n)
-    {
-        jdsp_ctx *ctx = ola->ctx;
-        const std::string e(entry);
-        if (n < 1) return fail(ctx, JDSP_EINVAL, (e + ": n_streams must be >= 1").c_str());
-        JDSP_HIP(ctx, hipSetDevice(ctx->device));
-        JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));      // nothing enqueued still uses the old buffers
-        n_streams = 0;
-        const size_t n_floats = 2 * (size_t)n * (size_t)n_tail();
-        hipError_t err = tails.alloc(n_floats ? n_floats : 1);
-        if (err == hipSuccess) err = parity.alloc((size_t)n);
-        if (err == hipSuccess) err = hipMemsetAsync(tails.get(), 0, tails.count() * sizeof(float), ctx->stream);
-        if (err == hipSuccess) err = hipMemsetAsync(parity.get(), 0, (size_t)n * sizeof(int), ctx->stream);
-        if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-        if (err != hipSuccess) {
-            tails.reset();
-            parity.reset();
-            return fail(ctx, err == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, (e + ": buffers").c_str(), err);
-        }
-        n_streams = n;
-        return JDSP_OK;
-    }
-    // the checks every entry over a list of ids makes before anything else: reserved, 0 <= n_ids <= n_streams
-    int check_count(const char *entry, long n_ids) const
-    {
-        if (!n_streams) return closed(entry);
-        const std::string e(entry);
-        if (n_ids < 0) return fail(ola->ctx, JDSP_EINVAL, (e + ": a count is < 0").c_str());
-        if (n_ids > n_streams)
-            return fail(ola->ctx, JDSP_EINVAL, (e + ": more ids than live streams (ids are distinct within a call)").c_str());
-        return JDSP_OK;
-    }
-    // host arrays only: every id in range, none twice
-    int check_ids(const char *entry, const int64_t *stream_id_host, long n_ids) const
-    {
-        const StreamIdVerdict v = stream_ids_check(stream_id_host, n_ids, n_streams);
-        return v == StreamIdVerdict::kOk ? JDSP_OK : fail(ola->ctx, JDSP_EINVAL, stream_ids_message(v, entry).c_str());
-    }
-    // the listed streams fresh again; stream_id_dev NULL: all of them
-    int reset_dev(const char *entry, const int64_t *stream_id_dev, long n_ids)
-    {
-        jdsp_ctx *ctx = ola->ctx;
-        if (!n_streams) return closed(entry);
-        const std::string e(entry);
-        if (!stream_id_dev) {
-            JDSP_HIP(ctx, hipMemsetAsync(tails.get(), 0, tails.count() * sizeof(float), ctx->stream));
-            JDSP_HIP(ctx, hipMemsetAsync(parity.get(), 0, (size_t)n_streams * sizeof(int), ctx->stream));
-            return JDSP_OK;
-        }
-        if (int rc = check_count(entry, n_ids)) return rc;
-        if (!aligned(stream_id_dev, 8)) return fail(ctx, JDSP_EINVAL, (e + ": stream_id must be 8-byte aligned").c_str());
-        if (launch_ola_streams_flush(ctx->stream, view(stream_id_dev), n_ids, nullptr, ola->g, ola->hop, nullptr, nullptr))
-            return fail(ctx, JDSP_EHIP, (e + ": launch").c_str(), hipGetLastError());
-        return JDSP_OK;
-    }
-    // the n - hop samples still in each listed stream's tail, at sample_first[i] onwards, then its reset
-    int flush_dev(const char *entry, const int64_t *stream_id_dev, const int64_t *sample_first_dev, long n_ids,
-                  int16_t *out_i16_dev, float *out_f32_dev)
-    {
-        jdsp_ctx *ctx = ola->ctx;
-        if (int rc = check_count(entry, n_ids)) return rc;
-        const std::string e(entry);
-        if (!aligned(stream_id_dev, 8) || !aligned(sample_first_dev, 8) || !aligned(out_i16_dev, 4) || !aligned(out_f32_dev, 8))
-            return fail(ctx, JDSP_EINVAL,
-                        (e + ": stream_id, sample_first and out_f32 must be 8-byte, out_i16 4-byte aligned").c_str());
-        if (n_ids == 0) return JDSP_OK;
-        if (!stream_id_dev || ((out_i16_dev || out_f32_dev) && !sample_first_dev))
-            return fail(ctx, JDSP_EINVAL, (e + ": stream_id or sample_first is NULL").c_str());
-        if (launch_ola_streams_flush(ctx->stream, view(stream_id_dev), n_ids,
-                                     reinterpret_cast<const long long *>(sample_first_dev), ola->g, ola->hop, out_i16_dev,
-                                     out_f32_dev))
-            return fail(ctx, JDSP_EHIP, (e + ": launch").c_str(), hipGetLastError());
-        return JDSP_OK;
-    }
-    // behind the transform launch over the chunks: the streams that were given frames carry their new tails
-    int commit(const char *entry, const int64_t *stream_id_dev, const int64_t *frame_first_dev, long n_chunks)
-    {
-        if (launch_ola_streams_commit(ola->ctx->stream, reinterpret_cast<const long long *>(stream_id_dev),
-                                      reinterpret_cast<const long long *>(frame_first_dev), n_chunks, parity.get()))
-            return fail(ola->ctx, JDSP_EHIP, (std::string(entry) + ": commit launch").c_str(), hipGetLastError());
-        return JDSP_OK;
-    }
-    // host pointers, synchronous: checks the ids and the n - hop long spans (even, ascending, disjoint, inside
-    // n_samples); the outputs are n_samples long and zero outside the spans
-    int flush(const char *entry, const int64_t *stream_id_host, const int64_t *sample_first_host, long n_ids,
-              long n_samples, int16_t *out_i16_host, float *out_f32_host)
-    {
-        jdsp_ctx *ctx = ola->ctx;
-        if (int rc = check_count(entry, n_ids)) return rc;
-        const std::string e(entry);
-        if (n_samples < 0) return fail(ctx, JDSP_EINVAL, (e + ": n_samples < 0").c_str());
-        if (n_ids > 0 && (!stream_id_host || !sample_first_host))
-            return fail(ctx, JDSP_EINVAL, (e + ": stream_id or sample_first is NULL").c_str());
-        if (int rc = check_ids(entry, stream_id_host, n_ids)) return rc;
-        std::vector<int64_t> unit((size_t)n_ids + 1);
-        for (long i = 0; i <= n_ids; i++) unit[(size_t)i] = i;
-        const int nt = n_tail();
-        const RaggedLayout lay = ragged_layout_check(sample_first_host, unit.data(), n_ids, n_samples, nt, nt ? nt : 1);
-        if (lay.verdict != RaggedVerdict::kOk)
-            return fail(ctx, JDSP_EINVAL, ragged_layout_message(lay.verdict, entry, "stream_id").c_str());
-        JDSP_HIP(ctx, hipSetDevice(ctx->device));
-        int16_t *d_i16 = nullptr;
-        float *d_f32 = nullptr;
-        const hipError_t err = ola->stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
-        if (err != hipSuccess) return fail(ctx, JDSP_EHIP, (e + ": buffers").c_str(), err);
-        HostCall hc(ctx, entry);
-        const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_ids * sizeof(int64_t));
-        const int64_t *d_sf = hc.upload(sample_first_host, (size_t)n_ids * sizeof(int64_t));
-        if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));
-        if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
-        if (hc.ok()) hc.result(flush_dev(entry, d_id, d_sf, n_ids, d_i16, d_f32));
-        ola->download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
-        return hc.finish();
-    }
-};
 
 }  // namespace jdsp
 

@@ -1,7 +1,7 @@
 // ola_stream.h -- the overlap-add output stream of the streaming synthesis kernels: istft_run (istft_kernels.hip, the
 // body under istft_run_kernel and istft_batch_kernel) and stftmask_run_kernel / stftmask_batch_kernel
 // (stftmask_kernels.hip) compute a windowed frame in their own way and hand it to the one stream defined here.  Its host side, what a handle carries from call to
-// call, is jdsp::OlaStream (jdsp_internal.h).
+// call, is jdsp::OlaStream (ola_api.h).
 //
 // One wave per run of consecutive frames (persistent: the launch picks the run so that the batch is about one round of
 // resident waves, in XCD-aware order, as denoise_run_kernel).  Lane l holds frame samples 2 l + 128 d, +1 (n = 1024, one

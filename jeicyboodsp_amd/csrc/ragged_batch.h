@@ -13,6 +13,9 @@
 // one span [0, n_frames) at sample 0 whose tail is carried by the handle instead of leaving from the registers -- under
 // which the same body (istft_run) is istft_run_kernel.  LiveSpan is RaggedSpan over the chunks of live streams: a span
 // that starts from a tail carried in memory and ends by writing the tail back (stftmask_live_kernel, istft_live_kernel).
+// Bodies: istft_run is all three synthesis kernels; stftmask_ragged is stftmask_batch_kernel and stftmask_live_kernel
+// (stftmask_run_kernel keeps a loop of its own); stft_half_batch_kernel has its own.  The host side of the entries that
+// launch them, for the two handles with an overlap-add output stream, is the ragged call layer of ola_api.h.
 #pragma once
 
 namespace jdsp {

@@ -1,5 +1,5 @@
 // stftmask_api.hip -- C ABI of the fused STFT masking stream object (include/jdsp.h, jdsp_stftmask_*).
-#include "jdsp_internal.h"
+#include "ola_api.h"
 
 using jdsp::fail;
 using jdsp::OlaStream;
@@ -33,6 +33,66 @@ struct jdsp_stftmask {
 static constexpr int kBins = 513;         // n/2 + 1 of the one supported n_fft
 
 static size_t mask_elem(const jdsp_stftmask *h) { return h->cfg.mask_kind == JDSP_MASK_COMPLEX ? sizeof(jdsp_c32) : sizeof(float); }
+
+// what the handle checks of the inputs of a ragged call itself (jdsp::OwnRules, ola_api.h)
+static jdsp::OwnRules own_rules(const jdsp_stftmask *h, const void *pcm, const void *mask, long mask_pitch)
+{
+    jdsp::OwnRules own;
+    if (mask_pitch != 0 && mask_pitch < kBins) own.pitch = "mask_pitch must be 0 (one row) or >= n_fft/2 + 1";
+    if (!jdsp::aligned(pcm, 4) || !jdsp::aligned(mask, mask_elem(h)))
+        own.align = "pcm must be 4-byte aligned, the mask 4-byte (REAL) or 8-byte (COMPLEX)";
+    if (!pcm || !mask) own.null = "pcm or mask is NULL";
+    return own;
+}
+
+// jdsp_stftmask_batch_dev (live == NULL) and jdsp_stftmask_streams_dev
+static int ragged_dev(jdsp_stftmask *h, jdsp::OlaStreams *live, const int16_t *pcm_dev, const void *mask_dev,
+                      long mask_pitch, const int64_t *stream_id_dev, const int64_t *sample_first_dev,
+                      const int64_t *frame_first_dev, long n, long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev)
+{
+    jdsp_ctx *ctx = h->ctx;
+    const char *entry = live ? "jdsp_stftmask_streams" : "jdsp_stftmask_batch";
+    switch (jdsp::ragged_call_check(ctx, live, entry, own_rules(h, pcm_dev, mask_dev, mask_pitch), stream_id_dev,
+                                    sample_first_dev, frame_first_dev, n, n_frames_total, out_i16_dev, out_f32_dev)) {
+    case jdsp::RaggedCall::kRejected: return JDSP_EINVAL;
+    case jdsp::RaggedCall::kNothing: h->count_valid = 0; return JDSP_OK;   // a call of no frames recomputed none
+    case jdsp::RaggedCall::kLaunch: break;
+    }
+    jdsp::LiveStreams view;
+    if (live) view = live->view(stream_id_dev);
+    if (jdsp::launch_stftmask_ragged(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev,
+                                     mask_dev, mask_pitch, n_frames_total,
+                                     reinterpret_cast<const long long *>(sample_first_dev),
+                                     reinterpret_cast<const long long *>(frame_first_dev), n, live ? &view : nullptr, h->wa,
+                                     h->ws, h->ola.g, out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt,
+                                     h->f64.get(), h->count.get(), h->next_epoch()))
+        return fail(ctx, JDSP_EHIP, (std::string(entry) + ": launch").c_str(), hipGetLastError());
+    return live ? live->commit(entry, stream_id_dev, frame_first_dev, n) : JDSP_OK;
+}
+
+// jdsp_stftmask_batch (live == NULL) and jdsp_stftmask_streams
+static int ragged_host(jdsp_stftmask *h, jdsp::OlaStreams *live, const int16_t *pcm_host, long n_samples,
+                       const void *mask_host, long mask_pitch, const int64_t *stream_id_host,
+                       const int64_t *sample_first_host, const int64_t *frame_first_host, long n, int16_t *out_i16_host,
+                       float *out_f32_host)
+{
+    return jdsp::ragged_host_call(
+        h->ola, live, live ? "jdsp_stftmask_streams" : "jdsp_stftmask_batch", own_rules(h, pcm_host, mask_host, mask_pitch),
+        stream_id_host, sample_first_host, frame_first_host, n, n_samples, h->cfg.n_fft, out_i16_host, out_f32_host,
+        [&](jdsp::HostCall &hc, long n_total, long end) {
+            const size_t mask_bytes = ((size_t)(n_total - 1) * mask_pitch + kBins) * mask_elem(h);
+            hipError_t e = h->h_pcm.grow((size_t)n_samples);
+            if (e == hipSuccess) e = h->h_mask.grow(mask_bytes);
+            if (e != hipSuccess) return e;
+            hc.upload_to(h->h_pcm.get(), pcm_host, (size_t)end * sizeof(int16_t));   // nothing past the last span is read
+            hc.upload_to(h->h_mask.get(), mask_host, mask_bytes);
+            return hipSuccess;
+        },
+        [&](const int64_t *d_id, const int64_t *d_sample, const int64_t *d_frame, long n_total, int16_t *d_i16, float *d_f32) {
+            return ragged_dev(h, live, h->h_pcm.get(), h->h_mask.get(), mask_pitch, d_id, d_sample, d_frame, n, n_total,
+                              d_i16, d_f32);
+        });
+}
 
 extern "C" {
 
@@ -212,34 +272,8 @@ int jdsp_stftmask_batch_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void
                             long n_frames_total, int16_t *out_i16_dev, float *out_f32_dev)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (n_utts < 0 || n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: n_utts or n_frames_total < 0");
-    if (mask_pitch != 0 && mask_pitch < kBins)
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: mask_pitch must be 0 (one row) or >= n_fft/2 + 1");
-    if (!jdsp::aligned(pcm_dev, 4) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
-        !jdsp::aligned(mask_dev, mask_elem(h)) || !jdsp::aligned(sample_first_dev, 8) ||
-        !jdsp::aligned(frame_first_dev, 8))
-        return fail(ctx, JDSP_EINVAL,
-                    "jdsp_stftmask_batch: pcm and out_i16 must be 4-byte, out_f32 and the offset arrays 8-byte aligned, "
-                    "the mask 4-byte (REAL) or 8-byte (COMPLEX)");
-    if (n_utts == 0 || n_frames_total == 0) {
-        h->count_valid = 0;
-        return JDSP_OK;
-    }
-    if (!pcm_dev || !mask_dev || !sample_first_dev || !frame_first_dev)
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: pcm, mask, sample_first or frame_first is NULL");
-    if (!out_i16_dev && !out_f32_dev) {                        // no stream to advance: nothing to do
-        h->count_valid = 0;
-        return JDSP_OK;
-    }
-    if (jdsp::launch_stftmask_batch(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev,
-                                    mask_dev, mask_pitch, n_frames_total,
-                                    reinterpret_cast<const long long *>(sample_first_dev),
-                                    reinterpret_cast<const long long *>(frame_first_dev), n_utts, h->wa, h->ws, h->ola.g,
-                                    out_i16_dev, out_f32_dev, ctx->stft1024_table.get(), h->ola.run_opt, h->f64.get(),
-                                    h->count.get(), h->next_epoch()))
-        return fail(ctx, JDSP_EHIP, "jdsp_stftmask_batch: launch", hipGetLastError());
-    return JDSP_OK;
+    return ragged_dev(h, nullptr, pcm_dev, mask_dev, mask_pitch, nullptr, sample_first_dev, frame_first_dev, n_utts,
+                      n_frames_total, out_i16_dev, out_f32_dev);
 }
 
 int jdsp_stftmask_batch(jdsp_stftmask *h, const int16_t *pcm_host, long n_samples, const void *mask_host, long mask_pitch,
@@ -247,42 +281,8 @@ int jdsp_stftmask_batch(jdsp_stftmask *h, const int16_t *pcm_host, long n_sample
                         int16_t *out_i16_host, float *out_f32_host)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: n_utts or n_samples < 0");
-    if (mask_pitch != 0 && mask_pitch < kBins)
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: mask_pitch must be 0 (one row) or >= n_fft/2 + 1");
-    if (n_utts > 0 && (!sample_first_host || !frame_first_host))
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: sample_first or frame_first is NULL");
-    jdsp::RaggedOffsets offs;
-    if (offs.check(ctx, "jdsp_stftmask_batch", "frame_first", sample_first_host, frame_first_host, n_utts, n_samples,
-                   h->cfg.n_fft, h->cfg.hop))
-        return JDSP_EINVAL;
-    const long n_total = offs.lay.n_total;
-    if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
-        if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
-        if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
-        return JDSP_OK;
-    }
-    if (!pcm_host || !mask_host) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_batch: pcm or mask is NULL");
-    JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t mask_bytes = ((size_t)(n_total - 1) * mask_pitch + kBins) * mask_elem(h);
-    int16_t *d_i16 = nullptr;
-    float *d_f32 = nullptr;
-    hipError_t e = h->h_pcm.grow((size_t)n_samples);
-    if (e == hipSuccess) e = h->h_mask.grow(mask_bytes);
-    if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_stftmask_batch: buffers", e);
-    jdsp::HostCall hc(ctx, "jdsp_stftmask_batch");
-    offs.upload(hc);
-    hc.upload_to(h->h_pcm.get(), pcm_host, (size_t)offs.lay.end * sizeof(int16_t));   // nothing past the last span is read
-    hc.upload_to(h->h_mask.get(), mask_host, mask_bytes);
-    if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the spans
-    if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
-    if (hc.ok())
-        hc.result(jdsp_stftmask_batch_dev(h, h->h_pcm.get(), h->h_mask.get(), mask_pitch, offs.d_sample, offs.d_unit, n_utts,
-                                          n_total, d_i16, d_f32));
-    h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
-    return hc.finish();
+    return ragged_host(h, nullptr, pcm_host, n_samples, mask_host, mask_pitch, nullptr, sample_first_host, frame_first_host,
+                       n_utts, out_i16_host, out_f32_host);
 }
 
 // ---- live streams ---------------------------------------------------------------------------------------------------
@@ -303,36 +303,8 @@ int jdsp_stftmask_streams_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const vo
                               float *out_f32_dev)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (int rc = h->live.check_count("jdsp_stftmask_streams", n_chunks)) return rc;
-    if (n_frames_total < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: n_frames_total < 0");
-    if (mask_pitch != 0 && mask_pitch < kBins)
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: mask_pitch must be 0 (one row) or >= n_fft/2 + 1");
-    if (!jdsp::aligned(pcm_dev, 4) || !jdsp::aligned(out_i16_dev, 4) || !jdsp::aligned(out_f32_dev, 8) ||
-        !jdsp::aligned(mask_dev, mask_elem(h)) || !jdsp::aligned(stream_id_dev, 8) ||
-        !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(frame_first_dev, 8))
-        return fail(ctx, JDSP_EINVAL,
-                    "jdsp_stftmask_streams: pcm and out_i16 must be 4-byte, out_f32, the stream ids and the offset arrays "
-                    "8-byte aligned, the mask 4-byte (REAL) or 8-byte (COMPLEX)");
-    if (n_chunks == 0 || n_frames_total == 0) {
-        h->count_valid = 0;
-        return JDSP_OK;
-    }
-    if (!pcm_dev || !mask_dev || !stream_id_dev || !sample_first_dev || !frame_first_dev)
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: pcm, mask, stream_id, sample_first or frame_first is NULL");
-    if (!out_i16_dev && !out_f32_dev) {                        // as the batch entry: nothing is done, no stream advances
-        h->count_valid = 0;
-        return JDSP_OK;
-    }
-    if (jdsp::launch_stftmask_live(ctx->stream, ctx->n_cu, h->cfg.hop, h->cfg.mask_kind == JDSP_MASK_COMPLEX, pcm_dev,
-                                   mask_dev, mask_pitch, n_frames_total,
-                                   reinterpret_cast<const long long *>(sample_first_dev),
-                                   reinterpret_cast<const long long *>(frame_first_dev), n_chunks,
-                                   h->live.view(stream_id_dev), h->wa, h->ws, h->ola.g, out_i16_dev, out_f32_dev,
-                                   ctx->stft1024_table.get(), h->ola.run_opt, h->f64.get(), h->count.get(),
-                                   h->next_epoch()))
-        return fail(ctx, JDSP_EHIP, "jdsp_stftmask_streams: launch", hipGetLastError());
-    return h->live.commit("jdsp_stftmask_streams", stream_id_dev, frame_first_dev, n_chunks);
+    return ragged_dev(h, &h->live, pcm_dev, mask_dev, mask_pitch, stream_id_dev, sample_first_dev, frame_first_dev, n_chunks,
+                      n_frames_total, out_i16_dev, out_f32_dev);
 }
 
 int jdsp_stftmask_streams_flush_dev(jdsp_stftmask *h, const int64_t *stream_id_dev, const int64_t *sample_first_dev,
@@ -348,45 +320,8 @@ int jdsp_stftmask_streams(jdsp_stftmask *h, const int16_t *pcm_host, long n_samp
                           const int64_t *frame_first_host, long n_chunks, int16_t *out_i16_host, float *out_f32_host)
 {
     if (!h) return JDSP_EINVAL;
-    jdsp_ctx *ctx = h->ctx;
-    if (int rc = h->live.check_count("jdsp_stftmask_streams", n_chunks)) return rc;
-    if (n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: n_samples < 0");
-    if (mask_pitch != 0 && mask_pitch < kBins)
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: mask_pitch must be 0 (one row) or >= n_fft/2 + 1");
-    if (n_chunks > 0 && (!stream_id_host || !sample_first_host || !frame_first_host))
-        return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: stream_id, sample_first or frame_first is NULL");
-    if (int rc = h->live.check_ids("jdsp_stftmask_streams", stream_id_host, n_chunks)) return rc;
-    jdsp::RaggedOffsets offs;
-    if (offs.check(ctx, "jdsp_stftmask_streams", "frame_first", sample_first_host, frame_first_host, n_chunks, n_samples,
-                   h->cfg.n_fft, h->cfg.hop))
-        return JDSP_EINVAL;
-    const long n_total = offs.lay.n_total;
-    if (n_total == 0 || (!out_i16_host && !out_f32_host)) {    // nothing to launch: the outputs are zero everywhere
-        if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
-        if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
-        return JDSP_OK;
-    }
-    if (!pcm_host || !mask_host) return fail(ctx, JDSP_EINVAL, "jdsp_stftmask_streams: pcm or mask is NULL");
-    JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t mask_bytes = ((size_t)(n_total - 1) * mask_pitch + kBins) * mask_elem(h);
-    int16_t *d_i16 = nullptr;
-    float *d_f32 = nullptr;
-    hipError_t e = h->h_pcm.grow((size_t)n_samples);
-    if (e == hipSuccess) e = h->h_mask.grow(mask_bytes);
-    if (e == hipSuccess) e = h->ola.stage_out((size_t)n_samples, out_i16_host, out_f32_host, d_i16, d_f32);
-    if (e != hipSuccess) return fail(ctx, JDSP_EHIP, "jdsp_stftmask_streams: buffers", e);
-    jdsp::HostCall hc(ctx, "jdsp_stftmask_streams");
-    offs.upload(hc);
-    const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_chunks * sizeof(int64_t));
-    hc.upload_to(h->h_pcm.get(), pcm_host, (size_t)offs.lay.end * sizeof(int16_t));   // nothing past the last span is read
-    hc.upload_to(h->h_mask.get(), mask_host, mask_bytes);
-    if (d_i16) hc.zero(d_i16, (size_t)n_samples * sizeof(int16_t));            // outside the written ranges
-    if (d_f32) hc.zero(d_f32, (size_t)n_samples * sizeof(float));
-    if (hc.ok())
-        hc.result(jdsp_stftmask_streams_dev(h, h->h_pcm.get(), h->h_mask.get(), mask_pitch, d_id, offs.d_sample, offs.d_unit,
-                                            n_chunks, n_total, d_i16, d_f32));
-    h->ola.download_out(hc, (size_t)n_samples, out_i16_host, out_f32_host);
-    return hc.finish();
+    return ragged_host(h, &h->live, pcm_host, n_samples, mask_host, mask_pitch, stream_id_host, sample_first_host,
+                       frame_first_host, n_chunks, out_i16_host, out_f32_host);
 }
 
 int jdsp_stftmask_streams_flush(jdsp_stftmask *h, const int64_t *stream_id_host, const int64_t *sample_first_host,

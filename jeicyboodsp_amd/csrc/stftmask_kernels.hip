@@ -399,7 +399,8 @@ int launch_stftmask(hipStream_t s, int n_cu, int hop, int complex_mask, const sh
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// ---- a batch of independent streams (utterances) in one launch (jdsp_stftmask_batch_*) ----------------------------
+// ---- a batch of independent streams (utterances), or the chunks of live streams, in one launch ---------------------
+// (jdsp_stftmask_batch_*, jdsp_stftmask_streams_*)
 // The waves are planned over the CONCATENATED frame axis: wave w owns the global frames [w run, (w + 1) run) whatever
 // the utterances' lengths are, so the plan is plan_ola_run's host arithmetic on the total alone.  Global frame j is
 // mask row j; it belongs to utterance u with frame_first[u] <= j < frame_first[u + 1] and starts at the sample
@@ -424,10 +425,17 @@ struct StftMaskBatchArgs {
     StftMaskF64 f64;
 };
 
-template <int R, int CPX>
-__global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_kernel(
-    StftMaskBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
-    const long long *__restrict__ frame_first)
+// The frame loop of stftmask_batch_kernel and stftmask_live_kernel, over RaggedSpan and LiveSpan (ragged_batch.h).
+// They differ where a span starts and ends: a live chunk starts from its stream's carried tail wherever the first frame
+// a wave computes is the chunk's first -- at the start of the walk and after every span.next() -- where an utterance
+// starts from zero; and after a chunk's last frame the new tail goes to the stream's other tail buffer (OlaAcc::shift)
+// where an utterance's is emitted behind it and the sums restart.  A chunk writes its hop F_c samples and nothing
+// behind them.  The frames, the rho criterion and the FP64 pass are functions of a frame's samples and mask row alone.
+// The arguments come by value: with a reference to the kernel's the compiler scheduled both kernels' loops otherwise
+// than it does a loop written into the kernel itself; by value both come out as they do from a loop of their own,
+// up to the operand order of commutative instructions (profiles/r19_ragged_call_layer.txt).
+template <int R, int CPX, class Span>
+__device__ __forceinline__ void stftmask_ragged(StftMaskBatchArgs a, const float2 *__restrict__ table, Span span)
 {
     constexpr int HR = 8 / R;
     constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
@@ -437,9 +445,8 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     int n_redo = 0;                                              // emitted frames of this run computed again in FP64
     long j0, j1;
     if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
-    RaggedSpan<1024 / R> span(sample_first, frame_first, a.n_utts);
     span.begin(j0);
-    const long js = span.first(j0, R);                           // the halo, never into the utterance before
+    const long js = span.first(j0, R);                           // the halo, never into the span before
 
     WaveTwiddles tw;
     load_wave_twiddles(tw, table, lane);
@@ -454,6 +461,9 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     }
     OlaAcc<float2, HR> ola;
     ola.init(a.g, lane);
+    if constexpr (Span::kLive) {
+        if (span.starts_span(js)) ola.load_tail(span.tail_in(), lane);
+    }
     float2 y[8], o[HR];
 
     const char *mask = static_cast<const char *>(a.mask);
@@ -465,8 +475,8 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
     mask_prepare(m, nm, lane);
     float m_sq = mask_energy(m, lane);
     for (long j = js; j < j1; j++) {
-        // the PCM's prefetch clamps inside the utterance: after its last frame the next frame's samples are another
-        // span's, read whole below.  The mask rows run on across utterances.
+        // the PCM's prefetch clamps inside the span: after its last frame the next frame's samples are another
+        // span's, read whole below.  The mask rows run on across spans.
         const bool last = span.last(j);
         const long jm = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
         pcm.prefetch(a.pcm, span.at(span.next_inside(j)), lane);
@@ -483,155 +493,84 @@ __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_ker
         }
         __builtin_amdgcn_sched_barrier(0);
         if (j >= j0) ola.emit(o, a.out, a.out_f32, span.at(j), lane);
-        ola.shift(false, nullptr, lane);
-        if (last) {
-            // a halo frame is never an utterance's last (j0 lies in the halo's utterance), so the wave that emits
-            // the last frame emits the tail
-            ola.emit_tail(a.out, a.out_f32, span.at(j + 1), lane);
-            ola.restart();
-            if (j + 1 < j1) {
-                span.next();                                     // frame j + 1 exists, so a non-empty utterance follows
+        // a halo frame is never a span's last (j0 lies in the halo's span), so the wave that emits the last frame
+        // emits or writes the tail
+        if constexpr (Span::kLive) {
+            ola.shift(last, span.tail_out(), lane);
+            if (last && j + 1 < j1) {
+                span.next();                                     // frame j + 1 exists, so a non-empty chunk follows
+                ola.load_tail(span.tail_in(), lane);
                 pcm.load(a.pcm, span.at(j + 1), lane);
+            }
+        } else {
+            ola.shift(false, nullptr, lane);
+            if (last) {
+                ola.emit_tail(a.out, a.out_f32, span.at(j + 1), lane);
+                ola.restart();
+                if (j + 1 < j1) {
+                    span.next();                                 // frame j + 1 exists, so a non-empty utterance follows
+                    pcm.load(a.pcm, span.at(j + 1), lane);
+                }
             }
         }
     }
     stftmask_count_end(a.f64, n_redo, lane);
 }
 
-template <int R>
-static void launch_batch_kind(hipStream_t s, int cpx, long grid, const StftMaskBatchArgs &a, const float2 *table,
-                              const long long *sample_first, const long long *frame_first)
+template <int R, int CPX>
+__global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_batch_kernel(
+    StftMaskBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
+    const long long *__restrict__ frame_first)
 {
-    if (cpx)
-        hipLaunchKernelGGL((stftmask_batch_kernel<R, 1>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
-                           frame_first);
-    else
-        hipLaunchKernelGGL((stftmask_batch_kernel<R, 0>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
-                           frame_first);
+    stftmask_ragged<R, CPX>(a, table, RaggedSpan<1024 / R>(sample_first, frame_first, a.n_utts));
 }
 
-int launch_stftmask_batch(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
-                          long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
-                          long n_utts, const float *wa, const float *ws, const float *g, short *out, float *out_f32,
-                          const float2 *table, int run_opt, const double *f64, unsigned int *count,
-                          unsigned int epoch)
-{
-    if (n_frames_total <= 0 || n_utts <= 0) return 0;
-    const int r = 1024 / hop;
-    const OlaRunPlan p = plan_ola_run(n_cu, JDSP_STFTMASK_RESIDENT, r, n_frames_total, run_opt);
-    StftMaskBatchArgs a = {pcm, mask, pitch, n_frames_total, wa, ws, g, n_utts, out, out_f32, (int)p.run,
-                           {f64, f64 + 1024, reinterpret_cast<const double2 *>(f64 + 2048), count, epoch}};
-    if (r == 1) launch_batch_kind<1>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
-    else if (r == 2) launch_batch_kind<2>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
-    else launch_batch_kind<4>(s, complex_mask, p.grid, a, table, sample_first, frame_first);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// ---- the chunks of live streams in one launch (jdsp_stftmask_streams_*) ---------------------------------------------
-// The batch kernel's loop over LiveSpan (ragged_batch.h), chunks where that has utterances, with three differences: the
-// sums start from the stream's carried tail wherever the first frame a wave computes is a chunk's first -- at the start
-// of its walk and after every span.next() -- where the batch starts from zero; after a chunk's last frame the new tail
-// goes to the stream's other tail buffer (OlaAcc::shift) where the batch emits it and restarts; and the chunk's stream
-// and parity are loaded next to its offsets, into scalar registers.  A chunk writes its hop F_c samples and nothing
-// behind them.  The frames, the rho criterion and the FP64 pass are the batch's: functions of a frame's samples and
-// mask row alone.
+// the chunks of live streams (jdsp_stftmask_streams_*): the chunk's stream and parity are loaded next to its offsets,
+// into scalar registers (LiveStreams, jdsp_internal.h)
 template <int R, int CPX>
 __global__ __launch_bounds__(64, JDSP_STFTMASK_RESIDENT) void stftmask_live_kernel(
     StftMaskBatchArgs a, const float2 *__restrict__ table, const long long *__restrict__ sample_first,
     const long long *__restrict__ frame_first, const long long *__restrict__ stream_id, const int *__restrict__ parity,
     LiveStreams live)
 {
-    constexpr int HR = 8 / R;
-    constexpr size_t kElem = CPX ? sizeof(float2) : sizeof(float);
-    JDSP_STFTMASK_LDS;
-    const int lane = threadIdx.x;
-    stftmask_count_begin(a.f64, lane);
-    int n_redo = 0;                                              // emitted frames of this run computed again in FP64
-    long j0, j1;
-    if (!ola_run_range(a.run, a.n_frames, j0, j1)) return;
-    LiveSpan<1024 / R> span(sample_first, frame_first, a.n_utts, stream_id, parity, live);
-    span.begin(j0);
-    const long js = span.first(j0, R);                           // the halo, never into the chunk before
+    stftmask_ragged<R, CPX>(a, table, LiveSpan<1024 / R>(sample_first, frame_first, a.n_utts, stream_id, parity, live));
+}
 
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    PairTwiddles pw;
-    load_pair_twiddles(pw, table, lane);
-    float2 wa[8], ws[8];
-    {
-        const float2 *wa_t = reinterpret_cast<const float2 *>(a.wa);
-        const float2 *ws_t = reinterpret_cast<const float2 *>(a.ws);
-#pragma unroll
-        for (int d = 0; d < 8; d++) { wa[d] = wa_t[lane + 64 * d]; ws[d] = ws_t[lane + 64 * d]; }
-    }
-    OlaAcc<float2, HR> ola;
-    ola.init(a.g, lane);
-    if (span.starts_span(js)) ola.load_tail(span.tail_in(), lane);
-    float2 y[8], o[HR];
-
-    const char *mask = static_cast<const char *>(a.mask);
-    const size_t row_bytes = (size_t)a.pitch * kElem;
-    PcmHops<HR> pcm;
-    MaskRow<CPX> m, nm;
-    pcm.load(a.pcm, span.at(js), lane);
-    mask_load(nm, mask + (size_t)js * row_bytes, lane);
-    mask_prepare(m, nm, lane);
-    float m_sq = mask_energy(m, lane);
-    for (long j = js; j < j1; j++) {
-        const bool last = span.last(j);
-        const long jm = j + 1 < a.n_frames ? j + 1 : a.n_frames - 1;
-        pcm.prefetch(a.pcm, span.at(span.next_inside(j)), lane);
-        if (a.pitch) mask_load(nm, mask + (size_t)jm * row_bytes, lane);
-        if (stftmask_frame<CPX>(pcm.raw, wa, tw, pw, lds, lane, m, m_sq, ws, y)) {
-            stftmask_frame_f64<CPX>(pcm.raw, a.f64, mask + (size_t)(a.pitch ? j : 0) * row_bytes, lds64, lane, y);
-            n_redo += j >= j0;
-        }
-        ola.add(y, o);
-        pcm.advance();                                           // staged before this frame's stores (frame_io.h)
-        if (a.pitch) {
-            mask_prepare(m, nm, lane);
-            m_sq = mask_energy(m, lane);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (j >= j0) ola.emit(o, a.out, a.out_f32, span.at(j), lane);
-        // a halo frame is never a chunk's last (j0 lies in the halo's chunk), so the wave that emits the last frame
-        // writes the tail
-        ola.shift(last, span.tail_out(), lane);
-        if (last && j + 1 < j1) {
-            span.next();                                         // frame j + 1 exists, so a non-empty chunk follows
-            ola.load_tail(span.tail_in(), lane);
-            pcm.load(a.pcm, span.at(j + 1), lane);
-        }
-    }
-    stftmask_count_end(a.f64, n_redo, lane);
+// live != NULL: the chunks of live streams
+template <int R, int CPX>
+static void launch_ragged_one(hipStream_t s, long grid, const StftMaskBatchArgs &a, const float2 *table,
+                              const long long *sample_first, const long long *frame_first, const LiveStreams *live)
+{
+    if (live)
+        hipLaunchKernelGGL((stftmask_live_kernel<R, CPX>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
+                           frame_first, live->stream_id, live->parity, *live);
+    else
+        hipLaunchKernelGGL((stftmask_batch_kernel<R, CPX>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
+                           frame_first);
 }
 
 template <int R>
-static void launch_live_kind(hipStream_t s, int cpx, long grid, const StftMaskBatchArgs &a, const float2 *table,
-                             const long long *sample_first, const long long *frame_first, const LiveStreams &live)
+static void launch_ragged_kind(hipStream_t s, int cpx, long grid, const StftMaskBatchArgs &a, const float2 *table,
+                               const long long *sample_first, const long long *frame_first, const LiveStreams *live)
 {
-    if (cpx)
-        hipLaunchKernelGGL((stftmask_live_kernel<R, 1>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
-                           frame_first, live.stream_id, live.parity, live);
-    else
-        hipLaunchKernelGGL((stftmask_live_kernel<R, 0>), dim3((unsigned)grid), dim3(64), 0, s, a, table, sample_first,
-                           frame_first, live.stream_id, live.parity, live);
+    if (cpx) launch_ragged_one<R, 1>(s, grid, a, table, sample_first, frame_first, live);
+    else launch_ragged_one<R, 0>(s, grid, a, table, sample_first, frame_first, live);
 }
 
-int launch_stftmask_live(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
-                         long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
-                         long n_chunks, const LiveStreams &live, const float *wa, const float *ws, const float *g,
-                         short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
-                         unsigned int *count, unsigned int epoch)
+int launch_stftmask_ragged(hipStream_t s, int n_cu, int hop, int complex_mask, const short *pcm, const void *mask,
+                           long pitch, long n_frames_total, const long long *sample_first, const long long *frame_first,
+                           long n_spans, const LiveStreams *live, const float *wa, const float *ws, const float *g,
+                           short *out, float *out_f32, const float2 *table, int run_opt, const double *f64,
+                           unsigned int *count, unsigned int epoch)
 {
-    if (n_frames_total <= 0 || n_chunks <= 0) return 0;
+    if (n_frames_total <= 0 || n_spans <= 0) return 0;
     const int r = 1024 / hop;
     const OlaRunPlan p = plan_ola_run(n_cu, JDSP_STFTMASK_RESIDENT, r, n_frames_total, run_opt);
-    StftMaskBatchArgs a = {pcm, mask, pitch, n_frames_total, wa, ws, g, n_chunks, out, out_f32, (int)p.run,
+    StftMaskBatchArgs a = {pcm, mask, pitch, n_frames_total, wa, ws, g, n_spans, out, out_f32, (int)p.run,
                            {f64, f64 + 1024, reinterpret_cast<const double2 *>(f64 + 2048), count, epoch}};
-    if (r == 1) launch_live_kind<1>(s, complex_mask, p.grid, a, table, sample_first, frame_first, live);
-    else if (r == 2) launch_live_kind<2>(s, complex_mask, p.grid, a, table, sample_first, frame_first, live);
-    else launch_live_kind<4>(s, complex_mask, p.grid, a, table, sample_first, frame_first, live);
+    if (r == 1) launch_ragged_kind<1>(s, complex_mask, p.grid, a, table, sample_first, frame_first, live);
+    else if (r == 2) launch_ragged_kind<2>(s, complex_mask, p.grid, a, table, sample_first, frame_first, live);
+    else launch_ragged_kind<4>(s, complex_mask, p.grid, a, table, sample_first, frame_first, live);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -1057,6 +1057,19 @@ class _OlaStream(_Child):
             return None
         return (out[:n_out], out_f32[:n_out]) if want_f32 else out[:n_out]
 
+    def _ragged(self, name, dev, inputs, arrays, counts, n_samples, want_f32, out, out_f32):
+        """One call of the ragged entry `name` ("_batch" or "_streams"): the device entry on torch's current stream for
+        the torch device `dev` or, with dev None, the host entry.  inputs: the C entry's arguments between the handle
+        and the offset arrays; arrays: ([ids,] sample_first, frame_first), on dev or in numpy; counts: the scalars
+        between them and the outputs.  Returns the n_samples of out, or of (out, out_f32) with want_f32."""
+        out = _batch_out(n_samples, np.int16, dev, out)
+        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+        entry = self._c(name + "_dev" if dev is not None else name)
+        self.eng._ck(entry(self._h, *inputs, *[_vp(a) for a in arrays], *counts, _vp(out), _vp(out_f32)))
+        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+
     def flush(self, want_f32=False):
         """The n_fft - hop samples still in the tail; the handle is reset afterwards."""
         n = self.n_fft - self.hop
@@ -1166,6 +1179,15 @@ class Istft(_OlaStream):
         self.layout = pick(layout, self.LAYOUTS)
         self.bins = self.n_fft // 2 + 1 if self.layout == _lib.SPEC_HALF else self.n_fft
 
+    @staticmethod
+    def _spec(spec):
+        """(spec, dev): a torch CUDA complex64 tensor, checked, and its device, or a numpy complex64 array and None"""
+        if _is_torch(spec):
+            import torch
+            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
+            return spec, spec.device
+        return np.ascontiguousarray(spec, np.complex64), None
+
     def process(self, spec, want_f32=False, out=None, out_f32=None, n_frames=None, write=True):
         """spec: complex64 [n_frames, row_pitch >= bins] (torch CUDA or numpy, rows contiguous).  Returns the int16
         samples of these frames (n_frames * hop), or (int16, float32) with want_f32.  write=False advances the stream
@@ -1173,13 +1195,7 @@ class Istft(_OlaStream):
         if n_frames is None:
             n_frames = spec.shape[0]
         pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
-        if _is_torch(spec):
-            import torch
-            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
-            dev = spec.device
-        else:
-            spec = np.ascontiguousarray(spec, np.complex64)
-            dev = None
+        spec, dev = self._spec(spec)
         return self._process(dev, (_vp(spec), pitch), n_frames, want_f32, write, out, out_f32)
 
     def process_batch(self, spec, frame_counts, utt_sample_first=None, want_f32=False, out=None, out_f32=None):
@@ -1202,24 +1218,13 @@ class Istft(_OlaStream):
         pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
         assert spec.ndim == 2 and spec.shape[0] >= n_total and pitch >= self.bins
         sample_first = np.ascontiguousarray(offs[:-1])
-        dev = spec.device if _is_torch(spec) else None
+        spec, dev = self._spec(spec)
         if dev is not None:
-            import torch
-            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
             key = (offs.tobytes(), counts.tobytes())
-            d_sample, d_frame, _ = _batch_offsets(self, key, sample_first, frame_first, dev)
+            arrays, sizes = _batch_offsets(self, key, sample_first, frame_first, dev)[:2], (n_utts, n_total)
         else:
-            spec = np.ascontiguousarray(spec, np.complex64)
-        out = _batch_out(n_samples, np.int16, dev, out)
-        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
-        if dev is not None:
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_istft_batch_dev(self._h, _vp(spec), pitch, _vp(d_sample), _vp(d_frame), n_utts, n_total,
-                                                _vp(out), _vp(out_f32)))
-        else:
-            self.eng._ck(L.jdsp_istft_batch(self._h, _vp(spec), pitch, _vp(sample_first), _vp(frame_first), n_utts,
-                                            n_samples, _vp(out), _vp(out_f32)))
-        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+            arrays, sizes = (sample_first, frame_first), (n_utts, n_samples)
+        return self._ragged("_batch", dev, (_vp(spec), pitch), arrays, sizes, n_samples, want_f32, out, out_f32)
 
     def process_streams(self, spec, stream_ids, frame_counts, chunk_sample_first=None, n_samples=None, want_f32=False,
                         out=None, out_f32=None):
@@ -1238,21 +1243,12 @@ class Istft(_OlaStream):
         pitch = spec.shape[-1] if spec.ndim == 2 else self.bins
         assert spec.ndim == 2 and spec.shape[0] >= n_total and pitch >= self.bins and n_samples >= end
         self._streams_torch = dev
+        spec = self._spec(spec)[0]
         if dev is not None:
-            import torch
-            assert spec.is_cuda and spec.dtype == torch.complex64 and spec.is_contiguous()
+            arrays, sizes = d, (n_chunks, n_total)
         else:
-            spec = np.ascontiguousarray(spec, np.complex64)
-        out = _batch_out(n_samples, np.int16, dev, out)
-        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
-        if dev is not None:
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_istft_streams_dev(self._h, _vp(spec), pitch, _vp(d[0]), _vp(d[1]), _vp(d[2]), n_chunks,
-                                                  n_total, _vp(out), _vp(out_f32)))
-        else:
-            self.eng._ck(L.jdsp_istft_streams(self._h, _vp(spec), pitch, _vp(ids), _vp(sample_first), _vp(frame_first),
-                                              n_chunks, n_samples, _vp(out), _vp(out_f32)))
-        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+            arrays, sizes = (ids, sample_first, frame_first), (n_chunks, n_samples)
+        return self._ragged("_streams", dev, (_vp(spec), pitch), arrays, sizes, n_samples, want_f32, out, out_f32)
 
 
 class StftMask(_OlaStream):
@@ -1272,6 +1268,22 @@ class StftMask(_OlaStream):
                                               pick(synthesis_window, self.WINDOWS), int(normalise), self.mask_kind))
         self.bins = self.n_fft // 2 + 1
 
+    def _inputs(self, pcm, mask, n_rows, n_least):
+        """(pcm, mask, mask_pitch, dev) of a call over n_rows frames that reads n_least samples: both torch CUDA, checked,
+        and their device, or numpy arrays of the handle's types and None"""
+        assert pcm.ndim == 1 and pcm.shape[0] >= n_least
+        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_rows)
+        pitch = mask.shape[1] if mask.ndim == 2 else 0
+        if _is_torch(pcm):
+            import torch
+            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
+            return pcm, mask, pitch, pcm.device
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
+        return pcm, mask, pitch, None
+
     def process(self, pcm, mask, n_frames=None, want_f32=False, write=True, out=None, out_f32=None):
         """pcm: int16, hop (n_frames - 1) + n_fft samples (n_frames defaults to all the whole frames pcm holds).
         mask: float32 (real) or complex64 (complex); [n_frames, pitch >= bins] with contiguous rows, or 1-D [bins]: one
@@ -1281,19 +1293,8 @@ class StftMask(_OlaStream):
         if n_frames is None:
             n_frames = max((pcm.shape[0] - self.n_fft) // self.hop + 1, 0)
         n_frames = int(n_frames)
-        assert pcm.ndim == 1 and pcm.shape[0] >= (self.hop * (n_frames - 1) + self.n_fft if n_frames else 0)
-        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_frames)
-        pitch = mask.shape[1] if mask.ndim == 2 else 0
-        if _is_torch(pcm):
-            import torch
-            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
-            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
-            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
-            dev = pcm.device
-        else:
-            pcm = np.ascontiguousarray(pcm, np.int16)
-            mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
-            dev = None
+        n_least = self.hop * (n_frames - 1) + self.n_fft if n_frames else 0
+        pcm, mask, pitch, dev = self._inputs(pcm, mask, n_frames, n_least)
         return self._process(dev, (_vp(pcm), _vp(mask), pitch), n_frames, want_f32, write, out, out_f32)
 
     def frames_recomputed(self):
@@ -1318,30 +1319,15 @@ class StftMask(_OlaStream):
         offs = np.ascontiguousarray(utt_sample_first, np.int64).reshape(-1)
         counts, frame_first = stftmask_batch_layout(offs, self.n_fft, self.hop)
         n_utts, n_total, n_samples = counts.size, int(frame_first[-1]), int(pcm.shape[0])
-        assert pcm.ndim == 1 and n_samples >= int(offs[-1])
-        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_total)
-        pitch = mask.shape[1] if mask.ndim == 2 else 0
+        pcm, mask, pitch, dev = self._inputs(pcm, mask, n_total, int(offs[-1]))
         sample_first = np.ascontiguousarray(offs[:-1])
-        dev = pcm.device if _is_torch(pcm) else None
         if dev is not None:
-            import torch
-            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
-            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
-            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
-            d_sample, d_frame, _ = _batch_offsets(self, offs.tobytes(), sample_first, frame_first, dev)
+            inputs, sizes = (_vp(pcm), _vp(mask), pitch), (n_utts, n_total)
+            arrays = _batch_offsets(self, offs.tobytes(), sample_first, frame_first, dev)[:2]
         else:
-            pcm = np.ascontiguousarray(pcm, np.int16)
-            mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
-        out = _batch_out(n_samples, np.int16, dev, out)
-        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
-        if dev is not None:
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_stftmask_batch_dev(self._h, _vp(pcm), _vp(mask), pitch, _vp(d_sample), _vp(d_frame),
-                                                   n_utts, n_total, _vp(out), _vp(out_f32)))
-        else:
-            self.eng._ck(L.jdsp_stftmask_batch(self._h, _vp(pcm), n_samples, _vp(mask), pitch, _vp(sample_first),
-                                               _vp(frame_first), n_utts, _vp(out), _vp(out_f32)))
-        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+            inputs, sizes = (_vp(pcm), n_samples, _vp(mask), pitch), (n_utts,)
+            arrays = (sample_first, frame_first)
+        return self._ragged("_batch", dev, inputs, arrays, sizes, n_samples, want_f32, out, out_f32)
 
     def process_streams(self, pcm, mask, stream_ids, frame_counts, chunk_sample_first=None, want_f32=False, out=None,
                         out_f32=None):
@@ -1358,28 +1344,14 @@ class StftMask(_OlaStream):
         dev = pcm.device if _is_torch(pcm) else None
         ids, sample_first, frame_first, d, end = self._chunks(stream_ids, frame_counts, chunk_sample_first, True, dev)
         n_chunks, n_total, n_samples = ids.size, int(frame_first[-1]), int(pcm.shape[0])
-        assert pcm.ndim == 1 and n_samples >= end
-        assert mask.ndim in (1, 2) and mask.shape[-1] >= self.bins and (mask.ndim == 1 or mask.shape[0] >= n_total)
-        pitch = mask.shape[1] if mask.ndim == 2 else 0
+        pcm, mask, pitch = self._inputs(pcm, mask, n_total, end)[:3]
         self._streams_torch = dev
         if dev is not None:
-            import torch
-            want = torch.complex64 if self.mask_kind == _lib.MASK_COMPLEX else torch.float32
-            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
-            assert mask.is_cuda and mask.dtype == want and mask.is_contiguous()
+            inputs, arrays, sizes = (_vp(pcm), _vp(mask), pitch), d, (n_chunks, n_total)
         else:
-            pcm = np.ascontiguousarray(pcm, np.int16)
-            mask = np.ascontiguousarray(mask, np.complex64 if self.mask_kind == _lib.MASK_COMPLEX else np.float32)
-        out = _batch_out(n_samples, np.int16, dev, out)
-        out_f32 = _batch_out(n_samples, np.float32, dev, out_f32) if want_f32 else None
-        if dev is not None:
-            self.eng._use_torch_stream()
-            self.eng._ck(L.jdsp_stftmask_streams_dev(self._h, _vp(pcm), _vp(mask), pitch, _vp(d[0]), _vp(d[1]), _vp(d[2]),
-                                                     n_chunks, n_total, _vp(out), _vp(out_f32)))
-        else:
-            self.eng._ck(L.jdsp_stftmask_streams(self._h, _vp(pcm), n_samples, _vp(mask), pitch, _vp(ids),
-                                                 _vp(sample_first), _vp(frame_first), n_chunks, _vp(out), _vp(out_f32)))
-        return (out[:n_samples], out_f32[:n_samples]) if want_f32 else out[:n_samples]
+            inputs, sizes = (_vp(pcm), n_samples, _vp(mask), pitch), (n_chunks,)
+            arrays = (ids, sample_first, frame_first)
+        return self._ragged("_streams", dev, inputs, arrays, sizes, n_samples, want_f32, out, out_f32)
 
 
 class GmmTrainer(_Child):

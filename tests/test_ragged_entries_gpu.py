@@ -2,7 +2,9 @@
 jdsp_denoise_batch) share one layout check (csrc/ragged_layout.h; tests/test_ragged_layout_cpu.py runs it on the host).
 Here each entry is called through the C ABI with the five layouts it must reject, and the WHOLE message is pinned --
 `<entry>: <reason>` with the entry's own word for its unit array -- where the entries' own error tests only look for
-the entry's name.  A good call succeeds before and after the bad ones and gives the same output both times."""
+the entry's name.  A good call succeeds before and after the bad ones and gives the same output both times.  The two
+host entries over the chunks of live streams (jdsp_istft_streams, jdsp_stftmask_streams) make the same check of their
+chunks and are held to the same messages."""
 import os
 import sys
 
@@ -114,6 +116,42 @@ def test_stftmask_batch_messages(eng, frames):
               lambda s, f, n: L.jdsp_stftmask_batch(h._h, vp(frames.pcm), n, vp(mask), PITCH, vp(s), vp(f), frames.n_utts,
                                                     vp(out), vp(out_f32)),
               lambda: [out, out_f32])
+    h.close()
+
+
+IDS = np.array([2, 0, 1], np.int64)                                        # the live streams of the chunks [2, 3, 1]
+
+
+def test_istft_streams_messages(eng):
+    from jeicyboodsp_amd._lib import lib as L
+    lay = Layout([2, 3, 1], HOP)                                           # a chunk's span is its hop F_c output samples
+    rng = np.random.default_rng(1502)
+    spec = ((rng.normal(size=(lay.total, PITCH)) + 1j * rng.normal(size=(lay.total, PITCH))) * 3000.0).astype(np.complex64)
+    h = eng.istft(n_fft=N, hop=HOP, layout="half")
+    h.open_streams(3)
+    out, out_f32 = np.zeros(lay.n_samples, np.int16), np.zeros(lay.n_samples, np.float32)
+
+    def call(s, f, n):
+        assert L.jdsp_istft_streams_reset_dev(h._h, None, 0) == 0          # every call finds the streams fresh
+        return L.jdsp_istft_streams(h._h, vp(spec), PITCH, vp(IDS), vp(s), vp(f), lay.n_utts, n, vp(out), vp(out_f32))
+
+    run_entry(eng, "jdsp_istft_streams", "frame_first", lay, call, lambda: [out, out_f32])
+    h.close()
+
+
+def test_stftmask_streams_messages(eng, frames):
+    from jeicyboodsp_amd._lib import lib as L
+    mask = np.full((frames.total, PITCH), 0.5, np.float32)
+    h = eng.stft_mask(n_fft=N, hop=HOP)
+    h.open_streams(3)
+    out, out_f32 = np.zeros(frames.n_samples, np.int16), np.zeros(frames.n_samples, np.float32)
+
+    def call(s, f, n):
+        assert L.jdsp_stftmask_streams_reset_dev(h._h, None, 0) == 0       # every call finds the streams fresh
+        return L.jdsp_stftmask_streams(h._h, vp(frames.pcm), n, vp(mask), PITCH, vp(IDS), vp(s), vp(f), frames.n_utts,
+                                       vp(out), vp(out_f32))
+
+    run_entry(eng, "jdsp_stftmask_streams", "frame_first", frames, call, lambda: [out, out_f32])
     h.close()
 
 

@@ -291,6 +291,58 @@ def test_fp64_pass_travels(eng):
     sm.close()
 
 
+def test_a_call_of_nothing_recomputed_no_frames(eng):
+    """jdsp_stftmask_frames_recomputed answers for the LAST call: after a call that recomputed frames, every batch or
+    streams call that has nothing to do -- no spans, no frames, no output to write, on the device entries; counts that
+    are all zero on the host entries -- leaves the count at 0, not at the earlier call's figure."""
+    import torch
+    import stftmask_fp32_ref as S
+    c = min((c for c in S.cases() if c["name"].startswith("notch")), key=lambda c: c["pcm"].size)
+    hop, F = c["hop"], c["F"]
+    pcm, mask = np.array(c["pcm"]), np.array(c["mask"])
+    pitch = mask.shape[1]
+    sm = eng.stft_mask(**cfg_of(hop, c["kind"], c["combo"]))
+    sm.open_streams(2)
+    d_pcm, d_mask = torch.from_numpy(pcm).cuda(), torch.from_numpy(mask).cuda()
+    ids, first = np.array([1], np.int64), np.array([0], np.int64)
+    ff, ff0 = np.array([0, F], np.int64), np.array([0, 0], np.int64)
+    d_ids, d_first, d_ff = (torch.from_numpy(a).cuda() for a in (ids, first, ff))
+    d_out = torch.zeros(pcm.size, dtype=torch.int16, device="cuda")
+    h_out = np.zeros(pcm.size, np.int16)
+    vp = lambda a: None if a is None else C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)  # noqa: E731
+
+    def batch_dev(n, total, out):
+        return sm._c("_batch_dev")(sm._h, vp(d_pcm), vp(d_mask), pitch, vp(d_first), vp(d_ff), n, total, vp(out), None)
+
+    def streams_dev(n, total, out):
+        return sm._c("_streams_dev")(sm._h, vp(d_pcm), vp(d_mask), pitch, vp(d_ids), vp(d_first), vp(d_ff), n, total,
+                                     vp(out), None)
+
+    nothing = [
+        ("batch_dev, n_utts 0", lambda: batch_dev(0, F, d_out)),
+        ("streams_dev, n_chunks 0", lambda: streams_dev(0, F, d_out)),
+        ("batch_dev, n_frames_total 0", lambda: batch_dev(1, 0, d_out)),
+        ("streams_dev, n_frames_total 0", lambda: streams_dev(1, 0, d_out)),
+        ("batch_dev, both outputs NULL", lambda: batch_dev(1, F, None)),
+        ("streams_dev, both outputs NULL", lambda: streams_dev(1, F, None)),
+        ("host batch, all counts 0", lambda: sm._c("_batch")(sm._h, vp(pcm), pcm.size, vp(mask), pitch, vp(first), vp(ff0), 1,
+                                                             vp(h_out), None)),
+        ("host streams, all counts 0", lambda: sm._c("_streams")(sm._h, vp(pcm), pcm.size, vp(mask), pitch, vp(ids), vp(first),
+                                                                 vp(ff0), 1, vp(h_out), None)),
+    ]
+    for what, call in nothing:
+        sm.reset()
+        sm.process(d_pcm, d_mask, F)
+        n = sm.frames_recomputed()
+        print("%s: %d frames recomputed before it" % (what, n))
+        assert n > 0, "the notched tone must recompute frames"
+        assert call() == 0, what
+        after = sm.frames_recomputed()
+        print("%s: %d after it" % (what, after))
+        assert after == 0, what
+    sm.close()
+
+
 # ---- 5. the host entries -------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 def test_host_entries(eng, kind):

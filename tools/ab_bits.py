@@ -140,6 +140,107 @@ def batches(eng):
                 sm.close()
 
 
+def stream_calls(R):
+    """Three calls of (stream, frames) chunks over five live streams: ids in no order, a stream or two absent from every
+    call, chunks of 0, 1, R - 1, R and R + 1 frames"""
+    return [[(3, R + 1), (0, 1), (4, 0), (1, R)],
+            [(2, R - 1), (0, R), (3, 1)],
+            [(4, R + 1), (1, 1), (0, R - 1), (2, R), (3, 0)]]
+
+
+def stream_offsets(counts, n, hop, with_pcm, gaps):
+    """the chunks' sample offsets: back to back, or pushed apart by even gaps that grow from chunk to chunk"""
+    import numpy as np
+    from jeicyboodsp_amd import sharding
+    packed = sharding.stream_chunks_layout(counts, n, hop, with_pcm)[0]
+    return packed + 2 * np.cumsum(np.arange(1, len(counts) + 1)) if gaps else packed
+
+
+def streams(eng):
+    """process_streams on both handles: the calls of stream_calls at every geometry, the second call at explicit offsets
+    with gaps, then flush_streams of all five; once per handle with a process_batch and one of the handle's own
+    process calls between the stream calls"""
+    import numpy as np
+    import torch
+    import stftmask_fp32_ref as S
+    N_LIVE = 5
+
+    def totals(R):
+        return [sum(f for call in stream_calls(R) for s, f in call if s == k) for k in range(N_LIVE)]
+
+    for n, layout in ((1024, "half"), (1024, "full"), (512, "full")):
+        for R in (1, 2, 4):
+            hop = n // R
+            rng = np.random.default_rng(7000 + n + hop + len(layout))
+            pitch = n if layout == "full" else n // 2 + 1
+            rows = [(rng.normal(size=(t, pitch)) + 1j * rng.normal(size=(t, pitch))) * 3000.0 * np.sqrt(n) / 2 for t in totals(R)]
+            rows = [r.astype(np.complex64) for r in rows]
+            own = torch.from_numpy(rows[0]).cuda()
+            ist = eng.istft(n_fft=n, hop=hop, layout=layout, synthesis_window="hann",
+                            analysis_window="hann" if R > 1 else "none")
+            ist.open_streams(N_LIVE)
+            for fpw in geometries(R) + ["interleaved"]:
+                ist.set_option("frames_per_wave", 0 if fpw == "interleaved" else fpw)
+                done, outs = [0] * N_LIVE, []
+                for k, call in enumerate(stream_calls(R)):
+                    counts = np.array([f for _, f in call], np.int64)
+                    spec = np.concatenate([rows[s][done[s]:done[s] + f] for s, f in call] + [rows[0][:1]])
+                    for s, f in call:
+                        done[s] += f
+                    first = stream_offsets(counts, n, hop, False, k == 1) if k == 1 else None
+                    outs += [x.clone() for x in ist.process_streams(torch.from_numpy(spec).cuda(), [s for s, _ in call],
+                                                                    counts, first, want_f32=True)]
+                    if fpw == "interleaved" and k == 0:
+                        outs += [x.clone() for x in ist.process_batch(own, [own.shape[0]], want_f32=True)]
+                    if fpw == "interleaved" and k == 1:
+                        outs += [x.clone() for x in ist.process(own, want_f32=True)]
+                outs += list(ist.flush_streams(np.arange(N_LIVE), want_f32=True))
+                if fpw == "interleaved":
+                    outs += list(ist.flush(want_f32=True))
+                yield "istft_streams %d/%d %s fpw %s" % (n, hop, layout, fpw), digest(*outs)
+            ist.close()
+    n = 1024
+    for hop in (1024, 512, 256):
+        R = n // hop
+        for kind in ("real", "complex"):
+            rng = np.random.default_rng(7100 + hop + len(kind))
+            tot = totals(R)
+            pcm = [np.clip(np.rint(rng.normal(0, 3000.0, hop * (t - 1) + n)), -32768, 32767).astype(np.int16) for t in tot]
+            mask = [S.mask_of(rng, kind, t) for t in tot]
+            own_pcm, own_mask = torch.from_numpy(pcm[0]).cuda(), torch.from_numpy(mask[0]).cuda()
+            own_offs = np.array([0, pcm[0].size], np.int64)
+            sm = eng.stft_mask(**mask_cfg(hop, kind, S.stream_combo(hop)))
+            sm.open_streams(N_LIVE)
+            for fpw in geometries(R) + ["interleaved"]:
+                sm.set_option("frames_per_wave", 0 if fpw == "interleaved" else fpw)
+                done, outs, n_redo = [0] * N_LIVE, [], []
+                for k, call in enumerate(stream_calls(R)):
+                    counts = np.array([f for _, f in call], np.int64)
+                    at = stream_offsets(counts, n, hop, True, k == 1)
+                    first = at if k == 1 else None                 # None: the handle packs them itself
+                    buf = np.full(int(at[-1]) + hop * max(int(counts[-1]) - 1, 0) + n, 32767, np.int16)
+                    for (s, f), a in zip(call, at):
+                        if f:
+                            buf[int(a):int(a) + hop * (f - 1) + n] = pcm[s][hop * done[s]:hop * (done[s] + f - 1) + n]
+                    m = np.concatenate([mask[s][done[s]:done[s] + f] for s, f in call] + [mask[0][:1]])
+                    for s, f in call:
+                        done[s] += f
+                    outs += [x.clone() for x in sm.process_streams(torch.from_numpy(buf).cuda(), torch.from_numpy(m).cuda(),
+                                                                   [s for s, _ in call], counts, first, want_f32=True)]
+                    n_redo.append(sm.frames_recomputed())
+                    if fpw == "interleaved" and k == 0:
+                        outs += [x.clone() for x in sm.process_batch(own_pcm, own_mask, own_offs, want_f32=True)]
+                        n_redo.append(sm.frames_recomputed())
+                    if fpw == "interleaved" and k == 1:
+                        outs += [x.clone() for x in sm.process(own_pcm, own_mask, want_f32=True)]
+                        n_redo.append(sm.frames_recomputed())
+                outs += list(sm.flush_streams(np.arange(N_LIVE), want_f32=True))
+                if fpw == "interleaved":
+                    outs += list(sm.flush(want_f32=True))
+                yield "stftmask_streams hop %d %s fpw %s" % (hop, kind, fpw), digest(*outs, np.array(n_redo))
+            sm.close()
+
+
 def periodic(n_fft):
     import denoise_fp32_ref as R
     return next(c for c in R.cases() if c["periodic"] and c["n_fft"] == n_fft)
@@ -190,7 +291,7 @@ def child():
         print("%s\t%.1f" % (c["name"], statistics.median(t[5:])))
         d.close()
     else:
-        for chain in (synthesis, masking, batches, denoise):
+        for chain in (synthesis, masking, batches, streams, denoise):
             for name, sha in chain(eng):
                 print("%s\t%s" % (name, sha), flush=True)
     eng.close()
