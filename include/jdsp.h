@@ -20,10 +20,38 @@
  *     handle's HIP stream: no allocation and no synchronisation once the
  *     handle is warm, i.e. after one call of that entry point (constant tables
  *     are built on first use) and after the matching *_reserve() where the
- *     entry has a workspace (jdsp_denoise_reserve, jdsp_hmm_reserve).  A warm
- *     "_dev" call can be captured into a hipGraph (bench.py does that).
+ *     entry has a workspace (jdsp_denoise_reserve, jdsp_denoise_batch_reserve,
+ *     jdsp_hmm_reserve, jdsp_fastconv_reserve, jdsp_*_streams_reserve).
  *     The plain entry points take HOST pointers, copy in, run, copy out and
  *     synchronise.
+ *   - GRAPH CAPTURE.  A warm "_dev" call can be captured into a hipGraph (bench.py
+ *     does that; tests/test_graph_replay_gpu.py captures every entry named here).
+ *     What a replay of the captured call does depends on where the entry's state
+ *     lives, in three classes.
+ *       Baked and live arguments, all classes: every SCALAR (n_frames, n_blocks, n_utts, n_chunks, n_ids,
+ *       n_frames_total, n_blocks_total, pitches, hops, methods, orders) and every POINTER is baked into the graph at
+ *       capture.  Read at replay: the CONTENTS of the buffers, and with them the device-side offset and id arrays
+ *       (sample_first, frame_first, block_first, utt_first, frame_start, stream_id).  A replay may therefore deal the same
+ *       n_frames_total among the same n_utts / n_chunks differently, move the spans, and name other streams.
+ *       Class S, stateless: jdsp_stft_i16_dev, jdsp_stft_half_i16_dev, jdsp_stft_i16_f64_dev, jdsp_stft_half_batch_dev,
+ *         jdsp_istft_batch_dev, jdsp_stftmask_batch_dev, jdsp_denoise_batch_dev, jdsp_mfcc_frames_dev,
+ *         jdsp_pitch_autocorr_dev, jdsp_pitch_lag_dev, jdsp_lpc_dev, jdsp_gmm_score_dev, jdsp_hmm_viterbi_dev,
+ *         jdsp_fft_process_f64_dev.  Every replay recomputes from what the buffers hold at that time and equals an
+ *         eager call on the same contents, bit for bit.  Replay as often as wanted.
+ *       Class D, state on the device only: jdsp_geq_process_dev, jdsp_nlms_process_dev, and the live streams
+ *         jdsp_stftmask_streams_dev / _streams_flush_dev / _streams_reset_dev and jdsp_istft_streams_dev /
+ *         _streams_flush_dev / _streams_reset_dev.  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
+ *         replay (or eager call) before it left, exactly as another eager call would.  Replay as often as wanted.
+ *       Class H, state the host carries (which ping-pong copy is current, the stream position, passed to the kernels
+ *         as arguments): jdsp_istft_process_dev / _flush_dev, jdsp_stftmask_process_dev / _flush_dev,
+ *         jdsp_denoise_process_dev, jdsp_fastconv_process_dev, jdsp_mvdr_process_dev, jdsp_mvdrn_process_dev.  A
+ *         captured call BELONGS TO THE HANDLE'S POSITION AT CAPTURE.  The host state advances when the call is
+ *         captured; the device catches up when the graph is replayed.  So the graph (of one call or of several
+ *         consecutive ones) may be replayed ONCE, there: nothing else may touch the handle between the capture and that
+ *         replay, and the handle's reset (or a flush, which resets) invalidates the graph.  A second replay reads the
+ *         stale copy and gives a wrong stream WITHOUT AN ERROR.  The replayable form of a jdsp_istft / jdsp_stftmask
+ *         stream is the same handle's live-stream entries with n_streams = 1 (class D).
+ *     The shard entries and the training entries are not covered by this promise.
  *   - spectra are interleaved (re, im) float pairs, full length n_fft per frame
  *     exactly like the reference's fftw_complex[FFT_PROCESSING_SIZE] buffers
  *     (SpectralSubtraction_final.cpp:205-206), in single precision.
@@ -215,9 +243,14 @@ int jdsp_stft_i16_f64(jdsp_ctx *ctx, const int16_t *pcm_host, long n_samples, in
  * n = 1024, hop = 512, FULL, NONE, NONE is SS:244-257 exactly.
  * Supported: n_fft 1024 or 512 with hop = n, n/2 or n/4.  Alignment: spec 8 bytes (a jdsp_c32), out_i16 4 bytes,
  * out_f32 8 bytes; anything else, or a row_pitch below the layout's bin count, is JDSP_EINVAL.  The _dev entries only
- * enqueue on the handle's stream (no allocation, no host synchronisation; graph-capturable); the state is n_fft floats
+ * enqueue on the handle's stream (no allocation, no host synchronisation); the state is n_fft floats
  * twice (ping-pong) plus the window and gain tables, allocated at create.  jdsp_istft_process / _flush: host
- * pointers, synchronous (device buffers grown on demand in the handle). */
+ * pointers, synchronous (device buffers grown on demand in the handle).
+ * Graph capture (Conventions): _process_dev and _flush_dev are class H -- WHICH of the two tails is current is host
+ * state passed to the launch, so a captured call, or a captured run of consecutive calls, is graph-capturable ONCE, AT
+ * THE STREAM POSITION IT WAS CAPTURED AT: replay it once, let nothing else touch the handle between capture and replay,
+ * and capture again after _reset / _flush.  To replay one graph per delivery use the live-stream entries below with
+ * n_streams = 1: the same stream, bit for bit, with its state on the device (class D).  _batch_dev is class S. */
 typedef struct jdsp_istft jdsp_istft;
 enum { JDSP_SPEC_FULL = 0, JDSP_SPEC_HALF = 1 };
 enum { JDSP_WIN_NONE = -1, JDSP_WIN_HAMMING = 0, JDSP_WIN_HANN = 1 };   /* numbering of "stft.window" */
@@ -315,9 +348,13 @@ int  jdsp_istft_streams_flush(jdsp_istft *h, const int64_t *stream_id_host, cons
  * Supported: n_fft = 1024 with hop 1024, 512 or 256; both mask kinds.  (n_fft = 512 is JDSP_EINVAL: DESIGN.md 7.)
  * Alignment: pcm and out_i16 4 bytes, out_f32 8 bytes, a REAL mask 4 bytes, a COMPLEX mask 8 bytes; anything else, a
  * mask_pitch in 1..n/2 or n_frames < 0 is JDSP_EINVAL with a jdsp_last_error text.  The _dev entries only enqueue on
- * the handle's stream (no allocation, no host synchronisation; graph-capturable); the state -- two tails (ping-pong),
+ * the handle's stream (no allocation, no host synchronisation); the state -- two tails (ping-pong),
  * the windows and the gain, the FP64 pass's tables and count -- is allocated at create.  jdsp_stftmask_process / _flush: host pointers, synchronous
- * (device buffers grown on demand in the handle). */
+ * (device buffers grown on demand in the handle).
+ * Graph capture (Conventions): _process_dev and _flush_dev are class H, as on jdsp_istft -- graph-capturable ONCE, AT THE
+ * STREAM POSITION THEY WERE CAPTURED AT: one replay, nothing else on the handle between capture and replay, capture
+ * again after _reset / _flush.  A caller that replays one graph per delivery uses jdsp_stftmask_streams_dev with
+ * n_streams = 1 (class D): the same stream, bit for bit.  _batch_dev is class S. */
 typedef struct jdsp_stftmask jdsp_stftmask;
 enum { JDSP_MASK_REAL = 0, JDSP_MASK_COMPLEX = 1 };
 typedef struct { int n_fft, hop, analysis_window, synthesis_window, normalise, mask_kind; } jdsp_stftmask_cfg;
@@ -329,8 +366,9 @@ int  jdsp_stftmask_reset(jdsp_stftmask *h);
 int  jdsp_stftmask_set_option(jdsp_stftmask *h, const char *name, long value);
 long jdsp_stftmask_samples_out(const jdsp_stftmask *h, long n_frames);
 /* Frames of the last _process / _batch call (host or device entry) that were computed again in FP64; 0 before any call
- * and after reset.  Waits for the handle's stream.  (A captured _dev call replayed from a graph back to back counts under the
- * one call number it was captured with: the figure is then the sum over those replays.) */
+ * and after reset.  Waits for the handle's stream.  (The call number is a scalar baked at capture: a captured _dev call
+ * replayed from a graph back to back counts under the one number it was captured with, and the figure is then the sum
+ * over those replays; a call in between under the next number zeroes it.) */
 long jdsp_stftmask_frames_recomputed(const jdsp_stftmask *h);
 int  jdsp_stftmask_process_dev(jdsp_stftmask *h, const int16_t *pcm_dev, const void *mask_dev, long mask_pitch,
                                long n_frames, int16_t *out_i16_dev, float *out_f32_dev);
@@ -403,7 +441,12 @@ int  jdsp_stftmask_batch(jdsp_stftmask *h, const int16_t *pcm_host, long n_sampl
  *     both outputs NULL it only resets them).  _streams_reset_dev zeroes the listed streams, or all when stream_id_dev
  *     is NULL (n_ids is then ignored).  Ids are distinct and in range, as above.
  *   - Every _dev entry only enqueues on the stream _process_dev uses: no allocation, no host synchronisation, no host
- *     read of the arrays, and nothing baked into a launch that would make a replayed capture wrong.
+ *     read of the arrays, and nothing baked into a launch that would make a replayed capture wrong.  They are
+ *     graph-capturable, class D (Conventions): n_chunks / n_ids, n_frames_total, the pitches and the pointers are baked;
+ *     stream_id, sample_first, frame_first and the buffers are read at replay; EVERY REPLAY ADVANCES the streams it
+ *     names then from where they stand then, so one captured delivery (or a captured run of deliveries, flushes and
+ *     resets) serves every later one of the same n_chunks and n_frames_total.  With n_streams = 1 this is the
+ *     replayable form of the handle's own _process_dev / _flush_dev stream, which is class H.
  *   - jdsp_stftmask_streams / _streams_flush: host pointers, synchronous, check everything; pcm and the outputs are
  *     n_samples long and the outputs ZERO outside the written ranges.  For the flush the spans are the n - hop
  *     samples at each sample_first[i] (even, ascending, disjoint, inside n_samples). */
@@ -504,7 +547,9 @@ int jdsp_denoise_vad_trace(jdsp_denoise *h, long n, uint8_t *voice_host, int64_t
  *     stream sums its noise average in chunks).
  *   - jdsp_denoise_batch_dev only enqueues on the context's stream: no allocation, no host synchronisation, no host
  *     read of the two offset arrays (int64, [n_utts] and [n_utts + 1], 8-byte aligned) -- hence n_blocks_total, which
- *     must equal block_first[n_utts].  It is graph-capturable.  The device-side offsets are the caller's contract, the
+ *     must equal block_first[n_utts].  It is graph-capturable, class S (Conventions): n_utts and n_blocks_total are
+ *     baked, the two offset arrays and the PCM are read at every replay, and a replay equals an eager call on the same
+ *     contents bit for bit, as often as it is replayed.  The device-side offsets are the caller's contract, the
  *     one of jdsp_stftmask_batch_dev: block_first[0] = 0 and non-decreasing; every sample_first[u] even, >= 0 and
  *     ascending; the spans, hop B_u long, disjoint and inside pcm and the outputs.  No PCM outside the spans is read.
  *     pcm and out 16-byte, precast 8-byte aligned, as in jdsp_denoise_process_dev.
