@@ -628,7 +628,14 @@ int jdsp_denoise_apply(jdsp_denoise *h, const int16_t *pcm_host, long n_blocks, 
  * stream produce no output (:119-123) and never reach the transform (the reference queues
  * uninitialised buffers for them, :120 -- defined as silence here).  out: n_filters planes of
  * n_out*block int16, plane-major; precast (may be NULL): the same values before the (short)
- * cast.  The handle carries the last n_taps-1 samples between calls. */
+ * cast.  The handle carries the samples its next call reaches back to (the last n_taps-1; the
+ * partitioned form: the last 512 ceil(n_taps/512)), so consecutive calls on one handle give the
+ * same bits, int16 and pre-cast, however the stream is cut into them, through either entry (not
+ * after jdsp_fastconv_set_position: see there).
+ * Alignment of pcm_dev, out_dev and precast_dev: natural alignment (2, 2 and 4 bytes).  The
+ * partitioned form stores two int16 as one dword and two pre-cast floats as one 8-byte store
+ * at whatever address that gives: at an odd sample / float offset these are unaligned stores,
+ * which the device takes as they are (global memory runs in unaligned-access mode under ROCm). */
 typedef struct jdsp_fastconv jdsp_fastconv;
 int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_filters, int n_fft,
                          jdsp_fastconv **out);
@@ -637,7 +644,10 @@ int jdsp_fastconv_reset(jdsp_fastconv *h);
 /* Multi-GPU / random access: pretend `blocks_consumed` blocks of the stream have already been
  * processed (history = silence).  A rank that owns output blocks [e0, e1) of a stream feeds
  * input blocks [e0 + hist_blocks - hist_blocks', ...): see sharding.fastconv_sharded -- it
- * prepends hist_blocks halo blocks and drops the outputs they produce. */
+ * prepends hist_blocks halo blocks and drops the outputs they produce.  The partitioned form's
+ * oldest frame reaches 512 ceil(n_taps/512) samples back, up to 512 more than the halo holds;
+ * they weigh nothing in the sum but are in the frame the transform rounds, so a position set
+ * this way equals the uncut stream within the 1e-5 bar, not bit for bit. */
 int jdsp_fastconv_set_position(jdsp_fastconv *h, long blocks_consumed);
 int jdsp_fastconv_block_len(const jdsp_fastconv *h);
 int jdsp_fastconv_hist_blocks(const jdsp_fastconv *h);

@@ -34,7 +34,14 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
     for (int f = 0; f < n_filters; f++)
         for (int i = 0; i < n_taps; i++) hpad[2 * ((size_t)f * n_fft + i)] = taps[(size_t)f * n_taps + i];
     hipError_t e = h->H.alloc(n);
-    const int hl = n_taps - 1 > 0 ? n_taps - 1 : 1;
+    // Uniformly partitioned form of the same convolution (fastconv_kernels.hip).  JDSP_FASTCONV_PARTITIONED=0 keeps the
+    // 8192-point kernel.  Its oldest frame starts 512 n_part samples back; the taps reach n_taps - 1 < 512 n_part back,
+    // so the samples in between weigh nothing in the sum -- but they are in the frame the transform rounds.  The handle
+    // carries all of them, and a stream gives the same bits however it is cut into calls.
+    const char *env = getenv("JDSP_FASTCONV_PARTITIONED");
+    const bool partitioned = n_fft == 8192 && h->block % 512 == 0 && !(env && env[0] == '0');
+    h->hist_len = partitioned ? 512 * ((n_taps + 511) / 512) : n_taps - 1;
+    const int hl = h->hist_len > 0 ? h->hist_len : 1;
     for (int i = 0; i < 2 && e == hipSuccess; i++) e = h->hist[i].alloc((size_t)hl);
     if (e == hipSuccess && n_fft == 8192 && !ctx->conv_tw8192.get()) {
         std::vector<float2> a(4096), b(4096);
@@ -54,10 +61,8 @@ int jdsp_fastconv_create(jdsp_ctx *ctx, const double *taps, int n_taps, int n_fi
             hc.result(fail(ctx, JDSP_EHIP, "spectrum_to_f32 launch", hipGetLastError()));
         rc = hc.finish();
     }
-    // Uniformly partitioned form of the same convolution (fastconv_kernels.hip): spectra of the 512-tap
-    // partitions, each zero-padded to 1024, bins 0..512.  JDSP_FASTCONV_PARTITIONED=0 keeps the 8192-point kernel.
-    const char *env = getenv("JDSP_FASTCONV_PARTITIONED");
-    if (!rc && n_fft == 8192 && h->block % 512 == 0 && !(env && env[0] == '0')) {
+    // spectra of the 512-tap partitions, each zero-padded to 1024, bins 0..512
+    if (!rc && partitioned) {
         const int P = (n_taps + 511) / 512;
         const size_t rows = (size_t)n_filters * P;
         std::vector<double> part(rows * 1024 * 2, 0.0);
@@ -99,7 +104,7 @@ int jdsp_fastconv_destroy(jdsp_fastconv *h)
 int jdsp_fastconv_reset(jdsp_fastconv *h)
 {
     if (!h) return JDSP_EINVAL;
-    const int hl = h->n_taps - 1 > 0 ? h->n_taps - 1 : 1;
+    const int hl = h->hist_len > 0 ? h->hist_len : 1;
     for (int i = 0; i < 2; i++) JDSP_HIP(h->ctx, hipMemsetAsync(h->hist[i].get(), 0, (size_t)hl * sizeof(short), h->ctx->stream));
     h->calls = 0;
     h->cur = 0;
@@ -161,7 +166,7 @@ int jdsp_fastconv_process_dev(jdsp_fastconv *h, const int16_t *pcm_dev, long n_b
     s.n_samples = n_blocks * h->block;
     s.global0 = h->calls * h->block;
     s.valid_from = (long)h->n_hist * h->block;
-    s.hist_len = h->n_taps - 1;
+    s.hist_len = h->hist_len;
     const int first = (int)(n_blocks - n_out);
     if (h->n_part) {
         int rc = jdsp_fastconv_reserve(h, n_blocks);

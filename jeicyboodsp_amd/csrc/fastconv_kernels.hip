@@ -786,6 +786,8 @@ __global__ __launch_bounds__(kUpolsWaves * 64) void fastconv_upols4_kernel(const
                 wave_lds_fence();
                 wave_fft512<true>(y, lds, lane, tw);
                 wave_lds_fence();
+                // out is 2-byte and precast 4-byte aligned (jdsp.h): at an odd sample / float offset the dword and the
+                // float2 store below are unaligned; global memory takes them (unaligned-access mode), no address test here
                 unsigned int *o = reinterpret_cast<unsigned int *>(out + (size_t)f * plane + t * 512) + lane;
                 float *pc = precast ? precast + (size_t)f * plane + t * 512 : nullptr;
 #pragma unroll

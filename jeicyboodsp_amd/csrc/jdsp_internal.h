@@ -660,7 +660,8 @@ struct jdsp_fastconv {
     jdsp::DevBuf<short> staged;           // [512 n_part + samples of a call]
     jdsp::DevBuf<float2> X;               // [frames][520]
     long ws_samples = 0;                  // samples per call the workspace is sized for
-    jdsp::DevBuf<short> hist[2];          // last n_taps-1 samples of the stream, ping-pong
+    jdsp::DevBuf<short> hist[2];          // last hist_len samples of the stream, ping-pong
+    int hist_len = 0;                     // n_taps - 1; partitioned: 512 n_part, every sample a call's first frames read
     int cur = 0;
     long calls = 0;                       // blocks consumed so far (siNumOfCount)
 };

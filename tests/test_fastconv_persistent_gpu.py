@@ -35,8 +35,8 @@ def _pcm(seed, n, sigma=2000.0):
 def _hrir(seed, n_filters):
     rng = np.random.default_rng(seed)
     h = np.stack([rng.normal(size=256) * np.exp(-np.arange(256) / (40.0 + 15.0 * f)) for f in range(n_filters)])
-    # unit energy: the output stays at the input's level (sigma 2000), far from +-32768 -- past it `(short)double` is
-    # undefined in the reference (3D:166) and a 1e-5 difference before the cast becomes 65,535 after it
+    # unit energy: the output stays at the input's level (sigma 2000), inside int16; pre-cast values past +-32768 are
+    # compared across the wrap in test_fastconv_streams_gpu.py::test_wrap_like_the_oracle_cast
     return h / np.sqrt((h * h).sum(axis=1, keepdims=True))
 
 

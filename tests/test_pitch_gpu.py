@@ -82,3 +82,64 @@ def test_pitch_silence_and_compat_calcpitch(eng, oracle, tmp_path):
     o_arg, o_max, o_ac = oracle.pitch_stream(pcm)
     at_ours = o_ac[np.arange(12), got]
     assert np.all((got == o_arg) | (o_max - at_ours <= 1e-5 * o_ac[:, 0]))
+
+
+# ---- the input families of the time-domain pitch entries (timedomain_ref.pitch_families), and a DC offset ----------
+ORDERED = ("voiced", "white", "mixed", "dc_offset")        # families whose maxima FP32 can order: the share is asserted
+
+
+def families(n_blocks):
+    import timedomain_ref as T
+    fam = dict(T.pitch_families(n_blocks))
+    fam["dc_offset"] = (T.voiced(11, n_blocks).astype(np.int32) + 12000).astype(np.int16)
+    assert np.abs(fam["dc_offset"].astype(np.int32) - 12000).max() < 20000          # nothing clipped or wrapped
+    return fam
+
+
+def check_family(name, arg, rmax, ac, o_arg, o_max, o_ac):
+    """check()'s rules; the share of equal lags only where the family has an order to find (on constant, silence and
+    full_scale every lag may tie with the maximum within the tolerance, and the tie rule is the whole check)"""
+    scale = o_ac[:, 0] + 1.0
+    err = float((np.abs(ac - o_ac) / scale[:, None]).max())
+    tol = 1e-5 * scale
+    same = arg == o_arg
+    at_ours = o_ac[np.arange(len(arg)), arg]
+    print("PITCH %-10s %2d blocks: autocorr %.3g of r[0] + 1, rmax %.3g, lags equal %d of %d"
+          % (name, len(arg), err, float((np.abs(rmax - o_max) / scale).max()), int(same.sum()), len(arg)))
+    assert err < 1e-5
+    assert np.all(np.abs(rmax - o_max) <= tol)
+    assert np.all(same | (o_max - at_ours <= tol))
+    assert np.all((arg >= 101) & (arg <= 511))
+    if name in ORDERED:
+        assert same.mean() > 0.98
+    if name == "silence":
+        assert np.all(arg == 101) and not rmax.any() and not ac.any()
+
+
+@pytest.mark.parametrize("n_blocks", [1, 2, 50])
+def test_pitch_families_host_and_device_with_hand_over(eng, oracle, n_blocks):
+    import torch
+    for name, pcm in families(n_blocks).items():
+        o_arg, o_max, o_ac = oracle.pitch_stream(pcm)
+        arg, rmax, ac = eng.pitch(pcm, want_autocorr=True)                                 # host entry
+        check_family(name, arg, rmax, ac, o_arg, o_max, o_ac)
+        t = torch.from_numpy(pcm).cuda()
+        d_arg, d_max, d_ac = eng.pitch(t, want_autocorr=True)                              # device entry
+        torch.cuda.synchronize()
+        d_arg, d_max, d_ac = d_arg.cpu().numpy(), d_max.cpu().numpy(), d_ac.cpu().numpy()
+        check_family(name, d_arg, d_max, d_ac, o_arg, o_max, o_ac)
+        assert np.array_equal(d_arg, arg) and np.array_equal(d_max.view(np.uint32), rmax.view(np.uint32))
+        assert np.array_equal(d_ac.view(np.uint32), ac.view(np.uint32))
+        if n_blocks < 2:
+            continue
+        # a cut with the keep buffer handed over: the blocks after it are the one-call stream's, bit for bit
+        c = n_blocks // 2
+        prev = pcm[(c - 1) * 512:c * 512]
+        h_arg, h_max, h_ac = eng.pitch(pcm[c * 512:], prev_block=prev, want_autocorr=True)
+        assert np.array_equal(h_arg, arg[c:]) and np.array_equal(h_max.view(np.uint32), rmax[c:].view(np.uint32))
+        assert np.array_equal(h_ac.view(np.uint32), ac[c:].view(np.uint32))
+        c_arg, c_max, c_ac = eng.pitch(t[c * 512:], prev_block=t[(c - 1) * 512:c * 512].clone(), want_autocorr=True)
+        torch.cuda.synchronize()
+        assert np.array_equal(c_arg.cpu().numpy(), arg[c:])
+        assert np.array_equal(c_max.cpu().numpy().view(np.uint32), rmax[c:].view(np.uint32))
+        assert np.array_equal(c_ac.cpu().numpy().view(np.uint32), ac[c:].view(np.uint32))
