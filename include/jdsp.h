@@ -40,7 +40,8 @@
  *         eager call on the same contents, bit for bit.  Replay as often as wanted.
  *       Class D, state on the device only: jdsp_geq_process_dev, jdsp_nlms_process_dev, and the live streams
  *         jdsp_stftmask_streams_dev / _streams_flush_dev / _streams_reset_dev and jdsp_istft_streams_dev /
- *         _streams_flush_dev / _streams_reset_dev.  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
+ *         _streams_flush_dev / _streams_reset_dev, and jdsp_denoise_streams_dev / jdsp_denoise_streams_reset_dev
+ *         (their *_reserve: jdsp_denoise_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
  *         replay (or eager call) before it left, exactly as another eager call would.  Replay as often as wanted.
  *       Class H, state the host carries (which ping-pong copy is current, the stream position, passed to the kernels
  *         as arguments): jdsp_istft_process_dev / _flush_dev, jdsp_stftmask_process_dev / _flush_dev,
@@ -75,7 +76,7 @@ extern "C" {
  *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added; the ragged-batch
  *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added;
  *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
- *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added
+ *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -573,6 +574,63 @@ int jdsp_denoise_batch_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_
 int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
                        const int64_t *block_first_host, long n_utts, int16_t *out_host, float *precast_host,
                        uint8_t *flags_host, float *noise_last_host);                   /* host path, synchronous */
+
+/* LIVE STREAMS on the denoise handle: n_streams independent streams of the reference's main() in the handle, next to
+ * its own one, whose statics (run length, running average, latched estimate, call counter, previous blocks, overlap)
+ * live ON THE DEVICE and are carried from call to call.  One call advances any subset of them by a chunk of blocks each,
+ * in one launch sequence.  The handle's own _process stream and the _batch entries are neither read nor written, and may
+ * be interleaved with these entries on the same handle.  (1024, 512) handles only: on a (512, 256) handle every entry
+ * here returns JDSP_EINVAL with a text, as the batch entries do.  (Vocabulary: jdsp_stftmask_streams_*, above.)
+ *   - A CHUNK is what one stream contributes to one call.  Chunk c belongs to stream stream_id[c] and holds B_c =
+ *     block_first[c + 1] - block_first[c] NEW blocks (>= 0) of hop = 512 samples at pcm[sample_first[c] .. + hop B_c):
+ *     jdsp_denoise_batch_dev's layout with chunks for utterances, plus stream_id.  The handle keeps the history it needs.
+ *   - EMISSION FOLLOWS THE STREAM.  A stream's block with index i (0-based, counted over all its calls) emits iff
+ *     i >= 2 (SS:260-263); the emitted block is the enhanced signal at the time of input block i - 1, as in _process.
+ *     For a stream that had seen N blocks the chunk emits E_c = B_c - max(0, min(B_c, 2 - N)) blocks, written PACKED at
+ *     out[sample_first[c] + hop e .. + hop), e < E_c; precast likewise.  The other hop (B_c - E_c) samples of the span
+ *     and everything outside the spans are neither written nor read.  There is NO FLUSH: the reference never emits a
+ *     stream's overlap at its end; a reset ends a stream.
+ *   - EQUIVALENCE, BIT FOR BIT: the emitted blocks of a stream, concatenated over its calls, are what
+ *     jdsp_denoise_batch writes for ONE utterance of all those blocks (batch output block k + 1 = emission k), on out,
+ *     precast, the VAD flags and the estimate in force (noise_last) -- however the blocks are cut into chunks and
+ *     calls, in whatever order the chunks stand, for every "blocks_per_wave" and both modes, frames that go through the
+ *     FP64 pass included.  A stream with no chunk in a call, or with a chunk of 0 blocks, is not touched.
+ *   - jdsp_denoise_streams_reserve(h, n_streams, max_blocks_total) is the only call that allocates, and it synchronises.
+ *     All streams start fresh; calling it again discards every stream.  Before it the other entries return JDSP_EINVAL
+ *     with a text.  Per stream 18,972 bytes of state: the last two blocks (2,048) and the overlap (2,048), each held
+ *     twice so that no launch reads memory it writes, the estimate twice (8,192), the running average (2,560) and
+ *     28 bytes of words.  Per call a workspace for max_blocks_total blocks: per block 1 (flag) + 4 (row index) + 4 (FP64
+ *     list) bytes, per stream 8 (a chunk's latch flag and list entry), and n_streams + max_blocks_total / 11 + 2 latched
+ *     rows of 4 KB.  A call beyond it is JDSP_EINVAL.
+ *   - jdsp_denoise_streams_dev and jdsp_denoise_streams_reset_dev only enqueue on the stream jdsp_denoise_batch_dev
+ *     uses: no allocation, no host synchronisation, no host read of the arrays.  Graph-capturable, class D
+ *     (Conventions): n_chunks / n_ids, n_blocks_total and the pointers are baked; ids, offsets and buffers are read at
+ *     replay, and every replay advances the named streams from where they stand.  The caller's contract on the device:
+ *     ids in [0, n_streams) and distinct within a call; n_chunks <= n_streams (checked); block_first[0] = 0,
+ *     non-decreasing, block_first[n_chunks] = n_blocks_total; sample_first even; the spans disjoint and inside the
+ *     buffers; pcm and out 16-byte, precast, n_emitted and the int64 arrays 8-byte aligned.
+ *   - flags [n_blocks_total] uint8 in concatenated block order; n_emitted [n_chunks] int64 = E_c.  Any output pointer
+ *     may be NULL.  With out and precast both NULL the state still advances exactly as with them (the VAD, the noise
+ *     estimate, the blocks and the overlap; nothing is emitted).  n_chunks == 0 or n_blocks_total == 0 launches nothing
+ *     and changes nothing.  reset_dev: the n_ids listed streams fresh again; stream_id_dev NULL: all of them.
+ *   - jdsp_denoise_streams (host pointers, synchronous) checks all of that, with sample_first ascending as in
+ *     jdsp_denoise_batch, and on a violation returns JDSP_EINVAL with a jdsp_last_error text and leaves every stream as
+ *     it was.  pcm, out and precast are n_samples long; the outputs are ZERO wherever the device entry would not write.
+ *   - jdsp_denoise_frames_recomputed reports a _streams call like any other.  A listed frame whose second output block
+ *     arrives with the stream's next call is computed in FP64 again there, and counts in both calls.
+ *   - jdsp_denoise_streams_state: [n_ids][1024] float32 estimates in force, in the layout of the batch entry's
+ *     noise_last (zeros: nothing has latched), and the blocks each stream has seen.  Synchronises; either may be NULL. */
+int jdsp_denoise_streams_reserve(jdsp_denoise *h, long n_streams, long max_blocks_total);
+int jdsp_denoise_streams_reset_dev(jdsp_denoise *h, const int64_t *stream_id_dev, long n_ids);   /* NULL: all */
+int jdsp_denoise_streams_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_t *stream_id_dev,
+                             const int64_t *sample_first_dev, const int64_t *block_first_dev, long n_chunks,
+                             long n_blocks_total, int16_t *out_dev, float *precast_dev, uint8_t *flags_dev,
+                             int64_t *n_emitted_dev);
+int jdsp_denoise_streams(jdsp_denoise *h, const int16_t *pcm_host, long n_samples, const int64_t *stream_id_host,
+                         const int64_t *sample_first_host, const int64_t *block_first_host, long n_chunks,
+                         int16_t *out_host, float *precast_host, uint8_t *flags_host, int64_t *n_emitted_host);
+int jdsp_denoise_streams_state(jdsp_denoise *h, const int64_t *stream_id_host, long n_ids, float *noise_host,
+                               int64_t *blocks_seen_host);      /* synchronises; either output may be NULL */
 
 /* Sharded denoise: one rank's share of ONE global stream of n_total blocks (multi-GPU,
  * SURVEY §8e).  The rank owns global blocks [b0, b1); pcm_ext_dev holds global blocks

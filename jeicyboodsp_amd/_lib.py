@@ -95,6 +95,11 @@ def _load():
         "jdsp_denoise_batch_reserve": (i, [vp, l, l]),
         "jdsp_denoise_batch_dev": (i, [vp, vp, vp, vp, l, l, vp, vp, vp, vp]),
         "jdsp_denoise_batch": (i, [vp, vp, l, vp, vp, l, vp, vp, vp, vp]),
+        "jdsp_denoise_streams_reserve": (i, [vp, l, l]),
+        "jdsp_denoise_streams_reset_dev": (i, [vp, vp, l]),
+        "jdsp_denoise_streams_dev": (i, [vp, vp, vp, vp, vp, l, l, vp, vp, vp, vp]),
+        "jdsp_denoise_streams": (i, [vp, vp, l, vp, vp, vp, l, vp, vp, vp, vp]),
+        "jdsp_denoise_streams_state": (i, [vp, vp, l, vp, vp]),
         "jdsp_gmm_create": (i, [vp, vp, i, C.POINTER(vp)]),
         "jdsp_gmm_destroy": (i, [vp]),
         "jdsp_gmm_set_option": (i, [vp, C.c_char_p, l]),

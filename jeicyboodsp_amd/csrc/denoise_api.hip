@@ -525,6 +525,219 @@ int jdsp_denoise_batch(jdsp_denoise *h, const int16_t *pcm_host, long n_samples,
     return hc.finish();
 }
 
+/* ---- live streams: chunks that continue carried streams (include/jdsp.h "live denoise streams") --- */
+static int live_open(jdsp_denoise *h, const char *what)
+{
+    if (h->lws.n_streams) return JDSP_OK;
+    return fail(h->ctx, JDSP_EINVAL, (std::string(what) + ": no live streams (call jdsp_denoise_streams_reserve first)").c_str());
+}
+
+// every stream fresh: zeros everywhere (both parities 0)
+static hipError_t live_zero(jdsp_denoise *h)
+{
+    jdsp_denoise::LiveWs &w = h->lws;
+    hipError_t e = hipMemsetAsync(w.state.get(), 0, w.state.count(), h->ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w.rows.get(), 0, (size_t)w.n_streams * 2 * 1024 * sizeof(float), h->ctx->stream);
+    return e;
+}
+
+int jdsp_denoise_streams_reserve(jdsp_denoise *h, long n_streams, long max_blocks_total)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    int rc = batch_supported(h, "jdsp_denoise_streams_reserve");
+    if (rc) return rc;
+    if (n_streams < 1 || n_streams > 0x3fffffffL || max_blocks_total < 0 || max_blocks_total > 0x3ffffff0L)
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_reserve: n_streams must be 1 .. 2^30 - 1, max_blocks_total 0 .. 2^30 - 16");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));          // nothing enqueued still uses the old buffers
+    jdsp_denoise::LiveWs &w = h->lws;
+    w = {};
+    if (h->redo_valid == 3) h->redo_valid = 0;
+    const size_t n = (size_t)n_streams, nb = (size_t)max_blocks_total;
+    // the state's parts in one allocation, the widest alignment first
+    const size_t b_seen = n * sizeof(long long), b_tail = 2 * n * 512 * sizeof(float),
+                 b_avg = n * jdsp::kLiveAvgFloats * sizeof(float), b_prev = 2 * n * 1024 * sizeof(short),
+                 b_word = n * sizeof(int);
+    hipError_t e = w.state.alloc(b_seen + b_tail + b_avg + b_prev + 5 * b_word);
+    if (e == hipSuccess) e = w.rows.alloc((2 * n + n + nb / 11 + 2) * 1024);
+    if (e == hipSuccess) e = w.flags.alloc(nb + 1);
+    if (e == hipSuccess) e = w.row_idx.alloc(nb + 1);
+    if (e == hipSuccess) e = w.redo.alloc(1 + nb + n);
+    if (e == hipSuccess) e = w.latched.alloc(n);
+    if (e == hipSuccess) {
+        char *p = w.state.get();
+        w.seen = reinterpret_cast<long long *>(p), p += b_seen;
+        float *tail = reinterpret_cast<float *>(p);
+        p += b_tail;
+        float *avg = reinterpret_cast<float *>(p);
+        p += b_avg;
+        short *prev = reinterpret_cast<short *>(p);
+        p += b_prev;
+        int *word = reinterpret_cast<int *>(p);
+        w.parity = word, w.est_parity = word + n;
+        w.view = {w.parity, w.est_parity, w.seen, word + 2 * n, word + 3 * n, prev, tail, avg, w.rows.get(), w.latched.get(),
+                  n_streams};
+        w.n_streams = n_streams;
+        e = live_zero(h);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    if (e != hipSuccess) {
+        w = {};
+        return fail(ctx, e == hipErrorOutOfMemory ? JDSP_ENOMEM : JDSP_EHIP, "jdsp_denoise_streams_reserve", e);
+    }
+    w.cap_blocks = max_blocks_total;
+    return JDSP_OK;
+}
+
+int jdsp_denoise_streams_reset_dev(jdsp_denoise *h, const int64_t *stream_id_dev, long n_ids)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    int rc = batch_supported(h, "jdsp_denoise_streams_reset_dev");
+    if (!rc) rc = live_open(h, "jdsp_denoise_streams_reset_dev");
+    if (rc) return rc;
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    jdsp_denoise::LiveWs &w = h->lws;
+    if (!stream_id_dev) {
+        JDSP_HIP(ctx, live_zero(h));
+        return JDSP_OK;
+    }
+    if (n_ids < 0 || n_ids > w.n_streams)
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_reset_dev: n_ids must be 0 .. n_streams (ids are distinct within a call)");
+    if (!jdsp::aligned(stream_id_dev, 8)) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_reset_dev: stream_id must be 8-byte aligned");
+    if (jdsp::launch_denoise_live_reset(ctx->stream, reinterpret_cast<const long long *>(stream_id_dev), n_ids, w.view,
+                                        w.parity, w.est_parity, w.seen))
+        return fail(ctx, JDSP_EHIP, "jdsp_denoise_streams_reset_dev: launch", hipGetLastError());
+    return JDSP_OK;
+}
+
+// the scalar checks both entries make before anything else
+static int live_counts(jdsp_denoise *h, const char *what, long n_chunks, long n_blocks_total)
+{
+    jdsp_ctx *ctx = h->ctx;
+    int rc = batch_supported(h, what);
+    if (!rc) rc = live_open(h, what);
+    if (rc) return rc;
+    const std::string e(what);
+    if (n_chunks < 0 || n_blocks_total < 0) return fail(ctx, JDSP_EINVAL, (e + ": n_chunks or the number of blocks < 0").c_str());
+    if (n_chunks > h->lws.n_streams)
+        return fail(ctx, JDSP_EINVAL, (e + ": more chunks than live streams (ids are distinct within a call)").c_str());
+    if (n_blocks_total > h->lws.cap_blocks)
+        return fail(ctx, JDSP_EINVAL, (e + ": more blocks than jdsp_denoise_streams_reserve sized the workspace for").c_str());
+    return JDSP_OK;
+}
+
+int jdsp_denoise_streams_dev(jdsp_denoise *h, const int16_t *pcm_dev, const int64_t *stream_id_dev,
+                             const int64_t *sample_first_dev, const int64_t *block_first_dev, long n_chunks,
+                             long n_blocks_total, int16_t *out_dev, float *precast_dev, uint8_t *flags_dev,
+                             int64_t *n_emitted_dev)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    int rc = live_counts(h, "jdsp_denoise_streams_dev", n_chunks, n_blocks_total);
+    if (rc) return rc;
+    if (!jdsp::aligned(pcm_dev, 16) || !jdsp::aligned(out_dev, 16) || !jdsp::aligned(precast_dev, 8) ||
+        !jdsp::aligned(stream_id_dev, 8) || !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(block_first_dev, 8) ||
+        !jdsp::aligned(n_emitted_dev, 8))
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_dev: pcm and out must be 16-byte, precast, n_emitted, the "
+                                      "stream ids and the offset arrays 8-byte aligned");
+    if (n_chunks == 0 || n_blocks_total == 0) return JDSP_OK;   // nothing launched, nothing changed
+    if (!pcm_dev || !stream_id_dev || !sample_first_dev || !block_first_dev)
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_dev: pcm, stream_id, sample_first or block_first is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    const jdsp_denoise::LiveWs &w = h->lws;
+    if (jdsp::launch_denoise_live(ctx->stream, h->mode, h->opt_k, ctx->n_cu, pcm_dev,
+                                  reinterpret_cast<const long long *>(stream_id_dev),
+                                  reinterpret_cast<const long long *>(sample_first_dev),
+                                  reinterpret_cast<const long long *>(block_first_dev), n_chunks, n_blocks_total, h->w_hi,
+                                  ctx->stft1024_table.get(), flags_dev ? flags_dev : w.flags.get(), w.row_idx.get(),
+                                  w.redo.get(), w.view, w.parity, w.est_parity, w.seen, out_dev, precast_dev,
+                                  reinterpret_cast<long long *>(n_emitted_dev)))
+        return fail(ctx, JDSP_EHIP, "jdsp_denoise_streams_dev: launch", hipGetLastError());
+    h->redo_valid = 3;
+    return JDSP_OK;
+}
+
+int jdsp_denoise_streams(jdsp_denoise *h, const int16_t *pcm_host, long n_samples, const int64_t *stream_id_host,
+                         const int64_t *sample_first_host, const int64_t *block_first_host, long n_chunks,
+                         int16_t *out_host, float *precast_host, uint8_t *flags_host, int64_t *n_emitted_host)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    const char *me = "jdsp_denoise_streams";
+    int rc = live_counts(h, me, n_chunks, 0);
+    if (rc) return rc;
+    if (n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams: n_samples < 0");
+    if (n_chunks > 0 && (!stream_id_host || !sample_first_host || !block_first_host))
+        return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams: stream_id, sample_first or block_first is NULL");
+    const jdsp::StreamIdVerdict v = jdsp::stream_ids_check(stream_id_host, n_chunks, h->lws.n_streams);
+    if (v != jdsp::StreamIdVerdict::kOk) return fail(ctx, JDSP_EINVAL, jdsp::stream_ids_message(v, me).c_str());
+    jdsp::RaggedOffsets offs;
+    if (offs.check(ctx, me, "block_first", sample_first_host, block_first_host, n_chunks, n_samples, h->block, h->block))
+        return JDSP_EINVAL;
+    const long n_total = offs.lay.n_total, end = offs.lay.end;
+    rc = live_counts(h, me, n_chunks, n_total);
+    if (rc) return rc;
+    // what no launch writes is zero
+    if (out_host && n_samples) memset(out_host, 0, (size_t)n_samples * sizeof(int16_t));
+    if (precast_host && n_samples) memset(precast_host, 0, (size_t)n_samples * sizeof(float));
+    if (n_emitted_host && n_chunks) memset(n_emitted_host, 0, (size_t)n_chunks * sizeof(int64_t));
+    if (n_total == 0) return JDSP_OK;                          // nothing to launch
+    if (!pcm_host) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams: pcm is NULL");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    jdsp::HostCall hc(ctx, me);
+    offs.upload(hc);
+    const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_chunks * sizeof(int64_t));
+    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));         // nothing past the last span is read
+    int16_t *d_out = out_host ? hc.alloc<int16_t>((size_t)end * sizeof(int16_t)) : nullptr;
+    float *d_pre = precast_host ? hc.alloc<float>((size_t)end * sizeof(float)) : nullptr;
+    uint8_t *d_flags = flags_host ? hc.alloc<uint8_t>((size_t)n_total) : nullptr;
+    int64_t *d_emit = n_emitted_host ? hc.alloc<int64_t>((size_t)n_chunks * sizeof(int64_t)) : nullptr;
+    if (d_out) hc.zero(d_out, (size_t)end * sizeof(int16_t));
+    if (d_pre) hc.zero(d_pre, (size_t)end * sizeof(float));
+    if (hc.ok())
+        hc.result(jdsp_denoise_streams_dev(h, d_pcm, d_id, offs.d_sample, offs.d_unit, n_chunks, n_total, d_out, d_pre,
+                                           d_flags, d_emit));
+    hc.download(out_host, d_out, d_out ? (size_t)end * sizeof(int16_t) : 0);
+    hc.download(precast_host, d_pre, d_pre ? (size_t)end * sizeof(float) : 0);
+    hc.download(flags_host, d_flags, (size_t)n_total);
+    hc.download(n_emitted_host, d_emit, (size_t)n_chunks * sizeof(int64_t));
+    return hc.finish();
+}
+
+int jdsp_denoise_streams_state(jdsp_denoise *h, const int64_t *stream_id_host, long n_ids, float *noise_host,
+                               int64_t *blocks_seen_host)
+{
+    if (!h) return JDSP_EINVAL;
+    jdsp_ctx *ctx = h->ctx;
+    const char *me = "jdsp_denoise_streams_state";
+    int rc = batch_supported(h, me);
+    if (!rc) rc = live_open(h, me);
+    if (rc) return rc;
+    const jdsp_denoise::LiveWs &w = h->lws;
+    if (n_ids < 0 || (n_ids > 0 && !stream_id_host)) return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_state: bad argument");
+    for (long i = 0; i < n_ids; i++)
+        if (stream_id_host[i] < 0 || stream_id_host[i] >= w.n_streams)
+            return fail(ctx, JDSP_EINVAL, "jdsp_denoise_streams_state: a stream id lies outside [0, n_streams)");
+    JDSP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (long i = 0; i < n_ids; i++) {
+        const int64_t id = stream_id_host[i];
+        int ep = 0;
+        JDSP_HIP(ctx, hipMemcpyAsync(&ep, w.est_parity + id, sizeof(int), hipMemcpyDeviceToHost, s));
+        if (blocks_seen_host)
+            JDSP_HIP(ctx, hipMemcpyAsync(blocks_seen_host + i, w.seen + id, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        JDSP_HIP(ctx, hipStreamSynchronize(s));
+        if (noise_host)
+            JDSP_HIP(ctx, hipMemcpyAsync(noise_host + (size_t)i * 1024,
+                                         w.rows.get() + ((size_t)(ep & 1) * w.n_streams + id) * 1024, 1024 * sizeof(float),
+                                         hipMemcpyDeviceToHost, s));
+    }
+    JDSP_HIP(ctx, hipStreamSynchronize(s));
+    return JDSP_OK;
+}
+
 int jdsp_denoise_noise(jdsp_denoise *h, double *noise_host)
 {
     if (!h || !noise_host) return JDSP_EINVAL;
@@ -543,7 +756,7 @@ long jdsp_denoise_frames_recomputed(jdsp_denoise *h)
     if (!h->redo_valid || (h->mode != JDSP_SPECSUB && h->n_fft == 1024)) return 0;   // 1024-point Wiener lists nothing
     int n = 0;
     JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    const int *count = h->redo_valid == 2 ? h->bws.redo.get() : h->ws.redo.get();
+    const int *count = h->redo_valid == 3 ? h->lws.redo.get() : h->redo_valid == 2 ? h->bws.redo.get() : h->ws.redo.get();
     JDSP_HIP(ctx, hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     JDSP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return n;

@@ -1842,6 +1842,409 @@ int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const s
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// =======================================================================================
+// The chunks of LIVE streams (jdsp_denoise_streams*, include/jdsp.h; DenoiseLive, jdsp_internal.h): the batch's layout
+// with chunks for utterances, but a chunk continues its stream instead of starting one.  Bit for bit the stream's
+// emitted blocks are what the batch kernels above write for ONE utterance of all its blocks, however they are cut:
+//   noise_live_kernel        noise_batch_kernel's chain, statement for statement, from the stream's carried run length
+//                            and average; before the chunk's first latch the estimate in force is the carried one
+//   denoise_live_kernel      denoise_batch_kernel's loop; where that kernel's halo frame would lie in front of the
+//                            chunk, the carried tail (that frame's y[d + 4]) and the carried previous block stand in
+//   denoise_redo_f64_live_kernel   redo_f64_run over RedoLive: a frame in front of the chunk is rebuilt from the
+//                            stream's last two blocks and the carried estimate
+//   denoise_live_commit_kernel     flips the parities, counts the blocks, reports E_c
+// Emission follows the stream: the block with stream index i >= 2 goes out packed from the span's start, block i -
+// max(N, 2) of the span for a stream that had seen N blocks.
+struct LiveChunk {
+    long s, N;                                                   // the stream, the blocks it had seen
+    int p;                                                       // the copy of prev / tail / listed it starts from
+};
+__device__ __forceinline__ LiveChunk live_chunk(const long long *__restrict__ stream_id, const int *__restrict__ parity,
+                                                const long long *__restrict__ seen, long c)
+{
+    LiveChunk k;
+    k.s = uniform_i64(stream_id + c);
+    k.p = __builtin_amdgcn_readfirstlane(parity[k.s]) & 1;
+    k.N = uniform_i64(seen + k.s);
+    return k;
+}
+
+__global__ __launch_bounds__(64) void noise_live_kernel(const short *__restrict__ pcm,
+                                                        const long long *__restrict__ stream_id,
+                                                        const long long *__restrict__ sample_first,
+                                                        const long long *__restrict__ block_first,
+                                                        const unsigned char *__restrict__ flags,
+                                                        const float2 *__restrict__ table, int *__restrict__ row_idx,
+                                                        DenoiseLive lv)
+{
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    const long c = blockIdx.x;
+    const long ub = uniform_i64(block_first + c), n_own = uniform_i64(block_first + c + 1) - ub;
+    if (n_own <= 0) return;                                      // the stream is not touched (the commit skips it too)
+    const LiveChunk k = live_chunk(stream_id, lv.parity, lv.seen, c);
+    const int ep = __builtin_amdgcn_readfirstlane(lv.est_parity[k.s]) & 1;
+    const short *own = pcm + uniform_i64(sample_first + c);
+    const short *before = lv.prev + ((size_t)k.p * lv.n_streams + k.s) * 1024 + 512;     // the stream's last block
+    FrameTables t;
+    load_frame_tables(t, table, lane);
+    PairTwiddles pw;
+    load_pair_twiddles(pw, table, lane);
+    constexpr int ND = 5;
+    float alo[ND], ahi[ND];
+    float *avg = lv.avg + (size_t)k.s * kLiveAvgFloats;
+#pragma unroll
+    for (int d = 0; d < ND; d++) { alo[d] = avg[lane + 64 * d]; ahi[d] = avg[320 + lane + 64 * d]; }
+    auto store_row = [&](float *row) {
+#pragma unroll
+        for (int d = 0; d < ND; d++) { row[lane + 64 * d] = alo[d]; row[lane + 64 * d + 512] = ahi[d]; }
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int m = lane + 64 * d;
+            if (m >= 1 && m <= 192) { row[1024 - m] = alo[d]; row[512 - m] = ahi[d]; }
+        }
+    };
+    int run_len = __builtin_amdgcn_readfirstlane(lv.run_len[k.s]);
+    int row = (int)(ep * lv.n_streams + k.s);                    // the carried estimate
+    int next_row = (int)(2 * lv.n_streams + c + ub / 11);        // a chunk of B blocks latches 1 + (B - 1) / 11 times at most
+    int any = 0;
+    for (long cb = 0; cb < n_own; cb += 64) {
+        const int n = n_own - cb < 64 ? (int)(n_own - cb) : 64;
+        const unsigned long long voice = __ballot(lane < n && flags[ub + cb + lane] != 0);
+        int mine = 0;
+        for (int i = 0; i < n; i++) {
+            if ((voice >> i) & 1ull) {
+                run_len = 0;                                     // SS:108
+            } else {
+                run_len = run_len < 11 ? run_len + 1 : 11;
+                if (run_len >= 2) {                              // SS:103-105: EstimateNoiseSpectrum
+                    const short *cur_block = own + (cb + i) * 512;
+                    unsigned int prev[4], cur[4];
+                    load_pairs(cb + i == 0 ? before : cur_block - 512, lane, prev);      // rgssKeepBuffer (SS:165-170)
+                    load_pairs(cur_block, lane, cur);
+                    float2 v[8], zr[ND];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
+                        v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
+                        v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
+                    }
+                    wave_fft512<false>(v, lds, lane, t.tw);
+                    wave_lds_fence();
+                    pair_fetch_lds(v, lds, lane, zr);
+                    const float h = run_len >= 3 ? 0.5f : 1.0f;  // SS:182-187
+#pragma unroll
+                    for (int d = 0; d < ND; d++) {
+                        const float2 ev = cadd_conj(v[d], zr[d]), od = csub_conj_mj(v[d], zr[d]);
+                        const float2 tw = cmul(pw.w[d], od);
+                        const float2 lo = cadd(ev, tw), hi = csub(ev, tw);
+                        alo[d] = (alo[d] + __builtin_amdgcn_sqrtf(lo.x * lo.x + lo.y * lo.y)) * h;
+                        ahi[d] = (ahi[d] + __builtin_amdgcn_sqrtf(hi.x * hi.x + hi.y * hi.y)) * h;
+                    }
+                    if (run_len == 10) {                         // SS:189-193; it applies to this block already
+                        row = next_row++;
+                        any = 1;
+                        store_row(lv.rows + (size_t)row * 1024);
+                        store_row(lv.rows + ((size_t)(ep ^ 1) * lv.n_streams + k.s) * 1024);   // the stream's next estimate
+                    }
+                }
+            }
+            if (lane == i) mine = row;
+        }
+        if (lane < n) row_idx[ub + cb + lane] = mine;
+    }
+#pragma unroll
+    for (int d = 0; d < ND; d++) { avg[lane + 64 * d] = alo[d]; avg[320 + lane + 64 * d] = ahi[d]; }
+    if (lane == 0) {
+        lv.run_len[k.s] = run_len;
+        lv.latched[c] = any;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ stream_id, const long long *__restrict__ sample_first,
+    const long long *__restrict__ block_first, const int *__restrict__ parity, const long long *__restrict__ seen,
+    long n_chunks, long n_blocks, const int *__restrict__ row_idx, const float2 *__restrict__ table,
+    short *__restrict__ out, float *__restrict__ precast, int run, int *__restrict__ redo, DenoiseLive lv)
+{
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    PhaseStat ps;
+    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
+    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * run;
+    if (j0 >= n_blocks) return;
+    const long j1 = j0 + run < n_blocks ? j0 + run : n_blocks;
+    long u = ragged_find_utt(block_first, n_chunks, j0);
+    long ub = uniform_i64(block_first + u), ue = uniform_i64(block_first + u + 1);
+    long base = uniform_i64(sample_first + u) - ub * 512;      // global block j of this chunk starts at base + 512 j
+    LiveChunk k = live_chunk(stream_id, parity, seen, u);
+    // stream index 0 or 1: the overlap entering block j0 is empty; the chunk's first block: it is the carried tail;
+    // else the frame of block j0 - 1 rebuilds it
+    const long js = (j0 > ub && k.N + (j0 - ub) >= 2) ? j0 - 1 : j0;
+
+    FrameTables t;
+    load_frame_tables(t, table, lane);
+    PairTwiddles sw;
+    load_pair_twiddles(sw, table, lane);
+    NoisePairRegs nz;
+    unsigned int raw[8], nxt[4], tk[4];
+    float2 tail[4], y[8];
+#pragma unroll
+    for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
+    // the block in front of js (at the chunk's first block it comes from the state, inside the loop)
+    load_pairs(pcm + base + (js > ub ? js - 1 : ub) * 512, lane, nxt);
+#pragma unroll
+    for (int r = 0; r < 4; r++) raw[r + 4] = nxt[r];
+    load_pairs(pcm + base + js * 512, lane, tk);
+    int cur_row = -1;
+    int next_idx = __builtin_amdgcn_readfirstlane(row_idx[js]);
+    unsigned prio_step = blockIdx.x >> 10;                    // step_priority: one step per block
+    for (long j = js; j < j1; j++) {
+        step_priority(prio_step);
+#pragma unroll
+        for (int r = 0; r < 4; r++) { raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
+        const int idx = next_idx;
+        int listed_in = 0;
+        if (j == ub) {
+            // the chunk's first block: the stream's last block and its overlap come from the state (zeros when fresh)
+            const size_t at = (size_t)k.p * lv.n_streams + k.s;
+            int sl = lane;
+            asm volatile("" : "+v"(sl));                         // per chunk: no lane offsets of the state kept across the run
+            unsigned int hp[4];
+            load_pairs(lv.prev + at * 1024 + 512, sl, hp);
+#pragma unroll
+            for (int r = 0; r < 4; r++) raw[r] = hp[r];
+            const float2 *tl = reinterpret_cast<const float2 *>(lv.tail + at * 512) + sl;
+#pragma unroll
+            for (int d = 0; d < 4; d++) tail[d] = tl[64 * d];
+            listed_in = MODE == 0 ? __builtin_amdgcn_readfirstlane(lv.listed[at]) : 0;
+        }
+        if (j + 1 == ue && j >= j0) {
+            // the chunk's last block, in the wave that owns it: with the block before, the stream's last two blocks (here,
+            // not beside the tail below: the first of them is not kept across the frame)
+            int sl = lane;
+            asm volatile("" : "+v"(sl));
+            unsigned int *pv = reinterpret_cast<unsigned int *>(lv.prev + ((size_t)(k.p ^ 1) * lv.n_streams + k.s) * 1024) + sl;
+#pragma unroll
+            for (int r = 0; r < 8; r++) pv[64 * r] = raw[r];
+        }
+        long un = u, ubn = ub, uen = ue, basen = base;
+        LiveChunk kn = k;
+        if (j + 1 < j1) {
+            if (j + 1 == ue) {
+                ubn = ue;
+                ragged_next_utt(block_first, n_chunks, un, uen);
+                basen = uniform_i64(sample_first + un) - ubn * 512;
+                kn = live_chunk(stream_id, parity, seen, un);
+            }
+            next_idx = row_idx[j + 1];
+            load_pairs(pcm + basen + (j + 1) * 512, lane, nxt);
+        }
+        const long i = k.N + (j - ub);                           // the block's index in its stream
+        int listed = 0;
+        if (i == 0) {
+            // the first call of a stream only stashes its block (SS:211-216): no output, empty overlap
+#pragma unroll
+            for (int d = 0; d < 8; d++) y[d] = make_float2(0.f, 0.f);
+        } else {
+            if (idx != cur_row) {                                // wave-uniform: another estimate is in force
+                cur_row = idx;
+                load_noise_pair_regs<MODE>(nz, lv.rows + (size_t)idx * 1024, lane);
+            }
+            denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);
+            // a frame FP32 cannot hold (phase_unsafe): again, in FP64
+            if (MODE == 0 && j >= j0 && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) {
+                phase_redo(redo, j, lane);
+                listed = 1;
+            }
+        }
+        // the stream's last frame was listed: the FP64 pass owes this block its other half (RedoLive)
+        if (MODE == 0 && listed_in && j >= j0) phase_redo(redo, ~j, lane);
+        float2 o[4];
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            o[d] = make_float2(tail[d].x + y[d].x, tail[d].y + y[d].y);      // SS:248 overlap-add
+            tail[d] = y[d + 4];                                               // SS:255-256
+        }
+        // taken before this block's stores (denoise_run_kernel)
+#pragma unroll
+        for (int r = 0; r < 4; r++) { tk[r] = nxt[r]; asm volatile("" : "+v"(tk[r])); }
+        next_idx = __builtin_amdgcn_readfirstlane(next_idx);
+        __builtin_amdgcn_sched_barrier(0);
+        if (j >= j0 && i >= 2) {
+            const long at = base + (j - (k.N < 2 ? 2 - k.N : 0)) * 512;      // packed from the span's start
+            if (out) {
+                unsigned int *dst = reinterpret_cast<unsigned int *>(out + at) + lane;
+#pragma unroll
+                for (int d = 0; d < 4; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
+            }
+            if (precast) {
+#pragma unroll
+                for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(precast + at + 2 * lane + 128 * d) = o[d];
+            }
+        }
+        if (j + 1 == ue && j >= j0) {
+            // the chunk's last block, in the wave that owns it: the stream's other copy takes what the next call starts from
+            const size_t at = (size_t)(k.p ^ 1) * lv.n_streams + k.s;
+            int sl = lane;
+            asm volatile("" : "+v"(sl));
+            float2 *tl = reinterpret_cast<float2 *>(lv.tail + at * 512) + sl;
+#pragma unroll
+            for (int d = 0; d < 4; d++) tl[64 * d] = tail[d];
+            if (lane == 0) lv.listed[at] = listed;
+        }
+        u = un; ub = ubn; ue = uen; base = basen; k = kn;
+    }
+}
+
+// A listed entry e >= 0 is the global frame e, as in the batch; e < 0 is the frame in front of the chunk whose first
+// block is ~e.  A frame with local index fb >= -1 exists when its stream index N + fb is >= 1; its samples come from
+// the chunk or, before it, from the stream's last two blocks; the frame in front of the chunk takes the carried estimate.
+struct RedoLive {
+    const short *pcm;
+    const long long *stream_id, *sample_first, *block_first;
+    long n_chunks;
+    const int *row_idx;
+    DenoiseLive lv;
+    short *out;               // may be NULL
+    float *precast;           // may be NULL
+    long ub, n_own, first, b, N;
+    const short *hist;
+    const float *est;
+    __device__ __forceinline__ void seek(long e)
+    {
+        const long j = e < 0 ? ~e : e;
+        const long c = ragged_find_utt(block_first, n_chunks, j);
+        ub = uniform_i64(block_first + c);
+        n_own = uniform_i64(block_first + c + 1) - ub;
+        first = uniform_i64(sample_first + c);
+        b = e < 0 ? -1 : j - ub;
+        const LiveChunk k = live_chunk(stream_id, lv.parity, lv.seen, c);
+        const int ep = __builtin_amdgcn_readfirstlane(lv.est_parity[k.s]) & 1;
+        N = k.N;
+        hist = lv.prev + ((size_t)k.p * lv.n_streams + k.s) * 1024;
+        est = lv.rows + ((size_t)ep * lv.n_streams + k.s) * 1024;
+    }
+    __device__ __forceinline__ bool have(int q) const { return b - 1 + q >= -1 && b - 1 + q < n_own && N + b - 1 + q >= 1; }
+    __device__ __forceinline__ double sample(int q, int i) const
+    {
+        const long at = (b - 2 + q) * 512 + i;
+        return (double)(at >= 0 ? pcm[first + at] : hist[1024 + at]);
+    }
+    __device__ __forceinline__ const float *row(int q) const
+    {
+        return b - 1 + q >= 0 ? lv.rows + (size_t)row_idx[ub + b - 1 + q] * 1024 : est;
+    }
+    __device__ __forceinline__ bool writes(int q) const { return b + q >= 0 && b + q < n_own && N + b + q >= 2; }
+    __device__ __forceinline__ bool carried(int) const { return false; }
+    __device__ __forceinline__ double carry(int) const { return 0.0; }
+    __device__ __forceinline__ void store(int q, int i, float o) const
+    {
+        const long at = first + (b + q - (N < 2 ? 2 - N : 0)) * 512 + i;
+        if (out) out[at] = (short)cast_i16_bits(o);
+        if (precast) precast[at] = o;
+    }
+    __device__ __forceinline__ void finish(const double *, int) const {}
+};
+
+__global__ __launch_bounds__(256) void denoise_redo_f64_live_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ stream_id, const long long *__restrict__ sample_first,
+    const long long *__restrict__ block_first, long n_chunks, const int *__restrict__ row_idx, DenoiseLive lv,
+    short *__restrict__ out, float *__restrict__ precast, const int *__restrict__ redo, int mode)
+{
+    redo_f64_run<1024>(redo, mode, RedoLive{pcm, stream_id, sample_first, block_first, n_chunks, row_idx, lv, out, precast,
+                                            0, 0, 0, 0, 0, nullptr, nullptr});
+}
+
+// one thread per chunk, behind every launch that read the state
+__global__ __launch_bounds__(256) void denoise_live_commit_kernel(const long long *__restrict__ stream_id,
+                                                                  const long long *__restrict__ block_first, long n_chunks,
+                                                                  const int *__restrict__ latched, int *__restrict__ parity,
+                                                                  int *__restrict__ est_parity, long long *__restrict__ seen,
+                                                                  long long *__restrict__ n_emitted)
+{
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_chunks) return;
+    const long long n_own = block_first[c + 1] - block_first[c];
+    long long e = 0;
+    if (n_own > 0) {
+        const long long s = stream_id[c], N = seen[s];
+        const long long silent = N < 2 ? 2 - N : 0;              // SS:260-263: the first two calls emit nothing
+        e = n_own > silent ? n_own - silent : 0;
+        parity[s] ^= 1;
+        if (latched[c]) est_parity[s] ^= 1;
+        seen[s] = N + n_own;
+    }
+    if (n_emitted) n_emitted[c] = e;
+}
+
+// one workgroup per listed stream
+__global__ __launch_bounds__(256) void denoise_live_reset_kernel(const long long *__restrict__ stream_id, DenoiseLive lv,
+                                                                 int *__restrict__ parity, int *__restrict__ est_parity,
+                                                                 long long *__restrict__ seen)
+{
+    const long long s = stream_id[blockIdx.x];
+    const int tid = threadIdx.x;
+    for (int e = 0; e < 2; e++) {
+        const size_t at = (size_t)e * lv.n_streams + s;
+        for (int i = tid; i < 512; i += 256) {
+            reinterpret_cast<unsigned int *>(lv.prev + at * 1024)[i] = 0u;
+            lv.tail[at * 512 + i] = 0.0f;
+        }
+        for (int i = tid; i < 1024; i += 256) lv.rows[at * 1024 + i] = 0.0f;
+        if (tid == 0) lv.listed[at] = 0;
+    }
+    for (int i = tid; i < kLiveAvgFloats; i += 256) lv.avg[(size_t)s * kLiveAvgFloats + i] = 0.0f;
+    if (tid == 0) {
+        lv.run_len[s] = 0;
+        parity[s] = 0;
+        est_parity[s] = 0;
+        seen[s] = 0;
+    }
+}
+
+int launch_denoise_live(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *stream_id,
+                        const long long *sample_first, const long long *block_first, long n_chunks, long n_blocks,
+                        const double *w_hi, const float2 *table, unsigned char *flags, int *row_idx, int *redo,
+                        const DenoiseLive &lv, int *parity, int *est_parity, long long *seen, short *out, float *precast,
+                        long long *n_emitted)
+{
+    if (n_blocks <= 0 || n_chunks <= 0) return 0;
+    hipLaunchKernelGGL(vad_flags_batch_kernel, dim3((unsigned)((n_blocks + kVadBlocksPerWave - 1) / kVadBlocksPerWave)),
+                       dim3(64), 0, s, pcm, sample_first, block_first, n_chunks, n_blocks, w_hi, flags);
+    hipLaunchKernelGGL(noise_live_kernel, dim3((unsigned)n_chunks), dim3(64), 0, s, pcm, stream_id, sample_first,
+                       block_first, flags, table, row_idx, lv);
+    if (mode == 0 && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
+    const long run = run_opt > 0 ? run_opt : resident_run(n_cu, n_blocks);
+    const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
+    if (mode == 0)
+        hipLaunchKernelGGL(denoise_live_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, stream_id, sample_first,
+                           block_first, lv.parity, lv.seen, n_chunks, n_blocks, row_idx, table, out, precast, (int)run, redo,
+                           lv);
+    else
+        hipLaunchKernelGGL(denoise_live_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, stream_id, sample_first,
+                           block_first, lv.parity, lv.seen, n_chunks, n_blocks, row_idx, table, out, precast, (int)run, redo,
+                           lv);
+    if (mode == 0 && (out || precast)) {
+        const long n_list = n_blocks + n_chunks;
+        hipLaunchKernelGGL(denoise_redo_f64_live_kernel, dim3((unsigned)(n_list < kRedoGrid ? n_list : kRedoGrid)), dim3(256),
+                           0, s, pcm, stream_id, sample_first, block_first, n_chunks, row_idx, lv, out, precast, redo, mode);
+    }
+    hipLaunchKernelGGL(denoise_live_commit_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, stream_id,
+                       block_first, n_chunks, lv.latched, parity, est_parity, seen, n_emitted);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_denoise_live_reset(hipStream_t s, const long long *stream_id, long n_ids, const DenoiseLive &lv, int *parity,
+                              int *est_parity, long long *seen)
+{
+    if (n_ids <= 0) return 0;
+    hipLaunchKernelGGL(denoise_live_reset_kernel, dim3((unsigned)n_ids), dim3(256), 0, s, stream_id, lv, parity, est_parity,
+                       seen);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ---- launchers of both frame sizes --------------------------------------------------------------
 // 512-point frames: the 512-point accumulate kernel, and the combine / fold / select kernels over bins 0..511 only (rows
 // and summaries keep the 1024-float pitch of the 1024-point path; bins 512.. are never read)

@@ -383,6 +383,40 @@ int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const s
                          const long long *block_first, long n_utts, long n_blocks, const double *w_hi,
                          const float2 *table, unsigned char *flags, int *row_idx, float *rows, int *redo, short *out,
                          float *precast, float *noise_last, int vad_only);
+// The live streams of a jdsp_denoise handle as a kernel sees them (jdsp_denoise_streams_*, include/jdsp.h): stream s is
+// a fresh stream of main() whose statics live here.  What several waves of one launch read and one of them writes is
+// held twice, and a word says which copy is current: prev, tail and listed under parity[s], the estimate under
+// est_parity[s].  A launch only READS the two words, loads from copy p and stores to copy p ^ 1; denoise_live_commit_kernel,
+// enqueued behind the launches, flips parity[s] for the streams that were given blocks, est_parity[s] for those whose
+// chunk latched, and adds the blocks to seen[s] (LiveStreams above is the same rule for an overlap-add tail).  The
+// running average and the run length are read and written by the one wave that walks the chunk's flags, so one copy.
+// Bytes per stream: 4,096 prev + 4,096 tail + 8,192 estimate + 2,560 average + 28 of words = 18,972.
+constexpr int kLiveAvgFloats = 640;       // noise_batch_kernel's pair-owned registers: [10][64]
+struct DenoiseLive {
+    const int *parity;        // [n_streams] 0 | 1
+    const int *est_parity;    // [n_streams] 0 | 1
+    const long long *seen;    // [n_streams] blocks delivered so far (the reference's call counters)
+    int *run_len;             // [n_streams] iNumOfIteration (SS:72), saturated at 11: only == 1, > 1, >= 3, == 10 are asked
+    int *listed;              // [2][n_streams] the stream's last frame went to the FP64 pass
+    short *prev;              // [2][n_streams][1024] the stream's last two blocks
+    float *tail;              // [2][n_streams][512] rgsdOveraped[512..1023] as the run kernel leaves it
+    float *avg;               // [n_streams][kLiveAvgFloats] rgsdAveragedNS
+    float *rows;              // [2 n_streams][1024] rgdEstimatedNS, copy e of stream s = row e n_streams + s; behind them
+                              // the rows latched in the current call, chunk c's from 2 n_streams + c + block_first[c] / 11
+    int *latched;             // [n_streams] per CHUNK of the current call: it latched
+    long n_streams;
+};
+// the chunks of live streams: the VAD, the noise pass (one wave per chunk, from the carried state), the run kernel, for
+// spectral subtraction the FP64 pass, and the commit.  out and precast may be NULL (the state advances all the same);
+// n_emitted may be NULL.  redo: [1 + n_blocks + n_chunks]
+int launch_denoise_live(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *stream_id,
+                        const long long *sample_first, const long long *block_first, long n_chunks, long n_blocks,
+                        const double *w_hi, const float2 *table, unsigned char *flags, int *row_idx, int *redo,
+                        const DenoiseLive &lv, int *parity, int *est_parity, long long *seen, short *out, float *precast,
+                        long long *n_emitted);
+// the n_ids listed streams fresh again
+int launch_denoise_live_reset(hipStream_t s, const long long *stream_id, long n_ids, const DenoiseLive &lv, int *parity,
+                              int *est_parity, long long *seen);
 int ensure_stft1024_table(jdsp_ctx *ctx);
 int ensure_vad_window(jdsp_ctx *ctx);
 // FP64 Hamming(2 block_len) over the positions a block occupies in the VAD's frame: keep + i, keep = block_len (SS:127-128)
@@ -576,8 +610,22 @@ struct jdsp_denoise {
         jdsp::DevBuf<int> redo;            // [n + 1] {count, frames...} as ws.redo
         long cap_blocks = -1, cap_utts = -1;
     } bws;
+    // sized by jdsp_denoise_streams_reserve: n_streams live streams (jdsp::DenoiseLive) and the workspace of one call
+    // over up to cap_blocks blocks.  Nothing here is read or written by the handle's own stream or the batch entries.
+    struct LiveWs {
+        long n_streams = 0, cap_blocks = 0;  // n_streams 0: not reserved
+        jdsp::DevBuf<char> state;          // one allocation: what DenoiseLive carries per stream, but the estimates
+        jdsp::DevBuf<float> rows;          // [2 n_streams + n_streams + cap_blocks / 11 + 2][1024]: DenoiseLive::rows
+        jdsp::DevBuf<unsigned char> flags; // [cap_blocks]
+        jdsp::DevBuf<int> row_idx;         // [cap_blocks]
+        jdsp::DevBuf<int> redo;            // [1 + cap_blocks + n_streams] {count, frames...}
+        jdsp::DevBuf<int> latched;         // [n_streams]
+        jdsp::DenoiseLive view;            // pointers into the above
+        int *parity = nullptr, *est_parity = nullptr;   // the three words only the commit and reset kernels write
+        long long *seen = nullptr;
+    } lws;
     long last_blocks = 0;
-    int redo_valid = 0;                   // the last call's count is there for jdsp_denoise_frames_recomputed: 1 in ws.redo[0], 2 in bws.redo[0]
+    int redo_valid = 0;                   // the last call's count is there for jdsp_denoise_frames_recomputed: 1 in ws.redo[0], 2 in bws.redo[0], 3 in lws.redo[0]
     int opt_k = 0;
     int opt_vad_trace = 0;                // 1: keep every block's energy sum and ZCR for jdsp_denoise_vad_trace (slower VAD kernel)
     int last_trace_valid = 0;             // the option's value when the last call ran: what jdsp_denoise_vad_trace may hand out

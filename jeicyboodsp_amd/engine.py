@@ -515,6 +515,93 @@ class Denoiser(_Child):
             res.append(noise[:n_utts])
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ---- live streams: n independent streams in the handle, advanced a chunk each by one call (jdsp_denoise_streams_*)
+    def open_streams(self, n_streams, max_blocks_total):
+        """Gives the handle n_streams live streams, all fresh, and the workspace of calls of up to max_blocks_total
+        blocks (jdsp_denoise_streams_reserve): the only call of the live entries that allocates, and it synchronises.
+        Calling it again discards every live stream's state."""
+        self.eng._ck(L.jdsp_denoise_streams_reserve(self._h, int(n_streams), int(max_blocks_total)))
+        self.n_streams = int(n_streams)
+        self._streams_torch = None      # the kind of the last process_streams() input
+        self._streams_key = None
+
+    def process_streams(self, pcm, stream_ids, block_counts, chunk_sample_first=None, want_precast=False,
+                        want_flags=False):
+        """One call over live streams (jdsp_denoise_streams; open_streams first): chunk c continues the live stream
+        stream_ids[c] with block_counts[c] >= 0 NEW blocks of self.block samples, at chunk_sample_first[c] of pcm (even,
+        ascending, disjoint; None: back to back, sharding.denoise_batch_layout).  Ids are distinct within a call.  The
+        chunk's E_c emitted blocks (sharding.denoise_stream_emitted) come out PACKED from the span's start; a stream's
+        emitted blocks over its calls equal, bit for bit, process_batch of all its blocks as one utterance.  torch CUDA
+        (the device entry on torch's current stream) or numpy (the host entry).  Returns (out int16 of pcm's length
+        [, precast float32][, flags uint8 [sum B_c]], n_emitted int64 [n_chunks]); what no chunk emitted is zero."""
+        from .sharding import denoise_batch_layout
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        counts = np.ascontiguousarray(block_counts, np.int64).reshape(-1)
+        assert ids.size == counts.size, "one block count per chunk"
+        packed, block_first, _ = denoise_batch_layout(counts, self.block)
+        if chunk_sample_first is None:
+            sample_first = packed
+        else:
+            sample_first = np.ascontiguousarray(chunk_sample_first, np.int64).reshape(-1)
+            assert sample_first.size == ids.size
+        n_chunks, n_total, n_samples = ids.size, int(block_first[-1]), int(pcm.shape[0])
+        assert pcm.ndim == 1
+        dev = pcm.device if _is_torch(pcm) else None
+        self._streams_torch = dev
+        if dev is not None:
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert n_chunks == 0 or int((sample_first + counts * self.block).max()) <= n_samples
+            key = (ids.tobytes(), sample_first.tobytes(), counts.tobytes(), dev)
+            if self._streams_key != key:
+                self._streams_dev = tuple(torch.from_numpy(a).to(dev) for a in (ids, sample_first, block_first))
+                self._streams_key = key
+            d_ids, d_sample, d_block = self._streams_dev
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+        out = _batch_out(n_samples, np.int16, dev)
+        pre = _batch_out(n_samples, np.float32, dev) if want_precast else None
+        flags = _batch_out(n_total, np.uint8, dev) if want_flags else None
+        emitted = _batch_out(n_chunks, np.int64, dev)
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_denoise_streams_dev(self._h, _vp(pcm), _vp(d_ids), _vp(d_sample), _vp(d_block), n_chunks,
+                                                    n_total, _vp(out), _vp(pre), _vp(flags), _vp(emitted)))
+        else:
+            self.eng._ck(L.jdsp_denoise_streams(self._h, _vp(pcm), n_samples, _vp(ids), _vp(sample_first), _vp(block_first),
+                                                n_chunks, _vp(out), _vp(pre), _vp(flags), _vp(emitted)))
+        res = [out[:n_samples]]
+        if want_precast:
+            res.append(pre[:n_samples])
+        if want_flags:
+            res.append(flags[:n_total])
+        res.append(emitted[:n_chunks])
+        return tuple(res)
+
+    def reset_streams(self, stream_ids=None):
+        """The listed live streams fresh again, or all of them with None (jdsp_denoise_streams_reset_dev; enqueue-only)."""
+        if stream_ids is None:
+            if self._streams_torch is not None:
+                self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_denoise_streams_reset_dev(self._h, None, 0))
+            return
+        import torch
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        dev = self._streams_torch if self._streams_torch is not None else torch.device("cuda", self.eng.device)
+        d_ids = torch.from_numpy(ids).to(dev)
+        self.eng._use_torch_stream()
+        self.eng._ck(L.jdsp_denoise_streams_reset_dev(self._h, _vp(d_ids), ids.size))
+        self._reset_args = d_ids                                # alive until the stream has run the call
+
+    def streams_state(self, stream_ids):
+        """(estimates float32 [n_ids, 1024] in process_batch's want_noise layout, zeros where nothing has latched;
+        blocks seen int64 [n_ids]) of the listed live streams (jdsp_denoise_streams_state; synchronises)."""
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        noise = np.zeros((max(ids.size, 1), 1024), np.float32)
+        seen = np.zeros(max(ids.size, 1), np.int64)
+        self.eng._ck(L.jdsp_denoise_streams_state(self._h, _vp(ids), ids.size, _vp(noise), _vp(seen)))
+        return noise[:ids.size], seen[:ids.size]
+
     # ---- one rank's share of a global stream (jdsp_denoise_shard_*; driver: sharding.denoise_sharded)
     def shard_vad(self, pcm_ext, ext0, b0, b1, n_total):
         import torch

@@ -223,6 +223,27 @@ def denoise_batch_layout(block_counts, hop):
     return sample_first[:-1].copy(), block_first, int(sample_first[-1])
 
 
+def denoise_stream_emitted(blocks_seen, block_counts):
+    """What the chunks of one Denoiser.process_streams call emit (jdsp_denoise_streams' n_emitted): a stream's first two
+    blocks emit nothing (SS:260-263: the reference's call counter), so the chunk of B_c = block_counts[c] blocks of a
+    stream that had seen N = blocks_seen[c] blocks emits E_c = B_c - max(0, min(B_c, 2 - N)).  Both arguments are
+    per-chunk sequences of equal length (a scalar blocks_seen stands for all chunks).  Returns numpy int64
+    [n_chunks].  The layout of the chunks is denoise_batch_layout's with chunks for utterances; a live stream lives on
+    one device, so over ranks the stream ids are split with stream_shard.  Negative values or lengths that differ:
+    ValueError."""
+    import numpy as np
+    counts = np.asarray(block_counts, dtype=np.int64).reshape(-1)
+    seen = np.asarray(blocks_seen, dtype=np.int64)
+    if seen.ndim == 0:
+        seen = np.full(counts.shape, int(seen), np.int64)
+    seen = seen.reshape(-1)
+    if seen.size != counts.size:
+        raise ValueError("one blocks_seen value per chunk")
+    if np.any(counts < 0) or np.any(seen < 0):
+        raise ValueError("blocks_seen and block counts must be >= 0")
+    return counts - np.maximum(0, np.minimum(counts, 2 - seen))
+
+
 def stftmask_batch_shard(frame_counts, rank, world):
     """Batched fused STFT masking (StftMask.process_batch) over `world` ranks: whole utterances per rank, contiguous,
     balanced by frame count (utterance_shard); an utterance is a stream of its own, so there is no halo and no

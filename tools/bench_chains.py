@@ -559,6 +559,90 @@ def main():
                     h.close()
                 sm.close()
                 del ins, o16, args_a, args_b, args_c, singles
+    if on("denoise_streams"):
+        # Live denoise streams (jdsp_denoise_streams_dev): 10,000 live streams, every call brings each of them a chunk
+        # of 4 blocks; a chunk is quiet (sigma 45) or loud (sigma 3000) at even odds, so runs of quiet blocks build up,
+        # latch and break across the calls.  Timed three ways in this process, in alternated rounds, every C entry called
+        # through ctypes with its arguments computed beforehand: (a) the streams entry -- VAD, noise pass, run kernel,
+        # FP64 pass (spectral subtraction) and commit --; (b) one jdsp_denoise handle per stream in a loop of
+        # _process_dev, over the first 1,000 streams and scaled by 10; (c) the stateless jdsp_denoise_batch_dev over the
+        # same chunks as utterances: other arithmetic at the boundaries, the same work, the yardstick.  The inputs rotate
+        # over 8 copies of 41 MB (328 MB, past the 256 MiB Infinity Cache).  Bytes per chunk come from the shapes:
+        # both read the chunk's 4 blocks; (c) writes 2 blocks, (a) writes 4 and reads and writes the stream's state.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        S, F, n_loop = 10000, 4, 1000
+        gen = torch.Generator(device="cuda").manual_seed(19)
+        ids = torch.from_numpy(np.random.default_rng(19).permutation(S).astype(np.int64)).cuda()
+        vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)   # noqa: E731
+        it, rounds = max(25 * a.iters, 100), 3
+        counts = np.full(S, F, np.int64)
+        sf, bf, n_samples = sharding.denoise_batch_layout(counts, 512)
+        d_sf, d_bf = torch.from_numpy(sf).cuda(), torch.from_numpy(bf).cuda()
+        total = S * F
+        ins = []
+        for _ in range(1 if a.warm else 8):
+            sigma = torch.where(torch.rand(S, device="cuda", generator=gen) < 0.5, 45.0, 3000.0)
+            draft = torch.randn((S, F * 512), device="cuda", generator=gen) * sigma[:, None]
+            ins.append(draft.round_().clamp_(-32768, 32767).to(torch.int16).view(-1))
+        del draft, sigma
+        o16 = torch.empty(n_samples, dtype=torch.int16, device="cuda")
+        block = 1024                                            # bytes of a block of int16
+        # the state a chunk reads and writes: one previous block in, two out; the overlap in and out (float32); the
+        # running average in and out; the estimate in force in; the words
+        state = block + 2 * block + 2 * 2048 + 2 * 2560 + 4096 + 28
+        bytes_a, bytes_c = F * block + F * block + state, F * block + (F - 2) * block
+        flops = 2 * 5 * 512 * 9 + 2 * 512 * 14
+        for mode, nm in ((0, "specsub"), (1, "wiener")):
+            d_a, d_c = eng.denoiser(mode), eng.denoiser(mode)
+            d_a.open_streams(S, total)
+            d_c.reserve_batch(total, S)
+            singles = [eng.denoiser(mode) for _ in range(n_loop)]
+            for h in singles:
+                eng._ck(L.jdsp_denoise_reserve(h._h, F))
+            args_a = [(d_a._h, vp(x), vp(ids), vp(d_sf), vp(d_bf), S, total, vp(o16), None, None, None) for x in ins]
+            args_c = [(d_c._h, vp(x), vp(d_sf), vp(d_bf), S, total, vp(o16), None, None, None) for x in ins]
+            args_b = [(h._h, vp(ins[0], 2 * int(sf[u])), F, vp(o16, 2 * int(sf[u])), None, None) for u, h in enumerate(singles)]
+            eng._use_torch_stream()
+            turn = [0]
+
+            def call_a():
+                turn[0] += 1
+                L.jdsp_denoise_streams_dev(*args_a[turn[0] % len(args_a)])
+
+            def call_c():
+                turn[0] += 1
+                L.jdsp_denoise_batch_dev(*args_c[turn[0] % len(args_c)])
+
+            def loop():
+                for p in args_b:
+                    L.jdsp_denoise_process_dev(*p)
+
+            assert L.jdsp_denoise_streams_dev(*args_a[0]) == 0 and L.jdsp_denoise_batch_dev(*args_c[0]) == 0
+            assert L.jdsp_denoise_process_dev(*args_b[0]) == 0
+            ms_a, ms_c, ms_b = timed_alternated([call_a, call_c, loop], [it, it, 1], rounds=rounds)
+            ms_b *= S / n_loop
+            n_redo = d_a.frames_recomputed()
+            inp = "rotated over %d copies of %.0f MB (from HBM)" % (len(ins), 2e-6 * n_samples)
+            shape = "10,000 live streams x 4 blocks per call, chunks quiet or loud at even odds"
+            report("denoise_streams_" + nm, ms_a, total, "blocks", bytes_a / F, flops,
+                   "(a) jdsp_denoise_streams_dev: %s; (a)/(c) = %.3f against a byte ratio of %.3f (%d against %d bytes per "
+                   "chunk, %d of them state); %.4f of the per-stream loop (b); %d frames through the FP64 pass in the last "
+                   "call; %d calls per round, %d rounds"
+                   % (shape, ms_a / ms_c, bytes_a / bytes_c, bytes_a, bytes_c, state, ms_a / ms_b, n_redo, it, rounds), inp=inp)
+            report("denoise_streams_" + nm + "_per_stream_loop", ms_b, total, "blocks", bytes_a / F, flops,
+                   "(b) one jdsp_denoise handle per stream, a loop of jdsp_denoise_process_dev from ctypes with precomputed "
+                   "arguments: measured over %d streams and scaled by %d; %.1f x the streams entry"
+                   % (n_loop, S // n_loop, ms_b / ms_a), inp=inp)
+            report("denoise_streams_" + nm + "_stateless_batch", ms_c, total, "blocks", bytes_c / F, flops,
+                   "(c) the yardstick: jdsp_denoise_batch_dev over the same chunks as utterances, nothing carried", inp=inp)
+            for h in singles:
+                h.close()
+            d_a.close()
+            d_c.close()
+            del args_a, args_b, args_c, singles
+        del ins, o16
     if on("mfcc"):
         x = torch.from_numpy(pcm_of(rng, 512 * (B + 1))).cuda()
         xr = rot(x)
