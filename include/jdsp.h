@@ -41,7 +41,8 @@
  *       Class D, state on the device only: jdsp_geq_process_dev, jdsp_nlms_process_dev, and the live streams
  *         jdsp_stftmask_streams_dev / _streams_flush_dev / _streams_reset_dev and jdsp_istft_streams_dev /
  *         _streams_flush_dev / _streams_reset_dev, and jdsp_denoise_streams_dev / jdsp_denoise_streams_reset_dev
- *         (their *_reserve: jdsp_denoise_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
+ *         (their *_reserve: jdsp_denoise_streams_reserve), and jdsp_binaural_render_dev /
+ *         jdsp_binaural_streams_reset_dev (jdsp_binaural_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
  *         replay (or eager call) before it left, exactly as another eager call would.  Replay as often as wanted.
  *       Class H, state the host carries (which ping-pong copy is current, the stream position, passed to the kernels
  *         as arguments): jdsp_istft_process_dev / _flush_dev, jdsp_stftmask_process_dev / _flush_dev,
@@ -76,7 +77,8 @@ extern "C" {
  *    jdsp_denoise_frames_recomputed added; the batched masking entries jdsp_stftmask_batch* added; the ragged-batch
  *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added;
  *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
- *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added
+ *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added;
+ *    live binaural rendering jdsp_binaural_* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -717,6 +719,94 @@ int jdsp_fastconv_process_dev(jdsp_fastconv *h, const int16_t *pcm_dev, long n_b
                               float *precast_dev, long *n_out_blocks);
 int jdsp_fastconv_process(jdsp_fastconv *h, const int16_t *pcm_host, long n_blocks, int16_t *out_host,
                           float *precast_host, long *n_out_blocks);
+
+/* ---- binaural rendering: live sources mixed per ear in the spectrum ------------------------- */
+/* NOT a reference function: the reference convolves one mono stream with one fixed filter set
+ * (Fast_Convolution_Based_3DAudio_Impl.cpp:102-177, jdsp_fastconv_* above).  This is the same overlap-save algorithm
+ * in the form a spatialiser serves: many short deliveries at once, each output a MIX of a handful of sources, each
+ * source heard from its own direction out of a bank of HRIRs at its own gain, both changing while the stream runs.
+ * Its oracle is the FP64 restatement in tests/binaural_ref.py.
+ *   - THE BANK.  hrir_taps: n_dirs directions x 2 ears x n_taps real taps (double, host), 1 <= n_taps <= 513,
+ *     1 <= n_dirs <= 16384.  Transforms are 1024-point and blocks are 512 samples (jdsp_binaural_block_len; what the
+ *     denoisers emit): the last 512 samples of a segment [previous block | block] are alias-free for up to 513 taps.
+ *     The spectra are computed once, in FP64 on the device as jdsp_fastconv_create does, and kept as FP32 with the
+ *     transform's 1/1024 and the split's 1/2 folded in (powers of two: exact) -- of every spectrum only the 640 values
+ *     that are not implied by its Hermitian symmetry in the kernel's pair scheme: 10 KB per direction.
+ *   - THE STREAMS.  jdsp_binaural_streams_reserve(h, n_streams) opens n_streams LIVE STREAMS, each ONE SOURCE AS HEARD
+ *     IN ONE MIX (a talker heard by four listeners is four streams whose chunks point at the same PCM).  A stream
+ *     carries its last 512 input samples, the direction and the gain of its last delivery, and a "started" word:
+ *     1,036 bytes, held twice under a device-side parity word (a mix's first block reads what its last block
+ *     replaces) = 2,076 bytes per stream.  It is the only call that allocates, and it synchronises; all streams
+ *     start fresh, and calling it again discards every stream.  Before it the other stream entries (_reset_dev,
+ *     _render_dev, _render, _streams_state) return JDSP_EINVAL with a text.
+ *   - ONE CALL (a delivery) renders n_mixes mixes.  Mix m produces B_m = block_first[m + 1] - block_first[m] >= 0
+ *     output blocks from the chunks c in [chunk_first[m], chunk_first[m + 1]) -- possibly none: B_m blocks of zeros.
+ *     Chunk c belongs to stream stream_id[c]; its new samples are pcm[sample_first[c] .. + 512 B_m) -- no overlap is
+ *     presented, the handle keeps the history -- heard from dir[c] (int32, in [0, n_dirs)) at gain[c] (float32).
+ *     Input spans are only read: they MAY COINCIDE OR OVERLAP (the one difference from the other entries' "disjoint
+ *     spans"; it holds for inputs only).
+ *   - SEMANTICS, in exact arithmetic, per ear e, block b and sample i of mix m: with x the stream (its carried history,
+ *     then this chunk; silence before a fresh stream's first sample), y_{d,g}[t] = g sum_k h[d][e][k] x[t - k], and
+ *     (d0, g0) the carried direction and gain ((d0, g0) = (d1, g1) for a fresh stream), chunk c contributes
+ *         y_{d1,g1}                                   to blocks b >= 1, and to block 0 when (d0, g0) == (d1, g1)
+ *                                                     (gains compared as bit patterns);
+ *         (1 - r[i]) y_{d0,g0} + r[i] y_{d1,g1},  r[i] = i / 512,   to block 0 otherwise:
+ *     a move or a gain step is a one-block linear cross-fade, and a constant source costs nothing extra.  The mix is
+ *     the sum over its chunks in list order.
+ *   - OUTPUT.  out_i16[e plane + 512 (block_first[m] + b) + i] = (short) of the float (truncate toward zero, keep the
+ *     low 16 bits, as every chain here); out_f32, same layout: the float itself.  Either may be NULL; with both NULL
+ *     the streams still advance.  Nothing else of the planes is written.
+ *   - STATE RULE.  After the call each delivered stream carries its chunk's last 512 samples and (d1, g1), started.
+ *     Streams with no chunk, and the chunks of a mix with B_m = 0, are untouched.
+ *   - THE ARITHMETIC, fixed (csrc/binaural_kernels.hip): per chunk one forward 1024-point real transform of the
+ *     segment in FP32; THE GAIN multiplies the chunk's split spectrum in FP32, before the bank values; the products
+ *     are accumulated per ear in list order; a block takes the PLAIN form -- one accumulated spectrum per ear, two
+ *     inverse transforms -- exactly when none of its chunks fades, else the FADED form: two accumulated spectra per
+ *     ear, "old" (d0, g0) and "new" (d1, g1), the unchanged chunks in both, four inverse transforms, and the ramp
+ *     fma(r, new, (1 - r) old) in FP32 in the time domain.  Which form a block takes depends only on the carried and
+ *     delivered (dir, gain) values.  S sources cost S + 2 transforms per block (S + 4 while something fades), not 3 S.
+ *   - GUARANTEES (tests/test_binaural_gpu.py).  (1) every float sample within 1e-5 sum_c P_c of the FP64 value, P_c the
+ *     largest magnitude of chunk c's contribution to either ear over the block; the int16 IS the cast of the float,
+ *     and within +-1 of the cast of the FP64 value.  (2) CUTS: a delivery of B blocks with (d, g) equals, bit for bit
+ *     in both outputs, any split of it into consecutive deliveries that each name the same (d, g), down to one block
+ *     per call.  (3) INDEPENDENCE: a mix's bits do not depend on its place among the mixes, on the other mixes, on
+ *     the order of mixes, on its streams' ids or on n_streams; they DO depend on the order of its own chunks.
+ *     (4) a mix whose every chunk has gain 0.0f and carried gain 0.0f is exact zeros.
+ *   - jdsp_binaural_render_dev and jdsp_binaural_streams_reset_dev only enqueue (the render launch and a commit
+ *     launch of n_chunks threads that flips the parity of the delivered streams): no allocation, no host
+ *     synchronisation, no host read of the arrays.  Graph-capturable, class D (Conventions): the scalars and the
+ *     pointers are baked; every array, dir and gain included, is read at replay, and every replay advances the named
+ *     streams from where they stand.  The caller's contract on the device: ids in [0, n_streams) and distinct within a
+ *     call; n_chunks <= n_streams (checked); both *_first arrays start at 0 and do not decrease, chunk_first[n_mixes] =
+ *     n_chunks, block_first[n_mixes] = n_blocks_total; sample_first even; plane even and >= 512 n_blocks_total
+ *     (checked); the spans inside pcm; the int64 arrays 8-byte, pcm, out_i16, dir and gain 4-byte, out_f32 8-byte
+ *     aligned (checked).  The device entry clamps dir and the ids into range instead of reading outside the bank.
+ *     n_mixes == 0 or n_blocks_total == 0 launches nothing and changes nothing.  reset_dev: the n_ids listed streams
+ *     fresh again; stream_id_dev NULL: all of them.
+ *   - jdsp_binaural_render (host pointers, synchronous; pcm is n_samples long, the outputs 2 x plane) checks all of
+ *     that and dir in range, finite gains, every span inside n_samples and the output blocks inside plane; on a
+ *     violation it returns JDSP_EINVAL with a jdsp_last_error text and leaves every stream as it was.  Its outputs are
+ *     ZERO outside the written blocks.
+ *   - jdsp_binaural_streams_state: per listed stream its 512 carried samples, direction, gain and started word (any
+ *     output may be NULL).  Synchronises. */
+typedef struct jdsp_binaural jdsp_binaural;
+int jdsp_binaural_create(jdsp_ctx *ctx, const double *hrir_taps /* [n_dirs][2][n_taps] */, int n_dirs, int n_taps,
+                         jdsp_binaural **out);
+int jdsp_binaural_destroy(jdsp_binaural *h);
+int jdsp_binaural_n_dirs(const jdsp_binaural *h);
+int jdsp_binaural_block_len(const jdsp_binaural *h);          /* 512 */
+int jdsp_binaural_streams_reserve(jdsp_binaural *h, long n_streams);
+int jdsp_binaural_streams_reset_dev(jdsp_binaural *h, const int64_t *stream_id_dev, long n_ids);   /* NULL: all */
+int jdsp_binaural_render_dev(jdsp_binaural *h, const int16_t *pcm_dev, const int64_t *stream_id_dev,
+                             const int64_t *sample_first_dev, const int32_t *dir_dev, const float *gain_dev,
+                             const int64_t *chunk_first_dev, const int64_t *block_first_dev, long n_mixes, long n_chunks,
+                             long n_blocks_total, int16_t *out_i16_dev, float *out_f32_dev, long plane);
+int jdsp_binaural_render(jdsp_binaural *h, const int16_t *pcm_host, long n_samples, const int64_t *stream_id_host,
+                         const int64_t *sample_first_host, const int32_t *dir_host, const float *gain_host,
+                         const int64_t *chunk_first_host, const int64_t *block_first_host, long n_mixes, long n_chunks,
+                         int16_t *out_i16_host, float *out_f32_host, long plane);
+int jdsp_binaural_streams_state(jdsp_binaural *h, const int64_t *stream_id_host, long n_ids, int16_t *hist_host,
+                                int32_t *dir_host, float *gain_host, int32_t *started_host);      /* synchronises */
 
 /* ---- FFT autocorrelation pitch --------------------------------------------------- */
 /* PitchEstimation_method1.cpp: CalcPitch (:69-116) for n_blocks blocks of 512 samples.

@@ -131,6 +131,15 @@ def _load():
         "jdsp_fastconv_blocks_out": (l, [vp, l]),
         "jdsp_fastconv_process_dev": (i, [vp, vp, l, vp, vp, C.POINTER(l)]),
         "jdsp_fastconv_process": (i, [vp, vp, l, vp, vp, C.POINTER(l)]),
+        "jdsp_binaural_create": (i, [vp, vp, i, i, C.POINTER(vp)]),
+        "jdsp_binaural_destroy": (i, [vp]),
+        "jdsp_binaural_n_dirs": (i, [vp]),
+        "jdsp_binaural_block_len": (i, [vp]),
+        "jdsp_binaural_streams_reserve": (i, [vp, l]),
+        "jdsp_binaural_streams_reset_dev": (i, [vp, vp, l]),
+        "jdsp_binaural_render_dev": (i, [vp, vp, vp, vp, vp, vp, vp, vp, l, l, l, vp, vp, l]),
+        "jdsp_binaural_render": (i, [vp, vp, l, vp, vp, vp, vp, vp, vp, l, l, vp, vp, l]),
+        "jdsp_binaural_streams_state": (i, [vp, vp, l, vp, vp, vp, vp]),
         "jdsp_vad_blocks": (i, [vp, vp, l, vp, vp, vp]),
         "jdsp_vad_blocks_ex": (i, [vp, i, i, vp, l, vp, vp, vp]),
         "jdsp_denoise_apply": (i, [vp, vp, l, vp, vp, vp, C.POINTER(l)]),

@@ -446,6 +446,30 @@ int launch_fastconv_upols(hipStream_t st, const ConvStream &s, long n_out_blocks
                           int n_filters, const float2 *Hp, const float2 *rect_table, short *staged, float2 *X,
                           short *out, float *precast, long plane, short *hist_out);
 int ensure_stft1024_table_rect(jdsp_ctx *ctx);
+// binaural_kernels.hip
+// The live streams of a jdsp_binaural handle as a kernel sees them (include/jdsp.h, "binaural rendering"): stream s is
+// one source as heard in one mix.  Everything it carries is held twice, copy p of stream s at index p n_streams + s, and
+// parity[s] says which copy is current -- the rule of LiveStreams and DenoiseLive: the wave of a mix's block 0 reads
+// the carried state while the wave of its last block writes the next one, and with more than one block they are not
+// the same wave.  A launch only READS parity (the kernel takes it as a __restrict__ argument of its own), loads from
+// copy p and stores to copy p ^ 1; binaural_commit_kernel, enqueued behind it, flips parity[s] for the chunks of mixes
+// that got blocks.  Bytes per stream, both copies: 2 x (1,024 + 4 + 4 + 4) = 2,072, and 4 of parity.
+struct BinauralStreams {
+    short *hist;          // [2][n_streams][512] the stream's last 512 samples (zeros: silence before a fresh stream)
+    int *dir;             // [2][n_streams] the direction of its last delivery
+    float *gain;          // [2][n_streams] ... and the gain, compared as a bit pattern
+    int *started;         // [2][n_streams] 0: fresh, (dir, gain) mean nothing and its first delivery does not fade
+    long n_streams;
+};
+// spec: [rows][1024] FP64 spectra of the zero-padded taps; bank: [rows][640] (the layout: binaural_kernels.hip)
+int launch_binaural_bank(hipStream_t s, const double2 *spec, float2 *bank, long rows);
+// the render launch over n_blocks_total > 0 blocks and the commit behind it; out_i16 and out_f32 may be NULL
+int launch_binaural_render(hipStream_t s, const short *pcm, const long long *stream_id, const long long *sample_first,
+                           const int *dir, const float *gain, const long long *chunk_first, const long long *block_first,
+                           long n_mixes, long n_chunks, long n_blocks_total, const float2 *bank, int n_dirs,
+                           const float2 *table, const BinauralStreams &st, int *parity, short *out_i16, float *out_f32,
+                           long plane);
+int launch_binaural_reset(hipStream_t s, const long long *stream_id, long n_ids, const BinauralStreams &st);
 // mvdr_kernels.hip
 int launch_mvdr(hipStream_t s, const short *left, const short *right, long n_blocks, long calls_before,
                 const MvdrState *st_in, MvdrState *st_out, const int *events, const DenoisePlan *plan,
@@ -712,6 +736,17 @@ struct jdsp_fastconv {
     int hist_len = 0;                     // n_taps - 1; partitioned: 512 n_part, every sample a call's first frames read
     int cur = 0;
     long calls = 0;                       // blocks consumed so far (siNumOfCount)
+};
+
+struct jdsp_binaural {
+    jdsp_ctx *ctx = nullptr;
+    int n_dirs = 0, n_taps = 0;
+    jdsp::DevBuf<float2> bank;            // [n_dirs][2][640]: binaural_kernels.hip
+    // sized by jdsp_binaural_streams_reserve
+    long n_streams = 0;                   // 0: not reserved
+    jdsp::DevBuf<char> state;             // one allocation: what BinauralStreams carries, and the parity words
+    jdsp::BinauralStreams view{};         // pointers into it
+    int *parity = nullptr;                // [n_streams]: only the commit kernel (and a reset of all) writes it
 };
 
 struct jdsp_mvdr {

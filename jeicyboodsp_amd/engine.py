@@ -99,6 +99,10 @@ class Engine(_Handle):
     def fastconv(self, taps, n_fft):
         return FastConv(self, taps, n_fft)
 
+    def binaural(self, hrirs):
+        """Live binaural renderer (jdsp_binaural) over the bank hrirs [n_dirs, 2, n_taps]."""
+        return Binaural(self, hrirs)
+
     def mvdr_multi(self, n_mics, delays=None, loading=0.0, n_fft=1024):
         return MvdrMulti(self, n_mics, delays, loading, n_fft)
 
@@ -935,6 +939,102 @@ class FastConv(_Child):
                                              (out if out.size else dummy).ctypes.data_as(C.c_void_p),
                                              pre.ctypes.data_as(C.c_void_p) if (want_precast and pre.size) else None, None))
         return (out, pre) if want_precast else out
+
+
+class Binaural(_Child):
+    """Live binaural rendering (jdsp_binaural; NOT a reference function: the overlap-save convolver of
+    Fast_Convolution_Based_3DAudio_Impl.cpp:102-177 generalised to mixes of moving sources).
+    hrirs: [n_dirs, 2, n_taps] float64, n_taps <= 513.  Blocks are self.block = 512 samples."""
+    _destroy = staticmethod(lambda h: L.jdsp_binaural_destroy(h))
+
+    def __init__(self, engine, hrirs):
+        self.eng = engine
+        hrirs = np.ascontiguousarray(np.asarray(hrirs, np.float64))
+        assert hrirs.ndim == 3 and hrirs.shape[1] == 2, "hrirs: [n_dirs, 2, n_taps]"
+        self.n_dirs, _, self.n_taps = hrirs.shape
+        h = C.c_void_p()
+        engine._ck(L.jdsp_binaural_create(engine._h, _vp(hrirs), self.n_dirs, self.n_taps, C.byref(h)))
+        self._h = h
+        self.block = L.jdsp_binaural_block_len(h)
+        self.n_streams = 0
+        self._streams_torch = None
+        engine._children.append(self)
+
+    def open_streams(self, n_streams):
+        """Gives the handle n_streams live streams, all fresh (jdsp_binaural_streams_reserve): the only call that
+        allocates, and it synchronises.  Calling it again discards every stream."""
+        self.eng._ck(L.jdsp_binaural_streams_reserve(self._h, int(n_streams)))
+        self.n_streams = int(n_streams)
+        self._streams_torch = None
+
+    def render(self, pcm, stream_ids, sample_first, dirs, gains, chunk_first, block_first, plane=None, want_i16=True,
+               want_f32=False):
+        """One delivery (jdsp_binaural_render; open_streams first): mix m renders block_first[m + 1] - block_first[m]
+        blocks from the chunks chunk_first[m] .. chunk_first[m + 1] - 1; chunk c continues stream stream_ids[c] with
+        the 512 B_m samples at sample_first[c] of pcm, heard from dirs[c] at gains[c] (sharding.binaural_layout packs
+        a delivery; input spans may coincide).  plane: samples per ear of the outputs (None: 512 sum B_m).  pcm torch
+        CUDA int16 (the device entry on torch's current stream; the arrays go up with the call) or numpy (the host
+        entry, which checks everything).  Returns out_i16 [2, plane] and / or out_f32 [2, plane] as asked (both: a
+        tuple); what no block wrote is zero."""
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        sf = np.ascontiguousarray(sample_first, np.int64).reshape(-1)
+        d = np.ascontiguousarray(dirs, np.int32).reshape(-1)
+        g = np.ascontiguousarray(gains, np.float32).reshape(-1)
+        cf = np.ascontiguousarray(chunk_first, np.int64).reshape(-1)
+        bf = np.ascontiguousarray(block_first, np.int64).reshape(-1)
+        assert ids.size == sf.size == d.size == g.size, "one id, offset, direction and gain per chunk"
+        assert cf.size == bf.size and cf.size >= 1, "chunk_first and block_first: [n_mixes + 1]"
+        n_mixes, n_chunks, n_total = cf.size - 1, ids.size, int(bf[-1])
+        if plane is None:
+            plane = self.block * n_total
+        plane = int(plane)
+        assert pcm.ndim == 1
+        n_samples = int(pcm.shape[0])
+        dev = pcm.device if _is_torch(pcm) else None
+        self._streams_torch = dev
+        o16 = _batch_out(2 * plane, np.int16, dev) if want_i16 else None
+        o32 = _batch_out(2 * plane, np.float32, dev) if want_f32 else None
+        if dev is not None:
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            counts = np.repeat(np.diff(bf), np.diff(cf)) if n_mixes else np.zeros(0, np.int64)
+            assert counts.size == n_chunks and (n_chunks == 0 or int((sf + counts * self.block).max()) <= n_samples)
+            self._render_args = tuple(torch.from_numpy(a).to(dev) for a in (ids, sf, d, g, cf, bf))   # alive until run
+            a = self._render_args
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_binaural_render_dev(self._h, _vp(pcm), _vp(a[0]), _vp(a[1]), _vp(a[2]), _vp(a[3]),
+                                                    _vp(a[4]), _vp(a[5]), n_mixes, n_chunks, n_total, _vp(o16), _vp(o32),
+                                                    plane))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            self.eng._ck(L.jdsp_binaural_render(self._h, _vp(pcm), n_samples, _vp(ids), _vp(sf), _vp(d), _vp(g), _vp(cf),
+                                                _vp(bf), n_mixes, n_chunks, _vp(o16), _vp(o32), plane))
+        res = tuple(o[:2 * plane].reshape(2, plane) for o in (o16, o32) if o is not None)
+        return res[0] if len(res) == 1 else (res if res else None)
+
+    def reset_streams(self, stream_ids=None):
+        """The listed live streams fresh again, or all of them with None (jdsp_binaural_streams_reset_dev; enqueue-only)."""
+        if stream_ids is None:
+            if self._streams_torch is not None:
+                self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_binaural_streams_reset_dev(self._h, None, 0))
+            return
+        import torch
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        dev = self._streams_torch if self._streams_torch is not None else torch.device("cuda", self.eng.device)
+        d_ids = torch.from_numpy(ids).to(dev)
+        self.eng._use_torch_stream()
+        self.eng._ck(L.jdsp_binaural_streams_reset_dev(self._h, _vp(d_ids), ids.size))
+        self._reset_args = d_ids                                # alive until the stream has run the call
+
+    def streams_state(self, stream_ids):
+        """(hist int16 [n_ids, 512], dir int32 [n_ids], gain float32 [n_ids], started int32 [n_ids]) of the listed live
+        streams: what each carries into its next delivery (jdsp_binaural_streams_state; synchronises)."""
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        n = max(ids.size, 1)
+        hist, d, g, st = np.zeros((n, 512), np.int16), np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        self.eng._ck(L.jdsp_binaural_streams_state(self._h, _vp(ids), ids.size, _vp(hist), _vp(d), _vp(g), _vp(st)))
+        return hist[:ids.size], d[:ids.size], g[:ids.size], st[:ids.size]
 
 
 class Mvdr(_Child):

@@ -223,6 +223,31 @@ def denoise_batch_layout(block_counts, hop):
     return sample_first[:-1].copy(), block_first, int(sample_first[-1])
 
 
+def binaural_layout(blocks_per_mix, chunks_per_mix):
+    """The back-to-back packing of one binaural delivery (Binaural.render, jdsp_binaural_render): mix m of
+    B_m = blocks_per_mix[m] >= 0 output blocks of 512 samples has S_m = chunks_per_mix[m] >= 0 chunks, one per source,
+    each 512 B_m new samples long, and the chunks' spans follow each other in list order without a gap.  Returns
+    (sample_first [n_chunks], chunk_first [n_mixes + 1], block_first [n_mixes + 1], chunk_mix [n_chunks], n_samples):
+    the four arrays as numpy int64, chunk_mix[c] the mix chunk c belongs to.  Input spans may also coincide (two streams
+    hearing one source): point their sample_first entries at the same span instead.  Mixes are independent of each
+    other, so over ranks a delivery is split by whole mixes: stftmask_batch_shard(blocks_per_mix, rank, world), with a
+    mix's streams living on the rank that renders it.  Negative counts or lengths that differ: ValueError."""
+    import numpy as np
+    blocks = np.asarray(blocks_per_mix, dtype=np.int64).reshape(-1)
+    chunks = np.asarray(chunks_per_mix, dtype=np.int64).reshape(-1)
+    if blocks.size != chunks.size:
+        raise ValueError("one block count and one chunk count per mix")
+    if np.any(blocks < 0) or np.any(chunks < 0):
+        raise ValueError("block and chunk counts must be >= 0")
+    zero = np.zeros(1, np.int64)
+    chunk_first = np.concatenate([zero, np.cumsum(chunks, dtype=np.int64)])
+    block_first = np.concatenate([zero, np.cumsum(blocks, dtype=np.int64)])
+    chunk_mix = np.repeat(np.arange(blocks.size, dtype=np.int64), chunks)
+    spans = 512 * blocks[chunk_mix]
+    sample_first = np.concatenate([zero, np.cumsum(spans, dtype=np.int64)])
+    return sample_first[:-1].copy(), chunk_first, block_first, chunk_mix, int(sample_first[-1])
+
+
 def denoise_stream_emitted(blocks_seen, block_counts):
     """What the chunks of one Denoiser.process_streams call emit (jdsp_denoise_streams' n_emitted): a stream's first two
     blocks emit nothing (SS:260-263: the reference's call counter), so the chunk of B_c = block_counts[c] blocks of a

@@ -758,6 +758,101 @@ def main():
                "BASELINE config 2: 256-tap pair, 769-sample blocks, mono in -> 2 ears out",
                cpu=cpu_rate(lambda: [orc.fastconv_stream(xs, h2[0], 1024), orc.fastconv_stream(xs, h2[1], 1024)], 512))
         fc.close()
+    if on("binaural"):
+        # Live binaural rendering (jdsp_binaural_render_dev): 2,000 mixes x 8 sources x 2 blocks per delivery out of a
+        # bank of 256 directions x 256 taps, 16,000 live streams.  Timed in this process, in alternated rounds, every C
+        # entry called through ctypes with its arguments computed beforehand: (a) no stream fades; (a') every stream
+        # moves in every delivery (the worst case: block 0 of every mix takes four inverse transforms); (b) today's
+        # route -- one jdsp_fastconv handle per source (n_fft 1024, the direction's two filters zero-padded to 513 taps
+        # so that its blocks are the same 512 samples) in a loop of _process_dev plus a torch sum per mix --, over the
+        # first 25 mixes and scaled by 80; (c) the yardstick: BASELINE config 2's convolver leg as time per transform
+        # (3 per block; (a) does S + 2 per block, (a') S + 4 for block 0 of a mix).  The inputs rotate over 9 copies of
+        # 32.8 MB (295 MB, past the 256 MiB Infinity Cache).
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        M, S, NB, n_dirs, n_taps, n_loop_mixes = 2000, 8, 2, 256, 256, 25
+        brng = np.random.default_rng(20)
+        bank = brng.normal(size=(n_dirs, 2, n_taps)) * np.exp(-np.arange(n_taps) / 48.0) * 0.05
+        hb = eng.binaural(bank)
+        n_chunks, total = M * S, M * NB
+        hb.open_streams(n_chunks)
+        sf, cf, bf, _, n_samples = sharding.binaural_layout([NB] * M, [S] * M)
+        vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)   # noqa: E731
+        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()   # noqa: E731
+        d_ids = dev(brng.permutation(n_chunks).astype(np.int64))
+        d_sf, d_cf, d_bf = dev(sf), dev(cf), dev(bf)
+        dirs0 = brng.integers(0, n_dirs, n_chunks).astype(np.int32)
+        d_dir = [dev(dirs0), dev((dirs0 + 1 + brng.integers(0, n_dirs - 1, n_chunks).astype(np.int32)) % n_dirs)]
+        d_gain = dev(brng.uniform(0.1, 2.0, n_chunks).astype(np.float32))
+        gen = torch.Generator(device="cuda").manual_seed(20)
+        ins = [(torch.randn(n_samples, device="cuda", generator=gen) * 1500.0).round_().clamp_(-32768, 32767).to(torch.int16)
+               for _ in range(1 if a.warm else 9)]
+        plane = 512 * total
+        o16 = torch.empty(2 * plane, dtype=torch.int16, device="cuda")
+        args = [[(hb._h, vp(x), vp(d_ids), vp(d_sf), vp(d), vp(d_gain), vp(d_cf), vp(d_bf), M, n_chunks, total, vp(o16),
+                  None, plane) for x in ins] for d in d_dir]
+        # (b): the first n_loop_mixes mixes' sources, one handle each
+        n_loop = n_loop_mixes * S
+        padded = np.zeros((n_dirs, 2, 513))
+        padded[:, :, :n_taps] = bank
+        singles = [eng.fastconv(padded[dirs0[c]], 1024) for c in range(n_loop)]
+        assert singles[0].block == 512
+        b16 = torch.empty((n_loop, 2, NB * 512), dtype=torch.int16, device="cuda")
+        args_b = [(h._h, vp(ins[0], 2 * int(sf[c])), NB, vp(b16[c]), None, None) for c, h in enumerate(singles)]
+        # (c): config 2's convolver leg
+        nb_c = 65536
+        xc = torch.from_numpy(pcm_of(rng, nb_c * 769, 2000.0)).cuda()
+        fcc = eng.fastconv(rng.normal(size=(2, 256)) * 0.1, 1024)
+        xcr = rot(xc)
+        eng._use_torch_stream()
+        turn = [0, 0]
+
+        def call_a():
+            turn[0] += 1
+            L.jdsp_binaural_render_dev(*args[0][turn[0] % len(ins)])
+
+        def call_fade():
+            turn[1] += 1
+            L.jdsp_binaural_render_dev(*args[turn[1] & 1][turn[1] % len(ins)])
+
+        def loop():
+            for p in args_b:
+                L.jdsp_fastconv_process_dev(*p)
+            b16.view(n_loop_mixes, S, 2, NB * 512).sum(dim=1, dtype=torch.int32)
+
+        def call_c():
+            fcc.process(xcr())
+
+        assert L.jdsp_binaural_render_dev(*args[0][0]) == 0 and L.jdsp_fastconv_process_dev(*args_b[0]) == 0
+        for h in singles:                                        # past every handle's first block, which it drops
+            L.jdsp_fastconv_process_dev(h._h, vp(ins[0]), 1, vp(b16), None, None)
+        it = max(5 * a.iters, 20)
+        ms_a, ms_f, ms_b, ms_c = timed_alternated([call_a, call_fade, loop, call_c], [it, it, 1, a.iters], rounds=5)
+        ms_b *= M / n_loop_mixes
+        tr_a, tr_f, tr_c = ms_a / (M * NB * (S + 2)), ms_f / (M * (NB * (S + 2) + 2)), ms_c / (nb_c * 3)
+        inp = "rotated over %d copies of %.1f MB (from HBM)" % (len(ins), 2e-6 * n_samples)
+        shape = "%d mixes x %d sources x %d blocks, bank %d directions x %d taps" % (M, S, NB, n_dirs, n_taps)
+        tflops = lambda n_tr: n_tr * (5 * 512 * 9 + 512 * 14) + S * 2 * 640 * 8   # noqa: E731
+        report("binaural_render", ms_a, total, "blocks", S * 1024 + 2 * 1024, tflops(S + 2),
+               "(a) jdsp_binaural_render_dev, no stream fading: %s; %.2f ns per transform = %.3f x the config-2 convolver's "
+               "%.2f ns (c); %.4f of the per-source loop (b); %d calls per round, 5 rounds"
+               % (shape, 1e6 * tr_a, tr_a / tr_c, 1e6 * tr_c, ms_a / ms_b, it), inp=inp)
+        report("binaural_render_all_fading", ms_f, total, "blocks", S * 1024 + 2 * 1024, tflops(S + 3),
+               "(a') the same with every stream moving in every delivery: block 0 of every mix takes S + 4 transforms; "
+               "%.2f ns per transform = %.3f x (c); %.3f x (a)" % (1e6 * tr_f, tr_f / tr_c, ms_f / ms_a), inp=inp)
+        report("binaural_per_source_loop", ms_b, total, "blocks", S * 1024 + S * 2 * 1024, tflops(3 * S),
+               "(b) today's route: one jdsp_fastconv handle per source (n_fft 1024, two filters, taps zero-padded to 513: blocks "
+               "of 512) in a loop of jdsp_fastconv_process_dev from ctypes with precomputed arguments, and one torch sum "
+               "per delivery over the sources of each mix: measured over %d mixes and scaled by %d; %.1f x (a)"
+               % (n_loop_mixes, M // n_loop_mixes, ms_b / ms_a), inp=inp)
+        report("binaural_yardstick_fastconv_1024_hrir_pair", ms_c, nb_c, "blocks", 4614, 3 * 5 * 512 * 9 + 3 * 512 * 14 + 2 * 1024 * 6,
+               "(c) BASELINE config 2 in the same alternated rounds: %.2f ns per transform (3 per block)" % (1e6 * tr_c))
+        for h in singles:
+            h.close()
+        fcc.close()
+        hb.close()
+        del ins, o16, b16, xc, xcr, args, args_b
     if on("fft"):
         n = 65536
         z = torch.from_numpy(rng.normal(size=(n, 512)) + 1j * rng.normal(size=(n, 512))).cuda()
