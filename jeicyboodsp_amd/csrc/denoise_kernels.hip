@@ -1599,20 +1599,33 @@ static void launch_denoise_redo(hipStream_t s, int n_fft, const short *pcm, long
 }
 
 // =======================================================================================
-// A batch of ragged utterances, each a fresh stream of main() (jdsp_denoise_batch*, include/jdsp.h): the VAD over the
-// concatenated block axis (vad_flags_batch_kernel above), then
-//   noise_batch_kernel         one wave per UTTERANCE walks its flags in order: main()'s run-length counter (SS:98-109),
-//                              the running average A <- h (A + |X|) of its events in registers (SS:165-187), a latch at
-//                              run length 10 (SS:189-193) into the row table, and per block the index of the row in
-//                              force.  All three start from zero at the utterance's first block.
-//   denoise_batch_kernel       denoise_run_kernel's frame over the concatenated block axis: the waves are planned over
-//                              all blocks, a wave finds its utterance by ragged_batch.h's search and walks on
-//   denoise_redo_f64_batch_kernel   the listed frames again in FP64, inside their utterance's bounds
-// An utterance holds a few hundred events where a stream holds tens of thousands, so the chain is not cut into affine
-// maps here: cutting it at positions of the batch would make an utterance's bits depend on where it stands.  Row 0 of
-// the table is zeros (nothing latched yet), shared by all utterances; an utterance of B blocks latches at most
-// floor(B / 10) times and sum floor(B_u / 10) <= floor(sum B_u / 10), so utterance u's rows start at
-// 1 + block_first[u] / 10 and no prefix sum over the utterances is needed.
+// Ragged calls over one concatenated block axis (ragged_batch.h), in two forms:
+//   a batch of ragged utterances, each a fresh stream of main() (jdsp_denoise_batch*, include/jdsp.h);
+//   the chunks of LIVE streams (jdsp_denoise_streams*; DenoiseLive, jdsp_internal.h): the batch's layout with chunks for
+//   utterances, but a chunk continues its stream instead of starting one.  Bit for bit the stream's emitted blocks are
+//   what the batch writes for ONE utterance of all its blocks, however they are cut.
+// Both forms are the same code below (a "chunk" is an utterance of the batch or a chunk of a live call); a carrier per
+// form, in the manner of RedoBatch / RedoLive, spells out in one-line members what a fresh chunk and a continued one
+// differ in.  After the VAD over the block axis (vad_flags_batch_kernel above):
+//   noise_chain         one wave per CHUNK walks its flags in order: main()'s run-length counter (SS:98-109), the
+//                       running average A <- h (A + |X|) of its events in registers (SS:165-187), a latch at run length
+//                       10 (SS:189-193) into the call's row table, and per block the index of the row in force.
+//                       noise_batch_kernel (NoiseBatch): all three start from zero.  noise_live_kernel (NoiseLive): from
+//                       the stream's carried run length, average and estimate.
+//   denoise_chunk_walk  denoise_run_kernel's frame over the block axis: the waves are planned over all blocks, a wave
+//                       finds its chunk by ragged_batch.h's search and walks on.  denoise_batch_kernel (WalkBatch, empty):
+//                       a chunk starts a stream.  denoise_live_kernel (WalkLive): where the halo frame would lie in front
+//                       of the chunk, the carried tail (that frame's y[d + 4]) and the carried previous block stand in.
+//   redo_f64_run        the listed frames again in FP64, inside their chunk's bounds (RedoBatch), or from the stream's
+//                       last two blocks and carried estimate where the frame lies in front of the chunk (RedoLive)
+//   denoise_live_commit_kernel   live only: flips the parities, counts the blocks, reports E_c
+// A chunk holds a few hundred events where a handle's own stream holds tens of thousands, so the chain is not cut into
+// affine maps here: cutting it at positions of the call would make a chunk's bits depend on where it stands.
+// The batch's row table: row 0 is zeros (nothing latched yet), shared by all utterances; an utterance of B blocks latches
+// at most floor(B / 10) times and sum floor(B_u / 10) <= floor(sum B_u / 10), so utterance u's rows start at
+// 1 + block_first[u] / 10 and no prefix sum over the utterances is needed.  The live table: the two estimate copies of
+// every stream, then chunk c's rows from 2 n_streams + c + block_first[c] / 11 (a chunk of B blocks latches
+// 1 + (B - 1) / 11 times at most).
 __device__ __forceinline__ void load_pairs(const short *__restrict__ block, int lane, unsigned int (&q)[4])
 {
     const unsigned int *src = reinterpret_cast<const unsigned int *>(block) + lane;
@@ -1620,241 +1633,6 @@ __device__ __forceinline__ void load_pairs(const short *__restrict__ block, int 
     for (int r = 0; r < 4; r++) q[r] = src[64 * r];
 }
 
-__global__ __launch_bounds__(64) void noise_batch_kernel(const short *__restrict__ pcm,
-                                                         const long long *__restrict__ sample_first,
-                                                         const long long *__restrict__ block_first,
-                                                         const unsigned char *__restrict__ flags,
-                                                         const float2 *__restrict__ table, float *__restrict__ rows,
-                                                         int *__restrict__ row_idx, float *__restrict__ noise_last)
-{
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    const int lane = threadIdx.x;
-    const long u = blockIdx.x;
-    const long ub = uniform_i64(block_first + u), n_own = uniform_i64(block_first + u + 1) - ub;
-    const short *own = pcm + uniform_i64(sample_first + u);
-    FrameTables t;
-    load_frame_tables(t, table, lane);
-    PairTwiddles pw;
-    load_pair_twiddles(pw, table, lane);
-    // the average in noise_accum_kernel's pair-owned layout: bins m, m + 512 of m = lane + 64 d; a row is stored as its
-    // ten own values plus the mirrors of m = 1..192
-    constexpr int ND = 5;
-    float alo[ND], ahi[ND];
-#pragma unroll
-    for (int d = 0; d < ND; d++) alo[d] = ahi[d] = 0.0f;
-    auto store_row = [&](float *row) {
-#pragma unroll
-        for (int d = 0; d < ND; d++) { row[lane + 64 * d] = alo[d]; row[lane + 64 * d + 512] = ahi[d]; }
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const int m = lane + 64 * d;
-            if (m >= 1 && m <= 192) { row[1024 - m] = alo[d]; row[512 - m] = ahi[d]; }
-        }
-    };
-    int run_len = 0, row = 0;                                    // iNumOfIteration (SS:72); the row in force
-    int next_row = 1 + (int)(ub / 10);
-    for (long c = 0; c < n_own; c += 64) {
-        const int n = n_own - c < 64 ? (int)(n_own - c) : 64;
-        const unsigned long long voice = __ballot(lane < n && flags[ub + c + lane] != 0);
-        int mine = 0;                                            // the row of block c + lane
-        for (int i = 0; i < n; i++) {
-            if ((voice >> i) & 1ull) {
-                run_len = 0;                                     // SS:108
-            } else if (++run_len >= 2) {                         // SS:103-105: EstimateNoiseSpectrum
-                const short *cur_block = own + (c + i) * 512;    // run length 2 at least: block c + i - 1 is the utterance's
-                unsigned int prev[4], cur[4];
-                load_pairs(cur_block - 512, lane, prev);         // rgssKeepBuffer (SS:165-170)
-                load_pairs(cur_block, lane, cur);
-                float2 v[8], zr[ND];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
-                    v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
-                    v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
-                }
-                wave_fft512<false>(v, lds, lane, t.tw);
-                wave_lds_fence();
-                pair_fetch_lds(v, lds, lane, zr);
-                const float h = run_len >= 3 ? 0.5f : 1.0f;      // SS:182-187
-#pragma unroll
-                for (int d = 0; d < ND; d++) {
-                    const float2 ev = cadd_conj(v[d], zr[d]), od = csub_conj_mj(v[d], zr[d]);
-                    const float2 tw = cmul(pw.w[d], od);
-                    const float2 lo = cadd(ev, tw), hi = csub(ev, tw);
-                    // hardware square root, 1 ulp (see noise_accum_kernel)
-                    alo[d] = (alo[d] + __builtin_amdgcn_sqrtf(lo.x * lo.x + lo.y * lo.y)) * h;
-                    ahi[d] = (ahi[d] + __builtin_amdgcn_sqrtf(hi.x * hi.x + hi.y * hi.y)) * h;
-                }
-                if (run_len == 10) {                             // SS:189-193; it applies to this block already
-                    row = next_row++;
-                    store_row(rows + (size_t)row * 1024);
-                    if (noise_last) store_row(noise_last + (size_t)u * 1024);
-                }
-            }
-            if (lane == i) mine = row;
-        }
-        if (lane < n) row_idx[ub + c + lane] = mine;
-    }
-    if (noise_last && row == 0) {                                // nothing latched: rgdEstimatedNS is still zero (SS:70)
-#pragma unroll
-        for (int r = 0; r < 16; r++) noise_last[(size_t)u * 1024 + lane + 64 * r] = 0.0f;
-    }
-}
-
-// denoise_run_kernel over the concatenated block axis.  Wave w owns the global blocks [w run, (w + 1) run); global
-// block j of utterance u (block_first[u] <= j < block_first[u + 1]) is its local block b = j - block_first[u] at the
-// samples base + 512 j.  Local block 0 only stashes its samples (SS:211-216), so the overlap restarts from zero by
-// itself where an utterance begins; the frame of local block b >= 1 is [block b - 1, block b], and with the overlap
-// it gives the enhanced samples at the time of block b - 1, written there when b >= 2 (SS:260-263: the first two
-// calls emit nothing).  So an utterance's first and last blocks are never written.  The halo frame in front of the
-// wave's first block goes through the SAME loop body as every other frame (emission off), never into the utterance
-// before: one inlined copy of the arithmetic, so the samples do not depend on where the waves are cut.
-template <int MODE>
-__global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_batch_kernel(
-    const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
-    long n_utts, long n_blocks, const int *__restrict__ row_idx, const float *__restrict__ noise_rows,
-    const float2 *__restrict__ table, short *__restrict__ out, float *__restrict__ precast, int run, int *__restrict__ redo)
-{
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    const int lane = threadIdx.x;
-    PhaseStat ps;
-    const long per_xcd = (gridDim.x + 7) >> 3;                // XCD-aware run order (speed only)
-    const long j0 = ((long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3)) * run;
-    if (j0 >= n_blocks) return;
-    const long j1 = j0 + run < n_blocks ? j0 + run : n_blocks;
-    long u = ragged_find_utt(block_first, n_utts, j0);
-    long ub = uniform_i64(block_first + u), ue = uniform_i64(block_first + u + 1);
-    long base = uniform_i64(sample_first + u) - ub * 512;      // global block j of this utterance starts at base + 512 j
-    // local block 0 or 1: the overlap entering block j0 is empty; else the frame of block j0 - 1 rebuilds it
-    const long js = j0 - ub >= 2 ? j0 - 1 : j0;
-
-    FrameTables t;
-    load_frame_tables(t, table, lane);
-    PairTwiddles sw;
-    load_pair_twiddles(sw, table, lane);
-    NoisePairRegs nz;
-    unsigned int raw[8], nxt[4], tk[4];
-    float2 tail[4], y[8];
-#pragma unroll
-    for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
-    // the block in front of js, clamped into the utterance (unused where it is clamped: local block 0 has no frame)
-    load_pairs(pcm + base + (js > ub ? js - 1 : ub) * 512, lane, nxt);
-#pragma unroll
-    for (int r = 0; r < 4; r++) raw[r + 4] = nxt[r];
-    load_pairs(pcm + base + js * 512, lane, tk);
-    int cur_row = -1;
-    int next_idx = __builtin_amdgcn_readfirstlane(row_idx[js]);
-    unsigned prio_step = blockIdx.x >> 10;                    // step_priority: one step per block
-    for (long j = js; j < j1; j++) {
-        step_priority(prio_step);
-#pragma unroll
-        for (int r = 0; r < 4; r++) { raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
-        const int idx = next_idx;
-        // the next block, needed one iteration from now (denoise_run_kernel); after an utterance's last block it is
-        // the first block of the next non-empty one
-        long un = u, ubn = ub, uen = ue, basen = base;
-        if (j + 1 < j1) {
-            if (j + 1 == ue) {
-                ubn = ue;
-                ragged_next_utt(block_first, n_utts, un, uen);
-                basen = uniform_i64(sample_first + un) - ubn * 512;
-            }
-            next_idx = row_idx[j + 1];
-            load_pairs(pcm + basen + (j + 1) * 512, lane, nxt);
-        }
-        const long b = j - ub;
-        if (b == 0) {
-            // the first call of a stream only stashes its block (SS:211-216): no output, empty overlap
-#pragma unroll
-            for (int d = 0; d < 8; d++) y[d] = make_float2(0.f, 0.f);
-        } else {
-            if (idx != cur_row) {                                // wave-uniform: another estimate is in force
-                cur_row = idx;
-                load_noise_pair_regs<MODE>(nz, noise_rows + (size_t)idx * 1024, lane);
-            }
-            denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);
-            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
-            if (MODE == 0 && j >= j0 && ue - ub >= 3 && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) phase_redo(redo, j, lane);
-        }
-        float2 o[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            o[d] = make_float2(tail[d].x + y[d].x, tail[d].y + y[d].y);      // SS:248 overlap-add
-            tail[d] = y[d + 4];                                               // SS:255-256
-        }
-        // taken before this block's stores (denoise_run_kernel)
-#pragma unroll
-        for (int r = 0; r < 4; r++) { tk[r] = nxt[r]; asm volatile("" : "+v"(tk[r])); }
-        next_idx = __builtin_amdgcn_readfirstlane(next_idx);
-        __builtin_amdgcn_sched_barrier(0);
-        if (j >= j0 && b >= 2) {
-            const long at = base + (j - 1) * 512;                // the time of local block b - 1
-            if (out) {
-                unsigned int *dst = reinterpret_cast<unsigned int *>(out + at) + lane;
-#pragma unroll
-                for (int d = 0; d < 4; d++) __builtin_nontemporal_store(cast_i16x2_bits(o[d].x, o[d].y), dst + 64 * d);
-            }
-            if (precast) {
-#pragma unroll
-                for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(precast + at + 2 * lane + 128 * d) = o[d];
-            }
-        }
-        u = un; ub = ubn; ue = uen; base = basen;
-    }
-}
-
-__global__ __launch_bounds__(256) void denoise_redo_f64_batch_kernel(
-    const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
-    long n_utts, const int *__restrict__ row_idx, const float *__restrict__ noise_rows, short *__restrict__ out,
-    float *__restrict__ precast, const int *__restrict__ redo, int mode)
-{
-    redo_f64_run<1024>(redo, mode, RedoBatch{pcm, sample_first, block_first, n_utts, row_idx, noise_rows, out, precast,
-                                             0, 0, 0, 0});
-}
-
-// run_opt: blocks per wave, 0 = one round of resident waves (resident_run).  flags / row_idx
-// [n_blocks], rows [n_blocks / 10 + 1][1024] with row 0 zero, redo [n_blocks + 1]: the handle's batch workspace.
-// out and precast may be NULL (both: the run kernel is not launched); noise_last may be NULL.
-int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *sample_first,
-                         const long long *block_first, long n_utts, long n_blocks, const double *w_hi,
-                         const float2 *table, unsigned char *flags, int *row_idx, float *rows, int *redo, short *out,
-                         float *precast, float *noise_last, int vad_only)
-{
-    if (n_blocks <= 0 || n_utts <= 0) return 0;
-    hipLaunchKernelGGL(vad_flags_batch_kernel, dim3((unsigned)((n_blocks + kVadBlocksPerWave - 1) / kVadBlocksPerWave)),
-                       dim3(64), 0, s, pcm, sample_first, block_first, n_utts, n_blocks, w_hi, flags);
-    if (vad_only) return hipGetLastError() == hipSuccess ? 0 : -1;
-    hipLaunchKernelGGL(noise_batch_kernel, dim3((unsigned)n_utts), dim3(64), 0, s, pcm, sample_first, block_first, flags,
-                       table, rows, row_idx, noise_last);
-    if (!out && !precast) return hipGetLastError() == hipSuccess ? 0 : -1;
-    if (mode == 0 && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
-    const long run = run_opt > 0 ? run_opt : resident_run(n_cu, n_blocks);
-    const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
-    if (mode == 0)
-        hipLaunchKernelGGL(denoise_batch_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, sample_first, block_first,
-                           n_utts, n_blocks, row_idx, rows, table, out, precast, (int)run, redo);
-    else
-        hipLaunchKernelGGL(denoise_batch_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, sample_first, block_first,
-                           n_utts, n_blocks, row_idx, rows, table, out, precast, (int)run, redo);
-    if (mode == 0)
-        hipLaunchKernelGGL(denoise_redo_f64_batch_kernel, dim3((unsigned)(n_blocks < kRedoGrid ? n_blocks : kRedoGrid)),
-                           dim3(256), 0, s, pcm, sample_first, block_first, n_utts, row_idx, rows, out, precast, redo, mode);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-// =======================================================================================
-// The chunks of LIVE streams (jdsp_denoise_streams*, include/jdsp.h; DenoiseLive, jdsp_internal.h): the batch's layout
-// with chunks for utterances, but a chunk continues its stream instead of starting one.  Bit for bit the stream's
-// emitted blocks are what the batch kernels above write for ONE utterance of all its blocks, however they are cut:
-//   noise_live_kernel        noise_batch_kernel's chain, statement for statement, from the stream's carried run length
-//                            and average; before the chunk's first latch the estimate in force is the carried one
-//   denoise_live_kernel      denoise_batch_kernel's loop; where that kernel's halo frame would lie in front of the
-//                            chunk, the carried tail (that frame's y[d + 4]) and the carried previous block stand in
-//   denoise_redo_f64_live_kernel   redo_f64_run over RedoLive: a frame in front of the chunk is rebuilt from the
-//                            stream's last two blocks and the carried estimate
-//   denoise_live_commit_kernel     flips the parities, counts the blocks, reports E_c
-// Emission follows the stream: the block with stream index i >= 2 goes out packed from the span's start, block i -
-// max(N, 2) of the span for a stream that had seen N blocks.
 struct LiveChunk {
     long s, N;                                                   // the stream, the blocks it had seen
     int p;                                                       // the copy of prev / tail / listed it starts from
@@ -1869,6 +1647,171 @@ __device__ __forceinline__ LiveChunk live_chunk(const long long *__restrict__ st
     return k;
 }
 
+// The running average of a chunk's wave in registers, in noise_accum_kernel's pair-owned layout: the bins m, m + 512 of
+// m = lane + 64 d; a row is stored as the ten own values plus the mirrors of m = 1..192.  The event's arithmetic and
+// the row's store are that kernel's, which keeps its own text: with all three noise kernels on this struct the
+// compiler orders eight zero moves in denoise_run_kernel<0>'s prologue differently, and no kernel outside the chain
+// and the walk was to change (profiles/r21_denoise_one_walk.txt).
+struct NoiseAvg {
+    static constexpr int ND = 5;
+    float lo[ND], hi[ND];
+    __device__ __forceinline__ void zero()
+    {
+#pragma unroll
+        for (int d = 0; d < ND; d++) lo[d] = hi[d] = 0.0f;
+    }
+    // one EstimateNoiseSpectrum event, A <- h (A + |FFT(window * [prev, cur])|): the blocks as load_block_pairs gives them
+    __device__ __forceinline__ void accumulate(const unsigned int (&prev)[4], const unsigned int (&cur)[4],
+                                               const FrameTables &t, const PairTwiddles &pw, float2 *lds, int lane, float h)
+    {
+        float2 v[8], zr[ND];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
+            v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
+            v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
+        }
+        wave_fft512<false>(v, lds, lane, t.tw);
+        wave_lds_fence();
+        pair_fetch_lds(v, lds, lane, zr);
+#pragma unroll
+        for (int d = 0; d < ND; d++) {
+            const float2 ev = cadd_conj(v[d], zr[d]), od = csub_conj_mj(v[d], zr[d]);
+            const float2 tw = cmul(pw.w[d], od);
+            const float2 a = cadd(ev, tw), b = csub(ev, tw);
+            // hardware square root, 1 ulp (see noise_accum_kernel)
+            lo[d] = (lo[d] + __builtin_amdgcn_sqrtf(a.x * a.x + a.y * a.y)) * h;
+            hi[d] = (hi[d] + __builtin_amdgcn_sqrtf(b.x * b.x + b.y * b.y)) * h;
+        }
+    }
+    __device__ __forceinline__ void store_row(float *row, int lane) const
+    {
+#pragma unroll
+        for (int d = 0; d < ND; d++) { row[lane + 64 * d] = lo[d]; row[lane + 64 * d + 512] = hi[d]; }
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const int m = lane + 64 * d;
+            if (m >= 1 && m <= 192) { row[1024 - m] = lo[d]; row[512 - m] = hi[d]; }
+        }
+    }
+};
+
+// What a fresh chunk and a continued one differ in, in the chain below.  start(): the average and the run length the chunk
+// begins with; row_in_force(): the row before its first latch; first_row(ub): the first row of the call's table it may
+// latch into; before(): the block in front of its first block; latch(): the second destination of a latched average;
+// finish(): after the last block.
+struct NoiseBatch {
+    float *noise_last;        // [n_utts][1024] or NULL: the estimate each utterance ends with
+    long u;
+    __device__ __forceinline__ int start(NoiseAvg &a, int) const { a.zero(); return 0; }
+    __device__ __forceinline__ int row_in_force() const { return 0; }
+    __device__ __forceinline__ int first_row(long ub) const { return 1 + (int)(ub / 10); }
+    // never read: the run length starts at 0
+    __device__ __forceinline__ const short *before(const short *own) const { return own - 512; }
+    __device__ __forceinline__ void latch(const NoiseAvg &a, int lane) const
+    {
+        if (noise_last) a.store_row(noise_last + (size_t)u * 1024, lane);
+    }
+    __device__ __forceinline__ void finish(const NoiseAvg &, int, bool latched, int lane) const
+    {
+        if (!noise_last || latched) return;                      // nothing latched: rgdEstimatedNS is still zero (SS:70)
+#pragma unroll
+        for (int r = 0; r < 16; r++) noise_last[(size_t)u * 1024 + lane + 64 * r] = 0.0f;
+    }
+};
+
+struct NoiseLive {
+    DenoiseLive lv;
+    long c;                   // the chunk
+    LiveChunk k;
+    int ep;                   // the estimate copy in force
+    __device__ __forceinline__ float *avg() const { return lv.avg + (size_t)k.s * kLiveAvgFloats; }
+    __device__ __forceinline__ int start(NoiseAvg &a, int lane) const
+    {
+#pragma unroll
+        for (int d = 0; d < NoiseAvg::ND; d++) { a.lo[d] = avg()[lane + 64 * d]; a.hi[d] = avg()[320 + lane + 64 * d]; }
+        return __builtin_amdgcn_readfirstlane(lv.run_len[k.s]);
+    }
+    __device__ __forceinline__ int row_in_force() const { return (int)(ep * lv.n_streams + k.s); }
+    __device__ __forceinline__ int first_row(long ub) const { return (int)(2 * lv.n_streams + c + ub / 11); }
+    __device__ __forceinline__ const short *before(const short *) const                      // the stream's last block
+    {
+        return lv.prev + ((size_t)k.p * lv.n_streams + k.s) * 1024 + 512;
+    }
+    __device__ __forceinline__ void latch(const NoiseAvg &a, int lane) const                 // the stream's next estimate
+    {
+        a.store_row(lv.rows + ((size_t)(ep ^ 1) * lv.n_streams + k.s) * 1024, lane);
+    }
+    __device__ __forceinline__ void finish(const NoiseAvg &a, int run_len, bool latched, int lane) const
+    {
+#pragma unroll
+        for (int d = 0; d < NoiseAvg::ND; d++) { avg()[lane + 64 * d] = a.lo[d]; avg()[320 + lane + 64 * d] = a.hi[d]; }
+        if (lane == 0) {
+            lv.run_len[k.s] = run_len;
+            lv.latched[c] = latched;
+        }
+    }
+};
+
+// own: the chunk's samples; ub, n_own: its first block on the block axis, its blocks; rows: the call's row table
+template <class Carry>
+__device__ __forceinline__ void noise_chain(const short *own, long ub, long n_own, const unsigned char *__restrict__ flags,
+                                            const float2 *__restrict__ table, float *rows, int *__restrict__ row_idx,
+                                            Carry cy)
+{
+    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
+    const int lane = threadIdx.x;
+    FrameTables t;
+    load_frame_tables(t, table, lane);
+    PairTwiddles pw;
+    load_pair_twiddles(pw, table, lane);
+    NoiseAvg a;
+    int run_len = cy.start(a, lane);                             // iNumOfIteration (SS:72)
+    int row = cy.row_in_force(), next_row = cy.first_row(ub);
+    bool latched = false;
+    for (long c = 0; c < n_own; c += 64) {
+        const int n = n_own - c < 64 ? (int)(n_own - c) : 64;
+        const unsigned long long voice = __ballot(lane < n && flags[ub + c + lane] != 0);
+        int mine = 0;                                            // the row of block c + lane
+        for (int i = 0; i < n; i++) {
+            if ((voice >> i) & 1ull) {
+                run_len = 0;                                     // SS:108
+            } else {
+                run_len = run_len < 11 ? run_len + 1 : 11;       // saturated: only >= 2, >= 3 and == 10 are asked of it
+                if (run_len >= 2) {                              // SS:103-105: EstimateNoiseSpectrum
+                    const short *cur_block = own + (c + i) * 512;
+                    unsigned int prev[4], cur[4];
+                    load_pairs(c + i == 0 ? cy.before(own) : cur_block - 512, lane, prev);   // rgssKeepBuffer (SS:165-170)
+                    load_pairs(cur_block, lane, cur);
+                    a.accumulate(prev, cur, t, pw, lds, lane, run_len >= 3 ? 0.5f : 1.0f);   // SS:182-187
+                    if (run_len == 10) {                         // SS:189-193; it applies to this block already
+                        row = next_row++;
+                        latched = true;
+                        a.store_row(rows + (size_t)row * 1024, lane);
+                        cy.latch(a, lane);
+                    }
+                }
+            }
+            if (lane == i) mine = row;
+        }
+        if (lane < n) row_idx[ub + c + lane] = mine;
+    }
+    cy.finish(a, run_len, latched, lane);
+}
+
+__global__ __launch_bounds__(64) void noise_batch_kernel(const short *__restrict__ pcm,
+                                                         const long long *__restrict__ sample_first,
+                                                         const long long *__restrict__ block_first,
+                                                         const unsigned char *__restrict__ flags,
+                                                         const float2 *__restrict__ table, float *__restrict__ rows,
+                                                         int *__restrict__ row_idx, float *__restrict__ noise_last)
+{
+    const long u = blockIdx.x;
+    const long ub = uniform_i64(block_first + u), n_own = uniform_i64(block_first + u + 1) - ub;
+    const short *own = pcm + uniform_i64(sample_first + u);
+    noise_chain(own, ub, n_own, flags, table, rows, row_idx, NoiseBatch{noise_last, u});
+}
+
 __global__ __launch_bounds__(64) void noise_live_kernel(const short *__restrict__ pcm,
                                                         const long long *__restrict__ stream_id,
                                                         const long long *__restrict__ sample_first,
@@ -1877,96 +1820,99 @@ __global__ __launch_bounds__(64) void noise_live_kernel(const short *__restrict_
                                                         const float2 *__restrict__ table, int *__restrict__ row_idx,
                                                         DenoiseLive lv)
 {
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    const int lane = threadIdx.x;
     const long c = blockIdx.x;
     const long ub = uniform_i64(block_first + c), n_own = uniform_i64(block_first + c + 1) - ub;
+    const short *own = pcm + uniform_i64(sample_first + c);     // (with the loads above: nothing it waits for)
     if (n_own <= 0) return;                                      // the stream is not touched (the commit skips it too)
     const LiveChunk k = live_chunk(stream_id, lv.parity, lv.seen, c);
     const int ep = __builtin_amdgcn_readfirstlane(lv.est_parity[k.s]) & 1;
-    const short *own = pcm + uniform_i64(sample_first + c);
-    const short *before = lv.prev + ((size_t)k.p * lv.n_streams + k.s) * 1024 + 512;     // the stream's last block
-    FrameTables t;
-    load_frame_tables(t, table, lane);
-    PairTwiddles pw;
-    load_pair_twiddles(pw, table, lane);
-    constexpr int ND = 5;
-    float alo[ND], ahi[ND];
-    float *avg = lv.avg + (size_t)k.s * kLiveAvgFloats;
-#pragma unroll
-    for (int d = 0; d < ND; d++) { alo[d] = avg[lane + 64 * d]; ahi[d] = avg[320 + lane + 64 * d]; }
-    auto store_row = [&](float *row) {
-#pragma unroll
-        for (int d = 0; d < ND; d++) { row[lane + 64 * d] = alo[d]; row[lane + 64 * d + 512] = ahi[d]; }
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const int m = lane + 64 * d;
-            if (m >= 1 && m <= 192) { row[1024 - m] = alo[d]; row[512 - m] = ahi[d]; }
-        }
-    };
-    int run_len = __builtin_amdgcn_readfirstlane(lv.run_len[k.s]);
-    int row = (int)(ep * lv.n_streams + k.s);                    // the carried estimate
-    int next_row = (int)(2 * lv.n_streams + c + ub / 11);        // a chunk of B blocks latches 1 + (B - 1) / 11 times at most
-    int any = 0;
-    for (long cb = 0; cb < n_own; cb += 64) {
-        const int n = n_own - cb < 64 ? (int)(n_own - cb) : 64;
-        const unsigned long long voice = __ballot(lane < n && flags[ub + cb + lane] != 0);
-        int mine = 0;
-        for (int i = 0; i < n; i++) {
-            if ((voice >> i) & 1ull) {
-                run_len = 0;                                     // SS:108
-            } else {
-                run_len = run_len < 11 ? run_len + 1 : 11;
-                if (run_len >= 2) {                              // SS:103-105: EstimateNoiseSpectrum
-                    const short *cur_block = own + (cb + i) * 512;
-                    unsigned int prev[4], cur[4];
-                    load_pairs(cb + i == 0 ? before : cur_block - 512, lane, prev);      // rgssKeepBuffer (SS:165-170)
-                    load_pairs(cur_block, lane, cur);
-                    float2 v[8], zr[ND];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
-                        v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
-                        v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
-                    }
-                    wave_fft512<false>(v, lds, lane, t.tw);
-                    wave_lds_fence();
-                    pair_fetch_lds(v, lds, lane, zr);
-                    const float h = run_len >= 3 ? 0.5f : 1.0f;  // SS:182-187
-#pragma unroll
-                    for (int d = 0; d < ND; d++) {
-                        const float2 ev = cadd_conj(v[d], zr[d]), od = csub_conj_mj(v[d], zr[d]);
-                        const float2 tw = cmul(pw.w[d], od);
-                        const float2 lo = cadd(ev, tw), hi = csub(ev, tw);
-                        alo[d] = (alo[d] + __builtin_amdgcn_sqrtf(lo.x * lo.x + lo.y * lo.y)) * h;
-                        ahi[d] = (ahi[d] + __builtin_amdgcn_sqrtf(hi.x * hi.x + hi.y * hi.y)) * h;
-                    }
-                    if (run_len == 10) {                         // SS:189-193; it applies to this block already
-                        row = next_row++;
-                        any = 1;
-                        store_row(lv.rows + (size_t)row * 1024);
-                        store_row(lv.rows + ((size_t)(ep ^ 1) * lv.n_streams + k.s) * 1024);   // the stream's next estimate
-                    }
-                }
-            }
-            if (lane == i) mine = row;
-        }
-        if (lane < n) row_idx[ub + cb + lane] = mine;
-    }
-#pragma unroll
-    for (int d = 0; d < ND; d++) { avg[lane + 64 * d] = alo[d]; avg[320 + lane + 64 * d] = ahi[d]; }
-    if (lane == 0) {
-        lv.run_len[k.s] = run_len;
-        lv.latched[c] = any;
-    }
+    noise_chain(own, ub, n_own, flags, table, lv.rows, row_idx, NoiseLive{lv, c, k, ep});
 }
 
-template <int MODE>
-__global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel(
-    const short *__restrict__ pcm, const long long *__restrict__ stream_id, const long long *__restrict__ sample_first,
-    const long long *__restrict__ block_first, const int *__restrict__ parity, const long long *__restrict__ seen,
-    long n_chunks, long n_blocks, const int *__restrict__ row_idx, const float2 *__restrict__ table,
-    short *__restrict__ out, float *__restrict__ precast, int run, int *__restrict__ redo, DenoiseLive lv)
+// What the walk below asks of a chunk that continues a stream; for a chunk that starts one (WalkBatch) every answer is
+// a constant and the struct is empty, so denoise_batch_kernel carries no state operand and no dead branch.
+//   seek(c)        the wave starts in chunk c
+//   seek_next(c)   the next block is the first of chunk c; step(): the walk goes on to the next block
+//   seen()         N, the blocks the chunk's stream had seen: block j of a chunk at ub has stream index N + (j - ub)
+//   enter()        at the chunk's first block: the stream's last block into raw[0..3], its overlap into tail; returns
+//                  whether the stream's last frame went to the FP64 pass
+//   keep_blocks()  at the chunk's last block, in the wave that owns it, BEFORE the frame: the stream's last two blocks
+//                  (the first of them is not kept across the frame: stored after it, it costs scratch)
+//   keep_tail()    the same place AFTER the stores: the overlap and the word the next call starts from
+//   lists(B)       whether a frame FP32 cannot hold, in a chunk of B blocks, goes to the FP64 pass
+//   emit_at()      where the output of block j goes
+struct WalkBatch {
+    __device__ __forceinline__ void seek(long) {}
+    __device__ __forceinline__ void seek_next(long) {}
+    __device__ __forceinline__ void step() {}
+    static __device__ __forceinline__ constexpr long seen() { return 0; }
+    __device__ __forceinline__ int enter(unsigned int (&)[8], float2 (&)[4], int) const { return 0; }
+    __device__ __forceinline__ void keep_blocks(const unsigned int (&)[8], int) const {}
+    __device__ __forceinline__ void keep_tail(const float2 (&)[4], int, int) const {}
+    // fewer than three blocks: nothing of the utterance is emitted
+    __device__ __forceinline__ bool lists(long n_own) const { return n_own >= 3; }
+    // time-aligned: the output of local block b stands at the time of local block b - 1
+    __device__ __forceinline__ long emit_at(long base, long j) const { return base + (j - 1) * 512; }
+};
+
+// The state's loads and stores form their lane offsets per chunk from an opaque copy of the lane: formed from `lane`
+// itself they are loop invariants, hoisted out of the run and kept in registers the frame needs.
+struct WalkLive {
+    const long long *stream_id;
+    const int *parity;
+    const long long *seen_;
+    DenoiseLive lv;
+    LiveChunk k, kn;          // of the block, of the next block
+    static __device__ __forceinline__ int opaque(int lane) { asm volatile("" : "+v"(lane)); return lane; }
+    __device__ __forceinline__ size_t copy(int p) const { return (size_t)p * lv.n_streams + k.s; }
+    __device__ __forceinline__ void seek(long c) { k = kn = live_chunk(stream_id, parity, seen_, c); }
+    __device__ __forceinline__ void seek_next(long c) { kn = live_chunk(stream_id, parity, seen_, c); }
+    __device__ __forceinline__ void step() { k = kn; }
+    __device__ __forceinline__ long seen() const { return k.N; }
+    __device__ __forceinline__ int enter(unsigned int (&raw)[8], float2 (&tail)[4], int lane) const   // (zeros when fresh)
+    {
+        const int sl = opaque(lane);
+        unsigned int hp[4];
+        load_pairs(lv.prev + copy(k.p) * 1024 + 512, sl, hp);
+#pragma unroll
+        for (int r = 0; r < 4; r++) raw[r] = hp[r];
+        const float2 *tl = reinterpret_cast<const float2 *>(lv.tail + copy(k.p) * 512) + sl;
+#pragma unroll
+        for (int d = 0; d < 4; d++) tail[d] = tl[64 * d];
+        return __builtin_amdgcn_readfirstlane(lv.listed[copy(k.p)]);
+    }
+    __device__ __forceinline__ void keep_blocks(const unsigned int (&raw)[8], int lane) const
+    {
+        unsigned int *pv = reinterpret_cast<unsigned int *>(lv.prev + copy(k.p ^ 1) * 1024) + opaque(lane);
+#pragma unroll
+        for (int r = 0; r < 8; r++) pv[64 * r] = raw[r];
+    }
+    __device__ __forceinline__ void keep_tail(const float2 (&tail)[4], int listed, int lane) const
+    {
+        float2 *tl = reinterpret_cast<float2 *>(lv.tail + copy(k.p ^ 1) * 512) + opaque(lane);
+#pragma unroll
+        for (int d = 0; d < 4; d++) tl[64 * d] = tail[d];
+        if (lane == 0) lv.listed[copy(k.p ^ 1)] = listed;
+    }
+    __device__ __forceinline__ bool lists(long) const { return true; }
+    // packed from the span's start: the first two blocks of a stream emit nothing (SS:260-263)
+    __device__ __forceinline__ long emit_at(long base, long j) const { return base + (j - (k.N < 2 ? 2 - k.N : 0)) * 512; }
+};
+
+// denoise_run_kernel over the concatenated block axis.  Wave w owns the global blocks [w run, (w + 1) run); global
+// block j of chunk u (block_first[u] <= j < block_first[u + 1]) has the stream index i = N + (j - block_first[u]) and
+// its samples at base + 512 j.  Stream block 0 only stashes its samples (SS:211-216), so the overlap restarts from zero
+// by itself where a stream begins; the frame of block i >= 1 is [block i - 1, block i], and with the overlap it gives
+// the enhanced samples at the time of block i - 1, emitted when i >= 2 (SS:260-263: the first two calls emit nothing).
+// So an utterance's first and last blocks are never written.  The halo frame in front of the wave's first block goes
+// through the SAME loop body as every other frame (emission off), never into the chunk before: one inlined copy of
+// the arithmetic, so the samples do not depend on where the waves are cut.
+template <int MODE, class Carry>
+__device__ __forceinline__ void denoise_chunk_walk(const short *__restrict__ pcm, const long long *__restrict__ sample_first,
+                                                   const long long *__restrict__ block_first, long n_chunks, long n_blocks,
+                                                   const int *__restrict__ row_idx, const float *__restrict__ rows,
+                                                   const float2 *__restrict__ table, short *__restrict__ out,
+                                                   float *__restrict__ precast, int run, int *__restrict__ redo, Carry cy)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
@@ -1978,10 +1924,10 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel
     long u = ragged_find_utt(block_first, n_chunks, j0);
     long ub = uniform_i64(block_first + u), ue = uniform_i64(block_first + u + 1);
     long base = uniform_i64(sample_first + u) - ub * 512;      // global block j of this chunk starts at base + 512 j
-    LiveChunk k = live_chunk(stream_id, parity, seen, u);
+    cy.seek(u);
     // stream index 0 or 1: the overlap entering block j0 is empty; the chunk's first block: it is the carried tail;
     // else the frame of block j0 - 1 rebuilds it
-    const long js = (j0 > ub && k.N + (j0 - ub) >= 2) ? j0 - 1 : j0;
+    const long js = (j0 > ub && cy.seen() + (j0 - ub) >= 2) ? j0 - 1 : j0;
 
     FrameTables t;
     load_frame_tables(t, table, lane);
@@ -1992,7 +1938,8 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel
     float2 tail[4], y[8];
 #pragma unroll
     for (int d = 0; d < 4; d++) tail[d] = make_float2(0.f, 0.f);
-    // the block in front of js (at the chunk's first block it comes from the state, inside the loop)
+    // the block in front of js, clamped into the chunk (unused where it is clamped: stream block 0 has no frame, and at
+    // a continued chunk's first block cy.enter() brings it)
     load_pairs(pcm + base + (js > ub ? js - 1 : ub) * 512, lane, nxt);
 #pragma unroll
     for (int r = 0; r < 4; r++) raw[r + 4] = nxt[r];
@@ -2005,44 +1952,24 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel
 #pragma unroll
         for (int r = 0; r < 4; r++) { raw[r] = raw[r + 4]; raw[r + 4] = tk[r]; }
         const int idx = next_idx;
-        int listed_in = 0;
-        if (j == ub) {
-            // the chunk's first block: the stream's last block and its overlap come from the state (zeros when fresh)
-            const size_t at = (size_t)k.p * lv.n_streams + k.s;
-            int sl = lane;
-            asm volatile("" : "+v"(sl));                         // per chunk: no lane offsets of the state kept across the run
-            unsigned int hp[4];
-            load_pairs(lv.prev + at * 1024 + 512, sl, hp);
-#pragma unroll
-            for (int r = 0; r < 4; r++) raw[r] = hp[r];
-            const float2 *tl = reinterpret_cast<const float2 *>(lv.tail + at * 512) + sl;
-#pragma unroll
-            for (int d = 0; d < 4; d++) tail[d] = tl[64 * d];
-            listed_in = MODE == 0 ? __builtin_amdgcn_readfirstlane(lv.listed[at]) : 0;
-        }
-        if (j + 1 == ue && j >= j0) {
-            // the chunk's last block, in the wave that owns it: with the block before, the stream's last two blocks (here,
-            // not beside the tail below: the first of them is not kept across the frame)
-            int sl = lane;
-            asm volatile("" : "+v"(sl));
-            unsigned int *pv = reinterpret_cast<unsigned int *>(lv.prev + ((size_t)(k.p ^ 1) * lv.n_streams + k.s) * 1024) + sl;
-#pragma unroll
-            for (int r = 0; r < 8; r++) pv[64 * r] = raw[r];
-        }
+        const bool last_owned = j + 1 == ue && j >= j0;         // the chunk's last block, in the wave that owns it
+        int listed_in = 0, listed = 0;
+        if (j == ub) listed_in = cy.enter(raw, tail, lane);
+        if (last_owned) cy.keep_blocks(raw, lane);
+        // the next block, needed one iteration from now (denoise_run_kernel); after a chunk's last block it is the
+        // first block of the next non-empty one
         long un = u, ubn = ub, uen = ue, basen = base;
-        LiveChunk kn = k;
         if (j + 1 < j1) {
             if (j + 1 == ue) {
                 ubn = ue;
                 ragged_next_utt(block_first, n_chunks, un, uen);
                 basen = uniform_i64(sample_first + un) - ubn * 512;
-                kn = live_chunk(stream_id, parity, seen, un);
+                cy.seek_next(un);
             }
             next_idx = row_idx[j + 1];
             load_pairs(pcm + basen + (j + 1) * 512, lane, nxt);
         }
-        const long i = k.N + (j - ub);                           // the block's index in its stream
-        int listed = 0;
+        const long i = cy.seen() + (j - ub);                     // the block's index in its stream
         if (i == 0) {
             // the first call of a stream only stashes its block (SS:211-216): no output, empty overlap
 #pragma unroll
@@ -2050,11 +1977,11 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel
         } else {
             if (idx != cur_row) {                                // wave-uniform: another estimate is in force
                 cur_row = idx;
-                load_noise_pair_regs<MODE>(nz, lv.rows + (size_t)idx * 1024, lane);
+                load_noise_pair_regs<MODE>(nz, rows + (size_t)idx * 1024, lane);
             }
             denoise_frame_pairs<MODE>(raw, t, sw, table, lds, lane, nz, y, ps);
-            // a frame FP32 cannot hold (phase_unsafe): again, in FP64
-            if (MODE == 0 && j >= j0 && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) {
+            // a frame FP32 cannot hold (phase_unsafe): again, in FP64, if one of its two blocks is emitted
+            if (MODE == 0 && j >= j0 && cy.lists(ue - ub) && phase_unsafe<1024>(ps.e, ps.err, sumsq(y))) {
                 phase_redo(redo, j, lane);
                 listed = 1;
             }
@@ -2073,7 +2000,7 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel
         next_idx = __builtin_amdgcn_readfirstlane(next_idx);
         __builtin_amdgcn_sched_barrier(0);
         if (j >= j0 && i >= 2) {
-            const long at = base + (j - (k.N < 2 ? 2 - k.N : 0)) * 512;      // packed from the span's start
+            const long at = cy.emit_at(base, j);
             if (out) {
                 unsigned int *dst = reinterpret_cast<unsigned int *>(out + at) + lane;
 #pragma unroll
@@ -2084,18 +2011,39 @@ __global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel
                 for (int d = 0; d < 4; d++) *reinterpret_cast<float2 *>(precast + at + 2 * lane + 128 * d) = o[d];
             }
         }
-        if (j + 1 == ue && j >= j0) {
-            // the chunk's last block, in the wave that owns it: the stream's other copy takes what the next call starts from
-            const size_t at = (size_t)(k.p ^ 1) * lv.n_streams + k.s;
-            int sl = lane;
-            asm volatile("" : "+v"(sl));
-            float2 *tl = reinterpret_cast<float2 *>(lv.tail + at * 512) + sl;
-#pragma unroll
-            for (int d = 0; d < 4; d++) tl[64 * d] = tail[d];
-            if (lane == 0) lv.listed[at] = listed;
-        }
-        u = un; ub = ubn; ue = uen; base = basen; k = kn;
+        if (last_owned) cy.keep_tail(tail, listed, lane);
+        u = un; ub = ubn; ue = uen; base = basen; cy.step();
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_batch_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
+    long n_utts, long n_blocks, const int *__restrict__ row_idx, const float *__restrict__ noise_rows,
+    const float2 *__restrict__ table, short *__restrict__ out, float *__restrict__ precast, int run, int *__restrict__ redo)
+{
+    denoise_chunk_walk<MODE>(pcm, sample_first, block_first, n_utts, n_blocks, row_idx, noise_rows, table, out, precast, run,
+                             redo, WalkBatch{});
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64, JDSP_DENOISE_RESIDENT) void denoise_live_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ stream_id, const long long *__restrict__ sample_first,
+    const long long *__restrict__ block_first, const int *__restrict__ parity, const long long *__restrict__ seen,
+    long n_chunks, long n_blocks, const int *__restrict__ row_idx, const float2 *__restrict__ table,
+    short *__restrict__ out, float *__restrict__ precast, int run, int *__restrict__ redo, DenoiseLive lv)
+{
+    denoise_chunk_walk<MODE>(pcm, sample_first, block_first, n_chunks, n_blocks, row_idx, lv.rows, table, out, precast, run,
+                             redo, WalkLive{stream_id, parity, seen, lv, {}, {}});
+}
+
+__global__ __launch_bounds__(256) void denoise_redo_f64_batch_kernel(
+    const short *__restrict__ pcm, const long long *__restrict__ sample_first, const long long *__restrict__ block_first,
+    long n_utts, const int *__restrict__ row_idx, const float *__restrict__ noise_rows, short *__restrict__ out,
+    float *__restrict__ precast, const int *__restrict__ redo, int mode)
+{
+    redo_f64_run<1024>(redo, mode, RedoBatch{pcm, sample_first, block_first, n_utts, row_idx, noise_rows, out, precast,
+                                             0, 0, 0, 0});
 }
 
 // A listed entry e >= 0 is the global frame e, as in the batch; e < 0 is the frame in front of the chunk whose first
@@ -2204,6 +2152,41 @@ __global__ __launch_bounds__(256) void denoise_live_reset_kernel(const long long
     }
 }
 
+// What both launchers below work out behind the noise pass: the blocks per wave (run_opt, or 0 = one round of resident
+// waves, resident_run), the run kernel's grid (its waves rounded up to eight) and the FP64 pass's grid over a list
+// of n_list entries at most.
+struct ChunkLaunch { int run; dim3 grid, redo_grid; };
+static ChunkLaunch chunk_launch(int run_opt, int n_cu, long n_blocks, long n_list)
+{
+    const long run = run_opt > 0 ? run_opt : resident_run(n_cu, n_blocks);
+    return {(int)run, dim3((unsigned)(((n_blocks + run - 1) / run + 7) / 8 * 8)),
+            dim3((unsigned)(n_list < kRedoGrid ? n_list : kRedoGrid))};
+}
+
+// flags / row_idx [n_blocks], rows [n_blocks / 10 + 1][1024] with row 0 zero, redo [n_blocks + 1]: the handle's batch
+// workspace.  out and precast may be NULL (both: the run kernel is not launched); noise_last may be NULL.
+int launch_denoise_batch(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *sample_first,
+                         const long long *block_first, long n_utts, long n_blocks, const double *w_hi,
+                         const float2 *table, unsigned char *flags, int *row_idx, float *rows, int *redo, short *out,
+                         float *precast, float *noise_last, int vad_only)
+{
+    if (n_blocks <= 0 || n_utts <= 0) return 0;
+    hipLaunchKernelGGL(vad_flags_batch_kernel, dim3((unsigned)((n_blocks + kVadBlocksPerWave - 1) / kVadBlocksPerWave)),
+                       dim3(64), 0, s, pcm, sample_first, block_first, n_utts, n_blocks, w_hi, flags);
+    if (vad_only) return hipGetLastError() == hipSuccess ? 0 : -1;
+    hipLaunchKernelGGL(noise_batch_kernel, dim3((unsigned)n_utts), dim3(64), 0, s, pcm, sample_first, block_first, flags,
+                       table, rows, row_idx, noise_last);
+    if (!out && !precast) return hipGetLastError() == hipSuccess ? 0 : -1;
+    if (mode == 0 && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
+    const ChunkLaunch g = chunk_launch(run_opt, n_cu, n_blocks, n_blocks);
+    hipLaunchKernelGGL(mode == 0 ? denoise_batch_kernel<0> : denoise_batch_kernel<1>, g.grid, dim3(64), 0, s, pcm,
+                       sample_first, block_first, n_utts, n_blocks, row_idx, rows, table, out, precast, g.run, redo);
+    if (mode == 0)
+        hipLaunchKernelGGL(denoise_redo_f64_batch_kernel, g.redo_grid, dim3(256), 0, s, pcm, sample_first, block_first,
+                           n_utts, row_idx, rows, out, precast, redo, mode);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_denoise_live(hipStream_t s, int mode, int run_opt, int n_cu, const short *pcm, const long long *stream_id,
                         const long long *sample_first, const long long *block_first, long n_chunks, long n_blocks,
                         const double *w_hi, const float2 *table, unsigned char *flags, int *row_idx, int *redo,
@@ -2216,27 +2199,19 @@ int launch_denoise_live(hipStream_t s, int mode, int run_opt, int n_cu, const sh
     hipLaunchKernelGGL(noise_live_kernel, dim3((unsigned)n_chunks), dim3(64), 0, s, pcm, stream_id, sample_first,
                        block_first, flags, table, row_idx, lv);
     if (mode == 0 && hipMemsetAsync(redo, 0, sizeof(int), s) != hipSuccess) return -1;
-    const long run = run_opt > 0 ? run_opt : resident_run(n_cu, n_blocks);
-    const long grid = ((n_blocks + run - 1) / run + 7) / 8 * 8;
-    if (mode == 0)
-        hipLaunchKernelGGL(denoise_live_kernel<0>, dim3((unsigned)grid), dim3(64), 0, s, pcm, stream_id, sample_first,
-                           block_first, lv.parity, lv.seen, n_chunks, n_blocks, row_idx, table, out, precast, (int)run, redo,
-                           lv);
-    else
-        hipLaunchKernelGGL(denoise_live_kernel<1>, dim3((unsigned)grid), dim3(64), 0, s, pcm, stream_id, sample_first,
-                           block_first, lv.parity, lv.seen, n_chunks, n_blocks, row_idx, table, out, precast, (int)run, redo,
-                           lv);
-    if (mode == 0 && (out || precast)) {
-        const long n_list = n_blocks + n_chunks;
-        hipLaunchKernelGGL(denoise_redo_f64_live_kernel, dim3((unsigned)(n_list < kRedoGrid ? n_list : kRedoGrid)), dim3(256),
-                           0, s, pcm, stream_id, sample_first, block_first, n_chunks, row_idx, lv, out, precast, redo, mode);
-    }
+    const ChunkLaunch g = chunk_launch(run_opt, n_cu, n_blocks, n_blocks + n_chunks);
+    hipLaunchKernelGGL(mode == 0 ? denoise_live_kernel<0> : denoise_live_kernel<1>, g.grid, dim3(64), 0, s, pcm, stream_id,
+                       sample_first, block_first, lv.parity, lv.seen, n_chunks, n_blocks, row_idx, table, out, precast,
+                       g.run, redo, lv);
+    if (mode == 0 && (out || precast))
+        hipLaunchKernelGGL(denoise_redo_f64_live_kernel, g.redo_grid, dim3(256), 0, s, pcm, stream_id, sample_first,
+                           block_first, n_chunks, row_idx, lv, out, precast, redo, mode);
     hipLaunchKernelGGL(denoise_live_commit_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, s, stream_id,
                        block_first, n_chunks, lv.latched, parity, est_parity, seen, n_emitted);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_denoise_live_reset(hipStream_t s, const long long *stream_id, long n_ids, const DenoiseLive &lv, int *parity,
+int launch_denoise_live_reset(hipStream_t s,const long long *stream_id, long n_ids, const DenoiseLive &lv, int *parity,
                               int *est_parity, long long *seen)
 {
     if (n_ids <= 0) return 0;

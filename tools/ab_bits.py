@@ -259,14 +259,84 @@ def denoise(eng):
         d.close()
         assert sum(n_redo) > 0
         yield "denoise %s in two calls (%d recomputed)" % (c["name"], sum(n_redo)), digest(*outs, np.array(n_redo))
-    c = periodic(1024)
+    yield from denoise_batches(eng)
+    yield from denoise_streams(eng)
+
+
+BPW = (0, 1, 4)          # the denoiser's blocks_per_wave: one round of resident waves, a wave per block, four blocks
+
+
+def speechlike_pcm():
+    """130 blocks of voice and pauses: one of the white streams of the denoise tests"""
+    import denoise_fp32_ref as R
+    return R.white_pcm(next(w for w in R.WHITE_STREAMS if w[:3] == (512, 9, 130)))
+
+
+def denoise_batches(eng):
+    """process_batch in both modes: utterances cut from the periodic stream (frames go to the FP64 pass) and from a
+    speech-like one (utterances of 0, 1, 2 and 3 blocks, one over the 64 blocks a wave ballots at a time)"""
+    import numpy as np
+    c, sp = periodic(1024), speechlike_pcm()
     nb = c["pcm"].size // 512
-    counts = [nb, nb - 7, nb // 2 + 3]
-    pcm = np.concatenate([c["pcm"][:k * 512] for k in counts])
-    d = eng.denoiser(0, 1024, 512)
-    outs = d.process_batch(pcm, counts, want_precast=True)
-    d.close()
-    yield "denoise_batch %s x 3 utterances" % c["name"], digest(*outs)
+    cuts = 512 * np.cumsum([0, 70, 0, 1, 2, 3, 12])
+    batches = ((c["name"], [c["pcm"][:k * 512] for k in (nb, nb - 7, nb // 2 + 3)]),
+               ("speechlike", [sp[a:b] for a, b in zip(cuts[:-1], cuts[1:])]))
+    for mode in (0, 1):
+        for name, utts in batches:
+            counts = [u.size // 512 for u in utts]
+            d = eng.denoiser(mode, 1024, 512)
+            for bpw in BPW:
+                d.set_option("blocks_per_wave", bpw)
+                outs = d.process_batch(np.concatenate(utts), counts, want_precast=True, want_flags=True, want_noise=True)
+                n_redo = d.frames_recomputed()
+                assert mode or name == "speechlike" or n_redo > 0
+                yield ("denoise_batch mode %d %s x %d utterances bpw %d (%d recomputed)" % (mode, name, len(utts), bpw, n_redo),
+                       digest(*outs, np.array(n_redo)))
+            d.close()
+
+
+def denoise_stream_calls():
+    """(stream, blocks) chunks over five live streams: ids in no order, a stream or two absent from every call, chunks
+    of 0, 1, 2, 3, 12 and 70 blocks (70: over the 64 blocks a wave ballots at a time); then stream 0 a block per call
+    through its periodic stretch, where every frame is the first and the last of its chunk"""
+    return [[(3, 2), (0, 12), (4, 0), (1, 1)],
+            [(2, 70), (0, 3), (3, 1), (1, 2)],
+            [(4, 12), (1, 70), (0, 1), (2, 0), (3, 3)],
+            [(0, 2), (2, 12), (4, 3)]] + [[(0, 1)]] * 10
+
+
+def denoise_streams(eng):
+    """process_streams in both modes at every blocks_per_wave.  Streams 0..3 read the periodic stream, repeated, from
+    the blocks 0, 5, 0 and 13 on; stream 4 the speech-like one.  Handed over: list entries of the live calls beyond
+    those of process_batch over each stream's whole history, i.e. frames whose second block came with the next call."""
+    import numpy as np
+    N_LIVE, calls = 5, denoise_stream_calls()
+    c = periodic(1024)
+    tiled = np.tile(c["pcm"], 3)
+    src = [tiled[512 * at:] for at in (0, 5, 0, 13)] + [speechlike_pcm()]
+    total = [sum(n for call in calls for s, n in call if s == k) for k in range(N_LIVE)]
+    assert all(3 <= t <= x.size // 512 for t, x in zip(total, src))
+    for mode in (0, 1):
+        d = eng.denoiser(mode, 1024, 512)
+        d.process_batch(np.concatenate([x[:512 * t] for x, t in zip(src, total)]), total)
+        n_batch = d.frames_recomputed()
+        for bpw in BPW:
+            d.set_option("blocks_per_wave", bpw)
+            d.open_streams(N_LIVE, 160)                          # every stream fresh again
+            done, outs, n_redo = [0] * N_LIVE, [], []
+            for call in calls:
+                pcm = np.concatenate([src[s][512 * done[s]:512 * (done[s] + n)] for s, n in call])
+                for s, n in call:
+                    done[s] += n
+                outs += list(d.process_streams(pcm, [s for s, _ in call], [n for _, n in call], want_precast=True,
+                                               want_flags=True))
+                n_redo.append(d.frames_recomputed())
+            outs += list(d.streams_state(np.arange(N_LIVE)))
+            handed = sum(n_redo) - n_batch
+            assert mode or (n_batch > 0 and handed > 0), (n_batch, n_redo)
+            yield ("denoise_streams mode %d bpw %d (%d recomputed, %d handed over)" % (mode, bpw, sum(n_redo), handed),
+                   digest(*outs, np.array(n_redo)))
+        d.close()
 
 
 def child():
