@@ -20,7 +20,7 @@
  *     handle's HIP stream: no allocation and no synchronisation once the
  *     handle is warm, i.e. after one call of that entry point (constant tables
  *     are built on first use) and after the matching *_reserve() where the
- *     entry has a workspace (jdsp_denoise_reserve, jdsp_denoise_batch_reserve,
+ *     entry has a workspace (jdsp_denoise_reserve, jdsp_denoise_batch_reserve, jdsp_mvdrn_batch_reserve,
  *     jdsp_hmm_reserve, jdsp_fastconv_reserve, jdsp_*_streams_reserve).
  *     The plain entry points take HOST pointers, copy in, run, copy out and
  *     synchronise.
@@ -34,7 +34,7 @@
  *       (sample_first, frame_first, block_first, utt_first, frame_start, stream_id).  A replay may therefore deal the same
  *       n_frames_total among the same n_utts / n_chunks differently, move the spans, and name other streams.
  *       Class S, stateless: jdsp_stft_i16_dev, jdsp_stft_half_i16_dev, jdsp_stft_i16_f64_dev, jdsp_stft_half_batch_dev,
- *         jdsp_istft_batch_dev, jdsp_stftmask_batch_dev, jdsp_denoise_batch_dev, jdsp_mfcc_frames_dev,
+ *         jdsp_istft_batch_dev, jdsp_stftmask_batch_dev, jdsp_denoise_batch_dev, jdsp_mvdrn_batch_dev, jdsp_mfcc_frames_dev,
  *         jdsp_pitch_autocorr_dev, jdsp_pitch_lag_dev, jdsp_lpc_dev, jdsp_gmm_score_dev, jdsp_hmm_viterbi_dev,
  *         jdsp_fft_process_f64_dev.  Every replay recomputes from what the buffers hold at that time and equals an
  *         eager call on the same contents, bit for bit.  Replay as often as wanted.
@@ -78,7 +78,7 @@ extern "C" {
  *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added;
  *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
  *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added;
- *    live binaural rendering jdsp_binaural_* added
+ *    live binaural rendering jdsp_binaural_* added; the batched n-microphone MVDR entries jdsp_mvdrn_batch* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -928,6 +928,61 @@ int jdsp_mvdrn_process_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stri
                            float *precast_dev, long *n_out_blocks);
 int jdsp_mvdrn_process(jdsp_mvdrn *h, const int16_t *pcm_host, long chan_stride, long n_blocks, int16_t *out_host,
                        float *precast_host, long *n_out_blocks);
+
+/* Batched n-microphone MVDR: n_utts INDEPENDENT utterances in one launch sequence, each a fresh stream with the
+ * handle's n_mics, delays_s and loading.  The entries neither read nor write the handle's own stream state (covariance,
+ * previous block, run length, call count), so they may be interleaved with _process on the same handle.  1024-point
+ * handles only: on an n_fft = 512 handle the three entries return JDSP_EINVAL with a text (two blocks share one inverse
+ * transform there, and the pairing across utterance boundaries is not built).  The layout is jdsp_denoise_batch_dev's,
+ * on n_mics planes; what is not restated here is as there.
+ *   - Utterance u has B_u = block_first[u + 1] - block_first[u] blocks (>= 0) of 512 samples; its block b of
+ *     microphone m is pcm[m chan_stride + sample_first[u] + 512 b .. + 512): the same offsets on every plane.  pcm is
+ *     16-byte aligned and chan_stride a multiple of 8, as in jdsp_mvdrn_process_dev; sample_first[u] is only even.
+ *   - Its result is what a fresh handle gives for _process of its B_u blocks: max(B_u - 1, 0) emitted blocks.  The
+ *     emission for input block b >= 1 (the frame [first 511 samples of block b - 1 | block b | 0], silence in front of
+ *     block 0) is written TIME-ALIGNED, at out[sample_first[u] + 512 b .. + 512); precast (the same samples before the
+ *     (short) cast) likewise.  out and precast are single planes.  The first block of each span is never written, and the
+ *     device entry touches no sample outside the spans.  Where the fresh handle's samples are non-finite -- before the
+ *     utterance's first estimation frame, and with loading == 0 before n_mics of them -- so are these: the non-finite
+ *     value in precast, 0 in out.
+ *   - flags [n_blocks_total] uint8: the VAD decision of every block on microphone 0, in concatenated block order.  Any
+ *     of the three output pointers may be NULL.
+ *   - An utterance's out, precast and flags do not depend, bit for bit, on where it stands in the batch, on its
+ *     neighbours, on gaps between the spans, on chan_stride, or on how the batch is split into calls: its estimation
+ *     frames are cut into chunks of 128 for the covariance update, a cut that depends on nothing but their number.
+ *     Against the oracle they are held to _process's bars; against _process of a fresh handle on the utterance alone
+ *     they agree to those bars, and bit equality is NOT promised (_process cuts by the call's count of estimation
+ *     frames).  Measured: for utterances of at most 128 estimation frames both cuts add one frame at a time from
+ *     zero, and the bits were equal in every case tried -- 8 utterances on 8 microphones, and on 3 microphones 127 and
+ *     128 frames as well as 129, 256 and 257, where the cuts differ (tests/test_mvdrn_batch_gpu.py prints it).
+ *   - jdsp_mvdrn_batch_dev only enqueues on the context's stream: no allocation, no host synchronisation, no host
+ *     read of the two offset arrays (int64, [n_utts] and [n_utts + 1], 8-byte aligned) -- hence n_blocks_total, which
+ *     must equal block_first[n_utts].  It is graph-capturable, class S (Conventions): n_utts, n_blocks_total,
+ *     chan_stride and the pointers are baked, the two offset arrays and the PCM are read at every replay, and a replay
+ *     equals an eager call on the same contents bit for bit, as often as it is replayed.  The device-side offsets are
+ *     the caller's contract: block_first[0] = 0 and non-decreasing; every sample_first[u] even, >= 0 and ascending; the
+ *     spans, 512 B_u long, disjoint and inside every plane and the outputs.  No PCM outside the spans is read.  out and
+ *     precast 4-byte aligned.
+ *   - Its workspace comes from jdsp_mvdrn_batch_reserve, the only call that allocates (and synchronises), kept apart
+ *     from _process's.  In the worst case every block is an estimation frame, so per reserved block it holds, as
+ *     _process's does, one spectrum set and one weight set, (n_mics + 8) x 513 x 8 bytes (65.7 KB at 8 microphones);
+ *     on top 8.2 KB of chunk sums (2 max_blocks_total / 128 + 2 slots of 513 x 64 x 16 bytes, used only by utterances of
+ *     more than 128 estimation frames) and 9 bytes of flag, weight-row index and event list: 73.9 KB per block at 8
+ *     microphones, 5.9 GB per 80,000 blocks; 8 bytes per reserved utterance.  A _dev call with more blocks or
+ *     utterances than reserved is JDSP_EINVAL with a text.  A corpus larger than memory is split into calls by whole
+ *     utterances; by the independence above the bits are the same.  A workspace below the worst case is not built.
+ *   - jdsp_mvdrn_batch (host pointers, synchronous) reserves on demand, checks the offsets as jdsp_denoise_batch does
+ *     and returns JDSP_EINVAL with a jdsp_last_error text otherwise.  pcm is n_mics planes chan_stride >= n_samples
+ *     apart; out and precast are n_samples long and ZERO wherever the device entry would not write.
+ *   - n_utts == 0, batches of empty utterances and all three outputs NULL succeed and launch nothing.  n_utts < 0 and
+ *     misaligned base pointers are JDSP_EINVAL. */
+int jdsp_mvdrn_batch_reserve(jdsp_mvdrn *h, long max_blocks_total, long max_utts);
+int jdsp_mvdrn_batch_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stride, const int64_t *sample_first_dev,
+                         const int64_t *block_first_dev, long n_utts, long n_blocks_total,
+                         int16_t *out_dev, float *precast_dev, uint8_t *flags_dev);
+int jdsp_mvdrn_batch(jdsp_mvdrn *h, const int16_t *pcm_host, long chan_stride, long n_samples,
+                     const int64_t *sample_first_host, const int64_t *block_first_host, long n_utts,
+                     int16_t *out_host, float *precast_host, uint8_t *flags_host);      /* host path, synchronous */
 
 /* ---- MFCC ---------------------------------------------------------------------- */
 /* MFCCFeatureExtraction_auto_version1.cpp.  The #defines at :23-33 become a runtime

@@ -175,6 +175,9 @@ def _load():
         "jdsp_mvdrn_blocks_out": (l, [vp, l]),
         "jdsp_mvdrn_process_dev": (i, [vp, vp, l, l, vp, vp, C.POINTER(l)]),
         "jdsp_mvdrn_process": (i, [vp, vp, l, l, vp, vp, C.POINTER(l)]),
+        "jdsp_mvdrn_batch_reserve": (i, [vp, l, l]),
+        "jdsp_mvdrn_batch_dev": (i, [vp, vp, l, vp, vp, l, l, vp, vp, vp]),
+        "jdsp_mvdrn_batch": (i, [vp, vp, l, l, vp, vp, l, vp, vp, vp]),
         "jdsp_stft_half_i16_dev": (i, [vp, vp, l, vp, l]),
         "jdsp_stft_i16_dev": (i, [vp, vp, l, i, i, vp]),
         "jdsp_stft_half_batch_dev": (i, [vp, vp, vp, vp, l, l, i, vp, l]),

@@ -140,6 +140,7 @@ struct DenoiseGeom {
 // BeamForming_MVDR_ver1.cpp's state between calls (device memory)
 constexpr int kMvdrTableVersions = 8192;     // 2-microphone MVDR: calls with fewer events than this get their weights from a table (16 KB per version)
 constexpr int kMvnChunks = 128;            // chunks the n-microphone covariance update cuts a call's events into
+constexpr int kMvnBatchEvents = 128;       // ... and the events per chunk of an utterance of a batch (mvdrn_batch_kernels.hip)
 
 struct MvdrState {
     int run_len;          // main(): iNumOfIteration             MVDR:59,99,108
@@ -500,6 +501,26 @@ int launch_mvdrn512(hipStream_t s, const short *pcm, long chan_stride, int n_mic
                     const short *prev_in, short *prev_out, const int *events, const DenoisePlan *plan, const int *ver_base,
                     const unsigned long long *snap_mask, float2 *spec, const double2 *cov_in, double2 *cov_out,
                     const double2 *steer, double loading, float2 *weights, const float2 *table, short *out, float *precast, double2 *chunk_ws, int chunk_cap);
+// mvdrn_batch_kernels.hip
+// The workspace of a batch of ragged utterances as the launcher sees it (jdsp_mvdrn::BatchWs owns it), for up to n
+// blocks in up to U utterances; P = kMvnBatchEvents.
+struct MvnBatchView {
+    unsigned char *code;   // [n] voice | first block of its utterance << 1
+    int *evpre;            // [n] estimation frames at or before each block of the concatenated axis: its weight row
+    int *events;           // [n] the block of every estimation frame
+    int *tile_off;         // [n / 2048 + 2] the prefix sum's tile offsets
+    int *ev_first;         // [U + 1] the first estimation frame of every utterance
+    int *slot_utt;         // [U + n / P + 2] the utterance of every chunk slot
+    float2 *spec;          // [n][n_mics][513]
+    float2 *weights;       // [n + 1][8][513]; row 0: no estimation frame yet
+    double2 *chunk;        // [2 n / P + 2][513][64] chunk sums, then entering matrices, of utterances of more than P events
+};
+// every utterance a fresh 1024-point stream; flags, out and precast may each be NULL (out and precast both NULL: the
+// VAD alone runs).  Enqueues only: no allocation, no synchronisation, no host read of the offsets.
+int launch_mvdrn_batch(hipStream_t s, const short *pcm, long chan_stride, int n_mics, const long long *sample_first,
+                       const long long *block_first, long n_utts, long n_blocks, const double *w_vad, const double2 *steer,
+                       double loading, const float2 *table, const MvnBatchView &ws, unsigned char *flags, short *out,
+                       float *precast);
 // pitch_kernels.hip
 int launch_pitch(hipStream_t s, const short *pcm, long n_blocks, const short *prev_block, const float2 *table, int *arg,
                  float *rmax, float *autocorr);
@@ -792,4 +813,13 @@ struct jdsp_mvdrn {
         jdsp::DevBuf<double2> chunk_ws;   // [2][chunk_cap][n_bins][64]: per-chunk covariance sums and entering matrices
         int chunk_cap = 0;
     } ws;
+    // sized by jdsp_mvdrn_batch_reserve for batches of up to cap_blocks blocks in up to cap_utts utterances
+    // (jdsp::MvnBatchView has the shapes); nothing here is read or written by the handle's own stream
+    struct BatchWs {
+        jdsp::DevBuf<unsigned char> code;
+        jdsp::DevBuf<int> evpre, events, tile_off, ev_first, slot_utt;
+        jdsp::DevBuf<float2> spec, weights;
+        jdsp::DevBuf<double2> chunk;
+        long cap_blocks = -1, cap_utts = -1;
+    } bws;
 };

@@ -1185,6 +1185,63 @@ class MvdrMulti(_Child):
                                           pre.ctypes.data_as(C.c_void_p) if want_precast else None, None))
         return (out[:n_out * B], pre[:n_out * B]) if want_precast else out[:n_out * B]
 
+    def reserve_batch(self, max_blocks_total, max_utts):
+        """Sizes the workspace of process_batch's device path (jdsp_mvdrn_batch_reserve): the only call of the batch
+        entries that allocates.  Call it before capturing process_batch in a graph."""
+        self.eng._ck(L.jdsp_mvdrn_batch_reserve(self._h, int(max_blocks_total), int(max_utts)))
+
+    def process_batch(self, pcm, block_counts, utt_sample_first=None, want_precast=False, want_flags=False, out=None):
+        """A batch of independent utterances in one launch sequence (jdsp_mvdrn_batch): each comes out as a fresh
+        handle's process of its blocks, and the handle's own stream is neither read nor advanced.  1024-point handles.
+        pcm: int16 [n_mics, n_samples]; block_counts: B_u >= 0 blocks of 512 samples per utterance (a host sequence);
+        utt_sample_first: the n_utts even sample offsets of the spans, the same on every plane, ascending and disjoint
+        (None: packed back to back, sharding.denoise_batch_layout).  torch CUDA (the device entry on torch's current
+        stream; rows may be strided by a multiple of 8 samples; it reserves on demand, so call reserve_batch first
+        under graph capture) or numpy (the host entry).  Returns int16 [n_samples], TIME-ALIGNED with pcm: the
+        beamformed samples of utterance u's blocks 1 .. B_u - 1 lie where those blocks lie in pcm; everything else is
+        zero, or is left as it was in `out` when given on the device path.  With want_precast / want_flags a tuple
+        follows the same order: float32 samples before the cast, uint8 VAD decisions of microphone 0 [sum B_u] in
+        concatenated block order."""
+        from .sharding import denoise_batch_layout
+        counts = np.ascontiguousarray(block_counts, np.int64).reshape(-1)
+        packed, block_first, n_packed = denoise_batch_layout(counts, self.block)
+        if utt_sample_first is None:
+            sample_first = packed
+        else:
+            sample_first = np.ascontiguousarray(utt_sample_first, np.int64).reshape(-1)[:counts.size]
+            assert sample_first.size == counts.size
+        assert pcm.ndim == 2 and pcm.shape[0] == self.n_mics
+        n_utts, n_total, n_samples = counts.size, int(block_first[-1]), int(pcm.shape[1])
+        dev = pcm.device if _is_torch(pcm) else None
+        if dev is not None:
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.stride(1) == 1
+            stride = int(pcm.stride(0))
+            assert n_utts == 0 or int((sample_first + counts * self.block).max()) <= n_samples
+            key = (sample_first.tobytes(), counts.tobytes())
+            d_sample, d_block, fresh = _batch_offsets(self, key, sample_first, block_first, dev)
+            if fresh:
+                self.reserve_batch(n_total, n_utts)             # a no-op once sized
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            stride = n_samples
+        out = _batch_out(n_samples, np.int16, dev, out)
+        pre = _batch_out(n_samples, np.float32, dev) if want_precast else None
+        flags = _batch_out(n_total, np.uint8, dev) if want_flags else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_mvdrn_batch_dev(self._h, _vp(pcm), stride, _vp(d_sample), _vp(d_block), n_utts, n_total,
+                                                _vp(out), _vp(pre), _vp(flags)))
+        else:
+            self.eng._ck(L.jdsp_mvdrn_batch(self._h, _vp(pcm), stride, n_samples, _vp(sample_first), _vp(block_first),
+                                            n_utts, _vp(out), _vp(pre), _vp(flags)))
+        res = [out[:n_samples]]
+        if want_precast:
+            res.append(pre[:n_samples])
+        if want_flags:
+            res.append(flags[:n_total])
+        return res[0] if len(res) == 1 else tuple(res)
+
 
 class _OlaStream(_Child):
     """What Istft and StftMask share, the overlap-add output stream behind both handles: a subclass names its C entry

@@ -458,6 +458,69 @@ def main():
             for d in (d_a, d_b, d_c):
                 d.close()
         del x, o16
+    if on("mvdrn_batch"):
+        # Batched n-microphone MVDR (jdsp_mvdrn_batch_dev): 8 microphones, loading 1e-3, 2,000 seeded utterances of
+        # 20..100 blocks of 512, packed, every utterance with a quiet lead of 6 blocks (5 estimation frames).  Timed three
+        # ways in this process, in alternated rounds: (a) the batch entry; (b) jdsp_mvdrn_reset + jdsp_mvdrn_process_dev
+        # per utterance on one handle, from ctypes with every argument computed beforehand, over the first 200
+        # utterances and scaled by 10; (c) ONE jdsp_mvdrn_process_dev over the same planes as a single stream of the
+        # same block count (a continuing stream: its output differs).  The PCM (about 1 GB over the eight planes) is far
+        # past the 256 MiB Infinity Cache, so one copy already comes from HBM.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        n_mics, n_utts, part = 8, 2000, 200
+        counts = np.random.default_rng(2000).integers(20, 101, n_utts).astype(np.int64)
+        sample_first, block_first, n_samples = sharding.denoise_batch_layout(counts, 512)
+        total = int(block_first[-1])
+        gen = torch.Generator(device="cuda").manual_seed(2000)
+        sigma = torch.full((total,), 3000.0, device="cuda")
+        sigma[torch.from_numpy((block_first[:-1, None] + np.arange(6)[None, :]).ravel()).cuda()] = 30.0
+        x = torch.empty((n_mics, n_samples), dtype=torch.int16, device="cuda")
+        for m in range(n_mics):
+            draft = torch.randn((total, 512), device="cuda", generator=gen) * sigma[:, None]
+            x[m] = draft.round_().clamp_(-32768, 32767).to(torch.int16).view(-1)
+        del draft, sigma
+        o16 = torch.empty(n_samples, dtype=torch.int16, device="cuda")
+        m_a, m_b, m_c = (eng.mvdr_multi(n_mics, None, 1e-3) for _ in range(3))
+        m_a.reserve_batch(total, n_utts)
+        px, po = x.data_ptr(), o16.data_ptr()
+        calls = [(m_b._h, C.c_void_p(px + 2 * int(sample_first[u])), n_samples, int(counts[u]),
+                  C.c_void_p(po + 2 * int(sample_first[u])), None, None) for u in range(part)]
+        stream_args = (m_c._h, C.c_void_p(px), n_samples, total, C.c_void_p(po), None, None)
+        eng._use_torch_stream()
+
+        def loop():
+            for p in calls:
+                L.jdsp_mvdrn_reset(p[0])
+                L.jdsp_mvdrn_process_dev(*p)
+
+        def stream():
+            L.jdsp_mvdrn_reset(m_c._h)
+            L.jdsp_mvdrn_process_dev(*stream_args)
+
+        batch = lambda: m_a.process_batch(x, counts, sample_first, out=o16)  # noqa: E731
+        assert L.jdsp_mvdrn_process_dev(*calls[0]) == 0 and L.jdsp_mvdrn_process_dev(*stream_args) == 0
+        it = 2 * a.iters                                        # a window of about 0.1 s for (a) and (c)
+        ms_a, ms_c, ms_b = timed_alternated([batch, stream, loop], [it, it, 4], rounds=5)
+        ms_b *= n_utts / part
+        what = "%d ragged utterances, %d blocks (%d..%d each), 8 microphones, 6 quiet blocks in front of each" % (
+            n_utts, total, counts.min(), counts.max())
+        inp = "one copy: %.2f GB of PCM per call (from HBM)" % (2e-9 * n_samples * n_mics)
+        nbytes, flops = 8 * 1024 + 1024, 9 * 5 * 512 * 9 + 9 * 512 * 14 + 1024 * 8 * 8
+        report("mvdrn_batch", ms_a, total, "blocks", nbytes, flops,
+               "(a) jdsp_mvdrn_batch_dev: %s; %.2f x the single stream (c), %.4f of the per-utterance loop (b)"
+               % (what, ms_a / ms_c, ms_a / ms_b), inp=inp)
+        report("mvdrn_batch_per_utterance_loop", ms_b, total, "blocks", nbytes, flops,
+               "(b) the same batch as %d x (jdsp_mvdrn_reset + jdsp_mvdrn_process_dev) on one handle, from ctypes with "
+               "precomputed arguments: measured over the first %d utterances and scaled by %d; %.1f x the batch entry"
+               % (n_utts, part, n_utts // part, ms_b / ms_a), inp=inp)
+        report("mvdrn_batch_single_stream", ms_c, total, "blocks", nbytes, flops,
+               "(c) ONE fresh stream of the same %d blocks over the same planes, jdsp_mvdrn_reset + one "
+               "jdsp_mvdrn_process_dev" % total, inp=inp)
+        for m in (m_a, m_b, m_c):
+            m.close()
+        del x, o16
     if on("stftmask_streams") or on("istft_streams"):
         # Live streams (jdsp_stftmask_streams_dev, jdsp_istft_streams_dev): 10,000 live streams, every call brings each
         # of them a chunk of 4 frames, hop 256 and 512, real mask / half layout (pitch 513).  Timed three ways in this
