@@ -765,9 +765,18 @@ int jdsp_fastconv_process(jdsp_fastconv *h, const int16_t *pcm_host, long n_bloc
  *     ear, "old" (d0, g0) and "new" (d1, g1), the unchanged chunks in both, four inverse transforms, and the ramp
  *     fma(r, new, (1 - r) old) in FP32 in the time domain.  Which form a block takes depends only on the carried and
  *     delivered (dir, gain) values.  S sources cost S + 2 transforms per block (S + 4 while something fades), not 3 S.
- *   - GUARANTEES (tests/test_binaural_gpu.py).  (1) every float sample within 1e-5 sum_c P_c of the FP64 value, P_c the
- *     largest magnitude of chunk c's contribution to either ear over the block; the int16 IS the cast of the float,
- *     and within +-1 of the cast of the FP64 value.  (2) CUTS: a delivery of B blocks with (d, g) equals, bit for bit
+ *   - GUARANTEES (tests/test_binaural_gpu.py; (1) on hard streams: tests/test_binaural_streams_gpu.py).  (1) every float
+ *     sample of an output block within 1e-5 sum_c max(P_c, 0.05 S_c) of the FP64 value: P_c the largest magnitude of
+ *     chunk c's contribution to either ear over the block, and S_c = (the largest |sample| of the chunk's 1024-sample
+ *     segment, silence before a fresh stream) x max(|g1| max_e sum_k |h[d1][e][k]|, and while the chunk fades
+ *     |g0| max_e sum_k |h[d0][e][k]|), which bounds every sample of the segment's circular convolution.  0.05 S_c is
+ *     the scale the FP32 round-off of a segment lives on where the kept samples themselves are (nearly) zero -- a quiet
+ *     block behind a loud one under a one-tap filter, DC into taps that sum to 0, the silence behind a click; there no
+ *     FP32 transform holds 1e-5 sum_c P_c, elsewhere the P_c terms are the larger and the bar is that one (the
+ *     convolver's floor, tests/fastconv_cases.py, per chunk).  Where the bar is 0 the block is exact zeros.  An ear
+ *     whose taps are all zero in every direction the mix hears is exact zeros.  The int16 IS the cast of the float,
+ *     also where the float lies past +-32768 (the low 16 bits), and within +-1 of the cast of the FP64 value modulo
+ *     65536.  Gains in the denormal range are outside the guarantee.  (2) CUTS: a delivery of B blocks with (d, g) equals, bit for bit
  *     in both outputs, any split of it into consecutive deliveries that each name the same (d, g), down to one block
  *     per call.  (3) INDEPENDENCE: a mix's bits do not depend on its place among the mixes, on the other mixes, on
  *     the order of mixes, on its streams' ids or on n_streams; they DO depend on the order of its own chunks.
