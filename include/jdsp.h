@@ -918,9 +918,13 @@ int jdsp_mvdr_shard_finish_dev(jdsp_mvdr *h, const double *sums_all_dev, int wor
  * bins (jdsp_mvdr above is that algorithm).  This keeps its framing, VAD, run counter and weight
  * formula and makes the correlation a Hermitian n_mics x n_mics matrix PER BIN, accumulated over
  * the same noise frames, R_k += X_k X_k^H / 1024; w_k = R_k^-1 c_k / (c_k^H R_k^-1 c_k) with
- * c_k[m] = exp(j 2 PI f_k delays_s[m]); y = IDFT(w^H X).  loading >= 0 adds
+ * c_k[m] = exp(j 2 PI f_k delays_s[m]); y = Re IDFT(w^H X) over k = 0..1023 with the bins above 512 the mirrors of
+ * those below (with a fractional delay w^H X is not real at k = 512; its imaginary part adds nothing to y).
+ * loading >= 0 adds
  * loading * trace(R_k)/n_mics to the diagonal (with 0, R_k is singular until n_mics noise frames
  * have been seen, and the output is NaN -> 0 like the reference's before its first estimate).
+ * Nothing is promised where R_k is only the transform's rounding error: after pauses that hold an exactly periodic
+ * signal and no noise, most bins' R_k, the weights and which samples are finite are decided by that rounding.
  * pcm: n_mics planes, chan_stride samples apart, each n_blocks*512 samples. 2 <= n_mics <= 8. */
 typedef struct jdsp_mvdrn jdsp_mvdrn;
 int jdsp_mvdrn_create(jdsp_ctx *ctx, int n_mics, const double *delays_s, double loading, jdsp_mvdrn **out);

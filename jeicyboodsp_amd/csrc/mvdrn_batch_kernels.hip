@@ -491,6 +491,10 @@ __global__ __launch_bounds__(64) void mvnb_apply_kernel(const short *__restrict_
             yhi[d].y += wh[d].x * hi.y + why * hi.x;
         }
     }
+    // Y[512] = w_512^H X[512] is its own mirror, and real only when c_512 is: with a fractional delay it is not, and the
+    // pre-split below would fold its imaginary part into the frame.  y is the real part of the IDFT (include/jdsp.h), to
+    // which Im Y[512] adds nothing: it goes in as zero, like the 512-point path's bin 256.
+    yhi[0].y = lane == 0 ? 0.f : yhi[0].y;
     float2 y[8], ret[4];
 #pragma unroll
     for (int d = 0; d < 5; d++) {

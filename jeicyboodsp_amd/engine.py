@@ -1143,11 +1143,11 @@ class MvdrMulti(_Child):
     def __init__(self, engine, n_mics, delays=None, loading=0.0, n_fft=1024):
         self.eng = engine
         self.n_mics = int(n_mics)
-        d = np.ascontiguousarray(delays if delays is not None else np.zeros(n_mics), np.float64)
-        assert d.size == n_mics
+        d = None if delays is None else np.ascontiguousarray(delays, np.float64)      # None: delays_s = NULL, no steering
+        assert d is None or d.size == n_mics
         h = C.c_void_p()
-        engine._ck(L.jdsp_mvdrn_create_cfg(engine._h, self.n_mics, d.ctypes.data_as(C.c_void_p), float(loading), int(n_fft),
-                                           C.byref(h)))
+        engine._ck(L.jdsp_mvdrn_create_cfg(engine._h, self.n_mics, None if d is None else d.ctypes.data_as(C.c_void_p),
+                                           float(loading), int(n_fft), C.byref(h)))
         self._h = h
         self.block = L.jdsp_mvdrn_block_len(h)
         engine._children.append(self)

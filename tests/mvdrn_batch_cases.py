@@ -103,9 +103,13 @@ def span_of(x, sample_first, n_blocks):
     return x[sample_first + B:sample_first + n_blocks * B]
 
 
-def check(out, pre, o_out, o_pre):
-    """Returns the share of the 1e-5 bar the worst finite sample takes (0 without finite samples)."""
+def check(out, pre, o_out, o_pre, held=None):
+    """Returns the share of the 1e-5 bar the worst finite sample takes (0 without finite samples).  `held` (bool per
+    sample, tests/mvdrn_cases.py's held_mask) names the samples that count; None: all of them."""
     assert out.shape == o_out.shape and pre.shape == o_pre.shape
+    if held is not None:
+        assert held.shape == pre.shape
+        out, pre, o_out, o_pre = out[held], pre[held], o_out[held], o_pre[held]
     fin = np.isfinite(o_pre)
     assert np.array_equal(np.isfinite(pre), fin)
     worst = 0.0
