@@ -877,7 +877,24 @@ int jdsp_lpc(jdsp_ctx *ctx, const int16_t *pcm_host, long n_blocks, int block_le
  * VoiceActivityDetection on the left channel (:207-242), EstimateSpatialCorrMtx (:244-270) and
  * ProcessMVDR (:124-205).  The first block of a stream produces no output (:201-204); until the
  * correlation matrix is invertible the reference's samples are NaN, cast to 0 here.
- * jdsp_mvdr_corr: current rgdSpatialCorr, row-major (4 doubles, host; synchronises). */
+ * jdsp_mvdr_corr: current rgdSpatialCorr, row-major (4 doubles, host; synchronises).
+ * GUARANTEES, of _process*, _apply and the sharded run alike, against the reference's own arithmetic in FP64
+ * (oracle/jdsp_oracle.c; tests/test_mvdr_gpu.py, and on hard scenes, delays and matrices tests/test_mvdr_hard_gpu.py):
+ *   - precast: every finite sample within 1e-5 of the stream's own finite peak (the largest finite |sample| of the FP64
+ *     value over the stream, at least 1), and finite exactly where the FP64 value is.
+ *   - out: the (short) cast of precast, within 1 LSB of the cast of the FP64 value.  With d_time != 0 the reference's
+ *     overwritten real part (:180-183) has gain above 1, so a full-scale stream leaves int16 before the cast (39,000 and
+ *     more); the cast then keeps the low 16 bits of the value truncated to int32, here as in the reference built for
+ *     x86-64, and the 1 LSB holds modulo 2^16.  (Where 1e-5 of the peak exceeds half an LSB -- a caller matrix close to
+ *     singular under a delay has a peak in the millions -- the first bar is the one that holds.)
+ *   - a singular matrix (before the first estimate; a channel that is exactly zero in every pause) gives the
+ *     reference's non-finite samples: the non-finite value in precast, 0 in out.
+ *   - rgdSpatialCorr: the diagonal is the exact integer sum of the estimation frames' energies (Parseval), within 1e-12
+ *     of the reference's; the off-diagonal, rounding error of the reference's transforms (1e-17 of the diagonal), is
+ *     exactly 0.
+ *   - the output does not depend on how the stream is cut into calls or on host against device pointers, bit for bit
+ *     (the matrix is a sum of integers, exact in FP64 in any grouping while it stays below 2^53; the weights are one
+ *     FP64 closed form whether a call reads them from its table or computes them per block). */
 typedef struct jdsp_mvdr jdsp_mvdr;
 int jdsp_mvdr_create(jdsp_ctx *ctx, double d_time, jdsp_mvdr **out);
 int jdsp_mvdr_destroy(jdsp_mvdr *h);

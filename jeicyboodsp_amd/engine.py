@@ -1098,14 +1098,17 @@ class Mvdr(_Child):
         self.eng._ck(L.jdsp_mvdr_shard_summary_dev(self._h, C.c_void_p(flags_all.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
-    def shard_finish(self, sums_all, world, rank):
+    def shard_finish(self, sums_all, world, rank, want_precast=False):
         import torch
         n_out = L.jdsp_mvdr_shard_blocks_out(self._h)
         out = torch.empty(max(n_out, 1) * 512, dtype=torch.int16, device=sums_all.device)
+        pre = torch.empty(max(n_out, 1) * 512, dtype=torch.float32, device=sums_all.device) if want_precast else None
         self.eng._use_torch_stream()
         self.eng._ck(L.jdsp_mvdr_shard_finish_dev(self._h, C.c_void_p(sums_all.data_ptr()), world, rank,
-                                                  C.c_void_p(out.data_ptr()), None, None))
-        return out[: n_out * 512]
+                                                  C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(pre.data_ptr()) if want_precast else None, None))
+        out = out[: n_out * 512]
+        return (out, pre[: n_out * 512]) if want_precast else out
 
     def process(self, left, right, want_precast=False):
         if _is_torch(left):
