@@ -14,7 +14,11 @@
 //   mvnb_utt_kernel          ev_first per utterance and the chunk slots (below)
 //   mvnb_event_spectra_kernel   X_m[k] of the frame [block j - 1, block j] of every event, both blocks inside the span
 //   mvnb_chunk_sums / _prefix / mvnb_update_kernel   R_k and the weights after every event, per utterance from zero
-//   mvnb_apply_kernel        one wave per block: mvdrn_apply_pairs_kernel's body on span addresses
+//   mvnb_apply_kernel        one wave per block: the beamformed frame on span addresses
+// The last four run the stream kernels' arithmetic, written once: the spectrum, the range sum and the emit are functions
+// of mvdrn_common.h, the walk with its solve and the beamformed frame are the body fragments mvdrn_walk_body.h and
+// mvdrn_frame_body.h, which mvdrn_kernels.hip includes too.  What is written here is what a batch has of its own: the
+// VAD, the prefix sum, the slots and the span addresses.
 //
 // The weight table has row 0 for "no event yet" (the zero matrix, solved like any other: the non-finite weights of a
 // fresh handle, the same for every utterance, so one row serves all) and row e + 1 for the e-th event of the GLOBAL
@@ -235,17 +239,7 @@ __global__ __launch_bounds__(64) void mvnb_event_spectra_kernel(const short *__r
         unsigned int raw[8];
         relayout_half(stage, lane, reinterpret_cast<const u32x4_span *>(cur - 512)[lane], raw);
         relayout_half(stage, lane, reinterpret_cast<const u32x4_span *>(cur)[lane], raw + 4);
-        float2 v[8], lo[8], hi[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) { const float2 s = unpack_i16x2(raw[r]); v[r] = make_float2(0.5f * s.x, 0.5f * s.y); }
-        mvn_spectrum(v, lds, lane, tw, wsp, lo, hi);
-        float2 *dst = spec + (size_t)w * kMvnBins;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            dst[128 * q + 2 * lane] = lo[2 * q];
-            dst[128 * q + 2 * lane + 1] = lo[2 * q + 1];
-        }
-        if (lane == 0) dst[512] = hi[0];
+        mvn_event_spectrum(raw, lds, lane, tw, wsp, spec + (size_t)w * kMvnBins);
     }
 }
 
@@ -277,22 +271,13 @@ __global__ __launch_bounds__(64) void mvnb_chunk_sums_kernel(const float2 *__res
                                                              const int *__restrict__ ev_first,
                                                              const int *__restrict__ slot_utt, double2 *__restrict__ chunk_ws)
 {
-    __shared__ __attribute__((aligned(16))) float2 sx[8][8];
     const int lane = threadIdx.x, grp = lane >> 3, r = lane & 7;
     const MvnbChunk c = mvnb_chunk_of(blockIdx.x, n_utts, ev_first, slot_utt);
     if (c.n_chunks < 2 || c.q + 1 >= c.n_chunks) return;
     const int kb = blockIdx.y * 8 + grp;
     const int k = kb < kMvnBins ? kb : kMvnBins - 1;             // a group past the last bin repeats it and stores nothing
     cd S[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) S[i] = {0.0, 0.0};
-    float2 xr = make_float2(0.f, 0.f);
-    if (r < n_mics) xr = spec[((size_t)c.e0 * n_mics + r) * kMvnBins + k];
-    for (int e = c.e0; e < c.e1; e++) {
-        const float2 x = xr;
-        if (r < n_mics && e + 1 < c.e1) xr = spec[((size_t)(e + 1) * n_mics + r) * kMvnBins + k];
-        mvn_row_add(S, x, sx[grp], r, 1.0 / 1024.0);
-    }
+    mvn_range_sum(S, grp, r, spec, c.e0, c.e1, n_mics, kMvnBins, k, 1.0 / 1024.0);
     if (kb < kMvnBins) {
         double2 *dst = chunk_ws + ((size_t)(c.store0 + c.q) * kMvnBins + k) * 64 + 8 * r;
 #pragma unroll
@@ -328,20 +313,15 @@ __global__ __launch_bounds__(64) void mvnb_chunk_prefix_kernel(long n_utts, cons
 }
 
 // (8 bins, slot): walks the chunk's events from the matrix entering it, one solve per event; the grid's LAST slot
-// solves the zero matrix instead, row 0 of the weight table.  The solve is mvdrn_update_kernel's elimination, statement
-// for statement (restated, not shared: that kernel keeps its body): Gaussian elimination of [R' | c] to a diagonal
-// (R' = R + loading tr(R) / n I), pivot rows unnormalised, each unknown divided by its pivot at the end, w = x / (c^H x).
-// weights[(row * 8 + m) * 513 + k], row = event + 1.
+// solves the zero matrix instead, row 0 of the weight table: a walk over no events that solves what it was given.  The
+// walk and its solve are mvdrn_update_kernel's, the same text (mvdrn_walk_body.h): weights[(row * 8 + m) * 513 + k],
+// row = event + 1 = the walk's version.
 __global__ __launch_bounds__(64) void mvnb_update_kernel(const float2 *__restrict__ spec, int n_mics, long n_utts,
                                                          const int *__restrict__ ev_first, const int *__restrict__ slot_utt,
                                                          const double2 *__restrict__ chunk_ws,
                                                          const double2 *__restrict__ steer, double loading,
                                                          float2 *__restrict__ weights)
 {
-    __shared__ __attribute__((aligned(16))) float2 sx[8][8];       // the event's spectra, [bin in wave][microphone]
-    __shared__ __attribute__((aligned(16))) double2 srow[8][9];    // the pivot row and its right-hand side
-    __shared__ __attribute__((aligned(16))) double2 sc[8][8];      // steering vectors
-    __shared__ __attribute__((aligned(16))) double2 sv[8][8];      // diagonals, then the unknowns
     const int lane = threadIdx.x, grp = lane >> 3, r = lane & 7;
     const bool row0 = blockIdx.x + 1 == gridDim.x;
     MvnbChunk c = {0, 0, 0, 0, 0};
@@ -351,7 +331,6 @@ __global__ __launch_bounds__(64) void mvnb_update_kernel(const float2 *__restric
     }
     const int kb = blockIdx.y * 8 + grp;
     const int k = kb < kMvnBins ? kb : kMvnBins - 1;
-    const bool row_live = r < n_mics;
     cd R[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) R[i] = {0.0, 0.0};
@@ -360,74 +339,29 @@ __global__ __launch_bounds__(64) void mvnb_update_kernel(const float2 *__restric
 #pragma unroll
         for (int i = 0; i < 8; i++) R[i] = cd_of(src[i]);
     }
-    const double2 sr = steer[(size_t)k * 8 + r];
-    const cd cr = {row_live ? sr.x : 0.0, row_live ? sr.y : 0.0};
-    sc[grp][r] = d2_of(cr);
-    // the zero matrix is a walk of one version that adds nothing
-    const int e1 = row0 ? 1 : c.e1;
-    float2 xr = make_float2(0.f, 0.f);
-    if (row_live && !row0) xr = spec[((size_t)c.e0 * n_mics + r) * kMvnBins + k];
-    for (int e = c.e0; e < e1; e++) {
-        if (!row0) mvn_row_add(R, xr, sx[grp], r, 1.0 / 1024.0);
-        if (row_live && !row0 && e + 1 < e1) xr = spec[((size_t)(e + 1) * n_mics + r) * kMvnBins + k];
-        double dgx = R[0].x;                                   // the diagonal entry (real) of this lane's row
-#pragma unroll
-        for (int c = 1; c < 8; c++) dgx = r == c ? R[c].x : dgx;
-        wave_lds_fence();
-        sv[grp][r] = make_double2(dgx, 0.0);
-        wave_lds_fence();
-        double tr = 0.0;
-        for (int d = 0; d < n_mics; d++) tr += sv[grp][d].x;
-        const double load = loading * tr / n_mics;
-        cd A[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            A[c].x = r == c ? (row_live ? R[c].x + load : 1.0) : R[c].x;
-            A[c].y = r == c && !row_live ? 0.0 : R[c].y;
-        }
-        cd b = cr, my_inv = {1.0, 0.0};
-#pragma unroll
-        for (int p = 0; p < 8; p++) {
-            if (p < n_mics) {
-                wave_lds_fence();
-                if (r == p) {
-#pragma unroll
-                    for (int c = p; c < 8; c++) srow[grp][c] = d2_of(A[c]);
-                    srow[grp][8] = d2_of(b);
-                }
-                wave_lds_fence();
-                const cd inv = cd_inv_fast(cd_of(srow[grp][p]));
-                cd f = cd_mul(A[p], inv);                       // this row's multiple of the pivot row
-                my_inv.x = r == p ? inv.x : my_inv.x;
-                my_inv.y = r == p ? inv.y : my_inv.y;
-                f.x = r == p ? 0.0 : f.x;
-                f.y = r == p ? 0.0 : f.y;
-#pragma unroll
-                for (int c = p + 1; c < 8; c++) A[c] = cd_sub(A[c], cd_mul(f, cd_of(srow[grp][c])));
-                b = cd_sub(b, cd_mul(f, cd_of(srow[grp][8])));
-            }
-        }
-        const cd x = cd_mul(b, my_inv);
-        wave_lds_fence();
-        sv[grp][r] = d2_of(x);
-        wave_lds_fence();
-        cd den = {0.0, 0.0};                                   // c^H x
-        for (int d = 0; d < n_mics; d++) {
-            const cd xd = cd_of(sv[grp][d]);
-            const cd cdv = cd_of(sc[grp][d]);
-            den.x += cdv.x * xd.x + cdv.y * xd.y;
-            den.y += cdv.x * xd.y - cdv.y * xd.x;
-        }
-        const cd w = cd_mul(x, cd_inv_fast(den));
-        const size_t row = row0 ? 0 : (size_t)e + 1;
-        if (row_live && kb < kMvnBins) weights[(row * 8 + r) * kMvnBins + k] = make_float2((float)w.x, (float)w.y);
-    }
+    constexpr int n_bins = kMvnBins;
+    constexpr double inv_n = 1.0 / 1024.0;
+    const int e0 = c.e0, e1 = c.e1;                               // the last slot: no events, and the leading version alone
+    const bool lead = row0;
+#include "mvdrn_walk_body.h"
 }
 
 // ---- 5. apply: one wave per block of the concatenated axis -----------------------------------------------------------
-// mvdrn_apply_pairs_kernel's body (pair-owned bins, see there).  The wave finds its utterance in scalar registers; an
-// utterance's first block has silence in front of it and emits nothing, so its wave leaves at once; every other block
+// The frame body of mvdrn_apply_pairs_kernel, the same text (mvdrn_frame_body.h).  The wave finds its utterance in scalar registers;
+// an utterance's first block has silence in front of it and emits nothing, so its wave leaves at once; every other block
 // reads the block before it from the span and writes time-aligned, at its own place in out and precast.
+struct MvnbSpanSrc {
+    const short *cur;                                              // block j of the next microphone asked for (they come in
+    long chan_stride;                                              // order); block j - 1 lies before it
+    __device__ __forceinline__ void load(int, int lane, u32x4 &prev, u32x4 &now)
+    {
+        prev = reinterpret_cast<const u32x4_span *>(cur - 512)[lane];
+        now = reinterpret_cast<const u32x4_span *>(cur)[lane];
+        cur += chan_stride;
+    }
+    __device__ __forceinline__ void done(int, int) const {}
+};
+
 __global__ __launch_bounds__(64) void mvnb_apply_kernel(const short *__restrict__ pcm, long chan_stride, int n_mics,
                                                         const long long *__restrict__ sample_first,
                                                         const long long *__restrict__ block_first, long n_utts,
@@ -437,8 +371,6 @@ __global__ __launch_bounds__(64) void mvnb_apply_kernel(const short *__restrict_
                                                         const float2 *__restrict__ table, short *__restrict__ out,
                                                         float *__restrict__ precast)
 {
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    __shared__ __attribute__((aligned(16))) unsigned int stage32[528];
     const int lane = threadIdx.x;
     const long per_xcd = (gridDim.x + 7) >> 3;
     const long j = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
@@ -449,69 +381,10 @@ __global__ __launch_bounds__(64) void mvnb_apply_kernel(const short *__restrict_
     const long at = uniform_i64(sample_first + u) + (j - ub) * 512;     // block j's first sample; block j - 1 is in the span
     const int seen = __builtin_amdgcn_readfirstlane(evpre[j]);
     const int row = seen == __builtin_amdgcn_readfirstlane(ev_first[u]) ? 0 : seen;
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    PairTwiddles pw;
-    load_pair_twiddles(pw, table, lane);
+    MvnbSpanSrc src = {pcm + at, chan_stride};
     const float2 *W = weights + (size_t)row * kMvnBins * 8;
-    const float nyq = lane == 0 ? -1.f : 1.f;                      // k = 512 (lane 0, d = 0) is its own mirror: conj(w) there
-
-    float2 ylo[5], yhi[5];
-#pragma unroll
-    for (int d = 0; d < 5; d++) { ylo[d] = make_float2(0.f, 0.f); yhi[d] = make_float2(0.f, 0.f); }
-    // a microphone's two blocks are requested while the one before it is transformed (the LDS fences would hold the loads back)
-    const short *cur = pcm + at;
-    u32x4 nxt_prev = reinterpret_cast<const u32x4_span *>(cur - 512)[lane];
-    u32x4 nxt_cur = reinterpret_cast<const u32x4_span *>(cur)[lane];
-    for (int m = 0; m < n_mics; m++) {
-        const float2 *Wm = W + (size_t)m * kMvnBins;
-        float2 wl[5], wh[5];
-#pragma unroll
-        for (int d = 0; d < 5; d++) { wl[d] = Wm[lane + 64 * d]; wh[d] = Wm[512 - lane - 64 * d]; }
-        const u32x4 img_prev = nxt_prev, img_cur = nxt_cur;
-        if (m + 1 < n_mics) {
-            cur += chan_stride;
-            nxt_prev = reinterpret_cast<const u32x4_span *>(cur - 512)[lane];
-            nxt_cur = reinterpret_cast<const u32x4_span *>(cur)[lane];
-        }
-        float2 v[8], zr[5];
-        mvdr_frame_pairs(stage32, lane, img_prev, img_cur, v, 0.5f);
-        wave_fft512<false>(v, lds, lane, tw);
-        wave_lds_fence();
-        pair_fetch_lds(v, lds, lane, zr);
-#pragma unroll
-        for (int d = 0; d < 5; d++) {
-            const float2 e = cadd_conj(v[d], zr[d]), o = csub_conj_mj(v[d], zr[d]);
-            const float2 t = cmul(pw.w[d], o);
-            const float2 lo = cadd(e, t), hi = csub(e, t);         // X[m], X[m + 512]
-            ylo[d].x += wl[d].x * lo.x + wl[d].y * lo.y;           // conj(w_m) X[m]
-            ylo[d].y += wl[d].x * lo.y - wl[d].y * lo.x;
-            const float why = d == 0 ? nyq * wh[d].y : wh[d].y;
-            yhi[d].x += wh[d].x * hi.x - why * hi.y;               // w_{512-m} X[m + 512]
-            yhi[d].y += wh[d].x * hi.y + why * hi.x;
-        }
-    }
-    // Y[512] = w_512^H X[512] is its own mirror, and real only when c_512 is: with a fractional delay it is not, and the
-    // pre-split below would fold its imaginary part into the frame.  y is the real part of the IDFT (include/jdsp.h), to
-    // which Im Y[512] adds nothing: it goes in as zero, like the 512-point path's bin 256.
-    yhi[0].y = lane == 0 ? 0.f : yhi[0].y;
-    float2 y[8], ret[4];
-#pragma unroll
-    for (int d = 0; d < 5; d++) {
-        if (d < 4) presplit_inv_pair(ylo[d], yhi[d], pw.w[d], y[d], ret[d]);
-        else y[d] = presplit_inv_reg(ylo[d], yhi[d], pw.w[d]);
-    }
-    pair_return_lds(ret, lds, lane, y);
-    wave_fft512<true>(y, lds, lane, tw);
-    short *o = out ? out + at : nullptr;
-    float *pc = precast ? precast + at : nullptr;
-#pragma unroll
-    for (int dd = 0; dd < 8; dd++) {
-        const int i0 = 2 * lane + 128 * dd - 511;
-        const float s0 = y[dd].x * (1.0f / 1024.0f), s1 = y[dd].y * (1.0f / 1024.0f);
-        if (i0 >= 0 && i0 < 512) { if (o) o[i0] = (short)cast_i16_bits(s0); if (pc) pc[i0] = s0; }
-        if (i0 + 1 >= 0 && i0 + 1 < 512) { if (o) o[i0 + 1] = (short)cast_i16_bits(s1); if (pc) pc[i0 + 1] = s1; }
-    }
+#include "mvdrn_frame_body.h"
+    mvn_emit_block<true>(y, lane, out ? out + at : nullptr, precast ? precast + at : nullptr);
 }
 
 int launch_mvdrn_batch(hipStream_t s, const short *pcm, long chan_stride, int n_mics, const long long *sample_first,

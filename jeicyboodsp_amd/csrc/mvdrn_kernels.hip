@@ -9,7 +9,10 @@
 //   mvdrn_event_spectra_kernel    X_m[k], k = 0..512, of every estimation frame and microphone
 //   mvdrn_chunk_sums / _prefix / mvdrn_update_kernel   R_k += X X^H / N per event, the weights after each
 //   mvdrn_apply_pairs_kernel      one wave per block: n_mics transforms, y = IDFT(w^H X)
-// (mvn_spectrum, the complex FP64 helpers and mvn_row_add: mvdrn_common.h, shared with mvdrn_batch_kernels.hip)
+// The arithmetic of these four is written once and shared with mvdrn_batch_kernels.hip: the frame's spectrum, the range
+// sum and the emit are functions of mvdrn_common.h, the walk with its solve and the beamformed frame are the body
+// fragments mvdrn_walk_body.h and mvdrn_frame_body.h (why text: see the former).  The kernels here are a stream's
+// addresses, chunk geometry and carried state around it.
 #include "frame_io.h"
 #include "jdsp_internal.h"
 #include "mvdrn_common.h"
@@ -50,17 +53,7 @@ __global__ __launch_bounds__(64) void mvdrn_event_spectra_kernel(const short *__
         unsigned int raw[8];
         relayout_half(stage, lane, mvn_block(chan, n_blocks, prev, j - 1, lane), raw);
         relayout_half(stage, lane, mvn_block(chan, n_blocks, prev, j, lane), raw + 4);
-        float2 v[8], lo[8], hi[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) { const float2 s = unpack_i16x2(raw[r]); v[r] = make_float2(0.5f * s.x, 0.5f * s.y); }
-        mvn_spectrum(v, lds, lane, tw, wsp, lo, hi);
-        float2 *dst = spec + (size_t)w * kMvnBins;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            dst[128 * q + 2 * lane] = lo[2 * q];
-            dst[128 * q + 2 * lane + 1] = lo[2 * q + 1];
-        }
-        if (lane == 0) dst[512] = hi[0];
+        mvn_event_spectrum(raw, lds, lane, tw, wsp, spec + (size_t)w * kMvnBins);
     }
 }
 
@@ -90,7 +83,6 @@ __global__ __launch_bounds__(64) void mvdrn_chunk_sums_kernel(const float2 *__re
                                                               double inv_n, const DenoisePlan *__restrict__ plan,
                                                               double2 *__restrict__ chunk_sum)
 {
-    __shared__ __attribute__((aligned(16))) float2 sx[8][8];
     const int lane = threadIdx.x, grp = lane >> 3, r = lane & 7, chunk = blockIdx.y;
     const int n_events = plan->n_events;
     const MvnChunks g = mvn_chunks(n_events);
@@ -99,15 +91,7 @@ __global__ __launch_bounds__(64) void mvdrn_chunk_sums_kernel(const float2 *__re
     const int k = kb < n_bins ? kb : n_bins - 1;                 // a group past the last bin repeats it and stores nothing
     const int e0 = chunk * g.per_chunk, e1 = e0 + g.per_chunk < n_events ? e0 + g.per_chunk : n_events;
     cd S[8];
-#pragma unroll
-    for (int c = 0; c < 8; c++) S[c] = {0.0, 0.0};
-    float2 xr = make_float2(0.f, 0.f);
-    if (r < n_mics && e0 < e1) xr = spec[((size_t)e0 * n_mics + r) * n_bins + k];
-    for (int e = e0; e < e1; e++) {
-        const float2 x = xr;
-        if (r < n_mics && e + 1 < e1) xr = spec[((size_t)(e + 1) * n_mics + r) * n_bins + k];
-        mvn_row_add(S, x, sx[grp], r, inv_n);
-    }
+    mvn_range_sum(S, grp, r, spec, e0, e1, n_mics, n_bins, k, inv_n);
     if (kb < n_bins) {
         double2 *dst = chunk_sum + ((size_t)chunk * n_bins + k) * 64 + 8 * r;
 #pragma unroll
@@ -142,102 +126,52 @@ __global__ __launch_bounds__(64) void mvdrn_chunk_prefix_kernel(const double2 *_
     cov_out[(size_t)k * 64 + lane] = R;
 }
 
-// After every event the weights are recomputed: Gaussian elimination of [R' | c] to a diagonal (R' = R + loading *
-// tr(R) / n * I, Hermitian positive definite once loaded, so no pivoting; pivot rows are left unnormalised and each
-// unknown is divided by its pivot at the end), then w = x / (c^H x).  Version 0 = the matrix carried in (chunk 0).
-// Step p: the lane holding row p puts its entries right of the diagonal and its right-hand side in LDS, the group's
-// other rows subtract their multiple of it.
+// After every event the weights are recomputed (mvdrn_walk_body.h: the walk and its solve): the chunk's events from the
+// matrix entering it.  Version 0 = the matrix carried in, which chunk 0 solves too.
 __global__ __launch_bounds__(64) void mvdrn_update_kernel(const float2 *__restrict__ spec, int n_mics, int n_bins,
                                                           double inv_n, const DenoisePlan *__restrict__ plan,
                                                           const double2 *__restrict__ chunk_start,
                                                           const double2 *__restrict__ steer, double loading,
                                                           float2 *__restrict__ weights)
 {
-    __shared__ __attribute__((aligned(16))) float2 sx[8][8];       // the event's spectra, [bin in wave][microphone]
-    __shared__ __attribute__((aligned(16))) double2 srow[8][9];    // the pivot row and its right-hand side
-    __shared__ __attribute__((aligned(16))) double2 sc[8][8];      // steering vectors
-    __shared__ __attribute__((aligned(16))) double2 sv[8][8];      // diagonals, then the unknowns
     const int lane = threadIdx.x, grp = lane >> 3, r = lane & 7, chunk = blockIdx.y;
     const int n_events = plan->n_events;
     const MvnChunks g = mvn_chunks(n_events);
     if (chunk > 0 && chunk >= g.n_chunks) return;
     const int kb = blockIdx.x * 8 + grp;
     const int k = kb < n_bins ? kb : n_bins - 1;
-    const bool row_live = r < n_mics;
     cd R[8];
     {
         const double2 *src = chunk_start + ((size_t)chunk * n_bins + k) * 64 + 8 * r;
 #pragma unroll
         for (int c = 0; c < 8; c++) R[c] = cd_of(src[c]);
     }
-    const double2 sr = steer[(size_t)k * 8 + r];
-    const cd cr = {row_live ? sr.x : 0.0, row_live ? sr.y : 0.0};
-    sc[grp][r] = d2_of(cr);
     const int e0 = chunk * g.per_chunk;
     const int e1 = e0 + g.per_chunk < n_events ? e0 + g.per_chunk : n_events;
-    float2 xr = make_float2(0.f, 0.f);
-    if (row_live && e0 < e1) xr = spec[((size_t)e0 * n_mics + r) * n_bins + k];     // event e0 is the first this chunk adds
-    for (int v = chunk == 0 ? 0 : e0 + 1; v <= e1; v++) {
-        if (v > e0) mvn_row_add(R, xr, sx[grp], r, inv_n);
-        if (row_live && v < e1) xr = spec[((size_t)v * n_mics + r) * n_bins + k];   // event v is the one version v + 1 adds
-        double dgx = R[0].x;                                   // the diagonal entry (real) of this lane's row
-#pragma unroll
-        for (int c = 1; c < 8; c++) dgx = r == c ? R[c].x : dgx;
-        wave_lds_fence();
-        sv[grp][r] = make_double2(dgx, 0.0);
-        wave_lds_fence();
-        double tr = 0.0;
-        for (int d = 0; d < n_mics; d++) tr += sv[grp][d].x;
-        const double load = loading * tr / n_mics;
-        cd A[8];
-#pragma unroll
-        for (int c = 0; c < 8; c++) {
-            A[c].x = r == c ? (row_live ? R[c].x + load : 1.0) : R[c].x;
-            A[c].y = r == c && !row_live ? 0.0 : R[c].y;
-        }
-        cd b = cr, my_inv = {1.0, 0.0};
-#pragma unroll
-        for (int p = 0; p < 8; p++) {
-            if (p < n_mics) {
-                wave_lds_fence();
-                if (r == p) {
-#pragma unroll
-                    for (int c = p; c < 8; c++) srow[grp][c] = d2_of(A[c]);
-                    srow[grp][8] = d2_of(b);
-                }
-                wave_lds_fence();
-                const cd inv = cd_inv_fast(cd_of(srow[grp][p]));
-                cd f = cd_mul(A[p], inv);                       // this row's multiple of the pivot row
-                my_inv.x = r == p ? inv.x : my_inv.x;
-                my_inv.y = r == p ? inv.y : my_inv.y;
-                f.x = r == p ? 0.0 : f.x;
-                f.y = r == p ? 0.0 : f.y;
-#pragma unroll
-                for (int c = p + 1; c < 8; c++) A[c] = cd_sub(A[c], cd_mul(f, cd_of(srow[grp][c])));
-                b = cd_sub(b, cd_mul(f, cd_of(srow[grp][8])));
-            }
-        }
-        const cd x = cd_mul(b, my_inv);
-        wave_lds_fence();
-        sv[grp][r] = d2_of(x);
-        wave_lds_fence();
-        cd den = {0.0, 0.0};                                   // c^H x
-        for (int d = 0; d < n_mics; d++) {
-            const cd xd = cd_of(sv[grp][d]);
-            const cd cdv = cd_of(sc[grp][d]);
-            den.x += cdv.x * xd.x + cdv.y * xd.y;
-            den.y += cdv.x * xd.y - cdv.y * xd.x;
-        }
-        const cd w = cd_mul(x, cd_inv_fast(den));
-        // [version][microphone][bin]: the apply kernel reads one microphone's weights for consecutive bins
-        if (row_live && kb < n_bins) weights[((size_t)v * 8 + r) * n_bins + k] = make_float2((float)w.x, (float)w.y);
-    }
+    const bool lead = chunk == 0;
+#include "mvdrn_walk_body.h"
 }
 
-// One wave per block, pair-owned bins (frame_io.h): lane l works on the bins m, m + 512 of m = l + 64 d, d < 5.  Y[k] =
-// sum_m conj(w_k[m]) X_m[k] with w_k = conj(w_{1024-k}) above 512 is Hermitian when the X_m are, so the 513 bins the
-// five items cover are all of it: ten weights and ten products per lane and microphone (sixteen with every bin a lane's
-// own), and the inverse transform's mirrored inputs come from presplit_inv_pair.
+// One wave per block: the beamformed frame (mvdrn_frame_body.h) on the blocks of a stream.  Block -1 is the previous call's last
+// block (none before the handle's first call: silence), and the wave of the call's last block hands it on.
+struct MvnStreamSrc {
+    const short *pcm, *prev_in;
+    short *prev_out;
+    long chan_stride, n_blocks, j, jp;
+    __device__ __forceinline__ void load(int m, int lane, u32x4 &prev, u32x4 &cur) const
+    {
+        const short *chan = pcm + (size_t)m * chan_stride, *carried = prev_in + (size_t)m * 512;
+        prev = mvn_block(chan, n_blocks, carried, jp, lane);
+        cur = mvn_block(chan, n_blocks, carried, j, lane);
+    }
+    __device__ __forceinline__ void done(int m, int lane) const
+    {
+        if (j == n_blocks - 1)
+            reinterpret_cast<u32x4 *>(prev_out + (size_t)m * 512)[lane] =
+                reinterpret_cast<const u32x4 *>(pcm + (size_t)m * chan_stride + j * 512)[lane];
+    }
+};
+
 __global__ __launch_bounds__(64) void mvdrn_apply_pairs_kernel(const short *__restrict__ pcm, long chan_stride, int n_mics,
                                                                long n_blocks, long calls_before,
                                                                const short *__restrict__ prev_in, short *__restrict__ prev_out,
@@ -247,80 +181,17 @@ __global__ __launch_bounds__(64) void mvdrn_apply_pairs_kernel(const short *__re
                                                                const float2 *__restrict__ table, short *__restrict__ out,
                                                                float *__restrict__ precast)
 {
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    __shared__ __attribute__((aligned(16))) unsigned int stage32[528];
     const int lane = threadIdx.x;
     const long per_xcd = (gridDim.x + 7) >> 3;
     const long j = (long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
     if (j >= n_blocks) return;
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    PairTwiddles pw;
-    load_pair_twiddles(pw, table, lane);
     const bool have_prev = calls_before + j > 0;
+    MvnStreamSrc src = {pcm, prev_in, prev_out, chan_stride, n_blocks, j, have_prev ? j - 1 : -2};
     const float2 *W = weights + (size_t)version_of(ver_base, snap_mask, j) * kMvnBins * 8;
-    const float nyq = lane == 0 ? -1.f : 1.f;                      // k = 512 (lane 0, d = 0) is its own mirror: conj(w) there
-
-    float2 ylo[5], yhi[5];
-#pragma unroll
-    for (int d = 0; d < 5; d++) { ylo[d] = make_float2(0.f, 0.f); yhi[d] = make_float2(0.f, 0.f); }
-    // a microphone's two blocks are requested while the one before it is transformed (the LDS fences would hold the loads back)
-    const long jp = have_prev ? j - 1 : -2;
-    u32x4 nxt_prev = mvn_block(pcm, n_blocks, prev_in, jp, lane), nxt_cur = mvn_block(pcm, n_blocks, prev_in, j, lane);
-    for (int m = 0; m < n_mics; m++) {
-        const short *chan = pcm + (size_t)m * chan_stride;
-        const float2 *Wm = W + (size_t)m * kMvnBins;
-        float2 wl[5], wh[5];
-#pragma unroll
-        for (int d = 0; d < 5; d++) { wl[d] = Wm[lane + 64 * d]; wh[d] = Wm[512 - lane - 64 * d]; }
-        const u32x4 img_prev = nxt_prev, img_cur = nxt_cur;
-        if (m + 1 < n_mics) {
-            nxt_prev = mvn_block(chan + chan_stride, n_blocks, prev_in + (size_t)(m + 1) * 512, jp, lane);
-            nxt_cur = mvn_block(chan + chan_stride, n_blocks, prev_in + (size_t)(m + 1) * 512, j, lane);
-        }
-        float2 v[8], zr[5];
-        mvdr_frame_pairs(stage32, lane, img_prev, img_cur, v, 0.5f);
-        wave_fft512<false>(v, lds, lane, tw);
-        wave_lds_fence();
-        pair_fetch_lds(v, lds, lane, zr);
-#pragma unroll
-        for (int d = 0; d < 5; d++) {
-            const float2 e = cadd_conj(v[d], zr[d]), o = csub_conj_mj(v[d], zr[d]);
-            const float2 t = cmul(pw.w[d], o);
-            const float2 lo = cadd(e, t), hi = csub(e, t);         // X[m], X[m + 512]
-            ylo[d].x += wl[d].x * lo.x + wl[d].y * lo.y;           // conj(w_m) X[m]
-            ylo[d].y += wl[d].x * lo.y - wl[d].y * lo.x;
-            const float why = d == 0 ? nyq * wh[d].y : wh[d].y;
-            yhi[d].x += wh[d].x * hi.x - why * hi.y;               // w_{512-m} X[m + 512]
-            yhi[d].y += wh[d].x * hi.y + why * hi.x;
-        }
-        if (j == n_blocks - 1)
-            reinterpret_cast<u32x4 *>(prev_out + (size_t)m * 512)[lane] = reinterpret_cast<const u32x4 *>(chan + j * 512)[lane];
-    }
-    // Y[512] = w_512^H X[512] is its own mirror, and real only when c_512 is: with a fractional delay it is not, and the
-    // pre-split below would fold its imaginary part into the frame.  y is the real part of the IDFT (include/jdsp.h), to
-    // which Im Y[512] adds nothing: it goes in as zero, like the 512-point path's bin 256.
-    yhi[0].y = lane == 0 ? 0.f : yhi[0].y;
-    float2 y[8], ret[4];
-#pragma unroll
-    for (int d = 0; d < 5; d++) {
-        if (d < 4) presplit_inv_pair(ylo[d], yhi[d], pw.w[d], y[d], ret[d]);
-        else y[d] = presplit_inv_reg(ylo[d], yhi[d], pw.w[d]);
-    }
-    pair_return_lds(ret, lds, lane, y);
-    wave_fft512<true>(y, lds, lane, tw);
+#include "mvdrn_frame_body.h"
     const long first_emit = calls_before >= 1 ? 0 : 1;
-    if (j >= first_emit) {
-        short *o = out + (j - first_emit) * 512;
-        float *pc = precast ? precast + (j - first_emit) * 512 : nullptr;
-#pragma unroll
-        for (int dd = 0; dd < 8; dd++) {
-            const int i0 = 2 * lane + 128 * dd - 511;
-            const float s0 = y[dd].x * (1.0f / 1024.0f), s1 = y[dd].y * (1.0f / 1024.0f);
-            if (i0 >= 0 && i0 < 512) { o[i0] = (short)cast_i16_bits(s0); if (pc) pc[i0] = s0; }
-            if (i0 + 1 >= 0 && i0 + 1 < 512) { o[i0 + 1] = (short)cast_i16_bits(s1); if (pc) pc[i0 + 1] = s1; }
-        }
-    }
+    if (j >= first_emit)
+        mvn_emit_block<false>(y, lane, out + (j - first_emit) * 512, precast ? precast + (j - first_emit) * 512 : nullptr);
 }
 
 // chunk_ws: 2 * chunk_cap * n_bins * 64 double2 (the chunk sums, then the matrices entering the chunks), [chunk][bin][64];

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bit comparison of builds of libjdsp.so on the overlap-add chains (GPU box only):
+"""Bit comparison of builds of libjdsp.so on the overlap-add, denoise and n-microphone MVDR chains (GPU box only):
     python tools/ab_bits.py build/variants/parent.so jeicyboodsp_amd/libjdsp.so ...
 Every library runs in a fresh child process (JDSP_LIB) over the same seeded inputs and prints one SHA-256 per case over
 the raw bytes of every output: int16, the float32 before the cast, the flushed tail and the recompute count where the
@@ -339,6 +339,58 @@ def denoise_streams(eng):
         d.close()
 
 
+def mvdrn(eng):
+    """The n-microphone MVDR, stream and batch.  Stream: a 40-block scene in calls of 1 + 11 + 28 blocks of 512 samples
+    (the carried block, the carried covariance and version 0 of a later call), at both loadings (0: a singular lead, NaN
+    frames) and both frame lengths (the 512-point path shares the update kernel); a steering of fractional delays; and
+    quiet runs of 129 and 300 estimation frames in one call (two and three events per chunk).  Batch: the
+    oracle-per-utterance batch, quiet runs around the chunk length P between two ordinary utterances, the fractional
+    steering, loading 0, and a batch with gaps on planes wider than their samples."""
+    import numpy as np
+    import torch
+    import mvdrn_batch_cases as K
+    from mvdrn_cases import steering_delays
+
+    def stream(name, pcm, delays, loading, n_fft, cuts):
+        h = eng.mvdr_multi(pcm.shape[0], delays, loading, n_fft)
+        outs, at = [], 0
+        for c in cuts:
+            outs += list(h.process(pcm[:, K.B * at:K.B * (at + c)], want_precast=True))
+            at += c
+        h.close()
+        return "mvdrn %s, %d mics, %d-point, loading %g, calls %s" % (name, pcm.shape[0], n_fft, loading, list(cuts)), digest(*outs)
+
+    for n_fft, n_mics in ((1024, 2), (1024, 3), (1024, 8), (512, 3), (512, 8)):
+        pcm, _, delays = K.array_scene(40 + n_mics, n_mics, 40)
+        for loading in (K.LOADING, 0.0):
+            yield stream("array_scene", pcm, delays, loading, n_fft, (1, 11, 28))
+    pcm = K.array_scene(48, 8, 40)[0]
+    yield stream("array_scene steering_frac", pcm, steering_delays("steering_frac", 8), K.LOADING, 1024, (1, 11, 28))
+    for n_events in (129, 300):
+        pcm = K.events_run(n_events, n_events)
+        for n_fft in (1024, 512):
+            yield stream("events_run %d" % n_events, pcm, K.delays_of(3), K.LOADING, n_fft, (pcm.shape[1] // K.B,))
+
+    def batch(name, utts, delays, loading, gaps=None, wider=0):
+        pcm, counts, first = K.pack(utts, gaps, pad=8 if wider else 0)
+        planes = torch.zeros(pcm.shape[0], pcm.shape[1] + wider, dtype=torch.int16).cuda()
+        planes[:, :pcm.shape[1]] = torch.from_numpy(pcm)
+        h = eng.mvdr_multi(pcm.shape[0], delays, loading)
+        outs = h.process_batch(planes[:, :pcm.shape[1]], counts, first, want_precast=True, want_flags=True)
+        h.close()
+        return "mvdrn_batch %s, %d mics x %d utterances, loading %g" % (name, pcm.shape[0], len(utts), loading), digest(*outs)
+
+    for n_mics in (3, 8):
+        yield batch("oracle_batch_utts", K.oracle_batch_utts(n_mics), K.delays_of(n_mics), K.LOADING)
+    for n_events in (K.P - 1, K.P, K.P + 1, 2 * K.P + 1):
+        utts = [K.utterance(1, 3, 12), K.events_run(n_events, n_events), K.utterance(2, 3, 12)]
+        yield batch("events_run %d" % n_events, utts, K.delays_of(3), K.LOADING)
+    utts = K.oracle_batch_utts(3)
+    yield batch("steering_frac", utts, steering_delays("steering_frac", 3), K.LOADING)
+    yield batch("oracle_batch_utts", utts, K.delays_of(3), 0.0)
+    yield batch("gaps, chan_stride + 64", utts, K.delays_of(3), K.LOADING, gaps=2 * np.arange(len(utts)), wider=64)
+
+
 def child():
     import jeicyboodsp_amd
     eng = jeicyboodsp_amd.Engine(0)
@@ -361,7 +413,7 @@ def child():
         print("%s\t%.1f" % (c["name"], statistics.median(t[5:])))
         d.close()
     else:
-        for chain in (synthesis, masking, batches, streams, denoise):
+        for chain in (synthesis, masking, batches, streams, denoise, mvdrn):
             for name, sha in chain(eng):
                 print("%s\t%s" % (name, sha), flush=True)
     eng.close()
