@@ -42,7 +42,8 @@
  *         jdsp_stftmask_streams_dev / _streams_flush_dev / _streams_reset_dev and jdsp_istft_streams_dev /
  *         _streams_flush_dev / _streams_reset_dev, and jdsp_denoise_streams_dev / jdsp_denoise_streams_reset_dev
  *         (their *_reserve: jdsp_denoise_streams_reserve), and jdsp_binaural_render_dev /
- *         jdsp_binaural_streams_reset_dev (jdsp_binaural_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
+ *         jdsp_binaural_streams_reset_dev (jdsp_binaural_streams_reserve), and jdsp_mvdrn_streams_dev /
+ *         jdsp_mvdrn_streams_reset_dev (jdsp_mvdrn_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
  *         replay (or eager call) before it left, exactly as another eager call would.  Replay as often as wanted.
  *       Class H, state the host carries (which ping-pong copy is current, the stream position, passed to the kernels
  *         as arguments): jdsp_istft_process_dev / _flush_dev, jdsp_stftmask_process_dev / _flush_dev,
@@ -78,7 +79,8 @@ extern "C" {
  *    analysis and synthesis entries jdsp_stft_half_batch* and jdsp_istft_batch* added;
  *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
  *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added;
- *    live binaural rendering jdsp_binaural_* added; the batched n-microphone MVDR entries jdsp_mvdrn_batch* added
+ *    live binaural rendering jdsp_binaural_* added; the batched n-microphone MVDR entries jdsp_mvdrn_batch* added;
+ *    the live n-microphone MVDR streams jdsp_mvdrn_streams* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -1013,6 +1015,88 @@ int jdsp_mvdrn_batch_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stride
 int jdsp_mvdrn_batch(jdsp_mvdrn *h, const int16_t *pcm_host, long chan_stride, long n_samples,
                      const int64_t *sample_first_host, const int64_t *block_first_host, long n_utts,
                      int16_t *out_host, float *precast_host, uint8_t *flags_host);      /* host path, synchronous */
+
+/* LIVE STREAMS on the n-microphone MVDR handle: n_streams independent streams of jdsp_mvdrn in the handle, next to its
+ * own one, whose state (the per-bin covariance, the last block of every microphone, whether that block was quiet, the
+ * counts of blocks and of estimation frames) lives ON THE DEVICE and is carried from call to call.  One call advances any subset of them by a ragged
+ * chunk of new blocks each, in one launch sequence of six launches whatever the number of chunks.  The handle's own
+ * _process stream and the _batch entries are neither read nor written, the three workspaces are kept apart, and the
+ * three may be interleaved on the same handle.  1024-point handles only: on an n_fft = 512 handle every entry here
+ * returns JDSP_EINVAL with a text, as the batch entries do.  (Vocabulary: jdsp_denoise_streams_*, above.)
+ *   - A CHUNK is what one stream contributes to one call.  Chunk c belongs to stream stream_id[c] and holds B_c =
+ *     block_first[c + 1] - block_first[c] NEW blocks (>= 0) of 512 samples per microphone, microphone m's at
+ *     pcm[m chan_stride + sample_first[c] .. + 512 B_c): jdsp_mvdrn_batch_dev's layout with chunks for utterances, plus
+ *     stream_id, and its alignment rules: pcm 16-byte aligned, chan_stride a multiple of 8, sample_first even, the int64
+ *     arrays 8-byte, out and precast 4-byte aligned.  The handle keeps the history it needs: the caller never presents
+ *     a block twice.
+ *   - EMISSION IS TIME-ALIGNED, as in the batch.  A stream's block with index i (0-based, counted over all its calls)
+ *     emits iff i >= 1: the frame [first 511 samples of block i - 1 | block i | 0], written at the block's own place,
+ *     out[sample_first[c] + 512 b .. + 512) for block b of chunk c; precast (the same samples before the (short) cast)
+ *     likewise.  out and precast are single planes.  The only block never written is block 0 of a stream's life; nothing
+ *     outside the spans is read or written.  Non-finite samples -- before the stream's first estimation frame, and with
+ *     loading == 0 before n_mics of them -- are the non-finite value in precast and 0 in out.  With loading == 0 this is
+ *     a RULE here: a sum of fewer than n_mics outer products is singular by rank, the stream counts its estimation
+ *     frames, and until there are n_mics of them the weights are NaN wherever the stream is cut.  _process and the
+ *     batch leave such a matrix to the elimination's rounding, which may give finite, meaningless samples instead
+ *     (observed: the block of the second estimation frame on 3 microphones); nothing is promised between them there.
+ *   - ESTIMATION FRAMES.  Block i is one iff blocks i and i - 1 are both quiet and both in the stream, so whether the
+ *     stream's last block was quiet is part of what it carries.  The covariance is the running sum of X X^H / 1024 over
+ *     them, carried in FP64.  A chunk's estimation frames are walked ONE AFTER ANOTHER from the carried matrix, whatever
+ *     their number: the chunk's blocks before its first one use the weights of the matrix carried in (a fresh stream's
+ *     is zero: the non-finite weights of a fresh handle, row 0 of the batch), and every estimation frame adds one set.
+ *     A LONG CHUNK IS THEREFORE SERIAL, about 3.6 us per estimation frame on one wave per eight bins: these entries are
+ *     for the short chunks of live delivery, and a recording belongs to jdsp_mvdrn_batch.
+ *   - CUT INDEPENDENCE, BIT FOR BIT: a stream's out, its finite precast samples, which samples are finite, its flags
+ *     and its carried covariance do not depend on how its blocks are cut into chunks and calls -- one block per call
+ *     counts, and so does a cut between the two quiet blocks of an estimation frame -- nor on the order of the chunks in
+ *     a call, on the stream id, on n_streams, on the other streams of the call, on gaps between the spans or on
+ *     chan_stride.  It follows from the walk: the sum is formed one frame at a time in the stream's own order wherever
+ *     the cuts fall.  A promise, compared as bytes (tests/test_mvdrn_streams_gpu.py).
+ *   - AGAINST THE ORACLE AND THE BATCH.  A stream's spans, concatenated over its calls, are held to the oracle's stream
+ *     of all its blocks at _process's bars (precast within 1e-5 of the stream's peak, int16 within 1 LSB, the same
+ *     samples finite, flags equal).  Against jdsp_mvdrn_batch of ONE utterance of all its blocks the int16 and the
+ *     finite float samples are equal as bytes while the utterance has at most 128 estimation frames: both then add one
+ *     frame at a time from zero through the same code (loading > 0; at loading 0 from the n_mics-th estimation frame
+ *     on, see above).  Beyond 128 the batch regroups its sums and only the bars are
+ *     promised.  Sign and payload of a NaN in precast are not part of any comparison between different kernels.
+ *   - A stream with no chunk in a call, or with a chunk of 0 blocks, is not touched.
+ *   - jdsp_mvdrn_streams_reserve(h, n_streams, max_blocks_total) is the only call that allocates, and it synchronises.
+ *     All streams start fresh; calling it again discards every stream.  Before it the other entries return JDSP_EINVAL
+ *     with a text.  Per stream 533,516 bytes of state, each part held once: the covariance [513][8][8] complex FP64
+ *     (525,312), the last block of 8 microphones (8,192), the count (8) and a word with the quiet bit and the
+ *     estimation frames so far, saturated at 8 (4).  Per call a workspace for
+ *     max_blocks_total blocks: per block, as jdsp_mvdrn_batch_reserve, one spectrum set and one weight set, (n_mics + 8)
+ *     x 513 x 8 bytes (65.7 KB at 8 microphones), and 9 bytes of flag, weight-row index and event list; per stream one
+ *     more weight set (32.8 KB: every chunk's first row solves the matrix carried in) and 4 bytes.  The weight table of
+ *     a call has n_blocks_total + n_chunks rows.  A call beyond the reservation is JDSP_EINVAL.
+ *   - jdsp_mvdrn_streams_dev and jdsp_mvdrn_streams_reset_dev only enqueue on the context's stream: no allocation, no
+ *     host synchronisation, no host read of the arrays.  Graph-capturable, class D (Conventions): n_chunks / n_ids,
+ *     n_blocks_total, chan_stride and the pointers are baked; ids, offsets and PCM are read at replay, and every replay
+ *     advances the named streams from where they stand.  Checked on the host: n_chunks <= n_streams, n_blocks_total <=
+ *     the reservation, the alignment.  The caller's contract on the device: ids in [0, n_streams) and distinct within a
+ *     call; block_first[0] = 0, non-decreasing, block_first[n_chunks] = n_blocks_total; sample_first even; the spans
+ *     disjoint and inside every plane and the outputs.
+ *   - flags [n_blocks_total] uint8: the VAD decision of every block on microphone 0, in concatenated block order.  Any
+ *     of the three output pointers may be NULL; with all of them NULL the state advances exactly as with them.
+ *     n_chunks == 0 or n_blocks_total == 0 launches nothing and changes nothing.  reset_dev: the n_ids listed streams
+ *     fresh again; stream_id_dev NULL: all of them.
+ *   - jdsp_mvdrn_streams (host pointers, synchronous) checks all of that, duplicate ids and overlapping spans included,
+ *     with sample_first ascending as in jdsp_mvdrn_batch, and on a violation returns JDSP_EINVAL with a jdsp_last_error
+ *     text and leaves every stream as it was.  pcm is n_mics planes chan_stride >= n_samples apart; out and precast are
+ *     n_samples long and ZERO wherever the device entry would not write.
+ *   - jdsp_mvdrn_streams_state: blocks_seen [n_ids] int64 and cov [n_ids][513][8][8] complex as interleaved doubles in
+ *     the handle's own layout (row, column; zeros for a fresh or reset stream).  Synchronises; either may be NULL. */
+int jdsp_mvdrn_streams_reserve(jdsp_mvdrn *h, long n_streams, long max_blocks_total);
+int jdsp_mvdrn_streams_reset_dev(jdsp_mvdrn *h, const int64_t *stream_id_dev, long n_ids);   /* NULL: all */
+int jdsp_mvdrn_streams_dev(jdsp_mvdrn *h, const int16_t *pcm_dev, long chan_stride, const int64_t *stream_id_dev,
+                           const int64_t *sample_first_dev, const int64_t *block_first_dev, long n_chunks,
+                           long n_blocks_total, int16_t *out_dev, float *precast_dev, uint8_t *flags_dev);
+int jdsp_mvdrn_streams(jdsp_mvdrn *h, const int16_t *pcm_host, long chan_stride, long n_samples,
+                       const int64_t *stream_id_host, const int64_t *sample_first_host,
+                       const int64_t *block_first_host, long n_chunks,
+                       int16_t *out_host, float *precast_host, uint8_t *flags_host);       /* host path, synchronous */
+int jdsp_mvdrn_streams_state(jdsp_mvdrn *h, const int64_t *stream_id_host, long n_ids,
+                             int64_t *blocks_seen_host, double *cov_host);   /* synchronises; either may be NULL */
 
 /* ---- MFCC ---------------------------------------------------------------------- */
 /* MFCCFeatureExtraction_auto_version1.cpp.  The #defines at :23-33 become a runtime

@@ -178,6 +178,11 @@ def _load():
         "jdsp_mvdrn_batch_reserve": (i, [vp, l, l]),
         "jdsp_mvdrn_batch_dev": (i, [vp, vp, l, vp, vp, l, l, vp, vp, vp]),
         "jdsp_mvdrn_batch": (i, [vp, vp, l, l, vp, vp, l, vp, vp, vp]),
+        "jdsp_mvdrn_streams_reserve": (i, [vp, l, l]),
+        "jdsp_mvdrn_streams_reset_dev": (i, [vp, vp, l]),
+        "jdsp_mvdrn_streams_dev": (i, [vp, vp, l, vp, vp, vp, l, l, vp, vp, vp]),
+        "jdsp_mvdrn_streams": (i, [vp, vp, l, l, vp, vp, vp, l, vp, vp, vp]),
+        "jdsp_mvdrn_streams_state": (i, [vp, vp, l, vp, vp]),
         "jdsp_stft_half_i16_dev": (i, [vp, vp, l, vp, l]),
         "jdsp_stft_i16_dev": (i, [vp, vp, l, i, i, vp]),
         "jdsp_stft_half_batch_dev": (i, [vp, vp, vp, vp, l, l, i, vp, l]),

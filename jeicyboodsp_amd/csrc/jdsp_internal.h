@@ -521,6 +521,35 @@ int launch_mvdrn_batch(hipStream_t s, const short *pcm, long chan_stride, int n_
                        const long long *block_first, long n_utts, long n_blocks, const double *w_vad, const double2 *steer,
                        double loading, const float2 *table, const MvnBatchView &ws, unsigned char *flags, short *out,
                        float *precast);
+// mvdrn_live_kernels.hip
+// The live streams of a jdsp_mvdrn handle as a kernel sees them (jdsp_mvdrn_streams_*, include/jdsp.h), and the
+// workspace of one delivery of up to n blocks in up to n_streams chunks.  Everything a stream carries is held ONCE
+// (DESIGN.md 3.13): its covariance is read and written by the one wave that walks its eight bins, and the carried
+// blocks, the count and the carried word are written by the delivery's last launch, which nothing of the delivery follows.
+// Bytes per stream: 525,312 covariance + 8,192 carried blocks + 8 + 4 = 533,516.
+struct MvnLive {
+    double2 *cov;          // [n_streams][513][64] the running sum, the handle's own layout
+    short *prev;           // [n_streams][8][512] the stream's last block of every microphone
+    long long *seen;       // [n_streams] blocks delivered so far
+    int *word;             // [n_streams] bit 0: the stream's last block was quiet; above it its estimation frames so
+                           // far, saturated at 8 (0 for a fresh stream)
+    long n_streams;
+    unsigned char *code;   // [n] the VAD's decision per block of the concatenated axis
+    int *row;              // [n] estimation frames of its chunk at or before each block: its weight row in the chunk
+    int *events;           // [n] chunk c's estimation frames as blocks of the chunk, from block_first[c] on
+    int *ev_n;             // [n_streams] their number, per chunk
+    float2 *spec;          // [n][n_mics][513] spectra of the estimation frames, chunk c's from row block_first[c] on
+    float2 *weights;       // [n + n_streams][8][513] chunk c's rows from block_first[c] + c on: the carried matrix, then
+                           // one per estimation frame
+};
+// the chunks of live streams: VAD, plan, event spectra, update, apply and the state; flags, out and precast may each be
+// NULL (the state advances all the same).  Enqueues only.
+int launch_mvdrn_live(hipStream_t s, const short *pcm, long chan_stride, int n_mics, const long long *stream_id,
+                      const long long *sample_first, const long long *block_first, long n_chunks, long n_blocks,
+                      const double *w_vad, const double2 *steer, double loading, const float2 *table, const MvnLive &lv,
+                      unsigned char *flags, short *out, float *precast);
+// the n_ids listed streams fresh again
+int launch_mvdrn_live_reset(hipStream_t s, const long long *stream_id, long n_ids, const MvnLive &lv);
 // pitch_kernels.hip
 int launch_pitch(hipStream_t s, const short *pcm, long n_blocks, const short *prev_block, const float2 *table, int *arg,
                  float *rmax, float *autocorr);
@@ -822,4 +851,14 @@ struct jdsp_mvdrn {
         jdsp::DevBuf<double2> chunk;
         long cap_blocks = -1, cap_utts = -1;
     } bws;
+    // sized by jdsp_mvdrn_streams_reserve: n_streams live streams and the workspace of one delivery (jdsp::MvnLive has
+    // the shapes); apart from the handle's own stream and from the batch workspace
+    struct LiveWs {
+        long n_streams = 0, cap_blocks = 0;   // n_streams 0: not reserved
+        jdsp::DevBuf<char> state;             // covariances, carried blocks, counts and quiet bits in one allocation
+        jdsp::DevBuf<unsigned char> code;
+        jdsp::DevBuf<int> row, events, ev_n;
+        jdsp::DevBuf<float2> spec, weights;
+        jdsp::MvnLive view = {};
+    } lws;
 };

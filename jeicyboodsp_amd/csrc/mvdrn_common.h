@@ -1,5 +1,5 @@
-// mvdrn_common.h -- the device code the n-microphone MVDR kernels of a stream (mvdrn_kernels.hip) and of a batch of
-// ragged utterances (mvdrn_batch_kernels.hip) share as functions: the 513-bin spectrum of a frame and its store, complex
+// mvdrn_common.h -- the device code the n-microphone MVDR kernels of a stream (mvdrn_kernels.hip), of a batch of
+// ragged utterances (mvdrn_batch_kernels.hip) and of live streams (mvdrn_live_kernels.hip) share as functions: the 513-bin spectrum of a frame and its store, complex
 // FP64 on (re, im) pairs, the covariance row update and its sum over an event range, and the emit of a beamformed block.
 // Each is called once per kernel, with what differs between a stream and a batch (addresses, chunk lookup) left to the
 // caller.  The two long bodies, the walk with its solve and the beamformed frame, are shared as text:

@@ -1,5 +1,6 @@
 // mvdrn_frame_body.h -- the beamformed frame of one block, the one text of it: a FRAGMENT of a kernel's body, included
-// once in mvdrn_apply_pairs_kernel (mvdrn_kernels.hip) and once in mvnb_apply_kernel (mvdrn_batch_kernels.hip), not a
+// once in mvdrn_apply_pairs_kernel (mvdrn_kernels.hip), once in mvnb_apply_kernel (mvdrn_batch_kernels.hip) and once in
+// mvnl_apply_kernel (mvdrn_live_kernels.hip), not a
 // header; text and not a function for mvdrn_walk_body.h's reason (as a function the batch kernel's products conj(w) X
 // and their sums came out with src0 and src1 exchanged, which shows where the weights are NaN).
 //

@@ -1,5 +1,6 @@
 // mvdrn_walk_body.h -- the covariance walk and its solve, the one text of it: a FRAGMENT of a kernel's body, included
-// once in mvdrn_update_kernel (mvdrn_kernels.hip) and once in mvnb_update_kernel (mvdrn_batch_kernels.hip), not a header.
+// once in mvdrn_update_kernel (mvdrn_kernels.hip), once in mvnb_update_kernel (mvdrn_batch_kernels.hip) and once in
+// mvnl_update_kernel (mvdrn_live_kernels.hip), not a header.
 //
 // Why not a function.  As `__device__ __forceinline__ mvn_update_walk(...)` both kernels kept their resources and every
 // opcode count, and every finite output bit; but the compiler simplifies a function on its own before it inlines it, the

@@ -1245,6 +1245,97 @@ class MvdrMulti(_Child):
             res.append(flags[:n_total])
         return res[0] if len(res) == 1 else tuple(res)
 
+    # ---- live streams: n independent streams in the handle, advanced a chunk each by one call (jdsp_mvdrn_streams_*)
+    def open_streams(self, n_streams, max_blocks_total):
+        """Gives the handle n_streams live streams, all fresh, and the workspace of calls of up to max_blocks_total
+        blocks (jdsp_mvdrn_streams_reserve): the only call of the live entries that allocates, and it synchronises.
+        533,516 bytes of state per stream.  Calling it again discards every live stream's state."""
+        self.eng._ck(L.jdsp_mvdrn_streams_reserve(self._h, int(n_streams), int(max_blocks_total)))
+        self.n_streams = int(n_streams)
+        self._streams_torch = None      # the kind of the last process_streams() input
+        self._streams_key = None
+
+    def process_streams(self, pcm, stream_ids, block_counts, chunk_sample_first=None, want_precast=False,
+                        want_flags=False, out=None):
+        """One call over live streams (jdsp_mvdrn_streams; open_streams first): chunk c continues the live stream
+        stream_ids[c] with block_counts[c] >= 0 NEW blocks of 512 samples per microphone, at chunk_sample_first[c] of
+        every plane of pcm int16 [n_mics, n_samples] (even, ascending, disjoint; None: back to back,
+        sharding.denoise_batch_layout).  Ids are distinct within a call.  torch CUDA (the device entry on torch's
+        current stream; rows may be strided by a multiple of 8 samples) or numpy (the host entry).  Returns int16
+        [n_samples], TIME-ALIGNED with pcm: every block is beamformed with the block before it, carried from the
+        stream's last call where it is the chunk's first, and lies where it lies in pcm; block 0 of a stream's life
+        (sharding.mvdrn_stream_written) and everything outside the spans is zero, or is left as it was in `out` when
+        given on the device path.  A stream's result does not depend, bit for bit, on how its blocks are cut into
+        chunks and calls.  With want_precast / want_flags a tuple follows the same order: float32 samples before the
+        cast, uint8 VAD decisions of microphone 0 [sum B_c] in concatenated block order."""
+        from .sharding import denoise_batch_layout
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        counts = np.ascontiguousarray(block_counts, np.int64).reshape(-1)
+        assert ids.size == counts.size, "one block count per chunk"
+        packed, block_first, _ = denoise_batch_layout(counts, self.block)
+        if chunk_sample_first is None:
+            sample_first = packed
+        else:
+            sample_first = np.ascontiguousarray(chunk_sample_first, np.int64).reshape(-1)
+            assert sample_first.size == ids.size
+        assert pcm.ndim == 2 and pcm.shape[0] == self.n_mics
+        n_chunks, n_total, n_samples = ids.size, int(block_first[-1]), int(pcm.shape[1])
+        dev = pcm.device if _is_torch(pcm) else None
+        self._streams_torch = dev
+        if dev is not None:
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and (pcm.stride(1) == 1 or n_samples == 0)
+            stride = int(pcm.stride(0)) if n_total else 0       # without a block nothing is read
+            assert n_chunks == 0 or int((sample_first + counts * self.block).max()) <= n_samples
+            key = (ids.tobytes(), sample_first.tobytes(), counts.tobytes(), dev)
+            if self._streams_key != key:
+                self._streams_dev = tuple(torch.from_numpy(a).to(dev) for a in (ids, sample_first, block_first))
+                self._streams_key = key
+            d_ids, d_sample, d_block = self._streams_dev
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            stride = n_samples
+        out = _batch_out(n_samples, np.int16, dev, out)
+        pre = _batch_out(n_samples, np.float32, dev) if want_precast else None
+        flags = _batch_out(n_total, np.uint8, dev) if want_flags else None
+        if dev is not None:
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_mvdrn_streams_dev(self._h, _vp(pcm), stride, _vp(d_ids), _vp(d_sample), _vp(d_block),
+                                                  n_chunks, n_total, _vp(out), _vp(pre), _vp(flags)))
+        else:
+            self.eng._ck(L.jdsp_mvdrn_streams(self._h, _vp(pcm), stride, n_samples, _vp(ids), _vp(sample_first),
+                                              _vp(block_first), n_chunks, _vp(out), _vp(pre), _vp(flags)))
+        res = [out[:n_samples]]
+        if want_precast:
+            res.append(pre[:n_samples])
+        if want_flags:
+            res.append(flags[:n_total])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def reset_streams(self, stream_ids=None):
+        """The listed live streams fresh again, or all of them with None (jdsp_mvdrn_streams_reset_dev; enqueue-only)."""
+        if stream_ids is None:
+            if self._streams_torch is not None:
+                self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_mvdrn_streams_reset_dev(self._h, None, 0))
+            return
+        import torch
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        dev = self._streams_torch if self._streams_torch is not None else torch.device("cuda", self.eng.device)
+        d_ids = torch.from_numpy(ids).to(dev)
+        self.eng._use_torch_stream()
+        self.eng._ck(L.jdsp_mvdrn_streams_reset_dev(self._h, _vp(d_ids), ids.size))
+        self._reset_args = d_ids                                # alive until the stream has run the call
+
+    def streams_state(self, stream_ids, want_cov=False):
+        """blocks seen int64 [n_ids] of the listed live streams and, with want_cov, their carried covariances
+        complex128 [n_ids, 513, 8, 8] (row, column; zeros for a fresh stream) (jdsp_mvdrn_streams_state; synchronises)."""
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        seen = np.zeros(max(ids.size, 1), np.int64)
+        cov = np.zeros((max(ids.size, 1), 513, 8, 8), np.complex128) if want_cov else None
+        self.eng._ck(L.jdsp_mvdrn_streams_state(self._h, _vp(ids), ids.size, _vp(seen), _vp(cov)))
+        return (seen[:ids.size], cov[:ids.size]) if want_cov else seen[:ids.size]
+
 
 class _OlaStream(_Child):
     """What Istft and StftMask share, the overlap-add output stream behind both handles: a subclass names its C entry

@@ -269,6 +269,27 @@ def denoise_stream_emitted(blocks_seen, block_counts):
     return counts - np.maximum(0, np.minimum(counts, 2 - seen))
 
 
+def mvdrn_stream_written(blocks_seen, block_counts):
+    """Where the chunks of one MvdrMulti.process_streams call start writing (jdsp_mvdrn_streams): emission is
+    time-aligned and the only block never written is block 0 of a stream's life, so the chunk of B_c = block_counts[c]
+    blocks of a stream that had seen N = blocks_seen[c] blocks writes its blocks from index 1 on when N == 0 and
+    B_c > 0, and from index 0 on otherwise.  Both arguments are per-chunk sequences of equal length (a scalar
+    blocks_seen stands for all chunks).  Returns numpy int64 [n_chunks].  The layout of the chunks is
+    denoise_batch_layout's with chunks for utterances; a live stream lives on one device, so over ranks the stream ids
+    are split with stream_shard.  Negative values or lengths that differ: ValueError."""
+    import numpy as np
+    counts = np.asarray(block_counts, dtype=np.int64).reshape(-1)
+    seen = np.asarray(blocks_seen, dtype=np.int64)
+    if seen.ndim == 0:
+        seen = np.full(counts.shape, int(seen), np.int64)
+    seen = seen.reshape(-1)
+    if seen.size != counts.size:
+        raise ValueError("one blocks_seen value per chunk")
+    if np.any(counts < 0) or np.any(seen < 0):
+        raise ValueError("blocks_seen and block counts must be >= 0")
+    return ((seen == 0) & (counts > 0)).astype(np.int64)
+
+
 def stftmask_batch_shard(frame_counts, rank, world):
     """Batched fused STFT masking (StftMask.process_batch) over `world` ranks: whole utterances per rank, contiguous,
     balanced by frame count (utterance_shard); an utterance is a stream of its own, so there is no halo and no

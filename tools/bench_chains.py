@@ -521,6 +521,69 @@ def main():
         for m in (m_a, m_b, m_c):
             m.close()
         del x, o16
+    if on("mvdrn_streams"):
+        # Live n-microphone MVDR streams (jdsp_mvdrn_streams_dev): 1,000 live streams x 4 blocks per delivery, 8
+        # microphones, loading 1e-3, the first two blocks of every chunk quiet (one estimation frame per chunk and
+        # delivery).  Timed three ways in this process, in alternated rounds: (a) the live entry, every call a further
+        # delivery to all streams; (b) one jdsp_mvdrn handle per stream and jdsp_mvdrn_process_dev per delivery, from
+        # ctypes with the handles made beforehand, over the first 100 streams and scaled by 10; (c)
+        # jdsp_mvdrn_batch_dev over the same chunks as fresh utterances, the stateless floor.  The PCM (33 MB over the
+        # eight planes) rotates over 6 copies; (a) moves the covariances on top, which no cache holds.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        n_mics, n_streams, per, part = 8, 1000, 4, 100
+        counts = np.full(n_streams, per, np.int64)
+        sample_first, block_first, n_samples = sharding.denoise_batch_layout(counts, 512)
+        total = int(block_first[-1])
+        gen = torch.Generator(device="cuda").manual_seed(1000)
+        sigma = torch.full((total,), 3000.0, device="cuda")
+        sigma[torch.from_numpy((block_first[:-1, None] + np.arange(2)[None, :]).ravel()).cuda()] = 30.0
+        x = torch.empty((n_mics, n_samples), dtype=torch.int16, device="cuda")
+        for m in range(n_mics):
+            draft = torch.randn((total, 512), device="cuda", generator=gen) * sigma[:, None]
+            x[m] = draft.round_().clamp_(-32768, 32767).to(torch.int16).view(-1)
+        del draft, sigma
+        xr = rot(x)
+        o16 = torch.empty(n_samples, dtype=torch.int16, device="cuda")
+        m_a, m_c = eng.mvdr_multi(n_mics, None, 1e-3), eng.mvdr_multi(n_mics, None, 1e-3)
+        m_a.open_streams(n_streams, total)
+        m_c.reserve_batch(total, n_streams)
+        singles = [eng.mvdr_multi(n_mics, None, 1e-3) for _ in range(part)]
+        ids = np.arange(n_streams, dtype=np.int64)
+        po = o16.data_ptr()
+        eng._use_torch_stream()
+
+        def loop():
+            px = xr().data_ptr()
+            for u, h in enumerate(singles):
+                off = 2 * int(sample_first[u])
+                L.jdsp_mvdrn_process_dev(h._h, C.c_void_p(px + off), n_samples, per, C.c_void_p(po + off), None, None)
+
+        live = lambda: m_a.process_streams(xr(), ids, counts, sample_first, out=o16)  # noqa: E731
+        batch = lambda: m_c.process_batch(xr(), counts, sample_first, out=o16)  # noqa: E731
+        loop()                                                  # every handle's first call: its workspace, no emission
+        ms_a, ms_c, ms_b = timed_alternated([live, batch, loop], [a.iters, a.iters, 4], rounds=5)
+        ms_b *= n_streams / part
+        assert m_a.streams_state([0, n_streams - 1]).min() > per * a.iters
+        state_bytes = 2 * 513 * 64 * 16                         # a stream's covariance, read and written per delivery
+        what = "%d live streams x %d blocks per delivery, 8 microphones, one estimation frame per chunk" % (n_streams, per)
+        inp = "rotated over 6 copies: %.1f MB of PCM per call" % (2e-6 * n_samples * n_mics)
+        nbytes, flops = 8 * 1024 + 1024, 9 * 5 * 512 * 9 + 9 * 512 * 14 + 1024 * 8 * 8
+        report("mvdrn_streams", ms_a, total, "blocks", nbytes + state_bytes // per, flops,
+               "(a) jdsp_mvdrn_streams_dev: %s; %.2f x the batch of fresh utterances (c), %.4f of the per-stream loop (b); "
+               "on top of (c) it moves each stream's covariance in and out, %.2f GB per call (%d bytes per block)"
+               % (what, ms_a / ms_c, ms_a / ms_b, 1e-9 * state_bytes * n_streams, state_bytes // per), inp=inp)
+        report("mvdrn_streams_per_stream_loop", ms_b, total, "blocks", nbytes, flops,
+               "(b) the same delivery as %d x jdsp_mvdrn_process_dev, one handle per stream, from ctypes: measured over "
+               "the first %d streams and scaled by %d; %.1f x the live entry" % (n_streams, part, n_streams // part, ms_b / ms_a),
+               inp=inp)
+        report("mvdrn_streams_fresh_batch", ms_c, total, "blocks", nbytes, flops,
+               "(c) jdsp_mvdrn_batch_dev over the same %d chunks as fresh utterances (no carried state: another result)"
+               % n_streams, inp=inp)
+        for m in [m_a, m_c] + singles:
+            m.close()
+        del x, xr, o16
     if on("stftmask_streams") or on("istft_streams"):
         # Live streams (jdsp_stftmask_streams_dev, jdsp_istft_streams_dev): 10,000 live streams, every call brings each
         # of them a chunk of 4 frames, hop 256 and 512, real mask / half layout (pitch 513).  Timed three ways in this
