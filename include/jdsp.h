@@ -1051,7 +1051,7 @@ int jdsp_mvdrn_batch(jdsp_mvdrn *h, const int16_t *pcm_host, long chan_stride, l
  *     counts, and so does a cut between the two quiet blocks of an estimation frame -- nor on the order of the chunks in
  *     a call, on the stream id, on n_streams, on the other streams of the call, on gaps between the spans or on
  *     chan_stride.  It follows from the walk: the sum is formed one frame at a time in the stream's own order wherever
- *     the cuts fall.  A promise, compared as bytes (tests/test_mvdrn_streams_gpu.py).
+ *     the cuts fall.  A promise, compared as bytes (tests/test_mvdrn_streams_gpu.py, tests/test_mvdrn_streams_hard_gpu.py).
  *   - AGAINST THE ORACLE AND THE BATCH.  A stream's spans, concatenated over its calls, are held to the oracle's stream
  *     of all its blocks at _process's bars (precast within 1e-5 of the stream's peak, int16 within 1 LSB, the same
  *     samples finite, flags equal).  Against jdsp_mvdrn_batch of ONE utterance of all its blocks the int16 and the
