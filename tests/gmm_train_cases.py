@@ -2,7 +2,11 @@
 Gaussian clusters (covariance eigenvalues a factor of 2 apart, random axes), far from the origin and from each other,
 so that no k-means decision or kept eigen-subspace sits near a tie.  The first 16 vectors of every file come from
 clusters 0,0,0,0,1,1,1,1,2,... so that the k-means start (vectors 0, 4, 8, 12: Train:120-124) has one vector per
-cluster."""
+cluster.
+
+overlapping_models and wide_models leave that safety on purpose (several k-means passes, rows with several selection
+bits, soft E-step weights, wide spectra): the scenes built on them (HARD_SCENES) are held to their regimes and to the
+restatement's margins in tests/test_gmm_train_hard_cpu.py."""
 import numpy as np
 
 
@@ -20,6 +24,87 @@ def class_models(rng, n_classes):
             lam = rng.uniform(4.0, 16.0) * 2.0 ** -np.arange(12.0)
             roots[c, k] = q * np.sqrt(lam)
     return centres, roots
+
+
+def _cluster_models(rng, n_classes, offset_norm, sep, lam):
+    """Per class one offset of norm offset_norm, four centres at offset + sep * unit vector, every covariance
+    Q diag(lam) Q' with its own random orthogonal Q."""
+    centres = np.empty((n_classes, 4, 12))
+    roots = np.empty((n_classes, 4, 12, 12))
+    for c in range(n_classes):
+        offset = rng.normal(0.0, 1.0, 12)
+        offset *= offset_norm / np.linalg.norm(offset)
+        for k in range(4):
+            d = rng.normal(0.0, 1.0, 12)
+            centres[c, k] = offset + sep * d / np.linalg.norm(d)
+            q, _ = np.linalg.qr(rng.normal(0.0, 1.0, (12, 12)))
+            roots[c, k] = q * np.sqrt(lam)
+    return centres, roots
+
+
+def overlapping_models(rng, n_classes, sep, lam_hi, ratio):
+    """Clusters that overlap (class_models' sit 40 apart with spreads of at most 4): centres `sep` from a class
+    offset of norm 30, eigenvalues lam_hi * ratio**-j.  k-means then moves vectors between clusters over several
+    passes (rows carry more than one selection bit), and the E-step's weights are soft."""
+    return _cluster_models(rng, n_classes, 30.0, sep, lam_hi * ratio ** -np.arange(12.0))
+
+
+def wide_models(rng, n_classes, decades, offset, sep):
+    """Covariance eigenvalues 100 * 10**(-decades j / 11), j = 0..11, on centres at norm `offset` from the origin: a
+    wide spectrum whose small end is far below the square of the data's size."""
+    return _cluster_models(rng, n_classes, offset, sep, 100.0 * 10.0 ** (-decades * np.arange(12.0) / 11.0))
+
+
+# The scenes of tests/test_gmm_train_hard_{cpu,gpu}.py: name -> (models, arguments, seed, classes, files per class,
+# shortest and longest file).  One default_rng(seed) draws the models and then the files.
+HARD_SCENES = {
+    "overlap6": ("overlapping", dict(sep=6.0, lam_hi=9.0, ratio=1.5), 1, 6, 3, 300, 700),
+    "overlap3": ("overlapping", dict(sep=3.0, lam_hi=9.0, ratio=1.3), 3, 6, 3, 300, 700),
+    "wide60": ("wide", dict(decades=6, offset=1000.0, sep=60.0), 1, 3, 2, 300, 500),
+    "wide15": ("wide", dict(decades=6, offset=1000.0, sep=15.0), 2, 3, 2, 300, 500),
+}
+
+# file lengths at and around the trainer's 64-frame tiles and 256-frame rounds
+TILE_EDGE_LENGTHS = [64, 65, 128, 255, 256, 257, 512, 513, 63, 127, 192, 320, 768, 1024, 100, 64, 256, 512]
+
+
+def hard_scene(name):
+    """-> feats, file_first, file_class, n_classes, models"""
+    kind, kw, seed, n_classes, fpc, lo, hi = HARD_SCENES[name]
+    rng = np.random.default_rng(seed)
+    models = (overlapping_models if kind == "overlapping" else wide_models)(rng, n_classes, **kw)
+    feats, ff, fc = make_files(rng, n_classes, fpc, lambda r: r.integers(lo, hi), models=models)
+    return feats, ff, fc, n_classes, models
+
+
+def unreachable_frame(name, cls, row=20):
+    """hard_scene(name) with one vector of class cls's second file moved to a cluster centre + 1e4 in every feature:
+    every exponent of its densities is below -1e6, so all four are exactly 0 (no denormal in between) and its weights
+    are 0/0.  -> feats, file_first, file_class, n_classes"""
+    feats, ff, fc, n_classes, (centres, _) = hard_scene(name)
+    f = int(np.nonzero(fc == cls)[0][1])
+    feats[ff[f] + row] = centres[cls, 0] + 1e4
+    return feats, ff, fc, n_classes
+
+
+def held_out(name, seed, files_per_class=3, lo=100, hi=300):
+    """files of hard_scene(name)'s models that the training never saw"""
+    n_classes, models = hard_scene(name)[3:]
+    return make_files(np.random.default_rng(seed), n_classes, files_per_class, lambda r: r.integers(lo, hi),
+                      models=models)
+
+
+def tile_edge_files(seed):
+    """6 separated classes x 3 files whose lengths are TILE_EDGE_LENGTHS, handed out in make_files' shuffled order."""
+    rng = np.random.default_rng(seed)
+    lengths = iter(TILE_EDGE_LENGTHS)
+    return make_files(rng, 6, 3, lambda r: next(lengths))
+
+
+def many_files(seed):
+    """2 separated classes x 150 files of 64..160 vectors: more files than one 256-file window of the trainer."""
+    rng = np.random.default_rng(seed)
+    return make_files(rng, 2, 150, lambda r: r.integers(64, 161))
 
 
 def draw_file(rng, centres, roots, n):

@@ -12,6 +12,16 @@ Besides the records it reports, for fixture hygiene, how close the data came to 
   eig_gap     smallest relative gap between eigenvalues 8 and 9 of every decomposition (it decides the kept subspace)
   eig_gap_in  smallest relative gap between adjacent eigenvalues among the top 8 (it decides how well eigenvectors
               compare; the parity tests scale their eigenvector tolerance by its inverse)
+and which regime the data reached (a fixture built to reach a regime asserts these):
+  passes_min, passes_max  fewest and most k-means passes of any class
+  multi_bit_rows          per k-means run, in the order run: rows that end with more than one selection bit (also kept
+                          in the class's state)
+  soft_min                smallest per-file fraction of E-step rows (the three iterations together) whose largest
+                          weight is below 1 - 1e-6
+  zero_density            frames whose four weighted densities sum to exactly 0 (their weights are 0/0)
+
+train(), em(), params() and sorted_eigen() take eigh=: another symmetric eigen-solver with numpy.linalg.eigh's
+interface (ascending eigenvalues, eigenvectors in columns), for measuring how much the records depend on the solver.
 """
 import numpy as np
 
@@ -30,6 +40,11 @@ class Margins:
         self.cost_gap = np.inf
         self.eig_gap = np.inf
         self.eig_gap_in = np.inf
+        self.passes_min = np.inf
+        self.passes_max = 0
+        self.multi_bit_rows = []
+        self.soft_min = np.inf
+        self.zero_density = 0
 
 
 class ClassState:
@@ -45,14 +60,15 @@ class ClassState:
         self.selected = np.zeros(4, np.int64)
         self.kmeans_cost = 0.0
         self.files = 0
+        self.multi_bit_rows = 0
 
 
-def sorted_eigen(cov, margins=None):
+def sorted_eigen(cov, margins=None, eigh=None):
     """Train:214-238 (= :483-506): the top PCA_LEN eigenpairs, ranked by the number of strictly larger eigenvalues;
     a rank nobody has keeps the previous pick.  A matrix with a non-finite entry gives NaN eigenpairs."""
     if not np.all(np.isfinite(cov)):
         return np.full(PCA_LEN, np.nan), np.full((FEATURE_LEN, PCA_LEN), np.nan)
-    lam, vec = np.linalg.eigh(cov)
+    lam, vec = (eigh or np.linalg.eigh)(cov)
     rank = [int((lam[j] < lam).sum()) for j in range(FEATURE_LEN)]          # Train:218-224
     arg, picks = 0, []
     for j in range(PCA_LEN):                                                # Train:226-238
@@ -133,30 +149,38 @@ def kmeans(X, st, max_passes, margins):
                 d = X[sel[:, j]] - st.mean[j]
                 st.cov[j] = (d.T @ d) / float(cnt[j])
         st.kmeans_passes, st.kmeans_capped, st.selected, st.kmeans_cost = count, int(go_on), cnt.astype(np.int64), cost
+        st.multi_bit_rows = int((sel.sum(axis=1) > 1).sum())
+        margins.passes_min, margins.passes_max = min(margins.passes_min, count), max(margins.passes_max, count)
+        margins.multi_bit_rows.append(st.multi_bit_rows)
         return
 
 
-def em(X, st, margins, iterations=3):
+def em(X, st, margins, iterations=3, eigh=None):
     """EmAlgorithmBasedGmmParameter (Train:255-340): three iterations (Train:333); the print-only log-likelihood pass
     (Train:326-332) is not computed."""
     n = len(X)
+    soft = 0
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         for _ in range(iterations):
             P = np.empty((n, NUM_OF_MIXTURE))
             for k in range(NUM_OF_MIXTURE):                                 # Train:270-276
-                lam, E = sorted_eigen(st.cov[k], margins)
+                lam, E = sorted_eigen(st.cov[k], margins, eigh)
                 P[:, k] = probability(X, st.mean[k], lam, E) * st.alpa[k]
             s = P[:, 0] + P[:, 1] + P[:, 2] + P[:, 3]
             W = P / s[:, None]                                              # Train:277-280
+            soft += int((W.max(axis=1) < 1.0 - 1e-6).sum())
+            margins.zero_density += int((s == 0.0).sum())
             nkey = st.alpa + W.sum(axis=0)                                  # Train:289-293
             st.alpa = nkey / n                                              # Train:294
             st.mean = (st.mean + W.T @ X) / nkey[:, None]                   # Train:297-304
             for k in range(NUM_OF_MIXTURE):                                 # Train:305-325
                 d = X - st.mean[k]
                 st.cov[k] = ((d * W[:, k:k + 1]).T @ d) / nkey[k]
+    if iterations:
+        margins.soft_min = min(margins.soft_min, soft / float(iterations * n))
 
 
-def train(feats, file_first, file_class, n_classes, states=None, max_passes=10000, margins=None):
+def train(feats, file_first, file_class, n_classes, states=None, max_passes=10000, margins=None, eigh=None):
     """main()'s file loop (Train:87-146) for files in order; `states` carries on from earlier calls."""
     states = states if states is not None else [ClassState() for _ in range(n_classes)]
     margins = margins if margins is not None else Margins()
@@ -172,18 +196,18 @@ def train(feats, file_first, file_class, n_classes, states=None, max_passes=1000
             kmeans(X, st, max_passes, margins)                              # Train:127
             st.alpa = np.full(NUM_OF_MIXTURE, 1.0 / NUM_OF_MIXTURE)         # Train:129-131
             st.seen = True
-        em(X, st, margins)                                                  # Train:138
+        em(X, st, margins, eigh=eigh)                                       # Train:138
         st.files += 1
     return states, margins
 
 
-def params(states, margins=None):
+def params(states, margins=None, eigh=None):
     """PCADiagonalizeCovarianceMatrix (Train:456-518) of each state -> TRAIN_PARAM records (the states unchanged)."""
     out = np.zeros(len(states), TRAIN_PARAM)
     for c, st in enumerate(states):
         out[c]["alpa"] = st.alpa
         for k in range(NUM_OF_MIXTURE):
-            lam, E = sorted_eigen(st.cov[k], margins)
+            lam, E = sorted_eigen(st.cov[k], margins, eigh)
             mean = np.zeros(FEATURE_LEN)
             mean[:PCA_LEN] = st.mean[k] @ E                                 # Train:508-511
             cov = st.cov[k].copy()

@@ -76,12 +76,12 @@ def test_gmm_train_parity_ragged(eng, ragged):
     tr.close()
 
 
-def _trained(eng, feats, ff, fc, cuts=None, threads=256, by_class=False, dev=False):
+def _trained(eng, feats, ff, fc, cuts=None, threads=256, by_class=False, dev=False, n_classes=25):
     import torch
-    tr = eng.gmm_trainer(25)
+    tr = eng.gmm_trainer(n_classes)
     tr.set_option("threads_per_class", threads)
     if by_class:
-        for c in range(25):
+        for c in range(n_classes):
             idx = np.nonzero(fc == c)[0]
             sub = np.concatenate([feats[ff[f]:ff[f + 1]] for f in idx])
             lens = ff[idx + 1] - ff[idx]
