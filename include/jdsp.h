@@ -21,7 +21,7 @@
  *     handle is warm, i.e. after one call of that entry point (constant tables
  *     are built on first use) and after the matching *_reserve() where the
  *     entry has a workspace (jdsp_denoise_reserve, jdsp_denoise_batch_reserve, jdsp_mvdrn_batch_reserve,
- *     jdsp_hmm_reserve, jdsp_fastconv_reserve, jdsp_*_streams_reserve).
+ *     jdsp_reverb_batch_reserve, jdsp_hmm_reserve, jdsp_fastconv_reserve, jdsp_*_streams_reserve).
  *     The plain entry points take HOST pointers, copy in, run, copy out and
  *     synchronise.
  *   - GRAPH CAPTURE.  A warm "_dev" call can be captured into a hipGraph (bench.py
@@ -31,10 +31,11 @@
  *       Baked and live arguments, all classes: every SCALAR (n_frames, n_blocks, n_utts, n_chunks, n_ids,
  *       n_frames_total, n_blocks_total, pitches, hops, methods, orders) and every POINTER is baked into the graph at
  *       capture.  Read at replay: the CONTENTS of the buffers, and with them the device-side offset and id arrays
- *       (sample_first, frame_first, block_first, utt_first, frame_start, stream_id).  A replay may therefore deal the same
+ *       (sample_first, frame_first, block_first, utt_first, frame_start, stream_id, ir, gain).  A replay may therefore deal the same
  *       n_frames_total among the same n_utts / n_chunks differently, move the spans, and name other streams.
  *       Class S, stateless: jdsp_stft_i16_dev, jdsp_stft_half_i16_dev, jdsp_stft_i16_f64_dev, jdsp_stft_half_batch_dev,
- *         jdsp_istft_batch_dev, jdsp_stftmask_batch_dev, jdsp_denoise_batch_dev, jdsp_mvdrn_batch_dev, jdsp_mfcc_frames_dev,
+ *         jdsp_istft_batch_dev, jdsp_stftmask_batch_dev, jdsp_denoise_batch_dev, jdsp_mvdrn_batch_dev,
+ *         jdsp_reverb_batch_dev, jdsp_mfcc_frames_dev,
  *         jdsp_pitch_autocorr_dev, jdsp_pitch_lag_dev, jdsp_lpc_dev, jdsp_gmm_score_dev, jdsp_hmm_viterbi_dev,
  *         jdsp_fft_process_f64_dev.  Every replay recomputes from what the buffers hold at that time and equals an
  *         eager call on the same contents, bit for bit.  Replay as often as wanted.
@@ -80,7 +81,7 @@ extern "C" {
  *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
  *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added;
  *    live binaural rendering jdsp_binaural_* added; the batched n-microphone MVDR entries jdsp_mvdrn_batch* added;
- *    the live n-microphone MVDR streams jdsp_mvdrn_streams* added
+ *    the live n-microphone MVDR streams jdsp_mvdrn_streams* added; batched reverberation jdsp_reverb_* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -729,6 +730,73 @@ int jdsp_fastconv_process_dev(jdsp_fastconv *h, const int16_t *pcm_dev, long n_b
                               float *precast_dev, long *n_out_blocks);
 int jdsp_fastconv_process(jdsp_fastconv *h, const int16_t *pcm_host, long n_blocks, int16_t *out_host,
                           float *precast_host, long *n_out_blocks);
+
+/* ---- batched reverberation: ragged utterances, each with its own room response ------------- */
+/* NOT a reference function: the reference convolves one stream with one fixed filter set (jdsp_fastconv_* above).  This
+ * is the same uniformly partitioned overlap-save as jdsp_fastconv's 8192-point path, as the stateless batch entry the
+ * other chains have: thousands of ragged utterances in one launch sequence, each convolved with its own long impulse
+ * response out of a bank, at its own gain.  Its oracle is the FP64 direct convolution of tests/reverb_ref.py.
+ *   - THE BANK.  taps: n_irs responses x n_taps real taps (double, host), 1 <= n_taps <= 7680, 1 <= n_irs <= 16384;
+ *     anything else is JDSP_EINVAL with a text.  A response is cut into P = ceil(n_taps / 512) partitions of 512 taps
+ *     (jdsp_reverb_n_part, 1 <= P <= 15); each, zero-padded to 1024 points, is transformed once in FP64 on the device
+ *     as jdsp_fastconv_create does and kept as an FP32 row of the bins 0..512 at a pitch of 520: 4,160 P bytes per
+ *     response, 62,400 at P = 15.  Blocks are 512 samples (jdsp_reverb_block_len).
+ *   - THE LAYOUT is jdsp_denoise_batch_dev's: utterance u has B_u = block_first[u + 1] - block_first[u] >= 0 blocks of
+ *     512 samples at pcm[sample_first[u]]; sample_first even; the spans disjoint, ascending and inside the buffers;
+ *     block_first[0] = 0, non-decreasing, block_first[n_utts] = n_blocks_total.  ir[u] (int32, in [0, n_irs)) names the
+ *     utterance's response and gain[u] (float32) its gain; gain NULL: every gain 1, bit for bit the same as an array
+ *     of 1.0f.
+ *   - SEMANTICS, in exact arithmetic, for 0 <= t < 512 B_u:  y_u[t] = gain[u] sum_k h[ir[u]][k] x_u[t - k],  x_u silent
+ *     before the utterance's first sample.  The output is as long as the input, time-aligned, and written at the same
+ *     offsets: out[sample_first[u] + t].  THE TAIL IS NOT APPENDED: a caller who wants the reverberation that rings on
+ *     after the utterance's last sample appends P blocks of zeros to the utterance.  Nothing outside the spans is read
+ *     or written; the analysis of an utterance's first block uses 512 zeros in front of it, not what precedes the
+ *     span in pcm.
+ *   - OUTPUT.  out_f32: the float value; out_i16: its (short) cast (truncate toward zero, keep the low 16 bits, as
+ *     every chain here).  Either may be NULL; with both NULL nothing is done.
+ *   - THE ARITHMETIC, fixed (csrc/reverb_kernels.hip): one 1024-point FP32 forward transform per block, of [previous
+ *     block | block], rectangular window, bins 0..512 to a workspace row; output block c of an utterance is the second
+ *     half of the inverse transform of sum_{p = 0}^{min(c, P - 1)} X[c - p] H_p, accumulated in FP32 with p ascending --
+ *     an order that depends on c and P alone, not on where the wave, the workgroup or the utterance stands; rows in
+ *     front of the utterance's first contribute nothing; the inverse's 1/1024 and the gain are ONE FP32 multiply per
+ *     sample, by gain[u] * 2^-10 (itself one FP32 product).
+ *   - GUARANTEES (tests/test_reverb_batch_gpu.py, bars: tests/reverb_cases.py).  (1) per utterance, with w the FP64
+ *     value, x the samples, g the gain and h the response: every float sample within 1e-5 max(max|w|, 0.05 max|x| |g|
+ *     sum|h|), and every sample of output block e within 1e-5 max(max|w| over the blocks e - 1 .. e + 1, 0.05 |g| sum|h|
+ *     max|x| over the 512 (P + 1) input samples that end with block e, silence before the utterance) -- the bars the
+ *     partitioned jdsp_fastconv path holds with the same arithmetic.  Where a bar is 0 the output is exact zeros
+ *     (silence, gain 0).  The int16 IS the cast of the float, also past +-32768 (the low 16 bits), and within +-1 of
+ *     the cast of the FP64 value modulo 65536.  (2) INDEPENDENCE: an utterance's bytes, in both outputs, do not depend
+ *     on its place in the batch or in pcm, on the other utterances, their responses or gains, on the order of the
+ *     utterances, or on how the batch is split into calls.
+ *   - jdsp_reverb_batch_dev only enqueues on the context's stream (a plan launch of one workgroup, the analysis, the
+ *     multiply-accumulate / inverse): no allocation, no host synchronisation, no host read of any array; every grid
+ *     comes from the scalars n_utts and n_blocks_total, which must equal block_first[n_utts].  Graph-capturable, class
+ *     S (Conventions): the scalars and the pointers are baked; pcm, the offsets, ir and gain are read at replay.  The
+ *     caller's contract on the device is the layout above; pcm and out_i16 16-byte, out_f32 and the offset arrays
+ *     8-byte, ir and gain 4-byte aligned (checked).  ir values are clamped into [0, n_irs) on the device instead of
+ *     reading outside the bank.  n_utts == 0, n_blocks_total == 0 and batches of empty utterances succeed and launch
+ *     nothing.
+ *   - Its workspace comes from jdsp_reverb_batch_reserve, the only call that allocates (and synchronises): 4,160
+ *     bytes per reserved block (the spectrum rows) and 8 (n_utts + 1) bytes of plan (the workgroups per utterance,
+ *     prefixed).  It only grows.  A non-empty batch before it, or one larger than the reservation in blocks or
+ *     utterances, is JDSP_EINVAL with a text.
+ *   - jdsp_reverb_batch (host pointers, synchronous; pcm and the outputs are n_samples long) reserves on demand,
+ *     checks the offsets as jdsp_denoise_batch does, and ir in range and the gains finite; a violation is JDSP_EINVAL
+ *     with a jdsp_last_error text.  Its outputs are ZERO outside the spans. */
+typedef struct jdsp_reverb jdsp_reverb;
+int jdsp_reverb_create(jdsp_ctx *ctx, const double *taps /* [n_irs][n_taps] */, int n_irs, int n_taps, jdsp_reverb **out);
+int jdsp_reverb_destroy(jdsp_reverb *h);
+int jdsp_reverb_n_irs(const jdsp_reverb *h);
+int jdsp_reverb_n_part(const jdsp_reverb *h);
+int jdsp_reverb_block_len(const jdsp_reverb *h);   /* 512 */
+int jdsp_reverb_batch_reserve(jdsp_reverb *h, long n_blocks, long n_utts);
+int jdsp_reverb_batch_dev(jdsp_reverb *h, const int16_t *pcm_dev, const int64_t *sample_first_dev,
+                          const int64_t *block_first_dev, const int32_t *ir_dev, const float *gain_dev /* may be NULL: 1 */,
+                          long n_utts, long n_blocks_total, int16_t *out_i16_dev, float *out_f32_dev);
+int jdsp_reverb_batch(jdsp_reverb *h, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
+                      const int64_t *block_first_host, const int32_t *ir_host, const float *gain_host, long n_utts,
+                      int16_t *out_i16_host, float *out_f32_host);
 
 /* ---- binaural rendering: live sources mixed per ear in the spectrum ------------------------- */
 /* NOT a reference function: the reference convolves one mono stream with one fixed filter set

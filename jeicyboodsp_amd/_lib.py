@@ -131,6 +131,14 @@ def _load():
         "jdsp_fastconv_blocks_out": (l, [vp, l]),
         "jdsp_fastconv_process_dev": (i, [vp, vp, l, vp, vp, C.POINTER(l)]),
         "jdsp_fastconv_process": (i, [vp, vp, l, vp, vp, C.POINTER(l)]),
+        "jdsp_reverb_create": (i, [vp, vp, i, i, C.POINTER(vp)]),
+        "jdsp_reverb_destroy": (i, [vp]),
+        "jdsp_reverb_n_irs": (i, [vp]),
+        "jdsp_reverb_n_part": (i, [vp]),
+        "jdsp_reverb_block_len": (i, [vp]),
+        "jdsp_reverb_batch_reserve": (i, [vp, l, l]),
+        "jdsp_reverb_batch_dev": (i, [vp, vp, vp, vp, vp, vp, l, l, vp, vp]),
+        "jdsp_reverb_batch": (i, [vp, vp, l, vp, vp, vp, vp, l, vp, vp]),
         "jdsp_binaural_create": (i, [vp, vp, i, i, C.POINTER(vp)]),
         "jdsp_binaural_destroy": (i, [vp]),
         "jdsp_binaural_n_dirs": (i, [vp]),

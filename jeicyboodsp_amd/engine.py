@@ -99,6 +99,10 @@ class Engine(_Handle):
     def fastconv(self, taps, n_fft):
         return FastConv(self, taps, n_fft)
 
+    def reverb(self, taps):
+        """Batched reverberator (jdsp_reverb) over the bank taps [n_irs, n_taps] of impulse responses."""
+        return Reverb(self, taps)
+
     def binaural(self, hrirs):
         """Live binaural renderer (jdsp_binaural) over the bank hrirs [n_dirs, 2, n_taps]."""
         return Binaural(self, hrirs)
@@ -939,6 +943,67 @@ class FastConv(_Child):
                                              (out if out.size else dummy).ctypes.data_as(C.c_void_p),
                                              pre.ctypes.data_as(C.c_void_p) if (want_precast and pre.size) else None, None))
         return (out, pre) if want_precast else out
+
+
+class Reverb(_Child):
+    """Batched reverberation (jdsp_reverb; NOT a reference function: the partitioned overlap-save convolver of
+    FastConv over a batch of ragged utterances, each with its own response out of a bank and its own gain).
+    taps: [n_irs, n_taps] (or [n_taps]) float64, n_taps <= 7680.  Blocks are self.block = 512 samples."""
+    _destroy = staticmethod(lambda h: L.jdsp_reverb_destroy(h))
+
+    def __init__(self, engine, taps):
+        self.eng = engine
+        taps = np.ascontiguousarray(np.atleast_2d(np.asarray(taps, np.float64)))
+        assert taps.ndim == 2, "taps: [n_irs, n_taps]"
+        self.n_irs, self.n_taps = taps.shape
+        h = C.c_void_p()
+        engine._ck(L.jdsp_reverb_create(engine._h, _vp(taps), self.n_irs, self.n_taps, C.byref(h)))
+        self._h = h
+        self.block = L.jdsp_reverb_block_len(h)
+        self.n_part = L.jdsp_reverb_n_part(h)
+        engine._children.append(self)
+
+    def reserve_batch(self, n_blocks, n_utts):
+        """Sizes the workspace of process_batch's device path (jdsp_reverb_batch_reserve): the only call of the batch
+        entries that allocates.  Call it before capturing process_batch in a graph."""
+        self.eng._ck(L.jdsp_reverb_batch_reserve(self._h, int(n_blocks), int(n_utts)))
+
+    def process_batch(self, pcm, sample_first, block_first, ir, gain=None, want_f32=False, out=None, out_f32=None):
+        """A batch of independent utterances in one launch sequence (jdsp_reverb_batch): utterance u is the
+        block_first[u + 1] - block_first[u] blocks of self.block samples at pcm[sample_first[u]] (the layout of
+        Denoiser.process_batch; sharding.denoise_batch_layout packs one), convolved with response ir[u] of the bank at
+        gain[u] (None: 1), silence in front of it.  pcm: int16; sample_first [n_utts], block_first [n_utts + 1], ir
+        [n_utts] and gain [n_utts]: host sequences.  torch CUDA pcm (the device entry on torch's current stream, the
+        four arrays copied over first and the workspace reserved on demand: a graph captures the C entry on arrays of its
+        own, after reserve_batch) or numpy (the host entry, which also checks the arrays).  Returns int16 of pcm's length, TIME-ALIGNED with pcm; outside
+        the spans it is zero, or left as it was in `out` / `out_f32` when given on the device path.  With want_f32:
+        (out, float32 values before the cast)."""
+        assert pcm.ndim == 1
+        n_samples = int(pcm.shape[0])
+        sample_first = np.ascontiguousarray(sample_first, np.int64).reshape(-1)
+        block_first = np.ascontiguousarray(block_first, np.int64).reshape(-1)
+        ir = np.ascontiguousarray(ir, np.int32).reshape(-1)
+        gain = None if gain is None else np.ascontiguousarray(gain, np.float32).reshape(-1)
+        n_utts = ir.size
+        assert sample_first.size == n_utts and block_first.size == n_utts + 1 and (gain is None or gain.size == n_utts)
+        dev = pcm.device if _is_torch(pcm) else None
+        o16 = _batch_out(n_samples, np.int16, dev, out)
+        o32 = _batch_out(n_samples, np.float32, dev, out_f32) if (want_f32 or out_f32 is not None) else None
+        if dev is not None:
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            n_total = int(block_first[-1])
+            d_first, d_block, d_ir = (torch.from_numpy(a).to(dev) for a in (sample_first, block_first, ir))
+            d_gain = None if gain is None else torch.from_numpy(gain).to(dev)
+            self.reserve_batch(n_total, n_utts)                 # a no-op once sized
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_reverb_batch_dev(self._h, _vp(pcm), _vp(d_first), _vp(d_block), _vp(d_ir), _vp(d_gain),
+                                                 n_utts, n_total, _vp(o16), _vp(o32)))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            self.eng._ck(L.jdsp_reverb_batch(self._h, _vp(pcm), n_samples, _vp(sample_first), _vp(block_first), _vp(ir),
+                                             _vp(gain), n_utts, _vp(o16), _vp(o32)))
+        return (o16[:n_samples], o32[:n_samples]) if want_f32 else o16[:n_samples]
 
 
 class Binaural(_Child):

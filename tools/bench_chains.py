@@ -521,6 +521,89 @@ def main():
         for m in (m_a, m_b, m_c):
             m.close()
         del x, o16
+    if on("reverb_batch"):
+        # Batched reverberation (jdsp_reverb_batch_dev): 2,000 seeded utterances of 50..300 blocks of 512 (even counts: the
+        # convolver's block is 1024), packed, each with its own response out of a bank of 256 x 7,169 taps, gains 1.
+        # Timed three ways in this process, in alternated rounds, every C entry called through ctypes with its arguments
+        # computed beforehand: (a) the batch entry; (b) 256 jdsp_fastconv handles (n_fft 8192, partitioned), one per
+        # response, jdsp_fastconv_reset + jdsp_fastconv_process_dev per utterance on its response's handle, over the
+        # first 200 utterances and scaled by 10 -- each call emits 7 blocks of 1024 fewer than it is fed (the
+        # reference's silent head), so (b) does a little less; (c) ONE jdsp_fastconv stream of the same total block
+        # count with one response.  The PCM rotates over 3 copies (one copy is already past the 256 MiB Infinity Cache).
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        n_utts, part, n_irs, n_taps = 2000, 200, 256, 7169
+        rs = np.random.default_rng(2900)
+        counts = 2 * rs.integers(25, 151, n_utts).astype(np.int64)
+        sample_first, block_first, n_samples = sharding.denoise_batch_layout(counts, 512)
+        total = int(block_first[-1])
+        taps = rs.normal(size=(n_irs, n_taps)) * np.exp(-np.arange(n_taps) / 1500.0) * 0.05
+        ir_h = rs.integers(0, n_irs, n_utts).astype(np.int32)
+        gen = torch.Generator(device="cuda").manual_seed(2900)
+        x = (torch.randn(n_samples, device="cuda", generator=gen) * 3000.0).round_().clamp_(-32768, 32767).to(torch.int16)
+        ins = [x] if a.warm else [x, x.clone(), x.clone()]
+        o16 = torch.empty(n_samples, dtype=torch.int16, device="cuda")
+        d_first, d_bf = torch.from_numpy(sample_first).cuda(), torch.from_numpy(block_first).cuda()
+        d_ir = torch.from_numpy(ir_h).cuda()
+        rv = eng.reverb(taps)
+        rv.reserve_batch(total, n_utts)
+        used = sorted(set(ir_h[:part].tolist()))
+        convs = {i: eng.fastconv(taps[i], 8192) for i in range(n_irs)}
+        one = eng.fastconv(taps[0], 8192)
+        for c in convs.values():
+            assert L.jdsp_fastconv_reserve(c._h, int(counts[:part].max()) // 2) == 0
+        assert L.jdsp_fastconv_reserve(one._h, total // 2) == 0
+        po = o16.data_ptr()
+        args_a = [(rv._h, C.c_void_p(t.data_ptr()), C.c_void_p(d_first.data_ptr()), C.c_void_p(d_bf.data_ptr()),
+                   C.c_void_p(d_ir.data_ptr()), None, n_utts, total, C.c_void_p(po), None) for t in ins]
+        calls = [[(convs[int(ir_h[u])]._h, C.c_void_p(t.data_ptr() + 2 * int(sample_first[u])), int(counts[u]) // 2,
+                   C.c_void_p(po + 2 * int(sample_first[u])), None, None) for u in range(part)] for t in ins]
+        args_c = [(one._h, C.c_void_p(t.data_ptr()), total // 2, C.c_void_p(po), None, None) for t in ins]
+        turn = [0, 0, 0]
+        eng._use_torch_stream()
+
+        def batch():
+            turn[0] += 1
+            L.jdsp_reverb_batch_dev(*args_a[turn[0] % len(ins)])
+
+        def loop():
+            turn[1] += 1
+            for p in calls[turn[1] % len(ins)]:
+                L.jdsp_fastconv_reset(p[0])
+                L.jdsp_fastconv_process_dev(*p)
+
+        def stream():
+            turn[2] += 1
+            L.jdsp_fastconv_reset(one._h)
+            L.jdsp_fastconv_process_dev(*args_c[turn[2] % len(ins)])
+
+        assert L.jdsp_reverb_batch_dev(*args_a[0]) == 0 and L.jdsp_fastconv_process_dev(*calls[0][0]) == 0
+        assert L.jdsp_fastconv_process_dev(*args_c[0]) == 0
+        ms_a, ms_c, ms_b = timed_alternated([batch, stream, loop], [a.iters, a.iters, 2], rounds=5)
+        ms_b *= n_utts / part
+        what = "%d ragged utterances, %d blocks of 512 (%d..%d each), %d responses x %d taps (P = %d), gains 1" % (
+            n_utts, total, counts.min(), counts.max(), n_irs, n_taps, rv.n_part)
+        inp = "rotated over %d copies of %.0f MB (from HBM)" % (len(ins), 2e-6 * n_samples)
+        ws = 4160 * total + 8 * (n_utts + 1)
+        nbytes = 1024 + 1024
+        flops = 2 * (5 * 512 * 9 + 512 * 14) + 8 * 513 * rv.n_part
+        report("reverb_batch", ms_a, total, "blocks", nbytes, flops,
+               "(a) jdsp_reverb_batch_dev: %s; workspace %.2f GB, bank %.1f MB; %.2f x the single stream (c), %.4f of the "
+               "per-utterance loop (b)" % (what, 1e-9 * ws, 1e-6 * 4160 * rv.n_part * n_irs, ms_a / ms_c, ms_a / ms_b), inp=inp)
+        report("reverb_batch_per_utterance_loop", ms_b, total, "blocks", nbytes, flops,
+               "(b) the same batch as %d x (jdsp_fastconv_reset + jdsp_fastconv_process_dev), one jdsp_fastconv handle per "
+               "response, from ctypes with precomputed arguments: measured over the first %d utterances (%d of the 256 handles) and "
+               "scaled by %d; every call emits 7 blocks of 1024 fewer than it is fed; %.1f x the batch entry"
+               % (n_utts, part, len(used), n_utts // part, ms_b / ms_a), inp=inp)
+        report("reverb_batch_single_stream", ms_c, total, "blocks", nbytes, flops,
+               "(c) ONE jdsp_fastconv stream of the same %d blocks of 512 with one response, jdsp_fastconv_reset + one "
+               "jdsp_fastconv_process_dev" % total, inp=inp)
+        rv.close()
+        one.close()
+        for c in convs.values():
+            c.close()
+        del x, ins, o16
     if on("mvdrn_streams"):
         # Live n-microphone MVDR streams (jdsp_mvdrn_streams_dev): 1,000 live streams x 4 blocks per delivery, 8
         # microphones, loading 1e-3, the first two blocks of every chunk quiet (one estimation frame per chunk and
