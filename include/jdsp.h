@@ -21,7 +21,8 @@
  *     handle is warm, i.e. after one call of that entry point (constant tables
  *     are built on first use) and after the matching *_reserve() where the
  *     entry has a workspace (jdsp_denoise_reserve, jdsp_denoise_batch_reserve, jdsp_mvdrn_batch_reserve,
- *     jdsp_reverb_batch_reserve, jdsp_hmm_reserve, jdsp_fastconv_reserve, jdsp_*_streams_reserve).
+ *     jdsp_reverb_batch_reserve, jdsp_reverb_streams_reserve, jdsp_hmm_reserve, jdsp_fastconv_reserve,
+ *     jdsp_*_streams_reserve).
  *     The plain entry points take HOST pointers, copy in, run, copy out and
  *     synchronise.
  *   - GRAPH CAPTURE.  A warm "_dev" call can be captured into a hipGraph (bench.py
@@ -44,7 +45,8 @@
  *         _streams_flush_dev / _streams_reset_dev, and jdsp_denoise_streams_dev / jdsp_denoise_streams_reset_dev
  *         (their *_reserve: jdsp_denoise_streams_reserve), and jdsp_binaural_render_dev /
  *         jdsp_binaural_streams_reset_dev (jdsp_binaural_streams_reserve), and jdsp_mvdrn_streams_dev /
- *         jdsp_mvdrn_streams_reset_dev (jdsp_mvdrn_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
+ *         jdsp_mvdrn_streams_reset_dev (jdsp_mvdrn_streams_reserve), and jdsp_reverb_streams_dev /
+ *         jdsp_reverb_streams_reset_dev (jdsp_reverb_streams_reserve).  EVERY REPLAY ADVANCES THE STREAMS: it continues from the state the
  *         replay (or eager call) before it left, exactly as another eager call would.  Replay as often as wanted.
  *       Class H, state the host carries (which ping-pong copy is current, the stream position, passed to the kernels
  *         as arguments): jdsp_istft_process_dev / _flush_dev, jdsp_stftmask_process_dev / _flush_dev,
@@ -81,7 +83,8 @@ extern "C" {
  *    jdsp_stftmask_frames_recomputed added; the batched denoise entries jdsp_denoise_batch* added; the live-stream
  *    entries jdsp_stftmask_streams* and jdsp_istft_streams* added; the live denoise streams jdsp_denoise_streams* added;
  *    live binaural rendering jdsp_binaural_* added; the batched n-microphone MVDR entries jdsp_mvdrn_batch* added;
- *    the live n-microphone MVDR streams jdsp_mvdrn_streams* added; batched reverberation jdsp_reverb_* added
+ *    the live n-microphone MVDR streams jdsp_mvdrn_streams* added; batched reverberation jdsp_reverb_* added;
+ *    the live reverberation streams jdsp_reverb_streams* added
  *    (backward compatible: nothing before them changed).  (1: rounds 1-2.) */
 #define JDSP_ABI_VERSION 2
 
@@ -797,6 +800,81 @@ int jdsp_reverb_batch_dev(jdsp_reverb *h, const int16_t *pcm_dev, const int64_t 
 int jdsp_reverb_batch(jdsp_reverb *h, const int16_t *pcm_host, long n_samples, const int64_t *sample_first_host,
                       const int64_t *block_first_host, const int32_t *ir_host, const float *gain_host, long n_utts,
                       int16_t *out_i16_host, float *out_f32_host);
+
+/* ---- live reverberation streams: carried spectra, a response per chunk -------------------------- */
+/* NOT a reference function: jdsp_reverb_batch's arithmetic with the history kept in the handle, for callers with
+ * thousands of open streams that each deliver a few blocks per tick, each in its own room.  The vocabulary is
+ * jdsp_mvdrn_streams_*'s, the layout and the arithmetic are jdsp_reverb_batch_dev's.  P = jdsp_reverb_n_part(h).
+ *   - A CHUNK is what one stream contributes to one call: chunk c belongs to stream stream_id[c] and holds B_c =
+ *     block_first[c + 1] - block_first[c] >= 0 NEW blocks of 512 samples at pcm[sample_first[c]], with the response
+ *     ir[c] and the gain gain[c] (NULL: every gain 1) for its blocks.  The handle keeps the history: the caller never
+ *     presents a block twice.  Offsets and alignment as in jdsp_reverb_batch_dev (sample_first even; spans disjoint,
+ *     ascending, inside the buffers; block_first[0] = 0, non-decreasing, block_first[n_chunks] = n_blocks_total).
+ *   - SEMANTICS, in exact arithmetic: with x_s the concatenation of every block stream s has been given since its
+ *     reserve or reset, and the chunk's blocks the stream blocks i0 .. i0 + B_c - 1, for t inside those blocks
+ *     y[t] = gain[c] sum_k h[ir[c]][k] x_s[t - k], silence before the stream's first sample.  Every block is written,
+ *     at its own place out[sample_first[c] + 512 b ..]; nothing outside the spans is read or written.  The outputs must
+ *     not overlap pcm: the last launch of a call reads pcm again.  A stream delivered with one response and gain
+ *     throughout is the batch's utterance of all its blocks.  A change of ir or gain between chunks is a HARD SWITCH at
+ *     the chunk boundary: the new response is applied to the whole carried history.  Cross-fading is not built, nor a
+ *     flush that rings the tail out: the caller delivers P blocks of zeros.
+ *   - THE ARITHMETIC is the batch's, for stream block i: one forward transform of [block i - 1 | block i];
+ *     sum_{p = 0}^{min(i, P - 1)} X[i - p] H_p, p ascending, in one FP32 accumulator chain; the walk ends at the
+ *     stream's block 0, so the stream counts its blocks; one multiply by gain[c] 2^-10.
+ *   - CUT INDEPENDENCE, BIT FOR BIT (tests/test_reverb_streams_gpu.py).  A stream's int16 and float bytes do not depend
+ *     on how its blocks are cut into chunks and calls (one block per call included), on the order of chunks in a call,
+ *     the stream id or n_streams, on the other streams or the gaps between spans.  For a stream with one (ir, gain)
+ *     throughout they EQUAL THE BYTES jdsp_reverb_batch writes for one utterance of all its blocks; for any chunk, that
+ *     batch's output for the utterance "all blocks so far" with the chunk's (ir, gain), sliced to the chunk -- a block is
+ *     a function of i, P, the samples, the response and the gain alone.  The batch's bars and int16 rules hold as there.
+ *   - A stream with no chunk in a call, or with a chunk of 0 blocks, is not touched.  With both outputs NULL the STATE
+ *     ADVANCES exactly as with them (the batch entry does nothing then).  n_chunks == 0 or n_blocks_total == 0 launches
+ *     nothing.
+ *   - STATE, per stream, each part held once: blocks_seen (8 bytes), the last block's 512 samples (1,024 bytes), and a
+ *     ring of the last P - 1 SPECTRUM rows, the row of stream block i at slot i mod (P - 1): 4,160 (P - 1) bytes, none
+ *     at P = 1 -- 59,272 bytes per stream at P = 15.  Carrying spectra, not PCM, is the point: no forward transform is
+ *     ever repeated.  Per call: a workspace of one row (4,160 bytes) per block of max_blocks_total and a plan of
+ *     8 (n_streams + 1) bytes.
+ *   - jdsp_reverb_streams_reserve(h, n_streams, max_blocks_total) is the only call that allocates, and it synchronises;
+ *     1 <= n_streams < 2^30, 0 <= max_blocks_total <= 2^30 - 16.  All streams start fresh; calling it again discards
+ *     them.  Before it the other entries return JDSP_EINVAL with a text.  The batch workspace and the live workspace
+ *     are kept apart: jdsp_reverb_batch_dev and jdsp_reverb_streams_dev may be interleaved on one handle.
+ *   - jdsp_reverb_streams_dev and jdsp_reverb_streams_reset_dev only enqueue on the context's stream: no allocation, no
+ *     host synchronisation, no host read of any array; every grid comes from the scalars alone.  The launches of a
+ *     delivery, whatever n_chunks, one linear chain with no parallel branches: the analysis of the new blocks into the
+ *     workspace (in front of a chunk's first block stand the stream's carried samples, zeros for a fresh stream); a plan
+ *     of one workgroup (waves per chunk, prefixed) and the multiply-accumulate / inverse, in which a WAVE owns two
+ *     consecutive blocks of one chunk, walks the rows from the newest down (this chunk's from the workspace, older ones
+ *     from the ring) and reads H straight from the bank -- no response in LDS, no workgroup barrier, workgroups of 4
+ *     waves; both skipped when both outputs are NULL; and the commit, which copies the chunk's last min(B_c, P - 1) rows
+ *     into the ring and its last 512 samples into the state and adds B_c to blocks_seen.  The commit is a launch of its
+ *     own because the launches before it read exactly what it writes: stream order makes a delivery race-free with
+ *     nothing held twice.  Graph-capturable, class D (Conventions): n_chunks / n_ids, n_blocks_total and the pointers are
+ *     baked; ids, offsets, ir, gain and pcm are read at replay; every replay advances the named streams.  Checked on the
+ *     host: n_chunks <= n_streams, n_blocks_total <= the reservation, the alignment (as the batch entry's; stream_id
+ *     8-byte).  The caller's contract on the device: ids in [0, n_streams) and distinct within a call, the offsets as in
+ *     the batch; ir is clamped into [0, n_irs) on the device.  jdsp_reverb_streams_reset_dev: the listed streams fresh
+ *     (NULL: all of them).
+ *   - LONG CHUNKS.  A chunk of hundreds of blocks works, but every wave reads H again from L2 and no speed is promised
+ *     for it: recordings belong to jdsp_reverb_batch.
+ *   - jdsp_reverb_streams (host pointers, synchronous; pcm and the outputs are n_samples long) checks all of that and
+ *     also duplicate or out-of-range ids, ir out of range, non-finite gains and overlapping spans; on a violation it
+ *     returns JDSP_EINVAL with a jdsp_last_error text and LEAVES EVERY STREAM AS IT WAS.  Its outputs are ZERO outside
+ *     the spans.
+ *   - jdsp_reverb_streams_state: blocks_seen and the last block's samples (zeros for a fresh stream) of the listed
+ *     streams; it synchronises; either pointer may be NULL. */
+int jdsp_reverb_streams_reserve(jdsp_reverb *h, long n_streams, long max_blocks_total);
+int jdsp_reverb_streams_reset_dev(jdsp_reverb *h, const int64_t *stream_id_dev, long n_ids);      /* NULL: all */
+int jdsp_reverb_streams_dev(jdsp_reverb *h, const int16_t *pcm_dev, const int64_t *stream_id_dev,
+                            const int64_t *sample_first_dev, const int64_t *block_first_dev,
+                            const int32_t *ir_dev, const float *gain_dev /* may be NULL: 1 */,
+                            long n_chunks, long n_blocks_total, int16_t *out_i16_dev, float *out_f32_dev);
+int jdsp_reverb_streams(jdsp_reverb *h, const int16_t *pcm_host, long n_samples, const int64_t *stream_id_host,
+                        const int64_t *sample_first_host, const int64_t *block_first_host,
+                        const int32_t *ir_host, const float *gain_host, long n_chunks,
+                        int16_t *out_i16_host, float *out_f32_host);                              /* synchronous */
+int jdsp_reverb_streams_state(jdsp_reverb *h, const int64_t *stream_id_host, long n_ids,
+                              int64_t *blocks_seen_host, int16_t *last_block_host /* [n_ids][512] */);
 
 /* ---- binaural rendering: live sources mixed per ear in the spectrum ------------------------- */
 /* NOT a reference function: the reference convolves one mono stream with one fixed filter set

@@ -139,6 +139,11 @@ def _load():
         "jdsp_reverb_batch_reserve": (i, [vp, l, l]),
         "jdsp_reverb_batch_dev": (i, [vp, vp, vp, vp, vp, vp, l, l, vp, vp]),
         "jdsp_reverb_batch": (i, [vp, vp, l, vp, vp, vp, vp, l, vp, vp]),
+        "jdsp_reverb_streams_reserve": (i, [vp, l, l]),
+        "jdsp_reverb_streams_reset_dev": (i, [vp, vp, l]),
+        "jdsp_reverb_streams_dev": (i, [vp, vp, vp, vp, vp, vp, vp, l, l, vp, vp]),
+        "jdsp_reverb_streams": (i, [vp, vp, l, vp, vp, vp, vp, vp, l, vp, vp]),
+        "jdsp_reverb_streams_state": (i, [vp, vp, l, vp, vp]),
         "jdsp_binaural_create": (i, [vp, vp, i, i, C.POINTER(vp)]),
         "jdsp_binaural_destroy": (i, [vp]),
         "jdsp_binaural_n_dirs": (i, [vp]),

@@ -948,7 +948,8 @@ class FastConv(_Child):
 class Reverb(_Child):
     """Batched reverberation (jdsp_reverb; NOT a reference function: the partitioned overlap-save convolver of
     FastConv over a batch of ragged utterances, each with its own response out of a bank and its own gain).
-    taps: [n_irs, n_taps] (or [n_taps]) float64, n_taps <= 7680.  Blocks are self.block = 512 samples."""
+    taps: [n_irs, n_taps] (or [n_taps]) float64, n_taps <= 7680.  Blocks are self.block = 512 samples.  The same
+    arithmetic over live streams whose history the handle carries: open_streams / process_streams."""
     _destroy = staticmethod(lambda h: L.jdsp_reverb_destroy(h))
 
     def __init__(self, engine, taps):
@@ -1004,6 +1005,89 @@ class Reverb(_Child):
             self.eng._ck(L.jdsp_reverb_batch(self._h, _vp(pcm), n_samples, _vp(sample_first), _vp(block_first), _vp(ir),
                                              _vp(gain), n_utts, _vp(o16), _vp(o32)))
         return (o16[:n_samples], o32[:n_samples]) if want_f32 else o16[:n_samples]
+
+    # ---- live streams: n independent streams in the handle, advanced a chunk each by one call (jdsp_reverb_streams_*)
+    def open_streams(self, n_streams, max_blocks_total):
+        """Gives the handle n_streams live streams, all fresh, and the workspace of calls of up to max_blocks_total
+        blocks (jdsp_reverb_streams_reserve): the only call of the live entries that allocates, and it synchronises.
+        1,032 + 4,160 (n_part - 1) bytes of state per stream.  Calling it again discards every live stream's state."""
+        self.eng._ck(L.jdsp_reverb_streams_reserve(self._h, int(n_streams), int(max_blocks_total)))
+        self.n_streams = int(n_streams)
+        self._streams_torch = None      # the kind of the last process_streams() input
+        self._streams_key = None
+
+    def process_streams(self, pcm, stream_ids, block_counts, ir, gain=None, chunk_sample_first=None, want_f32=False,
+                        out=None, out_f32=None):
+        """One call over live streams (jdsp_reverb_streams; open_streams first): chunk c continues the live stream
+        stream_ids[c] with block_counts[c] >= 0 NEW blocks of self.block samples at chunk_sample_first[c] of pcm int16
+        [n_samples] (even, ascending, disjoint; None: back to back, sharding.denoise_batch_layout), convolved with
+        response ir[c] at gain[c] (None: 1) over everything the stream has been given so far.  Ids are distinct within
+        a call.  torch CUDA (the device entry on torch's current stream) or numpy (the host entry, which also checks
+        the arrays).  Returns int16 [n_samples], TIME-ALIGNED with pcm; outside the spans it is zero, or left as it was
+        in `out` / `out_f32` when given on the device path.  A stream's result does not depend, bit for bit, on how its
+        blocks are cut into chunks and calls, and with one (ir, gain) throughout it is process_batch's of the whole
+        stream as one utterance.  With want_f32: (out, float32 values before the cast)."""
+        from .sharding import denoise_batch_layout
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        counts = np.ascontiguousarray(block_counts, np.int64).reshape(-1)
+        ir = np.ascontiguousarray(ir, np.int32).reshape(-1)
+        gain = None if gain is None else np.ascontiguousarray(gain, np.float32).reshape(-1)
+        assert ids.size == counts.size == ir.size and (gain is None or gain.size == ids.size), "one entry per chunk"
+        packed, block_first, _ = denoise_batch_layout(counts, self.block)
+        if chunk_sample_first is None:
+            sample_first = packed
+        else:
+            sample_first = np.ascontiguousarray(chunk_sample_first, np.int64).reshape(-1)
+            assert sample_first.size == ids.size
+        assert pcm.ndim == 1
+        n_chunks, n_total, n_samples = ids.size, int(block_first[-1]), int(pcm.shape[0])
+        dev = pcm.device if _is_torch(pcm) else None
+        self._streams_torch = dev
+        o16 = _batch_out(n_samples, np.int16, dev, out)
+        o32 = _batch_out(n_samples, np.float32, dev, out_f32) if (want_f32 or out_f32 is not None) else None
+        if dev is not None:
+            import torch
+            assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+            assert n_chunks == 0 or int((sample_first + counts * self.block).max()) <= n_samples
+            key = (ids.tobytes(), sample_first.tobytes(), counts.tobytes(), ir.tobytes(),
+                   None if gain is None else gain.tobytes(), dev)
+            if self._streams_key != key:
+                self._streams_dev = tuple(None if a is None else torch.from_numpy(a).to(dev)
+                                          for a in (ids, sample_first, block_first, ir, gain))
+                self._streams_key = key
+            d_ids, d_sample, d_block, d_ir, d_gain = self._streams_dev
+            self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_reverb_streams_dev(self._h, _vp(pcm), _vp(d_ids), _vp(d_sample), _vp(d_block), _vp(d_ir),
+                                                   _vp(d_gain), n_chunks, n_total, _vp(o16), _vp(o32)))
+        else:
+            pcm = np.ascontiguousarray(pcm, np.int16)
+            self.eng._ck(L.jdsp_reverb_streams(self._h, _vp(pcm), n_samples, _vp(ids), _vp(sample_first), _vp(block_first),
+                                               _vp(ir), _vp(gain), n_chunks, _vp(o16), _vp(o32)))
+        return (o16[:n_samples], o32[:n_samples]) if want_f32 else o16[:n_samples]
+
+    def reset_streams(self, stream_ids=None):
+        """The listed live streams fresh again, or all of them with None (jdsp_reverb_streams_reset_dev; enqueue-only)."""
+        if stream_ids is None:
+            if self._streams_torch is not None:
+                self.eng._use_torch_stream()
+            self.eng._ck(L.jdsp_reverb_streams_reset_dev(self._h, None, 0))
+            return
+        import torch
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        dev = self._streams_torch if self._streams_torch is not None else torch.device("cuda", self.eng.device)
+        d_ids = torch.from_numpy(ids).to(dev)
+        self.eng._use_torch_stream()
+        self.eng._ck(L.jdsp_reverb_streams_reset_dev(self._h, _vp(d_ids), ids.size))
+        self._reset_args = d_ids                                # alive until the stream has run the call
+
+    def streams_state(self, stream_ids):
+        """(blocks seen int64 [n_ids], the last block's samples int16 [n_ids, 512], zeros for a fresh stream) of the
+        listed live streams (jdsp_reverb_streams_state; synchronises)."""
+        ids = np.ascontiguousarray(stream_ids, np.int64).reshape(-1)
+        seen = np.zeros(max(ids.size, 1), np.int64)
+        last = np.zeros((max(ids.size, 1), self.block), np.int16)
+        self.eng._ck(L.jdsp_reverb_streams_state(self._h, _vp(ids), ids.size, _vp(seen), _vp(last)))
+        return seen[:ids.size], last[:ids.size]
 
 
 class Binaural(_Child):

@@ -604,6 +604,111 @@ def main():
         for c in convs.values():
             c.close()
         del x, ins, o16
+    if on("reverb_streams"):
+        # Live reverberation streams (jdsp_reverb_streams_dev): 2,000 live streams warmed with P blocks each, a bank of
+        # 256 responses x 7,169 taps (P = 15), stream s on response s mod 256, `per` NEW blocks per delivery, int16 out.
+        # Timed three ways in this process, in alternated rounds, every C entry called through ctypes with its arguments
+        # computed beforehand: (a) the live entry, every call a further delivery to all streams; (b) today's route,
+        # jdsp_reverb_batch_dev over 2,000 utterances of P + per blocks (the history presented again; the repacking
+        # copy is not counted), of which per are kept; (c) the stateless floor, jdsp_reverb_batch_dev over the same
+        # per-block chunks as fresh utterances (another result).  per = 4 is the figure, 1 and 32 are recorded beside
+        # it; at per = 4, (d) one jdsp_fastconv handle (n_fft 8192, blocks of 1024) per stream in a loop of
+        # jdsp_fastconv_process_dev, over the first 100 streams and scaled by 20.  The PCM rotates over 6 copies; what
+        # (a) moves on top is each stream's ring, which no cache holds at 116 MB.
+        import ctypes as C
+        from jeicyboodsp_amd import sharding
+        from jeicyboodsp_amd._lib import lib as L
+        n_streams, n_irs, n_taps, part = 2000, 256, 7169, 100
+        rs = np.random.default_rng(3000)
+        taps = rs.normal(size=(n_irs, n_taps)) * np.exp(-np.arange(n_taps) / 1500.0) * 0.05
+        rv = eng.reverb(taps)
+        P = rv.n_part
+        ids_h = np.arange(n_streams, dtype=np.int64)
+        ir_h = (ids_h % n_irs).astype(np.int32)
+        d_ids, d_ir = torch.from_numpy(ids_h).cuda(), torch.from_numpy(ir_h).cuda()
+        gen = torch.Generator(device="cuda").manual_seed(3000)
+        vp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)   # noqa: E731
+
+        def noise(n):
+            return (torch.randn(n, device="cuda", generator=gen) * 3000.0).round_().clamp_(-32768, 32767).to(torch.int16)
+
+        eng._use_torch_stream()
+        for per in (4, 1, 32):
+            lay = {}
+            for key, nb in (("a", per), ("b", P + per), ("w", P)):
+                sf, bf, ns = sharding.denoise_batch_layout(np.full(n_streams, nb, np.int64), 512)
+                lay[key] = (torch.from_numpy(sf).cuda(), torch.from_numpy(bf).cuda(), ns, int(bf[-1]))
+            xa, xb = rot(noise(lay["a"][2])), rot(noise(lay["b"][2]))
+            o16 = torch.empty(lay["b"][2], dtype=torch.int16, device="cuda")
+            rv.open_streams(n_streams, max(lay["a"][3], lay["w"][3]))
+            rv.reserve_batch(lay["b"][3], n_streams)
+            warm = noise(lay["w"][2])
+            assert L.jdsp_reverb_streams_dev(rv._h, vp(warm), vp(d_ids), vp(lay["w"][0]), vp(lay["w"][1]), vp(d_ir), None,
+                                             n_streams, lay["w"][3], None, None) == 0
+
+            def live():
+                L.jdsp_reverb_streams_dev(rv._h, vp(xa()), vp(d_ids), vp(lay["a"][0]), vp(lay["a"][1]), vp(d_ir), None,
+                                          n_streams, lay["a"][3], vp(o16), None)
+
+            def again():
+                L.jdsp_reverb_batch_dev(rv._h, vp(xb()), vp(lay["b"][0]), vp(lay["b"][1]), vp(d_ir), None, n_streams,
+                                        lay["b"][3], vp(o16), None)
+
+            def fresh():
+                L.jdsp_reverb_batch_dev(rv._h, vp(xa()), vp(lay["a"][0]), vp(lay["a"][1]), vp(d_ir), None, n_streams,
+                                        lay["a"][3], vp(o16), None)
+
+            it = max(25 * a.iters, 100)                         # a call is 0.05 to 0.6 ms: windows of tens of ms and more
+            fns, iters = [live, again, fresh], [it, it, it]
+            if per == 4:
+                convs = [eng.fastconv(taps[int(ir_h[s])], 8192) for s in range(part)]
+                for c in convs:
+                    assert c.block == 1024 and L.jdsp_fastconv_reserve(c._h, per // 2) == 0
+                sf_h = np.arange(n_streams, dtype=np.int64) * per * 512
+
+                def loop():
+                    px, po = xa().data_ptr(), o16.data_ptr()
+                    for s, c in enumerate(convs):
+                        off = 2 * int(sf_h[s])
+                        L.jdsp_fastconv_process_dev(c._h, C.c_void_p(px + off), per // 2, C.c_void_p(po + off), None, None)
+
+                for _ in range(P):                              # past the convolver's silent head: every call emits
+                    loop()
+                fns.append(loop)
+                iters.append(2)
+            ms = timed_alternated(fns, iters, rounds=5)
+            ms_a, ms_b, ms_c = ms[:3]
+            seen = rv.streams_state([0, n_streams - 1])[0]
+            assert seen.min() > P + per * a.iters
+            total = lay["a"][3]
+            what = "%d live streams x %d new blocks per delivery, %d responses x %d taps (P = %d), gains 1" % (
+                n_streams, per, n_irs, n_taps, P)
+            inp = "rotated over 6 copies: %.1f MB of PCM per call of (a) and (c), %.1f MB of (b)" % (
+                2e-6 * lay["a"][2], 2e-6 * lay["b"][2])
+            state = 4160 * (P - 1) + 1032
+            nbytes = 1024 + 1024
+            flops = 2 * (5 * 512 * 9 + 512 * 14) + 8 * 513 * P
+            tag = "" if per == 4 else "_%dblocks" % per
+            report("reverb_streams" + tag, ms_a, total, "blocks", nbytes, flops,
+                   "(a) jdsp_reverb_streams_dev: %s; %.3f of today's route (b), %.2f x the stateless floor (c); state %d "
+                   "bytes per stream, %.1f MB in all" % (what, ms_a / ms_b, ms_a / ms_c, state, 1e-6 * state * n_streams), inp=inp)
+            report("reverb_streams_history_again" + tag, ms_b, total, "blocks", nbytes, flops,
+                   "(b) jdsp_reverb_batch_dev over %d utterances of P + %d = %d blocks, the history presented again, %d "
+                   "kept: %.2f x the transforms and accumulations; %.2f x the live entry"
+                   % (n_streams, per, P + per, per, (P + per) / per, ms_b / ms_a), inp=inp)
+            report("reverb_streams_fresh_batch" + tag, ms_c, total, "blocks", nbytes, flops,
+                   "(c) jdsp_reverb_batch_dev over the same %d chunks of %d blocks as fresh utterances (no carried state: "
+                   "another result)" % (n_streams, per), inp=inp)
+            if per == 4:
+                ms_d = ms[3] * n_streams / part
+                report("reverb_streams_fastconv_loop", ms_d, total, "blocks", nbytes, flops,
+                       "(d) the same delivery as %d x jdsp_fastconv_process_dev (n_fft 8192, 2 blocks of 1024), one handle per "
+                       "stream, from ctypes: measured over the first %d streams and scaled by %d; %.1f x the live entry"
+                       % (n_streams, part, n_streams // part, ms_d / ms_a), inp=inp)
+                for c in convs:
+                    c.close()
+            del xa, xb, o16, warm
+        rv.close()
     if on("mvdrn_streams"):
         # Live n-microphone MVDR streams (jdsp_mvdrn_streams_dev): 1,000 live streams x 4 blocks per delivery, 8
         # microphones, loading 1e-3, the first two blocks of every chunk quiet (one estimation frame per chunk and
