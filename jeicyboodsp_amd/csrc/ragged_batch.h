@@ -9,7 +9,8 @@
 // of it is uniform across the wave: it lives in scalar registers and costs neither vector registers nor LDS.
 //
 // The span walk at the end is that state behind the questions a frame loop asks: RaggedSpan, the above, walked by
-// stftmask_batch_kernel, stft_half_batch_kernel and istft_batch_kernel, and StreamSpan, a single stream -- a batch of
+// stftmask_batch_kernel, stft_half_batch_kernel, istft_batch_kernel and reverb_analysis (reverb_body.h: the batch and
+// live reverberation analysis kernels, with blocks for frames), and StreamSpan, a single stream -- a batch of
 // one span [0, n_frames) at sample 0 whose tail is carried by the handle instead of leaving from the registers -- under
 // which the same body (istft_run) is istft_run_kernel.  LiveSpan is RaggedSpan over the chunks of live streams: a span
 // that starts from a tail carried in memory and ends by writing the tail back (stftmask_live_kernel, istft_live_kernel).

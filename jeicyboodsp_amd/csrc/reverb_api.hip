@@ -130,39 +130,8 @@ int jdsp_reverb_batch(jdsp_reverb *h, const int16_t *pcm_host, long n_samples, c
     if (n_utts < 0 || n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_reverb_batch: n_utts or n_samples < 0");
     if (n_utts > 0 && (!sample_first_host || !block_first_host || !ir_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_reverb_batch: sample_first, block_first or ir is NULL");
-    jdsp::RaggedOffsets offs;                                  // a span of b blocks is b hops: n = hop
-    if (offs.check(ctx, "jdsp_reverb_batch", "block_first", sample_first_host, block_first_host, n_utts, n_samples,
-                   jdsp::kReverbBlock, jdsp::kReverbBlock))
-        return JDSP_EINVAL;
-    for (long u = 0; u < n_utts; u++) {
-        if (ir_host[u] < 0 || ir_host[u] >= h->n_irs)
-            return fail(ctx, JDSP_EINVAL, "jdsp_reverb_batch: an ir entry lies outside [0, n_irs)");
-        if (gain_host && !std::isfinite(gain_host[u]))
-            return fail(ctx, JDSP_EINVAL, "jdsp_reverb_batch: a gain is not finite");
-    }
-    const long n_total = offs.lay.n_total, end = offs.lay.end;
-    // what no launch writes is zero: everything outside the spans
-    if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
-    if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
-    if (n_total == 0 || (!out_i16_host && !out_f32_host)) return JDSP_OK;        // nothing to launch
-    if (!pcm_host) return fail(ctx, JDSP_EINVAL, "jdsp_reverb_batch: pcm is NULL");
-    JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = jdsp_reverb_batch_reserve(h, n_total, n_utts);
-    if (rc) return rc;
-    jdsp::HostCall hc(ctx, "jdsp_reverb_batch");
-    offs.upload(hc);
-    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));   // nothing past the last span is read
-    const int32_t *d_ir = hc.upload(ir_host, (size_t)n_utts * sizeof(int32_t));
-    const float *d_gain = gain_host ? hc.upload(gain_host, (size_t)n_utts * sizeof(float)) : nullptr;
-    int16_t *d_out = out_i16_host ? hc.alloc<int16_t>((size_t)end * sizeof(int16_t)) : nullptr;
-    float *d_f32 = out_f32_host ? hc.alloc<float>((size_t)end * sizeof(float)) : nullptr;
-    if (d_out) hc.zero(d_out, (size_t)end * sizeof(int16_t));
-    if (d_f32) hc.zero(d_f32, (size_t)end * sizeof(float));
-    if (hc.ok())
-        hc.result(jdsp_reverb_batch_dev(h, d_pcm, offs.d_sample, offs.d_unit, d_ir, d_gain, n_utts, n_total, d_out, d_f32));
-    hc.download(out_i16_host, d_out, d_out ? (size_t)end * sizeof(int16_t) : 0);
-    hc.download(out_f32_host, d_f32, d_f32 ? (size_t)end * sizeof(float) : 0);
-    return hc.finish();
+    return jdsp::reverb_host_call(h, "jdsp_reverb_batch", false, pcm_host, n_samples, nullptr, sample_first_host, block_first_host,
+                                  ir_host, gain_host, n_utts, out_i16_host, out_f32_host);
 }
 
 }  // extern "C"

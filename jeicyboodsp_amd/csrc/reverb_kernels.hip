@@ -7,79 +7,19 @@
 //   reverb_mac_kernel       a workgroup = G = 32 output blocks of ONE utterance (16 waves x 2): H[ir[u]] in LDS once,
 //                           each wave walks the rows its two blocks need from the newest down and stops at the
 //                           utterance's first row; Hermitian extension, pre-split, inverse wave FFT, scale, cast
-// The arithmetic is fastconv_upols4_kernel's, instruction for instruction (the complex helpers are inline assembly:
-// wave_fft512.h), so what a block comes out as depends on its index in the utterance, the partition count, the samples
-// and the response alone -- not on the wave, the workgroup or the utterance's place in the batch.  The pieces that
-// live inside fastconv_kernels.hip and stft_kernels.hip (the pre-split of a pair, the even-row split store) are
-// restated here: those modules compile to the same text as before (profiles/r29_reverb_batch_isa.txt).
-#include "frame_io.h"
-#include "reverb.h"
-#include "ragged_batch.h"
+// The block itself -- plan, analysis, walk and finish -- is reverb_body.h, the text the live streams run too
+// (reverb_live_kernels.hip).  Here: zeros as the lead, the response into LDS, the XCD remap, rows of the workspace alone.
+#include "reverb_body.h"
 
 namespace jdsp {
 
-constexpr int kRvPitch = kUpolsRowPitch;
-constexpr int kRvWaves = 16, kRvK = 2, kRvDepth = 2;
+constexpr int kRvWaves = 16;
 static_assert(kRvWaves * kRvK == kReverbGroup, "G sub-blocks per workgroup");
-constexpr int kRvPlanThreads = 1024;
 
-__device__ __forceinline__ long rv_wgs_of(const long long *block_first, long u)
-{
-    const long b = (long)(block_first[u + 1] - block_first[u]);
-    return b > 0 ? (b + kReverbGroup - 1) / kReverbGroup : 0;
-}
-
-// wg_first[u] = sum over v < u of ceil(B_v / G), wg_first[n_utts] = the workgroups that have work.  One workgroup:
-// thread t owns a run of consecutive utterances, the runs' sums are scanned in LDS.
 __global__ __launch_bounds__(kRvPlanThreads) void reverb_plan_kernel(const long long *__restrict__ block_first, long n_utts,
                                                                      long long *__restrict__ wg_first)
 {
-    __shared__ long long part[kRvPlanThreads];
-    const int t = threadIdx.x;
-    const long per = (n_utts + kRvPlanThreads - 1) / kRvPlanThreads;
-    const long a = t * per < n_utts ? t * per : n_utts, b = a + per < n_utts ? a + per : n_utts;
-    long long sum = 0;
-    for (long u = a; u < b; u++) sum += rv_wgs_of(block_first, u);
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kRvPlanThreads; d <<= 1) {
-        const long long v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long run = part[t] - sum;
-    for (long u = a; u < b; u++) {
-        wg_first[u] = run;
-        run += rv_wgs_of(block_first, u);
-    }
-    if (t == kRvPlanThreads - 1) wg_first[n_utts] = part[t];
-}
-
-// ---- analysis -----------------------------------------------------------------------------------------------------
-// stft_kernels.hip's even-row split store (split_store_half<false>): every row here is 16-byte aligned
-template <int J>
-__device__ __forceinline__ void rv_split_store_j(const float2 *lds, int lane, const float2 *w2, float2 *row)
-{
-    const int m = 128 * J + 2 * lane;
-    const float4 zz = *reinterpret_cast<const float4 *>(&lds[m]);
-    float2 zr0, zr1;
-    load_mirror_pair(lds, m, zr0, zr1);
-    float2 lo0, hi0, lo1, hi1;
-    split_fwd<J>(make_float2(zz.x, zz.y), zr0, w2[0], lo0, hi0);
-    split_fwd<J>(make_float2(zz.z, zz.w), zr1, w2[1], lo1, hi1);
-    *reinterpret_cast<float4 *>(row + m) = make_float4(lo0.x, lo0.y, lo1.x, lo1.y);      // read again soon: not streamed
-    if (J == 0 && lane == 0) row[512] = hi0;                                             // bin 512 = X[0 + 512]
-}
-
-constexpr int kRvRun = 4;      // consecutive blocks of the concatenated block axis per wave: every sample is read once
-                               // inside a run, the previous block a second time at a run's start
-
-__device__ __forceinline__ void rv_load_half(const short *pcm, long at, int lane, unsigned int (&h)[4])
-{
-    const unsigned int *p = reinterpret_cast<const unsigned int *>(pcm + at) + lane;     // at is even: sample_first is
-#pragma unroll
-    for (int q = 0; q < 4; q++) h[q] = p[64 * q];
+    reverb_plan<kReverbGroup>(block_first, n_utts, wg_first);
 }
 
 __global__ __launch_bounds__(64) void reverb_analysis_kernel(const short *__restrict__ pcm,
@@ -88,66 +28,10 @@ __global__ __launch_bounds__(64) void reverb_analysis_kernel(const short *__rest
                                                              long n_blocks, const float2 *__restrict__ table,
                                                              float2 *__restrict__ X)
 {
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
-    const int lane = threadIdx.x;
-    const long j0 = (long)blockIdx.x * kRvRun;
-    if (j0 >= n_blocks) return;
-    const long j1 = j0 + kRvRun < n_blocks ? j0 + kRvRun : n_blocks;
-    RaggedSpan<kReverbBlock> span(sample_first, block_first, n_utts);
-    span.begin(j0);
-    unsigned int prev[4], cur[4], nxt[4];
-    if (j0 > span.ub) rv_load_half(pcm, span.at(j0 - 1), lane, prev);
-    else {
+    reverb_analysis(pcm, sample_first, block_first, n_utts, n_blocks, table, X, [](long, unsigned int (&h)[4]) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) prev[q] = 0u;                        // silence in front of the utterance
-    }
-    rv_load_half(pcm, span.at(j0), lane, cur);
-    FrameTables t;
-    load_frame_tables(t, table, lane);
-    for (long j = j0; j < j1; j++) {
-        const bool last = span.last(j);
-        const bool more = j + 1 < j1;
-        if (more) {
-            if (last) span.next();                                       // block j + 1 exists: a non-empty utterance follows
-            rv_load_half(pcm, span.at(j + 1), lane, nxt);
-        }
-        float2 v[8];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
-            v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
-            v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
-        }
-        wave_fft512<false>(v, lds, lane, t.tw);
-        store_natural_image(lds, lane, v);
-        wave_lds_fence();
-        float2 *row = X + j * kRvPitch;
-        rv_split_store_j<0>(lds, lane, t.wsp, row);
-        rv_split_store_j<1>(lds, lane, t.wsp, row);
-        rv_split_store_j<2>(lds, lane, t.wsp, row);
-        rv_split_store_j<3>(lds, lane, t.wsp, row);
-        wave_lds_fence();
-        if (more) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                prev[q] = last ? 0u : cur[q];                            // a new utterance starts from silence
-                cur[q] = nxt[q];
-            }
-        }
-    }
-}
-
-// ---- multiply-accumulate and inverse --------------------------------------------------------------------------------
-template <int J>
-__device__ __forceinline__ void rv_presplit_j(const float2 *img, float2 *zout, int lane, const float2 *wsp)
-{
-    const int m = 128 * J + 2 * lane;
-    const float4 yy = *reinterpret_cast<const float4 *>(&img[m]);
-    float2 zr0, zr1;
-    load_mirror_pair(img, m, zr0, zr1);                              // Y[512 - m], Y[511 - m]
-    // Y[m + 512] = conj(Y[512 - m]): the output is real
-    zout[2 * J] = presplit_inv<J>(make_float2(yy.x, yy.y), make_float2(zr0.x, -zr0.y), wsp[0]);
-    zout[2 * J + 1] = presplit_inv<J>(make_float2(yy.z, yy.w), make_float2(zr1.x, -zr1.y), wsp[1]);
+        for (int q = 0; q < 4; q++) h[q] = 0u;                           // silence in front of the utterance
+    });
 }
 
 struct ReverbMacArgs {
@@ -194,13 +78,6 @@ __global__ __launch_bounds__(kRvWaves * 64) void reverb_mac_kernel(ReverbMacArgs
     const long c0 = (lw * kRvWaves + wave) * kRvK;
     if (c0 >= n_b) return;                                                    // no barrier follows
 
-    float2 acc[kRvK][8], acc512[kRvK];
-#pragma unroll
-    for (int k = 0; k < kRvK; k++) {
-        acc512[k] = make_float2(0.f, 0.f);
-#pragma unroll
-        for (int q = 0; q < 8; q++) acc[k][q] = make_float2(0.f, 0.f);
-    }
     const long r_top = c0 + (kRvK - 1);
     const float2 *X = a.X + ub * kRvPitch;                                    // the utterance's row 0
     auto row_of = [&](int q) {
@@ -208,83 +85,12 @@ __global__ __launch_bounds__(kRvWaves * 64) void reverb_mac_kernel(ReverbMacArgs
         r = r < 0 ? 0 : (r >= n_b ? n_b - 1 : r);                             // clamped rows feed no written output
         return X + r * kRvPitch;
     };
-    float4 xb[kRvDepth][4];
-    float2 xb512[kRvDepth];
-#pragma unroll
-    for (int d = 0; d < kRvDepth; d++) {
-        const float2 *xr = row_of(d);
-#pragma unroll
-        for (int j = 0; j < 4; j++) xb[d][j] = *reinterpret_cast<const float4 *>(xr + 128 * j + 2 * lane);
-        xb512[d] = xr[512];
-    }
     // rows in front of the utterance's first contribute nothing: the walk ends at row 0
     const int n_full = n_part + kRvK - 1;
     const int n_iter = r_top + 1 < n_full ? (int)(r_top + 1) : n_full;
-    for (int q0 = 0; q0 < n_iter; q0 += kRvDepth) {
-#pragma unroll
-        for (int d = 0; d < kRvDepth; d++) {
-            const int q = q0 + d;
-            if (q >= n_iter) break;                                          // wave-uniform
-#pragma unroll
-            for (int k = 0; k < kRvK; k++) {
-                const int p = q - (kRvK - 1) + k;                            // wave-uniform
-                if (p < 0 || p >= n_part) continue;
-                const float2 *hr = Hs + p * kRvPitch;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float4 h = *reinterpret_cast<const float4 *>(hr + 128 * j + 2 * lane);
-                    const float4 x = xb[d][j];
-                    acc[k][2 * j] = cadd(acc[k][2 * j], cmul(make_float2(x.x, x.y), make_float2(h.x, h.y)));
-                    acc[k][2 * j + 1] = cadd(acc[k][2 * j + 1], cmul(make_float2(x.z, x.w), make_float2(h.z, h.w)));
-                }
-                acc512[k] = cadd(acc512[k], cmul(xb512[d], hr[512]));
-            }
-            if (q + kRvDepth < n_iter) {                                     // refill this slot
-                const float2 *xr = row_of(q + kRvDepth);
-#pragma unroll
-                for (int j = 0; j < 4; j++) xb[d][j] = *reinterpret_cast<const float4 *>(xr + 128 * j + 2 * lane);
-                xb512[d] = xr[512];
-            }
-        }
-    }
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    const float2 wsp[2] = {table[kStftSplit + 2 * lane], table[kStftSplit + 2 * lane + 1]};
-#pragma unroll
-    for (int k = 0; k < kRvK; k++) {
-        const long c = c0 + k;
-        if (c >= n_b) break;
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            *reinterpret_cast<float4 *>(&lds[128 * j + 2 * lane]) =
-                make_float4(acc[k][2 * j].x, acc[k][2 * j].y, acc[k][2 * j + 1].x, acc[k][2 * j + 1].y);
-        if (lane == 0) lds[512] = acc512[k];
-        wave_lds_fence();
-        float2 z[8], y[8];
-        rv_presplit_j<0>(lds, z, lane, wsp);
-        rv_presplit_j<1>(lds, z, lane, wsp);
-        rv_presplit_j<2>(lds, z, lane, wsp);
-        rv_presplit_j<3>(lds, z, lane, wsp);
-        wave_lds_fence();
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            *reinterpret_cast<float4 *>(&lds[128 * j + 2 * lane]) = make_float4(z[2 * j].x, z[2 * j].y, z[2 * j + 1].x, z[2 * j + 1].y);
-        wave_lds_fence();
-#pragma unroll
-        for (int r = 0; r < 8; r++) y[r] = lds[lane + 64 * r];
-        wave_lds_fence();
-        wave_fft512<true>(y, lds, lane, tw);
-        wave_lds_fence();
-        // samples 512..1023 of the frame are the valid ones: y[4..7] hold the pairs 2 lane + 128 d
-        const long at = s0 + c * kReverbBlock;                               // even: dword and float2 stores are aligned
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const float2 v = make_float2(y[d + 4].x * scale, y[d + 4].y * scale);
-            if (a.out_i16)
-                __builtin_nontemporal_store(cast_i16x2_bits(v.x, v.y), reinterpret_cast<unsigned int *>(a.out_i16 + at) + lane + 64 * d);
-            if (a.out_f32) *reinterpret_cast<float2 *>(a.out_f32 + at + 2 * lane + 128 * d) = v;
-        }
-    }
+    float2 acc[kRvK][8], acc512[kRvK];
+    reverb_mac_walk(row_of, Hs, n_iter, n_part, lane, acc, acc512);
+    reverb_finish(acc, acc512, lds, lane, table, c0, n_b, s0, scale, a.out_i16, a.out_f32);
 }
 
 int launch_reverb_batch(hipStream_t st, const ReverbBatchArgs &a, const float2 *bank, int n_part, int n_irs,

@@ -21,7 +21,7 @@ static hipError_t live_zero(jdsp_reverb *h)
 }
 
 // the scalar checks both entries make before anything else
-static int live_counts(jdsp_reverb *h, const char *what, long n_chunks, long n_blocks_total)
+int jdsp::reverb_live_counts(jdsp_reverb *h, const char *what, long n_chunks, long n_blocks_total)
 {
     jdsp_ctx *ctx = h->ctx;
     int rc = live_open(h, what);
@@ -93,7 +93,7 @@ int jdsp_reverb_streams_dev(jdsp_reverb *h, const int16_t *pcm_dev, const int64_
 {
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
-    int rc = live_counts(h, "jdsp_reverb_streams_dev", n_chunks, n_blocks_total);
+    int rc = jdsp::reverb_live_counts(h, "jdsp_reverb_streams_dev", n_chunks, n_blocks_total);
     if (rc) return rc;
     if (!jdsp::aligned(pcm_dev, 16) || !jdsp::aligned(out_i16_dev, 16) || !jdsp::aligned(out_f32_dev, 8) ||
         !jdsp::aligned(stream_id_dev, 8) || !jdsp::aligned(sample_first_dev, 8) || !jdsp::aligned(block_first_dev, 8) ||
@@ -122,48 +122,15 @@ int jdsp_reverb_streams(jdsp_reverb *h, const int16_t *pcm_host, long n_samples,
     if (!h) return JDSP_EINVAL;
     jdsp_ctx *ctx = h->ctx;
     const char *me = "jdsp_reverb_streams";
-    int rc = live_counts(h, me, n_chunks, 0);
+    int rc = jdsp::reverb_live_counts(h, me, n_chunks, 0);
     if (rc) return rc;
     if (n_samples < 0) return fail(ctx, JDSP_EINVAL, "jdsp_reverb_streams: n_samples < 0");
     if (n_chunks > 0 && (!stream_id_host || !sample_first_host || !block_first_host || !ir_host))
         return fail(ctx, JDSP_EINVAL, "jdsp_reverb_streams: stream_id, sample_first, block_first or ir is NULL");
     const jdsp::StreamIdVerdict v = jdsp::stream_ids_check(stream_id_host, n_chunks, h->lws.n_streams);
     if (v != jdsp::StreamIdVerdict::kOk) return fail(ctx, JDSP_EINVAL, jdsp::stream_ids_message(v, me).c_str());
-    jdsp::RaggedOffsets offs;                                  // a span of b blocks is b hops: n = hop
-    if (offs.check(ctx, me, "block_first", sample_first_host, block_first_host, n_chunks, n_samples, jdsp::kReverbBlock,
-                   jdsp::kReverbBlock))
-        return JDSP_EINVAL;
-    for (long c = 0; c < n_chunks; c++) {
-        if (ir_host[c] < 0 || ir_host[c] >= h->n_irs)
-            return fail(ctx, JDSP_EINVAL, "jdsp_reverb_streams: an ir entry lies outside [0, n_irs)");
-        if (gain_host && !std::isfinite(gain_host[c]))
-            return fail(ctx, JDSP_EINVAL, "jdsp_reverb_streams: a gain is not finite");
-    }
-    const long n_total = offs.lay.n_total, end = offs.lay.end;
-    rc = live_counts(h, me, n_chunks, n_total);
-    if (rc) return rc;
-    // what no launch writes is zero: everything outside the spans
-    if (out_i16_host && n_samples) memset(out_i16_host, 0, (size_t)n_samples * sizeof(int16_t));
-    if (out_f32_host && n_samples) memset(out_f32_host, 0, (size_t)n_samples * sizeof(float));
-    if (n_total == 0) return JDSP_OK;                          // nothing to launch
-    if (!pcm_host) return fail(ctx, JDSP_EINVAL, "jdsp_reverb_streams: pcm is NULL");
-    JDSP_HIP(ctx, hipSetDevice(ctx->device));
-    jdsp::HostCall hc(ctx, me);
-    offs.upload(hc);
-    const int64_t *d_id = hc.upload(stream_id_host, (size_t)n_chunks * sizeof(int64_t));
-    const int16_t *d_pcm = hc.upload(pcm_host, (size_t)end * sizeof(int16_t));   // nothing past the last span is read
-    const int32_t *d_ir = hc.upload(ir_host, (size_t)n_chunks * sizeof(int32_t));
-    const float *d_gain = gain_host ? hc.upload(gain_host, (size_t)n_chunks * sizeof(float)) : nullptr;
-    int16_t *d_out = out_i16_host ? hc.alloc<int16_t>((size_t)end * sizeof(int16_t)) : nullptr;
-    float *d_f32 = out_f32_host ? hc.alloc<float>((size_t)end * sizeof(float)) : nullptr;
-    if (d_out) hc.zero(d_out, (size_t)end * sizeof(int16_t));
-    if (d_f32) hc.zero(d_f32, (size_t)end * sizeof(float));
-    if (hc.ok())
-        hc.result(jdsp_reverb_streams_dev(h, d_pcm, d_id, offs.d_sample, offs.d_unit, d_ir, d_gain, n_chunks, n_total, d_out,
-                                          d_f32));
-    hc.download(out_i16_host, d_out, d_out ? (size_t)end * sizeof(int16_t) : 0);
-    hc.download(out_f32_host, d_f32, d_f32 ? (size_t)end * sizeof(float) : 0);
-    return hc.finish();
+    return jdsp::reverb_host_call(h, me, true, pcm_host, n_samples, stream_id_host, sample_first_host, block_first_host, ir_host,
+                                  gain_host, n_chunks, out_i16_host, out_f32_host);
 }
 
 int jdsp_reverb_streams_state(jdsp_reverb *h, const int64_t *stream_id_host, long n_ids, int64_t *blocks_seen_host,

@@ -1,5 +1,6 @@
 // reverb_live_kernels.hip -- live reverberation streams (include/jdsp.h "live reverberation streams"): the batch's
-// arithmetic (reverb_kernels.hip) over chunks of streams whose history the handle carries as SPECTRA.
+// block (reverb_body.h, the text reverb_kernels.hip runs too) over chunks of streams whose history the handle carries
+// as SPECTRA.
 //   reverb_live_plan_kernel     block_first -> wave_first: ceil(B_c / 2) waves per chunk, prefixed (one workgroup)
 //   reverb_live_analysis_kernel one half-spectrum row per NEW block into the call's workspace: the 1024-point frame
 //                               [previous block | block]; in front of a chunk's first block stand the stream's carried
@@ -14,75 +15,21 @@
 // The commit is a launch of its own because the analysis and the multiply-accumulate READ exactly what it WRITES (the
 // carried samples, the ring, blocks_seen): stream order makes a delivery race-free, with nothing held twice and no
 // parity word.
-// Why the bytes are the batch's: per output block the operations are reverb_mac_kernel's, in its order -- the same
-// rows (a row is a function of its two blocks of samples alone), the same H rows, p ascending in one accumulator chain
-// from zero, the same finish.  The pieces are restated here, as reverb_kernels.hip restates the convolver's: that
-// module's kernels compile to the same text as before (profiles/r30_reverb_streams_isa.txt).
-#include "frame_io.h"
-#include "reverb.h"
-#include "ragged_batch.h"
+// Why the bytes are the batch's: per output block the operations are reverb_mac_kernel's, in its order, because they
+// are the same functions -- the same rows (a row is a function of its two blocks of samples alone), the same H rows, p
+// ascending in one accumulator chain from zero, the same finish.  Here: the carried samples as the lead, rows of the
+// workspace and then of the ring, the response read from the bank, the commit and the reset.
+#include "reverb_body.h"
 
 namespace jdsp {
 
-constexpr int kRlPitch = kUpolsRowPitch;
 constexpr int kRlWaves = 4;                // waves per workgroup of the multiply-accumulate: independent of each other
-constexpr int kRlK = 2, kRlDepth = 2;      // blocks per wave, rows in flight
-constexpr int kRlRun = 4;                  // consecutive blocks of the concatenated block axis per analysis wave
-constexpr int kRlPlanThreads = 1024;
 constexpr int kRlCommitThreads = 256;
 
-__device__ __forceinline__ long rl_waves_of(const long long *block_first, long c)
-{
-    const long b = (long)(block_first[c + 1] - block_first[c]);
-    return b > 0 ? (b + kRlK - 1) / kRlK : 0;
-}
-
-// wave_first[c] = sum over d < c of ceil(B_d / 2), wave_first[n_chunks] = the waves that have work
-__global__ __launch_bounds__(kRlPlanThreads) void reverb_live_plan_kernel(const long long *__restrict__ block_first,
+__global__ __launch_bounds__(kRvPlanThreads) void reverb_live_plan_kernel(const long long *__restrict__ block_first,
                                                                           long n_chunks, long long *__restrict__ wave_first)
 {
-    __shared__ long long part[kRlPlanThreads];
-    const int t = threadIdx.x;
-    const long per = (n_chunks + kRlPlanThreads - 1) / kRlPlanThreads;
-    const long a = t * per < n_chunks ? t * per : n_chunks, b = a + per < n_chunks ? a + per : n_chunks;
-    long long sum = 0;
-    for (long c = a; c < b; c++) sum += rl_waves_of(block_first, c);
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < kRlPlanThreads; d <<= 1) {
-        const long long v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    long long run = part[t] - sum;
-    for (long c = a; c < b; c++) {
-        wave_first[c] = run;
-        run += rl_waves_of(block_first, c);
-    }
-    if (t == kRlPlanThreads - 1) wave_first[n_chunks] = part[t];
-}
-
-// ---- analysis -----------------------------------------------------------------------------------------------------
-template <int J>
-__device__ __forceinline__ void rl_split_store_j(const float2 *lds, int lane, const float2 *w2, float2 *row)
-{
-    const int m = 128 * J + 2 * lane;
-    const float4 zz = *reinterpret_cast<const float4 *>(&lds[m]);
-    float2 zr0, zr1;
-    load_mirror_pair(lds, m, zr0, zr1);
-    float2 lo0, hi0, lo1, hi1;
-    split_fwd<J>(make_float2(zz.x, zz.y), zr0, w2[0], lo0, hi0);
-    split_fwd<J>(make_float2(zz.z, zz.w), zr1, w2[1], lo1, hi1);
-    *reinterpret_cast<float4 *>(row + m) = make_float4(lo0.x, lo0.y, lo1.x, lo1.y);
-    if (J == 0 && lane == 0) row[512] = hi0;
-}
-
-__device__ __forceinline__ void rl_load_half(const short *pcm, long at, int lane, unsigned int (&h)[4])
-{
-    const unsigned int *p = reinterpret_cast<const unsigned int *>(pcm + at) + lane;     // at is even
-#pragma unroll
-    for (int q = 0; q < 4; q++) h[q] = p[64 * q];
+    reverb_plan<kRvK>(block_first, n_chunks, wave_first);
 }
 
 // what stands in front of the first block of chunk c: the carried samples of its stream, zeros for a fresh one
@@ -90,7 +37,7 @@ __device__ __forceinline__ void rl_load_carried(const ReverbLive &lv, const long
                                                 unsigned int (&h)[4])
 {
     const long s = uniform_i64(stream_id + c);
-    if (uniform_i64(lv.seen + s) > 0) rl_load_half(lv.last, s * kReverbBlock, lane, h);
+    if (uniform_i64(lv.seen + s) > 0) rv_load_half(lv.last, s * kReverbBlock, lane, h);
     else {
 #pragma unroll
         for (int q = 0; q < 4; q++) h[q] = 0u;
@@ -104,64 +51,9 @@ __global__ __launch_bounds__(64) void reverb_live_analysis_kernel(const short *_
                                                                   long n_blocks, const float2 *__restrict__ table,
                                                                   ReverbLive lv)
 {
-    __shared__ __attribute__((aligned(16))) float2 lds[kWaveLdsComplex];
     const int lane = threadIdx.x;
-    const long j0 = (long)blockIdx.x * kRlRun;
-    if (j0 >= n_blocks) return;
-    const long j1 = j0 + kRlRun < n_blocks ? j0 + kRlRun : n_blocks;
-    RaggedSpan<kReverbBlock> span(sample_first, block_first, n_chunks);
-    span.begin(j0);
-    unsigned int prev[4], cur[4], nxt[4];
-    if (j0 > span.ub) rl_load_half(pcm, span.at(j0 - 1), lane, prev);
-    else rl_load_carried(lv, stream_id, span.u, lane, prev);
-    rl_load_half(pcm, span.at(j0), lane, cur);
-    FrameTables t;
-    load_frame_tables(t, table, lane);
-    for (long j = j0; j < j1; j++) {
-        const bool last = span.last(j);
-        const bool more = j + 1 < j1;
-        if (more) {
-            if (last) span.next();                                       // block j + 1 exists: a non-empty chunk follows
-            rl_load_half(pcm, span.at(j + 1), lane, nxt);
-        }
-        float2 v[8];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const float2 s0 = unpack_i16x2(prev[r]), s1 = unpack_i16x2(cur[r]);
-            v[r] = make_float2(s0.x * t.win[r].x, s0.y * t.win[r].y);
-            v[r + 4] = make_float2(s1.x * t.win[r + 4].x, s1.y * t.win[r + 4].y);
-        }
-        wave_fft512<false>(v, lds, lane, t.tw);
-        store_natural_image(lds, lane, v);
-        wave_lds_fence();
-        float2 *row = lv.X + j * kRlPitch;
-        rl_split_store_j<0>(lds, lane, t.wsp, row);
-        rl_split_store_j<1>(lds, lane, t.wsp, row);
-        rl_split_store_j<2>(lds, lane, t.wsp, row);
-        rl_split_store_j<3>(lds, lane, t.wsp, row);
-        wave_lds_fence();
-        if (more) {
-            if (last) rl_load_carried(lv, stream_id, span.u, lane, prev);  // the next chunk starts from its own stream
-            else {
-#pragma unroll
-                for (int q = 0; q < 4; q++) prev[q] = cur[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) cur[q] = nxt[q];
-        }
-    }
-}
-
-// ---- multiply-accumulate and inverse --------------------------------------------------------------------------------
-template <int J>
-__device__ __forceinline__ void rl_presplit_j(const float2 *img, float2 *zout, int lane, const float2 *wsp)
-{
-    const int m = 128 * J + 2 * lane;
-    const float4 yy = *reinterpret_cast<const float4 *>(&img[m]);
-    float2 zr0, zr1;
-    load_mirror_pair(img, m, zr0, zr1);                              // Y[512 - m], Y[511 - m]
-    zout[2 * J] = presplit_inv<J>(make_float2(yy.x, yy.y), make_float2(zr0.x, -zr0.y), wsp[0]);
-    zout[2 * J + 1] = presplit_inv<J>(make_float2(yy.z, yy.w), make_float2(zr1.x, -zr1.y), wsp[1]);
+    reverb_analysis(pcm, sample_first, block_first, n_chunks, n_blocks, table, lv.X,
+                    [&](long c, unsigned int (&h)[4]) { rl_load_carried(lv, stream_id, c, lane, h); });
 }
 
 struct ReverbLiveMacArgs {
@@ -177,9 +69,8 @@ struct ReverbLiveMacArgs {
 
 // Wave w of the plan belongs to the chunk c with wave_first[c] <= w < wave_first[c + 1] (the scalar binary search of
 // ragged_batch.h) and owns its blocks k0 = 2 (w - wave_first[c]) and k0 + 1, stream blocks i0 + k0 and i0 + k0 + 1 with
-// i0 = blocks_seen of the chunk's stream.  Output block i is sum_{p = 0}^{min(i, P - 1)} X[i - p] H_p, p ascending: the
-// wave reads the rows k0 + 1, k0, ... down to max(-i0, k0 + 1 - P) in the chunk's own numbering, two in flight, every
-// row feeding both blocks; row r >= 0 is row block_first[c] + r of the workspace, row r < 0 is stream block i0 + r in
+// i0 = blocks_seen of the chunk's stream.  The walk reads the rows k0 + 1, k0, ... down to max(-i0, k0 + 1 - P) in the
+// chunk's own numbering; row r >= 0 is row block_first[c] + r of the workspace, row r < 0 is stream block i0 + r in
 // the ring.  Waves past wave_first[n_chunks] exit: the grid is the bound the host knows without reading the offsets.
 __global__ __launch_bounds__(kRlWaves * 64) void reverb_live_mac_kernel(ReverbLiveMacArgs a, ReverbLive lv,
                                                                          const float2 *__restrict__ table)
@@ -190,7 +81,7 @@ __global__ __launch_bounds__(kRlWaves * 64) void reverb_live_mac_kernel(ReverbLi
     const long w = (long)blockIdx.x * kRlWaves + wave;
     if (w >= uniform_i64(a.wave_first + a.n_chunks)) return;
     const long c = ragged_find_utt(a.wave_first, a.n_chunks, w);
-    const long k0 = (w - uniform_i64(a.wave_first + c)) * kRlK;
+    const long k0 = (w - uniform_i64(a.wave_first + c)) * kRvK;
     const long cb = uniform_i64(a.block_first + c);
     const long n_b = uniform_i64(a.block_first + c + 1) - cb;                 // > 0: the chunk has waves, and k0 < n_b
     const long s0 = uniform_i64(a.sample_first + c);
@@ -201,104 +92,27 @@ __global__ __launch_bounds__(kRlWaves * 64) void reverb_live_mac_kernel(ReverbLi
     irc = irc < 0 ? 0 : (irc >= a.n_irs ? a.n_irs - 1 : irc);                 // never outside the bank
     const float g = a.gain ? a.gain[c] : 1.0f;
     const float scale = g * (1.0f / 1024.0f);                                 // the inverse's 1/1024 and the gain: one factor
-    const float2 *H = a.bank + (size_t)irc * n_part * kRlPitch;
+    const float2 *H = a.bank + (size_t)irc * n_part * kRvPitch;
 
-    float2 acc[kRlK][8], acc512[kRlK];
-#pragma unroll
-    for (int k = 0; k < kRlK; k++) {
-        acc512[k] = make_float2(0.f, 0.f);
-#pragma unroll
-        for (int q = 0; q < 8; q++) acc[k][q] = make_float2(0.f, 0.f);
-    }
-    const long r_top = k0 + (kRlK - 1);
+    const long r_top = k0 + (kRvK - 1);
     const int ring_n = n_part > 1 ? n_part - 1 : 1;
     const int m0 = (int)(i0 % ring_n);                                        // the slot stream block i0 will take
-    const float2 *X = lv.X + cb * kRlPitch;                                   // the chunk's row 0
-    const float2 *ring = lv.ring + (size_t)s * (n_part - 1) * kRlPitch;       // never read at P = 1
+    const float2 *X = lv.X + cb * kRvPitch;                                   // the chunk's row 0
+    const float2 *ring = lv.ring + (size_t)s * (n_part - 1) * kRvPitch;       // never read at P = 1
     auto row_of = [&](int q) {
         long r = r_top - q;
-        if (r >= 0) return X + (r >= n_b ? n_b - 1 : r) * kRlPitch;           // clamped rows feed no written output
+        if (r >= 0) return X + (r >= n_b ? n_b - 1 : r) * kRvPitch;           // clamped rows feed no written output
         r = r < -(long)ring_n ? -(long)ring_n : r;                            // -(P - 1) <= r: never taken (n_iter)
         const int slot = m0 + (int)r;                                         // (i0 + r) mod (P - 1)
-        return ring + (slot < 0 ? slot + ring_n : slot) * kRlPitch;
+        return ring + (slot < 0 ? slot + ring_n : slot) * kRvPitch;
     };
-    // rows in front of the stream's first contribute nothing: the walk ends at stream block 0
-    const int n_full = n_part + kRlK - 1;
+    // rows in front of the stream's first contribute nothing: the walk ends at stream block 0 (n_iter >= 2: the two
+    // rows it starts with are rows of the chunk)
+    const int n_full = n_part + kRvK - 1;
     const int n_iter = i0 + r_top + 1 < n_full ? (int)(i0 + r_top + 1) : n_full;
-    float4 xb[kRlDepth][4];
-    float2 xb512[kRlDepth];
-#pragma unroll
-    for (int d = 0; d < kRlDepth; d++) {
-        const float2 *xr = row_of(d);                                         // n_iter >= 2: both are rows of the chunk
-#pragma unroll
-        for (int j = 0; j < 4; j++) xb[d][j] = *reinterpret_cast<const float4 *>(xr + 128 * j + 2 * lane);
-        xb512[d] = xr[512];
-    }
-    for (int q0 = 0; q0 < n_iter; q0 += kRlDepth) {
-#pragma unroll
-        for (int d = 0; d < kRlDepth; d++) {
-            const int q = q0 + d;
-            if (q >= n_iter) break;                                          // wave-uniform
-#pragma unroll
-            for (int k = 0; k < kRlK; k++) {
-                const int p = q - (kRlK - 1) + k;                            // wave-uniform
-                if (p < 0 || p >= n_part) continue;
-                const float2 *hr = H + p * kRlPitch;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float4 h = *reinterpret_cast<const float4 *>(hr + 128 * j + 2 * lane);
-                    const float4 x = xb[d][j];
-                    acc[k][2 * j] = cadd(acc[k][2 * j], cmul(make_float2(x.x, x.y), make_float2(h.x, h.y)));
-                    acc[k][2 * j + 1] = cadd(acc[k][2 * j + 1], cmul(make_float2(x.z, x.w), make_float2(h.z, h.w)));
-                }
-                acc512[k] = cadd(acc512[k], cmul(xb512[d], hr[512]));
-            }
-            if (q + kRlDepth < n_iter) {                                     // refill this slot
-                const float2 *xr = row_of(q + kRlDepth);
-#pragma unroll
-                for (int j = 0; j < 4; j++) xb[d][j] = *reinterpret_cast<const float4 *>(xr + 128 * j + 2 * lane);
-                xb512[d] = xr[512];
-            }
-        }
-    }
-    WaveTwiddles tw;
-    load_wave_twiddles(tw, table, lane);
-    const float2 wsp[2] = {table[kStftSplit + 2 * lane], table[kStftSplit + 2 * lane + 1]};
-#pragma unroll
-    for (int k = 0; k < kRlK; k++) {
-        const long b = k0 + k;
-        if (b >= n_b) break;
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            *reinterpret_cast<float4 *>(&lds[128 * j + 2 * lane]) =
-                make_float4(acc[k][2 * j].x, acc[k][2 * j].y, acc[k][2 * j + 1].x, acc[k][2 * j + 1].y);
-        if (lane == 0) lds[512] = acc512[k];
-        wave_lds_fence();
-        float2 z[8], y[8];
-        rl_presplit_j<0>(lds, z, lane, wsp);
-        rl_presplit_j<1>(lds, z, lane, wsp);
-        rl_presplit_j<2>(lds, z, lane, wsp);
-        rl_presplit_j<3>(lds, z, lane, wsp);
-        wave_lds_fence();
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            *reinterpret_cast<float4 *>(&lds[128 * j + 2 * lane]) = make_float4(z[2 * j].x, z[2 * j].y, z[2 * j + 1].x, z[2 * j + 1].y);
-        wave_lds_fence();
-#pragma unroll
-        for (int r = 0; r < 8; r++) y[r] = lds[lane + 64 * r];
-        wave_lds_fence();
-        wave_fft512<true>(y, lds, lane, tw);
-        wave_lds_fence();
-        // samples 512..1023 of the frame are the valid ones: y[4..7] hold the pairs 2 lane + 128 d
-        const long at = s0 + b * kReverbBlock;                               // even: dword and float2 stores are aligned
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const float2 v = make_float2(y[d + 4].x * scale, y[d + 4].y * scale);
-            if (a.out_i16)
-                __builtin_nontemporal_store(cast_i16x2_bits(v.x, v.y), reinterpret_cast<unsigned int *>(a.out_i16 + at) + lane + 64 * d);
-            if (a.out_f32) *reinterpret_cast<float2 *>(a.out_f32 + at + 2 * lane + 128 * d) = v;
-        }
-    }
+    float2 acc[kRvK][8], acc512[kRvK];
+    reverb_mac_walk(row_of, H, n_iter, n_part, lane, acc, acc512);
+    reverb_finish(acc, acc512, lds, lane, table, k0, n_b, s0, scale, a.out_i16, a.out_f32);
 }
 
 // ---- commit -----------------------------------------------------------------------------------------------------------
@@ -317,11 +131,11 @@ __global__ __launch_bounds__(kRlCommitThreads) void reverb_live_commit_kernel(co
     const long i0 = lv.seen[s];
     const int ring_n = n_part - 1;
     const long n_rows = n_b < ring_n ? n_b : ring_n;
-    float4 *ring = reinterpret_cast<float4 *>(lv.ring + (size_t)s * ring_n * kRlPitch);
+    float4 *ring = reinterpret_cast<float4 *>(lv.ring + (size_t)s * ring_n * kRvPitch);
     for (long k = n_b - n_rows; k < n_b; k++) {
-        const float4 *src = reinterpret_cast<const float4 *>(lv.X + (cb + k) * kRlPitch);
-        float4 *dst = ring + ((i0 + k) % ring_n) * (kRlPitch / 2);
-        for (int i = threadIdx.x; i < kRlPitch / 2; i += kRlCommitThreads) dst[i] = src[i];
+        const float4 *src = reinterpret_cast<const float4 *>(lv.X + (cb + k) * kRvPitch);
+        float4 *dst = ring + ((i0 + k) % ring_n) * (kRvPitch / 2);
+        for (int i = threadIdx.x; i < kRvPitch / 2; i += kRlCommitThreads) dst[i] = src[i];
     }
     {
         const unsigned int *src = reinterpret_cast<const unsigned int *>(pcm + sample_first[c] + (n_b - 1) * kReverbBlock);
@@ -346,11 +160,11 @@ int launch_reverb_live(hipStream_t st, const ReverbLiveArgs &a, const float2 *ba
                        const float2 *rect_table, const ReverbLive &lv, long long *wave_first)
 {
     if (a.n_chunks <= 0 || a.n_blocks_total <= 0) return 0;
-    const long runs = (a.n_blocks_total + kRlRun - 1) / kRlRun;
+    const long runs = (a.n_blocks_total + kRvRun - 1) / kRvRun;
     hipLaunchKernelGGL(reverb_live_analysis_kernel, dim3((unsigned)runs), dim3(64), 0, st, a.pcm, a.stream_id, a.sample_first,
                        a.block_first, a.n_chunks, a.n_blocks_total, rect_table, lv);
     if (a.out_i16 || a.out_f32) {                                             // with no output only the state advances
-        hipLaunchKernelGGL(reverb_live_plan_kernel, dim3(1), dim3(kRlPlanThreads), 0, st, a.block_first, a.n_chunks, wave_first);
+        hipLaunchKernelGGL(reverb_live_plan_kernel, dim3(1), dim3(kRvPlanThreads), 0, st, a.block_first, a.n_chunks, wave_first);
         // sum_c ceil(B_c / 2) <= (n_blocks_total + n_chunks) / 2
         const long waves = (a.n_blocks_total + a.n_chunks + 1) / 2;
         ReverbLiveMacArgs m = {bank, wave_first, a.stream_id, a.block_first, a.sample_first, a.ir, a.gain, a.n_chunks,

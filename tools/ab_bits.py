@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Bit comparison of builds of libjdsp.so on the overlap-add, denoise and n-microphone MVDR chains (GPU box only):
+"""Bit comparison of builds of libjdsp.so on the overlap-add, denoise, n-microphone MVDR and reverberation chains (GPU
+box only):
     python tools/ab_bits.py build/variants/parent.so jeicyboodsp_amd/libjdsp.so ...
 Every library runs in a fresh child process (JDSP_LIB) over the same seeded inputs and prints one SHA-256 per case over
 the raw bytes of every output: int16, the float32 before the cast, the flushed tail and the recompute count where the
@@ -391,6 +392,38 @@ def mvdrn(eng):
     yield batch("gaps, chan_stride + 64", utts, K.delays_of(3), K.LOADING, gaps=2 * np.arange(len(utts)), wider=64)
 
 
+def reverb(eng):
+    """The reverberator, batch and live, on the device entries.  Batch: every bank of tests/reverb_cases.banks() over
+    its batch (plan_of: utterances of 0, 1, 2, P - 1 .. P + 2, G - 1, G, G + 1 and 2 G + 1 blocks), spans apart by gaps_of.
+    Streams: all streams of tests/reverb_streams_cases of the bank side by side, the constant ones under one cut pattern
+    per case (the switched ones keep their own cuts), then the state of every stream."""
+    import numpy as np
+    import torch
+    import reverb_cases as K
+    import reverb_streams_cases as S
+    for name, taps in K.banks().items():
+        rv = eng.reverb(taps)
+        plan = K.plan_of(rv.n_part, rv.n_irs)
+        xs = [K.utterance(fam, nb, i) for i, (fam, nb, _, _) in enumerate(plan)]
+        pcm, first, block_first = K.pack(xs, K.gaps_of(len(xs)), fill=32767)
+        outs = rv.process_batch(torch.from_numpy(pcm).cuda(), first, block_first, [p[2] for p in plan], [p[3] for p in plan],
+                                want_f32=True)
+        yield "reverb_batch %s, P %d x %d utterances" % (name, rv.n_part, len(xs)), digest(*outs)
+        strs = S.streams(name)
+        rv.open_streams(len(strs), sum(s.x.size // S.B for s in strs))
+        for pattern in S.PATTERNS:
+            rv.reset_streams()
+            outs = []
+            for t, chunks in enumerate(S.deliveries(strs, rv.n_part, [pattern] * len(strs), len(pattern))):
+                pcm, first, counts = S.pack_call(strs, chunks, K.gaps_of(len(chunks)), tail=2 * (t % 3))
+                outs += [x.clone() for x in rv.process_streams(torch.from_numpy(pcm).cuda(), [c.stream for c in chunks], counts,
+                                                               [c.ir for c in chunks], [c.gain for c in chunks], first,
+                                                               want_f32=True)]
+            outs += list(rv.streams_state(np.arange(len(strs))))
+            yield "reverb_streams %s, P %d x %d streams, %s" % (name, rv.n_part, len(strs), pattern), digest(*outs)
+        rv.close()
+
+
 def child():
     import jeicyboodsp_amd
     eng = jeicyboodsp_amd.Engine(0)
@@ -413,7 +446,7 @@ def child():
         print("%s\t%.1f" % (c["name"], statistics.median(t[5:])))
         d.close()
     else:
-        for chain in (synthesis, masking, batches, streams, denoise, mvdrn):
+        for chain in (synthesis, masking, batches, streams, denoise, mvdrn, reverb):
             for name, sha in chain(eng):
                 print("%s\t%s" % (name, sha), flush=True)
     eng.close()
